@@ -22,6 +22,18 @@ RAM ops/s).  `--mode replicas` = N independent 2^18 RAMs, no collective (opt-in)
 
 `--workload ep` = BASELINE.json configs[1]: one GLWE x GGSW external product (latency) and a
 batch-256 launch (throughput).
+
+A plain run sets up, warms up, times the `--steps` steps and prints the result line.  Everything else
+(the per-op split, the back-to-back pass, the kernel-timing pass and its rooflines, the host hand-over
+pass, the weak-scaling reference, the README-block leg, the CPU baselines and the in-run parity check
+against the oracle) runs only with `--full`.
+
+`--dump-outputs DIR` writes what the timed path returned in its last timed step as float64 .npy files
+(exact: every limb is an int32 on the device): `read.npy` and `read_prepare_write.npy` (the word_size
+GLWEs a caller of read / read_prepare_write receives) and `rows_after_write.npy` (the RAM's rows after
+the last write; this rank's rows when sharded).  Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of
+the rows is written instead, with its row indices in `rows_after_write_index.npy`.  The inputs depend on
+the arguments alone, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -259,6 +271,28 @@ def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a, dtype=np.int64).tobytes()).hexdigest()
 
 
+DUMP_LIMIT_BYTES = 64_000_000   # --dump-outputs: at most this much in all
+OP_NAMES = ("read", "read_prepare_write", "write")     # the three calls of a step, in order
+
+
+def dump_outputs(path, results, rows):
+    """--dump-outputs: `results` = {name: [word_size][GLWE] int64} returned by the last timed step's reads, `rows` = [word_size][rows][GLWE]
+    int64 after its write.  float64 .npy files (exact: the limbs are int32 on the device); if everything would exceed DUMP_LIMIT_BYTES,
+    a fixed seeded sample of the rows (the same rows of every sub-RAM) and their indices."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in results.items()}
+    room = DUMP_LIMIT_BYTES - sum(a.nbytes for a in arrays.values()) - 4096 * (len(arrays) + 2)    # (.npy headers)
+    if rows.nbytes <= room:
+        arrays["rows_after_write"] = rows.astype(np.float64)
+    else:
+        k = max(1, room // (rows.shape[0] * rows.shape[2] * 8 + 8))
+        idx = np.sort(np.random.default_rng(2718).choice(rows.shape[1], size=k, replace=False))
+        arrays["rows_after_write"] = rows[:, idx].astype(np.float64)
+        arrays["rows_after_write_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def host_cpu():
     try:
         return open("/proc/cpuinfo").read().split("model name")[1].split("\n")[0].strip(": \t")
@@ -332,7 +366,7 @@ def bench_ep(pkg, args):
                                                  "frac": (cus * 2 * GLWE_I64 + GGSW_I64) / thr_ms / 1e6 / HBM_PEAK_GBS,
                                                  "algorithmic_bytes_single_product": ep_bytes}},
            "device": ram.device_info()}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         flags = oracle_native()                    # the CPU leg is built for the host it runs on, as the main baseline's is
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import pyoracle as po
@@ -372,18 +406,26 @@ def bench_group(args):
     ops = (lambda: grp.read(addr, keys, download=False), lambda: grp.read_prepare_write(addr, keys, download=False),
            lambda: grp.write(None, addr, keys))
 
-    def step():
+    got = {}     # --dump-outputs: what the last timed step's reads returned, and the time taken to fetch it (kept out of `elapsed`)
+
+    def step(keep=False):
         ts = []
-        for fn in ops:
+        for name, fn in zip(OP_NAMES, ops):
             a = time.perf_counter()
             fn()                               # group ops are synchronous: complete on every shard when they return
             ts.append((time.perf_counter() - a) * 1e3)
+            if keep and name != "write":
+                a = time.perf_counter()
+                got[name] = grp.result()
+                got["fetch_s"] = got.get("fetch_s", 0.0) + time.perf_counter() - a
         return ts
     for _ in range(args.warmup):
         step()
     t0 = time.perf_counter()
-    per_op = np.array([step() for _ in range(args.steps)])
-    elapsed = time.perf_counter() - t0
+    per_op = np.array([step(args.dump_outputs is not None and s == args.steps - 1) for s in range(args.steps)])
+    elapsed = time.perf_counter() - t0 - got.pop("fetch_s", 0.0)
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, got, grp.store_encrypted())
     read_ms, rpw_ms, write_ms = per_op.mean(axis=0)
     weight = 1 if strong else n
     log_entries = int(np.log2(max_addr))
@@ -433,7 +475,15 @@ def main():
     ap.add_argument("--no-kernel-timing", action="store_true", help="do not bracket kernels with HIP events")
     ap.add_argument("--no-boundary", action="store_true", help="skip the pass that includes the host hand-over")
     ap.add_argument("--no-readme-leg", action="store_true", help="skip the short pass on the README parameter block (reference_published)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the per-op split, the back-to-back and kernel-timing passes "
+                         "(rooflines), the host hand-over pass, the weak-scaling reference, the README-block leg, the CPU baselines and "
+                         "the in-run parity check (the --no-* options above thin this out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (read, read_prepare_write, rows after the write) to DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.workload == "ep":
+        ap.error("--dump-outputs: the ep workload returns no arrays")
 
     if args.mode == "group":
         return bench_group(args)
@@ -527,25 +577,36 @@ def main():
         step()
     barrier()
     # the timed region: the three calls of a step, the host waiting for each op before it makes the next call (one round trip
-    # per op, as the reference's synchronous calls have) — and nothing else: the per-op split comes from a pass of its own
+    # per op, as the reference's synchronous calls have) — and nothing else: the per-op split comes from a pass of its own.
+    # --dump-outputs: in the last step the host fetches each read's result after the op has completed (what a downloading
+    # caller receives; the root holds it when sharded), off the clock.
+    got, fetch_s = {}, 0.0
+    keep_step = args.steps - 1 if (args.dump_outputs is not None and rank == 0) else -1
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        for fn in ops:
+    for s in range(args.steps):
+        for name, fn in zip(OP_NAMES, ops):
             fn()
             ram.sync()
+            if s == keep_step and name != "write":
+                a = time.perf_counter()
+                got[name] = ram.result()
+                fetch_s += time.perf_counter() - a
     barrier()
-    elapsed = time.perf_counter() - t0
-    tp0 = time.perf_counter()
-    per_op = [step() for _ in range(args.steps)]       # the same K steps with one HIP-event pair per op on the context's stream
-    barrier()
-    per_op_elapsed = time.perf_counter() - tp0
+    elapsed = time.perf_counter() - t0      # (fetch_s is taken off below, once the ranks have agreed on both)
+    if keep_step >= 0:
+        dump_outputs(args.dump_outputs, got, ram.store_encrypted())
+    if args.full:
+        tp0 = time.perf_counter()
+        per_op = [step() for _ in range(args.steps)]       # the same K steps with one HIP-event pair per op on the context's stream
+        barrier()
+        per_op_elapsed = time.perf_counter() - tp0
     tail = ram.tail_stats()       # single-launch trace chains so far (warm-up + timed steps) and how many fell back
     mid = ram.mid_stats() if hasattr(ram, "mid_stats") else {"launches": 0, "fallbacks": 0}
     # For information only (never `value`): the same K steps enqueued back to back — with a NULL result pointer the ABI's
     # ops return as soon as they are enqueued — and ONE synchronisation at the end, i.e. without the host's round trip
     # between ops that the synchronous calls of the reference interface imply.
     pipelined = None
-    if not sharded:
+    if args.full and not sharded:
         barrier()
         tp = time.perf_counter()
         for _ in range(args.steps):
@@ -558,7 +619,7 @@ def main():
     # ~20 % to a step, so they are kept OUT of the timed region above.
     instr_elapsed = None
     light = None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         # first the dominant kernel alone: ONE event pair around each chain launch (8 records per step instead of ~200),
         # everything else enqueued as in the timed region — its step time is reported beside the timed one
         ram.profile_reset()
@@ -580,7 +641,7 @@ def main():
     # The same ops through the boundary's HOST buffers (int64 result out, int64 words in): host wall clock
     # per call.  Never part of `value`.
     boundary = None
-    if not args.no_boundary and not sharded:
+    if args.full and not args.no_boundary and not sharded:
         bt = []
         res_buf = np.zeros((ws, p.glwe_len()), dtype=np.int64)      # the caller's result buffer, reused (as a host loop would)
         for _ in range(max(5, min(args.steps, 20))):
@@ -596,15 +657,16 @@ def main():
         ram.stage_words(words)
     if dist is not None:
         import torch
-        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.dist_backend == "nccl" else "cpu")
+        t = torch.tensor([elapsed, fetch_s], dtype=torch.float64, device="cuda" if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
+        elapsed, fetch_s = (float(x) for x in t.tolist())
+    elapsed -= fetch_s       # the other ranks waited in their collectives while the root fetched
 
     # Weak scaling of ONE sharded RAM: the reference point is the same op on an unsharded RAM of the per-GPU size, measured HERE,
     # on rank 0's GPU, in this run (the other ranks wait): weak_scaling_efficiency = T(1) / T(N).  `value` stays the raw ops/s
     # of the RAM that was actually operated (whose size grows with N).
     weak_ref = None
-    if sharded and not strong and world > 1:
+    if args.full and sharded and not strong and world > 1:
         if rank == 0:
             r1 = pkg.Ram.new_from_ram_params(ws, [3, 3, 3, 3], 1 << args.log_max_addr, device=local_rank, **crypto)
             p1 = r1.params
@@ -634,8 +696,9 @@ def main():
             dist.destroy_process_group()
         return
 
-    per_op = np.array(per_op)              # [steps][3] ms, HIP events on the context's stream
-    read_ms, rpw_ms, write_ms = per_op.mean(axis=0)
+    if args.full:
+        per_op = np.array(per_op)              # [steps][3] ms, HIP events on the context's stream
+        read_ms, rpw_ms, write_ms = per_op.mean(axis=0)
     ms_per_step = elapsed * 1e3 / args.steps
     n_rams = 1 if mode != "replicas" else world
     raw_ops_per_s = n_rams * 2 * args.steps / elapsed
@@ -655,7 +718,7 @@ def main():
     out = {
         "metric": f"encrypted RAM read ops/s + write ops/s at 2^{args.log_max_addr} entries; achieved HBM GB/s vs peak",
         "value": raw_ops_per_s,
-        "value_incl_boundary": None,     # filled below: the same steps with the result handed to the host (what the reference's calls return)
+        **({"value_incl_boundary": None} if args.full else {}),     # filled below: the same steps with the result handed to the host (what the reference's calls return)
         "unit": "RAM ops/s (1 read + 1 write[=rpw+write] per step)" + (
             f" of the ONE 2^{log_entries}-entry RAM sharded over the {world} GPUs (weak scaling: 2^{args.log_max_addr} entries per GPU; "
             f"value(N) / value(1) = T(1) / T(N) is the weak-scaling efficiency)" if weight > 1 else ""),
@@ -673,45 +736,47 @@ def main():
         "ops_weighted_by_ram_size": (None if weight == 1 else
                                      {"value": raw_ops_per_s * weight,
                                       "what": f"information only: an op on the {world}*2^{args.log_max_addr}-entry RAM counted as {world} ops of the 2^{args.log_max_addr}-entry metric"}),
-        "weak_scaling_efficiency": (None if weak_ref is None else
-                                    {"value": weak_ref / ms_per_step, "t1_ms_per_step": weak_ref, "tN_ms_per_step": ms_per_step,
-                                     "what": f"T(1) / T(N): the same step on an unsharded 2^{args.log_max_addr}-entry RAM, measured in this run on rank 0's GPU, "
-                                             f"over the step on the 2^{log_entries}-entry RAM sharded over {world} GPUs"}),
-        "read_ops_s": n_rams * 1e3 / read_ms, "write_ops_s": n_rams * 1e3 / (rpw_ms + write_ms),
-        "read_ms": read_ms, "read_prepare_write_ms": rpw_ms, "write_ms": write_ms,
-        "per_op_split": {"what": "read_ms / read_prepare_write_ms / write_ms: a pass of the same K steps with one HIP-event pair per op "
-                                 "on the context's stream (kept out of the timed region)", "ms_per_step": per_op_elapsed * 1e3 / args.steps},
-        "ops_enqueued_back_to_back": (None if pipelined is None else
-                                      {"ram_ops_s": n_rams * 2 * args.steps / pipelined, "ms_per_step": pipelined * 1e3 / args.steps,
-                                       "note": "information only: K steps enqueued without waiting for each op (NULL result pointer), one "
-                                               "synchronisation at the end; `value` keeps one host round trip per op, as the reference's calls have"}),
-        "algorithmic_GBs_per_op": {"read": a_read / read_ms / 1e6, "read_prepare_write": a_rpw / rpw_ms / 1e6,
-                                   "write": a_write / write_ms / 1e6},
-        "reference_published": None,     # filled below: the published numbers against THIS run's times on the published block
+        **({"weak_scaling_efficiency": (None if weak_ref is None else
+                                        {"value": weak_ref / ms_per_step, "t1_ms_per_step": weak_ref, "tN_ms_per_step": ms_per_step,
+                                         "what": f"T(1) / T(N): the same step on an unsharded 2^{args.log_max_addr}-entry RAM, measured in this run on rank 0's GPU, "
+                                                 f"over the step on the 2^{log_entries}-entry RAM sharded over {world} GPUs"}),
+            "read_ops_s": n_rams * 1e3 / read_ms, "write_ops_s": n_rams * 1e3 / (rpw_ms + write_ms),
+            "read_ms": read_ms, "read_prepare_write_ms": rpw_ms, "write_ms": write_ms,
+            "per_op_split": {"what": "read_ms / read_prepare_write_ms / write_ms: a pass of the same K steps with one HIP-event pair per op "
+                                     "on the context's stream (kept out of the timed region)", "ms_per_step": per_op_elapsed * 1e3 / args.steps},
+            "ops_enqueued_back_to_back": (None if pipelined is None else
+                                          {"ram_ops_s": n_rams * 2 * args.steps / pipelined, "ms_per_step": pipelined * 1e3 / args.steps,
+                                           "note": "information only: K steps enqueued without waiting for each op (NULL result pointer), one "
+                                                   "synchronisation at the end; `value` keeps one host round trip per op, as the reference's calls have"}),
+            "algorithmic_GBs_per_op": {"read": a_read / read_ms / 1e6, "read_prepare_write": a_rpw / rpw_ms / 1e6,
+                                       "write": a_write / write_ms / 1e6},
+            "reference_published": None,     # filled below: the published numbers against THIS run's times on the published block
+            } if args.full else {}),     # --full: the figures of the passes beyond the timed one
         "trace_tail": dict(tail, note="trace chains at the end of a read run as one launch with in-kernel hand-offs; `fallbacks` of them "
                                       "gave up (CUs not available side by side) and were redone by the fused launch behind them"),
         "device": ram.device_info(),
     }
-    # The reference's only published numbers (README.md:36: 450 ms read / 1200 ms write, i9-12900K single thread, 2^18 entries) were
-    # taken with the README parameter block (5-limb trace keys), not with the source constants `value` is measured on: the ratios
-    # are quoted for the block they belong to — this run's own times when it IS that block, else a short leg on that block.
-    pub = {"read_ms": 450, "write_ms": 1200, "hw": "i9-12900K single thread (README.md:36), 2^18 entries, README.md:17-27 parameter block"}
-    leg = None
-    if crypto:
-        leg = {"read_ms": float(read_ms), "read_prepare_write_ms": float(rpw_ms), "write_ms": float(write_ms), "ms_per_step": ms_per_step,
-               "ram_ops_s": raw_ops_per_s, "steps": args.steps}
-    elif mode == "single" and not args.no_readme_leg and args.log_max_addr == 18:
-        leg = readme_leg(pkg, ws, args.log_max_addr, local_rank, max(5, min(args.steps, 20)), 5)
-    if leg is not None:
-        pub.update({"measured_on_the_same_block": leg,
-                    "speedup_read": 450.0 / leg["read_ms"], "speedup_write": 1200.0 / leg["write_ms"],
-                    "speedup_rpw_plus_write": (450.0 + 1200.0) / (leg["read_prepare_write_ms"] + leg["write_ms"]),
-                    "note": "like for like: the README block on this GPU" + ("" if crypto else " (a short leg of this run on a context of its own; `value` stays the source constants)")
-                            + "; call for call as the example times them (examples/fhe-ram.rs:98-154); Ram::write here resumes from what "
-                              "read_prepare_write kept, so speedup_rpw_plus_write (a read_prepare_write priced as a published read) is the fairer write figure"})
-    else:
-        pub["note"] = "not measured in this run (the published numbers belong to the README block at 2^18: run --params readme)"
-    out["reference_published"] = pub
+    if args.full:
+        # The reference's only published numbers (README.md:36: 450 ms read / 1200 ms write, i9-12900K single thread, 2^18 entries) were
+        # taken with the README parameter block (5-limb trace keys), not with the source constants `value` is measured on: the ratios
+        # are quoted for the block they belong to — this run's own times when it IS that block, else a short leg on that block.
+        pub = {"read_ms": 450, "write_ms": 1200, "hw": "i9-12900K single thread (README.md:36), 2^18 entries, README.md:17-27 parameter block"}
+        leg = None
+        if crypto:
+            leg = {"read_ms": float(read_ms), "read_prepare_write_ms": float(rpw_ms), "write_ms": float(write_ms), "ms_per_step": ms_per_step,
+                   "ram_ops_s": raw_ops_per_s, "steps": args.steps}
+        elif mode == "single" and not args.no_readme_leg and args.log_max_addr == 18:
+            leg = readme_leg(pkg, ws, args.log_max_addr, local_rank, max(5, min(args.steps, 20)), 5)
+        if leg is not None:
+            pub.update({"measured_on_the_same_block": leg,
+                        "speedup_read": 450.0 / leg["read_ms"], "speedup_write": 1200.0 / leg["write_ms"],
+                        "speedup_rpw_plus_write": (450.0 + 1200.0) / (leg["read_prepare_write_ms"] + leg["write_ms"]),
+                        "note": "like for like: the README block on this GPU" + ("" if crypto else " (a short leg of this run on a context of its own; `value` stays the source constants)")
+                                + "; call for call as the example times them (examples/fhe-ram.rs:98-154); Ram::write here resumes from what "
+                                  "read_prepare_write kept, so speedup_rpw_plus_write (a read_prepare_write priced as a published read) is the fairer write figure"})
+        else:
+            pub["note"] = "not measured in this run (the published numbers belong to the README block at 2^18: run --params readme)"
+        out["reference_published"] = pub
     out["roundoff_max"] = {"value": ram.roundoff_max(), "limit": 0.375,
                            "what": "largest |x - rint(x)| any rounding of an inverse transform has seen on the timed context (fheram_roundoff_max): the FFT64 "
                                    "arithmetic is exact while it stays below 1/2; above 3/8 every call returns FHERAM_ERR_PRECISION"}
@@ -730,7 +795,7 @@ def main():
                                 "`value` stays the device-resident figure the bench contract prescribes, value_incl_boundary is the same steps "
                                 "with the hand-over inside")
 
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         names = ("keyswitch", "keyswitch_fused", "keyswitch_chain_launch", "keyswitch_tail_launch", "keyswitch_mid_launch", "ext_product",
                  "ext_product_fused", "ext_product_mid_launch", "prepare", "elementwise", "read_chain_launch", "write_chain_launch")
         classes = {k: ram.profile_get(k) for k in names}
@@ -896,7 +961,7 @@ def main():
         out["forms"] = forms
 
     parity_failed = False
-    if not args.no_cpu_baseline and world == 1 and mode == "single":   # reported baseline: rank 0 at N = 1 only
+    if args.full and not args.no_cpu_baseline and world == 1 and mode == "single":   # reported baseline: rank 0 at N = 1 only
         # bounded sample (~10 s of CPU work at 2^18): the whole RAM, one step; beyond 2^18 one of the `ws` sub-RAMs, scaled by
         # ws (the reference processes them one after the other, ram.rs:187-190; prepare_inv is shared, <1 % of a write)
         flags = oracle_native()

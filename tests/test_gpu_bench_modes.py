@@ -28,6 +28,44 @@ def test_bench_external_product_mode():
     assert out["roofline"]["bound"] == "valu_fp64" and 0.0 < out["roofline"]["frac"] < 1.0 and 0.0 < out["roofline_hbm"]["frac"] < 1.0
 
 
+def test_bench_plain_run_dumps_the_last_step(tmp_path, po):
+    """A plain run (no --full) prints the headline line only; --dump-outputs writes what its last timed step returned, the same
+    from run to run, and equal to the oracle driven through the same warm-up + timed steps on the same inputs."""
+    import numpy as np
+    import bench
+    from _pkg import load_package
+    log_max_addr, ws, warmup, steps = 13, 4, 1, 2
+    names = ("read", "read_prepare_write", "rows_after_write")
+    dumps = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log-max-addr", str(log_max_addr), "--steps", str(steps),
+                            "--warmup", str(warmup), "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        out = last_json(r.stdout)
+        assert out["steps"] == steps and out["value"] > 0 and out["ms_per_step"] > 0 and out["higher_is_better"] is True
+        assert out["dtype"] == "f64" and out["unit"].startswith("RAM ops/s")
+        assert not any(k in out for k in ("read_ms", "roofline", "cpu_baseline", "parity_in_run", "reference_published"))
+        assert sorted(os.listdir(tmp_path / run)) == sorted(n + ".npy" for n in names)
+        dumps.append({n: np.load(tmp_path / run / (n + ".npy")) for n in names})
+    for n in names:
+        assert dumps[0][n].dtype == np.float64 and np.array_equal(dumps[0][n], dumps[1][n]), n
+
+    p = load_package().Parameters(max_addr=1 << log_max_addr, word_size=ws)
+    inp = bench.make_inputs(p, ws, 4, p.base2d().as_1d().size(), p.rows())
+    o = po.Oracle(po.OParams(max_addr=1 << log_max_addr, word_size=ws))
+    keys = o.keys_prepare({"gal_els": np.array([int(po.lib().fo_galois_element(12, i)) for i in range(12)], dtype=np.int64),
+                           "atk_glwe": inp["atk"], "atk_ggsw_inv": inp["atk_inv"], "tsk": inp["tsk"]})
+    addr = o.address_new(inp["addr"])
+    ram = o.ram_new()
+    ram.load(inp["rows"])
+    for _ in range(warmup + steps):
+        want = {"read": ram.read(addr, keys), "read_prepare_write": ram.read_prepare_write(addr, keys)}
+        ram.write(inp["words"], addr, keys)
+    want["rows_after_write"] = ram.store()
+    for n in names:
+        assert dumps[0][n].shape == want[n].shape and np.array_equal(dumps[0][n], want[n].astype(np.float64)), n
+
+
 def test_bench_sharded_one_rank_rccl_device_buffers():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",

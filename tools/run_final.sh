@@ -3,7 +3,7 @@
 source tools/gpu_steps.sh
 export O=gpurun_out/r6z; mkdir -p $O
 step 900 pytest_all.log python -m pytest tests -q -x -m gpu
-step 300 bench_default.json python bench.py
+step 300 bench_default.json python bench.py --full
 step 200 soak_ops.txt python tests/soak_gpu.py 120
 step 300 soak_flow.txt python tests/soak_flow_gpu.py 200
 step 100 soak_tail.txt python tests/soak_tail_gpu.py 60

@@ -54,10 +54,10 @@ PY
       tests/scale_digest_worker.py --mode ranks --log-max-addr $LOG --dist-backend $BACKEND $EXTRA > $out/rd_$n.json 2> $out/rd_$n.err; rd=$?
   PORT=$((PORT + 1))
   if [ $n -eq 1 ]; then
-    python bench.py --gpus 1 --log-max-addr $LOG --steps $STEPS --warmup $WARM --no-cpu-baseline > $out/rb_$n.json 2> $out/rb_$n.err; rb=$?
+    python bench.py --full --gpus 1 --log-max-addr $LOG --steps $STEPS --warmup $WARM --no-cpu-baseline > $out/rb_$n.json 2> $out/rb_$n.err; rb=$?
   else
     python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $PORT \
-        bench.py --gpus $n --total-log-max-addr $LOG --steps $STEPS --warmup $WARM --dist-backend $BACKEND $EXTRA > $out/rb_$n.json 2> $out/rb_$n.err; rb=$?
+        bench.py --full --gpus $n --total-log-max-addr $LOG --steps $STEPS --warmup $WARM --dist-backend $BACKEND $EXTRA > $out/rb_$n.json 2> $out/rb_$n.err; rb=$?
   fi
   python - "$out/rb_$n.json" $n ranks $rd $rb $BACKEND $LOG <<'PY'
 import json, sys
