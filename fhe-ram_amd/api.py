@@ -25,6 +25,7 @@ _LIB = None
 
 I64P = C.POINTER(C.c_int64)
 
+READ_BATCH_MAX = 8   # FHERAM_READ_BATCH_MAX (include/fheram.h)
 STATUS = {0: "OK", 1: "INVALID_ARG", 2: "STATE", 3: "UNINITIALIZED", 4: "KEYS", 5: "UNSUPPORTED", 6: "RANGE", 7: "DEVICE", 8: "PRECISION"}
 
 
@@ -77,6 +78,7 @@ _SYMBOLS = [
     ("fheram_address_create", C.c_int, [C.c_void_p, C.POINTER(I64P), C.c_int, C.POINTER(C.c_void_p)]),
     ("fheram_address_destroy", None, [C.c_void_p]),
     ("fheram_read", C.c_int, [C.c_void_p, C.c_void_p, I64P]),
+    ("fheram_read_batch", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, I64P]),
     ("fheram_read_prepare_write", C.c_int, [C.c_void_p, C.c_void_p, I64P]),
     ("fheram_write", C.c_int, [C.c_void_p, I64P, C.c_int, C.c_void_p]),
     ("fheram_word_stage", C.c_int, [C.c_void_p, I64P, C.c_int]),
@@ -709,6 +711,28 @@ class Ram:
         elif download:
             self._check_out(out)
         self._chk(library().fheram_read(self._h, address._device(self), _p(out) if download else None))
+        return out if download else None
+
+    def read_batch(self, addresses, keys: EvaluationKeysPrepared, download: bool = True, out=None):  # ram.rs:172, K times
+        """K = len(addresses) independent reads of this RAM as one operation (fheram_read_batch): int64 [K][word_size][GLWE],
+        slice i equal to read(addresses[i]).  1 <= K <= READ_BATCH_MAX; duplicates are allowed.  out: an int64 array of that
+        shape to receive the results (reused like read's)."""
+        addresses = list(addresses)
+        if not 1 <= len(addresses) <= READ_BATCH_MAX:
+            raise FheRamError(1, f"read_batch takes 1 to {READ_BATCH_MAX} addresses, got {len(addresses)}")
+        if not all(isinstance(a, Address) for a in addresses):
+            raise FheRamError(1, "read_batch: every entry must be an Address")
+        self._use_keys(keys)
+        p = self.params
+        k = len(addresses)
+        if download and out is None:
+            out = np.zeros((k, p.word_size(), p.glwe_len()), dtype=np.int64)
+        elif download:
+            if not (isinstance(out, np.ndarray) and out.dtype == np.int64 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]
+                    and out.size == k * p.word_size() * p.glwe_len()):
+                raise FheRamError(1, f"out must be a writeable C-contiguous int64 array of {k} x {p.word_size()} x {p.glwe_len()} elements")
+        arr = (C.c_void_p * k)(*[a._device(self) for a in addresses])
+        self._chk(library().fheram_read_batch(self._h, arr, k, _p(out) if download else None))
         return out if download else None
 
     def read_prepare_write(self, address: Address, keys: EvaluationKeysPrepared, download: bool = True, out=None):  # ram.rs:196

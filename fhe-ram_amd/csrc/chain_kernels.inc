@@ -1,5 +1,8 @@
-// Included TWICE by kernels.hpp (no include guard): the chain kernels that exist in two register budgets.
+// Included by kernels.hpp (no include guard): the chain kernels that exist in two register budgets.
 //   FK_KS_CHAIN_NAME / FK_READ_CHAIN_NAME : kernel names;  FK_VG : the literal for amdgpu_num_vgpr (units of two registers)
+//   FK_READ_CHAIN_ARGS / FK_READ_CHAIN_BATCH : RowChainArgs / 0, or RowChainBatchArgs / 1 for the read chain of fheram_read_batch
+//   (those two inclusions define no FK_KS_CHAIN_NAME: the trace chain has no batch form)
+#ifdef FK_KS_CHAIN_NAME
 // GLWE::trace(start, start + n) as ONE launch (see KsChainArgs in kernels.hpp)
 template <int SX, int SK, int SO, int YF = 0>   // YF: 0 int32 limbs between the steps (ks_run); 3 the intermediates as Y = ceil(A/2) with the closed-form normalisation, handed over through LDS and registers (ks_trace_l)
 __global__ __launch_bounds__(T, T / 256) __attribute__((amdgpu_num_vgpr(FK_VG))) void FK_KS_CHAIN_NAME(KsChainArgs ca) {
@@ -46,9 +49,10 @@ __global__ __launch_bounds__(T, T / 256) __attribute__((amdgpu_num_vgpr(FK_VG)))
         ka.rot_base = 0;
     }
 }
+#endif
 // read / read_prepare_write: a row's products of coordinate 0 + its alone packer levels as ONE launch (see RowChainArgs in kernels.hpp)
 template <int SK, int SG>
-__global__ __launch_bounds__(T, T / 256) __attribute__((amdgpu_num_vgpr(FK_VG))) void FK_READ_CHAIN_NAME(RowChainArgs ra) {
+__global__ __launch_bounds__(T, T / 256) __attribute__((amdgpu_num_vgpr(FK_VG))) void FK_READ_CHAIN_NAME(FK_READ_CHAIN_ARGS ra) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     if (ra.ks.pred) {   // the fallback launch behind k_trace_tail's products + trace chain: runs only if that launch gave up
         if (__hip_atomic_load(ra.ks.pred, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ra.ks.pred_seq) return;
@@ -63,17 +67,28 @@ __global__ __launch_bounds__(T, T / 256) __attribute__((amdgpu_num_vgpr(FK_VG)))
     for (int k = 0; k < E; k++) vc[k] = 0.0;
     {
         GlweRef in = ra.ep.src;
+#if FK_READ_CHAIN_BATCH
+        // the source row y mod src_rows and the prepared digits of address y / ws: recomputed where they are used (a few scalar
+        // instructions) rather than kept live across the steps, at this kernel's scalar register pressure
+#define FK_RC_OPND(i) (ra.ep.ggsw[i] + batch_opnd_offset(ra))
+#define FK_RC_SRC(a) batch_src_row(a, ra)
+#else
+#define FK_RC_OPND(i) ra.ep.ggsw[i]
+#define FK_RC_SRC(a) a
+#endif
 #pragma unroll 1
         for (int i = 0; i < ra.ep.n; i++) {      // n >= 2
             const GlweRef out = ra.ep.buf[i & 1];
             int tid = vt((int)threadIdx.x);
             asm volatile("" : "+v"(tid));   // see k_ext_product_chain
             __builtin_assume(tid >= 0 && tid < T);
-            if (i == 0) ep_step_r<SG, 0, 1>(in, out, ra.ep.ggsw[i], ra.ep.tw, lds, true, tid, vc);
-            else if (i + 1 < ra.ep.n) ep_step_r<SG, 1, 1>(in, out, ra.ep.ggsw[i], ra.ep.tw, lds, false, tid, vc);
-            else ep_step_r<SG, 1, 3>(in, out, ra.ep.ggsw[i], ra.ep.tw, lds, false, tid, vc, false, ra.store_ep != 0);
+            if (i == 0) ep_step_r<SG, 0, 1>(FK_RC_SRC(in), out, FK_RC_OPND(i), ra.ep.tw, lds, true, tid, vc);
+            else if (i + 1 < ra.ep.n) ep_step_r<SG, 1, 1>(in, out, FK_RC_OPND(i), ra.ep.tw, lds, false, tid, vc);
+            else ep_step_r<SG, 1, 3>(in, out, FK_RC_OPND(i), ra.ep.tw, lds, false, tid, vc, false, ra.store_ep != 0);
             in = out;
         }
+#undef FK_RC_OPND
+#undef FK_RC_SRC
     }
     KsArgs ka = ra.ks.base;
 #pragma unroll 1

@@ -161,6 +161,18 @@ struct fheram_ctx {
     int32_t* d_last_res = nullptr; // where the last read / read_prepare_write left its result (d_res or d_trtop)
     bool tree_rotate_pending = false;
     int32_t* d_trhi = nullptr;     // arena that holds trace(ct_hi) of the local rows during a write (A or C)
+    // fheram_read_batch (path.hpp read_batch_impl): buffers for batch_cap addresses, allocated on first use and grown to the largest
+    // batch seen.  Ciphertext y = k * ws + w of a batch is word w of address k; the arenas keep the rows' stride (sy = rows * GLWE).
+    int batch_cap = 0;
+    int32_t* d_bA = nullptr;       // [K*ws][rows]  ping-pong arenas of the batch's rows
+    int32_t* d_bB = nullptr;       // [K*ws][rows]
+    int32_t* d_bC = nullptr;       // [K*ws][rows]  stands in for the source a single-launch chain must leave intact (pack_levels); only when needed
+    int32_t* d_bres = nullptr;     // [K*ws]        the results
+    int32_t* d_btmp = nullptr;     // [K*ws]
+    int32_t* d_btmp2 = nullptr;    // [K*ws]
+    double* d_bprep = nullptr;     // [K][n_digits] prepared GGSW: address k's digits
+    int64_t* h_bres = nullptr;     // pinned, device-visible: the results as int64 (+ the monitor's maximum), as h_res
+    int64_t* d_h_bres = nullptr;
     int32_t* h_pin[2] = {nullptr, nullptr};   // pinned host staging (hand-over of int64 host buffers)
     hipEvent_t ev_pin[2] = {nullptr, nullptr};
     // the two hand-overs ON the path (result of a read out, words of a write in) have staging of their own:

@@ -186,6 +186,8 @@ int fheram_ctx_create_cfg(const fheram_params* p, int device, int shard, int n_s
     LDSATTR((&k_pair_z<4>)); LDSATTR((&k_pair_z<5>));
     LDSATTR((&k_read_chain<4, 4>)); LDSATTR((&k_read_chain<5, 4>)); LDSATTR((&k_write_chain<4, 4>)); LDSATTR((&k_write_chain<5, 4>));
     LDSATTR((&k_read_chain_w<4, 4>)); LDSATTR((&k_read_chain_w<5, 4>));
+    LDSATTR((&k_read_chain_b<4, 4>)); LDSATTR((&k_read_chain_b<5, 4>)); LDSATTR((&k_read_chain_bw<4, 4>)); LDSATTR((&k_read_chain_bw<5, 4>));
+    LDSATTR((&k_trace_tail_b<3, 4, 3>)); LDSATTR((&k_trace_tail_b<3, 5, 3>));
     LDSATTR((&k_keyswitch_chain_w<3, 4, 3, 3>)); LDSATTR((&k_keyswitch_chain_w<3, 5, 3, 3>));
     LDSATTR((&k_keyswitch_chain<3, 4, 3>));
     LDSATTR((&k_keyswitch_chain<3, 4, 3, 3>));
@@ -285,6 +287,7 @@ void fheram_ctx_destroy(fheram_ctx* c) {
     if (c->stream) hipStreamSynchronize(c->stream);
     if (c->stream2) hipStreamSynchronize(c->stream2);
     prof_collect(c);
+    batch_free(c);
     if (c->ev_fork) hipEventDestroy(c->ev_fork);
     if (c->ev_join) hipEventDestroy(c->ev_join);
     for (int i = 0; i < 2; i++) if (c->ev_inv[i]) hipEventDestroy(c->ev_inv[i]);
@@ -479,6 +482,34 @@ int fheram_read(fheram_ctx* c, const fheram_addr* addr, int64_t* out) {
     if (rc != FHERAM_OK) return rc;
     HIPCHK(c, hipGetLastError());
     return out ? fheram_result_download(c, out) : FHERAM_OK;
+}
+// K independent Ram::read (ram.rs:172-191) as one operation (path.hpp read_batch_impl)
+int fheram_read_batch(fheram_ctx* c, const fheram_addr* const* addrs, int n_addr, int64_t* out) {
+    if (!c) return FHERAM_ERR_INVALID_ARG;
+    if (!addrs) return fail(c, FHERAM_ERR_INVALID_ARG, "null address list");
+    if (n_addr < 1 || n_addr > FHERAM_READ_BATCH_MAX)
+        return fail(c, FHERAM_ERR_INVALID_ARG, "n_addr = " + std::to_string(n_addr) + " is outside [1, FHERAM_READ_BATCH_MAX = " + std::to_string(FHERAM_READ_BATCH_MAX) + "]");
+    for (int k = 0; k < n_addr; k++) {   // every address is checked before anything is enqueued
+        const int rc = check_common(c, addrs[k]);
+        if (rc != FHERAM_OK) return rc;
+    }
+    if (c->n_shards != 1) return fail(c, FHERAM_ERR_INVALID_ARG, "row-sharded context: use fheram_read_partial / fheram_read_finish");
+    if (c->state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.read: internal state is true -> requires calling Memory.write");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if (n_addr == 1) {
+        rc = run_op(c, addrs[0], 0, [&] { return read_impl(c, addrs[0], false); });
+        if (rc != FHERAM_OK) return rc;
+        HIPCHK(c, hipGetLastError());
+        return out ? fheram_result_download(c, out) : FHERAM_OK;
+    }
+    // (never captured: a batch's launch sequence depends on K addresses, and a read's state bookkeeping is done as it is enqueued)
+    rc = batch_reserve(c, n_addr);
+    if (rc != FHERAM_OK) return rc;
+    rc = read_batch_impl(c, addrs, n_addr);
+    if (rc != FHERAM_OK) return rc;
+    HIPCHK(c, hipGetLastError());
+    return out ? read_batch_download(c, n_addr, out) : FHERAM_OK;
 }
 int fheram_read_prepare_write(fheram_ctx* c, const fheram_addr* addr, int64_t* out) {
     int rc = check_common(c, addr);

@@ -276,7 +276,10 @@ void fill_row_chain(fheram_ctx* c, RowChainArgs& ra, const double* prep, int d, 
 }
 // read / read_prepare_write: d products of `src` with the prepared digits, then trace steps 0 .. n_tr-1 (the alone packer levels);
 // the result lands in dst; ep_store != nullptr: the products' result is also written there (in-place products of read_prepare_write)
-void launch_read_chain(fheram_ctx* c, GlweRef src, const GlweRef* ep_store, GlweRef dst, const double* prep, int d, int n_tr, int gx, int gy) {
+// bws > 0 (fheram_read_batch): gy = K * bws ciphertexts of K addresses; row y reads src at y mod bws and the digits of address y / bws,
+// which are opnd_stride elements apart from prep on (k_read_chain_b / _bw)
+void launch_read_chain(fheram_ctx* c, GlweRef src, const GlweRef* ep_store, GlweRef dst, const double* prep, int d, int n_tr, int gx, int gy,
+                       int bws = 0, long opnd_stride = 0) {
     ProfScope ps(c, "read_chain_launch", (uint64_t)gx * gy, 1);
     RowChainArgs ra;
     fill_row_chain(c, ra, prep, d, 0, n_tr);
@@ -286,6 +289,21 @@ void launch_read_chain(fheram_ctx* c, GlweRef src, const GlweRef* ep_store, Glwe
     ra.ks.base = ks_args(c, dst, dst, dst, trace_key(c, 0), c->gal[0]);
     ra.ks.buf[0] = ra.ks.buf[1] = dst;                            // only the last step stores
     ra.hi = dst; ra.trhi = dst;
+    if (bws > 0) {
+        RowChainBatchArgs rb;
+        static_cast<RowChainArgs&>(rb) = ra;
+        rb.opnd_stride = opnd_stride; rb.ws = bws; rb.src_rows = bws;
+        const bool w = c->wide;
+        if (w) c->wide_unsynced = true;
+        if (c->s_evk == 5) {
+            if (w) hipLaunchKernelGGL((k_read_chain_bw<5, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
+            else hipLaunchKernelGGL((k_read_chain_b<5, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
+        } else {
+            if (w) hipLaunchKernelGGL((k_read_chain_bw<4, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
+            else hipLaunchKernelGGL((k_read_chain_b<4, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
+        }
+        return;
+    }
     if (c->s_evk == 5) {
         if (c->wide) { c->wide_unsynced = true; hipLaunchKernelGGL((k_read_chain_w<5, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ra); }
         else hipLaunchKernelGGL((k_read_chain<5, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ra);
@@ -319,8 +337,11 @@ bool use_tail(const fheram_ctx* c, int n, int gx, int gy) {
 // prep != nullptr (round 6): the d external products with the prepared digits at `prep` run in front of the trace chain in the SAME launch
 // (coordinate 1's products, ram.rs:454 / 525-527): src -> products -> ep_out -> trace -> b[(n - 1) & 1]; store_ep: the caller needs ep_out
 // afterwards (read_prepare_write's tree[0]).  The fallback launch is then the fused row chain (k_read_chain), predicated likewise.
+// bws > 0 (fheram_read_batch, with prep): ciphertext y belongs to address y / bws, whose digits are opnd_stride elements apart from prep on
+// (k_trace_tail_b, and k_read_chain_b as its fallback)
 void launch_trace_tail(fheram_ctx* c, GlweRef src, const GlweRef (&b)[2], int start, int n, int gx, int gy,
-                       const double* prep = nullptr, int d = 0, GlweRef ep_out = GlweRef{nullptr, 0, 0}, bool store_ep = false) {
+                       const double* prep = nullptr, int d = 0, GlweRef ep_out = GlweRef{nullptr, 0, 0}, bool store_ep = false,
+                       int bws = 0, long opnd_stride = 0) {
     ProfScope ps(c, "keyswitch", (uint64_t)gx * gy, n);
     ProfScope pt(c, "keyswitch_tail_launch", (uint64_t)gx * gy * n, 1);
     TailArgs ta;
@@ -349,6 +370,22 @@ void launch_trace_tail(fheram_ctx* c, GlweRef src, const GlweRef (&b)[2], int st
         ra.ks.buf[0] = ra.ks.buf[1] = b[(n - 1) & 1];      // only the last step stores
         ra.hi = ra.trhi = b[(n - 1) & 1];
         ra.ks.pred = ca.pred; ra.ks.pred_seq = ca.pred_seq; ra.ks.host_count = ca.host_count;
+    }
+    if (bws > 0 && ta.n_ep) {
+        TailBatchArgs tb;
+        static_cast<TailArgs&>(tb) = ta;
+        tb.opnd_stride = opnd_stride; tb.ws = bws;
+        RowChainBatchArgs rb;
+        static_cast<RowChainArgs&>(rb) = ra;
+        rb.opnd_stride = opnd_stride; rb.ws = bws; rb.src_rows = gx * gy;   // the source is the batch's own: row y is y
+        if (c->s_evk == 5) {
+            hipLaunchKernelGGL((k_trace_tail_b<3, 5, 3>), dim3(TAIL_GROUPS * 2 * 5 * 3), dim3(T), LDS_BYTES, c->cur, tb);
+            hipLaunchKernelGGL((k_read_chain_b<5, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
+        } else {
+            hipLaunchKernelGGL((k_trace_tail_b<3, 4, 3>), dim3(TAIL_GROUPS * 2 * 4 * 3), dim3(T), LDS_BYTES, c->cur, tb);
+            hipLaunchKernelGGL((k_read_chain_b<4, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
+        }
+        return;
     }
     if (c->s_evk == 5) {
         hipLaunchKernelGGL((k_trace_tail<3, 5, 3>), dim3(TAIL_GROUPS * 2 * 5 * 3), dim3(T), LDS_BYTES, c->cur, ta);

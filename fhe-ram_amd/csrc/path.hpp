@@ -189,6 +189,120 @@ int read_impl(fheram_ctx* c, const fheram_addr* addr, bool prepare_write) {
     return rc;
 }
 
+// ---- fheram_read_batch: K Ram::read (ram.rs:172-191) of the same RAM as one launch sequence ---------------------------------------
+// A read does not change the RAM (SubRam::read asserts !state and only writes its scratch, ram.rs:393-396): K reads at K addresses
+// share the rows, the keys and every packing and trace step; only the products with the address digits differ.  The batch runs on
+// arenas of its own, [K * ws][rows] GLWEs with the rows' stride, so that ciphertext y = k * ws + w is word w of address k and every
+// address-independent step is ONE launch over gy = K * ws.
+void batch_free(fheram_ctx* c) {
+    void* bufs[] = {c->d_bA, c->d_bB, c->d_bC, c->d_bres, c->d_btmp, c->d_btmp2, c->d_bprep};
+    for (void* b : bufs) if (b) hipFree(b);
+    if (c->h_bres) hipHostFree(c->h_bres);
+    c->d_bA = c->d_bB = c->d_bC = c->d_bres = c->d_btmp = c->d_btmp2 = nullptr;
+    c->d_bprep = nullptr;
+    c->h_bres = c->d_h_bres = nullptr;
+    c->batch_cap = 0;
+}
+// The third arena is only needed where the alone packer levels run as the single-launch tail chain on the batch's rows (at most
+// TAIL_GROUPS ciphertexts: 2^13 with K * ws <= 4), whose source must survive the launch (pack_levels P0): allocated only then.
+bool batch_needs_third(const fheram_ctx* c, int K) {
+    if (c->n2 != 2) return false;
+    const int R = (int)c->rows, Y = K * c->ws, L0 = LOGN - ilog2_ceil(c->rows_glob);
+    return !use_row_fuse(c, (int)c->base2d[0].size(), L0, R, Y) && L0 > 0 && use_tail(c, L0, R, Y);
+}
+// grows the batch buffers to K addresses (and adds the third arena when this batch needs it); on failure the context holds none of
+// them (and single reads are unaffected)
+int batch_reserve(fheram_ctx* c, int K) {
+    const bool third = batch_needs_third(c, K);
+    if (K <= c->batch_cap && (!third || c->d_bC)) return FHERAM_OK;
+    if (K < c->batch_cap) K = c->batch_cap;   // (only the third arena is missing: keep the capacity)
+    if (c->batch_cap) { HIPCHK(c, hipStreamSynchronize(c->stream)); batch_free(c); }
+    const size_t G = fheram_ctx::GLWE, nct = (size_t)K * c->ws, nrow = nct * c->rows;
+    hipError_t e = hipSuccess;
+    auto dev = [&](auto** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc((void**)p, bytes); };
+    dev(&c->d_bA, nrow * G * sizeof(int32_t));
+    dev(&c->d_bB, nrow * G * sizeof(int32_t));
+    if (third) dev(&c->d_bC, nrow * G * sizeof(int32_t));
+    dev(&c->d_bres, nct * G * sizeof(int32_t));
+    dev(&c->d_btmp, nct * G * sizeof(int32_t));
+    dev(&c->d_btmp2, nct * G * sizeof(int32_t));
+    dev(&c->d_bprep, (size_t)K * c->n_digits * fheram_ctx::GGSW * sizeof(double));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_bres, (nct * G + 1) * sizeof(int64_t), hipHostMallocMapped);   // + the monitor's maximum
+    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&c->d_h_bres, c->h_bres, 0);
+    if (e != hipSuccess) {
+        batch_free(c);
+        (void)hipGetLastError();   // the next op's error check must not see this allocation's failure
+        return fail(c, FHERAM_ERR_DEVICE, std::string("read batch buffers for ") + std::to_string(K) + " addresses: " + hipGetErrorString(e));
+    }
+    c->batch_cap = K;
+    return FHERAM_OK;
+}
+// Products with address-dependent digits use the operand table (y / ws -> address) in the forms that carry one: the fused row chain
+// (k_read_chain_b) and the tail with products (k_trace_tail_b, fallback k_read_chain_b); every other form runs one launch per address
+// on its own y-slice with the single-read launchers.  The result of address k is at d_bres + k * ws GLWEs.
+int read_batch_impl(fheram_ctx* c, const fheram_addr* const* addrs, int K) {
+    c->wide = true;   // (Ram::read: never beside the gate wave)
+    const long G = (long)fheram_ctx::GLWE;
+    const long sy = (long)c->rows * G;
+    const int ws = c->ws, R = (int)c->rows, Y = K * ws;
+    const long ostride = (long)c->n_digits * (long)fheram_ctx::GGSW;              // one address's prepared digits
+    for (int k = 0; k < K; k++)                                                       // ram.rs:416-419, every address
+        launch_prepare(c, addrs[k]->d_ggsw, c->d_bprep + k * ostride, c->n_digits * (int)(fheram_ctx::GGSW / N));
+    auto bprep = [&](int k, int ci) { return c->d_bprep + k * ostride + (long)coord_first_digit(c, ci) * (long)fheram_ctx::GGSW; };
+    auto slice = [&](GlweRef r, int k) { r.p += (long)k * ws * r.sy; return r; };  // address k's ws ciphertexts
+    GlweRef tmp = ref(c->d_btmp, G, 0), ep_out = ref(c->d_btmp2, G, 0), res = ref(c->d_bres, G, 0);
+    const int d0 = (int)c->base2d[0].size();
+    if (c->n2 == 1) {                                                                 // rows == 1: res <- trace(products of the row)
+        GlweRef row0 = ref(c->d_data, sy, 0);
+        for (int k = 0; k < K; k++) ep_chain(c, row0, slice(ep_out, k), slice(tmp, k), bprep(k, 0), d0, 1, ws);   // ram.rs:451
+        trace_steps(c, ep_out, res, tmp, 0, LOGN, 1, Y);                                                      // ram.rs:457
+    } else {
+        GlweRef data = ref(c->d_data, sy, G), A = ref(c->d_bA, sy, G), B = ref(c->d_bB, sy, G);
+        const int L0 = LOGN - ilog2_ceil(c->rows_glob);
+        int32_t* packed;
+        if (use_row_fuse(c, d0, L0, R, Y)) {
+            launch_read_chain(c, data, nullptr, A, bprep(0, 0), d0, L0, R, Y, ws, ostride);                  // ram.rs:429-435, every address
+            packed = pack_levels(c, c->d_bA, c->d_bA, c->d_bB, sy, G, (size_t)R, Y, 0, L0);   // ram.rs:435-448 (no alone levels left: no third arena)
+        } else {
+            for (int k = 0; k < K; k++) ep_chain(c, data, slice(A, k), slice(B, k), bprep(k, 0), d0, R, ws);   // ram.rs:429-434
+            packed = pack_levels(c, c->d_bA, c->d_bA, c->d_bB, sy, G, (size_t)R, Y, L0, L0, false, c->d_bC);   // (d_bC: batch_needs_third)
+        }
+        const GlweRef pk = ref(packed, sy, 0);
+        const int d1 = (int)c->base2d[1].size();
+        GlweRef tb[2];
+        if (c->tail_ep && d1 >= 2 && d1 <= TAIL_EP_MAX && use_tail(c, LOGN, 1, Y) && chain_bufs(LOGN, ep_out, res, tmp, tb)) {
+            launch_trace_tail(c, pk, tb, 0, LOGN, 1, Y, bprep(0, 1), d1, ep_out, false, ws, ostride);         // ram.rs:454 + 457, every address
+        } else {
+            for (int k = 0; k < K; k++) ep_chain(c, slice(pk, k), slice(ep_out, k), slice(tmp, k), bprep(k, 1), d1, 1, ws);   // ram.rs:454
+            trace_steps(c, ep_out, res, tmp, 0, LOGN, 1, Y);                                                  // ram.rs:457
+        }
+        c->memo_alone = 0;
+    }
+    // what K reads leave behind: the last address's result where a read leaves it
+    launch_copy(c, slice(res, K - 1), ref(c->d_res, G, 0), 1, ws);
+    c->memo_top = false;
+    c->d_last_res = c->d_res;
+    c->prep1_ready = false;
+    return FHERAM_OK;
+}
+// the K results, widened into h_bres by the device; out: [K][ws][GLWE] int64
+int read_batch_download(fheram_ctx* c, int K, int64_t* out) {
+    const size_t n = (size_t)K * c->ws * fheram_ctx::GLWE;
+    const int n4 = (int)(n / 4);
+    hipLaunchKernelGGL(k_export_i64, dim3((n4 + 255) / 256), dim3(256), 0, c->stream, c->d_bres,
+                       reinterpret_cast<long long*>(c->d_h_bres), n4, reinterpret_cast<const long long*>(c->d_tw + N));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    c->wide_unsynced = false;
+    double m;
+    std::memcpy(&m, c->h_bres + n, 8);
+    if (c->monitor && m > MON_LIMIT) __atomic_store_n(c->h_ro_flag, 1u, __ATOMIC_RELAXED);
+    const int rc = check_precision(c);
+    if (rc != FHERAM_OK) return rc;
+    std::memcpy(out, c->h_bres, n * sizeof(int64_t));
+    return FHERAM_OK;
+}
+
 // Ram::write (ram.rs:226-294) in two stages.
 // Stage 1 (root / unsharded): write_first_step on the top of the tree and, for n2 == 2, the inverse
 // coordinate-1 products: leaves the un-rotated ct_lo of every sub-RAM in d_part.

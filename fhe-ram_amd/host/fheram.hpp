@@ -144,6 +144,24 @@ public:
         chk(fheram_read(ctx_, dev(address), out.data()));
         return split(out);
     }
+    // addresses.size() independent Ram::read (ram.rs:172-191) of this RAM as one operation (fheram_read_batch, at most
+    // FHERAM_READ_BATCH_MAX): result i is what read(*addresses[i], keys) returns
+    std::vector<std::vector<Glwe>> read_batch(std::vector<Address*>& addresses, const EvaluationKeysPrepared& keys) {
+        if (addresses.empty() || addresses.size() > FHERAM_READ_BATCH_MAX)
+            throw Error(FHERAM_ERR_INVALID_ARG, "read_batch takes 1 to FHERAM_READ_BATCH_MAX addresses");
+        use(keys);
+        std::vector<const fheram_addr*> handles;
+        for (Address* a : addresses) {
+            if (!a) throw Error(FHERAM_ERR_INVALID_ARG, "null address");
+            handles.push_back(dev(*a));
+        }
+        const size_t one = params.word_size() * glwe_len();
+        std::vector<int64_t> out(addresses.size() * one);
+        chk(fheram_read_batch(ctx_, handles.data(), (int)handles.size(), out.data()));
+        std::vector<std::vector<Glwe>> res;
+        for (size_t k = 0; k < addresses.size(); k++) res.push_back(split(std::vector<int64_t>(out.begin() + k * one, out.begin() + (k + 1) * one)));
+        return res;
+    }
     // Ram::read_prepare_write, ram.rs:196-222
     std::vector<Glwe> read_prepare_write(Address& address, const EvaluationKeysPrepared& keys) {
         use(keys);

@@ -102,6 +102,17 @@ void fheram_address_destroy(fheram_addr* addr);
 /* Ram::read (ram.rs:172-191).  out: [word_size][GLWE] int64, or NULL to leave the result on
  * the device (fetch it later with fheram_result_download). */
 int fheram_read(fheram_ctx* ctx, const fheram_addr* addr, int64_t* out);
+/* K = n_addr independent Ram::read (ram.rs:172-191) of the same RAM, as one operation.  A read does not change the RAM (only its
+ * scratch), so the K reads share the rows, the keys and every address-independent launch; only the products with the address
+ * digits are per address.
+ * out (may be NULL): [n_addr][word_size][GLWE] int64; slice i is bit-identical to what fheram_read(ctx, addrs[i], ...) returns
+ * on the same state.  Duplicates are allowed.  1 <= n_addr <= FHERAM_READ_BATCH_MAX.  Errors are those of fheram_read, checked
+ * for every address before anything is enqueued; a row-sharded context is refused (FHERAM_ERR_INVALID_ARG).  Afterwards
+ * fheram_result_download / _map return the result of addrs[n_addr-1], and the context is in the state the equivalent sequence
+ * of reads leaves.  The batch's device buffers are allocated on first use and grown to the largest n_addr seen (FHERAM_ERR_DEVICE
+ * if that fails; single reads still work); fheram_ctx_destroy frees them. */
+#define FHERAM_READ_BATCH_MAX 8
+int fheram_read_batch(fheram_ctx* ctx, const fheram_addr* const* addrs, int n_addr, int64_t* out);
 /* Ram::read_prepare_write (ram.rs:196-222). */
 int fheram_read_prepare_write(fheram_ctx* ctx, const fheram_addr* addr, int64_t* out);
 /* Ram::write (ram.rs:226-294).  w: n_w GLWEs, each encrypting [w,0,...,0] (ram.rs:228);
