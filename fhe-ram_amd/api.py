@@ -26,6 +26,7 @@ _LIB = None
 I64P = C.POINTER(C.c_int64)
 
 READ_BATCH_MAX = 8   # FHERAM_READ_BATCH_MAX (include/fheram.h)
+BANK_MAX = 8         # FHERAM_BANK_MAX
 STATUS = {0: "OK", 1: "INVALID_ARG", 2: "STATE", 3: "UNINITIALIZED", 4: "KEYS", 5: "UNSUPPORTED", 6: "RANGE", 7: "DEVICE", 8: "PRECISION"}
 
 
@@ -151,6 +152,28 @@ _SYMBOLS = [
     ("fheram_group_peer_info", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
     ("fheram_group_poisoned", C.c_int, [C.c_void_p]),
     ("fheram_group_roundoff_max", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    ("fheram_bank_create", C.c_int, [C.POINTER(_CParams), C.c_int, C.c_int, C.POINTER(_CConfig), C.POINTER(C.c_void_p)]),
+    ("fheram_bank_destroy", None, [C.c_void_p]),
+    ("fheram_bank_last_error", C.c_char_p, [C.c_void_p]),
+    ("fheram_bank_size", C.c_int, [C.c_void_p]),
+    ("fheram_bank_keys_load", C.c_int, [C.c_void_p, I64P, C.c_int, C.POINTER(I64P), I64P, C.c_int64, I64P]),
+    ("fheram_bank_ram_upload", C.c_int, [C.c_void_p, C.c_int, I64P]),
+    ("fheram_bank_ram_download", C.c_int, [C.c_void_p, C.c_int, I64P]),
+    ("fheram_bank_ram_tree_download", C.c_int, [C.c_void_p, C.c_int, C.c_int, I64P]),
+    ("fheram_bank_ram_state", C.c_int, [C.c_void_p, C.c_int]),
+    ("fheram_bank_address_create", C.c_int, [C.c_void_p, C.POINTER(I64P), C.c_int, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_read", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), I64P]),
+    ("fheram_bank_read_prepare_write", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), I64P]),
+    ("fheram_bank_write", C.c_int, [C.c_void_p, C.c_int, C.c_int, I64P, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_result_download", C.c_int, [C.c_void_p, C.c_int, C.c_int, I64P]),
+    ("fheram_bank_sync", C.c_int, [C.c_void_p]),
+    ("fheram_bank_roundoff_max", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    ("fheram_bank_roundoff_reset", C.c_int, [C.c_void_p]),
+    ("fheram_bank_tail_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("fheram_bank_mid_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("fheram_bank_profile_enable", C.c_int, [C.c_void_p, C.c_int]),
+    ("fheram_bank_profile_get", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    ("fheram_bank_profile_reset", C.c_int, [C.c_void_p]),
     ("fheram_selftest_convolve", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int]),
     ("fheram_selftest_convolve_rounded", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_double]),
 ]
@@ -400,6 +423,17 @@ class Address:
             grp._chk(library().fheram_group_address_create(grp._h, arr, len(self.digits), C.byref(out)))
             h = _GroupAddrHandle(out.value, grp)
             self._handles[id(grp)] = h
+        return h.h
+
+    def _bank(self, bank: "RamBank"):
+        """the device address bound to `bank` (fheram_bank_address_create): one handle serves any of its members"""
+        h = self._handles.get(id(bank))
+        if h is None:
+            arr = (I64P * len(self.digits))(*[_p(d) for d in self.digits])
+            out = C.c_void_p()
+            bank._chk(library().fheram_bank_address_create(bank._h, arr, len(self.digits), C.byref(out)))
+            h = _AddrHandle(out.value, bank)
+            self._handles[id(bank)] = h
         return h.h
 
     def _device(self, ram: "Ram"):
@@ -1078,3 +1112,175 @@ class GroupRam:
         m = C.c_double()
         self._chk(library().fheram_group_roundoff_max(self._h, C.byref(m)))
         return float(m.value)
+
+
+class RamBank:
+    """M RAMs of the same shape under ONE prepared key set on one GPU (fheram_bank): read / read_prepare_write / write on a
+    contiguous member range [first, first + len(addresses)) as ONE operation, one address per member.  Member m behaves exactly like a
+    standalone Ram driven through the same calls (int64-identical results, rows, tree and state); members outside a range are
+    untouched, and a refused call changes no member."""
+
+    def __init__(self, params: Optional[Parameters], n_members: int, device: int = 0, config: Optional[dict] = None):
+        """config: execution switches that differ from fheram_config_default(), as Ram's"""
+        self.params = params or Parameters.new()
+        self.n_members = int(n_members)
+        self._h = None
+        L = library()
+        out = C.c_void_p()
+        cp = self.params._c()
+        cfg = None
+        if config:
+            cfg = _CConfig()
+            L.fheram_config_default(C.byref(cfg))
+            for k, v in config.items():
+                if k not in _CONFIG_FIELDS:
+                    raise FheRamError(1, f"unknown execution switch {k!r}")
+                setattr(cfg, k, int(v))
+        rc = L.fheram_bank_create(C.byref(cp), device, self.n_members, C.byref(cfg) if cfg is not None else None, C.byref(out))
+        if rc != 0:
+            raise FheRamError(rc, L.fheram_bank_last_error(None).decode())
+        self._h = out.value
+        self._keys = None
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _LIB is not None:
+            _LIB.fheram_bank_destroy(self._h)
+            self._h = None
+
+    def __len__(self):
+        return library().fheram_bank_size(self._h)
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise FheRamError(rc, library().fheram_bank_last_error(self._h).decode())
+
+    def _use_keys(self, keys: EvaluationKeysPrepared):
+        if self._keys is keys:
+            return
+        if keys.atk_glwe is None:
+            raise FheRamError(5, "these keys were generated on another context's device (EvaluationKeysPrepared.encrypt_sk "
+                                 "without keep_std=True): their std forms are not on the host")
+        p = self.params
+        n, b2k = p.n(), p.basek()
+        atk_len = p.dnum_ct() * -(-p.k_evk_trace() // b2k) * 2 * n        # evk_glwe_infos, parameters.rs:71-81
+        inv_len = p.dnum_ggsw() * -(-p.k_evk_ggsw_inv() // b2k) * 2 * n   # evk_ggsw_infos, parameters.rs:83-93
+        if any(k.size != atk_len for k in keys.atk_glwe) or keys.atk_ggsw_inv.size != inv_len or keys.tsk_ggsw_inv.size != inv_len:
+            raise FheRamError(1, f"evaluation-key layout does not match the bank's (trace keys of {atk_len} limbs-elements, "
+                                 f"inverse / tensor keys of {inv_len}: evk_glwe_infos / evk_ggsw_infos, parameters.rs:71-93)")
+        arr = (I64P * len(keys.atk_glwe))(*[_p(k) for k in keys.atk_glwe])
+        self._chk(library().fheram_bank_keys_load(self._h, _p(keys.gal_els), len(keys.gal_els), arr, _p(keys.atk_ggsw_inv),
+                                                  keys.atk_ggsw_inv_p, _p(keys.tsk_ggsw_inv)))
+        self._keys = keys
+
+    def _member(self, member: int) -> int:
+        member = int(member)
+        if not 0 <= member < self.n_members:
+            raise FheRamError(1, f"member {member} is outside the bank's {self.n_members} members")
+        return member
+
+    def _range(self, first: int, n: int):
+        first, n = int(first), int(n)
+        if n < 1 or first < 0 or first + n > self.n_members:
+            raise FheRamError(1, f"member range [{first}, {first + n}) is empty or outside the bank's {self.n_members} members")
+        return first, n
+
+    # -- data hand-over
+    def load_encrypted(self, member: int, rows: np.ndarray):
+        """rows: [word_size][rows][GLWE] of one member, which becomes readable"""
+        p = self.params
+        rows = _i64(rows)
+        if rows.size != p.word_size() * p.rows() * p.glwe_len():
+            raise FheRamError(1, f"invalid data: expected {p.word_size()}x{p.rows()} GLWE rows (ram.rs:144-155)")
+        self._chk(library().fheram_bank_ram_upload(self._h, self._member(member), _p(rows)))
+
+    def store_encrypted(self, member: int) -> np.ndarray:
+        p = self.params
+        rows = np.zeros((p.word_size(), p.rows(), p.glwe_len()), dtype=np.int64)
+        self._chk(library().fheram_bank_ram_download(self._h, self._member(member), _p(rows)))
+        return rows
+
+    def tree(self, member: int, level: int = 0) -> np.ndarray:
+        out = np.zeros((self.params.word_size(), self.params.glwe_len()), dtype=np.int64)
+        self._chk(library().fheram_bank_ram_tree_download(self._h, self._member(member), level, _p(out)))
+        return out
+
+    def state(self, member: int) -> bool:
+        return bool(library().fheram_bank_ram_state(self._h, self._member(member)))
+
+    # -- the path
+    def _addrs(self, addresses, first):
+        addresses = list(addresses)
+        if not all(isinstance(a, Address) for a in addresses):
+            raise FheRamError(1, "every entry must be an Address (a null address is refused)")
+        first, n = self._range(first, len(addresses))
+        return first, n, (C.c_void_p * n)(*[a._bank(self) for a in addresses])
+
+    def _read(self, fn, addresses, keys, first, download):
+        first, n, arr = self._addrs(addresses, first)
+        self._use_keys(keys)
+        p = self.params
+        out = np.zeros((n, p.word_size(), p.glwe_len()), dtype=np.int64) if download else None
+        self._chk(fn(self._h, first, n, arr, _p(out) if download else None))
+        return out
+
+    def read(self, addresses, keys: EvaluationKeysPrepared, first: int = 0, download: bool = True):  # ram.rs:172, per member
+        """members first .. first + len(addresses) - 1 read at one address each: int64 [n][word_size][GLWE]"""
+        return self._read(library().fheram_bank_read, addresses, keys, first, download)
+
+    def read_prepare_write(self, addresses, keys: EvaluationKeysPrepared, first: int = 0, download: bool = True):  # ram.rs:196
+        return self._read(library().fheram_bank_read_prepare_write, addresses, keys, first, download)
+
+    def write(self, words, addresses, keys: EvaluationKeysPrepared, first: int = 0):  # ram.rs:226, per member
+        """words: [n][word_size][GLWE], member first + k's word at k"""
+        first, n, arr = self._addrs(addresses, first)
+        p = self.params
+        if words is None:
+            raise FheRamError(1, "null words")
+        w = _i64(words)
+        if w.size != n * p.word_size() * p.glwe_len():
+            raise FheRamError(1, f"w.len() != subrams.len() (ram.rs:243): expected {n} x {p.word_size()} GLWEs")
+        self._use_keys(keys)
+        self._chk(library().fheram_bank_write(self._h, first, n, _p(w), arr))
+
+    def result(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """the results of each member's last read / read_prepare_write"""
+        first, n = self._range(first, self.n_members - int(first) if n is None else n)
+        p = self.params
+        out = np.zeros((n, p.word_size(), p.glwe_len()), dtype=np.int64)
+        self._chk(library().fheram_bank_result_download(self._h, first, n, _p(out)))
+        return out
+
+    def sync(self):
+        self._chk(library().fheram_bank_sync(self._h))
+
+    def roundoff_max(self, check: bool = True) -> float:
+        """the largest |x - rint(x)| any inverse transform of the bank has rounded away; raises PRECISION above 3/8 unless check=False"""
+        m = C.c_double()
+        rc = library().fheram_bank_roundoff_max(self._h, C.byref(m))
+        if rc != 0 and (check or rc != 8):
+            self._chk(rc)
+        return float(m.value)
+
+    def roundoff_reset(self):
+        self._chk(library().fheram_bank_roundoff_reset(self._h))
+
+    def tail_stats(self):
+        n, f = C.c_uint64(), C.c_uint64()
+        self._chk(library().fheram_bank_tail_stats(self._h, C.byref(n), C.byref(f)))
+        return {"launches": int(n.value), "fallbacks": int(f.value)}
+
+    def mid_stats(self):
+        n, f = C.c_uint64(), C.c_uint64()
+        self._chk(library().fheram_bank_mid_stats(self._h, C.byref(n), C.byref(f)))
+        return {"launches": int(n.value), "fallbacks": int(f.value)}
+
+    def profile_enable(self, on=True):
+        self._chk(library().fheram_bank_profile_enable(self._h, int(on)))
+
+    def profile_reset(self):
+        self._chk(library().fheram_bank_profile_reset(self._h))
+
+    def profile_get(self, cls: str):
+        n, b, ms = C.c_uint64(), C.c_uint64(), C.c_double()
+        self._chk(library().fheram_bank_profile_get(self._h, cls.encode(), C.byref(n), C.byref(b), C.byref(ms)))
+        return {"launches": int(n.value), "blocks": int(b.value), "ms": float(ms.value)}

@@ -185,6 +185,7 @@ int fheram_ctx_create_cfg(const fheram_params* p, int device, int shard, int n_s
     LDSATTR((&k_ext_product_chain_r<4>));
     LDSATTR((&k_pair_z<4>)); LDSATTR((&k_pair_z<5>));
     LDSATTR((&k_read_chain<4, 4>)); LDSATTR((&k_read_chain<5, 4>)); LDSATTR((&k_write_chain<4, 4>)); LDSATTR((&k_write_chain<5, 4>));
+    LDSATTR((&k_write_chain_b<4, 4>)); LDSATTR((&k_write_chain_b<5, 4>));
     LDSATTR((&k_read_chain_w<4, 4>)); LDSATTR((&k_read_chain_w<5, 4>));
     LDSATTR((&k_read_chain_b<4, 4>)); LDSATTR((&k_read_chain_b<5, 4>)); LDSATTR((&k_read_chain_bw<4, 4>)); LDSATTR((&k_read_chain_bw<5, 4>));
     LDSATTR((&k_trace_tail_b<3, 4, 3>)); LDSATTR((&k_trace_tail_b<3, 5, 3>));
@@ -931,3 +932,4 @@ int fheram_device_info(const fheram_ctx* c, char* name, size_t name_len, int* cu
 #include "setup.hpp"
 #include "selftest.hpp"
 #include "group.hpp"
+#include "bank.hpp"

@@ -14,6 +14,7 @@
 //                  products in front of the trace, round 6)
 //   chain_kernels.inc           k_keyswitch_chain / k_read_chain in two register budgets (included twice: 240 registers beside the gate wave, 256 otherwise;
 //                               twice more for k_read_chain_b / _bw, the read chain of fheram_read_batch)
+//   write_chain.inc             k_write_chain, and k_write_chain_b with a per-member operand table (fheram_bank_write)
 //   trace_tail.inc              k_trace_tail, and k_trace_tail_b with per-address products (fheram_read_batch)
 //
 // Device GLWE layout: int32 [limb][col][N] (the host's int64 layout narrowed; limbs are
@@ -1925,39 +1926,23 @@ __device__ __forceinline__ GlweRef batch_src_row(GlweRef a, const RowChainBatchA
 #undef FK_READ_CHAIN_ARGS
 #undef FK_READ_CHAIN_BATCH
 
-template <int SK, int SG>   // (only ever launched by Ram::write: never beside the gate wave)
-__global__ __launch_bounds__(T, T / 256) __attribute__((amdgpu_num_vgpr(FK_WIDE_VGPRS))) void k_write_chain(RowChainArgs ra) {
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    RoMonitor ro_mon(lds, ra.ep.tw);
-    double vc[E];   // (written by the first step before anything reads it)
-    KsArgs ka = ra.ks.base;
-#pragma unroll 1
-    for (int i = 0; i < ra.ks.n; i++) {          // n >= 2
-        ka.out = ra.ks.buf[i & 1];
-        ka.key = ra.ks.key[i];
-        ka.ginv = ra.ks.ginv[i];
-        int tid = vt((int)threadIdx.x);
-        asm volatile("" : "+v"(tid));
-        __builtin_assume(tid >= 0 && tid < T);
-        if (i == 0) ks_trace_l<SK, false, 1>(ka, lds, true, tid, vc);
-        else if (i + 1 < ra.ks.n) ks_trace_l<SK, true, 1>(ka, lds, false, tid, vc);
-        else { ka.b = ra.hi; ka.out = ra.trhi; ks_trace_l<SK, true, 2>(ka, lds, false, tid, vc); }
-        ka.rot_mul = 0;
-        ka.rot_base = 0;
-    }
-    GlweRef in = ra.ep.src;
-#pragma unroll 1
-    for (int i = 0; i < ra.ep.n; i++) {          // n >= 2
-        const GlweRef out = ra.ep.buf[i & 1];
-        int tid = vt((int)threadIdx.x);
-        asm volatile("" : "+v"(tid));
-        __builtin_assume(tid >= 0 && tid < T);
-        if (i == 0) ep_step_r<SG, 2, 1>(in, out, ra.ep.ggsw[i], ra.ep.tw, lds, false, tid, vc);
-        else if (i + 1 < ra.ep.n) ep_step_r<SG, 1, 1>(in, out, ra.ep.ggsw[i], ra.ep.tw, lds, false, tid, vc);
-        else ep_step_r<SG, 1, 0>(in, out, ra.ep.ggsw[i], ra.ep.tw, lds, false, tid, vc);
-        in = out;
-    }
-}
+// (defined in write_chain.inc, which is included twice: k_write_chain, and k_write_chain_b with a per-member operand table — the write
+// chain over the rows of the M members of a bank as ONE launch, y = m * ws + w: ct_lo from slot y, the shared trace keys, and the inverse
+// digits of coordinate 0 of member y / ws at ep.ggsw[i] + (y / ws) * opnd_stride.  src_rows is not used: every operand but the digits is per y.)
+#define FK_WRITE_CHAIN_ARGS RowChainArgs
+#define FK_WRITE_CHAIN_BATCH 0
+#define FK_WRITE_CHAIN_NAME k_write_chain
+#include "write_chain.inc"
+#undef FK_WRITE_CHAIN_ARGS
+#undef FK_WRITE_CHAIN_BATCH
+#undef FK_WRITE_CHAIN_NAME
+#define FK_WRITE_CHAIN_ARGS RowChainBatchArgs
+#define FK_WRITE_CHAIN_BATCH 1
+#define FK_WRITE_CHAIN_NAME k_write_chain_b
+#include "write_chain.inc"
+#undef FK_WRITE_CHAIN_ARGS
+#undef FK_WRITE_CHAIN_BATCH
+#undef FK_WRITE_CHAIN_NAME
 
 // ---------------------------------------------------------------------------------------
 // k_trace_tail: the dependent trace chain at the end of a read (ram.rs:457,540: n steps on word_size ciphertexts)

@@ -277,9 +277,9 @@ void fill_row_chain(fheram_ctx* c, RowChainArgs& ra, const double* prep, int d, 
 // read / read_prepare_write: d products of `src` with the prepared digits, then trace steps 0 .. n_tr-1 (the alone packer levels);
 // the result lands in dst; ep_store != nullptr: the products' result is also written there (in-place products of read_prepare_write)
 // bws > 0 (fheram_read_batch): gy = K * bws ciphertexts of K addresses; row y reads src at y mod bws and the digits of address y / bws,
-// which are opnd_stride elements apart from prep on (k_read_chain_b / _bw)
+// which are opnd_stride elements apart from prep on (k_read_chain_b / _bw); src_rows > 0 (a bank, bank.hpp): row y reads src at y mod src_rows instead
 void launch_read_chain(fheram_ctx* c, GlweRef src, const GlweRef* ep_store, GlweRef dst, const double* prep, int d, int n_tr, int gx, int gy,
-                       int bws = 0, long opnd_stride = 0) {
+                       int bws = 0, long opnd_stride = 0, int src_rows = 0) {
     ProfScope ps(c, "read_chain_launch", (uint64_t)gx * gy, 1);
     RowChainArgs ra;
     fill_row_chain(c, ra, prep, d, 0, n_tr);
@@ -292,7 +292,7 @@ void launch_read_chain(fheram_ctx* c, GlweRef src, const GlweRef* ep_store, Glwe
     if (bws > 0) {
         RowChainBatchArgs rb;
         static_cast<RowChainArgs&>(rb) = ra;
-        rb.opnd_stride = opnd_stride; rb.ws = bws; rb.src_rows = bws;
+        rb.opnd_stride = opnd_stride; rb.ws = bws; rb.src_rows = src_rows > 0 ? src_rows : bws;
         const bool w = c->wide;
         if (w) c->wide_unsynced = true;
         if (c->s_evk == 5) {
@@ -313,7 +313,10 @@ void launch_read_chain(fheram_ctx* c, GlweRef src, const GlweRef* ep_store, Glwe
     }
 }
 // write: trace steps 0 .. n_tr-1 of ct_lo * X^-row (src, read rotated), data <- normalize(data - trhi + that), d products in place
-void launch_write_chain(fheram_ctx* c, GlweRef src, int rot_mul, int rot_base, GlweRef data, GlweRef trhi, const double* prep, int d, int n_tr, int gx, int gy) {
+// bws > 0 (a bank, bank.hpp): gy = n * bws ciphertexts of n members; row y takes the inverse digits of member y / bws, which are
+// opnd_stride elements apart from prep on (k_write_chain_b)
+void launch_write_chain(fheram_ctx* c, GlweRef src, int rot_mul, int rot_base, GlweRef data, GlweRef trhi, const double* prep, int d, int n_tr, int gx, int gy,
+                        int bws = 0, long opnd_stride = 0) {
     ProfScope ps(c, "write_chain_launch", (uint64_t)gx * gy, 1);
     RowChainArgs ra;
     fill_row_chain(c, ra, prep, d, 0, n_tr);
@@ -322,6 +325,14 @@ void launch_write_chain(fheram_ctx* c, GlweRef src, int rot_mul, int rot_base, G
     ra.hi = data; ra.trhi = trhi;
     ra.ep.src = data; ra.ep.buf[0] = ra.ep.buf[1] = data;         // only the last product stores: in place on the rows
     c->wide_unsynced = true;                                      // (k_write_chain takes the whole register file)
+    if (bws > 0) {
+        RowChainBatchArgs rb;
+        static_cast<RowChainArgs&>(rb) = ra;
+        rb.opnd_stride = opnd_stride; rb.ws = bws; rb.src_rows = gy;
+        if (c->s_evk == 5) hipLaunchKernelGGL((k_write_chain_b<5, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
+        else hipLaunchKernelGGL((k_write_chain_b<4, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
+        return;
+    }
     if (c->s_evk == 5) hipLaunchKernelGGL((k_write_chain<5, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ra);
     else hipLaunchKernelGGL((k_write_chain<4, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ra);
 }

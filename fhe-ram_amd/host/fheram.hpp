@@ -369,4 +369,108 @@ private:
     }
 };
 
+// M RAMs (ram.rs:25-29) of the same shape under ONE prepared key set on one GPU (fheram_bank_*): read / read_prepare_write / write on
+// the contiguous member range [first, first + addresses.size()) as ONE operation, one address per member.  Member m behaves exactly
+// like a Ram driven through the same calls; members outside a range are untouched; a refused call changes no member.
+class Bank {
+public:
+    Parameters params;
+    Bank(const Parameters& prm, int n_members, int device = 0) : params(prm) {
+        int rc = fheram_bank_create(&params.p, device, n_members, nullptr, &bank_);
+        if (rc != FHERAM_OK) throw Error(rc, fheram_bank_last_error(nullptr));
+    }
+    Bank(const Parameters& prm, int n_members, const fheram_config& cfg, int device = 0) : params(prm) {
+        int rc = fheram_bank_create(&params.p, device, n_members, &cfg, &bank_);
+        if (rc != FHERAM_OK) throw Error(rc, fheram_bank_last_error(nullptr));
+    }
+    Bank(const Bank&) = delete;
+    ~Bank() {
+        for (auto& kv : addr_) fheram_address_destroy(kv.second);
+        if (bank_) fheram_bank_destroy(bank_);
+    }
+    int size() const { return fheram_bank_size(bank_); }
+    size_t glwe_len() const { return ((params.k_glwe_ct() + params.basek() - 1) / params.basek()) * 2 * params.n(); }
+    // one member's rows [word_size][rows][GLWE] (Ram::encrypt_sk output, ram.rs:129-167); the member becomes readable
+    void load_encrypted(int member, const std::vector<int64_t>& rows) {
+        if (rows.size() != params.word_size() * ((params.max_addr() + params.n() - 1) / params.n()) * glwe_len())
+            throw Error(FHERAM_ERR_INVALID_ARG, "invalid data: data.len()/ram_chunks != max_addr (ram.rs:150-155)");
+        chk(fheram_bank_ram_upload(bank_, member, rows.data()));
+    }
+    std::vector<int64_t> store_encrypted(int member) {
+        std::vector<int64_t> rows(params.word_size() * ((params.max_addr() + params.n() - 1) / params.n()) * glwe_len());
+        chk(fheram_bank_ram_download(bank_, member, rows.data()));
+        return rows;
+    }
+    bool state(int member) const { return fheram_bank_ram_state(bank_, member) != 0; }            // SubRam::state, ram.rs:302
+    // result k = what member first + k's Ram::read(*addresses[k]) returns (ram.rs:172-191)
+    std::vector<std::vector<Glwe>> read(std::vector<Address*>& addresses, const EvaluationKeysPrepared& keys, int first = 0) {
+        return read_op(false, addresses, keys, first);
+    }
+    std::vector<std::vector<Glwe>> read_prepare_write(std::vector<Address*>& addresses, const EvaluationKeysPrepared& keys, int first = 0) {   // ram.rs:196-222
+        return read_op(true, addresses, keys, first);
+    }
+    // w[k]: the word_size GLWEs of member first + k (ram.rs:226-294)
+    void write(const std::vector<std::vector<Glwe>>& w, std::vector<Address*>& addresses, const EvaluationKeysPrepared& keys, int first = 0) {
+        if (w.size() != addresses.size()) throw Error(FHERAM_ERR_INVALID_ARG, "one word per address");
+        std::vector<int64_t> flat;
+        for (auto& word : w) {
+            if (word.size() != params.word_size()) throw Error(FHERAM_ERR_INVALID_ARG, "w.len() != subrams.len() (ram.rs:243)");
+            for (auto& g : word) flat.insert(flat.end(), g.begin(), g.end());
+        }
+        use(keys);
+        std::vector<const fheram_addr*> h = handles(addresses);
+        chk(fheram_bank_write(bank_, first, (int)h.size(), flat.data(), h.data()));
+    }
+    void sync() { chk(fheram_bank_sync(bank_)); }
+    double roundoff_max() { double m = 0.0; chk(fheram_bank_roundoff_max(bank_, &m)); return m; }
+    struct ChainStats { uint64_t launches = 0, redone = 0; };
+    ChainStats tail_stats() { ChainStats s; chk(fheram_bank_tail_stats(bank_, &s.launches, &s.redone)); return s; }
+    ChainStats mid_stats() { ChainStats s; chk(fheram_bank_mid_stats(bank_, &s.launches, &s.redone)); return s; }
+
+private:
+    fheram_bank* bank_ = nullptr;
+    const EvaluationKeysPrepared* keys_ = nullptr;
+    std::vector<std::pair<const Address*, fheram_addr*>> addr_;   // device copies bound to the bank, by host address object
+    void chk(int rc) { if (rc != FHERAM_OK) throw Error(rc, fheram_bank_last_error(bank_)); }
+    void use(const EvaluationKeysPrepared& k) {
+        if (keys_ == &k) return;
+        std::vector<const int64_t*> ptr;
+        for (auto& a : k.atk_glwe) ptr.push_back(a.data());
+        chk(fheram_bank_keys_load(bank_, k.gal_els.data(), (int)k.gal_els.size(), ptr.data(), k.atk_ggsw_inv.data(), k.atk_ggsw_inv_p,
+                                  k.tsk_ggsw_inv.data()));
+        keys_ = &k;
+    }
+    fheram_addr* dev(const Address& a) {
+        for (auto& kv : addr_) if (kv.first == &a) return kv.second;
+        std::vector<const int64_t*> ptr;
+        for (auto& d : a.digits) ptr.push_back(d.data());
+        fheram_addr* h = nullptr;
+        chk(fheram_bank_address_create(bank_, ptr.data(), (int)ptr.size(), &h));   // layout check of ram.rs:404
+        addr_.emplace_back(&a, h);
+        return h;
+    }
+    std::vector<const fheram_addr*> handles(std::vector<Address*>& addresses) {
+        if (addresses.empty()) throw Error(FHERAM_ERR_INVALID_ARG, "empty member range");
+        std::vector<const fheram_addr*> h;
+        for (Address* a : addresses) {
+            if (!a) throw Error(FHERAM_ERR_INVALID_ARG, "null address");
+            h.push_back(dev(*a));
+        }
+        return h;
+    }
+    std::vector<std::vector<Glwe>> read_op(bool prepare_write, std::vector<Address*>& addresses, const EvaluationKeysPrepared& keys, int first) {
+        use(keys);
+        std::vector<const fheram_addr*> h = handles(addresses);
+        const size_t g = glwe_len(), one = params.word_size() * g;
+        std::vector<int64_t> out(h.size() * one);
+        chk(prepare_write ? fheram_bank_read_prepare_write(bank_, first, (int)h.size(), h.data(), out.data())
+                          : fheram_bank_read(bank_, first, (int)h.size(), h.data(), out.data()));
+        std::vector<std::vector<Glwe>> res(h.size());
+        for (size_t k = 0; k < h.size(); k++)
+            for (size_t i = 0; i < params.word_size(); i++)
+                res[k].emplace_back(out.begin() + k * one + i * g, out.begin() + k * one + (i + 1) * g);
+        return res;
+    }
+};
+
 }  // namespace fheram

@@ -264,6 +264,57 @@ int fheram_group_poisoned(const fheram_group* grp);
 /* the largest round-off over the shards' monitors (fheram_roundoff_max on every shard) */
 int fheram_group_roundoff_max(fheram_group* grp, double* max_out);
 
+/* ---- bank: M RAMs of the same shape under ONE prepared key set on one GPU, and Ram::read / read_prepare_write / write on a
+ * contiguous range of them as ONE operation, one address per member.  Ram objects are independent units (ram.rs:25-29; `&mut self`
+ * serialises operations per RAM only): nothing orders operations on different RAMs, so their latency-bound steps (pair levels,
+ * coordinate-1 products, traces, the write's head) run as single launches over n * word_size ciphertexts, and the rows' chains as one
+ * launch with a per-member operand table.
+ * Semantics: a bank of M members behaves exactly like M contexts created with the same fheram_params / fheram_config, loaded with
+ * the same keys and rows and given the same per-member sequence of operations: every result, every row after a write, tree level 0
+ * and the state flag of member m are int64-identical to those of standalone context m.
+ * An operation names members [first, first + n) and n addresses (created with fheram_bank_address_create; the same handle may serve
+ * several members); members outside the range are untouched.  A range of one member is the plain operation on that member, so a host
+ * mixes operations by issuing ranges (a read on member 0 while member 1 sits between read_prepare_write and write).
+ * Every check — the state machine per member (ram.rs:393-396,472-475,555-558), uninitialised rows, missing keys, foreign addresses,
+ * null arguments — runs for the whole range before anything is enqueued: a refused call changes no member.
+ * A bank is never row-sharded and never part of a group.  One op in flight per bank; a bank is not thread-safe. */
+#define FHERAM_BANK_MAX 8
+typedef struct fheram_bank fheram_bank;
+/* cfg == NULL: fheram_config_default().  Checks, in this order: null pointers, n_members outside [1, FHERAM_BANK_MAX] and
+ * n_members * word_size > 64 (FHERAM_ERR_INVALID_ARG); the parameter checks of fheram_ctx_create_cfg (same codes and messages);
+ * only then "no HIP device" (FHERAM_ERR_DEVICE).  In a bank of more than one member the write's inverse digits are never started
+ * early (pre_inv reads as 0); a bank of one member is a plain context. */
+int fheram_bank_create(const fheram_params* params, int device, int n_members, const fheram_config* cfg, fheram_bank** out);
+void fheram_bank_destroy(fheram_bank* bank);
+const char* fheram_bank_last_error(const fheram_bank* bank);   /* bank == NULL: last fheram_bank_create failure */
+int fheram_bank_size(const fheram_bank* bank);
+/* ONE prepared key set for all members (keys.rs:57-71); arguments as fheram_keys_load */
+int fheram_bank_keys_load(fheram_bank* bank, const int64_t* gal_els, int n_gal, const int64_t* const* atk_glwe,
+                          const int64_t* atk_ggsw_inv, int64_t atk_ggsw_inv_p, const int64_t* tsk_ggsw_inv);
+int fheram_bank_ram_upload(fheram_bank* bank, int member, const int64_t* rows);   /* [word_size][rows][GLWE]; the member becomes readable */
+int fheram_bank_ram_download(fheram_bank* bank, int member, int64_t* rows);
+int fheram_bank_ram_tree_download(fheram_bank* bank, int member, int level, int64_t* out);
+int fheram_bank_ram_state(const fheram_bank* bank, int member);
+/* an Address bound to the bank (any member); freed with fheram_address_destroy */
+int fheram_bank_address_create(fheram_bank* bank, const int64_t* const* ggsw, int n_ggsw, fheram_addr** out);
+/* out: [n][word_size][GLWE], or NULL (no download: fheram_bank_result_download later) */
+int fheram_bank_read(fheram_bank* bank, int first, int n, const fheram_addr* const* addrs, int64_t* out);
+int fheram_bank_read_prepare_write(fheram_bank* bank, int first, int n, const fheram_addr* const* addrs, int64_t* out);
+/* w: [n][word_size][GLWE], member first + k's words at k */
+int fheram_bank_write(fheram_bank* bank, int first, int n, const int64_t* w, const fheram_addr* const* addrs);
+/* the results of each member's last read / read_prepare_write */
+int fheram_bank_result_download(fheram_bank* bank, int first, int n, int64_t* out);
+int fheram_bank_sync(fheram_bank* bank);
+/* one round-off monitor for the bank; FHERAM_ERR_PRECISION as for a context */
+int fheram_bank_roundoff_max(fheram_bank* bank, double* max_out);
+int fheram_bank_roundoff_reset(fheram_bank* bank);
+/* as fheram_tail_stats / fheram_mid_stats / fheram_profile_*: the launch classes are those of a context */
+int fheram_bank_tail_stats(fheram_bank* bank, uint64_t* launches, uint64_t* fallbacks);
+int fheram_bank_mid_stats(fheram_bank* bank, uint64_t* launches, uint64_t* fallbacks);
+int fheram_bank_profile_enable(fheram_bank* bank, int on);
+int fheram_bank_profile_get(fheram_bank* bank, const char* kernel_class, uint64_t* launches, uint64_t* blocks, double* total_ms);
+int fheram_bank_profile_reset(fheram_bank* bank);
+
 /* ---- Poulpy-level operations reached from the path, exposed for
  * parity tests and micro-benchmarks.  Inputs/outputs are host buffers in the layouts above. */
 
