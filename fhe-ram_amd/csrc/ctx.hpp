@@ -161,7 +161,7 @@ struct fheram_ctx {
     int32_t* d_last_res = nullptr; // where the last read / read_prepare_write left its result (d_res or d_trtop)
     bool tree_rotate_pending = false;
     int32_t* d_trhi = nullptr;     // arena that holds trace(ct_hi) of the local rows during a write (A or C)
-    // fheram_read_batch (path.hpp read_batch_impl): buffers for batch_cap addresses, allocated on first use and grown to the largest
+    // fheram_read_batch (path.hpp batch_opnds / batch_arenas): buffers for batch_cap addresses, allocated on first use and grown to the largest
     // batch seen.  Ciphertext y = k * ws + w of a batch is word w of address k; the arenas keep the rows' stride (sy = rows * GLWE).
     int batch_cap = 0;
     int32_t* d_bA = nullptr;       // [K*ws][rows]  ping-pong arenas of the batch's rows

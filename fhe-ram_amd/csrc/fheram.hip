@@ -422,19 +422,9 @@ void fheram_address_destroy(fheram_addr* a) {
 int fheram_result_map(fheram_ctx* c, const int64_t** out) {
     if (!c || !out) return FHERAM_ERR_INVALID_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    const int n4 = (int)((size_t)c->ws * fheram_ctx::GLWE / 4);
-    hipLaunchKernelGGL(k_export_i64, dim3((n4 + 255) / 256), dim3(256), 0, c->stream, c->d_last_res ? c->d_last_res : c->d_res,
-                       reinterpret_cast<long long*>(c->d_h_res), n4, reinterpret_cast<const long long*>(c->d_tw + N));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    c->wide_unsynced = false;
+    const ResRun run{c->d_last_res ? c->d_last_res : c->d_res, (size_t)c->ws * fheram_ctx::GLWE};
     *out = c->h_res;
-    {   // the monitor's maximum as it stood when the result was exported (the export kernel copies it behind the result)
-        double m;
-        std::memcpy(&m, c->h_res + (size_t)c->ws * fheram_ctx::GLWE, 8);
-        if (c->monitor && m > MON_LIMIT) __atomic_store_n(c->h_ro_flag, 1u, __ATOMIC_RELAXED);
-    }
-    return check_precision(c);
+    return result_export(c, &run, 1, c->h_res, c->d_h_res, nullptr);
 }
 int fheram_result_download(fheram_ctx* c, int64_t* out) {
     if (!c || !out) return FHERAM_ERR_INVALID_ARG;
@@ -479,12 +469,12 @@ int fheram_read(fheram_ctx* c, const fheram_addr* addr, int64_t* out) {
     if (c->n_shards != 1) return fail(c, FHERAM_ERR_INVALID_ARG, "row-sharded context: use fheram_read_partial / fheram_read_finish");
     if (c->state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.read: internal state is true -> requires calling Memory.write");
     HIPCHK(c, hipSetDevice(c->device));
-    rc = run_op(c, addr, 0, [&] { return read_impl(c, addr, false); });
+    rc = run_op(c, addr, 0, [&] { return read_impl(one_addr(c, &addr), ctx_arenas(c), false); });
     if (rc != FHERAM_OK) return rc;
     HIPCHK(c, hipGetLastError());
     return out ? fheram_result_download(c, out) : FHERAM_OK;
 }
-// K independent Ram::read (ram.rs:172-191) as one operation (path.hpp read_batch_impl)
+// K independent Ram::read (ram.rs:172-191) as one operation: path.hpp read_impl over K addresses, on the batch's arenas
 int fheram_read_batch(fheram_ctx* c, const fheram_addr* const* addrs, int n_addr, int64_t* out) {
     if (!c) return FHERAM_ERR_INVALID_ARG;
     if (!addrs) return fail(c, FHERAM_ERR_INVALID_ARG, "null address list");
@@ -499,7 +489,7 @@ int fheram_read_batch(fheram_ctx* c, const fheram_addr* const* addrs, int n_addr
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
     if (n_addr == 1) {
-        rc = run_op(c, addrs[0], 0, [&] { return read_impl(c, addrs[0], false); });
+        rc = run_op(c, addrs[0], 0, [&] { return read_impl(one_addr(c, addrs), ctx_arenas(c), false); });
         if (rc != FHERAM_OK) return rc;
         HIPCHK(c, hipGetLastError());
         return out ? fheram_result_download(c, out) : FHERAM_OK;
@@ -507,10 +497,14 @@ int fheram_read_batch(fheram_ctx* c, const fheram_addr* const* addrs, int n_addr
     // (never captured: a batch's launch sequence depends on K addresses, and a read's state bookkeeping is done as it is enqueued)
     rc = batch_reserve(c, n_addr);
     if (rc != FHERAM_OK) return rc;
-    rc = read_batch_impl(c, addrs, n_addr);
+    const Opnds o = batch_opnds(c, addrs, n_addr);
+    rc = read_impl(o, batch_arenas(c), false);
     if (rc != FHERAM_OK) return rc;
+    // what K reads leave behind: the last address's result where a read leaves it (d_last_res = d_res; nothing is kept for a write)
+    launch_copy(c, o.slice(ref(c->d_bres, (long)fheram_ctx::GLWE, 0), n_addr - 1), ref(c->d_res, (long)fheram_ctx::GLWE, 0), 1, c->ws);
     HIPCHK(c, hipGetLastError());
-    return out ? read_batch_download(c, n_addr, out) : FHERAM_OK;
+    const ResRun run{c->d_bres, (size_t)n_addr * c->ws * fheram_ctx::GLWE};
+    return out ? result_export(c, &run, 1, c->h_bres, c->d_h_bres, out) : FHERAM_OK;
 }
 int fheram_read_prepare_write(fheram_ctx* c, const fheram_addr* addr, int64_t* out) {
     int rc = check_common(c, addr);
@@ -518,7 +512,7 @@ int fheram_read_prepare_write(fheram_ctx* c, const fheram_addr* addr, int64_t* o
     if (c->n_shards != 1) return fail(c, FHERAM_ERR_INVALID_ARG, "row-sharded context: use fheram_read_partial / fheram_read_finish");
     if (c->state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.read: internal state is true -> requires calling Memory.write");
     HIPCHK(c, hipSetDevice(c->device));
-    rc = run_op(c, addr, 1, [&] { return read_impl(c, addr, true); });
+    rc = run_op(c, addr, 1, [&] { return read_impl(one_addr(c, &addr), ctx_arenas(c), true); });
     if (rc != FHERAM_OK) return rc;
     c->state = true;                                                                  // ram.rs:533
     HIPCHK(c, hipGetLastError());
@@ -550,12 +544,13 @@ int fheram_write(fheram_ctx* c, const int64_t* w, int n_w, const fheram_addr* ad
     if (!w && !c->words_staged) return fail(c, FHERAM_ERR_INVALID_ARG, "w == NULL and no staged words");
     // the part of a write that needs no words (trace(ct_hi) of every row, inverse of coordinate 0) is enqueued BEFORE the host
     // narrows the words: the GPU works while the host converts
-    if (w && !c->side_begun && !(c->use_graph && !c->profile)) write_side_begin(c, addr);
+    const Opnds o = one_addr(c, &addr);
+    if (w && !c->side_begun && !(c->use_graph && !c->profile)) write_side_begin(o);
     if (w) { rc = fheram_word_stage(c, w, n_w); if (rc != FHERAM_OK) { write_side_abort(c); return rc; } }
     rc = run_op(c, addr, 2, [&] {
-        if (!c->side_begun) write_side_begin(c, addr);   // (fheram_write_begin may have started it)
-        int r2 = write_top(c, addr);
-        return r2 == FHERAM_OK ? write_rows(c, addr) : r2;
+        if (!c->side_begun) write_side_begin(o);   // (fheram_write_begin may have started it)
+        int r2 = write_top(o);
+        return r2 == FHERAM_OK ? write_rows(o) : r2;
     });
     if (rc != FHERAM_OK) return rc;
     c->state = false;
@@ -592,7 +587,7 @@ int fheram_read_partial(fheram_ctx* c, const fheram_addr* addr, int prepare_writ
     if (c->state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.read: internal state is true -> requires calling Memory.write");
     HIPCHK(c, hipSetDevice(c->device));
     GlweRef packed;
-    rc = read_local(c, addr, prepare_write != 0, &packed, true);
+    rc = read_local(one_addr(c, &addr), ctx_arenas(c), prepare_write != 0, &packed, true);
     if (rc != FHERAM_OK) return rc;
     HIPCHK(c, hipGetLastError());
     if (prepare_write) c->state = true;
@@ -629,7 +624,7 @@ int fheram_write_begin(fheram_ctx* c, const fheram_addr* addr) {
     if (rc != FHERAM_OK) return rc;
     if (!c->state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.write: internal state is false -> requires calling Memory.read_prepare_write");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->side_begun) write_side_begin(c, addr);
+    if (!c->side_begun) write_side_begin(one_addr(c, &addr));
     HIPCHK(c, hipGetLastError());
     return FHERAM_OK;
 }
@@ -646,7 +641,7 @@ int fheram_read_finish(fheram_ctx* c, const fheram_addr* addr, int prepare_write
         rc = import_glwes(c, c->d_part, partials, partials_on_device, (size_t)c->ws);
     }
     if (rc != FHERAM_OK) return rc;
-    rc = read_top(c, addr, prepare_write != 0, gathered, ref(c->d_part, (long)fheram_ctx::GLWE, 0));
+    rc = read_top(one_addr(c, &addr), ctx_arenas(c), prepare_write != 0, gathered, ref(c->d_part, (long)fheram_ctx::GLWE, 0));
     if (rc != FHERAM_OK) return rc;
     HIPCHK(c, hipGetLastError());
     return out ? fheram_result_download(c, out) : fheram_sync(c);
@@ -661,8 +656,8 @@ int fheram_write_root(fheram_ctx* c, const int64_t* w, int n_w, const fheram_add
     HIPCHK(c, hipSetDevice(c->device));
     if (w) { rc = fheram_word_stage(c, w, n_w); if (rc != FHERAM_OK) return rc; }
     else if (!c->words_staged) return fail(c, FHERAM_ERR_INVALID_ARG, "w == NULL and no staged words");
-    if (!c->side_begun) write_side_begin(c, addr);   // the root's own rows: overlaps the latency-bound head below
-    rc = write_top(c, addr);
+    if (!c->side_begun) write_side_begin(one_addr(c, &addr));   // the root's own rows: overlaps the latency-bound head below
+    rc = write_top(one_addr(c, &addr));
     if (rc != FHERAM_OK) return rc;
     HIPCHK(c, hipGetLastError());
     return export_glwes(c, c->d_part, ct_lo_out, out_on_device, (size_t)c->ws);
@@ -673,10 +668,10 @@ int fheram_write_shard(fheram_ctx* c, const fheram_addr* addr, const void* ct_lo
     if (!ct_lo) return fail(c, FHERAM_ERR_INVALID_ARG, "null ct_lo");
     if (!c->state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.write: internal state is false -> requires calling Memory.read_prepare_write");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->side_begun) write_side_begin(c, addr);   // normally started earlier by fheram_write_begin / fheram_write_root
+    if (!c->side_begun) write_side_begin(one_addr(c, &addr));   // normally started earlier by fheram_write_begin / fheram_write_root
     rc = import_glwes(c, c->d_part, ct_lo, on_device, (size_t)c->ws);
     if (rc != FHERAM_OK) { write_side_abort(c); return rc; }
-    rc = write_rows(c, addr);
+    rc = write_rows(one_addr(c, &addr));
     if (rc != FHERAM_OK) return rc;
     HIPCHK(c, hipGetLastError());
     return FHERAM_OK;

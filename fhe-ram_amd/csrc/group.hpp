@@ -146,8 +146,9 @@ int group_read_job(fheram_group* g, const fheram_group_addr* ga, bool prepare_wr
     auto bail = [&](int rc) { g->failed.store(true, std::memory_order_release); return rc; };
     int rc;
     if (hipSetDevice(c->device) != hipSuccess) return bail(fail(c, FHERAM_ERR_DEVICE, "hipSetDevice"));
+    const Opnds o = one_addr(c, &addr);
     GlweRef packed;
-    rc = read_local(c, addr, prepare_write, &packed, true);            // ... -> d_part
+    rc = read_local(o, ctx_arenas(c), prepare_write, &packed, true);   // ... -> d_part
     if (rc != FHERAM_OK) return bail(rc);
     // (ram.rs:533: the state flag is committed by the caller once EVERY shard has come through)
     hipError_t e = hipMemcpyPeerAsync(r->d_gat[0] + (size_t)i * part, r->device, c->d_part, c->device, part * sizeof(int32_t), c->stream);
@@ -159,7 +160,7 @@ int group_read_job(fheram_group* g, const fheram_group_addr* ga, bool prepare_wr
     if (!await_count(g, g->parts_recorded, g->n())) return fail(c, FHERAM_ERR_DEVICE, "a shard failed (or did not arrive within 30 s) before the exchange");
     for (int k = 0; k < g->n(); k++)
         if (k != i && hipStreamWaitEvent(c->stream, g->ev_part[k], 0) != hipSuccess) return bail(fail(c, FHERAM_ERR_DEVICE, "hipStreamWaitEvent"));
-    rc = read_top(c, addr, prepare_write, c->d_gat[0], ref(c->d_part, (long)fheram_ctx::GLWE, 0));
+    rc = read_top(o, ctx_arenas(c), prepare_write, c->d_gat[0], ref(c->d_part, (long)fheram_ctx::GLWE, 0));
     if (rc != FHERAM_OK) return bail(rc);
     if (hipGetLastError() != hipSuccess) return bail(fail(c, FHERAM_ERR_DEVICE, "launch failure in read_top"));
     return out ? fheram_result_download(c, out) : fheram_sync(c);
@@ -174,9 +175,10 @@ int group_write_job(fheram_group* g, const fheram_group_addr* ga, int i) {
     auto bail = [&](int rc) { g->failed.store(true, std::memory_order_release); return rc; };
     int rc;
     if (hipSetDevice(c->device) != hipSuccess) return bail(fail(c, FHERAM_ERR_DEVICE, "hipSetDevice"));
-    if (!c->side_begun) write_side_begin(c, addr);                        // trace(ct_hi) of the local rows, inverse of coordinate 0: no ct_lo needed
+    const Opnds o = one_addr(c, &addr);
+    if (!c->side_begun) write_side_begin(o);                              // trace(ct_hi) of the local rows, inverse of coordinate 0: no ct_lo needed
     if (i == g->root) {
-        rc = write_top(c, addr);                                          // write_first_step + inverse coordinate-1 products -> ct_lo in d_part
+        rc = write_top(o);                                                // write_first_step + inverse coordinate-1 products -> ct_lo in d_part
         if (rc != FHERAM_OK) return bail(rc);
         for (int k = 0; k < g->n(); k++) {                                // the one exchange step of a write
             if (k == i) continue;
@@ -195,7 +197,7 @@ int group_write_job(fheram_group* g, const fheram_group_addr* ga, int i) {
     // leaves all rows as they were (the root included)
     g->ready.fetch_add(1, std::memory_order_release);
     if (!await_count(g, g->ready, g->n())) { write_side_abort(c); return fail(c, FHERAM_ERR_DEVICE, "a shard failed before the rows were written: the rows are unchanged, but the tree top and the write state have been consumed — upload the RAM again"); }
-    rc = write_rows(c, addr);                                             // write_mid_step on the local rows, write_last_step
+    rc = write_rows(o);                                                   // write_mid_step on the local rows, write_last_step
     if (rc != FHERAM_OK) return bail(rc);
     if (hipGetLastError() != hipSuccess) return bail(fail(c, FHERAM_ERR_DEVICE, "launch failure in write_rows"));
     return fheram_sync(c);                                                // the op is complete when every shard's rows are

@@ -260,6 +260,11 @@ void launch_trace_chain(fheram_ctx* c, GlweRef src, const GlweRef (&b)[2], int s
         else hipLaunchKernelGGL((k_keyswitch_chain<3, 4, 3>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ca);
     }
 }
+// The operand table of a launch over several addresses (path.hpp Opnds::table): gy = n * ws ciphertexts, ciphertext y takes the prepared
+// digits of address y / ws, which are `stride` elements apart from prep on, and reads a rows source at y mod src_rows (ws: every address reads
+// the same rows, fheram_read_batch; n * ws: its own, a bank range).  ws == 0: one address, no table (the kernels without one).
+// src_rows is read by launch_read_chain only: the write chain and the tail's fallback always run on rows of their own (y mod gy).
+struct OpndTable { int ws = 0; long stride = 0; int src_rows = 0; };
 // The two chains a row goes through back to back as ONE launch (k_read_chain / k_write_chain): both must be in the fused,
 // one-workgroup-per-ciphertext regime, in the forms that hand over through LDS and registers.
 bool use_row_fuse(const fheram_ctx* c, int d, int n_tr, int gx, int gy) {
@@ -276,10 +281,8 @@ void fill_row_chain(fheram_ctx* c, RowChainArgs& ra, const double* prep, int d, 
 }
 // read / read_prepare_write: d products of `src` with the prepared digits, then trace steps 0 .. n_tr-1 (the alone packer levels);
 // the result lands in dst; ep_store != nullptr: the products' result is also written there (in-place products of read_prepare_write)
-// bws > 0 (fheram_read_batch): gy = K * bws ciphertexts of K addresses; row y reads src at y mod bws and the digits of address y / bws,
-// which are opnd_stride elements apart from prep on (k_read_chain_b / _bw); src_rows > 0 (a bank, bank.hpp): row y reads src at y mod src_rows instead
-void launch_read_chain(fheram_ctx* c, GlweRef src, const GlweRef* ep_store, GlweRef dst, const double* prep, int d, int n_tr, int gx, int gy,
-                       int bws = 0, long opnd_stride = 0, int src_rows = 0) {
+// with a table: row y reads src at y mod t.src_rows and the digits of address y / t.ws (k_read_chain_b / _bw)
+void launch_read_chain(fheram_ctx* c, GlweRef src, const GlweRef* ep_store, GlweRef dst, const double* prep, int d, int n_tr, int gx, int gy, const OpndTable& t) {
     ProfScope ps(c, "read_chain_launch", (uint64_t)gx * gy, 1);
     RowChainArgs ra;
     fill_row_chain(c, ra, prep, d, 0, n_tr);
@@ -289,10 +292,10 @@ void launch_read_chain(fheram_ctx* c, GlweRef src, const GlweRef* ep_store, Glwe
     ra.ks.base = ks_args(c, dst, dst, dst, trace_key(c, 0), c->gal[0]);
     ra.ks.buf[0] = ra.ks.buf[1] = dst;                            // only the last step stores
     ra.hi = dst; ra.trhi = dst;
-    if (bws > 0) {
+    if (t.ws > 0) {
         RowChainBatchArgs rb;
         static_cast<RowChainArgs&>(rb) = ra;
-        rb.opnd_stride = opnd_stride; rb.ws = bws; rb.src_rows = src_rows > 0 ? src_rows : bws;
+        rb.opnd_stride = t.stride; rb.ws = t.ws; rb.src_rows = t.src_rows;
         const bool w = c->wide;
         if (w) c->wide_unsynced = true;
         if (c->s_evk == 5) {
@@ -313,10 +316,8 @@ void launch_read_chain(fheram_ctx* c, GlweRef src, const GlweRef* ep_store, Glwe
     }
 }
 // write: trace steps 0 .. n_tr-1 of ct_lo * X^-row (src, read rotated), data <- normalize(data - trhi + that), d products in place
-// bws > 0 (a bank, bank.hpp): gy = n * bws ciphertexts of n members; row y takes the inverse digits of member y / bws, which are
-// opnd_stride elements apart from prep on (k_write_chain_b)
-void launch_write_chain(fheram_ctx* c, GlweRef src, int rot_mul, int rot_base, GlweRef data, GlweRef trhi, const double* prep, int d, int n_tr, int gx, int gy,
-                        int bws = 0, long opnd_stride = 0) {
+// with a table (a bank range: every member its own rows): row y takes the inverse digits of member y / t.ws (k_write_chain_b)
+void launch_write_chain(fheram_ctx* c, GlweRef src, int rot_mul, int rot_base, GlweRef data, GlweRef trhi, const double* prep, int d, int n_tr, int gx, int gy, const OpndTable& t) {
     ProfScope ps(c, "write_chain_launch", (uint64_t)gx * gy, 1);
     RowChainArgs ra;
     fill_row_chain(c, ra, prep, d, 0, n_tr);
@@ -325,10 +326,10 @@ void launch_write_chain(fheram_ctx* c, GlweRef src, int rot_mul, int rot_base, G
     ra.hi = data; ra.trhi = trhi;
     ra.ep.src = data; ra.ep.buf[0] = ra.ep.buf[1] = data;         // only the last product stores: in place on the rows
     c->wide_unsynced = true;                                      // (k_write_chain takes the whole register file)
-    if (bws > 0) {
+    if (t.ws > 0) {
         RowChainBatchArgs rb;
         static_cast<RowChainArgs&>(rb) = ra;
-        rb.opnd_stride = opnd_stride; rb.ws = bws; rb.src_rows = gy;
+        rb.opnd_stride = t.stride; rb.ws = t.ws; rb.src_rows = gy;
         if (c->s_evk == 5) hipLaunchKernelGGL((k_write_chain_b<5, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
         else hipLaunchKernelGGL((k_write_chain_b<4, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
         return;
@@ -348,11 +349,9 @@ bool use_tail(const fheram_ctx* c, int n, int gx, int gy) {
 // prep != nullptr (round 6): the d external products with the prepared digits at `prep` run in front of the trace chain in the SAME launch
 // (coordinate 1's products, ram.rs:454 / 525-527): src -> products -> ep_out -> trace -> b[(n - 1) & 1]; store_ep: the caller needs ep_out
 // afterwards (read_prepare_write's tree[0]).  The fallback launch is then the fused row chain (k_read_chain), predicated likewise.
-// bws > 0 (fheram_read_batch, with prep): ciphertext y belongs to address y / bws, whose digits are opnd_stride elements apart from prep on
-// (k_trace_tail_b, and k_read_chain_b as its fallback)
+// with a table (and prep): ciphertext y takes the digits of address y / t.ws (k_trace_tail_b, and k_read_chain_b as its fallback)
 void launch_trace_tail(fheram_ctx* c, GlweRef src, const GlweRef (&b)[2], int start, int n, int gx, int gy,
-                       const double* prep = nullptr, int d = 0, GlweRef ep_out = GlweRef{nullptr, 0, 0}, bool store_ep = false,
-                       int bws = 0, long opnd_stride = 0) {
+                       const double* prep = nullptr, int d = 0, GlweRef ep_out = GlweRef{nullptr, 0, 0}, bool store_ep = false, const OpndTable& t = {}) {
     ProfScope ps(c, "keyswitch", (uint64_t)gx * gy, n);
     ProfScope pt(c, "keyswitch_tail_launch", (uint64_t)gx * gy * n, 1);
     TailArgs ta;
@@ -382,13 +381,13 @@ void launch_trace_tail(fheram_ctx* c, GlweRef src, const GlweRef (&b)[2], int st
         ra.hi = ra.trhi = b[(n - 1) & 1];
         ra.ks.pred = ca.pred; ra.ks.pred_seq = ca.pred_seq; ra.ks.host_count = ca.host_count;
     }
-    if (bws > 0 && ta.n_ep) {
+    if (t.ws > 0 && ta.n_ep) {
         TailBatchArgs tb;
         static_cast<TailArgs&>(tb) = ta;
-        tb.opnd_stride = opnd_stride; tb.ws = bws;
+        tb.opnd_stride = t.stride; tb.ws = t.ws;
         RowChainBatchArgs rb;
         static_cast<RowChainArgs&>(rb) = ra;
-        rb.opnd_stride = opnd_stride; rb.ws = bws; rb.src_rows = gx * gy;   // the source is the batch's own: row y is y
+        rb.opnd_stride = t.stride; rb.ws = t.ws; rb.src_rows = gx * gy;   // the source is the batch's own: row y is y
         if (c->s_evk == 5) {
             hipLaunchKernelGGL((k_trace_tail_b<3, 5, 3>), dim3(TAIL_GROUPS * 2 * 5 * 3), dim3(T), LDS_BYTES, c->cur, tb);
             hipLaunchKernelGGL((k_read_chain_b<5, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
@@ -507,16 +506,16 @@ int32_t* pack_levels(fheram_ctx* c, int32_t* src, int32_t* A, int32_t* B, long s
 }
 // CoordinatePrepared::prepare (coordinate_prepared.rs:104-116) for coordinate `ci` of addr.
 int coord_first_digit(const fheram_ctx* c, int ci) { int s = 0; for (int i = 0; i < ci; i++) s += (int)c->base2d[i].size(); return s; }
-// The prepared digits of coordinate ci live at prep_of(c, ci) inside d_prep ([n_digits] prepared GGSW).
-double* prep_of(const fheram_ctx* c, int ci) { return c->d_prep + (size_t)coord_first_digit(c, ci) * fheram_ctx::GGSW; }
-void coordinate_prepare(fheram_ctx* c, const fheram_addr* addr, int ci) {
+// The prepared digits of coordinate ci live at its first digit inside an address's table ([n_digits] prepared GGSW: d_prep, or a slot of a wider table).
+double* digits_of(const fheram_ctx* c, double* table, int ci) { return table + (size_t)coord_first_digit(c, ci) * fheram_ctx::GGSW; }
+void coordinate_prepare(fheram_ctx* c, const fheram_addr* addr, int ci, double* table) {
     const int d = (int)c->base2d[ci].size();
-    launch_prepare(c, addr->d_ggsw + (size_t)coord_first_digit(c, ci) * fheram_ctx::GGSW, prep_of(c, ci), d * (int)(fheram_ctx::GGSW / N));
+    launch_prepare(c, addr->d_ggsw + (size_t)coord_first_digit(c, ci) * fheram_ctx::GGSW, digits_of(c, table, ci), d * (int)(fheram_ctx::GGSW / N));
 }
 // every coordinate of the address in ONE launch (the reference prepares coordinate i at the top of loop iteration i,
 // ram.rs:416-419; nothing in between depends on the order)
-void coordinate_prepare_all(fheram_ctx* c, const fheram_addr* addr) {
-    launch_prepare(c, addr->d_ggsw, c->d_prep, c->n_digits * (int)(fheram_ctx::GGSW / N));
+void coordinate_prepare_all(fheram_ctx* c, const fheram_addr* addr, double* table) {
+    launch_prepare(c, addr->d_ggsw, table, c->n_digits * (int)(fheram_ctx::GGSW / N));
 }
 // CoordinatePrepared::prepare_inv (coordinate_prepared.rs:121-142): GGSW(X^i) -> GGSW(X^-i).
 void ggsw_inverse(fheram_ctx* c, const int32_t* in, int32_t* tmp, int d) {
@@ -529,7 +528,6 @@ void ggsw_inverse(fheram_ctx* c, const int32_t* in, int32_t* tmp, int d) {
     KsArgs kt = ks_args(c, ref(tmp, (long)fheram_ctx::GGSW, 2 * g4), ref(tmp, 0, 0), ref(tmp + g4, (long)fheram_ctx::GGSW, 2 * g4), c->d_tsk, 1);
     launch_ks<KS_TENSOR, 4, 5, 4>(c, kt, fheram_ctx::DNUM_CT, d);
 }
-double* prep_inv_of(const fheram_ctx* c, int ci) { return c->d_prep_inv + (size_t)coord_first_digit(c, ci) * fheram_ctx::GGSW; }
 void coordinate_prepare_inv(fheram_ctx* c, const fheram_addr* addr, int ci, int32_t* tmp, double* prep) {
     const int d = (int)c->base2d[ci].size();
     ggsw_inverse(c, addr->d_ggsw + (size_t)coord_first_digit(c, ci) * fheram_ctx::GGSW, tmp, d);
@@ -561,7 +559,7 @@ void precompute_inverse(fheram_ctx* c, const fheram_addr* addr, int ci, bool for
     }
     hipStream_t keep = c->cur;
     c->cur = c->stream2;
-    coordinate_prepare_inv(c, addr, ci, c->d_ggsw_inv + (size_t)coord_first_digit(c, ci) * fheram_ctx::GGSW, prep_inv_of(c, ci));
+    coordinate_prepare_inv(c, addr, ci, c->d_ggsw_inv + (size_t)coord_first_digit(c, ci) * fheram_ctx::GGSW, digits_of(c, c->d_prep_inv, ci));
     hipEventRecord(c->ev_inv[ci], c->stream2);
     c->cur = keep;
     c->inv_id[ci] = addr->id;

@@ -1,12 +1,73 @@
 // Private to fheram.hip: Ram::read / read_prepare_write / write as launch sequences (reference: src/ram.rs).
+// ONE read sequence (read_local + read_top, together read_impl) and ONE write sequence (write_side_begin, write_top, write_rows), over an
+// operand set (Opnds: whose digits a product uses) and, for reads, an arena set (ReadArenas: where it runs).  The plain context, the stages of
+// a row-sharded RAM (fheram.hip, group.hpp), fheram_read_batch and fheram_bank_* (bank.hpp) all run these; what is specific to one of them
+// is a visible condition in the sequence (n == 1: pre_inv, the gate wave, ev_opstart, ev_wdone, sharding, capture; a bank range: bank_row_fuse).
 #pragma once
 #include "launch.hpp"
 
 namespace {
 
+// use_row_fuse for a range of bank members.  A lone context splits by column while rows * ws * 2 workgroups still fit the chip (pick_nco),
+// which rules the fused row chain out; for a range the alternative to the ONE launch with an operand table is not one column-split
+// launch per step but one per MEMBER and step, so the range takes one workgroup per ciphertext from the start.  (The smaller regimes —
+// limb split, fine split, the mid chains — keep their precedence inside use_row_fuse.)
+bool bank_row_fuse(fheram_ctx* c, int d, int n_tr, int gx, int gy) {
+    const int nco = c->nco;
+    if (nco == 0) c->nco = 2;
+    const bool fuse = use_row_fuse(c, d, n_tr, gx, gy);
+    c->nco = nco;
+    return fuse;
+}
+
+// One operation's OPERAND SET: n addresses of ws ciphertexts each (Y = n * ws; ciphertext y = k * ws + w is word w of address k).
+// n == 1 is the plain operation: the context's own digit slots, every `for k` loop below runs once and no launch takes a table.
+// n > 1: the prepared digits of address k sit k * stride further in a table; every address-independent step is ONE launch over Y, the products
+// use the table in the forms that carry one (launch.hpp OpndTable) and run one launch per address on its y-slice with the plain launchers
+// everywhere else.  Never sharded, never captured, never with early inverse digits (pre_inv) then.
+struct Opnds {
+    fheram_ctx* c;
+    const fheram_addr* const* addrs;
+    int n, ws;
+    double *tab, *tab_inv;   // (inverse) digits of address 0
+    long stride;
+    bool own_rows;           // a bank range: address k reads and writes member k's rows; false (fheram_read_batch): every address reads the same rows
+    int Y() const { return n * ws; }
+    double* prep(int k, int ci) const { return digits_of(c, tab + k * stride, ci); }
+    double* inv(int k, int ci) const { return digits_of(c, tab_inv + k * stride, ci); }
+    GlweRef slice(GlweRef r, int k) const { r.p += (long)k * ws * r.sy; return r; }   // address k's ws ciphertexts
+    GlweRef rows(GlweRef r, int k) const { return own_rows ? slice(r, k) : r; }
+    OpndTable table() const { return n == 1 ? OpndTable{} : OpndTable{ws, stride, own_rows ? Y() : ws}; }
+    // the fused row chain (k_read_chain / k_write_chain) for this operation: a bank range decides for itself, a batch as a lone context does
+    bool row_fuse(int d, int n_tr, int gx) const { return n > 1 && own_rows ? bank_row_fuse(c, d, n_tr, gx, Y()) : use_row_fuse(c, d, n_tr, gx, Y()); }
+};
+// the plain operation: one address (a = &addr), the context's d_prep / d_prep_inv, the context's word count (a bank view's range of one member)
+Opnds one_addr(fheram_ctx* c, const fheram_addr* const* a) { return Opnds{c, a, 1, c->ws, c->d_prep, c->d_prep_inv, 0, true}; }
+
+// A read's ARENA SET: the rows it reads, the ping-pong arenas A / B with the optional third and fourth (pack_levels P0 / P1), the per-ciphertext
+// buffers, and where the result goes.  The context's own (for a bank: the view's, bank.hpp), or a batch's (batch_arenas below).
+struct ReadArenas {
+    int32_t *rows, *A, *B, *C, *D;   // [Y][rows]
+    int32_t *part, *tmp, *tmp2, *res;   // [Y]; part: the packed row where no arena holds it (rows == 1, a shard's partial)
+};
+ReadArenas ctx_arenas(const fheram_ctx* c) { return ReadArenas{c->d_data, c->d_scrA, c->d_scrB, c->d_scrC, c->d_scrD, c->d_part, c->d_tmp, c->d_tmp2, c->d_res}; }
+
+// What an operation leaves on the host, once it has been enqueued — or replayed (run_op), which does not run the enqueue functions.
+// A read has one such function per stage, because the stages of a row-sharded RAM run on different contexts.
+void read_local_done(fheram_ctx* c, bool prepare_write) {   // memo_alone: arena A keeps the rows after their alone levels (two coordinates only)
+    if (c->n2 == 2) c->memo_alone = (prepare_write && c->memo) ? LOGN - ilog2_ceil(c->rows_glob) : 0;
+}
+void read_top_done(fheram_ctx* c, bool prepare_write) {
+    c->memo_top = prepare_write && c->memo;           // d_trtop = trace(tree top), kept for the write
+    c->d_last_res = c->memo_top ? c->d_trtop : c->d_res;
+    c->prep1_ready = false;
+}
+// (inv_id / inv_pending are consumed where the write uses the inverse digits, write_side_begin and write_top; a replay finds them at 0, see run_op)
+void write_done(fheram_ctx* c) { c->memo_top = false; c->memo_alone = 0; c->side_begun = false; c->tree_rotate_pending = false; }
+
 // The launch sequence of an op is a function of (context, address, op) and of a few bits of the context's state (what a
 // write may resume from): with FHERAM_GRAPH=1 it is captured once per address and state signature into a hipGraph and
-// replayed, instead of being re-enqueued kernel by kernel.
+// replayed, instead of being re-enqueued kernel by kernel.  (One address only; pre_inv is off under FHERAM_GRAPH=1, so inv_id stays 0.)
 template <typename F>
 int run_op(fheram_ctx* c, const fheram_addr* addr, int which, F&& enqueue) {
     if (!c->use_graph || c->profile) return enqueue();
@@ -31,16 +92,8 @@ int run_op(fheram_ctx* c, const fheram_addr* addr, int which, F&& enqueue) {
         a->graph_sig[which] = sig;
     }
     HIPCHK(c, hipGraphLaunch(a->graph[which], c->stream));
-    // the host-side bookkeeping the enqueue functions do (a replay does not run them)
-    const int L0 = LOGN - ilog2_ceil(c->rows_glob);
-    if (which == 0) { c->memo_top = false; c->d_last_res = c->d_res; }
-    else if (which == 1) {
-        c->memo_top = c->memo != 0;
-        c->d_last_res = c->memo_top ? c->d_trtop : c->d_res;
-        c->memo_alone = (c->memo && c->n2 == 2 && L0 > 0) ? L0 : 0;
-        if (c->pre_inv && (long)c->rows * c->ws <= c->cus) for (int ci = 0; ci < c->n2; ci++) c->inv_id[ci] = addr->id;
-    } else { c->memo_top = false; c->memo_alone = 0; c->side_begun = false; c->tree_rotate_pending = false; c->inv_id[0] = c->inv_id[1] = 0; }
-    c->prep1_ready = false;
+    if (which == 2) write_done(c);
+    else { read_local_done(c, which == 1); read_top_done(c, which == 1); }
     return FHERAM_OK;
 }
 
@@ -55,77 +108,72 @@ int check_common(fheram_ctx* c, const fheram_addr* addr) {
     return FHERAM_OK;
 }
 
-// SubRam::read (ram.rs:382-459) / SubRam::read_prepare_write (ram.rs:461-542) for all sub-RAMs at
-// once, in two stages so that a row-sharded RAM can exchange between them.
+// SubRam::read (ram.rs:382-459) / SubRam::read_prepare_write (ram.rs:461-542) for all sub-RAMs of every address of the operand
+// set at once, in two stages so that a row-sharded RAM can exchange between them.
 // Stage 1 (every shard): coordinate-0 products on the local rows + the packing levels that stay
 // inside the shard.  The packed GLWE of every sub-RAM is left where the last launch wrote it (*packed_out,
-// indexed by sub-RAM); to_part also copies it into d_part (the buffer a sharded RAM exchanges).
-int read_local(fheram_ctx* c, const fheram_addr* addr, bool prepare_write, GlweRef* packed_out, bool to_part) {
-    c->wide = !prepare_write;   // read_prepare_write parks the gate wave beside its launches (read_top): its chain kernels keep a wave slot free
-    if (prepare_write && c->pre_inv == 1 && !capturing(c) && c->wide_unsynced) {   // the gate wave may not be parked before this op's own launches start (ctx.hpp: ev_opstart)
+// indexed by sub-RAM); to_part also copies it into a.part (d_part: the buffer a sharded RAM exchanges).
+int read_local(const Opnds& o, const ReadArenas& a, bool prepare_write, GlweRef* packed_out, bool to_part) {
+    fheram_ctx* c = o.c;
+    const int n = o.n, ws = o.ws, Y = o.Y(), R = (int)c->rows;
+    c->wide = !prepare_write || n > 1;   // read_prepare_write parks the gate wave beside its launches (read_top): its chain kernels keep a wave slot free; several addresses never park one
+    if (n == 1 && prepare_write && c->pre_inv == 1 && !capturing(c) && c->wide_unsynced) {   // the gate wave may not be parked before this op's own launches start (ctx.hpp: ev_opstart)
         hipEventRecord(c->ev_opstart, c->stream);
         c->opstart_valid = true;
     }
     const long G = (long)fheram_ctx::GLWE;
     const long sy = (long)c->rows * G;
-    const int ws = c->ws;
-    const int R = (int)c->rows;
-    GlweRef data = ref(c->d_data, sy, G), A = ref(c->d_scrA, sy, G), B = ref(c->d_scrB, sy, G);
-    GlweRef part = ref(c->d_part, G, 0);
-    const bool all = (c->n_shards == 1 && c->n2 == 2);   // unsharded: both coordinates now, one launch
-    if (all) coordinate_prepare_all(c, addr); else coordinate_prepare(c, addr, 0);    // ram.rs:416-419 / 496-499
+    GlweRef data = ref(a.rows, sy, G), A = ref(a.A, sy, G), B = ref(a.B, sy, G);
+    GlweRef part = ref(a.part, G, 0);
+    const bool all = (c->n_shards == 1 && c->n2 == 2);   // unsharded: both coordinates now, one launch per address
+    for (int k = 0; k < n; k++)                                                           // ram.rs:416-419 / 496-499
+        if (all) coordinate_prepare_all(c, o.addrs[k], o.tab + k * o.stride); else coordinate_prepare(c, o.addrs[k], 0, o.tab + k * o.stride);
     c->prep1_ready = all;
+    read_local_done(c, prepare_write);
     const int d0 = (int)c->base2d[0].size();
     if (c->n2 == 1) {
-        GlweRef row0 = ref(c->d_data, sy, 0);
-        if (prepare_write) {
-            ep_chain(c, row0, row0, ref(c->d_scrA, sy, 0), prep_of(c, 0), d0, 1, ws);     // ram.rs:502-504 (rows == 1)
-            *packed_out = row0;
-            if (to_part) launch_copy(c, row0, part, 1, ws);
-        } else {
-            ep_chain(c, row0, part, ref(c->d_tmp, G, 0), prep_of(c, 0), d0, 1, ws);       // ram.rs:451
-            *packed_out = part;
-        }
+        GlweRef row0 = ref(a.rows, sy, 0);
+        for (int k = 0; k < n; k++)
+            if (prepare_write) ep_chain(c, o.rows(row0, k), o.rows(row0, k), o.slice(ref(a.A, sy, 0), k), o.prep(k, 0), d0, 1, ws);   // ram.rs:502-504 (rows == 1)
+            else ep_chain(c, o.rows(row0, k), o.slice(part, k), o.slice(ref(a.tmp, G, 0), k), o.prep(k, 0), d0, 1, ws);                 // ram.rs:451
+        *packed_out = prepare_write ? row0 : part;
+        if (prepare_write && to_part) launch_copy(c, row0, part, 1, Y);
         return FHERAM_OK;
     }
-    int32_t* leaves;
     const int L0 = LOGN - ilog2_ceil(c->rows_glob);
-    const bool keep = prepare_write && c->memo && L0 > 0;   // leaves = d_data then: arena A keeps the rows after their alone levels
+    const bool keep = c->memo_alone > 0;   // leaves = the rows then: arena A keeps the rows after their alone levels
     int32_t* packed;
-    if (use_row_fuse(c, d0, L0, R, ws) && !(prepare_write && (d0 & 1))) {
-        // the products and the alone packer levels as ONE launch (k_read_chain): rows after the alone levels in arena A
-        // (read_prepare_write: the products' result also lands in the rows, ram.rs:502-504)
-        launch_read_chain(c, data, prepare_write ? &data : nullptr, A, prep_of(c, 0), d0, L0, R, ws);
-        packed = pack_levels(c, c->d_scrA, c->d_scrA, c->d_scrB, sy, G, (size_t)R, ws, 0, L0, keep, c->d_scrC, c->d_scrD);   // ram.rs:435-448 / 510-521: the pairing levels
+    if (o.row_fuse(d0, L0, R) && !(prepare_write && (d0 & 1))) {
+        // the products and the alone packer levels as ONE launch (k_read_chain; with a table: row y takes the digits of address y / ws):
+        // rows after the alone levels in arena A (read_prepare_write: the products' result also lands in the rows, ram.rs:502-504)
+        launch_read_chain(c, data, prepare_write ? &data : nullptr, A, o.prep(0, 0), d0, L0, R, Y, o.table());   // ram.rs:429-435 / 502-514
+        packed = pack_levels(c, a.A, a.A, a.B, sy, G, (size_t)R, Y, 0, L0, keep, a.C, a.D);   // ram.rs:435-448 / 510-521: the pairing levels
     } else {
-    if (prepare_write) {
-        ep_chain(c, data, data, A, prep_of(c, 0), d0, R, ws);                             // ram.rs:502-504
-        leaves = c->d_data;
-    } else {
-        ep_chain(c, data, A, B, prep_of(c, 0), d0, R, ws);                                // ram.rs:429-434
-        leaves = c->d_scrA;
+        for (int k = 0; k < n; k++)
+            if (prepare_write) ep_chain(c, o.rows(data, k), o.rows(data, k), o.slice(A, k), o.prep(k, 0), d0, R, ws);   // ram.rs:502-504
+            else ep_chain(c, o.rows(data, k), o.slice(A, k), o.slice(B, k), o.prep(k, 0), d0, R, ws);                   // ram.rs:429-434
+        packed = pack_levels(c, prepare_write ? a.rows : a.A, a.A, a.B, sy, G, (size_t)R, Y, L0, L0, keep, a.C, a.D);   // ram.rs:435-448 / 510-521
     }
-    packed = pack_levels(c, leaves, c->d_scrA, c->d_scrB, sy, G, (size_t)R, ws, L0, L0, keep, c->d_scrC, c->d_scrD);   // ram.rs:435-448 / 510-521
-    }
-    c->memo_alone = keep ? L0 : 0;
     *packed_out = ref(packed, sy, 0);
-    if (to_part) launch_copy(c, *packed_out, part, 1, ws);
+    if (to_part) launch_copy(c, *packed_out, part, 1, Y);
     return FHERAM_OK;
 }
 // Stage 2 (root / unsharded): remaining packing levels over the shards' partials (`gathered`:
 // [n_shards][ws] GLWEs, or nullptr when the RAM is not sharded and the packed rows are at `pk`),
-// coordinate-1 products and the final trace.  Result left in d_res.  Every step is out of place, so
+// coordinate-1 products and the final trace.  Result left in a.res (d_trtop: below).  Every step is out of place, so
 // nothing has to be copied between them.
-int read_top(fheram_ctx* c, const fheram_addr* addr, bool prepare_write, int32_t* gathered, GlweRef pk) {
-    c->wide = !prepare_write;
+int read_top(const Opnds& o, const ReadArenas& a, bool prepare_write, int32_t* gathered, GlweRef pk) {
+    fheram_ctx* c = o.c;
+    const int n = o.n, ws = o.ws, Y = o.Y();
+    c->wide = !prepare_write || n > 1;
     const long G = (long)fheram_ctx::GLWE;
-    const int ws = c->ws;
-    GlweRef tmp = ref(c->d_tmp, G, 0), tree = ref(c->d_tree, G, 0);
+    GlweRef tmp = ref(a.tmp, G, 0);
     GlweRef last = pk;
     // coordinate 1's products inside the trace chain's launch (k_trace_tail's product steps): from two digits on (the fallback is the fused row chain)
-    const int d1q = c->n2 == 2 ? (int)c->base2d[1].size() : 0;
-    const bool fuse_ep = c->n2 == 2 && c->tail_ep && d1q >= 2 && d1q <= TAIL_EP_MAX && use_tail(c, LOGN, 1, ws);
-    GlweRef ep_out = prepare_write ? tree : ref(c->d_tmp2, G, 0);
+    const int d1 = c->n2 == 2 ? (int)c->base2d[1].size() : 0;
+    const bool fuse_ep = c->n2 == 2 && c->tail_ep && d1 >= 2 && d1 <= TAIL_EP_MAX && use_tail(c, LOGN, 1, Y);
+    GlweRef ep_out = ref(prepare_write ? c->d_tree : a.tmp2, G, 0);                       // read_prepare_write: tree[0] <- rotated packed row, ram.rs:525-527
+    auto products1 = [&] { for (int k = 0; k < n; k++) ep_chain(c, o.slice(pk, k), o.slice(ep_out, k), o.slice(tmp, k), o.prep(k, 1), d1, 1, ws); };   // ram.rs:454 (not into res: the trace below runs out of place) / 525-527 + 502-504 (i = 1)
     if (c->n2 == 2) {
         if (gathered) {
             const int kG = ilog2_ceil((size_t)c->n_shards);
@@ -134,39 +182,29 @@ int read_top(fheram_ctx* c, const fheram_addr* addr, bool prepare_write, int32_t
             int32_t* packed = pack_levels(c, gathered, a0, a1, G, (long)ws * G, (size_t)c->n_shards, ws, 0, LOGN - kG);
             pk = ref(packed, G, 0);
         }
-        if (!c->prep1_ready) coordinate_prepare(c, addr, 1);
-        c->prep1_ready = false;
-        const int d1 = (int)c->base2d[1].size();
-        if (fuse_ep) {
-            last = ep_out;                                                            // (enqueued below, with the trace chain)
-        } else if (prepare_write) {
-            ep_chain(c, pk, tree, tmp, prep_of(c, 1), d1, 1, ws);                         // ram.rs:525-527 + 502-504 (i = 1): tree[0] <- rotated packed row
-            last = tree;                                                              // ram.rs:535 (res <- tree[0])
-        } else {
-            GlweRef tmp2 = ref(c->d_tmp2, G, 0);
-            ep_chain(c, pk, tmp2, tmp, prep_of(c, 1), d1, 1, ws);                         // ram.rs:454 (not into res: the trace below runs out of place)
-            last = tmp2;
-        }
-    }                                                                                 // n2 == 1: res <- packed row (ram.rs:452 / 537)
+        if (!c->prep1_ready) coordinate_prepare(c, o.addrs[0], 1, o.tab);                 // (a sharded RAM: one address)
+        if (!fuse_ep) products1();                                                        // (else enqueued below, with the trace chain)
+        last = ep_out;                                                                    // ram.rs:535 (res <- tree[0])
+    }                                                                                     // n2 == 1: res <- packed row (ram.rs:452 / 537)
     // read_prepare_write: the result is also what write_first_step computes first (trace of the same ciphertext,
     // ram.rs:571-572): it lands in d_trtop, which no read overwrites, and stays there for the write
     // the write's inverse digits, next to the trace chain below (one launch on half of the XCDs; the side stream has the
     // lowest priority, so that launch is placed first)
     // (only while the write's chains are one workgroup round on the chip: with several rounds — 2^21 on one GPU — the
     // earlier start of the write's main chain interleaves it with the side chain less favourably, write 8.57 -> 8.74 ms)
-    const bool pre = prepare_write && c->pre_inv && (long)c->rows * c->ws <= c->cus;
+    const bool pre = n == 1 && prepare_write && c->pre_inv && (long)c->rows * c->ws <= c->cus;
     const bool gated = pre && c->pre_inv == 1 && !capturing(c) && use_tail(c, LOGN, 1, ws);   // FHERAM_PRE_INV=2: event fork (A/B switch)
     if (pre && !gated)
-        for (int ci = c->n2 - 1; ci >= 0; ci--) precompute_inverse(c, addr, ci, ci == c->n2 - 1);   // coordinate 1 first: the write's head needs it first
-    c->memo_top = prepare_write && c->memo;
-    c->d_last_res = c->memo_top ? c->d_trtop : c->d_res;
+        for (int ci = c->n2 - 1; ci >= 0; ci--) precompute_inverse(c, o.addrs[0], ci, ci == c->n2 - 1);   // coordinate 1 first: the write's head needs it first
+    read_top_done(c, prepare_write);
+    const GlweRef res = ref(c->memo_top ? c->d_trtop : a.res, G, 0);
     const uint64_t tl0 = c->tail_launches;
     GlweRef tb[2];
-    if (fuse_ep && chain_bufs(LOGN, last, ref(c->d_last_res, G, 0), tmp, tb))          // ram.rs:454 / 525-527 + 457 / 540 as ONE launch
-        launch_trace_tail(c, pk, tb, 0, LOGN, 1, ws, prep_of(c, 1), d1q, ep_out, prepare_write);
+    if (fuse_ep && chain_bufs(LOGN, last, res, tmp, tb))                               // ram.rs:454 / 525-527 + 457 / 540 as ONE launch
+        launch_trace_tail(c, pk, tb, 0, LOGN, 1, Y, o.prep(0, 1), d1, ep_out, prepare_write, o.table());
     else {
-        if (fuse_ep) ep_chain(c, pk, ep_out, tmp, prep_of(c, 1), d1q, 1, ws);          // (cannot happen with these buffers; kept for safety)
-        trace_steps(c, last, ref(c->d_last_res, G, 0), tmp, 0, LOGN, 1, ws);          // ram.rs:457 / 540
+        if (fuse_ep) products1();                                                      // (cannot happen with these buffers; kept for safety)
+        trace_steps(c, last, res, tmp, 0, LOGN, 1, Y);                                 // ram.rs:457 / 540
     }
     if (gated && !c->opstart_valid && c->wide_unsynced) {   // (a root's read_finish: no read_local of this op ran on this context)
         hipEventRecord(c->ev_opstart, c->stream);
@@ -174,16 +212,17 @@ int read_top(fheram_ctx* c, const fheram_addr* addr, bool prepare_write, int32_t
     }
     if (gated) {   // behind a gate that opens when the trace chain's launch is placed (no event on the main stream); host order is irrelevant
         const unsigned seq = c->tail_launches != tl0 ? c->tail_seq : 0;                // 0: no such launch after all -> event fork
-        for (int ci = c->n2 - 1; ci >= 0; ci--) precompute_inverse(c, addr, ci, ci == c->n2 - 1, seq);
+        for (int ci = c->n2 - 1; ci >= 0; ci--) precompute_inverse(c, o.addrs[0], ci, ci == c->n2 - 1, seq);
     }
     return FHERAM_OK;
 }
-int read_impl(fheram_ctx* c, const fheram_addr* addr, bool prepare_write) {
+int read_impl(const Opnds& o, const ReadArenas& a, bool prepare_write) {
+    fheram_ctx* c = o.c;
     GlweRef packed;
-    int rc = read_local(c, addr, prepare_write, &packed, false);
+    int rc = read_local(o, a, prepare_write, &packed, false);
     if (rc != FHERAM_OK) return rc;
-    rc = read_top(c, addr, prepare_write, nullptr, packed);
-    if (prepare_write && c->inv_id[0] == addr->id && capturing(c))                    // a capture ends with every fork joined
+    rc = read_top(o, a, prepare_write, nullptr, packed);
+    if (o.n == 1 && prepare_write && c->inv_id[0] == o.addrs[0]->id && capturing(c))   // a capture ends with every fork joined
         for (int ci = 0; ci < c->n2; ci++) hipStreamWaitEvent(c->stream, c->ev_inv[ci], 0);
     if (rc == FHERAM_OK && prepare_write) c->state = true;                            // ram.rs:533
     return rc;
@@ -237,102 +276,65 @@ int batch_reserve(fheram_ctx* c, int K) {
     c->batch_cap = K;
     return FHERAM_OK;
 }
-// Products with address-dependent digits use the operand table (y / ws -> address) in the forms that carry one: the fused row chain
-// (k_read_chain_b) and the tail with products (k_trace_tail_b, fallback k_read_chain_b); every other form runs one launch per address
-// on its own y-slice with the single-read launchers.  The result of address k is at d_bres + k * ws GLWEs.
-int read_batch_impl(fheram_ctx* c, const fheram_addr* const* addrs, int K) {
-    c->wide = true;   // (Ram::read: never beside the gate wave)
-    const long G = (long)fheram_ctx::GLWE;
-    const long sy = (long)c->rows * G;
-    const int ws = c->ws, R = (int)c->rows, Y = K * ws;
-    const long ostride = (long)c->n_digits * (long)fheram_ctx::GGSW;              // one address's prepared digits
-    for (int k = 0; k < K; k++)                                                       // ram.rs:416-419, every address
-        launch_prepare(c, addrs[k]->d_ggsw, c->d_bprep + k * ostride, c->n_digits * (int)(fheram_ctx::GGSW / N));
-    auto bprep = [&](int k, int ci) { return c->d_bprep + k * ostride + (long)coord_first_digit(c, ci) * (long)fheram_ctx::GGSW; };
-    auto slice = [&](GlweRef r, int k) { r.p += (long)k * ws * r.sy; return r; };  // address k's ws ciphertexts
-    GlweRef tmp = ref(c->d_btmp, G, 0), ep_out = ref(c->d_btmp2, G, 0), res = ref(c->d_bres, G, 0);
-    const int d0 = (int)c->base2d[0].size();
-    if (c->n2 == 1) {                                                                 // rows == 1: res <- trace(products of the row)
-        GlweRef row0 = ref(c->d_data, sy, 0);
-        for (int k = 0; k < K; k++) ep_chain(c, row0, slice(ep_out, k), slice(tmp, k), bprep(k, 0), d0, 1, ws);   // ram.rs:451
-        trace_steps(c, ep_out, res, tmp, 0, LOGN, 1, Y);                                                      // ram.rs:457
-    } else {
-        GlweRef data = ref(c->d_data, sy, G), A = ref(c->d_bA, sy, G), B = ref(c->d_bB, sy, G);
-        const int L0 = LOGN - ilog2_ceil(c->rows_glob);
-        int32_t* packed;
-        if (use_row_fuse(c, d0, L0, R, Y)) {
-            launch_read_chain(c, data, nullptr, A, bprep(0, 0), d0, L0, R, Y, ws, ostride);                  // ram.rs:429-435, every address
-            packed = pack_levels(c, c->d_bA, c->d_bA, c->d_bB, sy, G, (size_t)R, Y, 0, L0);   // ram.rs:435-448 (no alone levels left: no third arena)
-        } else {
-            for (int k = 0; k < K; k++) ep_chain(c, data, slice(A, k), slice(B, k), bprep(k, 0), d0, R, ws);   // ram.rs:429-434
-            packed = pack_levels(c, c->d_bA, c->d_bA, c->d_bB, sy, G, (size_t)R, Y, L0, L0, false, c->d_bC);   // (d_bC: batch_needs_third)
-        }
-        const GlweRef pk = ref(packed, sy, 0);
-        const int d1 = (int)c->base2d[1].size();
-        GlweRef tb[2];
-        if (c->tail_ep && d1 >= 2 && d1 <= TAIL_EP_MAX && use_tail(c, LOGN, 1, Y) && chain_bufs(LOGN, ep_out, res, tmp, tb)) {
-            launch_trace_tail(c, pk, tb, 0, LOGN, 1, Y, bprep(0, 1), d1, ep_out, false, ws, ostride);         // ram.rs:454 + 457, every address
-        } else {
-            for (int k = 0; k < K; k++) ep_chain(c, slice(pk, k), slice(ep_out, k), slice(tmp, k), bprep(k, 1), d1, 1, ws);   // ram.rs:454
-            trace_steps(c, ep_out, res, tmp, 0, LOGN, 1, Y);                                                  // ram.rs:457
-        }
-        c->memo_alone = 0;
+// The batch as an operand set and an arena set for read_impl: the digits' table is d_bprep, every address reads the context's rows and the
+// launches write batch arenas only.  The result of address k is at d_bres + k * ws GLWEs; rows == 1: the products land in d_btmp2.
+Opnds batch_opnds(fheram_ctx* c, const fheram_addr* const* addrs, int K) { return Opnds{c, addrs, K, c->ws, c->d_bprep, nullptr, (long)c->n_digits * (long)fheram_ctx::GGSW, false}; }
+ReadArenas batch_arenas(const fheram_ctx* c) { return ReadArenas{c->d_data, c->d_bA, c->d_bB, c->d_bC, nullptr, c->d_btmp2, c->d_btmp, c->d_btmp2, c->d_bres}; }
+
+// The one result export: every run (source, int32 count) is widened by the device into the pinned buffer h (device address d_h), back to
+// back, with the monitor's maximum as it stood then behind the last (the export kernel copies it there); out != nullptr: copied out.
+struct ResRun { const int32_t* src; size_t n; };
+int result_export(fheram_ctx* c, const ResRun* runs, int n_runs, int64_t* h, int64_t* d_h, int64_t* out) {
+    size_t n = 0;
+    for (int i = 0; i < n_runs; i++) {
+        const int n4 = (int)(runs[i].n / 4);
+        hipLaunchKernelGGL(k_export_i64, dim3((n4 + 255) / 256), dim3(256), 0, c->stream, runs[i].src, reinterpret_cast<long long*>(d_h + n), n4,
+                           reinterpret_cast<const long long*>(c->d_tw + N));
+        n += runs[i].n;
     }
-    // what K reads leave behind: the last address's result where a read leaves it
-    launch_copy(c, slice(res, K - 1), ref(c->d_res, G, 0), 1, ws);
-    c->memo_top = false;
-    c->d_last_res = c->d_res;
-    c->prep1_ready = false;
-    return FHERAM_OK;
-}
-// the K results, widened into h_bres by the device; out: [K][ws][GLWE] int64
-int read_batch_download(fheram_ctx* c, int K, int64_t* out) {
-    const size_t n = (size_t)K * c->ws * fheram_ctx::GLWE;
-    const int n4 = (int)(n / 4);
-    hipLaunchKernelGGL(k_export_i64, dim3((n4 + 255) / 256), dim3(256), 0, c->stream, c->d_bres,
-                       reinterpret_cast<long long*>(c->d_h_bres), n4, reinterpret_cast<const long long*>(c->d_tw + N));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
     c->wide_unsynced = false;
     double m;
-    std::memcpy(&m, c->h_bres + n, 8);
+    std::memcpy(&m, h + n, 8);
     if (c->monitor && m > MON_LIMIT) __atomic_store_n(c->h_ro_flag, 1u, __ATOMIC_RELAXED);
     const int rc = check_precision(c);
-    if (rc != FHERAM_OK) return rc;
-    std::memcpy(out, c->h_bres, n * sizeof(int64_t));
-    return FHERAM_OK;
+    if (rc == FHERAM_OK && out) std::memcpy(out, h, n * sizeof(int64_t));
+    return rc;
 }
 
-// Ram::write (ram.rs:226-294) in two stages.
+// Ram::write (ram.rs:226-294) of every address of the operand set, in two stages and a side stage.
 // Stage 1 (root / unsharded): write_first_step on the top of the tree and, for n2 == 2, the inverse
 // coordinate-1 products: leaves the un-rotated ct_lo of every sub-RAM in d_part.
-int write_top(fheram_ctx* c, const fheram_addr* addr) {
+int write_top(const Opnds& o) {
+    fheram_ctx* c = o.c;
     c->wide = true;             // (everything a write enqueues runs behind read_prepare_write's trace chain, whose placement releases the gate wave)
     const long G = (long)fheram_ctx::GLWE;
     const long sy = (long)c->rows * G;
-    const int ws = c->ws;
+    const int n = o.n, ws = o.ws, Y = o.Y();
     GlweRef wref = ref(c->d_w, G, 0), tmp = ref(c->d_tmp, G, 0), tmp2 = ref(c->d_tmp2, G, 0), tree = ref(c->d_tree, G, 0);
     // write_first_step (ram.rs:544-577): t <- normalize(t - trace(t) + w)
     GlweRef top = (c->n2 != 1) ? tree : ref(c->d_data, sy, 0);
     GlweRef tr = tmp;
     if (c->memo_top) tr = ref(c->d_trtop, G, 0);      // = trace(top), computed by read_prepare_write on this very ciphertext
-    else trace_steps(c, top, tmp, tmp2, 0, LOGN, 1, ws);
+    else trace_steps(c, top, tmp, tmp2, 0, LOGN, 1, Y);
     {
-        ProfScope ps(c, "elementwise", ws);
-        hipLaunchKernelGGL((k_sub_add_norm<3>), dim3(1, ws, EW_SLICES), dim3(256), 0, c->cur, top, tr, wref, top);
+        ProfScope ps(c, "elementwise", Y);
+        hipLaunchKernelGGL((k_sub_add_norm<3>), dim3(1, Y, EW_SLICES), dim3(256), 0, c->cur, top, tr, wref, top);
     }
     c->memo_top = false;
     if (c->n2 == 2) {
-        if (c->inv_id[1] == addr->id) wait_inverse(c, c->stream, 1);                   // started by read_prepare_write
+        // the head: per address, the inverse of coordinate 1 (ram.rs:260-271) and its products on the address's tree top (ram.rs:610)
+        if (n == 1 && c->inv_id[1] == o.addrs[0]->id) wait_inverse(c, c->stream, 1);    // started by read_prepare_write
         else {
             // another address (or new keys): a precompute that read_prepare_write started for ITS address may still be
-            // writing prep_inv_of(c, 1) on the side stream — the main stream must not overtake it
-            if (c->inv_pending[1]) wait_inverse(c, c->stream, 1);
-            coordinate_prepare_inv(c, addr, 1, c->d_ggsw_tmp, prep_inv_of(c, 1));     // ram.rs:260-271
+            // writing d_prep_inv on the side stream — the main stream must not overtake it
+            if (n == 1 && c->inv_pending[1]) wait_inverse(c, c->stream, 1);
+            for (int k = 0; k < n; k++) coordinate_prepare_inv(c, o.addrs[k], 1, c->d_ggsw_tmp, o.inv(k, 1));   // ram.rs:260-271
         }
-        c->inv_pending[1] = false;
-        c->inv_id[1] = 0;
-        ep_chain(c, tree, ref(c->d_part, G, 0), tmp, prep_inv_of(c, 1), (int)c->base2d[1].size(), 1, ws);   // ram.rs:610: the un-rotated ct_lo, in d_part
+        if (n == 1) { c->inv_pending[1] = false; c->inv_id[1] = 0; }
+        for (int k = 0; k < n; k++)                                                        // ram.rs:610: the un-rotated ct_lo, in d_part
+            ep_chain(c, o.slice(tree, k), o.slice(ref(c->d_part, G, 0), k), o.slice(tmp, k), o.inv(k, 1), (int)c->base2d[1].size(), 1, ws);
         // tree[0] <- ct_lo * X^-rows (ram.rs:629, `rows` rotations by X^-1): nothing in this write reads it again, so
         // the rotation is enqueued behind the rows' work (write_rows) instead of in front of it
         c->tree_rotate_pending = true;
@@ -343,29 +345,29 @@ int write_top(fheram_ctx* c, const fheram_addr* addr) {
 // (ram.rs:616) and the inverse of coordinate 0 (ram.rs:278-289).  It is enqueued on the side stream
 // so that it fills the CUs the latency-bound stage 1 (a chain of word_size-ciphertext launches)
 // leaves idle.
-void write_side_begin(fheram_ctx* c, const fheram_addr* addr) {
+void write_side_begin(const Opnds& o) {
+    fheram_ctx* c = o.c;
     c->wide = true;
     const long G = (long)fheram_ctx::GLWE;
     const long sy = (long)c->rows * G;
     hipEventRecord(c->ev_fork, c->stream);            // everything before this write (rows after rpw)
     hipStreamWaitEvent(c->stream2, c->ev_fork, 0);
     c->cur = c->stream2;
-    if (c->n2 == 2) {
+    if (c->n2 == 2) {                                 // every row of every address: ONE chain
         c->d_trhi = c->d_scrA;
         if (c->memo_alone > 0) {   // arena A = the rows after trace steps 0 .. memo_alone-1 (left there by read_prepare_write)
             // ping-pong A <-> C; an odd number of remaining steps ends in C
             if ((LOGN - c->memo_alone) % 2 == 1) c->d_trhi = c->d_scrC;
             int32_t* tmp = c->d_trhi == c->d_scrA ? c->d_scrC : c->d_scrA;
-            trace_steps(c, ref(c->d_scrA, sy, G), ref(c->d_trhi, sy, G), ref(tmp, sy, G), c->memo_alone, LOGN, (int)c->rows, c->ws);
+            trace_steps(c, ref(c->d_scrA, sy, G), ref(c->d_trhi, sy, G), ref(tmp, sy, G), c->memo_alone, LOGN, (int)c->rows, o.Y());
         } else {
-            trace_steps(c, ref(c->d_data, sy, G), ref(c->d_scrA, sy, G), ref(c->d_scrC, sy, G), 0, LOGN, (int)c->rows, c->ws);
+            trace_steps(c, ref(c->d_data, sy, G), ref(c->d_scrA, sy, G), ref(c->d_scrC, sy, G), 0, LOGN, (int)c->rows, o.Y());
         }
         c->memo_alone = 0;
     }
-    if (c->inv_id[0] == addr->id) wait_inverse(c, c->stream2, 0);   // started by read_prepare_write (on this very stream)
-    else coordinate_prepare_inv(c, addr, 0, c->d_ggsw_tmp2, prep_inv_of(c, 0));   // (a precompute for another address sits on this very stream: ordered)
-    c->inv_id[0] = 0;
-    c->inv_pending[0] = false;
+    if (o.n == 1 && c->inv_id[0] == o.addrs[0]->id) wait_inverse(c, c->stream2, 0);   // started by read_prepare_write (on this very stream)
+    else for (int k = 0; k < o.n; k++) coordinate_prepare_inv(c, o.addrs[k], 0, c->d_ggsw_tmp2, o.inv(k, 0));   // (a precompute for another address sits on this very stream: ordered)
+    if (o.n == 1) { c->inv_id[0] = 0; c->inv_pending[0] = false; }
     hipEventRecord(c->ev_join, c->stream2);
     c->cur = c->stream;
     c->side_begun = true;
@@ -378,45 +380,41 @@ void write_side_abort(fheram_ctx* c) {
     c->side_begun = false;
 }
 // Stage 2 (every shard): write_mid_step on the local rows given ct_lo (in d_part), then write_last_step.
-int write_rows(fheram_ctx* c, const fheram_addr* addr) {
+int write_rows(const Opnds& o) {
+    fheram_ctx* c = o.c;
     c->wide = true;
     const long G = (long)fheram_ctx::GLWE;
     const long sy = (long)c->rows * G;
-    const int ws = c->ws, R = (int)c->rows;
+    const int n = o.n, ws = o.ws, Y = o.Y(), R = (int)c->rows;
     GlweRef data = ref(c->d_data, sy, G), A = ref(c->d_scrA, sy, G), B = ref(c->d_scrB, sy, G), D = ref(c->d_scrD, sy, G);
-    GlweRef trhi = ref(c->d_trhi ? c->d_trhi : c->d_scrA, sy, G);
+    GlweRef trhi = ref(c->d_trhi ? c->d_trhi : c->d_scrA, sy, G), part = ref(c->d_part, G, 0);
     const int d0 = (int)c->base2d[0].size();
-    if (c->n2 == 2 && use_row_fuse(c, d0, LOGN, R, ws)) {
-        // trace(ct_lo * X^-row), normalize(ct_hi - trace(ct_hi) + that) and write_last_step's products as ONE launch (k_write_chain);
-        // it needs trace(ct_hi) and the inverse digits of coordinate 0 from the side stream at its start (that stream's chain holds
-        // every CU until then anyway)
+    const bool fuse = c->n2 == 2 && o.row_fuse(d0, LOGN, R);
+    if (fuse) {
+        // trace(ct_lo * X^-row), normalize(ct_hi - trace(ct_hi) + that) and write_last_step's products as ONE launch (k_write_chain; with a table:
+        // row y takes the inverse digits of address y / ws); it needs trace(ct_hi) and the inverse digits of coordinate 0 from the side stream at
+        // its start (that stream's chain holds every CU until then anyway)
         hipStreamWaitEvent(c->stream, c->ev_join, 0);
-        launch_write_chain(c, ref(c->d_part, G, 0), c->n_shards, c->shard, data, trhi, prep_inv_of(c, 0), d0, LOGN, R, ws);   // ram.rs:612-646
-        if (c->tree_rotate_pending) {   // root / unsharded: the tree's copy of ct_lo, rotated (see write_top)
-            ProfScope ps(c, "elementwise", ws);
-            hipLaunchKernelGGL((k_rotate<3>), dim3(1, ws, EW_SLICES), dim3(256), 0, c->cur, ref(c->d_part, G, 0), ref(c->d_tree, G, 0), -(int)c->rows_glob);
-            c->tree_rotate_pending = false;
-        }
-    } else {
-    if (c->n2 == 2)
-        trace_steps(c, ref(c->d_part, G, 0), B, D, 0, LOGN, R, ws, c->n_shards, c->shard);     // tmp_a = trace(ct_lo * X^-row)   ram.rs:621,629
+        launch_write_chain(c, part, c->n_shards, c->shard, data, trhi, o.inv(0, 0), d0, LOGN, R, Y, o.table());   // ram.rs:612-646
+    } else if (c->n2 == 2)
+        trace_steps(c, part, B, D, 0, LOGN, R, Y, c->n_shards, c->shard);                      // tmp_a = trace(ct_lo * X^-row)   ram.rs:621,629
     if (c->tree_rotate_pending) {   // root / unsharded: the tree's copy of ct_lo, rotated (see write_top)
-        ProfScope ps(c, "elementwise", ws);
-        hipLaunchKernelGGL((k_rotate<3>), dim3(1, ws, EW_SLICES), dim3(256), 0, c->cur, ref(c->d_part, G, 0), ref(c->d_tree, G, 0), -(int)c->rows_glob);
-        c->tree_rotate_pending = false;
+        ProfScope ps(c, "elementwise", Y);
+        hipLaunchKernelGGL((k_rotate<3>), dim3(1, Y, EW_SLICES), dim3(256), 0, c->cur, part, ref(c->d_tree, G, 0), -(int)c->rows_glob);
     }
-    hipStreamWaitEvent(c->stream, c->ev_join, 0);                                              // side stream: trace(ct_hi), inverse coordinate 0
-    if (c->n2 == 2) {
-        ProfScope ps(c, "elementwise", (uint64_t)R * ws);
-        hipLaunchKernelGGL((k_sub_add_norm<3>), dim3(R, ws, EW_SLICES), dim3(256), 0, c->cur, data, trhi, B, data);   // ram.rs:617,625-626
-    }
-    ep_chain(c, data, data, A, prep_inv_of(c, 0), d0, R, ws);                                         // ram.rs:644-646
+    if (!fuse) {
+        hipStreamWaitEvent(c->stream, c->ev_join, 0);                                          // side stream: trace(ct_hi), inverse coordinate 0
+        if (c->n2 == 2) {
+            ProfScope ps(c, "elementwise", (uint64_t)R * Y);
+            hipLaunchKernelGGL((k_sub_add_norm<3>), dim3(R, Y, EW_SLICES), dim3(256), 0, c->cur, data, trhi, B, data);   // ram.rs:617,625-626
+        }
+        for (int k = 0; k < n; k++) ep_chain(c, o.slice(data, k), o.slice(data, k), o.slice(A, k), o.inv(k, 0), d0, R, ws);   // ram.rs:644-646
     }
     // the next read_prepare_write's side work overwrites d_prep_inv: it is ordered behind this write by an event (the gate
-    // launch in front of that work is time-bounded, so it cannot be the only ordering)
-    if (!capturing(c)) { hipEventRecord(c->ev_wdone, c->stream); c->wdone_pending = true; }
+    // launch in front of that work is time-bounded, so it cannot be the only ordering); a table's inverse digits have no such reader
+    if (n == 1 && !capturing(c)) { hipEventRecord(c->ev_wdone, c->stream); c->wdone_pending = true; }
+    write_done(c);
     c->state = false;                                                                          // ram.rs:648
-    c->side_begun = false;
     return FHERAM_OK;
 }
 

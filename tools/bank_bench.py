@@ -224,6 +224,8 @@ def main():
     ap.add_argument("--worker", action="store_true")
     ap.add_argument("--baseline-lib", default=None, help="libfheram.so built from the parent commit (default: this tree's library, which "
                                                          "makes the baseline legs a self-comparison, recorded as such)")
+    ap.add_argument("--candidate-lib", default=None, help="library of the bank leg (default: this tree's); a parent build here measures the bank "
+                                                          "leg of that build, for comparing two builds' banks in one session")
     ap.add_argument("--log-max-addr", type=int, default=18)
     ap.add_argument("--members", default="1,2,4,8")
     ap.add_argument("--word-size", type=int, default=4)
@@ -234,7 +236,7 @@ def main():
     args = ap.parse_args()
     if args.worker:
         return worker_main()
-    base, cand = Remote(args.baseline_lib), Remote(None)
+    base, cand = Remote(args.baseline_lib), Remote(args.candidate_lib)
     result = {"tool": "tools/bank_bench.py", "log_max_addr": args.log_max_addr, "word_size": args.word_size, "reps": args.reps,
               "iters_per_rep": args.iters, "baseline_is_parent_build": bool(args.baseline_lib), "clock": "host perf_counter around synced ops",
               "spread": "p10..p90 of the repetitions of a leg over its median", "members": {}}
