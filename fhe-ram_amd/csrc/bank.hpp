@@ -62,7 +62,7 @@ Opnds bank_opnds(fheram_bank* b, const fheram_addr* const* addrs, int n) {
 int bank_check(fheram_bank* b, int first, int n, const fheram_addr* const* addrs, int want_state) {
     if (!b) return FHERAM_ERR_INVALID_ARG;
     fheram_ctx* c = b->c;
-    if (!c->mid && c->mid_saved && ++c->mid_off_ops >= 256) { c->mid = c->mid_saved; c->mid_saved = 0; c->mid_bad_windows = 0; c->mid_off_ops = 0; }   // (path.hpp check_common)
+    mid_rearm(c);
     if (first < 0 || n < 1 || first > b->M - n)
         return fail(c, FHERAM_ERR_INVALID_ARG, "member range [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") is empty or outside the bank's " + std::to_string(b->M) + " members");
     if (addrs) for (int k = 0; k < n; k++)

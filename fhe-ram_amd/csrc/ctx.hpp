@@ -121,7 +121,7 @@ struct fheram_ctx {
     unsigned mid_fb_mark = 0;
     int mid_bad_windows = 0, mid_saved = 0;          // auto-disable of the single-launch mid chains: consecutive bad windows; the setting to come back to
     uint64_t mid_window_cts = 0, mid_disabled_count = 0; // ciphertexts launched in the current window of 64 launches; times the path has been switched off
-    unsigned mid_off_ops = 0;                        // ops since then (re-armed after 256)
+    unsigned mid_off_ops = 0;                        // ops since then (re-armed after 256: launch.hpp mid_rearm)
     unsigned* h_mid_fb = nullptr;      // pinned, device-visible: ciphertexts redone, [0] main stream, [16] side stream
     unsigned* d_mid_sync[2] = {nullptr, nullptr};   // [64 groups][32] + [_, ciphertexts redone]: main / side stream
     double* d_mid_big[2] = {nullptr, nullptr};      // [step parity][ciphertext x RS <= 64] x BIG_STRIDE doubles: k_chain_mid's partial limb polynomials
@@ -166,7 +166,7 @@ struct fheram_ctx {
     int batch_cap = 0;
     int32_t* d_bA = nullptr;       // [K*ws][rows]  ping-pong arenas of the batch's rows
     int32_t* d_bB = nullptr;       // [K*ws][rows]
-    int32_t* d_bC = nullptr;       // [K*ws][rows]  stands in for the source a single-launch chain must leave intact (pack_levels); only when needed
+    int32_t* d_bC = nullptr;       // [K*ws][rows]  stands in for the source the tail launch must leave intact (pack_levels); only when needed (path.hpp batch_needs_third)
     int32_t* d_bres = nullptr;     // [K*ws]        the results
     int32_t* d_btmp = nullptr;     // [K*ws]
     int32_t* d_btmp2 = nullptr;    // [K*ws]

@@ -5,13 +5,34 @@
 
 namespace {
 
+// ---- naming a kernel instantiation ----------------------------------------------------------
+// f(sk): the limb count of the context's trace / packing keys as a compile-time constant (decltype(sk)::value)
+template <typename F>
+void with_evk(const fheram_ctx* c, F&& f) {
+    if (c->s_evk == 5) f(std::integral_constant<int, 5>{});
+    else f(std::integral_constant<int, 4>{});
+}
+// f(sk, w): decltype(w)::value also selects the 256-register variant of a chain kernel (`_w`), for a launch that can never meet the gate
+// wave (ctx.hpp wide); the context remembers that such a launch is under way (wide_unsynced)
+template <typename F>
+void with_evk_wide(fheram_ctx* c, bool wide, F&& f) {
+    if (wide) c->wide_unsynced = true;
+    with_evk(c, [&](auto sk) { if (wide) f(sk, std::true_type{}); else f(sk, std::false_type{}); });
+}
+// Under FHERAM_GRAPH=1 the enqueue functions run inside a stream capture: forked work has to be joined before the
+// capture ends, an event recorded inside one captured op cannot be waited on from another, and a launch that carries a
+// generation number (the single-launch chains) would replay it.
+bool capturing(const fheram_ctx* c) { return c->use_graph && !c->profile; }
+
 // ---- kernel launchers ---------------------------------------------------------------------
 constexpr int LIMB_SPLIT_MAX = 64;   // ciphertexts per launch the limb-parallel path is used for (at most)
 constexpr int EW_SLICES = 8;   // workgroups per ciphertext of the elementwise kernels (blockIdx.z)
 // One workgroup per ciphertext does the least work (no repeated forward transforms); splitting by
 // output column doubles the number of workgroups, which pays while the batch cannot fill the CUs.
-int pick_nco(const fheram_ctx* c, int gx, int gy) {
+// one_wg: the caller's launch takes one workgroup per ciphertext wherever the context leaves the choice (chain_form)
+int pick_nco(const fheram_ctx* c, int gx, int gy, bool one_wg = false) {
     if (c->nco != 0) return c->nco;
+    if (one_wg) return 2;
     return ((long)gx * gy * 2 <= c->cus) ? 1 : 2;
 }
 // gal != 0: automorphism key of Galois element gal, prepared as FFT(phi_gal(K)) (see k_prepare)
@@ -101,8 +122,7 @@ const double* trace_key(fheram_ctx* c, int i) { return c->d_atk + (size_t)i * c-
 // the automorphism family on RAM ciphertexts (3 limbs) with a trace key of the context's size (4 or 5 limbs)
 template <int MODE>
 void launch_ks_tr(fheram_ctx* c, const KsArgs& ka, int gx, int gy) {
-    if (c->s_evk == 5) launch_ks<MODE, 3, 5, 3>(c, ka, gx, gy);
-    else launch_ks<MODE, 3, 4, 3>(c, ka, gx, gy);
+    with_evk(c, [&](auto sk) { launch_ks<MODE, 3, decltype(sk)::value, 3>(c, ka, gx, gy); });
 }
 bool same(const GlweRef& a, const GlweRef& b) { return a.p == b.p; }
 
@@ -123,21 +143,77 @@ void run_chain(fheram_ctx* c, int n, GlweRef src, GlweRef dst, GlweRef tmp, int 
         cur = out;
     }
 }
-// Dependent chains on 9..64 ciphertexts (MAX_ADDR = 2^13 .. 2^16: the alone packer levels, the products of coordinate 0,
-// write_mid_step's traces): ONE launch with in-kernel hand-offs (k_chain_mid), followed by the fused chain launch that redoes
-// the ciphertexts whose group gave up (normally none).  Returns the split (0: not applicable; 1: <3,2>, 2: <1,1>, 3: <1,2>).
-int use_mid(const fheram_ctx* c, int n, int gx, int gy, int sk, bool ep = false) {
-    const long batch = (long)gx * gy;
-    if (!(c->mid && c->limb_split && n >= 2 && n <= CHAIN_MAX && batch > TAIL_GROUPS &&
-          c->cus >= TAIL_GROUPS * 32 &&      // the whole chip (8 XCDs x 32 CUs)
-          !(c->use_graph && !c->profile)))   // a captured launch would replay its generation number
-        return 0;
-    if (batch <= 16) return 1;
-    if (ep || c->mid < 2) return 0;          // the coarser splits: trace chains only
-    const int m1 = 2 * sk, m2 = sk;          // members of <1,1>, <1,2>
-    if (batch <= 8 * (32 / m1)) return 2;
-    if (batch <= 8 * (32 / m2)) return 3;
-    return 0;
+// ---- the launch form of a dependent chain -------------------------------------------------------
+// In which form n dependent steps on a (gx, gy) grid of ciphertexts run: THE one place that decides it.  The first that applies:
+//   Tail  (trace steps only) at most 8 ciphertexts, one per XCD — the latency-bound end of the path: ONE launch with in-kernel
+//         hand-offs (k_trace_tail), followed by the fused chain launch that only runs if that one gave up;
+//   Mid   9..64 ciphertexts (MAX_ADDR = 2^13 .. 2^16: the alone packer levels, the products of coordinate 0, write_mid_step's traces):
+//         ONE launch with in-kernel hand-offs (k_chain_mid, in the split `split`), followed by the fused chain launch that redoes
+//         the ciphertexts whose group gave up (normally none);
+//   Chain a batch large enough for the fused decomposition (one workgroup per ciphertext): ONE launch, the workgroup ping-pongs
+//         between its own slots of two buffers;
+//   Steps one launch (or launch pair) per step, each in the decomposition launch_ks / launch_ep choose for it.
+// Tail and Mid split by the batch size; Tail and Chain exclude each other too (whatever admits the tail also admits the limb
+// split, which Chain is the alternative to), so a chain that is in the Chain form would be so without the tail.
+// What a form needs of the caller's buffers is checked where it is launched (plan_chain).
+enum class ChainForm { Tail, Mid, Chain, Steps };
+struct ChainPlan {
+    ChainForm form;
+    int split;   // Mid: the template arguments of k_chain_mid (1: <3,2>, 2: <1,1>, 3: <1,2>)
+};
+struct ChainQuery {
+    bool ep;                // external products with an address's digits (4 key limbs); false: trace steps with the context's trace keys
+    int n, gx, gy;
+    bool rotated = false;   // the first step reads its input rotated (write path): nothing the tail launch can do
+    bool one_wg = false;    // a range of bank members: one workgroup per ciphertext unless the context forces a split (path.hpp Opnds::row_fuse)
+    bool handoff = true;    // false: without the forms that hand over inside the kernel (Tail, Mid) — what plan_chain asks when the buffers rule them out
+};
+ChainPlan chain_form(const fheram_ctx* c, const ChainQuery& q) {
+    const long batch = (long)q.gx * q.gy;
+    const int sk = q.ep ? 4 : c->s_evk;
+    const bool len = q.n >= 2 && q.n <= CHAIN_MAX;
+    const bool handoff = q.handoff && len && c->limb_split &&
+                         c->cus >= TAIL_GROUPS * 32 &&   // the whole chip (8 XCDs x 32 CUs): a partition could not hold the groups side by side
+                         !capturing(c);                  // a captured launch would replay its generation number
+    if (handoff && !q.ep && !q.rotated && c->tail && c->fine_split && batch <= TAIL_GROUPS &&
+        c->cur == c->stream &&   // every launch of a context shares d_tail_sync: main stream only
+        2 * sk * 3 <= 32)        // the workgroups of a ciphertext fit the 32 CUs of one XCD (24 with 4-limb keys, 30 with 5)
+        return {ChainForm::Tail, 0};
+    if (handoff && c->mid && batch > TAIL_GROUPS) {
+        if (batch <= 16) return {ChainForm::Mid, 1};
+        if (!q.ep && c->mid >= 2) {   // the coarser splits, of 2 * sk and sk members: trace chains only
+            if (batch <= 8 * (32 / (2 * sk))) return {ChainForm::Mid, 2};
+            if (batch <= 8 * (32 / sk)) return {ChainForm::Mid, 3};
+        }
+    }
+    if (len && c->chain && pick_nco(c, q.gx, q.gy, q.one_wg) == 2 && !use_limb_split(c, q.gx, q.gy, sk) &&
+        !use_fine_split(c, q.gx, q.gy, q.ep ? 2 * 4 * 2 * 3 : 2 * sk * 3))
+        return {ChainForm::Chain, 0};
+    return {ChainForm::Steps, 0};
+}
+// picks (b0, b1) for a chain src -> dst with scratch tmp such that the last step lands in dst (step i writes b[i & 1]); false when the
+// first step would have to write what it reads (src == dst and n odd)
+bool chain_bufs(int n, GlweRef src, GlweRef dst, GlweRef tmp, GlweRef (&b)[2]) {
+    if (n % 2 == 1) { if (same(src, dst)) return false; b[0] = dst; b[1] = tmp; }
+    else { b[0] = tmp; b[1] = dst; }
+    return !same(b[0], src);
+}
+// The form the chain src -> dst with scratch tmp takes: chain_form's, unless these buffers rule it out.  Tail: the source must survive
+// the launch (its fallback restarts from it), so neither buffer is the source; Mid: in place too (only the last step writes the
+// destination), but the first step must not write what it reads.  fits: b holds chain_bufs' choice (Chain without it: trace_steps, ep_chain).
+ChainPlan plan_chain(const fheram_ctx* c, ChainQuery q, GlweRef src, GlweRef dst, GlweRef tmp, GlweRef (&b)[2], bool& fits) {
+    fits = chain_bufs(q.n, src, dst, tmp, b);
+    ChainPlan p = chain_form(c, q);
+    if ((p.form == ChainForm::Tail && !(fits && !same(b[1], src))) || (p.form == ChainForm::Mid && !fits)) {
+        q.handoff = false;
+        p = chain_form(c, q);
+    }
+    return p;
+}
+// the single-launch mid chains, switched off because their launches kept giving up (fill_mid), are tried again 256 ops
+// later: a neighbour that held the CUs for a while does not cost the path its faster form for the context's life
+void mid_rearm(fheram_ctx* c) {
+    if (!c->mid && c->mid_saved && ++c->mid_off_ops >= 256) { c->mid = c->mid_saved; c->mid_saved = 0; c->mid_bad_windows = 0; c->mid_off_ops = 0; }
 }
 template <bool EP>
 void fill_mid(fheram_ctx* c, MidArgs& ma, GlweRef src, GlweRef dst, int n, int gx, int gy) {
@@ -149,7 +225,7 @@ void fill_mid(fheram_ctx* c, MidArgs& ma, GlweRef src, GlweRef dst, int n, int g
     // ciphertexts it had to redo into a pinned host word (read without a synchronisation: a stale value only delays the
     // decision by a window).  A WINDOW is 64 launches; it is bad when more than a quarter of the ciphertexts launched in it
     // (counted, both streams) were redone.  One contended launch does not switch the path off, two bad windows in a row do
-    // (fheram_mid_state); 256 ops later (path.hpp) the single-launch form is tried again.
+    // (fheram_mid_state); 256 ops later (mid_rearm) the single-launch form is tried again.
     c->mid_window_cts += (uint64_t)(gx * gy);
     if (!c->mid_test && c->mid_launches - c->mid_launch_mark >= 64) {
         const unsigned fb = __atomic_load_n(c->h_mid_fb, __ATOMIC_RELAXED) + __atomic_load_n(c->h_mid_fb + 16, __ATOMIC_RELAXED);
@@ -181,13 +257,11 @@ void launch_mid_trace(fheram_ctx* c, GlweRef src, const GlweRef (&b)[2], int sta
     ca.buf[0] = b[0]; ca.buf[1] = b[1]; ca.n = n;
     ca.done = ma.sync; ca.done_seq = ma.seq; ca.host_count = c->h_mid_fb + (c->cur == c->stream2 ? 16 : 0);
     for (int i = 0; i < n; i++) { ma.opnd[i] = ca.key[i] = trace_key(c, start + i); ma.ginv[i] = ca.ginv[i] = galois_inv_mod(galois_mod(c->gal[start + i])); }
-    if (c->s_evk == 5) {
-        if (split == 1) launch_k_mid_trace<5, 3, 2>(c, ma); else if (split == 2) launch_k_mid_trace<5, 1, 1>(c, ma); else launch_k_mid_trace<5, 1, 2>(c, ma);
-        hipLaunchKernelGGL((k_keyswitch_chain<3, 5, 3>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ca);
-    } else {
-        if (split == 1) launch_k_mid_trace<4, 3, 2>(c, ma); else if (split == 2) launch_k_mid_trace<4, 1, 1>(c, ma); else launch_k_mid_trace<4, 1, 2>(c, ma);
-        hipLaunchKernelGGL((k_keyswitch_chain<3, 4, 3>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ca);
-    }
+    with_evk(c, [&](auto sk) {
+        constexpr int SK = decltype(sk)::value;
+        if (split == 1) launch_k_mid_trace<SK, 3, 2>(c, ma); else if (split == 2) launch_k_mid_trace<SK, 1, 1>(c, ma); else launch_k_mid_trace<SK, 1, 2>(c, ma);
+        hipLaunchKernelGGL((k_keyswitch_chain<3, SK, 3>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ca);
+    });
 }
 void launch_mid_ep(fheram_ctx* c, GlweRef src, const GlweRef (&b)[2], const double* prep, int d, int gx, int gy) {
     ProfScope ps(c, "ext_product", (uint64_t)gx * gy, d);
@@ -201,19 +275,6 @@ void launch_mid_ep(fheram_ctx* c, GlweRef src, const GlweRef (&b)[2], const doub
     hipLaunchKernelGGL((k_chain_mid<true, 4, 3, 2>), dim3(8 * 2 * 12), dim3(T), LDS_BYTES, c->cur, ma);
     hipLaunchKernelGGL((k_ext_product_chain<3, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ca);
 }
-// A dependent chain of n fused steps on the same ciphertexts runs as ONE launch when the batch is large enough
-// for the fused decomposition (one workgroup per ciphertext): the workgroup ping-pongs between its own slots
-// of two buffers.  bufs: step i writes b[i & 1]; b[0] must not be the source.
-bool use_chain(const fheram_ctx* c, int n, int gx, int gy, int sk) {
-    return c->chain && n >= 2 && n <= CHAIN_MAX && c->nco != 1 && !use_limb_split(c, gx, gy, sk) && pick_nco(c, gx, gy) == 2;
-}
-// picks (b0, b1) for a chain src -> dst with scratch tmp such that the last step lands in dst; false when the
-// first step would have to write what it reads (src == dst and n odd)
-bool chain_bufs(int n, GlweRef src, GlweRef dst, GlweRef tmp, GlweRef (&b)[2]) {
-    if (n % 2 == 1) { if (same(src, dst)) return false; b[0] = dst; b[1] = tmp; }
-    else { b[0] = tmp; b[1] = dst; }
-    return !same(b[0], src);
-}
 void launch_ep_chain(fheram_ctx* c, GlweRef src, const GlweRef (&b)[2], const double* prep, int d, int gx, int gy) {
     ProfScope ps(c, "ext_product", (uint64_t)gx * gy, d);
     ProfScope pf(c, "ext_product_fused", (uint64_t)gx * gy, d);
@@ -226,18 +287,16 @@ void launch_ep_chain(fheram_ctx* c, GlweRef src, const GlweRef (&b)[2], const do
 // CoordinatePrepared::product / product_inplace (coordinate_prepared.rs:147-177): d external products.
 void ep_chain(fheram_ctx* c, GlweRef src, GlweRef dst, GlweRef tmp, const double* prep, int d, int gx, int gy) {
     if (gx <= 0 || gy <= 0) return;
-    if (use_mid(c, d, gx, gy, 4, true)) {
-        GlweRef b[2];   // in place too (read_prepare_write): only the last step writes the destination
-        if (chain_bufs(d, src, dst, tmp, b)) { launch_mid_ep(c, src, b, prep, d, gx, gy); return; }
-    }
-    if (use_chain(c, d, gx, gy, 4) && !use_fine_split(c, gx, gy, 2 * 4 * 2 * 3)) {
-        GlweRef b[2];
-        if (chain_bufs(d, src, dst, tmp, b)) { launch_ep_chain(c, src, b, prep, d, gx, gy); return; }
-        if (chain_bufs(d, src, tmp, dst, b)) {   // src == dst, d odd: finish in tmp, copy back
-            launch_ep_chain(c, src, b, prep, d, gx, gy);
-            launch_copy(c, tmp, dst, gx, gy);
-            return;
-        }
+    GlweRef b[2];
+    bool fits;
+    switch (plan_chain(c, ChainQuery{true, d, gx, gy}, src, dst, tmp, b, fits).form) {
+    case ChainForm::Mid: launch_mid_ep(c, src, b, prep, d, gx, gy); return;   // in place too (read_prepare_write)
+    case ChainForm::Chain:
+        if (!fits && !chain_bufs(d, src, tmp, dst, b)) break;   // (src == dst, d odd: finish in tmp, copy back)
+        launch_ep_chain(c, src, b, prep, d, gx, gy);
+        if (!fits) launch_copy(c, tmp, dst, gx, gy);
+        return;
+    default: break;
     }
     run_chain(c, d, src, dst, tmp, gx, gy, [&](int i, GlweRef in, GlweRef out) { launch_ep(c, in, out, prep + (size_t)i * fheram_ctx::GGSW, gx, gy); });
 }
@@ -250,28 +309,32 @@ void launch_trace_chain(fheram_ctx* c, GlweRef src, const GlweRef (&b)[2], int s
     ca.buf[0] = b[0]; ca.buf[1] = b[1]; ca.n = n;
     for (int i = 0; i < n; i++) { ca.key[i] = trace_key(c, start + i); ca.ginv[i] = galois_inv_mod(galois_mod(c->gal[start + i])); }
     const int yf = n >= 2 ? c->chain_y : 0;   // intermediates handed over as Y = ceil(A/2) through LDS and registers (ks_trace_l); 0: int32 limbs (ks_run)
-    if (c->s_evk == 5) {
-        if (yf && c->wide) { c->wide_unsynced = true; hipLaunchKernelGGL((k_keyswitch_chain_w<3, 5, 3, 3>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ca); }
-        else if (yf) hipLaunchKernelGGL((k_keyswitch_chain<3, 5, 3, 3>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ca);
-        else hipLaunchKernelGGL((k_keyswitch_chain<3, 5, 3>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ca);
-    } else {
-        if (yf && c->wide) { c->wide_unsynced = true; hipLaunchKernelGGL((k_keyswitch_chain_w<3, 4, 3, 3>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ca); }
-        else if (yf) hipLaunchKernelGGL((k_keyswitch_chain<3, 4, 3, 3>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ca);
-        else hipLaunchKernelGGL((k_keyswitch_chain<3, 4, 3>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ca);
-    }
+    with_evk_wide(c, yf && c->wide, [&](auto sk, auto w) {
+        constexpr int SK = decltype(sk)::value;
+        if (!yf) hipLaunchKernelGGL((k_keyswitch_chain<3, SK, 3>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ca);
+        else if constexpr (decltype(w)::value) hipLaunchKernelGGL((k_keyswitch_chain_w<3, SK, 3, 3>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ca);
+        else hipLaunchKernelGGL((k_keyswitch_chain<3, SK, 3, 3>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ca);
+    });
 }
 // The operand table of a launch over several addresses (path.hpp Opnds::table): gy = n * ws ciphertexts, ciphertext y takes the prepared
 // digits of address y / ws, which are `stride` elements apart from prep on, and reads a rows source at y mod src_rows (ws: every address reads
 // the same rows, fheram_read_batch; n * ws: its own, a bank range).  ws == 0: one address, no table (the kernels without one).
 // src_rows is read by launch_read_chain only: the write chain and the tail's fallback always run on rows of their own (y mod gy).
 struct OpndTable { int ws = 0; long stride = 0; int src_rows = 0; };
-// The two chains a row goes through back to back as ONE launch (k_read_chain / k_write_chain): both must be in the fused,
-// one-workgroup-per-ciphertext regime, in the forms that hand over through LDS and registers.
-bool use_row_fuse(const fheram_ctx* c, int d, int n_tr, int gx, int gy) {
-    return c->fuse && c->chain_y == 3 && d >= 2 && d <= CHAIN_MAX && n_tr >= 2 && n_tr <= CHAIN_MAX &&
-           use_chain(c, d, gx, gy, 4) && !use_mid(c, d, gx, gy, 4, true) && !use_fine_split(c, gx, gy, 2 * 4 * 2 * 3) &&
-           use_chain(c, n_tr, gx, gy, c->s_evk) && !use_mid(c, n_tr, gx, gy, c->s_evk) && !use_fine_split(c, gx, gy, 2 * c->s_evk * 3) &&
-           !(c->use_graph && !c->profile);
+// The two chains a row goes through back to back as ONE launch (k_read_chain / k_write_chain): both must be in the Chain form
+// (chain_form: whether the trace chain's first step reads rotated input does not matter to it), in the variants that hand over through
+// LDS and registers.  one_wg: ChainQuery's.
+bool use_row_fuse(const fheram_ctx* c, int d, int n_tr, int gx, int gy, bool one_wg = false) {
+    return c->fuse && c->chain_y == 3 && !capturing(c) &&
+           chain_form(c, ChainQuery{true, d, gx, gy, false, one_wg}).form == ChainForm::Chain &&
+           chain_form(c, ChainQuery{false, n_tr, gx, gy, false, one_wg}).form == ChainForm::Chain;
+}
+// the arguments of a `_b` kernel: those of the row chain with the operand table behind them; row y reads the source at y mod src_rows
+RowChainBatchArgs with_table(const RowChainArgs& ra, const OpndTable& t, int src_rows) {
+    RowChainBatchArgs rb;
+    static_cast<RowChainArgs&>(rb) = ra;
+    rb.opnd_stride = t.stride; rb.ws = t.ws; rb.src_rows = src_rows;
+    return rb;
 }
 void fill_row_chain(fheram_ctx* c, RowChainArgs& ra, const double* prep, int d, int start, int n_tr) {
     ra.ep.tw = c->d_tw; ra.ep.n = d;
@@ -292,28 +355,18 @@ void launch_read_chain(fheram_ctx* c, GlweRef src, const GlweRef* ep_store, Glwe
     ra.ks.base = ks_args(c, dst, dst, dst, trace_key(c, 0), c->gal[0]);
     ra.ks.buf[0] = ra.ks.buf[1] = dst;                            // only the last step stores
     ra.hi = dst; ra.trhi = dst;
-    if (t.ws > 0) {
-        RowChainBatchArgs rb;
-        static_cast<RowChainArgs&>(rb) = ra;
-        rb.opnd_stride = t.stride; rb.ws = t.ws; rb.src_rows = t.src_rows;
-        const bool w = c->wide;
-        if (w) c->wide_unsynced = true;
-        if (c->s_evk == 5) {
-            if (w) hipLaunchKernelGGL((k_read_chain_bw<5, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
-            else hipLaunchKernelGGL((k_read_chain_b<5, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
+    with_evk_wide(c, c->wide, [&](auto sk, auto w) {
+        constexpr int SK = decltype(sk)::value;
+        constexpr bool W = decltype(w)::value;
+        if (t.ws > 0) {
+            const RowChainBatchArgs rb = with_table(ra, t, t.src_rows);
+            if constexpr (W) hipLaunchKernelGGL((k_read_chain_bw<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
+            else hipLaunchKernelGGL((k_read_chain_b<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
         } else {
-            if (w) hipLaunchKernelGGL((k_read_chain_bw<4, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
-            else hipLaunchKernelGGL((k_read_chain_b<4, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
+            if constexpr (W) hipLaunchKernelGGL((k_read_chain_w<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ra);
+            else hipLaunchKernelGGL((k_read_chain<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ra);
         }
-        return;
-    }
-    if (c->s_evk == 5) {
-        if (c->wide) { c->wide_unsynced = true; hipLaunchKernelGGL((k_read_chain_w<5, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ra); }
-        else hipLaunchKernelGGL((k_read_chain<5, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ra);
-    } else {
-        if (c->wide) { c->wide_unsynced = true; hipLaunchKernelGGL((k_read_chain_w<4, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ra); }
-        else hipLaunchKernelGGL((k_read_chain<4, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ra);
-    }
+    });
 }
 // write: trace steps 0 .. n_tr-1 of ct_lo * X^-row (src, read rotated), data <- normalize(data - trhi + that), d products in place
 // with a table (a bank range: every member its own rows): row y takes the inverse digits of member y / t.ws (k_write_chain_b)
@@ -326,26 +379,13 @@ void launch_write_chain(fheram_ctx* c, GlweRef src, int rot_mul, int rot_base, G
     ra.hi = data; ra.trhi = trhi;
     ra.ep.src = data; ra.ep.buf[0] = ra.ep.buf[1] = data;         // only the last product stores: in place on the rows
     c->wide_unsynced = true;                                      // (k_write_chain takes the whole register file)
-    if (t.ws > 0) {
-        RowChainBatchArgs rb;
-        static_cast<RowChainArgs&>(rb) = ra;
-        rb.opnd_stride = t.stride; rb.ws = t.ws; rb.src_rows = gy;
-        if (c->s_evk == 5) hipLaunchKernelGGL((k_write_chain_b<5, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
-        else hipLaunchKernelGGL((k_write_chain_b<4, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
-        return;
-    }
-    if (c->s_evk == 5) hipLaunchKernelGGL((k_write_chain<5, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ra);
-    else hipLaunchKernelGGL((k_write_chain<4, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ra);
+    with_evk(c, [&](auto sk) {
+        constexpr int SK = decltype(sk)::value;
+        if (t.ws > 0) hipLaunchKernelGGL((k_write_chain_b<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, with_table(ra, t, gy));
+        else hipLaunchKernelGGL((k_write_chain<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ra);
+    });
 }
-// The latency-bound end of the path (at most 8 ciphertexts, one per XCD): n trace steps as ONE launch with in-kernel
-// hand-offs (k_trace_tail), followed by the fused chain launch that only runs if that one gave up.
-bool use_tail(const fheram_ctx* c, int n, int gx, int gy) {
-    return c->tail && c->limb_split && c->fine_split && n >= 2 && n <= CHAIN_MAX && (long)gx * gy <= TAIL_GROUPS &&
-           c->cur == c->stream &&            // every launch of a context shares d_tail_sync: main stream only
-           2 * c->s_evk * 3 <= 32 &&         // the workgroups of a ciphertext fit the 32 CUs of one XCD (24 with 4-limb keys, 30 with 5)
-           c->cus >= TAIL_GROUPS * 32 &&     // the whole chip (8 XCDs x 32 CUs): a partition could not hold the groups side by side
-           !(c->use_graph && !c->profile);   // a captured launch would replay its generation number
-}
+// The Tail form of a trace chain (chain_form): n trace steps as ONE launch with in-kernel hand-offs (k_trace_tail) and its fallback launch.
 // prep != nullptr (round 6): the d external products with the prepared digits at `prep` run in front of the trace chain in the SAME launch
 // (coordinate 1's products, ram.rs:454 / 525-527): src -> products -> ep_out -> trace -> b[(n - 1) & 1]; store_ep: the caller needs ep_out
 // afterwards (read_prepare_write's tree[0]).  The fallback launch is then the fused row chain (k_read_chain), predicated likewise.
@@ -381,56 +421,41 @@ void launch_trace_tail(fheram_ctx* c, GlweRef src, const GlweRef (&b)[2], int st
         ra.hi = ra.trhi = b[(n - 1) & 1];
         ra.ks.pred = ca.pred; ra.ks.pred_seq = ca.pred_seq; ra.ks.host_count = ca.host_count;
     }
-    if (t.ws > 0 && ta.n_ep) {
-        TailBatchArgs tb;
-        static_cast<TailArgs&>(tb) = ta;
-        tb.opnd_stride = t.stride; tb.ws = t.ws;
-        RowChainBatchArgs rb;
-        static_cast<RowChainArgs&>(rb) = ra;
-        rb.opnd_stride = t.stride; rb.ws = t.ws; rb.src_rows = gx * gy;   // the source is the batch's own: row y is y
-        if (c->s_evk == 5) {
-            hipLaunchKernelGGL((k_trace_tail_b<3, 5, 3>), dim3(TAIL_GROUPS * 2 * 5 * 3), dim3(T), LDS_BYTES, c->cur, tb);
-            hipLaunchKernelGGL((k_read_chain_b<5, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
-        } else {
-            hipLaunchKernelGGL((k_trace_tail_b<3, 4, 3>), dim3(TAIL_GROUPS * 2 * 4 * 3), dim3(T), LDS_BYTES, c->cur, tb);
-            hipLaunchKernelGGL((k_read_chain_b<4, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
+    with_evk(c, [&](auto sk) {
+        constexpr int SK = decltype(sk)::value;
+        const dim3 groups(TAIL_GROUPS * 2 * SK * 3);
+        if (t.ws > 0 && ta.n_ep) {
+            TailBatchArgs tb;
+            static_cast<TailArgs&>(tb) = ta;
+            tb.opnd_stride = t.stride; tb.ws = t.ws;
+            hipLaunchKernelGGL((k_trace_tail_b<3, SK, 3>), groups, dim3(T), LDS_BYTES, c->cur, tb);
+            hipLaunchKernelGGL((k_read_chain_b<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, with_table(ra, t, gx * gy));   // the source is the batch's own: row y is y
+            return;
         }
-        return;
-    }
-    if (c->s_evk == 5) {
-        hipLaunchKernelGGL((k_trace_tail<3, 5, 3>), dim3(TAIL_GROUPS * 2 * 5 * 3), dim3(T), LDS_BYTES, c->cur, ta);
-        if (ta.n_ep) hipLaunchKernelGGL((k_read_chain<5, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ra);
-        else hipLaunchKernelGGL((k_keyswitch_chain<3, 5, 3>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ca);
-    } else {
-        hipLaunchKernelGGL((k_trace_tail<3, 4, 3>), dim3(TAIL_GROUPS * 2 * 4 * 3), dim3(T), LDS_BYTES, c->cur, ta);
-        if (ta.n_ep) hipLaunchKernelGGL((k_read_chain<4, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ra);
-        else hipLaunchKernelGGL((k_keyswitch_chain<3, 4, 3>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ca);
-    }
+        hipLaunchKernelGGL((k_trace_tail<3, SK, 3>), groups, dim3(T), LDS_BYTES, c->cur, ta);
+        if (ta.n_ep) hipLaunchKernelGGL((k_read_chain<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ra);
+        else hipLaunchKernelGGL((k_keyswitch_chain<3, SK, 3>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ca);
+    });
 }
 // GLWE::trace(start, end): step i = rsh(1) then a += phi_{g_i}(KS(a)).
 // The first step may read its input rotated by X^-(x*rot_mul) (write path, ram.rs:621,629).
 void trace_steps(fheram_ctx* c, GlweRef src, GlweRef dst, GlweRef tmp, int start, int end, int gx, int gy, int rot_mul = 0, int rot_base = 0) {
     if (gx <= 0 || gy <= 0) return;
     const int n = end - start;
-    if (rot_mul == 0 && rot_base == 0 && use_tail(c, n, gx, gy)) {
-        // the source must survive the launch (its fallback restarts from it): out of place only
-        GlweRef b[2];
-        if (chain_bufs(n, src, dst, tmp, b) && !same(b[1], src)) { launch_trace_tail(c, src, b, start, n, gx, gy); return; }
+    GlweRef b[2];
+    bool fits;
+    const ChainPlan p = plan_chain(c, ChainQuery{false, n, gx, gy, rot_mul != 0 || rot_base != 0}, src, dst, tmp, b, fits);
+    switch (p.form) {
+    case ChainForm::Tail: launch_trace_tail(c, src, b, start, n, gx, gy); return;
+    case ChainForm::Mid: launch_mid_trace(c, src, b, start, n, gx, gy, rot_mul, rot_base, p.split); return;
+    case ChainForm::Chain:
+        if (!fits && !chain_bufs(n, src, tmp, dst, b)) break;   // (src == dst, n odd: finish in tmp, copy back)
+        launch_trace_chain(c, src, b, start, n, gx, gy, rot_mul, rot_base);
+        if (!fits) launch_copy(c, tmp, dst, gx, gy);
+        return;
+    case ChainForm::Steps: break;
     }
-    if (const int split = use_mid(c, n, gx, gy, c->s_evk)) {
-        GlweRef b[2];
-        if (chain_bufs(n, src, dst, tmp, b)) { launch_mid_trace(c, src, b, start, n, gx, gy, rot_mul, rot_base, split); return; }
-    }
-    if (use_chain(c, n, gx, gy, c->s_evk) && !use_fine_split(c, gx, gy, 2 * c->s_evk * 3)) {
-        GlweRef b[2];
-        if (chain_bufs(n, src, dst, tmp, b)) { launch_trace_chain(c, src, b, start, n, gx, gy, rot_mul, rot_base); return; }
-        if (chain_bufs(n, src, tmp, dst, b)) {
-            launch_trace_chain(c, src, b, start, n, gx, gy, rot_mul, rot_base);
-            launch_copy(c, tmp, dst, gx, gy);
-            return;
-        }
-    }
-    run_chain(c, end - start, src, dst, tmp, gx, gy, [&](int i, GlweRef in, GlweRef out) {
+    run_chain(c, n, src, dst, tmp, gx, gy, [&](int i, GlweRef in, GlweRef out) {
         KsArgs ka = ks_args(c, in, in, out, trace_key(c, start + i), c->gal[start + i], 0, i == 0 ? rot_mul : 0, i == 0 ? rot_base : 0);
         launch_ks_tr<KS_TRACE>(c, ka, gx, gy);
     });
@@ -450,39 +475,14 @@ int32_t* pack_levels(fheram_ctx* c, int32_t* src, int32_t* A, int32_t* B, long s
     const int k = ilog2_ceil(count);
     int32_t* cur = src;
     auto other = [&](int32_t* x) { return x == A ? B : A; };
-    if (keep_alone && n_alone > 0 && count > 0) {
-        // src -> ... -> A in n_alone out-of-place steps between A and B (src is neither)
-        trace_steps(c, ref(src, sy, sx), ref(A, sy, sx), ref(B, sy, sx), 0, n_alone, (int)count, gy);
-        cur = A;
-    } else
-    if (count > 0 && use_tail(c, n_alone, (int)count, gy) && (other(other(cur)) != cur || (P0 && P0 != cur))) {
-        // at most 8 leaves (MAX_ADDR = 2^13): the single-launch trace chain of the tail.  Its source must survive the launch
-        // (the fallback restarts from it): when the leaves sit in one of the arenas the third one (P0) stands in for it
-        int32_t* b0 = other(cur);
-        int32_t* b1 = other(b0) != cur ? other(b0) : P0;
-        const GlweRef b[2] = {ref(b0, sy, sx), ref(b1, sy, sx)};
-        launch_trace_tail(c, ref(cur, sy, sx), b, 0, n_alone, (int)count, gy);
-        cur = ((n_alone - 1) & 1) ? b1 : b0;
-    } else
-    if (count > 0 && use_mid(c, n_alone, (int)count, gy, c->s_evk)) {
-        int32_t* b0 = other(cur);
+    if (n_alone > 0 && count > 0) {
+        // the alone levels, step i into b[i & 1]: the leaves' own arena is the second buffer when they sit in A or B — except for the Tail
+        // form (at most 8 leaves, MAX_ADDR = 2^13), whose source must survive the launch: the third arena (P0) stands in for it there
+        int32_t* b0 = other(src);
         int32_t* b1 = other(b0);
-        const GlweRef b[2] = {ref(b0, sy, sx), ref(b1, sy, sx)};
-        launch_mid_trace(c, ref(cur, sy, sx), b, 0, n_alone, (int)count, gy, 0, 0, use_mid(c, n_alone, (int)count, gy, c->s_evk));
-        cur = ((n_alone - 1) & 1) ? b1 : b0;
-    } else
-    if (count > 0 && use_chain(c, n_alone, (int)count, gy, c->s_evk) && !use_fine_split(c, (int)count, gy, 2 * c->s_evk * 3)) {
-        int32_t* b0 = other(cur);
-        int32_t* b1 = other(b0);
-        const GlweRef b[2] = {ref(b0, sy, sx), ref(b1, sy, sx)};
-        launch_trace_chain(c, ref(cur, sy, sx), b, 0, n_alone, (int)count, gy, 0, 0);
-        cur = ((n_alone - 1) & 1) ? b1 : b0;
-    } else
-    for (int i = 0; i < n_alone; i++) {
-        int32_t* nxt = other(cur);
-        KsArgs ka = ks_args(c, ref(cur, sy, sx), ref(cur, sy, sx), ref(nxt, sy, sx), trace_key(c, i), c->gal[i]);
-        launch_ks_tr<KS_TRACE>(c, ka, (int)count, gy);
-        cur = nxt;
+        if (b1 == src && P0 && P0 != src && chain_form(c, ChainQuery{false, n_alone, (int)count, gy}).form == ChainForm::Tail) b1 = P0;
+        cur = keep_alone ? A : ((n_alone - 1) & 1) ? b1 : b0;   // keep_alone: src is neither A nor B
+        trace_steps(c, ref(src, sy, sx), ref(cur, sy, sx), ref(cur == b0 ? b1 : b0, sy, sx), 0, n_alone, (int)count, gy);
     }
     size_t live = count;
     for (int m = 0; m < k; m++) {
@@ -534,9 +534,6 @@ void coordinate_prepare_inv(fheram_ctx* c, const fheram_addr* addr, int ci, int3
     launch_prepare(c, tmp, prep, d * (int)(fheram_ctx::GGSW / N));
 }
 
-// Under FHERAM_GRAPH=1 the enqueue functions run inside a stream capture: forked work has to be joined before the
-// capture ends, and an event recorded inside one captured op cannot be waited on from another.
-bool capturing(const fheram_ctx* c) { return c->use_graph && !c->profile; }
 // read_prepare_write: start the inverse digits of coordinate ci on the side stream (they depend on the address and the
 // keys only), behind everything enqueued on the main stream so far; Ram::write picks them up through ev_inv[ci].
 // fork == false: behind what the side stream already holds (the other coordinate): one event record on the main stream

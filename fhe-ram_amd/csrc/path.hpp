@@ -2,23 +2,11 @@
 // ONE read sequence (read_local + read_top, together read_impl) and ONE write sequence (write_side_begin, write_top, write_rows), over an
 // operand set (Opnds: whose digits a product uses) and, for reads, an arena set (ReadArenas: where it runs).  The plain context, the stages of
 // a row-sharded RAM (fheram.hip, group.hpp), fheram_read_batch and fheram_bank_* (bank.hpp) all run these; what is specific to one of them
-// is a visible condition in the sequence (n == 1: pre_inv, the gate wave, ev_opstart, ev_wdone, sharding, capture; a bank range: bank_row_fuse).
+// is a visible condition in the sequence (n == 1: pre_inv, the gate wave, ev_opstart, ev_wdone, sharding, capture; a bank range: Opnds::row_fuse).
 #pragma once
 #include "launch.hpp"
 
 namespace {
-
-// use_row_fuse for a range of bank members.  A lone context splits by column while rows * ws * 2 workgroups still fit the chip (pick_nco),
-// which rules the fused row chain out; for a range the alternative to the ONE launch with an operand table is not one column-split
-// launch per step but one per MEMBER and step, so the range takes one workgroup per ciphertext from the start.  (The smaller regimes —
-// limb split, fine split, the mid chains — keep their precedence inside use_row_fuse.)
-bool bank_row_fuse(fheram_ctx* c, int d, int n_tr, int gx, int gy) {
-    const int nco = c->nco;
-    if (nco == 0) c->nco = 2;
-    const bool fuse = use_row_fuse(c, d, n_tr, gx, gy);
-    c->nco = nco;
-    return fuse;
-}
 
 // One operation's OPERAND SET: n addresses of ws ciphertexts each (Y = n * ws; ciphertext y = k * ws + w is word w of address k).
 // n == 1 is the plain operation: the context's own digit slots, every `for k` loop below runs once and no launch takes a table.
@@ -38,8 +26,11 @@ struct Opnds {
     GlweRef slice(GlweRef r, int k) const { r.p += (long)k * ws * r.sy; return r; }   // address k's ws ciphertexts
     GlweRef rows(GlweRef r, int k) const { return own_rows ? slice(r, k) : r; }
     OpndTable table() const { return n == 1 ? OpndTable{} : OpndTable{ws, stride, own_rows ? Y() : ws}; }
-    // the fused row chain (k_read_chain / k_write_chain) for this operation: a bank range decides for itself, a batch as a lone context does
-    bool row_fuse(int d, int n_tr, int gx) const { return n > 1 && own_rows ? bank_row_fuse(c, d, n_tr, gx, Y()) : use_row_fuse(c, d, n_tr, gx, Y()); }
+    // The fused row chain (k_read_chain / k_write_chain) for this operation.  A lone context — and a batch like it — splits by column while
+    // rows * ws * 2 workgroups still fit the chip (pick_nco), which rules the chain out; for a range of bank members the alternative to the ONE
+    // launch with an operand table is not one column-split launch per step but one per MEMBER and step, so the range takes one workgroup
+    // per ciphertext from the start.  (The smaller regimes — limb split, fine split, the mid chains — keep their precedence: chain_form.)
+    bool row_fuse(int d, int n_tr, int gx) const { return use_row_fuse(c, d, n_tr, gx, Y(), n > 1 && own_rows); }
 };
 // the plain operation: one address (a = &addr), the context's d_prep / d_prep_inv, the context's word count (a bank view's range of one member)
 Opnds one_addr(fheram_ctx* c, const fheram_addr* const* a) { return Opnds{c, a, 1, c->ws, c->d_prep, c->d_prep_inv, 0, true}; }
@@ -98,10 +89,8 @@ int run_op(fheram_ctx* c, const fheram_addr* addr, int which, F&& enqueue) {
 }
 
 int check_common(fheram_ctx* c, const fheram_addr* addr) {
-    // the single-launch mid chains, switched off because their launches kept giving up (launch.hpp fill_mid), are tried again
-    // 256 ops later: a neighbour that held the CUs for a while does not cost the path its faster form for the context's life
-    if (c && !c->mid && c->mid_saved && ++c->mid_off_ops >= 256) { c->mid = c->mid_saved; c->mid_saved = 0; c->mid_bad_windows = 0; c->mid_off_ops = 0; }
     if (!c) return FHERAM_ERR_INVALID_ARG;
+    mid_rearm(c);
     if (!addr || addr->ctx != c) return fail(c, FHERAM_ERR_INVALID_ARG, "address does not belong to this context (layout mismatch, ram.rs:404)");
     if (!c->initialized) return fail(c, FHERAM_ERR_UNINITIALIZED, "unitialized memory: self.data.len()=0");
     if (!c->keys_loaded) return fail(c, FHERAM_ERR_KEYS, "evaluation keys not loaded");
@@ -171,7 +160,8 @@ int read_top(const Opnds& o, const ReadArenas& a, bool prepare_write, int32_t* g
     GlweRef last = pk;
     // coordinate 1's products inside the trace chain's launch (k_trace_tail's product steps): from two digits on (the fallback is the fused row chain)
     const int d1 = c->n2 == 2 ? (int)c->base2d[1].size() : 0;
-    const bool fuse_ep = c->n2 == 2 && c->tail_ep && d1 >= 2 && d1 <= TAIL_EP_MAX && use_tail(c, LOGN, 1, Y);
+    auto tail_top = [&] { return chain_form(c, ChainQuery{false, LOGN, 1, Y}).form == ChainForm::Tail; };   // the final trace: will it ask for the tail launch (as things stand now)
+    const bool fuse_ep = c->n2 == 2 && c->tail_ep && d1 >= 2 && d1 <= TAIL_EP_MAX && tail_top();
     GlweRef ep_out = ref(prepare_write ? c->d_tree : a.tmp2, G, 0);                       // read_prepare_write: tree[0] <- rotated packed row, ram.rs:525-527
     auto products1 = [&] { for (int k = 0; k < n; k++) ep_chain(c, o.slice(pk, k), o.slice(ep_out, k), o.slice(tmp, k), o.prep(k, 1), d1, 1, ws); };   // ram.rs:454 (not into res: the trace below runs out of place) / 525-527 + 502-504 (i = 1)
     if (c->n2 == 2) {
@@ -193,7 +183,7 @@ int read_top(const Opnds& o, const ReadArenas& a, bool prepare_write, int32_t* g
     // (only while the write's chains are one workgroup round on the chip: with several rounds — 2^21 on one GPU — the
     // earlier start of the write's main chain interleaves it with the side chain less favourably, write 8.57 -> 8.74 ms)
     const bool pre = n == 1 && prepare_write && c->pre_inv && (long)c->rows * c->ws <= c->cus;
-    const bool gated = pre && c->pre_inv == 1 && !capturing(c) && use_tail(c, LOGN, 1, ws);   // FHERAM_PRE_INV=2: event fork (A/B switch)
+    const bool gated = pre && c->pre_inv == 1 && !capturing(c) && tail_top();   // FHERAM_PRE_INV=2: event fork (A/B switch)
     if (pre && !gated)
         for (int ci = c->n2 - 1; ci >= 0; ci--) precompute_inverse(c, o.addrs[0], ci, ci == c->n2 - 1);   // coordinate 1 first: the write's head needs it first
     read_top_done(c, prepare_write);
@@ -244,10 +234,9 @@ void batch_free(fheram_ctx* c) {
 }
 // The third arena is only needed where the alone packer levels run as the single-launch tail chain on the batch's rows (at most
 // TAIL_GROUPS ciphertexts: 2^13 with K * ws <= 4), whose source must survive the launch (pack_levels P0): allocated only then.
+// (The very question pack_levels asks; the fused row chain, which would leave it no alone levels, excludes the Tail form: launch.hpp chain_form.)
 bool batch_needs_third(const fheram_ctx* c, int K) {
-    if (c->n2 != 2) return false;
-    const int R = (int)c->rows, Y = K * c->ws, L0 = LOGN - ilog2_ceil(c->rows_glob);
-    return !use_row_fuse(c, (int)c->base2d[0].size(), L0, R, Y) && L0 > 0 && use_tail(c, L0, R, Y);
+    return c->n2 == 2 && chain_form(c, ChainQuery{false, LOGN - ilog2_ceil(c->rows_glob), (int)c->rows, K * c->ws}).form == ChainForm::Tail;
 }
 // grows the batch buffers to K addresses (and adds the third arena when this batch needs it); on failure the context holds none of
 // them (and single reads are unaffected)

@@ -153,7 +153,8 @@ int fheram_roundoff_reset(fheram_ctx* ctx);
  * this is what an RCCL collective moves). */
 int fheram_ctx_create_sharded(const fheram_params* params, int device, int shard, int n_shards, fheram_ctx** out);
 
-/* Execution switches of a context: which decomposition / hand-over form the launchers of csrc/launch.hpp choose.  Every setting
+/* Execution switches of a context: which decomposition the launchers of csrc/launch.hpp choose for a step and which launch form
+ * (chain_form there) for a dependent chain.  Every setting
  * computes the same results (tests/test_gpu_parity.py and test_gpu_golden.py force each one); the defaults are the fastest
  * measured forms.  fheram_config_default() fills the library defaults and then applies the FHERAM_* environment overrides of
  * the same names (FHERAM_LIMB_SPLIT, _FINE_SPLIT, _MEMO, _PRE_INV, _TAIL, _TAIL_EP, _MID, _CHAIN, _CHAIN_Y, _PAIR_Z, _FUSE, _GRAPH,
