@@ -23,7 +23,7 @@ __global__ __launch_bounds__(T, T / 256) __attribute__((amdgpu_num_vgpr(FK_VG)))
         }
     }
     KsArgs ka = ca.base;
-    [[maybe_unused]] double vcarry[E];   // YF = 3: the body column's Y on its way from one step to the next
+    double vcarry[E];   // YF = 3: the body column's Y on its way from one step to the next
 #pragma unroll
     for (int k = 0; k < E; k++) vcarry[k] = 0.0;
 #pragma unroll 1

@@ -548,11 +548,6 @@ __device__ __forceinline__ void ntt_inv(double (&x)[B][E], const double* tw, dou
     if constexpr (B == 1) { double* const d[1] = {data}; fft_inv_skew<1, FENCE ? 1 : 0>(x, tw, d, tid); }
     else { double* const d[2] = {data, data + LDS_DATA}; fft_inv_skew<2, FENCE ? 1 : 0>(x, tw, d, tid); }
 }
-template <bool FENCE = true>
-__device__ __forceinline__ void ntt_inv2_skew(double (&x)[2][E], const double* tw, double* d0, double* d1, int tid) {
-    double* const d[2] = {d0, d1};
-    fft_inv_skew<2, FENCE ? 1 : 0>(x, tw, d, tid);
-}
 // the pairs of one limb loop (same two buffers every time, register work and operand loads in between): fenced by the free counter
 __device__ __forceinline__ void ntt_inv2_loop(double (&x)[2][E], const double* tw, double* d0, double* d1, int tid) {
     double* const d[2] = {d0, d1};
@@ -562,7 +557,6 @@ __device__ __forceinline__ void ntt_inv1_loop(double (&x)[1][E], const double* t
     double* const d[1] = {d0};
     fft_inv_skew<1, 2>(x, tw, d, tid);
 }
-__device__ __forceinline__ void ntt_fwd3_skew(double (&x)[3][E], const double* tw, double* data, int tid) { ntt_fwd<3>(x, tw, data, tid); }
 
 // copy the twiddle table (NC complex values) into LDS
 __device__ __forceinline__ void load_twiddles(double* tw_lds, const double* __restrict__ tw_g, int tid) {

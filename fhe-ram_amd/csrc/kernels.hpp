@@ -22,6 +22,13 @@
 // scaled by 1/n (n = N/2 complex points: the inverse transform's factor), stored so that thread t's
 // elements (2kk, 2kk+1) are one 16-byte word at [kk*T + t] (coalesced 16 B/lane loads).
 // Every kernel that rounds the output of an inverse transform constructs a RoMonitor (fft_dev.hpp) first.
+//
+// What a build can still switch (-D) measures what something costs; nothing here chooses between two implementations
+// (a decided experiment leaves the code, its write-up stays in HISTORY.md and profiles/):
+//   FK_STAMP (FK_STAMP_STEP, FK_STAMP_STEP_Y)                     in-kernel time stamps for tools/stamp_*.py
+//   FK_NO_OPERANDS, FK_HALF_OPERANDS, FK_NO_PROLOGUE_OPS          the operand stream left out (wrong results)
+//   FK_MONITOR=0 (fft_dev.hpp)                                    the round-off monitor left out
+//   FK_CHAIN_VGPRS                                                the chain kernels' register cap (the attribute wants a literal)
 #pragma once
 #include "fft_dev.hpp"
 #include <type_traits>
@@ -80,7 +87,7 @@ __device__ unsigned long long g_stamps[192];
         }                                                                                          \
         __builtin_amdgcn_sched_barrier(0);                                                         \
     } while (0)
-// ks_trace_y inside a chain launch: wave 0 of workgroup (0,0,0), step FK_STAMP_STEP of the chain
+// a step (ks_trace_l, ep_step_r, ep_run) inside a chain launch: wave 0 of workgroup (0,0,0), step FK_STAMP_STEP of the chain
 #define YSTAMP(i)                                                                                  \
     do {                                                                                           \
         __builtin_amdgcn_sched_barrier(0);                                                         \
@@ -113,9 +120,6 @@ __device__ __forceinline__ long glwe_off(int limb, int col) { return (long)(limb
 // compiler adds it to the lane's 64-bit address with two VALU instructions per access (~100 per key-switch input, ~130 per
 // output).  The empty asm pins the base to SGPRs and keeps the zero extension of the offset next to the access, which is
 // what instruction selection needs to pick the scalar-base form.  `base` MUST be wave uniform.
-#ifndef FK_SADDR
-#define FK_SADDR 1
-#endif
 typedef const __attribute__((address_space(1))) char* gbytes_t;
 typedef __attribute__((address_space(1))) char* gbytes_w_t;
 // a pointer every lane holds the same value of, moved to scalar registers (folds away where the compiler already knows it
@@ -125,40 +129,19 @@ __device__ __forceinline__ unsigned long long uniform_u64(unsigned long long v) 
     return ((unsigned long long)hi << 32) | lo;
 }
 __device__ __forceinline__ int gload_i32(const int32_t* base, unsigned byte_off) {
-#if FK_SADDR
     gbytes_t b = (gbytes_t)uniform_u64((unsigned long long)base);
     asm("" : "+s"(b));
     return *(const __attribute__((address_space(1))) int*)(b + byte_off);
-#else
-    return *reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(base) + byte_off);
-#endif
 }
 __device__ __forceinline__ double gload_f64(const double* base, unsigned byte_off) {
-#if FK_SADDR
     gbytes_t b = (gbytes_t)uniform_u64((unsigned long long)base);
     asm("" : "+s"(b));
     return *(const __attribute__((address_space(1))) double*)(b + byte_off);
-#else
-    return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(base) + byte_off);
-#endif
-}
-__device__ __forceinline__ void gstore_f64(double* base, unsigned byte_off, double v) {
-#if FK_SADDR
-    gbytes_w_t b = (gbytes_w_t)uniform_u64((unsigned long long)base);
-    asm("" : "+s"(b));
-    *(__attribute__((address_space(1))) double*)(b + byte_off) = v;
-#else
-    *reinterpret_cast<double*>(reinterpret_cast<char*>(base) + byte_off) = v;
-#endif
 }
 __device__ __forceinline__ void gstore_i32(int32_t* base, unsigned byte_off, int v) {
-#if FK_SADDR
     gbytes_w_t b = (gbytes_w_t)uniform_u64((unsigned long long)base);
     asm("" : "+s"(b));
     *(__attribute__((address_space(1))) int*)(b + byte_off) = v;
-#else
-    *reinterpret_cast<int32_t*>(reinterpret_cast<char*>(base) + byte_off) = v;
-#endif
 }
 
 // ---------------------------------------------------------------------------------------
@@ -225,29 +208,15 @@ __device__ __forceinline__ void cmac(double& ar, double& ai, double xr, double x
     ai = __builtin_fma(xr, gi, ai);
     ai = __builtin_fma(xi, gr, ai);
 }
-__device__ __forceinline__ void mac_poly(double (&acc)[E], const double (&x)[E], const double* __restrict__ g, int tid) {
-    const double2* gp = reinterpret_cast<const double2*>(g);
-#pragma unroll
-    for (int kk = 0; kk < E / 2; kk++) {
-#ifdef FK_NO_OPERANDS   // measurement only (wrong results): what the step costs without its operand stream
-        double2 v;
-        asm volatile("" : "=v"(v.x), "=v"(v.y));
-#else
-        const double2 v = gp[kk * T + tid];
-#endif
-        cmac(acc[2 * kk], acc[2 * kk + 1], x[2 * kk], x[2 * kk + 1], v.x, v.y);
-    }
-}
 
 // Prepared-operand registers of one polynomial (E/2 16-byte words per thread).
 struct OpRegs { double2 v[E / 2]; };
 __device__ __forceinline__ void load_ops(OpRegs& o, const double* __restrict__ g, int tid) {
-#ifdef FK_NO_OPERANDS
+#ifdef FK_NO_OPERANDS   // measurement only (wrong results): what the step costs without its operand stream
 #pragma unroll
     for (int kk = 0; kk < E / 2; kk++) asm volatile("" : "=v"(o.v[kk].x), "=v"(o.v[kk].y));
     return;
 #endif
-#if FK_SADDR
     // Every operand polynomial of a launch is addressed as (wave-uniform base) + (lane offset): the base — key / GGSW
     // pointer, limb, column, kk * 8 KiB — lives in scalar registers and is advanced by scalar adds, the lane offset is ONE
     // 32-bit register (tid * 16) for all loads: `global_load_dwordx4 v, v_off, s[base]`.  Left to itself the compiler folds
@@ -269,11 +238,6 @@ __device__ __forceinline__ void load_ops(OpRegs& o, const double* __restrict__ g
         o.v[kk].x = w.x;
         o.v[kk].y = w.y;
     }
-#else
-    const double2* gp = reinterpret_cast<const double2*>(g);
-#pragma unroll
-    for (int kk = 0; kk < E / 2; kk++) o.v[kk] = gp[kk * T + tid];
-#endif
 }
 // Makes the compiler materialise x here (no instruction): code motion passes sink a multiply-accumulate towards its first use, which
 // may lie behind the NEXT operands' requests — and then its wait covers those requests as well.
@@ -299,35 +263,16 @@ __device__ __forceinline__ void mac_regs(double (&acc)[E], const double (&x)[E],
 // k_ext_product: res = a (x) G   (SURVEY.md A.4), SA = limbs of a and res, SG = limbs of G.
 // Phase 1: the 2*SA limb polynomials of a are transformed (SA at a time) and stay in registers.
 // Phase 2: for each output column, the SG output limbs are produced from the least significant
-// one upwards, two at a time: pointwise MAC of the 2*SA inputs against G, a paired inverse
+// one upwards, BI at a time: pointwise MAC of the 2*SA inputs against G, an inverse
 // transform, then the base-2^17 normalisation steps whose carry is the only state that survives
 // to the next limbs (vec_znx_big_normalize walks the limbs in exactly this order).
 // NCO = 1: blockIdx.z selects the output column (two workgroups per ciphertext, phase 1 done by
 // both).  res must not alias a.
 // ---------------------------------------------------------------------------------------
-// Batch sizes of the transforms (tuning knobs): BF polynomials per forward NTT call, BI per inverse.
-#ifndef FK_BF
-#define FK_BF 3
-#endif
-#ifndef FK_BI
-#define FK_BI 1
-#endif
-constexpr int BF = FK_BF, BI = FK_BI;
-#ifndef FK_EARLY_FETCH
-#define FK_EARLY_FETCH 0
-#endif
-#ifndef FK_SPREAD_FETCH
-#define FK_SPREAD_FETCH 1      // ks_run: the next limb's operand loads spread over the post-step
-#endif
-#ifndef FK_WARM_OPERANDS
-#define FK_WARM_OPERANDS 0     // ep_run: the first output limb's operands touched in front of the forward transforms (every line: 52.1 against 51.3 us per product; one stripe per polynomial: neutral): off
-#endif
-#ifndef FK_EP_PREFETCH
-#define FK_EP_PREFETCH 0       // ep_run: the first output limb's operands of a column requested ahead of the column loop (75 spilled registers: off)
-#endif
-#ifndef FK_SPREAD_FETCH_EP
-#define FK_SPREAD_FETCH_EP 1   // ep_run: the next limb's twelve operand loads in two bursts around the normalisation step (8 + 4: 50.7 against 51.3 us per product; interleaved with its parts: 247 registers, over the cap, six spilled, 51.9)
-#endif
+// Polynomials per transform call of the unchained kernels (ks_run, ep_run): BF forward, BI inverse.
+// (BI = 1: the `for (b < BI)` loops of the two limb loops run once.  Written out as straight-line code they compile to
+// different device code, so they stay as they are until a change that is measured: DESIGN.md 10.3.)
+constexpr int BF = 3, BI = 1;
 // Register cap of the chain kernels (see k_keyswitch_chain): one workgroup per CU, two waves per SIMD; above 240 registers the
 // two waves leave no room for the one-wave gate launch of read_prepare_write and the workgroup stays off that CU.
 #ifndef FK_CHAIN_VGPRS
@@ -340,34 +285,21 @@ constexpr int BF = FK_BF, BI = FK_BI;
 #define FK_WIDE_VGPRS 128
 static_assert(BF <= BMAX && BI <= BMAX, "LDS holds BMAX exchange buffers");
 
-// forward transform of S polynomials, BF at a time
-#ifndef FK_KS_PROLOGUE_EXTRA
-#define FK_KS_PROLOGUE_EXTRA 2   // ks_trace_l: operand polynomials of a step's first pair requested beside the window, behind the forward transforms
-#endif
-#ifndef FK_KS_WINDOW
-#define FK_KS_WINDOW 2    // ks_trace_l: operand polynomials in flight under the transforms (16 registers each; 3: 69 spilled registers, slower)
-#endif
-#ifndef FK_EP_WINDOW
-#define FK_EP_WINDOW 2    // ep_step_r: the same (3: 75 spilled registers, slower)
-#endif
-#ifndef FK_FWD_SKEW
-#define FK_FWD_SKEW 1   // ks_trace_l: the three forward transforms half a phase apart (ntt_fwd3_skew): trace step 35.8 -> 35.6 us, step 2.198 -> 2.18 ms; the same in the products: +1 % per product, not used there
-#endif
-template <int S, int R = 0, bool SKEW = false>
+// forward transform of S polynomials, BF at a time (half a phase apart inside a call: fft_fwd_skew)
+template <int S, int R = 0>
 __device__ __forceinline__ void fwd_all(double (&x)[S][E], const double* tw, double* data, int tid) {
-    if constexpr (SKEW && FK_FWD_SKEW && S == 3 && R == 0 && BF == 3) { ntt_fwd3_skew(x, tw, data, tid); return; }
     if constexpr (R < S) {
         constexpr int C = (S - R < BF) ? (S - R) : BF;
         ntt_fwd<C>(*reinterpret_cast<double(*)[C][E]>(&x[R]), tw, data, tid);
-        fwd_all<S, R + C, false>(x, tw, data, tid);
+        fwd_all<S, R + C>(x, tw, data, tid);
     }
 }
 
 template <int SA, int SG>
 __device__ __forceinline__ void ep_mac(double (&acc)[E], const double (&x0)[SA][E], const double (&x1)[SA][E], OpRegs (&g)[SA],
-                                       const double* __restrict__ ggsw, int j, int co, int jnext, int tid) {
-    // g holds the column_in 0 operands of limb j on entry (requested by ep_fetch0 after the previous
-    // inverse transform)
+                                       const double* __restrict__ ggsw, int j, int co, int tid) {
+    // g holds the column_in 0 operands of limb j on entry (requested by ep_run around the previous limb's
+    // normalisation step)
     // each operand register set is refilled with the column_in 1 operands as soon as its column_in 0 product
     // has been taken, so the refills are in flight during the remaining products of the first half
 #pragma unroll
@@ -379,9 +311,9 @@ __device__ __forceinline__ void ep_mac(double (&acc)[E], const double (&x0)[SA][
     }
 #pragma unroll
     for (int r = 0; r < SA; r++) mac_regs(acc, x1[r], g[r]);
-    (void)jnext;
     __builtin_amdgcn_sched_barrier(0);
 }
+
 template <int SA, int SG>
 __device__ __forceinline__ void ep_fetch0(OpRegs (&g)[SA], const double* __restrict__ ggsw, int j, int co, int tid) {
 #pragma unroll
@@ -433,17 +365,11 @@ __device__ __forceinline__ void ep_run(GlweRef a, GlweRef res, const double* __r
     const int co0 = (NCO == 1) ? (int)blockIdx.z : 0;
 
     double x0[SA][E], x1[SA][E];   // limbs of column 0 / column 1 of a
-    OpRegs gpre[SA];               // operands requested ahead of the column loop (FK_EP_PREFETCH)
     // The operands of a product are touched for the first time by every workgroup at once, when the first output limb of the
     // first column asks for them: the stamps (tools/stamp_chain.py) show 3 us more for that limb than for any other (cold
-    // lines, cold translations).  The registers to request them earlier are not there (FK_EP_PREFETCH spills), but ONE 8-byte
-    // load per thread and operand polynomial, 64 bytes apart, touches every line of the six polynomials of that limb: issued
-    // here, in front of the forward transforms, summed into one register that nothing reads.
-    [[maybe_unused]] double warm = 0.0;
-    if constexpr (STAGE == 0 && FK_WARM_OPERANDS) {
-#pragma unroll
-        for (int w = 0; w < 2 * SA; w++) warm += ggsw[(long)((w * SG + (SG - 1)) * 2 + co0) * N + tid];   // (one coalesced 4 KB stripe per polynomial: translations and the first lines)
-    }
+    // lines, cold translations).  Tried and dropped: requesting them ahead of the column loop (75 spilled registers), and
+    // touching their lines in front of the forward transforms (every line: 52.1 against 51.3 us per product; one stripe
+    // per polynomial: neutral).  HISTORY.md, "The product kernel's operand loads in two bursts".
     {
         int xi[SA][E];
 #pragma unroll
@@ -466,16 +392,9 @@ __device__ __forceinline__ void ep_run(GlweRef a, GlweRef res, const double* __r
         for (int r = 0; r < SA; r++)
 #pragma unroll
             for (int k = 0; k < E; k++) x1[r][k] = (double)xi[r][k];
-        if constexpr (STAGE == 0 && FK_EP_PREFETCH) {
-            // the column_in 0 operands of the first output limb of the first column: requested in front of the second batch of
-            // forward transforms (accumulator and carries are not live yet), so that no column starts with an exposed round trip
-#pragma unroll
-            for (int r = 0; r < SA; r++) load_ops(gpre[r], ggsw + (long)(((2 * r) * SG + (SG - 1)) * 2 + co0) * N, tid);
-        }
         fwd_all<SA>(x1, tw, data, tid);
         YSTAMP(3);
     }
-    if constexpr (STAGE == 0 && FK_WARM_OPERANDS) asm volatile("" ::"v"(warm));   // the loads are kept; their values end here
     if constexpr (STAGE == 1) {
         const int co = (int)blockIdx.z / SG, j = SG - 1 - (int)blockIdx.z % SG;
         OpRegs g[SA];
@@ -484,7 +403,7 @@ __device__ __forceinline__ void ep_run(GlweRef a, GlweRef res, const double* __r
         double acc[1][E];
 #pragma unroll
         for (int k = 0; k < E; k++) acc[0][k] = 0.0;
-        ep_mac<SA, SG>(acc[0], x0, x1, g, ggsw, j, co, -1, tid);
+        ep_mac<SA, SG>(acc[0], x0, x1, g, ggsw, j, co, tid);
         ntt_inv<1, false>(acc, tw, data, tid);   // the only inverse transform of this workgroup
         double* bp = big + big_ct() + (long)(co * SG + j) * N;
 #pragma unroll
@@ -495,7 +414,7 @@ __device__ __forceinline__ void ep_run(GlweRef a, GlweRef res, const double* __r
     // Consecutive inverse transforms alternate between two exchange buffers: the cross-wave reads of one
     // are then always fenced from the next writes into the same buffer by the exchange-0 barrier of the
     // transform in between, and no barrier is needed at the start of a transform.
-    constexpr bool DB = (2 * BI <= BMAX);
+    static_assert(2 * BI <= BMAX, "two sets of exchange buffers");
     int it = 0;
 #pragma unroll 1
     for (int c = 0; c < NCO; c++) {
@@ -504,13 +423,8 @@ __device__ __forceinline__ void ep_run(GlweRef a, GlweRef res, const double* __r
 #pragma unroll
         for (int k = 0; k < E; k++) carry[k] = 0.0;
         OpRegs g[SA];
-        if constexpr (STAGE == 0 && FK_EP_PREFETCH) {
 #pragma unroll
-            for (int r = 0; r < SA; r++) g[r] = gpre[r];
-        } else {
-#pragma unroll
-            for (int r = 0; r < SA; r++) load_ops(g[r], ggsw + (long)(((2 * r) * SG + (SG - 1)) * 2 + co) * N, tid);
-        }
+        for (int r = 0; r < SA; r++) load_ops(g[r], ggsw + (long)(((2 * r) * SG + (SG - 1)) * 2 + co) * N, tid);
 
         auto emit = [&](const double (&v_)[E], int j) {
 #pragma unroll
@@ -521,57 +435,33 @@ __device__ __forceinline__ void ep_run(GlweRef a, GlweRef res, const double* __r
                 if (j < SA) gstore_i32(rp + glwe_off(j, co), (unsigned)(tid + T * k) * 4u, (int)digit_of(v, cy));
             }
         };
-        constexpr int REM = SG % BI;   // limbs left over for a final narrower batch
 #pragma unroll 1
-        for (int j = SG - 1; j >= BI - 1 + REM; j -= BI) {
+        for (int j = SG - 1; j >= BI - 1; j -= BI) {
             double acc[BI][E];
 #pragma unroll
             for (int b = 0; b < BI; b++) {
 #pragma unroll
                 for (int k = 0; k < E; k++) acc[b][k] = 0.0;
                 if (b > 0) ep_fetch0<SA, SG>(g, ggsw, j - b, co, tid);
-                ep_mac<SA, SG>(acc[b], x0, x1, g, ggsw, j - b, co, j - b - 1, tid);
+                ep_mac<SA, SG>(acc[b], x0, x1, g, ggsw, j - b, co, tid);
             }
             YSTAMP(8 + (c * SG + (SG - 1 - j)) * 4);
-            if constexpr (FK_EARLY_FETCH == 1) {
-                if (j - BI >= 0) ep_fetch0<SA, SG>(g, ggsw, j - BI, co, tid);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            ntt_inv<BI, !DB>(acc, tw, data + (DB ? (it++ & 1) * BI * LDS_DATA : 0), tid);
+            ntt_inv<BI, false>(acc, tw, data + (it++ & 1) * BI * LDS_DATA, tid);
             YSTAMP(9 + (c * SG + (SG - 1 - j)) * 4);
-            if constexpr (STAGE == 0 && FK_EP_PREFETCH) {
-                if (j - BI < 0 && c + 1 < NCO) {   // last limb of this column: the next column's first operands arrive during its normalisation step
-#pragma unroll
-                    for (int r = 0; r < SA; r++) load_ops(gpre[r], ggsw + (long)(((2 * r) * SG + (SG - 1)) * 2 + co + 1) * N, tid);
-                }
-            }
-            if constexpr (FK_EARLY_FETCH == 0 && FK_SPREAD_FETCH_EP && BI == 1) {
-                // the next limb's column_in 0 operands, one polynomial at a time between the parts of the normalisation step (see
-                // ks_trace_y: twelve loads per thread from all waves at once wait for the address unit)
-                const bool more = j - BI >= 0;
-                const int jn = j - BI;
-                auto fetch1 = [&](int r) { if (more) load_ops(g[r], ggsw + (long)(((2 * r) * SG + jn) * 2 + co) * N, tid); };
-                fetch1(0);
-                if (SA > 1) fetch1(1);
-                __builtin_amdgcn_sched_barrier(0);
-                emit(acc[0], j);
-                __builtin_amdgcn_sched_barrier(0);
-                if (SA > 2) fetch1(2);
-                static_assert(SA <= 3, "three operand polynomials per half");
-            } else {
-                if constexpr (FK_EARLY_FETCH == 0) { if (j - BI >= 0) ep_fetch0<SA, SG>(g, ggsw, j - BI, co, tid); }   // overlaps the normalisation step
-#pragma unroll
-                for (int b = 0; b < BI; b++) emit(acc[b], j - b);
-            }
+            // the next limb's column_in 0 operands in two bursts around the normalisation step: twelve loads per thread from all
+            // waves at once wait for the address unit (8 + 4: 50.7 against 51.3 us per product; interleaved with the step's parts:
+            // 247 registers, over the cap, six spilled, 51.9: HISTORY.md, "The product kernel's operand loads in two bursts")
+            static_assert(BI == 1 && SA <= 3, "one limb at a time, three operand polynomials per half");
+            const bool more = j - BI >= 0;
+            const int jn = j - BI;
+            auto fetch1 = [&](int r) { if (more) load_ops(g[r], ggsw + (long)(((2 * r) * SG + jn) * 2 + co) * N, tid); };
+            fetch1(0);
+            if (SA > 1) fetch1(1);
+            __builtin_amdgcn_sched_barrier(0);
+            emit(acc[0], j);
+            __builtin_amdgcn_sched_barrier(0);
+            if (SA > 2) fetch1(2);
             YSTAMP(10 + (c * SG + (SG - 1 - j)) * 4);
-        }
-        if constexpr (REM == 1) {
-            double acc[1][E];
-#pragma unroll
-            for (int k = 0; k < E; k++) acc[0][k] = 0.0;
-            ep_mac<SA, SG>(acc[0], x0, x1, g, ggsw, 0, co, -1, tid);
-            ntt_inv<1, !DB>(acc, tw, data + (DB ? (it++ & 1) * BI * LDS_DATA : 0), tid);
-            emit(acc[0], 0);
         }
     }
     YSTAMP(5);
@@ -953,10 +843,9 @@ __device__ __forceinline__ void ks_run(const KsArgs& ka, double* lds, bool load_
 #pragma unroll
             for (int r = 0; r < SX; r++) load_ops(g[r], ka.key + (long)((r * SK + j) * 2 + co) * N, tid);
         };
-        auto mac = [&](double (&acc)[E], int jnext) {
+        auto mac = [&](double (&acc)[E]) {
 #pragma unroll
             for (int k = 0; k < E; k++) acc[k] = 0.0;
-            (void)jnext;
 #pragma unroll
             for (int r = 0; r < SX; r++) mac_regs(acc, xh[r], g[r]);
             __builtin_amdgcn_sched_barrier(0);
@@ -1017,7 +906,7 @@ __device__ __forceinline__ void ks_run(const KsArgs& ka, double* lds, bool load_
             const int j = SK - 1 - (int)blockIdx.z % SK;
             fetch(j);
             double acc[1][E];
-            mac(acc[0], -1);
+            mac(acc[0]);
             ntt_inv<1, false>(acc, tw, data, tid);   // the only inverse transform of this workgroup
             add_body(acc[0], j);
             double* bgp = ka.big + big_ct() + (long)(co * SK + j) * N;
@@ -1025,27 +914,23 @@ __device__ __forceinline__ void ks_run(const KsArgs& ka, double* lds, bool load_
             for (int k = 0; k < E; k++) bgp[tid + T * k] = acc[0][k];
             return;
         }
-        constexpr int REM = SK % KBI;
         STAMP(4 + 24 * c);
         fetch(SK - 1);
 #pragma unroll 1
-        for (int j = SK - 1; j >= KBI - 1 + REM; j -= KBI) {
+        for (int j = SK - 1; j >= KBI - 1; j -= KBI) {
             double acc[KBI][E];
             STAMP(8 + 4 * (SK - 1 - j) + 24 * c);
 #pragma unroll
             for (int b = 0; b < KBI; b++) {
                 if (b > 0) fetch(j - b);
-                mac(acc[b], j - b - 1);
+                mac(acc[b]);
             }
             STAMP(9 + 4 * (SK - 1 - j) + 24 * c);
-            if constexpr (FK_EARLY_FETCH == 1) {   // operands of the next limb requested BEFORE the transform: 48 more live registers across it
-                if (j - KBI >= 0) fetch(j - KBI);
-                __builtin_amdgcn_sched_barrier(0);
-            }
             ntt_inv<KBI, !DB>(acc, tw, data + (DB ? (it++ & 1) * KBI * LDS_DATA : 0), tid);
-            if constexpr (FK_EARLY_FETCH == 0 && FK_SPREAD_FETCH && KBI == 1 && SX == 3) {
-                // next limb's operands: their latency overlaps the post-step; one operand polynomial at a time around its parts (see
-                // ks_trace_y: twelve loads per thread from all waves at once queue at the address unit)
+            if constexpr (SX == 3) {
+                static_assert(KBI == 1, "one limb at a time");
+                // next limb's operands: their latency overlaps the post-step; one operand polynomial at a time around its parts (twelve
+                // loads per thread from all waves at once queue at the address unit: HISTORY.md, "Operand loads spread over the post-step")
                 const bool more = j - KBI >= 0;
                 auto fetch1 = [&](int r) { if (more) load_ops(g[r], ka.key + (long)((r * SK + (j - KBI)) * 2 + co) * N, tid); };
                 fetch1(0);
@@ -1060,23 +945,16 @@ __device__ __forceinline__ void ks_run(const KsArgs& ka, double* lds, bool load_
                 __builtin_amdgcn_sched_barrier(0);
                 fetch1(2);
             } else {
-            if constexpr (FK_EARLY_FETCH == 0) { if (j - KBI >= 0) fetch(j - KBI); }   // (FK_EARLY_FETCH == 2: timing diagnostic, operands never refetched, results wrong)   // next limb's operands: their latency overlaps the post-step
-            STAMP(10 + 4 * (SK - 1 - j) + 24 * c);
+                if (j - KBI >= 0) fetch(j - KBI);   // next limb's operands: their latency overlaps the post-step
+                STAMP(10 + 4 * (SK - 1 - j) + 24 * c);
 #pragma unroll
-            for (int b = 0; b < KBI; b++) add_body(acc[b], j - b);
-            STAMP(11 + 4 * (SK - 1 - j) + 24 * c);
+                for (int b = 0; b < KBI; b++) add_body(acc[b], j - b);
+                STAMP(11 + 4 * (SK - 1 - j) + 24 * c);
 #pragma unroll
-            for (int b = 0; b < KBI; b++) emit(acc[b], j - b);
+                for (int b = 0; b < KBI; b++) emit(acc[b], j - b);
             }
         }
         STAMP(5 + 24 * c);
-        if constexpr (REM == 1) {
-            double acc[1][E];
-            mac(acc[0], -1);
-            ntt_inv<1, !DB>(acc, tw, data + (DB ? (it++ & 1) * KBI * LDS_DATA : 0), tid);
-            add_body(acc[0], 0);
-            emit(acc[0], 0);
-        }
     }
 }
 
@@ -1128,7 +1006,7 @@ __device__ __forceinline__ double take_digit(double& c) {
 //        V = Y  [+- Y_body(src) for the body column: vec_znx_big_add_small of phi_g(rsh1(a).body)]
 //            + e + acc_2 + cmod(acc_1, 2^34) * 2^17 + cmod(acc_0, 2^17) * 2^34          (cmod: centred remainder)
 // with every term an exact integer below 2^50 in magnitude (|acc_j| < 2^47, |Y| < 2^50 + 2^33): |V| < 2^52.2, exact in
-// FP64.  The output is A = V - 2^51 * floor((V + C) / 2^51), handed over as Y' = ceil(A / 2) as in ks_trace_y.
+// FP64.  The output is A = V - 2^51 * floor((V + C) / 2^51), handed over as Y' = ceil(A / 2) (the one-double form of "One fused trace step" above).
 // Same integers as the limb-by-limb walk (tests: every digest and oracle comparison of the Y form also runs in this form).
 //
 // What it buys: (i) the post-step of an output limb is 1-4 FP64 instructions per coefficient instead of ~9 (+ ~8 for the
@@ -1265,20 +1143,19 @@ __device__ __forceinline__ void ks_trace_l(const KsArgs& ka, double* lds, bool l
             sidx = (sidx + sstep) & (2 * N - 1);
         }
     }
-    constexpr bool STREAM = true;        // (round 6: odd limb counts — the README block's 5-limb keys — stream too: pairs + one, see below)
+    // (round 6: odd limb counts — the README block's 5-limb keys — stream too: pairs + one, see below)
     static_assert(!(SK & 1) || SK == 5, "odd limb counts: the pairs-plus-one schedule below is written out for five limbs");
-    constexpr int KW = FK_KS_WINDOW, NQ = 2 * SX;
-    [[maybe_unused]] OpRegs w[STREAM ? KW : 1];
-    [[maybe_unused]] double accn[2][E];
+    constexpr int KW = 2;   // operand polynomials in flight under the transforms (16 registers each; 3: 69 spilled registers, slower)
+    constexpr int NQ = 2 * SX;
+    OpRegs w[KW];
+    double accn[2][E];
     // operand q of the pair of output limbs (j, j - 1) of column co_: limb j - q / SX, digit row q % SX
-    [[maybe_unused]] auto kopnd = [&](int co_, int j_, int q) { return ka.key + (long)(((q % SX) * SK + (j_ - q / SX)) * 2 + co_) * N; };
-    if constexpr (STREAM) {
+    auto kopnd = [&](int co_, int j_, int q) { return ka.key + (long)(((q % SX) * SK + (j_ - q / SX)) * 2 + co_) * N; };
 #pragma unroll
-        for (int i = 0; i < KW; i++) load_ops_p(w[i], kopnd(1, SK - 1, i), tid);
-        __builtin_amdgcn_sched_barrier(0);
-    }
+    for (int i = 0; i < KW; i++) load_ops_p(w[i], kopnd(1, SK - 1, i), tid);
+    __builtin_amdgcn_sched_barrier(0);
     YSTAMP(2);
-    fwd_all<SX, 0, true>(xh, tw, data, tid);   // its first exchange starts with a barrier: every gather above is done before the buffers are overwritten
+    fwd_all<SX>(xh, tw, data, tid);   // its first exchange starts with a barrier: every gather above is done before the buffers are overwritten
     YSTAMP(3);
     // the body column's Y goes to buffer 2 (natural order), for the gather of column 0 (own coefficient +- phi_g's source
     // coefficient), once every wave is through the forward transforms (their wave-local exchanges use that buffer too)
@@ -1288,13 +1165,13 @@ __device__ __forceinline__ void ks_trace_l(const KsArgs& ka, double* lds, bool l
     double y1n[E];   // column 1's output Y, on its way to buffer 2 (the next step's mask staging)
 #pragma unroll
     for (int k = 0; k < E; k++) y1n[k] = 0.0;
-    if constexpr (STREAM) {
+    {
         // The first pair's products have nothing to run under.  Their first KW operands arrived during the forward transforms; the next KP go into
         // registers that are free here (no pair is being transformed yet: the second accumulator pair's) and are requested at once, the last
         // NQ - KW - KP into the window as it drains: the wait is one round trip instead of two.
-        constexpr int KP = FK_KS_PROLOGUE_EXTRA;
-        static_assert(KW + KP <= NQ, "prologue window");
-        [[maybe_unused]] OpRegs pw[KP > 0 ? KP : 1];
+        constexpr int KP = 2;   // operand polynomials of a step's first pair requested beside the window, behind the forward transforms
+        static_assert(KP >= 1 && KW + KP <= NQ, "prologue window");
+        OpRegs pw[KP];
 #pragma unroll
         for (int i = 0; i < KP; i++) load_ops_p(pw[i], kopnd(1, SK - 1, KW + i), tid);
 #pragma unroll
@@ -1304,7 +1181,6 @@ __device__ __forceinline__ void ks_trace_l(const KsArgs& ka, double* lds, bool l
         // order of use: w[0..KW-1] (polynomials 0..KW-1), pw (KW..KW+KP-1), then the window again (KW+KP..NQ-1)
 #pragma unroll
         for (int q = 0; q < NQ; q++) {
-            constexpr int dummy = 0; (void)dummy;
             const bool from_pw = (q >= KW && q < KW + KP);
             const int slot = (q < KW) ? q : (q - KW - KP) % KW;          // window slot of a polynomial that goes through the window
             if (from_pw) mac_regs(accn[q / SX], xh[q % SX], pw[(q - KW) < KP && q >= KW ? q - KW : 0]);
@@ -1352,7 +1228,7 @@ __device__ __forceinline__ void ks_trace_l(const KsArgs& ka, double* lds, bool l
         // lone limb of column 1 is summed into accn[0], accn[1] already takes limb 4 of column 0, and limb 3 goes to accn[0] under the
         // lone limb's own transform (the pair then arrives swapped: SWAP).
         constexpr int NTOT = 2 * SK * SX;
-        [[maybe_unused]] auto kop = [&](int p_) { return kopnd(p_ < SK * SX ? 1 : 0, SK - 1, p_ % (SK * SX)); };
+        auto kop = [&](int p_) { return kopnd(p_ < SK * SX ? 1 : 0, SK - 1, p_ % (SK * SX)); };
         auto unit = [&](auto nb_tag, auto p_tag, auto nh_tag, auto swap_tag, auto j_tag) {
             constexpr int NB = decltype(nb_tag)::value, P = decltype(p_tag)::value, NH = decltype(nh_tag)::value, J = decltype(j_tag)::value;
             constexpr bool SWAP = decltype(swap_tag)::value;
@@ -1519,7 +1395,7 @@ __device__ __forceinline__ void ep_step_r(GlweRef a, GlweRef res, const double* 
 #pragma unroll
             for (int k = 0; k < E; k++) x[r][k] = (double)xi[r][k];
     };
-    [[maybe_unused]] double a1s[E];
+    double a1s[E];
     if constexpr (IN == 1) {
         double a0[E];
 #pragma unroll
@@ -1540,7 +1416,7 @@ __device__ __forceinline__ void ep_step_r(GlweRef a, GlweRef res, const double* 
     // the stream is one sequence).  Two accumulators: the one being transformed, the one being summed.  The first limb's products
     // have no inverse transform to run under: its first W operands arrive during the first three forward transforms, the next W
     // during the other three.
-    constexpr int W = FK_EP_WINDOW;
+    constexpr int W = 2;   // operand polynomials in flight under the transforms (16 registers each, as in ks_trace_l; 3: 75 spilled registers, slower)
     constexpr int NQ = 2 * SA;
     static_assert(W >= 1 && W <= SA, "window");
     OpRegs w[W];
@@ -1706,7 +1582,7 @@ struct KsChainArgs {
     unsigned* done = nullptr;        // fallback launch behind k_chain_mid: a ciphertext is redone unless done[ct * 32 + 3] == done_seq
     unsigned done_seq = 0;
 };
-// YF: the intermediates of the chain are handed over as Y = ceil(A/2) (ks_trace_y).  YF = false is the limb-form chain; it
+// YF: the intermediates of the chain are handed over as Y = ceil(A/2) (see "One fused trace step" above ks_trace_l).  YF = false is the limb-form chain; it
 // is also what runs as the predicated fallback behind k_trace_tail: that launch normally has nothing to do, but it needs
 // its registers and LDS granted before it can say so, and it must slip in next to the side-stream work that
 // read_prepare_write starts beside the trace chain — with the leaner limb-form kernel (<= 232 VGPRs: two waves leave room
@@ -2344,7 +2220,7 @@ __global__ __launch_bounds__(256) void k_sub_add_norm(GlweRef a, GlweRef b, Glwe
 //   <RS = 1, LPM = 2>  <= 64 (TRACE): the same with two output limb polynomials per member;                  hand-off A
 //   normalisation phase: one thread per (column, coefficient), MEMBERS * T threads per ciphertext — the body column of a
 //     trace step (vec_znx_big_add_small) and its `+ x` join the sums here;                                    hand-off B
-// Intermediate ciphertexts live in a scratch of their own, in the one-double form of ks_trace_y: TRACE: Y = ceil(A/2) (the
+// Intermediate ciphertexts live in a scratch of their own, in the one-double form of the chain steps (see "One fused trace step" above ks_trace_l): TRACE: Y = ceil(A/2) (the
 // consumer wants rsh1 of the previous output: its digits ARE the digits of Y); EP: A itself.  Same sums, same carry chain per
 // coefficient as the fused kernels: bit-identical results.  The destination is written by the LAST step only, after the
 // group's last hand-off — so the chain may run in place (read_prepare_write's products on the stored rows).

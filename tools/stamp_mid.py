@@ -1,5 +1,5 @@
 """Diagnostic: real-time-clock stamps inside k_chain_mid (ciphertext 0, third step, every member).  Needs the -DFK_STAMP build:
-    make -C fhe-ram_amd/csrc VARIANT=stamp HIPFLAGS+=-DFK_STAMP variant;  FHERAM_LIB=fhe-ram_amd/libfheram_stamp.so python tools/stamp_mid.py [batch]"""
+    make -C fhe-ram_amd/csrc VARIANT=stamp EXTRA=-DFK_STAMP variant;  FHERAM_LIB=fhe-ram_amd/libfheram_stamp.so python tools/stamp_mid.py [batch]"""
 import ctypes as C, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,5 +1,5 @@
 """Diagnostic: cycle stamps inside k_trace_tail, third step, members 0 and 23 of group 0 (needs the -DFK_STAMP build,
-FHERAM_LIB=...: make -C fhe-ram_amd/csrc VARIANT=stamp HIPFLAGS+=-DFK_STAMP variant)."""
+FHERAM_LIB=...: make -C fhe-ram_amd/csrc VARIANT=stamp EXTRA=-DFK_STAMP variant)."""
 import ctypes as C, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
