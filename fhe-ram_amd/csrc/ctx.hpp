@@ -31,6 +31,20 @@ struct ProfCls {
 
 inline uint64_t next_addr_id() { static std::atomic<uint64_t> n{0}; return ++n; }
 
+// What ONE RAM carries from one operation to the next: a context holds one, a bank one per member (bank.hpp), and an operation updates
+// the one its operand set names (path.hpp Opnds::st).
+struct RamState {
+    bool initialized = false, state = false;
+    // Results of read_prepare_write that Ram::write recomputes on the unchanged state (FHERAM_MEMO=0 recomputes them):
+    //  memo_top  : d_trtop = trace(tree top) — the output of read_prepare_write (ram.rs:540) is the very value
+    //              write_first_step computes first (ram.rs:571-572: same ciphertext, same deterministic operations);
+    //  memo_alone: arena A holds every local row after the packer levels in which it is alone (ram.rs:514; n steps),
+    //              which ARE the first n steps of trace(ct_hi) in write_mid_step (ram.rs:616).
+    bool memo_top = false;
+    int memo_alone = 0;
+    bool res_in_trtop = false;   // the last read / read_prepare_write left its result in d_trtop (else d_res)
+};
+
 struct fheram_ctx {
     fheram_params p;
     int device = 0;
@@ -39,8 +53,11 @@ struct fheram_ctx {
     hipStream_t cur = nullptr;       // stream the launchers currently enqueue on
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipEvent_t ev_xout = nullptr, ev_xin = nullptr;   // ordering against a caller's stream (fheram_stream_signal / _wait)
-    bool side_begun = false;                          // write_side_begin has been enqueued for the pending write
-    // derived
+    // the write in flight:
+    bool side_begun = false;                          // write_side_begin has been enqueued for it
+    bool trhi_in_C = false;                           // trace(ct_hi) of the local rows is in arena C (else A)
+    bool tree_rotate_pending = false;                 // write_top left the tree's rotated copy of ct_lo to write_rows
+    // derived from the parameters (never changed after creation)
     int ws = 0, n2 = 0, n_digits = 0;
     size_t rows = 0;        // GLWE rows per sub-RAM held by THIS context (all of them unless sharded)
     size_t rows_glob = 0;   // rows per sub-RAM of the whole RAM
@@ -54,7 +71,7 @@ struct fheram_ctx {
     static constexpr size_t GGSW = (size_t)DNUM_CT * 2 * GLWE4;            // elements of a GGSW
     static constexpr size_t EVK5 = (size_t)DNUM_GGSW * S_INV * 2 * N;      // inverse / tensor key
     static constexpr size_t GGSW5 = (size_t)DNUM_GGSW * 2 * S_INV * 2 * N; // one bit of an FheUint (N4)
-    // device
+    // device: keys and tables, then the buffers indexed by ciphertext (the sequences of path.hpp reach the latter through a RamView only)
     double* d_tw = nullptr;
     double ninv = 0.0;
     double* d_atk = nullptr;       // [log_n] prepared trace keys
@@ -89,13 +106,9 @@ struct fheram_ctx {
     int32_t* d_ggsw_tmp = nullptr; // [max digits per coordinate] std GGSW (inversion result)
     int32_t* d_ggsw_tmp2 = nullptr;
     int max_digits = 0;
-    bool initialized = false, state = false, words_staged = false;
-    // Results of read_prepare_write that Ram::write recomputes on the unchanged state (FHERAM_MEMO=0 recomputes them):
-    //  memo_top  : d_trtop = trace(tree top) — the output of read_prepare_write (ram.rs:540) is the very value
-    //              write_first_step computes first (ram.rs:571-572: same ciphertext, same deterministic operations);
-    //  memo_alone: arena A holds every local row after the packer levels in which it is alone (ram.rs:514; n steps),
-    //              which ARE the first n steps of trace(ct_hi) in write_mid_step (ram.rs:616).
-    int memo = 1;
+    RamState ram;                  // this context's RAM (a bank's context: unused, the members' are in fheram_bank)
+    bool words_staged = false;
+    int memo = 1;                  // FHERAM_MEMO=0: a write recomputes what read_prepare_write could have kept (RamState::memo_top / memo_alone)
     //  tail: the dependent trace chain at the end of a read as ONE launch with in-kernel hand-offs (k_trace_tail);
     //        FHERAM_TAIL=0: one launch pair per step as before;  FHERAM_TAIL=2 / 3: test hooks, the launch gives up two steps before its end
     //        and the fused fallback launch behind it does the work.
@@ -155,13 +168,8 @@ struct fheram_ctx {
     bool opstart_valid = false;
     bool wide_unsynced = false;
     bool wdone_pending = false;
-    bool memo_top = false;
-    int memo_alone = 0;
     int32_t* d_trtop = nullptr;    // [ws]
-    int32_t* d_last_res = nullptr; // where the last read / read_prepare_write left its result (d_res or d_trtop)
-    bool tree_rotate_pending = false;
-    int32_t* d_trhi = nullptr;     // arena that holds trace(ct_hi) of the local rows during a write (A or C)
-    // fheram_read_batch (path.hpp batch_opnds / batch_arenas): buffers for batch_cap addresses, allocated on first use and grown to the largest
+    // fheram_read_batch (path.hpp batch_opnds / batch_view): buffers for batch_cap addresses, allocated on first use and grown to the largest
     // batch seen.  Ciphertext y = k * ws + w of a batch is word w of address k; the arenas keep the rows' stride (sy = rows * GLWE).
     int batch_cap = 0;
     int32_t* d_bA = nullptr;       // [K*ws][rows]  ping-pong arenas of the batch's rows
@@ -345,6 +353,17 @@ int download_i64(fheram_ctx* c, int64_t* dst, const int32_t* src, size_t n) {
             widen(c->h_pin[(k - 1) & 1], dst + off, m);
         }
     }
+    return FHERAM_OK;
+}
+// The words of a write, n_ct ciphertexts, on their way to d_w: narrowed into the pinned buffer h_w and copied asynchronously — the call
+// does not wait for the copy (the kernels that read d_w are ordered behind it on the stream; h_w is reused only after its event).
+int stage_words(fheram_ctx* c, int32_t* d_w, const int64_t* w, int n_ct) {
+    if (c->w_busy) { HIPCHK(c, hipEventSynchronize(c->ev_w)); c->w_busy = false; }
+    const size_t n = (size_t)n_ct * fheram_ctx::GLWE;
+    if (!narrow(w, c->h_w, n)) return fail(c, FHERAM_ERR_RANGE, "limb out of the normalised range [-2^16, 2^16]");
+    HIPCHK(c, hipMemcpyAsync(d_w, c->h_w, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_w, c->stream));
+    c->w_busy = true;
     return FHERAM_OK;
 }
 

@@ -366,7 +366,7 @@ int fheram_keys_load(fheram_ctx* c, const int64_t* gal_els, int n_gal, const int
     c->keys_loaded = true;
     c->inv_id[0] = c->inv_id[1] = 0;   // inverse digits prepared with the previous keys are void
     c->inv_pending[0] = c->inv_pending[1] = false;
-    c->memo_top = false; c->memo_alone = 0;   // ... and so are the traces read_prepare_write kept for the write (ram.rs:572,616 use the keys of the write)
+    c->ram.memo_top = false; c->ram.memo_alone = 0;   // ... and so are the traces read_prepare_write kept for the write (ram.rs:572,616 use the keys of the write)
     return FHERAM_OK;
 }
 
@@ -376,12 +376,12 @@ int fheram_ram_upload(fheram_ctx* c, const int64_t* rows) {
     HIPCHK(c, hipSetDevice(c->device));
     int rc = upload_i64(c, c->d_data, rows, (size_t)c->ws * c->rows * fheram_ctx::GLWE);
     if (rc != FHERAM_OK) return rc;
-    c->initialized = true; c->state = false; c->memo_top = false; c->memo_alone = 0;
+    c->ram.initialized = true; c->ram.state = false; c->ram.memo_top = false; c->ram.memo_alone = 0;
     return FHERAM_OK;
 }
 int fheram_ram_download(fheram_ctx* c, int64_t* rows) {
     if (!c || !rows) return FHERAM_ERR_INVALID_ARG;
-    if (!c->initialized) return fail(c, FHERAM_ERR_UNINITIALIZED, "unitialized memory: self.data.len()=0");
+    if (!c->ram.initialized) return fail(c, FHERAM_ERR_UNINITIALIZED, "unitialized memory: self.data.len()=0");
     HIPCHK(c, hipSetDevice(c->device));
     const int rc = download_i64(c, rows, c->d_data, (size_t)c->ws * c->rows * fheram_ctx::GLWE);
     return rc == FHERAM_OK ? check_precision(c) : rc;
@@ -392,7 +392,7 @@ int fheram_ram_tree_download(fheram_ctx* c, int level, int64_t* out) {
     HIPCHK(c, hipSetDevice(c->device));
     return download_i64(c, out, c->d_tree, (size_t)c->ws * fheram_ctx::GLWE);
 }
-int fheram_ram_state(const fheram_ctx* c) { return c ? (int)c->state : 0; }
+int fheram_ram_state(const fheram_ctx* c) { return c ? (int)c->ram.state : 0; }
 
 int fheram_address_create(fheram_ctx* c, const int64_t* const* ggsw, int n_ggsw, fheram_addr** out) {
     if (!c || !out) return FHERAM_ERR_INVALID_ARG;
@@ -422,7 +422,7 @@ void fheram_address_destroy(fheram_addr* a) {
 int fheram_result_map(fheram_ctx* c, const int64_t** out) {
     if (!c || !out) return FHERAM_ERR_INVALID_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    const ResRun run{c->d_last_res ? c->d_last_res : c->d_res, (size_t)c->ws * fheram_ctx::GLWE};
+    const ResRun run{c->ram.res_in_trtop ? c->d_trtop : c->d_res, (size_t)c->ws * fheram_ctx::GLWE};
     *out = c->h_res;
     return result_export(c, &run, 1, c->h_res, c->d_h_res, nullptr);
 }
@@ -467,9 +467,9 @@ int fheram_read(fheram_ctx* c, const fheram_addr* addr, int64_t* out) {
     int rc = check_common(c, addr);
     if (rc != FHERAM_OK) return rc;
     if (c->n_shards != 1) return fail(c, FHERAM_ERR_INVALID_ARG, "row-sharded context: use fheram_read_partial / fheram_read_finish");
-    if (c->state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.read: internal state is true -> requires calling Memory.write");
+    if (c->ram.state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.read: internal state is true -> requires calling Memory.write");
     HIPCHK(c, hipSetDevice(c->device));
-    rc = run_op(c, addr, 0, [&] { return read_impl(one_addr(c, &addr), ctx_arenas(c), false); });
+    rc = run_op(c, addr, 0, [&] { return read_impl(one_addr(c, &addr), ctx_view(c), false); });
     if (rc != FHERAM_OK) return rc;
     HIPCHK(c, hipGetLastError());
     return out ? fheram_result_download(c, out) : FHERAM_OK;
@@ -485,11 +485,11 @@ int fheram_read_batch(fheram_ctx* c, const fheram_addr* const* addrs, int n_addr
         if (rc != FHERAM_OK) return rc;
     }
     if (c->n_shards != 1) return fail(c, FHERAM_ERR_INVALID_ARG, "row-sharded context: use fheram_read_partial / fheram_read_finish");
-    if (c->state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.read: internal state is true -> requires calling Memory.write");
+    if (c->ram.state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.read: internal state is true -> requires calling Memory.write");
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
     if (n_addr == 1) {
-        rc = run_op(c, addrs[0], 0, [&] { return read_impl(one_addr(c, addrs), ctx_arenas(c), false); });
+        rc = run_op(c, addrs[0], 0, [&] { return read_impl(one_addr(c, addrs), ctx_view(c), false); });
         if (rc != FHERAM_OK) return rc;
         HIPCHK(c, hipGetLastError());
         return out ? fheram_result_download(c, out) : FHERAM_OK;
@@ -498,9 +498,9 @@ int fheram_read_batch(fheram_ctx* c, const fheram_addr* const* addrs, int n_addr
     rc = batch_reserve(c, n_addr);
     if (rc != FHERAM_OK) return rc;
     const Opnds o = batch_opnds(c, addrs, n_addr);
-    rc = read_impl(o, batch_arenas(c), false);
+    rc = read_impl(o, batch_view(c), false);
     if (rc != FHERAM_OK) return rc;
-    // what K reads leave behind: the last address's result where a read leaves it (d_last_res = d_res; nothing is kept for a write)
+    // what K reads leave behind: the last address's result where a read leaves it (RamState::res_in_trtop = false; nothing is kept for a write)
     launch_copy(c, o.slice(ref(c->d_bres, (long)fheram_ctx::GLWE, 0), n_addr - 1), ref(c->d_res, (long)fheram_ctx::GLWE, 0), 1, c->ws);
     HIPCHK(c, hipGetLastError());
     const ResRun run{c->d_bres, (size_t)n_addr * c->ws * fheram_ctx::GLWE};
@@ -510,11 +510,11 @@ int fheram_read_prepare_write(fheram_ctx* c, const fheram_addr* addr, int64_t* o
     int rc = check_common(c, addr);
     if (rc != FHERAM_OK) return rc;
     if (c->n_shards != 1) return fail(c, FHERAM_ERR_INVALID_ARG, "row-sharded context: use fheram_read_partial / fheram_read_finish");
-    if (c->state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.read: internal state is true -> requires calling Memory.write");
+    if (c->ram.state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.read: internal state is true -> requires calling Memory.write");
     HIPCHK(c, hipSetDevice(c->device));
-    rc = run_op(c, addr, 1, [&] { return read_impl(one_addr(c, &addr), ctx_arenas(c), true); });
+    rc = run_op(c, addr, 1, [&] { return read_impl(one_addr(c, &addr), ctx_view(c), true); });
     if (rc != FHERAM_OK) return rc;
-    c->state = true;                                                                  // ram.rs:533
+    c->ram.state = true;                                                                  // ram.rs:533
     HIPCHK(c, hipGetLastError());
     return out ? fheram_result_download(c, out) : FHERAM_OK;
 }
@@ -522,38 +522,31 @@ int fheram_word_stage(fheram_ctx* c, const int64_t* w, int n_w) {
     if (!c || !w) return FHERAM_ERR_INVALID_ARG;
     if (n_w != c->ws) return fail(c, FHERAM_ERR_INVALID_ARG, "w.len() != subrams.len() (ram.rs:243)");
     HIPCHK(c, hipSetDevice(c->device));
-    // narrowed into a pinned buffer of its own and copied asynchronously: the call does not wait for the copy (the kernels
-    // that read d_w are ordered behind it on the stream; the buffer is reused only after its event)
-    if (c->w_busy) { HIPCHK(c, hipEventSynchronize(c->ev_w)); c->w_busy = false; }
-    const size_t n = (size_t)c->ws * fheram_ctx::GLWE;
-    if (!narrow(w, c->h_w, n)) return fail(c, FHERAM_ERR_RANGE, "limb out of the normalised range [-2^16, 2^16]");
-    HIPCHK(c, hipMemcpyAsync(c->d_w, c->h_w, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_w, c->stream));
-    c->w_busy = true;
-    c->words_staged = true;
-    return FHERAM_OK;
+    const int rc = stage_words(c, c->d_w, w, c->ws);
+    if (rc == FHERAM_OK) c->words_staged = true;
+    return rc;
 }
 // Ram::write, ram.rs:226-294
 int fheram_write(fheram_ctx* c, const int64_t* w, int n_w, const fheram_addr* addr) {
     int rc = check_common(c, addr);
     if (rc != FHERAM_OK) return rc;
     if (n_w != c->ws) return fail(c, FHERAM_ERR_INVALID_ARG, "w.len() != subrams.len() (ram.rs:243)");
-    if (!c->state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.write: internal state is false -> requires calling Memory.read_prepare_write");
+    if (!c->ram.state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.write: internal state is false -> requires calling Memory.read_prepare_write");
     HIPCHK(c, hipSetDevice(c->device));
     if (c->n_shards != 1) return fail(c, FHERAM_ERR_INVALID_ARG, "row-sharded context: use fheram_write_root / fheram_write_shard");
     if (!w && !c->words_staged) return fail(c, FHERAM_ERR_INVALID_ARG, "w == NULL and no staged words");
     // the part of a write that needs no words (trace(ct_hi) of every row, inverse of coordinate 0) is enqueued BEFORE the host
     // narrows the words: the GPU works while the host converts
     const Opnds o = one_addr(c, &addr);
-    if (w && !c->side_begun && !(c->use_graph && !c->profile)) write_side_begin(o);
+    if (w && !c->side_begun && !(c->use_graph && !c->profile)) write_side_begin(o, ctx_view(c));
     if (w) { rc = fheram_word_stage(c, w, n_w); if (rc != FHERAM_OK) { write_side_abort(c); return rc; } }
     rc = run_op(c, addr, 2, [&] {
-        if (!c->side_begun) write_side_begin(o);   // (fheram_write_begin may have started it)
-        int r2 = write_top(o);
-        return r2 == FHERAM_OK ? write_rows(o) : r2;
+        if (!c->side_begun) write_side_begin(o, ctx_view(c));   // (fheram_write_begin may have started it)
+        int r2 = write_top(o, ctx_view(c));
+        return r2 == FHERAM_OK ? write_rows(o, ctx_view(c)) : r2;
     });
     if (rc != FHERAM_OK) return rc;
-    c->state = false;
+    c->ram.state = false;
     HIPCHK(c, hipGetLastError());
     return FHERAM_OK;
 }
@@ -584,13 +577,13 @@ int fheram_read_partial(fheram_ctx* c, const fheram_addr* addr, int prepare_writ
     int rc = check_common(c, addr);
     if (rc != FHERAM_OK) return rc;
     if (!out) return fail(c, FHERAM_ERR_INVALID_ARG, "null output");
-    if (c->state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.read: internal state is true -> requires calling Memory.write");
+    if (c->ram.state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.read: internal state is true -> requires calling Memory.write");
     HIPCHK(c, hipSetDevice(c->device));
     GlweRef packed;
-    rc = read_local(one_addr(c, &addr), ctx_arenas(c), prepare_write != 0, &packed, true);
+    rc = read_local(one_addr(c, &addr), ctx_view(c), prepare_write != 0, &packed, true);
     if (rc != FHERAM_OK) return rc;
     HIPCHK(c, hipGetLastError());
-    if (prepare_write) c->state = true;
+    if (prepare_write) c->ram.state = true;
     return export_glwes(c, c->d_part, out, out_on_device, (size_t)c->ws);   // device buffers: asynchronous, see fheram_stream_signal
 }
 int fheram_stream_signal(fheram_ctx* c, void* hip_stream) {
@@ -622,9 +615,9 @@ int fheram_device_free(fheram_ctx* c, void* ptr) {
 int fheram_write_begin(fheram_ctx* c, const fheram_addr* addr) {
     int rc = check_common(c, addr);
     if (rc != FHERAM_OK) return rc;
-    if (!c->state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.write: internal state is false -> requires calling Memory.read_prepare_write");
+    if (!c->ram.state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.write: internal state is false -> requires calling Memory.read_prepare_write");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->side_begun) write_side_begin(one_addr(c, &addr));
+    if (!c->side_begun) write_side_begin(one_addr(c, &addr), ctx_view(c));
     HIPCHK(c, hipGetLastError());
     return FHERAM_OK;
 }
@@ -641,7 +634,7 @@ int fheram_read_finish(fheram_ctx* c, const fheram_addr* addr, int prepare_write
         rc = import_glwes(c, c->d_part, partials, partials_on_device, (size_t)c->ws);
     }
     if (rc != FHERAM_OK) return rc;
-    rc = read_top(one_addr(c, &addr), ctx_arenas(c), prepare_write != 0, gathered, ref(c->d_part, (long)fheram_ctx::GLWE, 0));
+    rc = read_top(one_addr(c, &addr), ctx_view(c), prepare_write != 0, gathered, ref(c->d_part, (long)fheram_ctx::GLWE, 0));
     if (rc != FHERAM_OK) return rc;
     HIPCHK(c, hipGetLastError());
     return out ? fheram_result_download(c, out) : fheram_sync(c);
@@ -651,13 +644,13 @@ int fheram_write_root(fheram_ctx* c, const int64_t* w, int n_w, const fheram_add
     if (rc != FHERAM_OK) return rc;
     if (n_w != c->ws) return fail(c, FHERAM_ERR_INVALID_ARG, "w.len() != subrams.len() (ram.rs:243)");
     if (c->n2 != 2) return fail(c, FHERAM_ERR_INVALID_ARG, "a row-sharded RAM has two coordinates");
-    if (!c->state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.write: internal state is false -> requires calling Memory.read_prepare_write");
+    if (!c->ram.state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.write: internal state is false -> requires calling Memory.read_prepare_write");
     if (!ct_lo_out) return fail(c, FHERAM_ERR_INVALID_ARG, "null output");
     HIPCHK(c, hipSetDevice(c->device));
     if (w) { rc = fheram_word_stage(c, w, n_w); if (rc != FHERAM_OK) return rc; }
     else if (!c->words_staged) return fail(c, FHERAM_ERR_INVALID_ARG, "w == NULL and no staged words");
-    if (!c->side_begun) write_side_begin(one_addr(c, &addr));   // the root's own rows: overlaps the latency-bound head below
-    rc = write_top(one_addr(c, &addr));
+    if (!c->side_begun) write_side_begin(one_addr(c, &addr), ctx_view(c));   // the root's own rows: overlaps the latency-bound head below
+    rc = write_top(one_addr(c, &addr), ctx_view(c));
     if (rc != FHERAM_OK) return rc;
     HIPCHK(c, hipGetLastError());
     return export_glwes(c, c->d_part, ct_lo_out, out_on_device, (size_t)c->ws);
@@ -666,12 +659,12 @@ int fheram_write_shard(fheram_ctx* c, const fheram_addr* addr, const void* ct_lo
     int rc = check_common(c, addr);
     if (rc != FHERAM_OK) return rc;
     if (!ct_lo) return fail(c, FHERAM_ERR_INVALID_ARG, "null ct_lo");
-    if (!c->state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.write: internal state is false -> requires calling Memory.read_prepare_write");
+    if (!c->ram.state) return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.write: internal state is false -> requires calling Memory.read_prepare_write");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->side_begun) write_side_begin(one_addr(c, &addr));   // normally started earlier by fheram_write_begin / fheram_write_root
+    if (!c->side_begun) write_side_begin(one_addr(c, &addr), ctx_view(c));   // normally started earlier by fheram_write_begin / fheram_write_root
     rc = import_glwes(c, c->d_part, ct_lo, on_device, (size_t)c->ws);
     if (rc != FHERAM_OK) { write_side_abort(c); return rc; }
-    rc = write_rows(one_addr(c, &addr));
+    rc = write_rows(one_addr(c, &addr), ctx_view(c));
     if (rc != FHERAM_OK) return rc;
     HIPCHK(c, hipGetLastError());
     return FHERAM_OK;

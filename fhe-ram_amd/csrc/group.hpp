@@ -115,7 +115,7 @@ int group_precheck(fheram_group* g, const fheram_group_addr* ga, bool want_state
     for (int i = 0; i < g->n(); i++) {
         fheram_ctx* c = g->ctx[i];
         int rc = check_common(c, ga->a[i]);
-        if (rc == FHERAM_OK && c->state != want_state) rc = fail(c, FHERAM_ERR_STATE, state_msg);
+        if (rc == FHERAM_OK && c->ram.state != want_state) rc = fail(c, FHERAM_ERR_STATE, state_msg);
         if (rc != FHERAM_OK) { g->err = "shard " + std::to_string(i) + ": " + c->err; return rc; }
     }
     return FHERAM_OK;
@@ -148,7 +148,7 @@ int group_read_job(fheram_group* g, const fheram_group_addr* ga, bool prepare_wr
     if (hipSetDevice(c->device) != hipSuccess) return bail(fail(c, FHERAM_ERR_DEVICE, "hipSetDevice"));
     const Opnds o = one_addr(c, &addr);
     GlweRef packed;
-    rc = read_local(o, ctx_arenas(c), prepare_write, &packed, true);   // ... -> d_part
+    rc = read_local(o, ctx_view(c), prepare_write, &packed, true);   // ... -> d_part
     if (rc != FHERAM_OK) return bail(rc);
     // (ram.rs:533: the state flag is committed by the caller once EVERY shard has come through)
     hipError_t e = hipMemcpyPeerAsync(r->d_gat[0] + (size_t)i * part, r->device, c->d_part, c->device, part * sizeof(int32_t), c->stream);
@@ -160,7 +160,7 @@ int group_read_job(fheram_group* g, const fheram_group_addr* ga, bool prepare_wr
     if (!await_count(g, g->parts_recorded, g->n())) return fail(c, FHERAM_ERR_DEVICE, "a shard failed (or did not arrive within 30 s) before the exchange");
     for (int k = 0; k < g->n(); k++)
         if (k != i && hipStreamWaitEvent(c->stream, g->ev_part[k], 0) != hipSuccess) return bail(fail(c, FHERAM_ERR_DEVICE, "hipStreamWaitEvent"));
-    rc = read_top(o, ctx_arenas(c), prepare_write, c->d_gat[0], ref(c->d_part, (long)fheram_ctx::GLWE, 0));
+    rc = read_top(o, ctx_view(c), prepare_write, c->d_gat[0], ref(c->d_part, (long)fheram_ctx::GLWE, 0));
     if (rc != FHERAM_OK) return bail(rc);
     if (hipGetLastError() != hipSuccess) return bail(fail(c, FHERAM_ERR_DEVICE, "launch failure in read_top"));
     return out ? fheram_result_download(c, out) : fheram_sync(c);
@@ -176,9 +176,9 @@ int group_write_job(fheram_group* g, const fheram_group_addr* ga, int i) {
     int rc;
     if (hipSetDevice(c->device) != hipSuccess) return bail(fail(c, FHERAM_ERR_DEVICE, "hipSetDevice"));
     const Opnds o = one_addr(c, &addr);
-    if (!c->side_begun) write_side_begin(o);                              // trace(ct_hi) of the local rows, inverse of coordinate 0: no ct_lo needed
+    if (!c->side_begun) write_side_begin(o, ctx_view(c));                              // trace(ct_hi) of the local rows, inverse of coordinate 0: no ct_lo needed
     if (i == g->root) {
-        rc = write_top(o);                                                // write_first_step + inverse coordinate-1 products -> ct_lo in d_part
+        rc = write_top(o, ctx_view(c));                                                // write_first_step + inverse coordinate-1 products -> ct_lo in d_part
         if (rc != FHERAM_OK) return bail(rc);
         for (int k = 0; k < g->n(); k++) {                                // the one exchange step of a write
             if (k == i) continue;
@@ -197,7 +197,7 @@ int group_write_job(fheram_group* g, const fheram_group_addr* ga, int i) {
     // leaves all rows as they were (the root included)
     g->ready.fetch_add(1, std::memory_order_release);
     if (!await_count(g, g->ready, g->n())) { write_side_abort(c); return fail(c, FHERAM_ERR_DEVICE, "a shard failed before the rows were written: the rows are unchanged, but the tree top and the write state have been consumed — upload the RAM again"); }
-    rc = write_rows(o);                                                   // write_mid_step on the local rows, write_last_step
+    rc = write_rows(o, ctx_view(c));                                                   // write_mid_step on the local rows, write_last_step
     if (rc != FHERAM_OK) return bail(rc);
     if (hipGetLastError() != hipSuccess) return bail(fail(c, FHERAM_ERR_DEVICE, "launch failure in write_rows"));
     return fheram_sync(c);                                                // the op is complete when every shard's rows are
@@ -417,7 +417,7 @@ int fheram_group_read_prepare_write(fheram_group* g, const fheram_group_addr* ad
     if (rc != FHERAM_OK) return rc;
     g->parts_recorded.store(0); g->failed.store(false);
     rc = group_poison(g, run_all(g, [&](int i) { return group_read_job(g, addr, true, out, i); }));
-    if (rc == FHERAM_OK) for (fheram_ctx* c : g->ctx) c->state = true;      // ram.rs:533, on every shard or on none
+    if (rc == FHERAM_OK) for (fheram_ctx* c : g->ctx) c->ram.state = true;      // ram.rs:533, on every shard or on none
     return rc;
 }
 /* Ram::write (ram.rs:226-294); w == NULL uses the words staged by fheram_group_word_stage */

@@ -1,6 +1,6 @@
 // Private to fheram.hip: Ram::read / read_prepare_write / write as launch sequences (reference: src/ram.rs).
 // ONE read sequence (read_local + read_top, together read_impl) and ONE write sequence (write_side_begin, write_top, write_rows), over an
-// operand set (Opnds: whose digits a product uses) and, for reads, an arena set (ReadArenas: where it runs).  The plain context, the stages of
+// operand set (Opnds: whose digits a product uses, whose RAM state it updates) and a view (RamView: the buffers it runs on).  The plain context, the stages of
 // a row-sharded RAM (fheram.hip, group.hpp), fheram_read_batch and fheram_bank_* (bank.hpp) all run these; what is specific to one of them
 // is a visible condition in the sequence (n == 1: pre_inv, the gate wave, ev_opstart, ev_wdone, sharding, capture; a bank range: Opnds::row_fuse).
 #pragma once
@@ -15,6 +15,7 @@ namespace {
 // everywhere else.  Never sharded, never captured, never with early inverse digits (pre_inv) then.
 struct Opnds {
     fheram_ctx* c;
+    RamState* st;            // the RAM(s) operated on: read and updated as the operation is enqueued (the context's own; a bank range: the merge of its members')
     const fheram_addr* const* addrs;
     int n, ws;
     double *tab, *tab_inv;   // (inverse) digits of address 0
@@ -32,29 +33,33 @@ struct Opnds {
     // per ciphertext from the start.  (The smaller regimes — limb split, fine split, the mid chains — keep their precedence: chain_form.)
     bool row_fuse(int d, int n_tr, int gx) const { return use_row_fuse(c, d, n_tr, gx, Y(), n > 1 && own_rows); }
 };
-// the plain operation: one address (a = &addr), the context's d_prep / d_prep_inv, the context's word count (a bank view's range of one member)
-Opnds one_addr(fheram_ctx* c, const fheram_addr* const* a) { return Opnds{c, a, 1, c->ws, c->d_prep, c->d_prep_inv, 0, true}; }
+// the plain operation: one address (a = &addr), the context's d_prep / d_prep_inv, ws ciphertexts (the context's word count and RAM; one member of a bank: its)
+Opnds one_addr(fheram_ctx* c, const fheram_addr* const* a, int ws, RamState* st) { return Opnds{c, st, a, 1, ws, c->d_prep, c->d_prep_inv, 0, true}; }
+Opnds one_addr(fheram_ctx* c, const fheram_addr* const* a) { return one_addr(c, a, c->ws, &c->ram); }
 
-// A read's ARENA SET: the rows it reads, the ping-pong arenas A / B with the optional third and fourth (pack_levels P0 / P1), the per-ciphertext
-// buffers, and where the result goes.  The context's own (for a bank: the view's, bank.hpp), or a batch's (batch_arenas below).
-struct ReadArenas {
+// An operation's VIEW: every buffer indexed by ciphertext y, from the operation's first.  The rows, the ping-pong arenas A / B with the third
+// and fourth (pack_levels P0 / P1; the write's trace(ct_hi)), the per-ciphertext buffers, and where the result goes.  The context's own
+// (ctx_view), a batch's (batch_view below: a batch never writes), or a range of a bank's members (bank.hpp bank_view).
+struct RamView {
     int32_t *rows, *A, *B, *C, *D;   // [Y][rows]
-    int32_t *part, *tmp, *tmp2, *res;   // [Y]; part: the packed row where no arena holds it (rows == 1, a shard's partial)
+    int32_t *part, *tmp, *tmp2, *res, *tree, *w, *trtop;   // [Y]; part: the packed row where no arena holds it (rows == 1, a shard's partial) / the un-rotated ct_lo
 };
-ReadArenas ctx_arenas(const fheram_ctx* c) { return ReadArenas{c->d_data, c->d_scrA, c->d_scrB, c->d_scrC, c->d_scrD, c->d_part, c->d_tmp, c->d_tmp2, c->d_res}; }
+RamView ctx_view(const fheram_ctx* c) {
+    return RamView{c->d_data, c->d_scrA, c->d_scrB, c->d_scrC, c->d_scrD, c->d_part, c->d_tmp, c->d_tmp2, c->d_res, c->d_tree, c->d_w, c->d_trtop};
+}
 
 // What an operation leaves on the host, once it has been enqueued — or replayed (run_op), which does not run the enqueue functions.
 // A read has one such function per stage, because the stages of a row-sharded RAM run on different contexts.
-void read_local_done(fheram_ctx* c, bool prepare_write) {   // memo_alone: arena A keeps the rows after their alone levels (two coordinates only)
-    if (c->n2 == 2) c->memo_alone = (prepare_write && c->memo) ? LOGN - ilog2_ceil(c->rows_glob) : 0;
+void read_local_done(const fheram_ctx* c, RamState* st, bool prepare_write) {   // memo_alone: arena A keeps the rows after their alone levels (two coordinates only)
+    if (c->n2 == 2) st->memo_alone = (prepare_write && c->memo) ? LOGN - ilog2_ceil(c->rows_glob) : 0;
 }
-void read_top_done(fheram_ctx* c, bool prepare_write) {
-    c->memo_top = prepare_write && c->memo;           // d_trtop = trace(tree top), kept for the write
-    c->d_last_res = c->memo_top ? c->d_trtop : c->d_res;
+void read_top_done(fheram_ctx* c, RamState* st, bool prepare_write) {
+    st->memo_top = prepare_write && c->memo;          // trtop = trace(tree top), kept for the write
+    st->res_in_trtop = st->memo_top;
     c->prep1_ready = false;
 }
 // (inv_id / inv_pending are consumed where the write uses the inverse digits, write_side_begin and write_top; a replay finds them at 0, see run_op)
-void write_done(fheram_ctx* c) { c->memo_top = false; c->memo_alone = 0; c->side_begun = false; c->tree_rotate_pending = false; }
+void write_done(fheram_ctx* c, RamState* st) { st->memo_top = false; st->memo_alone = 0; c->side_begun = false; c->tree_rotate_pending = false; }
 
 // The launch sequence of an op is a function of (context, address, op) and of a few bits of the context's state (what a
 // write may resume from): with FHERAM_GRAPH=1 it is captured once per address and state signature into a hipGraph and
@@ -65,7 +70,7 @@ int run_op(fheram_ctx* c, const fheram_addr* addr, int which, F&& enqueue) {
     fheram_addr* a = const_cast<fheram_addr*>(addr);
     // what the enqueue function reads of the context's mutable state (a write resumes from what read_prepare_write kept —
     // or not, after a key load or with another address): a capture taken under another signature is not replayed
-    const unsigned sig = 1u | (c->memo_top ? 2u : 0u) | ((unsigned)c->memo_alone << 2) | (c->side_begun ? 64u : 0u) |
+    const unsigned sig = 1u | (c->ram.memo_top ? 2u : 0u) | ((unsigned)c->ram.memo_alone << 2) | (c->side_begun ? 64u : 0u) |
                          (c->inv_id[0] == addr->id ? 128u : 0u) | (c->inv_id[1] == addr->id ? 256u : 0u);
     if (a->graph[which] && a->graph_sig[which] != sig) { hipGraphExecDestroy(a->graph[which]); a->graph[which] = nullptr; }
     if (!a->graph[which]) {
@@ -83,8 +88,8 @@ int run_op(fheram_ctx* c, const fheram_addr* addr, int which, F&& enqueue) {
         a->graph_sig[which] = sig;
     }
     HIPCHK(c, hipGraphLaunch(a->graph[which], c->stream));
-    if (which == 2) write_done(c);
-    else { read_local_done(c, which == 1); read_top_done(c, which == 1); }
+    if (which == 2) write_done(c, &c->ram);
+    else { read_local_done(c, &c->ram, which == 1); read_top_done(c, &c->ram, which == 1); }
     return FHERAM_OK;
 }
 
@@ -92,7 +97,7 @@ int check_common(fheram_ctx* c, const fheram_addr* addr) {
     if (!c) return FHERAM_ERR_INVALID_ARG;
     mid_rearm(c);
     if (!addr || addr->ctx != c) return fail(c, FHERAM_ERR_INVALID_ARG, "address does not belong to this context (layout mismatch, ram.rs:404)");
-    if (!c->initialized) return fail(c, FHERAM_ERR_UNINITIALIZED, "unitialized memory: self.data.len()=0");
+    if (!c->ram.initialized) return fail(c, FHERAM_ERR_UNINITIALIZED, "unitialized memory: self.data.len()=0");
     if (!c->keys_loaded) return fail(c, FHERAM_ERR_KEYS, "evaluation keys not loaded");
     return FHERAM_OK;
 }
@@ -102,7 +107,7 @@ int check_common(fheram_ctx* c, const fheram_addr* addr) {
 // Stage 1 (every shard): coordinate-0 products on the local rows + the packing levels that stay
 // inside the shard.  The packed GLWE of every sub-RAM is left where the last launch wrote it (*packed_out,
 // indexed by sub-RAM); to_part also copies it into a.part (d_part: the buffer a sharded RAM exchanges).
-int read_local(const Opnds& o, const ReadArenas& a, bool prepare_write, GlweRef* packed_out, bool to_part) {
+int read_local(const Opnds& o, const RamView& a, bool prepare_write, GlweRef* packed_out, bool to_part) {
     fheram_ctx* c = o.c;
     const int n = o.n, ws = o.ws, Y = o.Y(), R = (int)c->rows;
     c->wide = !prepare_write || n > 1;   // read_prepare_write parks the gate wave beside its launches (read_top): its chain kernels keep a wave slot free; several addresses never park one
@@ -118,7 +123,7 @@ int read_local(const Opnds& o, const ReadArenas& a, bool prepare_write, GlweRef*
     for (int k = 0; k < n; k++)                                                           // ram.rs:416-419 / 496-499
         if (all) coordinate_prepare_all(c, o.addrs[k], o.tab + k * o.stride); else coordinate_prepare(c, o.addrs[k], 0, o.tab + k * o.stride);
     c->prep1_ready = all;
-    read_local_done(c, prepare_write);
+    read_local_done(c, o.st, prepare_write);
     const int d0 = (int)c->base2d[0].size();
     if (c->n2 == 1) {
         GlweRef row0 = ref(a.rows, sy, 0);
@@ -130,7 +135,7 @@ int read_local(const Opnds& o, const ReadArenas& a, bool prepare_write, GlweRef*
         return FHERAM_OK;
     }
     const int L0 = LOGN - ilog2_ceil(c->rows_glob);
-    const bool keep = c->memo_alone > 0;   // leaves = the rows then: arena A keeps the rows after their alone levels
+    const bool keep = o.st->memo_alone > 0;   // leaves = the rows then: arena A keeps the rows after their alone levels
     int32_t* packed;
     if (o.row_fuse(d0, L0, R) && !(prepare_write && (d0 & 1))) {
         // the products and the alone packer levels as ONE launch (k_read_chain; with a table: row y takes the digits of address y / ws):
@@ -151,7 +156,7 @@ int read_local(const Opnds& o, const ReadArenas& a, bool prepare_write, GlweRef*
 // [n_shards][ws] GLWEs, or nullptr when the RAM is not sharded and the packed rows are at `pk`),
 // coordinate-1 products and the final trace.  Result left in a.res (d_trtop: below).  Every step is out of place, so
 // nothing has to be copied between them.
-int read_top(const Opnds& o, const ReadArenas& a, bool prepare_write, int32_t* gathered, GlweRef pk) {
+int read_top(const Opnds& o, const RamView& a, bool prepare_write, int32_t* gathered, GlweRef pk) {
     fheram_ctx* c = o.c;
     const int n = o.n, ws = o.ws, Y = o.Y();
     c->wide = !prepare_write || n > 1;
@@ -162,7 +167,7 @@ int read_top(const Opnds& o, const ReadArenas& a, bool prepare_write, int32_t* g
     const int d1 = c->n2 == 2 ? (int)c->base2d[1].size() : 0;
     auto tail_top = [&] { return chain_form(c, ChainQuery{false, LOGN, 1, Y}).form == ChainForm::Tail; };   // the final trace: will it ask for the tail launch (as things stand now)
     const bool fuse_ep = c->n2 == 2 && c->tail_ep && d1 >= 2 && d1 <= TAIL_EP_MAX && tail_top();
-    GlweRef ep_out = ref(prepare_write ? c->d_tree : a.tmp2, G, 0);                       // read_prepare_write: tree[0] <- rotated packed row, ram.rs:525-527
+    GlweRef ep_out = ref(prepare_write ? a.tree : a.tmp2, G, 0);                          // read_prepare_write: tree[0] <- rotated packed row, ram.rs:525-527
     auto products1 = [&] { for (int k = 0; k < n; k++) ep_chain(c, o.slice(pk, k), o.slice(ep_out, k), o.slice(tmp, k), o.prep(k, 1), d1, 1, ws); };   // ram.rs:454 (not into res: the trace below runs out of place) / 525-527 + 502-504 (i = 1)
     if (c->n2 == 2) {
         if (gathered) {
@@ -182,12 +187,12 @@ int read_top(const Opnds& o, const ReadArenas& a, bool prepare_write, int32_t* g
     // lowest priority, so that launch is placed first)
     // (only while the write's chains are one workgroup round on the chip: with several rounds — 2^21 on one GPU — the
     // earlier start of the write's main chain interleaves it with the side chain less favourably, write 8.57 -> 8.74 ms)
-    const bool pre = n == 1 && prepare_write && c->pre_inv && (long)c->rows * c->ws <= c->cus;
+    const bool pre = n == 1 && prepare_write && c->pre_inv && (long)c->rows * Y <= c->cus;
     const bool gated = pre && c->pre_inv == 1 && !capturing(c) && tail_top();   // FHERAM_PRE_INV=2: event fork (A/B switch)
     if (pre && !gated)
         for (int ci = c->n2 - 1; ci >= 0; ci--) precompute_inverse(c, o.addrs[0], ci, ci == c->n2 - 1);   // coordinate 1 first: the write's head needs it first
-    read_top_done(c, prepare_write);
-    const GlweRef res = ref(c->memo_top ? c->d_trtop : a.res, G, 0);
+    read_top_done(c, o.st, prepare_write);
+    const GlweRef res = ref(o.st->memo_top ? a.trtop : a.res, G, 0);
     const uint64_t tl0 = c->tail_launches;
     GlweRef tb[2];
     if (fuse_ep && chain_bufs(LOGN, last, res, tmp, tb))                               // ram.rs:454 / 525-527 + 457 / 540 as ONE launch
@@ -206,7 +211,7 @@ int read_top(const Opnds& o, const ReadArenas& a, bool prepare_write, int32_t* g
     }
     return FHERAM_OK;
 }
-int read_impl(const Opnds& o, const ReadArenas& a, bool prepare_write) {
+int read_impl(const Opnds& o, const RamView& a, bool prepare_write) {
     fheram_ctx* c = o.c;
     GlweRef packed;
     int rc = read_local(o, a, prepare_write, &packed, false);
@@ -214,7 +219,7 @@ int read_impl(const Opnds& o, const ReadArenas& a, bool prepare_write) {
     rc = read_top(o, a, prepare_write, nullptr, packed);
     if (o.n == 1 && prepare_write && c->inv_id[0] == o.addrs[0]->id && capturing(c))   // a capture ends with every fork joined
         for (int ci = 0; ci < c->n2; ci++) hipStreamWaitEvent(c->stream, c->ev_inv[ci], 0);
-    if (rc == FHERAM_OK && prepare_write) c->state = true;                            // ram.rs:533
+    if (rc == FHERAM_OK && prepare_write) o.st->state = true;                         // ram.rs:533
     return rc;
 }
 
@@ -265,10 +270,10 @@ int batch_reserve(fheram_ctx* c, int K) {
     c->batch_cap = K;
     return FHERAM_OK;
 }
-// The batch as an operand set and an arena set for read_impl: the digits' table is d_bprep, every address reads the context's rows and the
+// The batch as an operand set and a view for read_impl: the digits' table is d_bprep, every address reads the context's rows and the
 // launches write batch arenas only.  The result of address k is at d_bres + k * ws GLWEs; rows == 1: the products land in d_btmp2.
-Opnds batch_opnds(fheram_ctx* c, const fheram_addr* const* addrs, int K) { return Opnds{c, addrs, K, c->ws, c->d_bprep, nullptr, (long)c->n_digits * (long)fheram_ctx::GGSW, false}; }
-ReadArenas batch_arenas(const fheram_ctx* c) { return ReadArenas{c->d_data, c->d_bA, c->d_bB, c->d_bC, nullptr, c->d_btmp2, c->d_btmp, c->d_btmp2, c->d_bres}; }
+Opnds batch_opnds(fheram_ctx* c, const fheram_addr* const* addrs, int K) { return Opnds{c, &c->ram, addrs, K, c->ws, c->d_bprep, nullptr, (long)c->n_digits * (long)fheram_ctx::GGSW, false}; }
+RamView batch_view(const fheram_ctx* c) { return RamView{c->d_data, c->d_bA, c->d_bB, c->d_bC, nullptr, c->d_btmp2, c->d_btmp, c->d_btmp2, c->d_bres, nullptr, nullptr, nullptr}; }
 
 // The one result export: every run (source, int32 count) is widened by the device into the pinned buffer h (device address d_h), back to
 // back, with the monitor's maximum as it stood then behind the last (the export kernel copies it there); out != nullptr: copied out.
@@ -295,23 +300,23 @@ int result_export(fheram_ctx* c, const ResRun* runs, int n_runs, int64_t* h, int
 // Ram::write (ram.rs:226-294) of every address of the operand set, in two stages and a side stage.
 // Stage 1 (root / unsharded): write_first_step on the top of the tree and, for n2 == 2, the inverse
 // coordinate-1 products: leaves the un-rotated ct_lo of every sub-RAM in d_part.
-int write_top(const Opnds& o) {
+int write_top(const Opnds& o, const RamView& v) {
     fheram_ctx* c = o.c;
     c->wide = true;             // (everything a write enqueues runs behind read_prepare_write's trace chain, whose placement releases the gate wave)
     const long G = (long)fheram_ctx::GLWE;
     const long sy = (long)c->rows * G;
     const int n = o.n, ws = o.ws, Y = o.Y();
-    GlweRef wref = ref(c->d_w, G, 0), tmp = ref(c->d_tmp, G, 0), tmp2 = ref(c->d_tmp2, G, 0), tree = ref(c->d_tree, G, 0);
+    GlweRef wref = ref(v.w, G, 0), tmp = ref(v.tmp, G, 0), tmp2 = ref(v.tmp2, G, 0), tree = ref(v.tree, G, 0);
     // write_first_step (ram.rs:544-577): t <- normalize(t - trace(t) + w)
-    GlweRef top = (c->n2 != 1) ? tree : ref(c->d_data, sy, 0);
+    GlweRef top = (c->n2 != 1) ? tree : ref(v.rows, sy, 0);
     GlweRef tr = tmp;
-    if (c->memo_top) tr = ref(c->d_trtop, G, 0);      // = trace(top), computed by read_prepare_write on this very ciphertext
+    if (o.st->memo_top) tr = ref(v.trtop, G, 0);     // = trace(top), computed by read_prepare_write on this very ciphertext
     else trace_steps(c, top, tmp, tmp2, 0, LOGN, 1, Y);
     {
         ProfScope ps(c, "elementwise", Y);
         hipLaunchKernelGGL((k_sub_add_norm<3>), dim3(1, Y, EW_SLICES), dim3(256), 0, c->cur, top, tr, wref, top);
     }
-    c->memo_top = false;
+    o.st->memo_top = false;
     if (c->n2 == 2) {
         // the head: per address, the inverse of coordinate 1 (ram.rs:260-271) and its products on the address's tree top (ram.rs:610)
         if (n == 1 && c->inv_id[1] == o.addrs[0]->id) wait_inverse(c, c->stream, 1);    // started by read_prepare_write
@@ -323,7 +328,7 @@ int write_top(const Opnds& o) {
         }
         if (n == 1) { c->inv_pending[1] = false; c->inv_id[1] = 0; }
         for (int k = 0; k < n; k++)                                                        // ram.rs:610: the un-rotated ct_lo, in d_part
-            ep_chain(c, o.slice(tree, k), o.slice(ref(c->d_part, G, 0), k), o.slice(tmp, k), o.inv(k, 1), (int)c->base2d[1].size(), 1, ws);
+            ep_chain(c, o.slice(tree, k), o.slice(ref(v.part, G, 0), k), o.slice(tmp, k), o.inv(k, 1), (int)c->base2d[1].size(), 1, ws);
         // tree[0] <- ct_lo * X^-rows (ram.rs:629, `rows` rotations by X^-1): nothing in this write reads it again, so
         // the rotation is enqueued behind the rows' work (write_rows) instead of in front of it
         c->tree_rotate_pending = true;
@@ -334,7 +339,7 @@ int write_top(const Opnds& o) {
 // (ram.rs:616) and the inverse of coordinate 0 (ram.rs:278-289).  It is enqueued on the side stream
 // so that it fills the CUs the latency-bound stage 1 (a chain of word_size-ciphertext launches)
 // leaves idle.
-void write_side_begin(const Opnds& o) {
+void write_side_begin(const Opnds& o, const RamView& v) {
     fheram_ctx* c = o.c;
     c->wide = true;
     const long G = (long)fheram_ctx::GLWE;
@@ -343,16 +348,11 @@ void write_side_begin(const Opnds& o) {
     hipStreamWaitEvent(c->stream2, c->ev_fork, 0);
     c->cur = c->stream2;
     if (c->n2 == 2) {                                 // every row of every address: ONE chain
-        c->d_trhi = c->d_scrA;
-        if (c->memo_alone > 0) {   // arena A = the rows after trace steps 0 .. memo_alone-1 (left there by read_prepare_write)
-            // ping-pong A <-> C; an odd number of remaining steps ends in C
-            if ((LOGN - c->memo_alone) % 2 == 1) c->d_trhi = c->d_scrC;
-            int32_t* tmp = c->d_trhi == c->d_scrA ? c->d_scrC : c->d_scrA;
-            trace_steps(c, ref(c->d_scrA, sy, G), ref(c->d_trhi, sy, G), ref(tmp, sy, G), c->memo_alone, LOGN, (int)c->rows, o.Y());
-        } else {
-            trace_steps(c, ref(c->d_data, sy, G), ref(c->d_scrA, sy, G), ref(c->d_scrC, sy, G), 0, LOGN, (int)c->rows, o.Y());
-        }
-        c->memo_alone = 0;
+        const int kept = o.st->memo_alone;   // > 0: arena A = the rows after trace steps 0 .. kept-1 (left there by read_prepare_write)
+        c->trhi_in_C = kept > 0 && (LOGN - kept) % 2 == 1;   // ping-pong A <-> C; an odd number of remaining steps ends in C
+        if (kept > 0) trace_steps(c, ref(v.A, sy, G), ref(c->trhi_in_C ? v.C : v.A, sy, G), ref(c->trhi_in_C ? v.A : v.C, sy, G), kept, LOGN, (int)c->rows, o.Y());
+        else trace_steps(c, ref(v.rows, sy, G), ref(v.A, sy, G), ref(v.C, sy, G), 0, LOGN, (int)c->rows, o.Y());
+        o.st->memo_alone = 0;
     }
     if (o.n == 1 && c->inv_id[0] == o.addrs[0]->id) wait_inverse(c, c->stream2, 0);   // started by read_prepare_write (on this very stream)
     else for (int k = 0; k < o.n; k++) coordinate_prepare_inv(c, o.addrs[k], 0, c->d_ggsw_tmp2, o.inv(k, 0));   // (a precompute for another address sits on this very stream: ordered)
@@ -369,14 +369,14 @@ void write_side_abort(fheram_ctx* c) {
     c->side_begun = false;
 }
 // Stage 2 (every shard): write_mid_step on the local rows given ct_lo (in d_part), then write_last_step.
-int write_rows(const Opnds& o) {
+int write_rows(const Opnds& o, const RamView& v) {
     fheram_ctx* c = o.c;
     c->wide = true;
     const long G = (long)fheram_ctx::GLWE;
     const long sy = (long)c->rows * G;
     const int n = o.n, ws = o.ws, Y = o.Y(), R = (int)c->rows;
-    GlweRef data = ref(c->d_data, sy, G), A = ref(c->d_scrA, sy, G), B = ref(c->d_scrB, sy, G), D = ref(c->d_scrD, sy, G);
-    GlweRef trhi = ref(c->d_trhi ? c->d_trhi : c->d_scrA, sy, G), part = ref(c->d_part, G, 0);
+    GlweRef data = ref(v.rows, sy, G), A = ref(v.A, sy, G), B = ref(v.B, sy, G), D = ref(v.D, sy, G);
+    GlweRef trhi = ref(c->trhi_in_C ? v.C : v.A, sy, G), part = ref(v.part, G, 0);
     const int d0 = (int)c->base2d[0].size();
     const bool fuse = c->n2 == 2 && o.row_fuse(d0, LOGN, R);
     if (fuse) {
@@ -389,7 +389,7 @@ int write_rows(const Opnds& o) {
         trace_steps(c, part, B, D, 0, LOGN, R, Y, c->n_shards, c->shard);                      // tmp_a = trace(ct_lo * X^-row)   ram.rs:621,629
     if (c->tree_rotate_pending) {   // root / unsharded: the tree's copy of ct_lo, rotated (see write_top)
         ProfScope ps(c, "elementwise", Y);
-        hipLaunchKernelGGL((k_rotate<3>), dim3(1, Y, EW_SLICES), dim3(256), 0, c->cur, part, ref(c->d_tree, G, 0), -(int)c->rows_glob);
+        hipLaunchKernelGGL((k_rotate<3>), dim3(1, Y, EW_SLICES), dim3(256), 0, c->cur, part, ref(v.tree, G, 0), -(int)c->rows_glob);
     }
     if (!fuse) {
         hipStreamWaitEvent(c->stream, c->ev_join, 0);                                          // side stream: trace(ct_hi), inverse coordinate 0
@@ -402,8 +402,8 @@ int write_rows(const Opnds& o) {
     // the next read_prepare_write's side work overwrites d_prep_inv: it is ordered behind this write by an event (the gate
     // launch in front of that work is time-bounded, so it cannot be the only ordering); a table's inverse digits have no such reader
     if (n == 1 && !capturing(c)) { hipEventRecord(c->ev_wdone, c->stream); c->wdone_pending = true; }
-    write_done(c);
-    c->state = false;                                                                          // ram.rs:648
+    write_done(c, o.st);
+    o.st->state = false;                                                                       // ram.rs:648
     return FHERAM_OK;
 }
 

@@ -227,7 +227,7 @@ int fheram_ram_encrypt_sk(fheram_ctx* c, const fheram_secret* sk, const uint8_t*
             rc = encrypt_staged(c, sk->d_hat, c->d_data + (w * c->rows + x0) * G, pre, nullptr, (int)nx, S);
             if (rc != FHERAM_OK) return rc;
         }
-    c->initialized = true; c->state = false;
+    c->ram.initialized = true; c->ram.state = false;
     return FHERAM_OK;
 }
 
@@ -357,7 +357,7 @@ int fheram_keys_encrypt_sk(fheram_ctx* c, const fheram_secret* sk, const int64_t
     c->keys_loaded = true;
     c->inv_id[0] = c->inv_id[1] = 0;
     c->inv_pending[0] = c->inv_pending[1] = false;
-    c->memo_top = false; c->memo_alone = 0;
+    c->ram.memo_top = false; c->ram.memo_alone = 0;
     return FHERAM_OK;
 }
 

@@ -425,6 +425,47 @@ def test_one_row_and_identical_members_2_12(po):
     assert e.value.code == ST_INVALID_ARG
 
 
+def test_one_row_ranges_of_distinct_members_2_12(po):
+    """2^12 again, where the rows themselves are the tree top and part / tmp stand in for the arenas — now with a word size of 2, so
+    that a member's offset is not its ciphertext's, distinct members, and ranges that start behind member 0: every member equals its
+    standalone Ram and the members outside a range keep their rows and state."""
+    M = 3
+    w = World(po, 1 << 12, M, word_size=2, seed=120, n_addr=2)
+    bank = w.new_bank(M)
+    rams = [w.new_ram(m) for m in range(M)]
+    a, b = w.addrs
+    vals, wct = w.words(M, seed=121)
+
+    def member0_untouched(what):   # (no tree at one coordinate: rows and state are all a member has)
+        assert bank.state(0) is False, what
+        assert np.array_equal(bank.store_encrypted(0), rows0), what
+
+    rows0 = bank.store_encrypted(0)
+    got = bank.read_prepare_write([a, b], w.keys, first=1)
+    for k, (m, adr) in enumerate(((1, a), (2, b))):
+        assert np.array_equal(got[k], rams[m].read_prepare_write(adr, w.keys)), m
+        assert bank.state(m) is True
+    member0_untouched("rpw [1,3)")
+    bank.write(wct[1:3], [a, b], w.keys, first=1)
+    for m, adr in ((1, a), (2, b)):
+        rams[m].write(wct[m], adr, w.keys)
+        assert np.array_equal(bank.store_encrypted(m), rams[m].store_encrypted()), m
+        assert bank.state(m) is False
+    member0_untouched("write [1,3)")
+    got = bank.read([a], w.keys, first=2)
+    assert np.array_equal(got[0], rams[2].read(a, w.keys))
+    res = bank.result(1, 2)   # member 1: what its read_prepare_write left (in another buffer); member 2: the read just done
+    assert np.array_equal(res[0], rams[1].result()) and np.array_equal(res[1], rams[2].result())
+    got = bank.read([b, a, b], w.keys)
+    for m, adr in enumerate((b, a, b)):
+        assert np.array_equal(got[m], rams[m].read(adr, w.keys)), m
+    data1 = w.data[1].copy()
+    data1[w.ws * w.idx[0]: w.ws * (w.idx[0] + 1)] = vals[1]
+    w.check_word(got[1], data1, 0, written=True)
+    w.check_word(got[0], w.data[0], 1)
+    member0_untouched("end")
+
+
 def test_2_18_two_members_against_two_contexts():
     """Synthetic normalised limbs for keys, address digits, rows and words (no oracle encryption at this size): a bank step equals two
     standalone contexts by SHA-256 of results and rows, takes no fallback, and its round-off stays where the contexts' own is."""

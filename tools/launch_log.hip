@@ -6,13 +6,24 @@
 // gated) over a sweep of configurations, chain lengths, grids and buffer layouts.  Two trees dispatch alike exactly when their logs are
 // equal, so a change to a launch form is one `diff` away from its evidence:
 //
-//   hipcc -std=c++17 -O1 --offload-arch=gfx950 -ftrivial-auto-var-init=zero -Wno-unused-variable -I fhe-ram_amd/csrc -I tools -o launch_log tools/launch_log.hip
+//   hipcc -std=c++17 -O1 --offload-arch=gfx950 -ftrivial-auto-var-init=zero -Wno-unused-variable -Wno-unused-value -Wl,--unresolved-symbols=ignore-all -I fhe-ram_amd/csrc -I tools -o launch_log tools/launch_log.hip
 //   ./launch_log > profiles/chain_form_launch_log.txt      one digest line per configuration (FNV-1a over its launch lines)
 //   ./launch_log 17                                        every launch line of configuration 17
 //
 // -ftrivial-auto-var-init=zero makes the padding of the argument structs part of a reproducible digest.  The include path names the
 // csrc/ to log; launch_log_shim.hpp (tools/ for this tree) reaches what has no name of its own there.
 // Trace chains are logged for 0 .. LOGN steps (the context has LOGN trace keys), product chains and the predicates for 0 .. CHAIN_MAX + 1.
+//
+// Second mode, the SEQUENCES themselves (path.hpp read_impl and the write triple) for a context, a batch and ranges of a bank's members:
+//
+//   ./launch_log path > profiles/ram_view_path_log.txt     one digest line per configuration
+//   ./launch_log path 17                                   every line of configuration 17
+//
+// Every buffer is a fake arena 4 GiB from the next, so an argument that points into one shows as a<arena>+<byte offset> behind the launch's
+// digest, events show as record / wait lines, and after every operation the log holds each RAM's state, the flags of the write in flight and
+// the context's buffer fields and word count: a range's pointer arithmetic, and anything an operation leaves behind in the context, is in
+// the log.  What differs between trees — how a bank range is presented to the sequences, where the per-RAM state lives — is in the shim.
+// bank.hpp names entry points of fheram.hip that this program never calls: link with -Wl,--unresolved-symbols=ignore-all.
 #include <hip/hip_runtime.h>
 #include <sys/mman.h>
 #include <cinttypes>
@@ -22,7 +33,7 @@
 #include <string>
 
 namespace ll {
-bool verbose = false;
+bool verbose = false, path_mode = false;
 uint64_t digest = 0, lines = 0;
 hipStream_t main_stream = nullptr;
 uint64_t fnv(uint64_t h, const void* p, size_t n) {
@@ -72,6 +83,21 @@ std::string kernel_name(const char* text, const char* site_) {
     }
     return out;
 }
+// a fake device address (arena k of fake<>() below: k + 1 in the upper half) as a<k>+<byte offset>; anything else: empty
+std::string arena_of(uint64_t v) {
+    if (v < 0x100000000ull || v >= 0x10000000000ull) return "";
+    char buf[48];
+    std::snprintf(buf, sizeof buf, "a%u+%#x", (unsigned)(v >> 32) - 1, (unsigned)v);
+    return buf;
+}
+void arenas_in(std::string& out, const void* p, size_t n) {   // the 8-byte words of an argument that hold such an address
+    for (size_t i = 0; i + 8 <= n; i += 8) {
+        uint64_t v;
+        std::memcpy(&v, static_cast<const char*>(p) + i, 8);
+        const std::string a = arena_of(v);
+        if (!a.empty()) out += " " + a;
+    }
+}
 template <typename... A>
 void record(const char* kernel, const char* site, dim3 g, dim3 b, size_t lds, hipStream_t s, const A&... a) {
     uint64_t h = 0xcbf29ce484222325ull;
@@ -80,17 +106,26 @@ void record(const char* kernel, const char* site, dim3 g, dim3 b, size_t lds, hi
     char buf[512];
     std::snprintf(buf, sizeof buf, "  %s grid=(%u,%u,%u) wg=%u lds=%zu %s args=%zuB:%016" PRIx64, kernel_name(kernel, site).c_str(), g.x, g.y, g.z, b.x, lds,
                   s == main_stream ? "main" : "side", bytes, h);
-    line(buf);
+    std::string l = buf;
+    if (path_mode) (arenas_in(l, &a, sizeof(a)), ...);
+    line(l);
+}
+hipError_t event(const char* what, const void* ev, hipStream_t s) {
+    if (path_mode) line(std::string("  ") + what + " " + arena_of((uint64_t)(uintptr_t)ev) + (s == main_stream ? " main" : " side"));
+    return hipSuccess;
 }
 }  // namespace ll
 
 #undef hipLaunchKernelGGL
 #define hipLaunchKernelGGL(kernel, grid, block, lds, stream, ...) ll::record(#kernel, __PRETTY_FUNCTION__, grid, block, lds, stream, __VA_ARGS__)
-// ProfScope under `profile`: no event is created or recorded
+// no event is created, recorded or waited for, no stream waited for (ProfScope under `profile`; the sequences of path mode, where record and wait are logged)
 #define hipEventCreate(e) (*(e) = nullptr, hipSuccess)
-#define hipEventRecord(e, s) ((void)(e), (void)(s), hipSuccess)
+#define hipEventRecord(e, s) ll::event("record", e, s)
+#define hipStreamWaitEvent(s, e, flags) ll::event("wait", e, s)
+#define hipStreamSynchronize(s) ((void)(s), hipSuccess)
+#define hipGetLastError() hipSuccess
 
-#include "path.hpp"
+#include "bank.hpp"
 #include <launch_log_shim.hpp>   // (angle brackets: from the include path, not from beside this file)
 
 namespace {
@@ -222,7 +257,7 @@ void run_config(fheram_ctx* c) {
         head("predicates", n, gx, gy, 0);
         long bits = 0;
         for (int n_tr = 0; n_tr <= CHAIN_MAX + 1; n_tr++) {
-            const Opnds ctx{c, nullptr, 1, gy, nullptr, nullptr, 0, true}, batch{c, nullptr, 2, (gy + 1) / 2, nullptr, nullptr, 0, false}, bank{c, nullptr, 2, (gy + 1) / 2, nullptr, nullptr, 0, true};
+            const Opnds ctx = shim_opnds(c, 1, gy, true), batch = shim_opnds(c, 2, (gy + 1) / 2, false), bank = shim_opnds(c, 2, (gy + 1) / 2, true);
             bits = bits * 8 + (ctx.row_fuse(n, n_tr, gx) ? 1 : 0) + (batch.row_fuse(n, n_tr, gx) ? 2 : 0) + (bank.row_fuse(n, n_tr, gx) ? 4 : 0);
         }
         tail_line("row_fuse (ctx, batch, bank) x n_tr", bits);
@@ -235,12 +270,179 @@ void run_config(fheram_ctx* c) {
     }
 }
 
+// ---- path mode: the sequences on a context, a batch and ranges of a bank's members ---------------------------------------------------
+// the switch settings the bank suite forces (tests/test_gpu_bank.py FORMS, as fheram_ctx_create_cfg derives them)
+const Setting PATH_SETTINGS[] = {
+    {"default", [](fheram_ctx*) {}},
+    {"tail=0", [](fheram_ctx* c) { c->tail = 0; }},
+    {"tail_ep=0", [](fheram_ctx* c) { c->tail_ep = 0; }},
+    {"mid=0", [](fheram_ctx* c) { c->mid = 0; }},
+    {"fuse=0", [](fheram_ctx* c) { c->fuse = 0; }},
+    {"chain_y=0", [](fheram_ctx* c) { c->chain_y = 0; }},
+    {"memo=0", [](fheram_ctx* c) { c->memo = 0; c->pre_inv = 0; }},
+    {"pre_inv=0", [](fheram_ctx* c) { c->pre_inv = 0; }},
+    {"pre_inv=2", [](fheram_ctx* c) { c->pre_inv = 2; }},
+    {"safe", [](fheram_ctx* c) { c->safe = 1; c->tail = 0; c->tail_test = 0; c->mid = 0; c->mid_test = 0; c->pre_inv = 2; c->monitor = 2; }},
+};
+const int PATH_LOG_MAX_ADDR[] = {12, 13, 14, 16, 18};
+
+// the buffers indexed by ciphertext: arena(i) for field i; the batch's: arena(16 + i)
+struct Field { const char* name; int32_t* fheram_ctx::*p; };
+const Field FIELDS[] = {{"data", &fheram_ctx::d_data}, {"scrA", &fheram_ctx::d_scrA}, {"scrB", &fheram_ctx::d_scrB}, {"scrC", &fheram_ctx::d_scrC},
+                        {"scrD", &fheram_ctx::d_scrD}, {"tree", &fheram_ctx::d_tree}, {"res", &fheram_ctx::d_res}, {"tmp", &fheram_ctx::d_tmp},
+                        {"tmp2", &fheram_ctx::d_tmp2}, {"w", &fheram_ctx::d_w}, {"part", &fheram_ctx::d_part}, {"trtop", &fheram_ctx::d_trtop}};
+const Field BATCH_FIELDS[] = {{"bA", &fheram_ctx::d_bA}, {"bB", &fheram_ctx::d_bB}, {"bC", &fheram_ctx::d_bC}, {"bres", &fheram_ctx::d_bres},
+                              {"btmp", &fheram_ctx::d_btmp}, {"btmp2", &fheram_ctx::d_btmp2}};
+
+fheram_ctx* make_path_ctx(unsigned* host_words, int lg, int ws, int s_evk, const Setting& st) {
+    fheram_ctx* c = make_ctx(host_words);
+    c->cus = 256; c->s_evk = s_evk; c->atk = (size_t)fheram_ctx::DNUM_CT * s_evk * 2 * N;
+    c->ws = ws; c->rows = c->rows_glob = (size_t)1 << (lg - LOGN);
+    c->base2d.clear();
+    for (int bits = lg; bits != 0;) {   // get_base_2d with DECOMP_N = [3, 3, 3, 3] (fheram_ctx_create_cfg)
+        std::vector<int> v;
+        for (int i = 0; i < 4; i++) {
+            if (3 <= bits) { v.push_back(3); bits -= 3; }
+            else { if (bits != 0) { v.push_back(bits); bits = 0; } break; }
+        }
+        c->base2d.push_back(v);
+    }
+    c->n2 = (int)c->base2d.size();
+    for (auto& v : c->base2d) { c->n_digits += (int)v.size(); c->max_digits = std::max(c->max_digits, (int)v.size()); }
+    c->d_prep_inv = fake<double*>(14); c->d_ggsw_tmp = fake<int32_t*>(15); c->d_ggsw_tmp2 = fake<int32_t*>(16); c->d_ggsw_inv = fake<int32_t*>(17);
+    c->d_atk_inv = fake<double*>(18); c->d_tsk = fake<double*>(19);
+    c->ev_fork = fake<hipEvent_t>(20); c->ev_join = fake<hipEvent_t>(21); c->ev_inv[0] = fake<hipEvent_t>(22); c->ev_inv[1] = fake<hipEvent_t>(23);
+    c->ev_wdone = fake<hipEvent_t>(24); c->ev_opstart = fake<hipEvent_t>(25);
+    c->d_bprep = fake<double*>(26);
+    for (int i = 0; i < 12; i++) c->*FIELDS[i].p = arena(i);
+    for (int i = 0; i < 6; i++) c->*BATCH_FIELDS[i].p = arena(16 + i);
+    c->batch_cap = 4;
+    c->keys_loaded = true;
+    c->cur = c->stream;
+    st.apply(c);
+    return c;
+}
+fheram_addr* make_addr(fheram_ctx* c, int k) { return new fheram_addr{c, fake<int32_t*>(56 + k), c->n_digits, 0}; }
+
+uint64_t path_ops = 0;
+void op(const std::string& what) { path_ops++; ll::line(what); }
+// what an operation left in the context: its own RAM state, the flags of the write in flight, every buffer field and the word count
+void dump_ctx(const fheram_ctx* c) {
+    const ShimState s = shim_state(c);
+    char buf[160];
+    std::snprintf(buf, sizeof buf, "  -> ctx state=%d memo_top=%d memo_alone=%d res_in_trtop=%d | side_begun=%d trhi=%c rotate_pending=%d words_staged=%d | ws=%d", s.state,
+                  s.memo_top, s.memo_alone, s.res_in_trtop, c->side_begun, c->side_begun ? shim_trhi(c) : '-', c->tree_rotate_pending, c->words_staged, c->ws);
+    std::string l = buf;
+    for (const Field& f : FIELDS) l += std::string(" ") + f.name + "=" + ll::arena_of((uint64_t)(uintptr_t)(c->*f.p));
+    ll::line(l);
+}
+void dump_bank(const fheram_bank* b) {
+    for (int m = 0; m < b->M; m++) {
+        const ShimState s = shim_state(b, m);
+        char buf[128];
+        std::snprintf(buf, sizeof buf, "  -> member %d state=%d memo_top=%d memo_alone=%d res_in_trtop=%d", m, s.state, s.memo_top, s.memo_alone, s.res_in_trtop);
+        ll::line(buf);
+    }
+    dump_ctx(b->c);
+}
+// where the words of a write are staged, between the side stage and the top: the destination, the count, the flags of the write in flight
+auto staging(fheram_ctx* c, int rc) {
+    return [c, rc](const int32_t* d_w, int n_ct) {
+        char buf[128];
+        std::snprintf(buf, sizeof buf, "  word stage -> %s, %d ciphertexts%s | side_begun=%d trhi=%c", ll::arena_of((uint64_t)(uintptr_t)d_w).c_str(), n_ct,
+                      rc == FHERAM_OK ? "" : " (refused)", c->side_begun, c->n2 == 2 ? shim_trhi(c) : '-');
+        ll::line(buf);
+        return rc;
+    };
+}
+void synced(fheram_ctx* c) { c->wide_unsynced = false; }   // the host has waited for the stream (a result download)
+
+void run_path_ctx(fheram_ctx* c) {
+    const fheram_addr* a[4];
+    for (int k = 0; k < 4; k++) a[k] = make_addr(c, k);
+    shim_loaded(c);
+    op("ctx read a0"); shim_read(c, a[0], false); dump_ctx(c); synced(c);
+    op("ctx read_prepare_write a0"); shim_read(c, a[0], true); dump_ctx(c); synced(c);
+    op("ctx write a0"); shim_write(c, a[0], staging(c, FHERAM_OK)); dump_ctx(c);
+    op("ctx read_prepare_write a1 (the host does not wait)"); shim_read(c, a[1], true); dump_ctx(c);
+    op("ctx write a1 after a key load"); shim_new_keys(c); c->inv_id[0] = c->inv_id[1] = 0; c->inv_pending[0] = c->inv_pending[1] = false;
+    shim_write(c, a[1], staging(c, FHERAM_OK)); dump_ctx(c);
+    op("ctx read a0"); shim_read(c, a[0], false); dump_ctx(c); synced(c);
+    for (int K = 2; K <= 4; K += 2) {
+        op("ctx read_batch K=" + std::to_string(K));
+        c->d_bC = batch_needs_third(c, K) ? arena(18) : nullptr;   // (as batch_reserve allocates it)
+        shim_batch(c, a, K);
+        launch_copy(c, ref(c->d_bres + (size_t)(K - 1) * c->ws * fheram_ctx::GLWE, (long)fheram_ctx::GLWE, 0), ref(c->d_res, (long)fheram_ctx::GLWE, 0), 1, c->ws);   // (fheram_read_batch)
+        dump_ctx(c); synced(c);
+    }
+    for (int k = 0; k < 4; k++) delete a[k];
+}
+void bank_step(fheram_bank* b, int first, int n, const fheram_addr* const* a, int stage_rc = FHERAM_OK) {
+    const std::string r = " [" + std::to_string(first) + ", " + std::to_string(first + n) + ")";
+    op("bank read_prepare_write" + r); shim_bank_read(b, first, n, a, true); dump_bank(b); synced(b->c);
+    if (stage_rc != FHERAM_OK) { op("bank write" + r + ", words refused"); shim_bank_write(b, first, n, a, staging(b->c, stage_rc)); dump_bank(b); }
+    op("bank write" + r); shim_bank_write(b, first, n, a, staging(b->c, FHERAM_OK)); dump_bank(b);
+    op("bank read" + r); shim_bank_read(b, first, n, a, false); dump_bank(b); synced(b->c);
+}
+void run_path_bank(fheram_ctx* c, int M, int mws) {
+    fheram_bank* b = new fheram_bank();
+    b->c = c; b->M = M; b->mws = mws;
+    b->d_prep = fake<double*>(60); b->d_prep_inv = fake<double*>(61);
+    if (M > 1) c->pre_inv = 0;   // (fheram_bank_create)
+    shim_loaded(b);
+    const fheram_addr* a[3];
+    for (int k = 0; k < 3; k++) a[k] = make_addr(c, k);
+    ll::line("bank M=" + std::to_string(M));
+    bank_step(b, 0, M, a, M == 2 ? FHERAM_ERR_RANGE : FHERAM_OK);
+    if (M == 3) {
+        bank_step(b, 1, 1, a + 1);   // one member: the plain operation, memo kept
+        bank_step(b, 1, 2, a + 1);
+        op("bank read_prepare_write [0, 1)"); shim_bank_read(b, 0, 1, a, true); dump_bank(b); synced(c);
+        op("bank read_prepare_write [1, 3)"); shim_bank_read(b, 1, 2, a + 1, true); dump_bank(b); synced(c);
+        op("bank write [0, 3) over both"); shim_bank_write(b, 0, 3, a, staging(c, FHERAM_OK)); dump_bank(b);
+        op("bank read [2, 3)"); shim_bank_read(b, 2, 1, a + 2, false); dump_bank(b); synced(c);
+    }
+    for (int k = 0; k < 3; k++) delete a[k];
+    delete b;
+}
+
+int path_main(long only, unsigned* host_words) {
+    ll::path_mode = true;
+    if (only < 0) {
+        std::string legend = "# arenas:";
+        for (int i = 0; i < 12; i++) legend += std::string(" a") + std::to_string(32 + i) + "=" + FIELDS[i].name;
+        for (int i = 0; i < 6; i++) legend += std::string(" a") + std::to_string(48 + i) + "=" + BATCH_FIELDS[i].name;
+        std::puts(legend.c_str());
+        std::puts("# a13=prep a14=prep_inv a15=ggsw_tmp a16=ggsw_tmp2 a17=ggsw_inv a26=bprep a56..=address digits a60=bank prep a61=bank prep_inv; events: a20=fork a21=join a22,a23=inv a24=wdone a25=opstart");
+    }
+    long id = 0;
+    for (int lg : PATH_LOG_MAX_ADDR) for (int ws : {1, 4}) for (int s_evk = 4; s_evk <= 5; s_evk++) for (const Setting& st : PATH_SETTINGS) {
+        if (only >= 0 && id != only) { id++; continue; }
+        ll::verbose = only >= 0;
+        ll::digest = 0xcbf29ce484222325ull; ll::lines = 0; path_ops = 0;
+        std::printf("config %ld: max_addr=2^%d word_size=%d s_evk=%d %s\n", id, lg, ws, s_evk, st.name);
+        fheram_ctx* c = make_path_ctx(host_words, lg, ws, s_evk, st);
+        run_path_ctx(c);
+        delete c;
+        for (int M = 1; M <= 3; M++) {
+            c = make_path_ctx(host_words, lg, M * ws, s_evk, st);
+            run_path_bank(c, M, ws);
+            delete c;
+        }
+        std::printf("config %ld: %" PRIu64 " operations, %" PRIu64 " lines, digest %016" PRIx64 "\n", id, path_ops, ll::lines, ll::digest);
+        id++;
+    }
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
-    const long only = argc > 1 ? std::atol(argv[1]) : -1;
+    const bool path = argc > 1 && !std::strcmp(argv[1], "path");
+    const long only = argc > 1 + path ? std::atol(argv[1 + path]) : -1;
     unsigned* host_words = static_cast<unsigned*>(mmap(reinterpret_cast<void*>(0x7e0000000000ull), 4096, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_FIXED_NOREPLACE, -1, 0));
     if (host_words == MAP_FAILED) { std::perror("mmap"); return 1; }
+    if (path) return path_main(only, host_words);
     long id = 0;
     for (int cus : CUS) for (int s_evk = 4; s_evk <= 5; s_evk++) for (const Setting& st : SETTINGS)
     for (int side = 0; side < 2; side++) for (int graph = 0; graph < 2; graph++) for (int profile = 0; profile < 2; profile++, id++) {
