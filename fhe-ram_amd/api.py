@@ -27,6 +27,7 @@ I64P = C.POINTER(C.c_int64)
 
 READ_BATCH_MAX = 8   # FHERAM_READ_BATCH_MAX (include/fheram.h)
 BANK_MAX = 8         # FHERAM_BANK_MAX
+DERIVE_MAX = 8       # FHERAM_DERIVE_MAX
 STATUS = {0: "OK", 1: "INVALID_ARG", 2: "STATE", 3: "UNINITIALIZED", 4: "KEYS", 5: "UNSUPPORTED", 6: "RANGE", 7: "DEVICE", 8: "PRECISION"}
 
 
@@ -121,6 +122,11 @@ _SYMBOLS = [
     ("fheram_fheuint_download", C.c_int, [C.c_void_p, C.c_void_p, I64P]),
     ("fheram_fheuint_destroy", None, [C.c_void_p]),
     ("fheram_address_set_from_fheuint", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    ("fheram_address_alloc", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("fheram_address_derive", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_fheuint_create", C.c_int, [C.c_void_p, I64P, C.c_int, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_address_alloc", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_address_derive", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     ("fheram_timer_begin", C.c_int, [C.c_void_p]),
     ("fheram_timer_end", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("fheram_profile_enable", C.c_int, [C.c_void_p, C.c_int]),
@@ -365,6 +371,8 @@ class Address:
         """std-form GGSW digits on the host; an address encrypted on the device downloads them on first use"""
         if self._digits is None:
             h = next(iter(self._handles.values()))
+            if isinstance(h.ram, RamBank):
+                raise FheRamError(5, "the digits of an address derived on a bank stay on its device (the ABI has no bank form of fheram_address_download)")
             n_digits = self.base2d.as_1d().size()
             out = np.zeros((n_digits, h.ram.params.ggsw_len()), dtype=np.int64)
             h.ram._chk(library().fheram_address_download(h.ram._h, h.h, _p(out)))
@@ -401,6 +409,19 @@ class Address:
         ram._chk(library().fheram_address_set_from_fheuint(ram._h, fheuint._h, int(bool(sign)), C.byref(out)))
         self._digits = None
         self._handles = {id(ram): _AddrHandle(out.value, ram)}
+        return self
+
+    @classmethod
+    def alloc(cls, owner):
+        """an address on `owner`'s device (a Ram or a RamBank) with its buffers and no digits yet (fheram_address_alloc): what
+        derive_addresses fills; read / write refuse it until then"""
+        self = cls.__new__(cls)
+        self.base2d = owner.params.base2d()
+        out = C.c_void_p()
+        fn = library().fheram_bank_address_alloc if isinstance(owner, RamBank) else library().fheram_address_alloc
+        owner._chk(fn(owner._h, C.byref(out)))
+        self._digits = None
+        self._handles = {id(owner): _AddrHandle(out.value, owner)}
         return self
 
     @classmethod
@@ -467,10 +488,12 @@ class FheUintPrepared:
         self.ram, self._h, self.n_bits = ram, handle, n_bits
 
     @classmethod
-    def from_host(cls, ram: "Ram", bits):
+    def from_host(cls, ram, bits):
+        """ram: a Ram, or a RamBank (fheram_bank_fheuint_create: an integer any member's addresses can be derived from)"""
         bits = _i64(bits)
         out = C.c_void_p()
-        ram._chk(library().fheram_fheuint_create(ram._h, _p(bits), bits.shape[0], C.byref(out)))
+        fn = library().fheram_bank_fheuint_create if isinstance(ram, RamBank) else library().fheram_fheuint_create
+        ram._chk(fn(ram._h, _p(bits), bits.shape[0], C.byref(out)))
         return cls(ram, out.value, bits.shape[0])
 
     @classmethod
@@ -487,6 +510,8 @@ class FheUintPrepared:
         return cls(ram, out.value, n_bits)
 
     def download(self) -> np.ndarray:
+        if isinstance(self.ram, RamBank):
+            raise FheRamError(5, "an integer created on a bank stays on its device (the ABI has no bank form of fheram_fheuint_download)")
         out = np.zeros((self.n_bits, library().fheram_fheuint_ggsw_len(self.ram._h)), dtype=np.int64)
         self.ram._chk(library().fheram_fheuint_download(self.ram._h, self._h, _p(out)))
         return out
@@ -495,6 +520,30 @@ class FheUintPrepared:
         if getattr(self, "_h", None) and _LIB is not None:
             _LIB.fheram_fheuint_destroy(self._h)
             self._h = None
+
+
+def _derive_addresses(owner, fn, fheuints, addrs, sign):
+    """Ram.derive_addresses / RamBank.derive_addresses: addrs[i] <- Address::set_from_fheuint(fheuints[i]) as ONE launch"""
+    fheuints = list(fheuints)
+    k = len(fheuints)
+    if not 1 <= k <= DERIVE_MAX:
+        raise FheRamError(1, f"derive_addresses takes 1 to DERIVE_MAX = {DERIVE_MAX} integers, got {k}")
+    if not all(isinstance(f, FheUintPrepared) for f in fheuints):
+        raise FheRamError(1, "derive_addresses: every integer must be a FheUintPrepared")
+    if addrs is None:
+        addrs = [Address.alloc(owner) for _ in range(k)]
+    else:
+        addrs = list(addrs)
+        if len(addrs) != k or not all(isinstance(a, Address) for a in addrs):
+            raise FheRamError(1, f"derive_addresses: {k} integers need {k} Address objects")
+    handles = [a._bank(owner) if isinstance(owner, RamBank) else a._device(owner) for a in addrs]   # (an address made from host digits: created here)
+    fa, aa = (C.c_void_p * k)(*[f._h for f in fheuints]), (C.c_void_p * k)(*handles)
+    owner._chk(fn(owner._h, fa, k, int(bool(sign)), aa))
+    for a, f in zip(addrs, fheuints):
+        a._digits = None                                               # the host copy, and the handles on other devices, held the old digits
+        a._handles = {id(owner): a._handles[id(owner)]}
+        a._derived_from = f                                            # the integer stays alive until the launch that reads it has run
+    return addrs
 
 
 class _AddrHandle:
@@ -777,6 +826,13 @@ class Ram:
             self._check_out(out)
         self._chk(library().fheram_read_prepare_write(self._h, address._device(self), _p(out) if download else None))
         return out if download else None
+
+    def derive_addresses(self, fheuints, addrs=None, sign: bool = False):
+        """addrs[i] <- Address::set_from_fheuint(fheuints[i]) (conversion.rs:68-82) for 1 to DERIVE_MAX encrypted integers as ONE launch
+        on this Ram's stream (fheram_address_derive): no allocation, no host wait; later operations that use the addresses are ordered
+        behind it.  addrs: existing Address objects to overwrite in place (from Address.alloc, host digits, encrypt_sk or an earlier
+        derivation; no address twice), or None to allocate them.  sign=False: the convention Ram.read accepts.  Returns the addresses."""
+        return _derive_addresses(self, library().fheram_address_derive, fheuints, addrs, sign)
 
     def write(self, w, address: Address, keys: EvaluationKeysPrepared):  # ram.rs:226
         self._use_keys(keys)
@@ -1241,6 +1297,11 @@ class RamBank:
             raise FheRamError(1, f"w.len() != subrams.len() (ram.rs:243): expected {n} x {p.word_size()} GLWEs")
         self._use_keys(keys)
         self._chk(library().fheram_bank_write(self._h, first, n, _p(w), arr))
+
+    def derive_addresses(self, fheuints, addrs=None, sign: bool = False):
+        """as Ram.derive_addresses, with integers and addresses bound to this bank (FheUintPrepared.from_host(bank, ...),
+        Address.alloc(bank)): a derived address is an ordinary bank address and may serve several members"""
+        return _derive_addresses(self, library().fheram_bank_address_derive, fheuints, addrs, sign)
 
     def result(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
         """the results of each member's last read / read_prepare_write"""

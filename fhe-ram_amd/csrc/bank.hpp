@@ -51,8 +51,10 @@ int bank_check(fheram_bank* b, int first, int n, const fheram_addr* const* addrs
     mid_rearm(c);
     if (first < 0 || n < 1 || first > b->M - n)
         return fail(c, FHERAM_ERR_INVALID_ARG, "member range [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") is empty or outside the bank's " + std::to_string(b->M) + " members");
-    if (addrs) for (int k = 0; k < n; k++)
+    if (addrs) for (int k = 0; k < n; k++) {
         if (!addrs[k] || addrs[k]->ctx != c) return fail(c, FHERAM_ERR_INVALID_ARG, "address " + std::to_string(k) + " is null or does not belong to this bank (layout mismatch, ram.rs:404)");
+        if (addrs[k]->empty) return fail(c, FHERAM_ERR_INVALID_ARG, "address " + std::to_string(k) + " is an empty address: fheram_bank_address_alloc without fheram_bank_address_derive");
+    }
     for (int m = first; m < first + n; m++)
         if (!b->ram[m].initialized) return fail(c, FHERAM_ERR_UNINITIALIZED, "unitialized memory: self.data.len()=0 (member " + std::to_string(m) + ")");
     if (want_state < 0) return FHERAM_OK;
@@ -204,6 +206,21 @@ int fheram_bank_ram_state(const fheram_bank* b, int member) { return (b && membe
 int fheram_bank_address_create(fheram_bank* b, const int64_t* const* ggsw, int n_ggsw, fheram_addr** out) {
     if (!b) return FHERAM_ERR_INVALID_ARG;
     return fheram_address_create(b->c, ggsw, n_ggsw, out);
+}
+
+// Addresses derived from encrypted integers (setup.hpp fheram_address_derive): the bank's integers, addresses and the one launch are its
+// context's; a derived address is an ordinary bank address and may serve several members.
+int fheram_bank_fheuint_create(fheram_bank* b, const int64_t* bits, int n_bits, fheram_fheuint** out) {
+    if (!b) return FHERAM_ERR_INVALID_ARG;
+    return fheram_fheuint_create(b->c, bits, n_bits, out);
+}
+int fheram_bank_address_alloc(fheram_bank* b, fheram_addr** out) {
+    if (!b) return FHERAM_ERR_INVALID_ARG;
+    return fheram_address_alloc(b->c, out);
+}
+int fheram_bank_address_derive(fheram_bank* b, const fheram_fheuint* const* fus, int n, int sign, fheram_addr* const* addrs) {
+    if (!b) return FHERAM_ERR_INVALID_ARG;
+    return fheram_address_derive(b->c, fus, n, sign, addrs);
 }
 
 int fheram_bank_read(fheram_bank* b, int first, int n, const fheram_addr* const* addrs, int64_t* out) {

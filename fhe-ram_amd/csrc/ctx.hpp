@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/fheram.h"
 #include "kernels.hpp"
+#include "cmux_chain.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -167,6 +168,11 @@ struct fheram_ctx {
     hipEvent_t ev_opstart = nullptr;
     bool opstart_valid = false;
     bool wide_unsynced = false;
+    // The second reason for the record: the side work reads the address's digits (coordinate_prepare_inv), and fheram_address_derive writes
+    // them with a launch on the main stream that no host wait follows.  The gate wave is time-bounded, so it cannot be what orders that
+    // read behind the launch: derive_unsynced = such a launch has been enqueued and the host has not waited for the stream since; the next
+    // gated read_prepare_write then records ev_opstart behind it, whatever wide_unsynced says.
+    bool derive_unsynced = false;
     bool wdone_pending = false;
     int32_t* d_trtop = nullptr;    // [ws]
     // fheram_read_batch (path.hpp batch_opnds / batch_view): buffers for batch_cap addresses, allocated on first use and grown to the largest
@@ -208,6 +214,7 @@ struct fheram_addr {
     uint64_t id = next_addr_id();   // never reused (a freed address may be followed by another one at the same pointer)
     hipGraphExec_t graph[3] = {nullptr, nullptr, nullptr};   // captured launch sequences: read, read_prepare_write, write
     unsigned graph_sig[3] = {0, 0, 0};                       // context state the capture depended on (run_op)
+    bool empty = false;                                      // fheram_address_alloc: buffers and no digits yet; read / write refuse it until fheram_address_derive has filled it
 };
 
 struct fheram_fheuint {

@@ -217,6 +217,7 @@ int fheram_ctx_create_cfg(const fheram_params* p, int device, int shard, int n_s
     LDSATTR((&k_encrypt_sk<3, 0>)); LDSATTR((&k_encrypt_sk<3, 1>));
     LDSATTR((&k_encrypt_sk<4, 0>)); LDSATTR((&k_encrypt_sk<4, 1>));
     LDSATTR((&k_encrypt_sk<5, 0>)); LDSATTR((&k_encrypt_sk<5, 1>));
+    CCHK(cmux_chain_register());
 #undef LDSATTR_KS
 #undef LDSATTR_KS4
 #undef LDSATTR
@@ -439,7 +440,7 @@ int fheram_sync(fheram_ctx* c) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
-    c->wide_unsynced = false;
+    c->wide_unsynced = c->derive_unsynced = false;
     return check_precision(c);
 }
 int fheram_roundoff_max(fheram_ctx* c, double* max_out) {
@@ -772,7 +773,7 @@ int fheram_timer_end(fheram_ctx* c, float* ms) {
     HIPCHK(c, hipEventRecord(c->t1, c->stream));
     HIPCHK(c, hipEventSynchronize(c->t1));
     HIPCHK(c, hipEventElapsedTime(ms, c->t0, c->t1));
-    c->wide_unsynced = false;   // (t1 was recorded behind everything enqueued on the main stream)
+    c->wide_unsynced = c->derive_unsynced = false;   // (t1 was recorded behind everything enqueued on the main stream)
     return check_precision(c);
 }
 int fheram_profile_enable(fheram_ctx* c, int on) {

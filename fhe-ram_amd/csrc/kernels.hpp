@@ -16,6 +16,9 @@
 //                               twice more for k_read_chain_b / _bw, the read chain of fheram_read_batch)
 //   write_chain.inc             k_write_chain, and k_write_chain_b with a per-member operand table (fheram_bank_write)
 //   trace_tail.inc              k_trace_tail, and k_trace_tail_b with per-address products (fheram_read_batch)
+//   cmux_chain.hip              k_cmux_chain: the CMux chains of Address::set_from_fheuint for K integers as one launch (fheram_address_derive),
+//                               a translation unit of its own (cmux_chain.hpp).  It includes this file for the helpers and templates, so a kernel
+//                               that is NOT a template must sit inside #ifndef FK_NO_PLAIN_KERNELS here (else the two units define it twice: a link error)
 //
 // Device GLWE layout: int32 [limb][col][N] (the host's int64 layout narrowed; limbs are
 // normalised to 17 bits so nothing is lost).  Prepared operands: double, transform domain,
@@ -154,6 +157,7 @@ __device__ __forceinline__ void gstore_i32(int32_t* base, unsigned byte_off, int
 // phi_g to its INPUT instead of to every output limb:  phi_g(sum_r x_r * K_r) = sum_r phi_g(x_r) * phi_g(K_r).
 // ---------------------------------------------------------------------------------------
 constexpr size_t LDS_PREPARE_BYTES = (size_t)(LDS_TW + 2 * LDS_DATA) * sizeof(double);
+#ifndef FK_NO_PLAIN_KERNELS   // (cmux_chain.hip: a second translation unit takes the helpers and templates only)
 __global__ __launch_bounds__(T) void k_prepare(const int32_t* __restrict__ in, double* __restrict__ out,
                                                const double* __restrict__ tw_g, double ninv, int ginv, int npoly) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -200,6 +204,7 @@ __global__ __launch_bounds__(T) void k_prepare(const int32_t* __restrict__ in, d
         }
     }
 }
+#endif
 
 // acc += x (.) g for one prepared polynomial: 4 complex points per thread, (re, im) = elements (2kk, 2kk+1); 4 FMAs per point
 __device__ __forceinline__ void cmac(double& ar, double& ai, double xr, double xi, double gr, double gi) {
@@ -1844,9 +1849,11 @@ __device__ __forceinline__ GlweRef batch_src_row(GlweRef a, const RowChainBatchA
 constexpr int TAIL_GROUPS = 8;
 // One wave on the side stream that holds back what is enqueued behind it until the single-launch trace chain of
 // generation `seq` says its workgroups are placed (sync[8*32 + 2]), or GATE_SPIN_MAX polls have passed (a few ms: only the
-// timing of the work behind it depends on this, never a result).  An event recorded on the main stream for the same
+// timing of the work behind it depends on this, never a result: whatever that work READS must be ordered by something else —
+// the address's digits behind a fheram_address_derive launch by ev_opstart, ctx.hpp derive_unsynced).  An event recorded on the main stream for the same
 // purpose delays the launch behind it by 7-13 us; a stream wait-value makes the command processor poll (slower still).
 constexpr int GATE_SPIN_MAX = 1 << 13;
+#ifndef FK_NO_PLAIN_KERNELS   // (cmux_chain.hip: a second translation unit takes the helpers and templates only)
 __global__ __launch_bounds__(64) void k_tail_gate(const unsigned* gate, unsigned seq) {
     if (threadIdx.x != 0) return;
     for (int spin = 0; spin < GATE_SPIN_MAX; spin++) {
@@ -1854,6 +1861,7 @@ __global__ __launch_bounds__(64) void k_tail_gate(const unsigned* gate, unsigned
         __builtin_amdgcn_s_sleep(8);
     }
 }
+#endif
 constexpr int TAIL_SPIN_MAX = 1 << 14;   // x one L2 round trip (>= 0.3 us) >= 5 ms
 struct TailArgs {
     GlweRef src, buf[2];             // step i writes buf[i & 1] (buf[0] must not be the source)
@@ -2573,6 +2581,7 @@ __global__ __launch_bounds__(T, T / 256) void k_chain_mid(MidArgs ma) {
 
 // int32 device limbs -> int64 host layout, written straight into pinned host memory (the result of a read)
 // mon: the round-off monitor's maximum (fft_dev.hpp), copied behind the result: the host sees it with the result, for free
+#ifndef FK_NO_PLAIN_KERNELS   // (cmux_chain.hip: a second translation unit takes the helpers and templates only)
 __global__ __launch_bounds__(256) void k_export_i64(const int32_t* __restrict__ src, long long* __restrict__ dst, int n4, const long long* mon) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i == 0) dst[4 * (long)n4] = __hip_atomic_load(mon, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2583,6 +2592,7 @@ __global__ __launch_bounds__(256) void k_export_i64(const int32_t* __restrict__ 
     reinterpret_cast<longlong2*>(dst)[2 * i] = a;
     reinterpret_cast<longlong2*>(dst)[2 * i + 1] = b;
 }
+#endif
 // out = a   (glwe_copy, ram.rs:526,535,537)
 template <int S>
 __global__ __launch_bounds__(256) void k_copy(GlweRef a, GlweRef out) {

@@ -97,6 +97,7 @@ int check_common(fheram_ctx* c, const fheram_addr* addr) {
     if (!c) return FHERAM_ERR_INVALID_ARG;
     mid_rearm(c);
     if (!addr || addr->ctx != c) return fail(c, FHERAM_ERR_INVALID_ARG, "address does not belong to this context (layout mismatch, ram.rs:404)");
+    if (addr->empty) return fail(c, FHERAM_ERR_INVALID_ARG, "empty address: fheram_address_alloc without fheram_address_derive");
     if (!c->ram.initialized) return fail(c, FHERAM_ERR_UNINITIALIZED, "unitialized memory: self.data.len()=0");
     if (!c->keys_loaded) return fail(c, FHERAM_ERR_KEYS, "evaluation keys not loaded");
     return FHERAM_OK;
@@ -111,7 +112,7 @@ int read_local(const Opnds& o, const RamView& a, bool prepare_write, GlweRef* pa
     fheram_ctx* c = o.c;
     const int n = o.n, ws = o.ws, Y = o.Y(), R = (int)c->rows;
     c->wide = !prepare_write || n > 1;   // read_prepare_write parks the gate wave beside its launches (read_top): its chain kernels keep a wave slot free; several addresses never park one
-    if (n == 1 && prepare_write && c->pre_inv == 1 && !capturing(c) && c->wide_unsynced) {   // the gate wave may not be parked before this op's own launches start (ctx.hpp: ev_opstart)
+    if (n == 1 && prepare_write && c->pre_inv == 1 && !capturing(c) && (c->wide_unsynced || c->derive_unsynced)) {   // the gate wave may not be parked before this op's own launches start, nor its work read digits a derive launch is still writing (ctx.hpp: ev_opstart)
         hipEventRecord(c->ev_opstart, c->stream);
         c->opstart_valid = true;
     }
@@ -201,7 +202,7 @@ int read_top(const Opnds& o, const RamView& a, bool prepare_write, int32_t* gath
         if (fuse_ep) products1();                                                      // (cannot happen with these buffers; kept for safety)
         trace_steps(c, last, res, tmp, 0, LOGN, 1, Y);                                 // ram.rs:457 / 540
     }
-    if (gated && !c->opstart_valid && c->wide_unsynced) {   // (a root's read_finish: no read_local of this op ran on this context)
+    if (gated && !c->opstart_valid && (c->wide_unsynced || c->derive_unsynced)) {   // (a root's read_finish: no read_local of this op ran on this context)
         hipEventRecord(c->ev_opstart, c->stream);
         c->opstart_valid = true;
     }
@@ -288,7 +289,7 @@ int result_export(fheram_ctx* c, const ResRun* runs, int n_runs, int64_t* h, int
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
-    c->wide_unsynced = false;
+    c->wide_unsynced = c->derive_unsynced = false;
     double m;
     std::memcpy(&m, h + n, 8);
     if (c->monitor && m > MON_LIMIT) __atomic_store_n(c->h_ro_flag, 1u, __ATOMIC_RELAXED);

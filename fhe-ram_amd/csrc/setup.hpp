@@ -286,6 +286,7 @@ int fheram_address_encrypt_sk(fheram_ctx* c, const fheram_secret* sk, uint32_t v
 int fheram_address_download(fheram_ctx* c, const fheram_addr* a, int64_t* out) {
     if (!c || !out) return FHERAM_ERR_INVALID_ARG;
     if (!a || a->ctx != c) return fail(c, FHERAM_ERR_INVALID_ARG, "address belongs to another context");
+    if (a->empty) return fail(c, FHERAM_ERR_INVALID_ARG, "empty address: fheram_address_alloc without fheram_address_derive");
     HIPCHK(c, hipSetDevice(c->device));
     return download_i64(c, out, a->d_ggsw, (size_t)a->n_digits * fheram_ctx::GGSW);
 }
@@ -495,6 +496,79 @@ int fheram_address_set_from_fheuint(fheram_ctx* c, const fheram_fheuint* f, int 
     hipFree(big);
     if (e != hipSuccess) { fheram_address_destroy(a); return fail(c, FHERAM_ERR_DEVICE, std::string("set_from_fheuint: ") + hipGetErrorString(e)); }
     *out = a;
+    return FHERAM_OK;
+}
+
+// ---- fheram_address_derive: the same conversion for K integers as ONE launch on the context's stream (k_cmux_chain, cmux_chain.hip) ----
+// No allocation, no host wait, into existing addresses: what a host needs whose every address comes from an encrypted integer.
+int fheram_address_alloc(fheram_ctx* c, fheram_addr** out) {
+    if (!c || !out) return FHERAM_ERR_INVALID_ARG;
+    *out = nullptr;
+    HIPCHK(c, hipSetDevice(c->device));
+    fheram_addr* a = new fheram_addr{c, nullptr, c->n_digits, c->device};
+    a->empty = true;
+    const hipError_t e = hipMalloc(&a->d_ggsw, (size_t)c->n_digits * fheram_ctx::GGSW * sizeof(int32_t));
+    if (e != hipSuccess) { delete a; return fail(c, FHERAM_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+    *out = a;
+    return FHERAM_OK;
+}
+int fheram_address_derive(fheram_ctx* c, const fheram_fheuint* const* fus, int n, int sign, fheram_addr* const* addrs) {
+    if (!c) return FHERAM_ERR_INVALID_ARG;
+    if (!fus || !addrs) return fail(c, FHERAM_ERR_INVALID_ARG, "null integer or address list");
+    if (n < 1 || n > FHERAM_DERIVE_MAX)
+        return fail(c, FHERAM_ERR_INVALID_ARG, "n = " + std::to_string(n) + " is outside [1, FHERAM_DERIVE_MAX = " + std::to_string(FHERAM_DERIVE_MAX) + "]");
+    static_assert(FHERAM_DERIVE_MAX == DERIVE_K_MAX, "the argument struct of k_cmux_chain holds FHERAM_DERIVE_MAX integers and addresses");
+    unsigned bits = 0;
+    for (auto& b1 : c->base2d) for (int b : b1) bits += (unsigned)b;
+    for (int k = 0; k < n; k++) {   // every check for the whole list before anything is enqueued: a refused call changes no address
+        if (!fus[k] || fus[k]->ctx != c) return fail(c, FHERAM_ERR_INVALID_ARG, "integer " + std::to_string(k) + " is null or belongs to another context");
+        if (!addrs[k] || addrs[k]->ctx != c) return fail(c, FHERAM_ERR_INVALID_ARG, "address " + std::to_string(k) + " is null or belongs to another context");
+        if ((int)bits > fus[k]->n_bits) return fail(c, FHERAM_ERR_INVALID_ARG, "the address plan is wider than the encrypted integer");
+        for (int q = 0; q < k; q++)
+            if (addrs[q] == addrs[k]) return fail(c, FHERAM_ERR_INVALID_ARG, "address " + std::to_string(k) + " appears twice in the list");
+    }
+    if (c->n_digits > DERIVE_DIGITS_MAX)
+        return fail(c, FHERAM_ERR_UNSUPPORTED, "fheram_address_derive takes digit plans of at most " + std::to_string(DERIVE_DIGITS_MAX) + " digits");
+    HIPCHK(c, hipSetDevice(c->device));
+    CmuxChainArgs ca{};
+    ca.tw = c->d_tw;
+    ca.sign = sign ? 1 : 0;
+    {
+        int digit = 0;
+        unsigned bit_rsh = 0;
+        for (auto& base1d : c->base2d) {                                                      // conversion.rs:45
+            unsigned bit_lsh = 0;                                                             // :46
+            for (int bit_mask : base1d) {                                                     // :49
+                ca.first[digit] = (unsigned char)bit_rsh; ca.bits[digit] = (unsigned char)bit_mask; ca.lsh[digit] = (unsigned char)bit_lsh;
+                bit_lsh += (unsigned)bit_mask;                                                // :61
+                bit_rsh += (unsigned)bit_mask;                                                // :62
+                digit++;
+            }
+        }
+    }
+    // Work of an earlier operation that still reads these digits on the side stream: inverse digits started early by read_prepare_write
+    // (precompute_inverse: ev_inv) and the side stage of a write that has begun and not yet joined (write_side_begin: ev_join).
+    bool wait_inv[2] = {false, false};
+    for (int k = 0; k < n; k++) {
+        ca.fu[k] = fus[k]->d_prep;
+        ca.out[k] = addrs[k]->d_ggsw;
+        for (int ci = 0; ci < 2; ci++) if (c->inv_pending[ci] && c->inv_id[ci] == addrs[k]->id) wait_inv[ci] = true;
+    }
+    for (int ci = 0; ci < 2; ci++) if (wait_inv[ci]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_inv[ci], 0));
+    if (c->side_begun) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
+    c->cur = c->stream;
+    {
+        const int rows = fheram_ctx::DNUM_CT * 2;
+        ProfScope ps(c, "derive", (uint64_t)n * c->n_digits * rows);
+        cmux_chain_launch(dim3(rows, c->n_digits, n), c->cur, ca);
+    }
+    HIPCHK(c, hipGetLastError());
+    // The handle now names other digits: a fresh id, so that nothing the context remembers by identity (inverse digits started early for the
+    // old ones, run_op's signature) can be resumed.  The captured launch sequences stay: they read d_ggsw, which has not moved, when replayed.
+    for (int k = 0; k < n; k++) { addrs[k]->id = next_addr_id(); addrs[k]->empty = false; }
+    // ... and a later read_prepare_write must not let its side work read them before this launch has run: the gate wave in front of that
+    // work gives up after a few ms, so the op records ev_opstart behind this launch (ctx.hpp derive_unsynced; read_local / read_top).
+    c->derive_unsynced = true;
     return FHERAM_OK;
 }
 

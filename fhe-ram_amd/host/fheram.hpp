@@ -249,6 +249,25 @@ public:
         chk(fheram_address_set_from_fheuint(ctx_, fheuint.h_, sign ? 1 : 0, &a.h_));
         a.owner_ = this;
     }
+    // The same for 1 to FHERAM_DERIVE_MAX integers as ONE launch on this Ram's stream (fheram_address_derive): no allocation, no host wait;
+    // later operations that use the addresses are ordered behind it.  *addrs[i] is overwritten in place when it already lives on this
+    // Ram's device (whatever made it) and gets its device buffers here otherwise; its host digits are dropped.  No address twice.  The
+    // integers must stay alive until sync().
+    void derive(const std::vector<const FheUintPrepared*>& fheuints, const std::vector<Address*>& addrs, bool sign = false) {
+        if (fheuints.empty() || fheuints.size() > FHERAM_DERIVE_MAX || addrs.size() != fheuints.size())
+            throw Error(FHERAM_ERR_INVALID_ARG, "derive takes 1 to FHERAM_DERIVE_MAX integers and as many addresses");
+        std::vector<const fheram_fheuint*> fh;
+        std::vector<fheram_addr*> ah;
+        for (const FheUintPrepared* f : fheuints) { if (!f) throw Error(FHERAM_ERR_INVALID_ARG, "null integer"); fh.push_back(f->h_); }
+        for (Address* a : addrs) {
+            if (!a) throw Error(FHERAM_ERR_INVALID_ARG, "null address");
+            if (a->h_ && a->owner_ != this) { fheram_address_destroy(a->h_); a->h_ = nullptr; }
+            if (!a->h_) { chk(fheram_address_alloc(ctx_, &a->h_)); a->owner_ = this; }
+            ah.push_back(a->h_);
+        }
+        chk(fheram_address_derive(ctx_, fh.data(), (int)fh.size(), sign ? 1 : 0, ah.data()));
+        for (Address* a : addrs) a->digits.clear();
+    }
     // EvaluationKeys::encrypt_sk + EvaluationKeysPrepared::prepare, keys.rs:135-180,57-71: generated and
     // prepared on this context; `keys` is marked as the set in use (its std forms stay empty).
     void encrypt_keys(EvaluationKeysPrepared& keys, const Secret& sk, Source& source_xa, Source& source_xe) {
@@ -420,6 +439,33 @@ public:
         use(keys);
         std::vector<const fheram_addr*> h = handles(addresses);
         chk(fheram_bank_write(bank_, first, (int)h.size(), flat.data(), h.data()));
+    }
+    // an encrypted integer on the bank's device, from host ciphertexts [n_bits][fheram_fheuint_ggsw_len] (fheram_bank_fheuint_create)
+    class FheUintPrepared {
+    public:
+        FheUintPrepared(Bank& bank, const std::vector<int64_t>& bits, int n_bits) { bank.chk(fheram_bank_fheuint_create(bank.bank_, bits.data(), n_bits, &h_)); }
+        ~FheUintPrepared() { if (h_) fheram_fheuint_destroy(h_); }
+        FheUintPrepared(const FheUintPrepared&) = delete;
+    private:
+        friend class Bank;
+        fheram_fheuint* h_ = nullptr;
+    };
+    // as Ram::derive (fheram_bank_address_derive): *addrs[i] becomes an ordinary address of this bank, which may serve several members
+    void derive(const std::vector<const FheUintPrepared*>& fheuints, const std::vector<Address*>& addrs, bool sign = false) {
+        if (fheuints.empty() || fheuints.size() > FHERAM_DERIVE_MAX || addrs.size() != fheuints.size())
+            throw Error(FHERAM_ERR_INVALID_ARG, "derive takes 1 to FHERAM_DERIVE_MAX integers and as many addresses");
+        std::vector<const fheram_fheuint*> fh;
+        std::vector<fheram_addr*> ah;
+        for (const FheUintPrepared* f : fheuints) { if (!f) throw Error(FHERAM_ERR_INVALID_ARG, "null integer"); fh.push_back(f->h_); }
+        for (Address* a : addrs) {
+            if (!a) throw Error(FHERAM_ERR_INVALID_ARG, "null address");
+            fheram_addr* h = nullptr;
+            for (auto& kv : addr_) if (kv.first == a) h = kv.second;
+            if (!h) { chk(fheram_bank_address_alloc(bank_, &h)); addr_.emplace_back(a, h); }
+            ah.push_back(h);
+        }
+        chk(fheram_bank_address_derive(bank_, fh.data(), (int)fh.size(), sign ? 1 : 0, ah.data()));
+        for (Address* a : addrs) a->digits.clear();
     }
     void sync() { chk(fheram_bank_sync(bank_)); }
     double roundoff_max() { double m = 0.0; chk(fheram_bank_roundoff_max(bank_, &m)); return m; }

@@ -402,6 +402,27 @@ void fheram_fheuint_destroy(fheram_fheuint* fu);
  * Address::encrypt_sk, address.rs:102-108, i.e. an address Ram::read accepts). */
 int fheram_address_set_from_fheuint(fheram_ctx* ctx, const fheram_fheuint* fu, int sign, fheram_addr** out);
 
+/* ---- The same conversion on a step's critical path: K addresses from K encrypted integers as ONE launch, into existing addresses.
+ * (The CONTRACT-COMPATIBLE-ONLY warning above applies unchanged: same input type, same contract, same digits bit for bit.) */
+#define FHERAM_DERIVE_MAX 8
+/* an address with its device buffers and no digits yet; read / write refuse it (FHERAM_ERR_INVALID_ARG, "empty address") until derived */
+int fheram_address_alloc(fheram_ctx* ctx, fheram_addr** out);
+/* addrs[i] <- Address::set_from_fheuint(fus[i]) for i < n, as ONE launch enqueued on the context's stream.  No allocation, no
+ * host wait: returns once enqueued; later operations of ctx that use addrs[i] are ordered behind it.  sign as in
+ * fheram_address_set_from_fheuint.  addrs[i] may come from fheram_address_alloc, _create, _encrypt_sk or an earlier derivation
+ * (overwritten in place).  The integers must stay alive until the context has been synchronised.
+ * Every check runs for the whole list before anything is enqueued (a refused call changes no address); FHERAM_ERR_INVALID_ARG:
+ * null pointers, n outside [1, FHERAM_DERIVE_MAX], an integer or address of another context or bank, an integer narrower than
+ * the address plan, the same address twice in addrs (the same integer twice in fus is allowed).  FHERAM_ERR_UNSUPPORTED: a digit
+ * plan of more than 8 digits (use fheram_address_set_from_fheuint). */
+int fheram_address_derive(fheram_ctx* ctx, const fheram_fheuint* const* fus, int n, int sign, fheram_addr* const* addrs);
+/* The same on a bank: integers and addresses bound to the bank (any member).  A derived address is an ordinary bank address
+ * (fheram_bank_address_create's kind) and may serve several members.  Integers are freed with fheram_fheuint_destroy, addresses
+ * with fheram_address_destroy. */
+int fheram_bank_fheuint_create(fheram_bank* bank, const int64_t* bits, int n_bits, fheram_fheuint** out);
+int fheram_bank_address_alloc(fheram_bank* bank, fheram_addr** out);
+int fheram_bank_address_derive(fheram_bank* bank, const fheram_fheuint* const* fus, int n, int sign, fheram_addr* const* addrs);
+
 /* ---- Measurement hooks (bench.py).  HIP events recorded on the context's own stream. */
 int fheram_timer_begin(fheram_ctx* ctx);
 int fheram_timer_end(fheram_ctx* ctx, float* elapsed_ms);
