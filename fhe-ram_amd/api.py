@@ -27,6 +27,7 @@ I64P = C.POINTER(C.c_int64)
 
 READ_BATCH_MAX = 8   # FHERAM_READ_BATCH_MAX (include/fheram.h)
 BANK_MAX = 8         # FHERAM_BANK_MAX
+READ_LIST_MAX = 8    # FHERAM_READ_LIST_MAX
 DERIVE_MAX = 8       # FHERAM_DERIVE_MAX
 STATUS = {0: "OK", 1: "INVALID_ARG", 2: "STATE", 3: "UNINITIALIZED", 4: "KEYS", 5: "UNSUPPORTED", 6: "RANGE", 7: "DEVICE", 8: "PRECISION"}
 
@@ -172,6 +173,8 @@ _SYMBOLS = [
     ("fheram_bank_read_prepare_write", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), I64P]),
     ("fheram_bank_write", C.c_int, [C.c_void_p, C.c_int, C.c_int, I64P, C.POINTER(C.c_void_p)]),
     ("fheram_bank_result_download", C.c_int, [C.c_void_p, C.c_int, C.c_int, I64P]),
+    ("fheram_bank_read_list", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.c_int, I64P]),
+    ("fheram_bank_read_list_result", C.c_int, [C.c_void_p, C.c_int, C.c_int, I64P]),
     ("fheram_bank_sync", C.c_int, [C.c_void_p]),
     ("fheram_bank_roundoff_max", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     ("fheram_bank_roundoff_reset", C.c_int, [C.c_void_p]),
@@ -1297,6 +1300,34 @@ class RamBank:
             raise FheRamError(1, f"w.len() != subrams.len() (ram.rs:243): expected {n} x {p.word_size()} GLWEs")
         self._use_keys(keys)
         self._chk(library().fheram_bank_write(self._h, first, n, _p(w), arr))
+
+    def read_list(self, members, addresses, keys: EvaluationKeysPrepared, download: bool = True):
+        """K reads as ONE operation (fheram_bank_read_list), entry k on member members[k] at addresses[k]: any order, any repetition,
+        any subset of the members; 1 <= K <= READ_LIST_MAX and K * word_size <= 64.  int64 [K][word_size][GLWE], slice k equal to
+        read([addresses[k]], keys, first=members[k]); the bank is left where that sequence of single-member reads leaves it, and
+        members that are not named are untouched.  download=False: no host wait (list_result later)."""
+        members, addresses = [int(m) for m in members], list(addresses)
+        if not 1 <= len(members) <= READ_LIST_MAX or len(addresses) != len(members):
+            raise FheRamError(1, f"read_list takes 1 to {READ_LIST_MAX} members and as many addresses, got {len(members)} and {len(addresses)}")
+        if not all(isinstance(a, Address) for a in addresses):
+            raise FheRamError(1, "every entry must be an Address (a null address is refused)")
+        n = len(members)
+        for m in members:
+            self._member(m)
+        arr = (C.c_void_p * n)(*[a._bank(self) for a in addresses])
+        self._use_keys(keys)
+        p = self.params
+        out = np.zeros((n, p.word_size(), p.glwe_len()), dtype=np.int64) if download else None
+        self._chk(library().fheram_bank_read_list(self._h, (C.c_int * n)(*members), arr, n, _p(out) if download else None))
+        return out
+
+    def list_result(self, first: int = 0, n: int = 1) -> np.ndarray:
+        """entries [first, first + n) of the last read_list: int64 [n][word_size][GLWE]"""
+        first, n = int(first), int(n)
+        p = self.params
+        out = np.zeros((max(n, 1), p.word_size(), p.glwe_len()), dtype=np.int64)
+        self._chk(library().fheram_bank_read_list_result(self._h, first, n, _p(out)))
+        return out
 
     def derive_addresses(self, fheuints, addrs=None, sign: bool = False):
         """as Ram.derive_addresses, with integers and addresses bound to this bank (FheUintPrepared.from_host(bank, ...),

@@ -188,6 +188,7 @@ int fheram_ctx_create_cfg(const fheram_params* p, int device, int shard, int n_s
     LDSATTR((&k_write_chain_b<4, 4>)); LDSATTR((&k_write_chain_b<5, 4>));
     LDSATTR((&k_read_chain_w<4, 4>)); LDSATTR((&k_read_chain_w<5, 4>));
     LDSATTR((&k_read_chain_b<4, 4>)); LDSATTR((&k_read_chain_b<5, 4>)); LDSATTR((&k_read_chain_bw<4, 4>)); LDSATTR((&k_read_chain_bw<5, 4>));
+    LDSATTR((&k_read_chain_lw<4, 4>)); LDSATTR((&k_read_chain_lw<5, 4>));
     LDSATTR((&k_trace_tail_b<3, 4, 3>)); LDSATTR((&k_trace_tail_b<3, 5, 3>));
     LDSATTR((&k_keyswitch_chain_w<3, 4, 3, 3>)); LDSATTR((&k_keyswitch_chain_w<3, 5, 3, 3>));
     LDSATTR((&k_keyswitch_chain<3, 4, 3>));

@@ -13,7 +13,8 @@
 //   k_trace_tail / k_chain_mid  dependent chains on few ciphertexts with in-kernel hand-offs between workgroups of one XCD (k_trace_tail: coordinate 1's
 //                  products in front of the trace, round 6)
 //   chain_kernels.inc           k_keyswitch_chain / k_read_chain in two register budgets (included twice: 240 registers beside the gate wave, 256 otherwise;
-//                               twice more for k_read_chain_b / _bw, the read chain of fheram_read_batch)
+//                               twice more for k_read_chain_b / _bw, the read chain of fheram_read_batch, and once for k_read_chain_lw,
+//                               that of fheram_bank_read_list)
 //   write_chain.inc             k_write_chain, and k_write_chain_b with a per-member operand table (fheram_bank_write)
 //   trace_tail.inc              k_trace_tail, and k_trace_tail_b with per-address products (fheram_read_batch)
 //   cmux_chain.hip              k_cmux_chain: the CMux chains of Address::set_from_fheuint for K integers as one launch (fheram_address_derive),
@@ -1780,7 +1781,8 @@ struct RowChainBatchArgs : RowChainArgs {
     long opnd_stride = 0;
     int ws = 1, src_rows = 1;
 };
-__device__ __forceinline__ long batch_opnd_offset(const RowChainBatchArgs& ra) {
+template <typename Args>   // RowChainBatchArgs, RowChainListArgs
+__device__ __forceinline__ long batch_opnd_offset(const Args& ra) {
     int y = (int)blockIdx.y;
     asm volatile("" : "+v"(y));   // opaque: recomputed at every use, never hoisted out of the step loop and kept live
     return (long)(__builtin_amdgcn_readfirstlane(y) / ra.ws) * ra.opnd_stride;
@@ -1800,6 +1802,33 @@ __device__ __forceinline__ GlweRef batch_src_row(GlweRef a, const RowChainBatchA
 #undef FK_READ_CHAIN_NAME
 #undef FK_VG
 #define FK_READ_CHAIN_NAME k_read_chain_bw
+#define FK_VG FK_WIDE_VGPRS
+#include "chain_kernels.inc"
+#undef FK_READ_CHAIN_NAME
+#undef FK_VG
+#undef FK_READ_CHAIN_ARGS
+#undef FK_READ_CHAIN_BATCH
+// fheram_bank_read_list: the read chain over the rows of K list entries as ONE launch, y = k * ws + w, entry k on member map(k) of a bank
+// in any order and with repeats.  The products read source row map(y / ws) * ws + y mod ws of the bank's rows and take the prepared
+// digits of entry k, as above.  The map travels by value, four bits per entry (K <= 8, members < 8): no table in device memory.
+struct RowChainListArgs : RowChainArgs {
+    long opnd_stride = 0;
+    int ws = 1;
+    unsigned src_map = 0;   // the member of entry k in bits [4k, 4k + 4)
+};
+__device__ __forceinline__ GlweRef list_src_row(GlweRef a, const RowChainListArgs& ra) {   // at(a) then reads row map(y / ws) * ws + y mod ws
+    int y = (int)blockIdx.y;
+    asm volatile("" : "+v"(y));   // as batch_src_row: wave-uniform scalar work, recomputed where it is used
+    const int k = __builtin_amdgcn_readfirstlane(y) / ra.ws;
+    const int m = (int)((ra.src_map >> (4 * k)) & 15u);
+    a.p += (long)((m - k) * ra.ws) * a.sy;   // m * ws + y mod ws - y
+    return a;
+}
+#define FK_READ_CHAIN_ARGS RowChainListArgs
+#define FK_READ_CHAIN_BATCH 2
+// One register budget, the whole file (k_read_chain_lw): a list of several entries is always a read, which never parks the gate wave
+// beside its launches (path.hpp read_local: wide), so a capped form could never be launched.
+#define FK_READ_CHAIN_NAME k_read_chain_lw
 #define FK_VG FK_WIDE_VGPRS
 #include "chain_kernels.inc"
 #undef FK_READ_CHAIN_NAME

@@ -320,7 +320,9 @@ void launch_trace_chain(fheram_ctx* c, GlweRef src, const GlweRef (&b)[2], int s
 // digits of address y / ws, which are `stride` elements apart from prep on, and reads a rows source at y mod src_rows (ws: every address reads
 // the same rows, fheram_read_batch; n * ws: its own, a bank range).  ws == 0: one address, no table (the kernels without one).
 // src_rows is read by launch_read_chain only: the write chain and the tail's fallback always run on rows of their own (y mod gy).
-struct OpndTable { int ws = 0; long stride = 0; int src_rows = 0; };
+// mapped (fheram_bank_read_list): the rows source is a bank's and entry k reads member (src_map >> 4k) & 15 of it, row
+// member * ws + y mod ws (k_read_chain_lw); like src_rows read by launch_read_chain only.
+struct OpndTable { int ws = 0; long stride = 0; int src_rows = 0; bool mapped = false; unsigned src_map = 0; };
 // The two chains a row goes through back to back as ONE launch (k_read_chain / k_write_chain): both must be in the Chain form
 // (chain_form: whether the trace chain's first step reads rotated input does not matter to it), in the variants that hand over through
 // LDS and registers.  one_wg: ChainQuery's.
@@ -344,7 +346,8 @@ void fill_row_chain(fheram_ctx* c, RowChainArgs& ra, const double* prep, int d, 
 }
 // read / read_prepare_write: d products of `src` with the prepared digits, then trace steps 0 .. n_tr-1 (the alone packer levels);
 // the result lands in dst; ep_store != nullptr: the products' result is also written there (in-place products of read_prepare_write)
-// with a table: row y reads src at y mod t.src_rows and the digits of address y / t.ws (k_read_chain_b / _bw)
+// with a table: row y reads src at y mod t.src_rows and the digits of address y / t.ws (k_read_chain_b / _bw); with a source map in it,
+// src at row map(y / t.ws) * t.ws + y mod t.ws (k_read_chain_lw)
 void launch_read_chain(fheram_ctx* c, GlweRef src, const GlweRef* ep_store, GlweRef dst, const double* prep, int d, int n_tr, int gx, int gy, const OpndTable& t) {
     ProfScope ps(c, "read_chain_launch", (uint64_t)gx * gy, 1);
     RowChainArgs ra;
@@ -355,6 +358,14 @@ void launch_read_chain(fheram_ctx* c, GlweRef src, const GlweRef* ep_store, Glwe
     ra.ks.base = ks_args(c, dst, dst, dst, trace_key(c, 0), c->gal[0]);
     ra.ks.buf[0] = ra.ks.buf[1] = dst;                            // only the last step stores
     ra.hi = dst; ra.trhi = dst;
+    if (t.mapped) {   // a read list: never beside the gate wave (read_local: wide), so the whole register file, as k_write_chain
+        RowChainListArgs rl;
+        static_cast<RowChainArgs&>(rl) = ra;
+        rl.opnd_stride = t.stride; rl.ws = t.ws; rl.src_map = t.src_map;
+        c->wide_unsynced = true;
+        with_evk(c, [&](auto sk) { hipLaunchKernelGGL((k_read_chain_lw<decltype(sk)::value, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rl); });
+        return;
+    }
     with_evk_wide(c, c->wide, [&](auto sk, auto w) {
         constexpr int SK = decltype(sk)::value;
         constexpr bool W = decltype(w)::value;

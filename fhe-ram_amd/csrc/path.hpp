@@ -1,8 +1,8 @@
 // Private to fheram.hip: Ram::read / read_prepare_write / write as launch sequences (reference: src/ram.rs).
 // ONE read sequence (read_local + read_top, together read_impl) and ONE write sequence (write_side_begin, write_top, write_rows), over an
 // operand set (Opnds: whose digits a product uses, whose RAM state it updates) and a view (RamView: the buffers it runs on).  The plain context, the stages of
-// a row-sharded RAM (fheram.hip, group.hpp), fheram_read_batch and fheram_bank_* (bank.hpp) all run these; what is specific to one of them
-// is a visible condition in the sequence (n == 1: pre_inv, the gate wave, ev_opstart, ev_wdone, sharding, capture; a bank range: Opnds::row_fuse).
+// a row-sharded RAM (fheram.hip, group.hpp), fheram_read_batch and fheram_bank_* (bank.hpp; its read list too) all run these; what is specific to one of them
+// is a visible condition in the sequence (n == 1: pre_inv, the gate wave, ev_opstart, ev_wdone, sharding, capture; a bank range or list: Opnds::row_fuse).
 #pragma once
 #include "launch.hpp"
 
@@ -21,17 +21,21 @@ struct Opnds {
     double *tab, *tab_inv;   // (inverse) digits of address 0
     long stride;
     bool own_rows;           // a bank range: address k reads and writes member k's rows; false (fheram_read_batch): every address reads the same rows
+    bool mapped = false;     // a bank's read list: address k reads member member(k)'s rows of the view's (the whole bank's); read-only
+    unsigned src_map = 0;    // ... the source map, four bits per entry: what the table forms take by value (launch.hpp OpndTable)
+    int member(int k) const { return (int)((src_map >> (4 * k)) & 15u); }
     int Y() const { return n * ws; }
     double* prep(int k, int ci) const { return digits_of(c, tab + k * stride, ci); }
     double* inv(int k, int ci) const { return digits_of(c, tab_inv + k * stride, ci); }
     GlweRef slice(GlweRef r, int k) const { r.p += (long)k * ws * r.sy; return r; }   // address k's ws ciphertexts
-    GlweRef rows(GlweRef r, int k) const { return own_rows ? slice(r, k) : r; }
-    OpndTable table() const { return n == 1 ? OpndTable{} : OpndTable{ws, stride, own_rows ? Y() : ws}; }
+    GlweRef rows(GlweRef r, int k) const { return mapped ? slice(r, member(k)) : own_rows ? slice(r, k) : r; }
+    OpndTable table() const { return n == 1 ? OpndTable{} : OpndTable{ws, stride, own_rows ? Y() : ws, mapped, src_map}; }
     // The fused row chain (k_read_chain / k_write_chain) for this operation.  A lone context — and a batch like it — splits by column while
     // rows * ws * 2 workgroups still fit the chip (pick_nco), which rules the chain out; for a range of bank members the alternative to the ONE
     // launch with an operand table is not one column-split launch per step but one per MEMBER and step, so the range takes one workgroup
-    // per ciphertext from the start.  (The smaller regimes — limb split, fine split, the mid chains — keep their precedence: chain_form.)
-    bool row_fuse(int d, int n_tr, int gx) const { return use_row_fuse(c, d, n_tr, gx, Y(), n > 1 && own_rows); }
+    // per ciphertext from the start, and so does a read list, which is a bank operation.  (The smaller regimes — limb split, fine split, the
+    // mid chains — keep their precedence: chain_form.)
+    bool row_fuse(int d, int n_tr, int gx) const { return use_row_fuse(c, d, n_tr, gx, Y(), n > 1 && (own_rows || mapped)); }
 };
 // the plain operation: one address (a = &addr), the context's d_prep / d_prep_inv, ws ciphertexts (the context's word count and RAM; one member of a bank: its)
 Opnds one_addr(fheram_ctx* c, const fheram_addr* const* a, int ws, RamState* st) { return Opnds{c, st, a, 1, ws, c->d_prep, c->d_prep_inv, 0, true}; }
@@ -39,7 +43,7 @@ Opnds one_addr(fheram_ctx* c, const fheram_addr* const* a) { return one_addr(c, 
 
 // An operation's VIEW: every buffer indexed by ciphertext y, from the operation's first.  The rows, the ping-pong arenas A / B with the third
 // and fourth (pack_levels P0 / P1; the write's trace(ct_hi)), the per-ciphertext buffers, and where the result goes.  The context's own
-// (ctx_view), a batch's (batch_view below: a batch never writes), or a range of a bank's members (bank.hpp bank_view).
+// (ctx_view), a batch's (batch_view below: a batch never writes), a range of a bank's members (bank.hpp bank_view) or a bank's read list (list_view).
 struct RamView {
     int32_t *rows, *A, *B, *C, *D;   // [Y][rows]
     int32_t *part, *tmp, *tmp2, *res, *tree, *w, *trtop;   // [Y]; part: the packed row where no arena holds it (rows == 1, a shard's partial) / the un-rotated ct_lo
@@ -241,9 +245,11 @@ void batch_free(fheram_ctx* c) {
 // The third arena is only needed where the alone packer levels run as the single-launch tail chain on the batch's rows (at most
 // TAIL_GROUPS ciphertexts: 2^13 with K * ws <= 4), whose source must survive the launch (pack_levels P0): allocated only then.
 // (The very question pack_levels asks; the fused row chain, which would leave it no alone levels, excludes the Tail form: launch.hpp chain_form.)
-bool batch_needs_third(const fheram_ctx* c, int K) {
-    return c->n2 == 2 && chain_form(c, ChainQuery{false, LOGN - ilog2_ceil(c->rows_glob), (int)c->rows, K * c->ws}).form == ChainForm::Tail;
+// n_ct: the operation's ciphertexts (a batch: K * ws; a bank's read list, whose context has the word count of the whole bank: n * its members' ws)
+bool third_arena_needed(const fheram_ctx* c, int n_ct) {
+    return c->n2 == 2 && chain_form(c, ChainQuery{false, LOGN - ilog2_ceil(c->rows_glob), (int)c->rows, n_ct}).form == ChainForm::Tail;
 }
+bool batch_needs_third(const fheram_ctx* c, int K) { return third_arena_needed(c, K * c->ws); }
 // grows the batch buffers to K addresses (and adds the third arena when this batch needs it); on failure the context holds none of
 // them (and single reads are unaffected)
 int batch_reserve(fheram_ctx* c, int K) {

@@ -428,6 +428,25 @@ public:
     std::vector<std::vector<Glwe>> read_prepare_write(std::vector<Address*>& addresses, const EvaluationKeysPrepared& keys, int first = 0) {   // ram.rs:196-222
         return read_op(true, addresses, keys, first);
     }
+    // members.size() independent reads as ONE operation (fheram_bank_read_list), entry k on member members[k] at *addresses[k]: any order,
+    // any repetition, any subset of the members; 1 to FHERAM_READ_LIST_MAX entries and entries * word_size <= 64.  Result k is what
+    // read({addresses[k]}, keys, members[k]) returns, and the bank is left where that sequence of single-member reads leaves it.
+    std::vector<std::vector<Glwe>> read_list(const std::vector<int>& members, std::vector<Address*>& addresses, const EvaluationKeysPrepared& keys) {
+        if (members.empty() || members.size() > FHERAM_READ_LIST_MAX || addresses.size() != members.size())
+            throw Error(FHERAM_ERR_INVALID_ARG, "read_list takes 1 to FHERAM_READ_LIST_MAX members and as many addresses");
+        use(keys);
+        std::vector<const fheram_addr*> h = handles(addresses);
+        std::vector<int64_t> out(h.size() * params.word_size() * glwe_len());
+        chk(fheram_bank_read_list(bank_, members.data(), h.data(), (int)h.size(), out.data()));
+        return split(out, h.size());
+    }
+    // entries [first, first + n) of the last list (fheram_bank_read_list_result)
+    std::vector<std::vector<Glwe>> list_result(int first, int n) {
+        if (n < 1) throw Error(FHERAM_ERR_INVALID_ARG, "empty slice of the last list");
+        std::vector<int64_t> out((size_t)n * params.word_size() * glwe_len());
+        chk(fheram_bank_read_list_result(bank_, first, n, out.data()));
+        return split(out, (size_t)n);
+    }
     // w[k]: the word_size GLWEs of member first + k (ram.rs:226-294)
     void write(const std::vector<std::vector<Glwe>>& w, std::vector<Address*>& addresses, const EvaluationKeysPrepared& keys, int first = 0) {
         if (w.size() != addresses.size()) throw Error(FHERAM_ERR_INVALID_ARG, "one word per address");
@@ -507,12 +526,15 @@ private:
     std::vector<std::vector<Glwe>> read_op(bool prepare_write, std::vector<Address*>& addresses, const EvaluationKeysPrepared& keys, int first) {
         use(keys);
         std::vector<const fheram_addr*> h = handles(addresses);
-        const size_t g = glwe_len(), one = params.word_size() * g;
-        std::vector<int64_t> out(h.size() * one);
+        std::vector<int64_t> out(h.size() * params.word_size() * glwe_len());
         chk(prepare_write ? fheram_bank_read_prepare_write(bank_, first, (int)h.size(), h.data(), out.data())
                           : fheram_bank_read(bank_, first, (int)h.size(), h.data(), out.data()));
-        std::vector<std::vector<Glwe>> res(h.size());
-        for (size_t k = 0; k < h.size(); k++)
+        return split(out, h.size());
+    }
+    std::vector<std::vector<Glwe>> split(const std::vector<int64_t>& out, size_t n) const {   // [n][word_size][GLWE]
+        const size_t g = glwe_len(), one = params.word_size() * g;
+        std::vector<std::vector<Glwe>> res(n);
+        for (size_t k = 0; k < n; k++)
             for (size_t i = 0; i < params.word_size(); i++)
                 res[k].emplace_back(out.begin() + k * one + i * g, out.begin() + k * one + (i + 1) * g);
         return res;

@@ -67,6 +67,43 @@ int main() {
         if (grp.size() != 2) return 8;
         try { fheram::Address a2; grp.read(a2, fheram::EvaluationKeysPrepared()); return 9; }
         catch (const fheram::Error& e) { std::printf("group refused as the reference would: %s\n", e.what()); }
+        {   // Bank::read_list on a bank of two members: slice k is what the single-member read of members[k] returns, in any order and
+            // with repeats; afterwards the bank is where those reads leave it.  Synthetic normalised limbs (the path is deterministic).
+            const fheram::Parameters bp(4, {3, 3, 3, 3}, 1 << 12);
+            const size_t n = bp.n();
+            uint64_t lcg = 88172645463325252ull;
+            auto synth = [&](size_t count) {
+                std::vector<int64_t> v(count);
+                for (auto& x : v) { lcg = lcg * 6364136223846793005ull + 1442695040888963407ull; x = (int64_t)((lcg >> 40) & 0x1ffff) - (1 << 16); }
+                return v;
+            };
+            fheram::EvaluationKeysPrepared bk;
+            bk.gal_els.push_back(-1);
+            for (uint32_t i = 1; i < bp.p.log_n; i++) {
+                uint64_t g = 5;
+                for (uint32_t s = 1; s < i; s++) g = g * g % (2 * n);
+                bk.gal_els.push_back((int64_t)g);
+            }
+            for (size_t i = 0; i < bk.gal_els.size(); i++) bk.atk_glwe.push_back(synth(3 * 4 * 2 * n));
+            bk.atk_ggsw_inv = synth(4 * 5 * 2 * n);
+            bk.tsk_ggsw_inv = synth(4 * 5 * 2 * n);
+            fheram::Bank bank(bp, 2);
+            for (int m = 0; m < 2; m++) bank.load_encrypted(m, synth(4 * bank.glwe_len()));
+            auto address = [&] { std::vector<std::vector<int64_t>> d; for (int i = 0; i < 4; i++) d.push_back(synth(3 * 2 * 4 * 2 * n)); return d; };
+            fheram::Address a0(address()), a1(address());
+            std::vector<fheram::Address*> la = {&a0, &a1, &a1}, one(1);
+            const std::vector<int> members = {1, 0, 1};
+            const auto got = bank.read_list(members, la, bk);
+            if (got.size() != 3 || bank.list_result(1, 2) != std::vector<std::vector<fheram::Glwe>>(got.begin() + 1, got.end())) return 11;
+            for (size_t k = 0; k < members.size(); k++) {
+                one[0] = la[k];
+                if (bank.read(one, bk, members[k])[0] != got[k]) { std::printf("read_list: entry %zu differs from the single-member read\n", k); return 11; }
+            }
+            if (bank.state(0) || bank.state(1)) return 11;
+            try { std::vector<fheram::Address*> bad = {&a0}; bank.read_list({2}, bad, bk); return 12; }
+            catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 12; }
+            std::printf("bank read list == single-member reads: ok\n");
+        }
     } catch (const fheram::Error& e) {
         if (e.code != FHERAM_ERR_DEVICE) { std::printf("unexpected error %d: %s\n", e.code, e.what()); return 4; }
         std::printf("no GPU: %s\n", e.what());

@@ -305,6 +305,26 @@ int fheram_bank_read_prepare_write(fheram_bank* bank, int first, int n, const fh
 int fheram_bank_write(fheram_bank* bank, int first, int n, const int64_t* w, const fheram_addr* const* addrs);
 /* the results of each member's last read / read_prepare_write */
 int fheram_bank_result_download(fheram_bank* bank, int first, int n, int64_t* out);
+/* A read list: reads of ANY members as one operation — any order, any repetition, any subset (a VM step that reads rs1 and rs2 from
+ * the register file, an instruction word and a data word: members {0, 0, 1, 2}).  The latency-bound end of a read is paid once for the
+ * list, and the rows' chains of all entries are one launch.  Slice k of the results is int64-identical to what
+ * fheram_bank_read(bank, members[k], 1, &addrs[k], ...) returns on the same state, and the bank is afterwards where the sequence of
+ * those n single-member reads leaves it: every named member in state 0 with rows and tree level 0 unchanged,
+ * fheram_bank_result_download of it returning the result of the LAST entry that named it; members that are not named are untouched in
+ * every respect (one that sits between read_prepare_write and write resumes its write from what it kept: the list runs on buffers of
+ * its own, allocated on first use, grown to the largest list seen and freed with the bank).
+ * 1 <= n <= FHERAM_READ_LIST_MAX and n * word_size <= 64.  Checked for the whole list before anything is enqueued, a refused call
+ * changes nothing: null pointers, n out of range, a member index outside the bank, a foreign or empty address
+ * (FHERAM_ERR_INVALID_ARG); a named member without rows (FHERAM_ERR_UNINITIALIZED); keys not loaded (FHERAM_ERR_KEYS); a named member
+ * between read_prepare_write and write (FHERAM_ERR_STATE).  FHERAM_ERR_DEVICE: the list's buffers cannot be allocated (every other
+ * operation still works).  There is no list form of read_prepare_write / write: a RAM has one pending write. */
+#define FHERAM_READ_LIST_MAX 8
+/* K = n independent Ram::read (ram.rs:172-191), entry k on member members[k] at addrs[k], as ONE operation.
+ * Any order, any repetition, any subset of the bank's members.  out: [n][word_size][GLWE], or NULL (no host wait). */
+int fheram_bank_read_list(fheram_bank* bank, const int* members, const fheram_addr* const* addrs, int n, int64_t* out);
+/* entries [first, first + n) of the LAST list, [n][word_size][GLWE]; for a list that was enqueued with out == NULL.
+ * FHERAM_ERR_STATE before any list has run, FHERAM_ERR_INVALID_ARG for a slice outside the last list. */
+int fheram_bank_read_list_result(fheram_bank* bank, int first, int n, int64_t* out);
 int fheram_bank_sync(fheram_bank* bank);
 /* one round-off monitor for the bank; FHERAM_ERR_PRECISION as for a context */
 int fheram_bank_roundoff_max(fheram_bank* bank, double* max_out);
