@@ -8,8 +8,8 @@
 // write_rows with the operand set of the range (bank_opnds):
 //   - a range of ONE member is the plain operation (one_addr), memo included;
 //   - a wider range has its digits in a table: every address-independent step is one launch over n * ws ciphertexts, the address-dependent
-//     products take the table where a table form exists (k_read_chain_b / _bw, k_trace_tail_b with its k_read_chain_b fallback,
-//     k_write_chain_b) and run one launch per member on the member's y-slice everywhere else (prepare, the GGSW inversion, the unfused
+//     products take the table where a table form exists (k_read_chain_t, k_trace_tail_t with its k_read_chain_t fallback,
+//     k_write_chain_t) and run one launch per member on the member's y-slice everywhere else (prepare, the GGSW inversion, the unfused
 //     product chains, n2 == 1).
 // Per-member state (the state flag, what read_prepare_write kept for the write, where the last result is) lives here, one RamState per
 // member; an operation runs on the merge of its range's (bank_merge) and hands the outcome back to every member of it (bank_assign).  The
@@ -17,34 +17,23 @@
 // never started early in a bank of more than one member (pre_inv shares d_prep_inv and d_tail_sync between members); a bank of ONE member
 // is a plain context in every respect.
 // A READ LIST (fheram_bank_read_list) is the general read: entry k reads member members[k], in any order and with repeats.  It is the same
-// read_impl with a third operand set and view (list_opnds / list_view): the rows are the whole bank's, reached through a source map (one
-// member index per entry: Opnds::rows for the per-entry launches, k_read_chain_lw for the rows' chain), the digits sit in a table of
-// the list's own, and every launch writes buffers of the list's own (ListBufs), as a batch's do — so the arenas, trtop and tree of a member
-// that sits between read_prepare_write and write are not touched.  It runs on a scratch RamState; every named member is then left as a
+// read_impl on the same kind of operand set (path.hpp table_opnds) with the members as its source map, over the whole bank's rows (one
+// member index per entry: Opnds::rows for the per-entry launches, k_read_chain_t for the rows' chain — a range is the identity map, a
+// batch the map 0, 0, ...); the digits sit in a table of the list's own, and every launch writes buffers of the list's own (ReadBufs, the
+// very set a batch has: path.hpp read_many) — so the arenas, trtop and tree of a member that sits between read_prepare_write and write are not touched.  It runs on a scratch RamState; every named member is then left as a
 // read leaves it, with the result of the last entry that named it in its slice of d_res.
 // Bank operations are never captured into a hipGraph: under graph = 1 they are enqueued directly, in the forms that mode selects.
 #pragma once
 #include "path.hpp"
 
-// The buffers of a read list: for `cap` entries, allocated on first use, grown to the largest list seen, freed with the bank.  Ciphertext
-// y = k * mws + w is word w of entry k; the arenas keep the rows' stride.  (What fheram_ctx::d_b* are to fheram_read_batch — sized by the
-// members' word count, not by the context's, which is the whole bank's.)
-struct ListBufs {
-    int cap = 0;
-    int32_t *A = nullptr, *B = nullptr;   // [cap * mws][rows]  ping-pong arenas (these, tmp, tmp2 and prep: from the first list of several entries on)
-    int32_t* C = nullptr;                 // [cap * mws][rows]  only where the alone levels run as the tail chain (path.hpp third_arena_needed)
-    int32_t *res = nullptr, *tmp = nullptr, *tmp2 = nullptr;   // [cap * mws]
-    double* prep = nullptr;               // [cap][n_digits] prepared GGSW: entry k's digits (the bank's d_prep holds M)
-    int64_t *h_res = nullptr, *d_h_res = nullptr;   // pinned, device-visible: the results as int64 (+ the monitor's maximum), as h_res
-    int last_n = 0;                       // entries of the last list (their results are in res); 0: none has run
-};
 struct fheram_bank {
     fheram_ctx* c = nullptr;      // word count M * mws; never row-sharded, never part of a group
     int M = 0, mws = 0;
     RamState ram[FHERAM_BANK_MAX];
     double* d_prep = nullptr;     // [n][n_digits] prepared GGSW: the digits of the k-th address of the range being read   (M > 1)
     double* d_prep_inv = nullptr; // [n][n_digits] the inverse digits of the k-th address of the range being written      (M > 1)
-    ListBufs list;
+    ReadBufs list;                // fheram_bank_read_list: buffers of its own (path.hpp reads_reserve), sized by mws
+    int list_n = 0;               // entries of the last list (their results are in list.res); 0: none has run
 };
 
 namespace {
@@ -58,22 +47,27 @@ RamView bank_view(const fheram_bank* b, int first) {
     return v;
 }
 // the operand set of an operation on a range: one member is the plain operation on the view; more have their digits in the bank's tables
+// and address k works on member k of the view
 Opnds bank_opnds(fheram_bank* b, RamState* st, const fheram_addr* const* addrs, int n) {
     if (n == 1) return one_addr(b->c, addrs, b->mws, st);
-    return Opnds{b->c, st, addrs, n, b->mws, b->d_prep, b->d_prep_inv, (long)b->c->n_digits * (long)fheram_ctx::GGSW, true};
+    return table_opnds(b->c, st, addrs, n, b->mws, b->d_prep, b->d_prep_inv, SRC_MAP_IDENTITY, true);
 }
 
-// ---- checks: the whole range before anything is enqueued -----------------------------------------------------------------------------
+// ---- checks: the whole range (or list) before anything is enqueued --------------------------------------------------------------------
+int check_addrs(fheram_ctx* c, const fheram_addr* const* addrs, int n) {
+    for (int k = 0; k < n; k++) {
+        if (!addrs[k] || addrs[k]->ctx != c) return fail(c, FHERAM_ERR_INVALID_ARG, "address " + std::to_string(k) + " is null or does not belong to this bank (layout mismatch, ram.rs:404)");
+        if (addrs[k]->empty) return fail(c, FHERAM_ERR_INVALID_ARG, "address " + std::to_string(k) + " is an empty address: fheram_bank_address_alloc without fheram_bank_address_derive");
+    }
+    return FHERAM_OK;
+}
 int bank_check(fheram_bank* b, int first, int n, const fheram_addr* const* addrs, int want_state) {
     if (!b) return FHERAM_ERR_INVALID_ARG;
     fheram_ctx* c = b->c;
     mid_rearm(c);
     if (first < 0 || n < 1 || first > b->M - n)
         return fail(c, FHERAM_ERR_INVALID_ARG, "member range [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") is empty or outside the bank's " + std::to_string(b->M) + " members");
-    if (addrs) for (int k = 0; k < n; k++) {
-        if (!addrs[k] || addrs[k]->ctx != c) return fail(c, FHERAM_ERR_INVALID_ARG, "address " + std::to_string(k) + " is null or does not belong to this bank (layout mismatch, ram.rs:404)");
-        if (addrs[k]->empty) return fail(c, FHERAM_ERR_INVALID_ARG, "address " + std::to_string(k) + " is an empty address: fheram_bank_address_alloc without fheram_bank_address_derive");
-    }
+    if (addrs) { const int rc = check_addrs(c, addrs, n); if (rc != FHERAM_OK) return rc; }
     for (int m = first; m < first + n; m++)
         if (!b->ram[m].initialized) return fail(c, FHERAM_ERR_UNINITIALIZED, "unitialized memory: self.data.len()=0 (member " + std::to_string(m) + ")");
     if (want_state < 0) return FHERAM_OK;
@@ -134,59 +128,6 @@ int bank_read_op(fheram_bank* b, int first, int n, const fheram_addr* const* add
 
 
 // ---- the read list ---------------------------------------------------------------------------------------------------------------
-void list_free(fheram_bank* b) {
-    ListBufs& L = b->list;
-    void* bufs[] = {L.A, L.B, L.C, L.res, L.tmp, L.tmp2, L.prep};
-    for (void* p : bufs) if (p) hipFree(p);
-    if (L.h_res) hipHostFree(L.h_res);
-    L = ListBufs{};
-}
-// grows the list's buffers to n entries (and adds the third arena when this list needs it); on failure the bank holds none of them (and
-// every other operation is unaffected).  A list of one entry is the plain read on the member's own buffers: it needs the result
-// buffers only, so the arenas, the temporaries and the digit table wait for the first list of several entries.
-int list_reserve(fheram_bank* b, int n) {
-    fheram_ctx* c = b->c;
-    ListBufs& L = b->list;
-    const bool work = n > 1, third = work && third_arena_needed(c, n * b->mws);
-    if (n <= L.cap && (!work || L.A) && (!third || L.C)) return FHERAM_OK;
-    if (n < L.cap) n = L.cap;   // (only the working buffers or the third arena are missing: keep the capacity)
-    const bool had_work = L.A != nullptr, had_third = L.C != nullptr;
-    if (L.cap) { HIPCHK(c, hipStreamSynchronize(c->stream)); list_free(b); }
-    const size_t G = fheram_ctx::GLWE, nct = (size_t)n * b->mws, nrow = nct * c->rows;
-    hipError_t e = hipSuccess;
-    auto dev = [&](auto** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc((void**)p, bytes); };
-    dev(&L.res, nct * G * sizeof(int32_t));
-    if (work || had_work) {
-        dev(&L.A, nrow * G * sizeof(int32_t));
-        dev(&L.B, nrow * G * sizeof(int32_t));
-        if (third || had_third) dev(&L.C, nrow * G * sizeof(int32_t));
-        dev(&L.tmp, nct * G * sizeof(int32_t));
-        dev(&L.tmp2, nct * G * sizeof(int32_t));
-        dev(&L.prep, (size_t)n * c->n_digits * fheram_ctx::GGSW * sizeof(double));
-    }
-    if (e == hipSuccess) e = hipHostMalloc((void**)&L.h_res, (nct * G + 1) * sizeof(int64_t), hipHostMallocMapped);   // + the monitor's maximum
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&L.d_h_res, L.h_res, 0);
-    if (e != hipSuccess) {
-        list_free(b);
-        (void)hipGetLastError();   // the next op's error check must not see this allocation's failure
-        return fail(c, FHERAM_ERR_DEVICE, std::string("read list buffers for ") + std::to_string(n) + " entries: " + hipGetErrorString(e));
-    }
-    L.cap = n;
-    return FHERAM_OK;
-}
-// The list as an operand set and a view for read_impl: the digits' table is the list's, entry k reads the rows of member members[k] out of
-// the bank's (the view's rows are the whole bank's) and the launches write the list's buffers only.  The result of entry k is at
-// res + k * mws GLWEs.  A bank of one member has one source: the list is what fheram_read_batch runs (every entry reads the same rows).
-Opnds list_opnds(fheram_bank* b, RamState* st, const int* members, const fheram_addr* const* addrs, int n) {
-    Opnds o{b->c, st, addrs, n, b->mws, b->list.prep, nullptr, (long)b->c->n_digits * (long)fheram_ctx::GGSW, false};
-    o.mapped = b->M > 1;
-    for (int k = 0; k < n; k++) o.src_map |= (unsigned)members[k] << (4 * k);
-    return o;
-}
-RamView list_view(const fheram_bank* b) {
-    const ListBufs& L = b->list;
-    return RamView{b->c->d_data, L.A, L.B, L.C, nullptr, L.tmp2, L.tmp, L.tmp2, L.res, nullptr, nullptr, nullptr};
-}
 // the whole list before anything is enqueued; codes, order and messages as bank_check
 int list_check(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n) {
     if (!b) return FHERAM_ERR_INVALID_ARG;
@@ -200,10 +141,8 @@ int list_check(fheram_bank* b, const int* members, const fheram_addr* const* add
     for (int k = 0; k < n; k++)
         if (members[k] < 0 || members[k] >= b->M)
             return fail(c, FHERAM_ERR_INVALID_ARG, "entry " + std::to_string(k) + " names member " + std::to_string(members[k]) + ", outside the bank's " + std::to_string(b->M) + " members");
-    for (int k = 0; k < n; k++) {
-        if (!addrs[k] || addrs[k]->ctx != c) return fail(c, FHERAM_ERR_INVALID_ARG, "address " + std::to_string(k) + " is null or does not belong to this bank (layout mismatch, ram.rs:404)");
-        if (addrs[k]->empty) return fail(c, FHERAM_ERR_INVALID_ARG, "address " + std::to_string(k) + " is an empty address: fheram_bank_address_alloc without fheram_bank_address_derive");
-    }
+    const int rc = check_addrs(c, addrs, n);
+    if (rc != FHERAM_OK) return rc;
     for (int k = 0; k < n; k++)
         if (!b->ram[members[k]].initialized) return fail(c, FHERAM_ERR_UNINITIALIZED, "unitialized memory: self.data.len()=0 (member " + std::to_string(members[k]) + ")");
     if (!c->keys_loaded) return fail(c, FHERAM_ERR_KEYS, "evaluation keys not loaded");
@@ -212,11 +151,7 @@ int list_check(fheram_bank* b, const int* members, const fheram_addr* const* add
             return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.read: internal state is true -> requires calling Memory.write (member " + std::to_string(members[k]) + ")");
     return FHERAM_OK;
 }
-int list_result(fheram_bank* b, int first, int n, int64_t* out) {
-    const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
-    const ResRun run{b->list.res + (size_t)first * per, (size_t)n * per};
-    return result_export(b->c, &run, 1, b->list.h_res, b->list.d_h_res, out);
-}
+int list_result(fheram_bank* b, int first, int n, int64_t* out) { return reads_export(b->c, b->list, (size_t)first * b->mws, (size_t)n * b->mws, out); }
 
 }  // namespace
 
@@ -260,7 +195,7 @@ void fheram_bank_destroy(fheram_bank* b) {
     }
     if (b->d_prep) hipFree(b->d_prep);
     if (b->d_prep_inv) hipFree(b->d_prep_inv);
-    list_free(b);
+    reads_free(b->list);
     fheram_ctx_destroy(b->c);
     delete b;
 }
@@ -366,48 +301,49 @@ int fheram_bank_result_download(fheram_bank* b, int first, int n, int64_t* out) 
     HIPCHK(b->c, hipSetDevice(b->c->device));
     return bank_result(b, first, n, out);
 }
-// K = n independent Ram::read (ram.rs:172-191), entry k on member members[k], as one operation: path.hpp read_impl over the list's operand
-// set and view.  What the sequence of those K single-member reads leaves: every named member in state 0 with nothing kept for a write, the
-// result of the last entry that named it where its own read would have left it (its slice of d_res); every other member as it was.
+// K = n independent Ram::read (ram.rs:172-191), entry k on member members[k], as one operation: path.hpp read_many with the members as the
+// source map, on the list's own buffers and a scratch RamState.  What the sequence of those K single-member reads leaves: every named member
+// in state 0 with nothing kept for a write, the result of the last entry that named it where its own read would have left it (its slice of
+// d_res); every other member as it was.  A bank of one member has one source: the list is what fheram_read_batch runs.
 int fheram_bank_read_list(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n, int64_t* out) {
     int rc = list_check(b, members, addrs, n);
     if (rc != FHERAM_OK) return rc;
     fheram_ctx* c = b->c;
     HIPCHK(c, hipSetDevice(c->device));
-    rc = list_reserve(b, n);
-    if (rc != FHERAM_OK) { b->list.last_n = 0; return rc; }
     const long G = (long)fheram_ctx::GLWE;
-    const GlweRef lres = ref(b->list.res, G, 0);
-    b->list.last_n = 0;   // until this list is enqueued there is no last list: several entries overwrite res as they run (one entry only with its closing copy, but the rule is one)
+    auto res_of = [&](int m) { return ref(c->d_res + (size_t)m * b->mws * G, G, 0); };
+    b->list_n = 0;   // until this list is enqueued there is no last list: several entries overwrite res as they run (one entry only with its closing copy, but the rule is one)
     if (n == 1) {   // the plain single-member read; its result is also the list's
-        rc = bank_read_op(b, members[0], 1, addrs, false, nullptr);
+        rc = reads_reserve(c, b->list, 1, b->mws);
+        if (rc == FHERAM_OK) rc = bank_read_op(b, members[0], 1, addrs, false, nullptr);
         if (rc != FHERAM_OK) return rc;
-        launch_copy(c, ref(c->d_res + (size_t)members[0] * b->mws * G, G, 0), lres, 1, b->mws);
-    } else {
-        RamState st{true, false, false, 0, false};
-        const Opnds o = list_opnds(b, &st, members, addrs, n);
-        rc = read_impl(o, list_view(b), false);
-        if (rc != FHERAM_OK) return rc;
+        launch_copy(c, res_of(members[0]), ref(b->list.res, G, 0), 1, b->mws);
+        b->list_n = 1;
+        HIPCHK(c, hipGetLastError());
+        return out ? list_result(b, 0, 1, out) : FHERAM_OK;
+    }
+    RamState st{true, false, false, 0, false};
+    unsigned map = 0;
+    for (int k = 0; k < n; k++) map |= (unsigned)members[k] << (4 * k);
+    return read_many(c, b->list, &st, addrs, n, b->mws, map, b->M > 1, out, [&](const Opnds& o) {
         for (int m = 0; m < b->M; m++) {
             int last = -1;
             for (int k = 0; k < n; k++) if (members[k] == m) last = k;
             if (last < 0) continue;
             RamState& r = b->ram[m];
             r.state = false; r.memo_top = false; r.memo_alone = 0; r.res_in_trtop = false;
-            launch_copy(c, o.slice(lres, last), ref(c->d_res + (size_t)m * b->mws * G, G, 0), 1, b->mws);
+            launch_copy(c, o.slice(ref(b->list.res, G, 0), last), res_of(m), 1, b->mws);
         }
-    }
-    b->list.last_n = n;
-    HIPCHK(c, hipGetLastError());
-    return out ? list_result(b, 0, n, out) : FHERAM_OK;
+        b->list_n = n;
+    });
 }
 int fheram_bank_read_list_result(fheram_bank* b, int first, int n, int64_t* out) {
     if (!b) return FHERAM_ERR_INVALID_ARG;
     fheram_ctx* c = b->c;
     if (!out) return fail(c, FHERAM_ERR_INVALID_ARG, "null output");
-    if (!b->list.last_n) return fail(c, FHERAM_ERR_STATE, "no read list has run on this bank");
-    if (first < 0 || n < 1 || first > b->list.last_n - n)
-        return fail(c, FHERAM_ERR_INVALID_ARG, "entries [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") are empty or outside the last list's " + std::to_string(b->list.last_n) + " entries");
+    if (!b->list_n) return fail(c, FHERAM_ERR_STATE, "no read list has run on this bank");
+    if (first < 0 || n < 1 || first > b->list_n - n)
+        return fail(c, FHERAM_ERR_INVALID_ARG, "entries [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") are empty or outside the last list's " + std::to_string(b->list_n) + " entries");
     HIPCHK(c, hipSetDevice(c->device));
     return list_result(b, first, n, out);
 }

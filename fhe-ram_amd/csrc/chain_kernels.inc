@@ -1,8 +1,7 @@
 // Included by kernels.hpp (no include guard): the chain kernels that exist in two register budgets.
 //   FK_KS_CHAIN_NAME / FK_READ_CHAIN_NAME : kernel names;  FK_VG : the literal for amdgpu_num_vgpr (units of two registers)
-//   FK_READ_CHAIN_ARGS / FK_READ_CHAIN_BATCH : RowChainArgs / 0, RowChainBatchArgs / 1 for the read chain of fheram_read_batch, or
-//   RowChainListArgs / 2 for that of fheram_bank_read_list
-//   (those four inclusions define no FK_KS_CHAIN_NAME: the trace chain has no batch form)
+//   FK_READ_CHAIN_ARGS / FK_READ_CHAIN_TABLE : RowChainArgs / 0, or RowChainTableArgs / 1 for the read chain over several addresses
+//   (that inclusion defines no FK_KS_CHAIN_NAME: the trace chain has no table form)
 #ifdef FK_KS_CHAIN_NAME
 // GLWE::trace(start, start + n) as ONE launch (see KsChainArgs in kernels.hpp)
 template <int SX, int SK, int SO, int YF = 0>   // YF: 0 int32 limbs between the steps (ks_run); 3 the intermediates as Y = ceil(A/2) with the closed-form normalisation, handed over through LDS and registers (ks_trace_l)
@@ -68,15 +67,11 @@ __global__ __launch_bounds__(T, T / 256) __attribute__((amdgpu_num_vgpr(FK_VG)))
     for (int k = 0; k < E; k++) vc[k] = 0.0;
     {
         GlweRef in = ra.ep.src;
-#if FK_READ_CHAIN_BATCH
-        // the source row y mod src_rows and the prepared digits of address y / ws: recomputed where they are used (a few scalar
-        // instructions) rather than kept live across the steps, at this kernel's scalar register pressure
-#define FK_RC_OPND(i) (ra.ep.ggsw[i] + batch_opnd_offset(ra))
-#if FK_READ_CHAIN_BATCH == 2
-#define FK_RC_SRC(a) list_src_row(a, ra)   // (the list: source row map(y / ws) * ws + y mod ws)
-#else
-#define FK_RC_SRC(a) batch_src_row(a, ra)
-#endif
+#if FK_READ_CHAIN_TABLE
+        // the source row map(y / ws) * ws + y mod ws and the prepared digits of address y / ws: recomputed where they are used (a few
+        // scalar instructions) rather than kept live across the steps, at this kernel's scalar register pressure
+#define FK_RC_OPND(i) (ra.ep.ggsw[i] + table_opnd_offset(ra))
+#define FK_RC_SRC(a) table_src_row(a, ra)
 #else
 #define FK_RC_OPND(i) ra.ep.ggsw[i]
 #define FK_RC_SRC(a) a

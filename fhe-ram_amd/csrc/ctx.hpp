@@ -46,6 +46,19 @@ struct RamState {
     bool res_in_trtop = false;   // the last read / read_prepare_write left its result in d_trtop (else d_res)
 };
 
+// The buffers of a read of several addresses as one operation (fheram_read_batch: the context's; fheram_bank_read_list: the bank's, sized by
+// the members' word count, not by the context's, which is the whole bank's): for `cap` addresses of ws ciphertexts, allocated on first use,
+// grown to the largest operation seen (path.hpp reads_reserve), freed with their owner.  Ciphertext y = k * ws + w is word w of address k;
+// the arenas keep the rows' stride (sy = rows * GLWE).  Every launch of such an operation writes these only (path.hpp reads_view).
+struct ReadBufs {
+    int cap = 0;
+    int32_t *A = nullptr, *B = nullptr;   // [cap * ws][rows]  ping-pong arenas (these, tmp, tmp2 and prep: from the first operation of several addresses on)
+    int32_t* C = nullptr;                 // [cap * ws][rows]  only where the alone levels run as the tail chain (path.hpp third_arena_needed)
+    int32_t *res = nullptr, *tmp = nullptr, *tmp2 = nullptr;   // [cap * ws]
+    double* prep = nullptr;               // [cap][n_digits] prepared GGSW: address k's digits
+    int64_t *h_res = nullptr, *d_h_res = nullptr;   // pinned, device-visible: the results as int64 (+ the monitor's maximum), as fheram_ctx::h_res
+};
+
 struct fheram_ctx {
     fheram_params p;
     int device = 0;
@@ -175,18 +188,7 @@ struct fheram_ctx {
     bool derive_unsynced = false;
     bool wdone_pending = false;
     int32_t* d_trtop = nullptr;    // [ws]
-    // fheram_read_batch (path.hpp batch_opnds / batch_view): buffers for batch_cap addresses, allocated on first use and grown to the largest
-    // batch seen.  Ciphertext y = k * ws + w of a batch is word w of address k; the arenas keep the rows' stride (sy = rows * GLWE).
-    int batch_cap = 0;
-    int32_t* d_bA = nullptr;       // [K*ws][rows]  ping-pong arenas of the batch's rows
-    int32_t* d_bB = nullptr;       // [K*ws][rows]
-    int32_t* d_bC = nullptr;       // [K*ws][rows]  stands in for the source the tail launch must leave intact (pack_levels); only when needed (path.hpp batch_needs_third)
-    int32_t* d_bres = nullptr;     // [K*ws]        the results
-    int32_t* d_btmp = nullptr;     // [K*ws]
-    int32_t* d_btmp2 = nullptr;    // [K*ws]
-    double* d_bprep = nullptr;     // [K][n_digits] prepared GGSW: address k's digits
-    int64_t* h_bres = nullptr;     // pinned, device-visible: the results as int64 (+ the monitor's maximum), as h_res
-    int64_t* d_h_bres = nullptr;
+    ReadBufs batch;                // fheram_read_batch: its arenas, results and digit table (path.hpp reads_reserve / reads_view), sized by this context's word count
     int32_t* h_pin[2] = {nullptr, nullptr};   // pinned host staging (hand-over of int64 host buffers)
     hipEvent_t ev_pin[2] = {nullptr, nullptr};
     // the two hand-overs ON the path (result of a read out, words of a write in) have staging of their own:

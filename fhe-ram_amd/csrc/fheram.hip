@@ -185,11 +185,10 @@ int fheram_ctx_create_cfg(const fheram_params* p, int device, int shard, int n_s
     LDSATTR((&k_ext_product_chain_r<4>));
     LDSATTR((&k_pair_z<4>)); LDSATTR((&k_pair_z<5>));
     LDSATTR((&k_read_chain<4, 4>)); LDSATTR((&k_read_chain<5, 4>)); LDSATTR((&k_write_chain<4, 4>)); LDSATTR((&k_write_chain<5, 4>));
-    LDSATTR((&k_write_chain_b<4, 4>)); LDSATTR((&k_write_chain_b<5, 4>));
+    LDSATTR((&k_write_chain_t<4, 4>)); LDSATTR((&k_write_chain_t<5, 4>));
     LDSATTR((&k_read_chain_w<4, 4>)); LDSATTR((&k_read_chain_w<5, 4>));
-    LDSATTR((&k_read_chain_b<4, 4>)); LDSATTR((&k_read_chain_b<5, 4>)); LDSATTR((&k_read_chain_bw<4, 4>)); LDSATTR((&k_read_chain_bw<5, 4>));
-    LDSATTR((&k_read_chain_lw<4, 4>)); LDSATTR((&k_read_chain_lw<5, 4>));
-    LDSATTR((&k_trace_tail_b<3, 4, 3>)); LDSATTR((&k_trace_tail_b<3, 5, 3>));
+    LDSATTR((&k_read_chain_t<4, 4>)); LDSATTR((&k_read_chain_t<5, 4>));
+    LDSATTR((&k_trace_tail_t<3, 4, 3>)); LDSATTR((&k_trace_tail_t<3, 5, 3>));
     LDSATTR((&k_keyswitch_chain_w<3, 4, 3, 3>)); LDSATTR((&k_keyswitch_chain_w<3, 5, 3, 3>));
     LDSATTR((&k_keyswitch_chain<3, 4, 3>));
     LDSATTR((&k_keyswitch_chain<3, 4, 3, 3>));
@@ -290,7 +289,7 @@ void fheram_ctx_destroy(fheram_ctx* c) {
     if (c->stream) hipStreamSynchronize(c->stream);
     if (c->stream2) hipStreamSynchronize(c->stream2);
     prof_collect(c);
-    batch_free(c);
+    reads_free(c->batch);
     if (c->ev_fork) hipEventDestroy(c->ev_fork);
     if (c->ev_join) hipEventDestroy(c->ev_join);
     for (int i = 0; i < 2; i++) if (c->ev_inv[i]) hipEventDestroy(c->ev_inv[i]);
@@ -496,17 +495,11 @@ int fheram_read_batch(fheram_ctx* c, const fheram_addr* const* addrs, int n_addr
         HIPCHK(c, hipGetLastError());
         return out ? fheram_result_download(c, out) : FHERAM_OK;
     }
-    // (never captured: a batch's launch sequence depends on K addresses, and a read's state bookkeeping is done as it is enqueued)
-    rc = batch_reserve(c, n_addr);
-    if (rc != FHERAM_OK) return rc;
-    const Opnds o = batch_opnds(c, addrs, n_addr);
-    rc = read_impl(o, batch_view(c), false);
-    if (rc != FHERAM_OK) return rc;
-    // what K reads leave behind: the last address's result where a read leaves it (RamState::res_in_trtop = false; nothing is kept for a write)
-    launch_copy(c, o.slice(ref(c->d_bres, (long)fheram_ctx::GLWE, 0), n_addr - 1), ref(c->d_res, (long)fheram_ctx::GLWE, 0), 1, c->ws);
-    HIPCHK(c, hipGetLastError());
-    const ResRun run{c->d_bres, (size_t)n_addr * c->ws * fheram_ctx::GLWE};
-    return out ? result_export(c, &run, 1, c->h_bres, c->d_h_bres, out) : FHERAM_OK;
+    // every address reads the same rows (the map 0, 0, ...); what K reads leave behind: the last address's result where a read leaves it
+    // (RamState::res_in_trtop = false; nothing is kept for a write)
+    return read_many(c, c->batch, &c->ram, addrs, n_addr, c->ws, 0, false, out, [&](const Opnds& o) {
+        launch_copy(c, o.slice(ref(c->batch.res, (long)fheram_ctx::GLWE, 0), n_addr - 1), ref(c->d_res, (long)fheram_ctx::GLWE, 0), 1, c->ws);
+    });
 }
 int fheram_read_prepare_write(fheram_ctx* c, const fheram_addr* addr, int64_t* out) {
     int rc = check_common(c, addr);

@@ -13,10 +13,9 @@
 //   k_trace_tail / k_chain_mid  dependent chains on few ciphertexts with in-kernel hand-offs between workgroups of one XCD (k_trace_tail: coordinate 1's
 //                  products in front of the trace, round 6)
 //   chain_kernels.inc           k_keyswitch_chain / k_read_chain in two register budgets (included twice: 240 registers beside the gate wave, 256 otherwise;
-//                               twice more for k_read_chain_b / _bw, the read chain of fheram_read_batch, and once for k_read_chain_lw,
-//                               that of fheram_bank_read_list)
-//   write_chain.inc             k_write_chain, and k_write_chain_b with a per-member operand table (fheram_bank_write)
-//   trace_tail.inc              k_trace_tail, and k_trace_tail_b with per-address products (fheram_read_batch)
+//                               once more for k_read_chain_t, the read chain over several addresses: RowChainTableArgs)
+//   write_chain.inc             k_write_chain, and k_write_chain_t with a per-member operand table (fheram_bank_write)
+//   trace_tail.inc              k_trace_tail, and k_trace_tail_t with per-address products (several addresses)
 //   cmux_chain.hip              k_cmux_chain: the CMux chains of Address::set_from_fheuint for K integers as one launch (fheram_address_derive),
 //                               a translation unit of its own (cmux_chain.hpp).  It includes this file for the helpers and templates, so a kernel
 //                               that is NOT a template must sit inside #ifndef FK_NO_PLAIN_KERNELS here (else the two units define it twice: a link error)
@@ -34,6 +33,7 @@
 //   FK_MONITOR=0 (fft_dev.hpp)                                    the round-off monitor left out
 //   FK_CHAIN_VGPRS                                                the chain kernels' register cap (the attribute wants a literal)
 #pragma once
+#include "../../include/fheram.h"   // the public maxima the table forms are sized by
 #include "fft_dev.hpp"
 #include <type_traits>
 
@@ -1756,7 +1756,7 @@ struct RowChainArgs {
 // meet the gate wave, k_keyswitch_chain_w / k_read_chain_w with the whole register file for those that cannot — the attribute wants a literal,
 // and a shared body function would take the kernel's argument struct by reference, i.e. copy it to scratch)
 #define FK_READ_CHAIN_ARGS RowChainArgs
-#define FK_READ_CHAIN_BATCH 0
+#define FK_READ_CHAIN_TABLE 0
 #define FK_KS_CHAIN_NAME k_keyswitch_chain
 #define FK_READ_CHAIN_NAME k_read_chain
 #define FK_VG FK_CHAIN_VGPRS
@@ -1772,86 +1772,60 @@ struct RowChainArgs {
 #undef FK_READ_CHAIN_NAME
 #undef FK_VG
 #undef FK_READ_CHAIN_ARGS
-#undef FK_READ_CHAIN_BATCH
-// fheram_read_batch: the read chain over the rows of K addresses as ONE launch, y = k * ws + w.  The rows are shared: the products
-// read source row y mod src_rows (src_rows = ws: the RAM's rows; = K * ws: a batch arena, as behind k_trace_tail_b) and take the
-// prepared digits of address k = y / ws, at ep.ggsw[i] + k * opnd_stride.  Instantiations of their own (k_read_chain_b, capped; _bw,
-// the whole register file), so that the single-address kernels carry no runtime field for it.
-struct RowChainBatchArgs : RowChainArgs {
-    long opnd_stride = 0;
-    int ws = 1, src_rows = 1;
-};
-template <typename Args>   // RowChainBatchArgs, RowChainListArgs
-__device__ __forceinline__ long batch_opnd_offset(const Args& ra) {
-    int y = (int)blockIdx.y;
-    asm volatile("" : "+v"(y));   // opaque: recomputed at every use, never hoisted out of the step loop and kept live
-    return (long)(__builtin_amdgcn_readfirstlane(y) / ra.ws) * ra.opnd_stride;
-}
-__device__ __forceinline__ GlweRef batch_src_row(GlweRef a, const RowChainBatchArgs& ra) {   // at(a) then reads row y mod src_rows
-    int y = (int)blockIdx.y;
-    asm volatile("" : "+v"(y));
-    y = __builtin_amdgcn_readfirstlane(y);
-    a.p += (long)(y % ra.src_rows - y) * a.sy;
-    return a;
-}
-#define FK_READ_CHAIN_ARGS RowChainBatchArgs
-#define FK_READ_CHAIN_BATCH 1
-#define FK_READ_CHAIN_NAME k_read_chain_b
-#define FK_VG FK_CHAIN_VGPRS
-#include "chain_kernels.inc"
-#undef FK_READ_CHAIN_NAME
-#undef FK_VG
-#define FK_READ_CHAIN_NAME k_read_chain_bw
-#define FK_VG FK_WIDE_VGPRS
-#include "chain_kernels.inc"
-#undef FK_READ_CHAIN_NAME
-#undef FK_VG
-#undef FK_READ_CHAIN_ARGS
-#undef FK_READ_CHAIN_BATCH
-// fheram_bank_read_list: the read chain over the rows of K list entries as ONE launch, y = k * ws + w, entry k on member map(k) of a bank
-// in any order and with repeats.  The products read source row map(y / ws) * ws + y mod ws of the bank's rows and take the prepared
-// digits of entry k, as above.  The map travels by value, four bits per entry (K <= 8, members < 8): no table in device memory.
-struct RowChainListArgs : RowChainArgs {
+#undef FK_READ_CHAIN_TABLE
+// The TABLE form of the row chains: one launch over the rows of n addresses, y = k * ws + w (fheram_read_batch, a range of a bank's members,
+// fheram_bank_read_list).  Entry k = y / ws takes its prepared digits at ep.ggsw[i] + k * opnd_stride and reads the rows of member map(k) of
+// the source: row map(k) * ws + y mod ws.  A batch is the map 0,0,0,... (every entry reads the same rows), a bank range the identity
+// relative to its view, a list any map.  The map travels by value, four bits per entry: no table in device memory.  Instantiations of
+// their own, so that the single-address kernels carry no runtime field for it.
+struct RowChainTableArgs : RowChainArgs {
     long opnd_stride = 0;
     int ws = 1;
     unsigned src_map = 0;   // the member of entry k in bits [4k, 4k + 4)
 };
-__device__ __forceinline__ GlweRef list_src_row(GlweRef a, const RowChainListArgs& ra) {   // at(a) then reads row map(y / ws) * ws + y mod ws
+static_assert(FHERAM_READ_BATCH_MAX <= 8 && FHERAM_BANK_MAX <= 8 && FHERAM_READ_LIST_MAX <= 8, "the source map holds eight entries of four bits");
+static_assert(FHERAM_BANK_MAX <= 16, "a member index fits four bits");
+__device__ __forceinline__ long table_opnd_offset(const RowChainTableArgs& ra) {
     int y = (int)blockIdx.y;
-    asm volatile("" : "+v"(y));   // as batch_src_row: wave-uniform scalar work, recomputed where it is used
+    asm volatile("" : "+v"(y));   // opaque: recomputed at every use, never hoisted out of the step loop and kept live
+    return (long)(__builtin_amdgcn_readfirstlane(y) / ra.ws) * ra.opnd_stride;
+}
+__device__ __forceinline__ GlweRef table_src_row(GlweRef a, const RowChainTableArgs& ra) {   // at(a) then reads row map(y / ws) * ws + y mod ws
+    int y = (int)blockIdx.y;
+    asm volatile("" : "+v"(y));   // as table_opnd_offset: wave-uniform scalar work, recomputed where it is used
     const int k = __builtin_amdgcn_readfirstlane(y) / ra.ws;
     const int m = (int)((ra.src_map >> (4 * k)) & 15u);
     a.p += (long)((m - k) * ra.ws) * a.sy;   // m * ws + y mod ws - y
     return a;
 }
-#define FK_READ_CHAIN_ARGS RowChainListArgs
-#define FK_READ_CHAIN_BATCH 2
-// One register budget, the whole file (k_read_chain_lw): a list of several entries is always a read, which never parks the gate wave
-// beside its launches (path.hpp read_local: wide), so a capped form could never be launched.
-#define FK_READ_CHAIN_NAME k_read_chain_lw
+#define FK_READ_CHAIN_ARGS RowChainTableArgs
+#define FK_READ_CHAIN_TABLE 1
+// One register budget, the whole file (k_read_chain_t): several addresses are never a gated read_prepare_write, the only operation that parks
+// the gate wave beside its launches (path.hpp read_local: wide), so a capped form could never be launched.
+#define FK_READ_CHAIN_NAME k_read_chain_t
 #define FK_VG FK_WIDE_VGPRS
 #include "chain_kernels.inc"
 #undef FK_READ_CHAIN_NAME
 #undef FK_VG
 #undef FK_READ_CHAIN_ARGS
-#undef FK_READ_CHAIN_BATCH
+#undef FK_READ_CHAIN_TABLE
 
-// (defined in write_chain.inc, which is included twice: k_write_chain, and k_write_chain_b with a per-member operand table — the write
+// (defined in write_chain.inc, which is included twice: k_write_chain, and k_write_chain_t with a per-member operand table — the write
 // chain over the rows of the M members of a bank as ONE launch, y = m * ws + w: ct_lo from slot y, the shared trace keys, and the inverse
-// digits of coordinate 0 of member y / ws at ep.ggsw[i] + (y / ws) * opnd_stride.  src_rows is not used: every operand but the digits is per y.)
+// digits of coordinate 0 of member y / ws at ep.ggsw[i] + (y / ws) * opnd_stride.  The map is not read: every operand but the digits is per y.)
 #define FK_WRITE_CHAIN_ARGS RowChainArgs
-#define FK_WRITE_CHAIN_BATCH 0
+#define FK_WRITE_CHAIN_TABLE 0
 #define FK_WRITE_CHAIN_NAME k_write_chain
 #include "write_chain.inc"
 #undef FK_WRITE_CHAIN_ARGS
-#undef FK_WRITE_CHAIN_BATCH
+#undef FK_WRITE_CHAIN_TABLE
 #undef FK_WRITE_CHAIN_NAME
-#define FK_WRITE_CHAIN_ARGS RowChainBatchArgs
-#define FK_WRITE_CHAIN_BATCH 1
-#define FK_WRITE_CHAIN_NAME k_write_chain_b
+#define FK_WRITE_CHAIN_ARGS RowChainTableArgs
+#define FK_WRITE_CHAIN_TABLE 1
+#define FK_WRITE_CHAIN_NAME k_write_chain_t
 #include "write_chain.inc"
 #undef FK_WRITE_CHAIN_ARGS
-#undef FK_WRITE_CHAIN_BATCH
+#undef FK_WRITE_CHAIN_TABLE
 #undef FK_WRITE_CHAIN_NAME
 
 // ---------------------------------------------------------------------------------------
@@ -1968,24 +1942,24 @@ __device__ __forceinline__ void ld_l2_pair(const int32_t* p, int& a, int& b) {
 // coefficient anyway) for s < n-1, and a workgroup of step s+1 loads ONE limb polynomial (16 KB) instead of three.
 #define FK_TAIL_NAME k_trace_tail
 #define FK_TAIL_ARGS TailArgs
-#define FK_TAIL_BATCH 0
+#define FK_TAIL_TABLE 0
 #include "trace_tail.inc"
 #undef FK_TAIL_NAME
 #undef FK_TAIL_ARGS
-#undef FK_TAIL_BATCH
-// fheram_read_batch: the tail over the word_size ciphertexts of several addresses (y = k * ws + w, at most TAIL_GROUPS in all); the
+#undef FK_TAIL_TABLE
+// The table form: the tail over the word_size ciphertexts of several addresses (y = k * ws + w, at most TAIL_GROUPS in all); the
 // products of ciphertext y take the prepared digits of address y / ws, at ggsw[i] + (y / ws) * opnd_stride
-struct TailBatchArgs : TailArgs {
+struct TailTableArgs : TailArgs {
     long opnd_stride = 0;
     int ws = 1;
 };
-#define FK_TAIL_NAME k_trace_tail_b
-#define FK_TAIL_ARGS TailBatchArgs
-#define FK_TAIL_BATCH 1
+#define FK_TAIL_NAME k_trace_tail_t
+#define FK_TAIL_ARGS TailTableArgs
+#define FK_TAIL_TABLE 1
 #include "trace_tail.inc"
 #undef FK_TAIL_NAME
 #undef FK_TAIL_ARGS
-#undef FK_TAIL_BATCH
+#undef FK_TAIL_TABLE
 
 #ifdef FK_STAMP
 // Diagnostic: one inverse + one forward pair transform with stamps around them.

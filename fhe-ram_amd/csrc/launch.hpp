@@ -317,12 +317,12 @@ void launch_trace_chain(fheram_ctx* c, GlweRef src, const GlweRef (&b)[2], int s
     });
 }
 // The operand table of a launch over several addresses (path.hpp Opnds::table): gy = n * ws ciphertexts, ciphertext y takes the prepared
-// digits of address y / ws, which are `stride` elements apart from prep on, and reads a rows source at y mod src_rows (ws: every address reads
-// the same rows, fheram_read_batch; n * ws: its own, a bank range).  ws == 0: one address, no table (the kernels without one).
-// src_rows is read by launch_read_chain only: the write chain and the tail's fallback always run on rows of their own (y mod gy).
-// mapped (fheram_bank_read_list): the rows source is a bank's and entry k reads member (src_map >> 4k) & 15 of it, row
-// member * ws + y mod ws (k_read_chain_lw); like src_rows read by launch_read_chain only.
-struct OpndTable { int ws = 0; long stride = 0; int src_rows = 0; bool mapped = false; unsigned src_map = 0; };
+// digits of address k = y / ws, which are `stride` elements apart from prep on, and reads the rows of member (src_map >> 4k) & 15 of the
+// rows source, row member * ws + y mod ws (all 0: every address reads the same rows, fheram_read_batch; the identity: its own, a bank range;
+// anything: fheram_bank_read_list).  ws == 0: one address, no table (the kernels without one).
+// src_map is read by launch_read_chain only: the write chain and the tail's fallback always run on rows of their own (row y is y).
+struct OpndTable { int ws = 0; long stride = 0; unsigned src_map = 0; };
+constexpr unsigned SRC_MAP_IDENTITY = 0x76543210u;   // entry k reads member k
 // The two chains a row goes through back to back as ONE launch (k_read_chain / k_write_chain): both must be in the Chain form
 // (chain_form: whether the trace chain's first step reads rotated input does not matter to it), in the variants that hand over through
 // LDS and registers.  one_wg: ChainQuery's.
@@ -331,12 +331,12 @@ bool use_row_fuse(const fheram_ctx* c, int d, int n_tr, int gx, int gy, bool one
            chain_form(c, ChainQuery{true, d, gx, gy, false, one_wg}).form == ChainForm::Chain &&
            chain_form(c, ChainQuery{false, n_tr, gx, gy, false, one_wg}).form == ChainForm::Chain;
 }
-// the arguments of a `_b` kernel: those of the row chain with the operand table behind them; row y reads the source at y mod src_rows
-RowChainBatchArgs with_table(const RowChainArgs& ra, const OpndTable& t, int src_rows) {
-    RowChainBatchArgs rb;
-    static_cast<RowChainArgs&>(rb) = ra;
-    rb.opnd_stride = t.stride; rb.ws = t.ws; rb.src_rows = src_rows;
-    return rb;
+// the arguments of a `_t` kernel: those of the row chain with the operand table behind them
+RowChainTableArgs with_table(const RowChainArgs& ra, const OpndTable& t) {
+    RowChainTableArgs rt;
+    static_cast<RowChainArgs&>(rt) = ra;
+    rt.opnd_stride = t.stride; rt.ws = t.ws; rt.src_map = t.src_map;
+    return rt;
 }
 void fill_row_chain(fheram_ctx* c, RowChainArgs& ra, const double* prep, int d, int start, int n_tr) {
     ra.ep.tw = c->d_tw; ra.ep.n = d;
@@ -346,8 +346,7 @@ void fill_row_chain(fheram_ctx* c, RowChainArgs& ra, const double* prep, int d, 
 }
 // read / read_prepare_write: d products of `src` with the prepared digits, then trace steps 0 .. n_tr-1 (the alone packer levels);
 // the result lands in dst; ep_store != nullptr: the products' result is also written there (in-place products of read_prepare_write)
-// with a table: row y reads src at y mod t.src_rows and the digits of address y / t.ws (k_read_chain_b / _bw); with a source map in it,
-// src at row map(y / t.ws) * t.ws + y mod t.ws (k_read_chain_lw)
+// with a table: row y reads src at row map(y / t.ws) * t.ws + y mod t.ws and the digits of address y / t.ws (k_read_chain_t)
 void launch_read_chain(fheram_ctx* c, GlweRef src, const GlweRef* ep_store, GlweRef dst, const double* prep, int d, int n_tr, int gx, int gy, const OpndTable& t) {
     ProfScope ps(c, "read_chain_launch", (uint64_t)gx * gy, 1);
     RowChainArgs ra;
@@ -358,29 +357,22 @@ void launch_read_chain(fheram_ctx* c, GlweRef src, const GlweRef* ep_store, Glwe
     ra.ks.base = ks_args(c, dst, dst, dst, trace_key(c, 0), c->gal[0]);
     ra.ks.buf[0] = ra.ks.buf[1] = dst;                            // only the last step stores
     ra.hi = dst; ra.trhi = dst;
-    if (t.mapped) {   // a read list: never beside the gate wave (read_local: wide), so the whole register file, as k_write_chain
-        RowChainListArgs rl;
-        static_cast<RowChainArgs&>(rl) = ra;
-        rl.opnd_stride = t.stride; rl.ws = t.ws; rl.src_map = t.src_map;
+    if (t.ws > 0) {   // several addresses: never beside the gate wave (read_local: wide), so the whole register file, as k_write_chain
         c->wide_unsynced = true;
-        with_evk(c, [&](auto sk) { hipLaunchKernelGGL((k_read_chain_lw<decltype(sk)::value, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rl); });
+        with_evk(c, [&](auto sk) {
+            constexpr int SK = decltype(sk)::value;
+            hipLaunchKernelGGL((k_read_chain_t<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, with_table(ra, t));
+        });
         return;
     }
     with_evk_wide(c, c->wide, [&](auto sk, auto w) {
         constexpr int SK = decltype(sk)::value;
-        constexpr bool W = decltype(w)::value;
-        if (t.ws > 0) {
-            const RowChainBatchArgs rb = with_table(ra, t, t.src_rows);
-            if constexpr (W) hipLaunchKernelGGL((k_read_chain_bw<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
-            else hipLaunchKernelGGL((k_read_chain_b<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, rb);
-        } else {
-            if constexpr (W) hipLaunchKernelGGL((k_read_chain_w<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ra);
-            else hipLaunchKernelGGL((k_read_chain<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ra);
-        }
+        if constexpr (decltype(w)::value) hipLaunchKernelGGL((k_read_chain_w<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ra);
+        else hipLaunchKernelGGL((k_read_chain<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ra);
     });
 }
 // write: trace steps 0 .. n_tr-1 of ct_lo * X^-row (src, read rotated), data <- normalize(data - trhi + that), d products in place
-// with a table (a bank range: every member its own rows): row y takes the inverse digits of member y / t.ws (k_write_chain_b)
+// with a table (a bank range: every member its own rows): row y takes the inverse digits of member y / t.ws (k_write_chain_t, which reads no map)
 void launch_write_chain(fheram_ctx* c, GlweRef src, int rot_mul, int rot_base, GlweRef data, GlweRef trhi, const double* prep, int d, int n_tr, int gx, int gy, const OpndTable& t) {
     ProfScope ps(c, "write_chain_launch", (uint64_t)gx * gy, 1);
     RowChainArgs ra;
@@ -392,7 +384,7 @@ void launch_write_chain(fheram_ctx* c, GlweRef src, int rot_mul, int rot_base, G
     c->wide_unsynced = true;                                      // (k_write_chain takes the whole register file)
     with_evk(c, [&](auto sk) {
         constexpr int SK = decltype(sk)::value;
-        if (t.ws > 0) hipLaunchKernelGGL((k_write_chain_b<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, with_table(ra, t, gy));
+        if (t.ws > 0) hipLaunchKernelGGL((k_write_chain_t<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, with_table(ra, t));
         else hipLaunchKernelGGL((k_write_chain<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ra);
     });
 }
@@ -400,7 +392,8 @@ void launch_write_chain(fheram_ctx* c, GlweRef src, int rot_mul, int rot_base, G
 // prep != nullptr (round 6): the d external products with the prepared digits at `prep` run in front of the trace chain in the SAME launch
 // (coordinate 1's products, ram.rs:454 / 525-527): src -> products -> ep_out -> trace -> b[(n - 1) & 1]; store_ep: the caller needs ep_out
 // afterwards (read_prepare_write's tree[0]).  The fallback launch is then the fused row chain (k_read_chain), predicated likewise.
-// with a table (and prep): ciphertext y takes the digits of address y / t.ws (k_trace_tail_b, and k_read_chain_b as its fallback)
+// with a table (and prep): ciphertext y takes the digits of address y / t.ws (k_trace_tail_t, and k_read_chain_t as its fallback: on the
+// operation's own arenas, where row y is y whatever the operand set's map says — the identity; a whole-register-file launch like every k_read_chain_t)
 void launch_trace_tail(fheram_ctx* c, GlweRef src, const GlweRef (&b)[2], int start, int n, int gx, int gy,
                        const double* prep = nullptr, int d = 0, GlweRef ep_out = GlweRef{nullptr, 0, 0}, bool store_ep = false, const OpndTable& t = {}) {
     ProfScope ps(c, "keyswitch", (uint64_t)gx * gy, n);
@@ -436,11 +429,12 @@ void launch_trace_tail(fheram_ctx* c, GlweRef src, const GlweRef (&b)[2], int st
         constexpr int SK = decltype(sk)::value;
         const dim3 groups(TAIL_GROUPS * 2 * SK * 3);
         if (t.ws > 0 && ta.n_ep) {
-            TailBatchArgs tb;
-            static_cast<TailArgs&>(tb) = ta;
-            tb.opnd_stride = t.stride; tb.ws = t.ws;
-            hipLaunchKernelGGL((k_trace_tail_b<3, SK, 3>), groups, dim3(T), LDS_BYTES, c->cur, tb);
-            hipLaunchKernelGGL((k_read_chain_b<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, with_table(ra, t, gx * gy));   // the source is the batch's own: row y is y
+            TailTableArgs tt;
+            static_cast<TailArgs&>(tt) = ta;
+            tt.opnd_stride = t.stride; tt.ws = t.ws;
+            hipLaunchKernelGGL((k_trace_tail_t<3, SK, 3>), groups, dim3(T), LDS_BYTES, c->cur, tt);
+            c->wide_unsynced = true;
+            hipLaunchKernelGGL((k_read_chain_t<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, with_table(ra, OpndTable{t.ws, t.stride, SRC_MAP_IDENTITY}));
             return;
         }
         hipLaunchKernelGGL((k_trace_tail<3, SK, 3>), groups, dim3(T), LDS_BYTES, c->cur, ta);

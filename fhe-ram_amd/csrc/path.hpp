@@ -2,7 +2,8 @@
 // ONE read sequence (read_local + read_top, together read_impl) and ONE write sequence (write_side_begin, write_top, write_rows), over an
 // operand set (Opnds: whose digits a product uses, whose RAM state it updates) and a view (RamView: the buffers it runs on).  The plain context, the stages of
 // a row-sharded RAM (fheram.hip, group.hpp), fheram_read_batch and fheram_bank_* (bank.hpp; its read list too) all run these; what is specific to one of them
-// is a visible condition in the sequence (n == 1: pre_inv, the gate wave, ev_opstart, ev_wdone, sharding, capture; a bank range or list: Opnds::row_fuse).
+// is a visible condition in the sequence (n == 1: pre_inv, the gate wave, ev_opstart, ev_wdone, sharding, capture; a bank range or list: Opnds::bank in row_fuse).
+// Several addresses are ONE kind of operand set (table_opnds: a digit table and a source map) and several reads ONE buffer set (ReadBufs, read_many).
 #pragma once
 #include "launch.hpp"
 
@@ -20,30 +21,36 @@ struct Opnds {
     int n, ws;
     double *tab, *tab_inv;   // (inverse) digits of address 0
     long stride;
-    bool own_rows;           // a bank range: address k reads and writes member k's rows; false (fheram_read_batch): every address reads the same rows
-    bool mapped = false;     // a bank's read list: address k reads member member(k)'s rows of the view's (the whole bank's); read-only
-    unsigned src_map = 0;    // ... the source map, four bits per entry: what the table forms take by value (launch.hpp OpndTable)
+    // whose rows address k works on: member (src_map >> 4k) & 15 of the view's rows, four bits per address — what the table forms take by value
+    // (launch.hpp OpndTable).  n == 1 and fheram_read_batch: 0, every address the view's first ws rows; a bank range: the identity, address k
+    // reads and writes member k of the range; a bank's read list: its members, of the whole bank's rows (read-only)
+    unsigned src_map;
+    bool bank;               // a range or a read list of a bank of several members, n > 1: row_fuse
     int member(int k) const { return (int)((src_map >> (4 * k)) & 15u); }
     int Y() const { return n * ws; }
     double* prep(int k, int ci) const { return digits_of(c, tab + k * stride, ci); }
     double* inv(int k, int ci) const { return digits_of(c, tab_inv + k * stride, ci); }
     GlweRef slice(GlweRef r, int k) const { r.p += (long)k * ws * r.sy; return r; }   // address k's ws ciphertexts
-    GlweRef rows(GlweRef r, int k) const { return mapped ? slice(r, member(k)) : own_rows ? slice(r, k) : r; }
-    OpndTable table() const { return n == 1 ? OpndTable{} : OpndTable{ws, stride, own_rows ? Y() : ws, mapped, src_map}; }
+    GlweRef rows(GlweRef r, int k) const { return slice(r, member(k)); }
+    OpndTable table() const { return n == 1 ? OpndTable{} : OpndTable{ws, stride, src_map}; }
     // The fused row chain (k_read_chain / k_write_chain) for this operation.  A lone context — and a batch like it — splits by column while
     // rows * ws * 2 workgroups still fit the chip (pick_nco), which rules the chain out; for a range of bank members the alternative to the ONE
     // launch with an operand table is not one column-split launch per step but one per MEMBER and step, so the range takes one workgroup
     // per ciphertext from the start, and so does a read list, which is a bank operation.  (The smaller regimes — limb split, fine split, the
     // mid chains — keep their precedence: chain_form.)
-    bool row_fuse(int d, int n_tr, int gx) const { return use_row_fuse(c, d, n_tr, gx, Y(), n > 1 && (own_rows || mapped)); }
+    bool row_fuse(int d, int n_tr, int gx) const { return use_row_fuse(c, d, n_tr, gx, Y(), bank); }
 };
 // the plain operation: one address (a = &addr), the context's d_prep / d_prep_inv, ws ciphertexts (the context's word count and RAM; one member of a bank: its)
-Opnds one_addr(fheram_ctx* c, const fheram_addr* const* a, int ws, RamState* st) { return Opnds{c, st, a, 1, ws, c->d_prep, c->d_prep_inv, 0, true}; }
+Opnds one_addr(fheram_ctx* c, const fheram_addr* const* a, int ws, RamState* st) { return Opnds{c, st, a, 1, ws, c->d_prep, c->d_prep_inv, 0, 0, false}; }
 Opnds one_addr(fheram_ctx* c, const fheram_addr* const* a) { return one_addr(c, a, c->ws, &c->ram); }
+// n > 1 addresses of ws ciphertexts, their digits in a table ([n][n_digits] prepared GGSW; tab_inv: of a set that is written, else nullptr)
+Opnds table_opnds(fheram_ctx* c, RamState* st, const fheram_addr* const* addrs, int n, int ws, double* tab, double* tab_inv, unsigned src_map, bool bank) {
+    return Opnds{c, st, addrs, n, ws, tab, tab_inv, (long)c->n_digits * (long)fheram_ctx::GGSW, src_map, bank};
+}
 
 // An operation's VIEW: every buffer indexed by ciphertext y, from the operation's first.  The rows, the ping-pong arenas A / B with the third
 // and fourth (pack_levels P0 / P1; the write's trace(ct_hi)), the per-ciphertext buffers, and where the result goes.  The context's own
-// (ctx_view), a batch's (batch_view below: a batch never writes), a range of a bank's members (bank.hpp bank_view) or a bank's read list (list_view).
+// (ctx_view), those of a read of several addresses (reads_view below: a batch's or a read list's, never written through), or a range of a bank's members (bank.hpp bank_view).
 struct RamView {
     int32_t *rows, *A, *B, *C, *D;   // [Y][rows]
     int32_t *part, *tmp, *tmp2, *res, *tree, *w, *trtop;   // [Y]; part: the packed row where no arena holds it (rows == 1, a shard's partial) / the un-rotated ct_lo
@@ -228,59 +235,59 @@ int read_impl(const Opnds& o, const RamView& a, bool prepare_write) {
     return rc;
 }
 
-// ---- fheram_read_batch: K Ram::read (ram.rs:172-191) of the same RAM as one launch sequence ---------------------------------------
-// A read does not change the RAM (SubRam::read asserts !state and only writes its scratch, ram.rs:393-396): K reads at K addresses
-// share the rows, the keys and every packing and trace step; only the products with the address digits differ.  The batch runs on
-// arenas of its own, [K * ws][rows] GLWEs with the rows' stride, so that ciphertext y = k * ws + w is word w of address k and every
-// address-independent step is ONE launch over gy = K * ws.
-void batch_free(fheram_ctx* c) {
-    void* bufs[] = {c->d_bA, c->d_bB, c->d_bC, c->d_bres, c->d_btmp, c->d_btmp2, c->d_bprep};
-    for (void* b : bufs) if (b) hipFree(b);
-    if (c->h_bres) hipHostFree(c->h_bres);
-    c->d_bA = c->d_bB = c->d_bC = c->d_bres = c->d_btmp = c->d_btmp2 = nullptr;
-    c->d_bprep = nullptr;
-    c->h_bres = c->d_h_bres = nullptr;
-    c->batch_cap = 0;
+// ---- several Ram::read (ram.rs:172-191) as one launch sequence: fheram_read_batch, fheram_bank_read_list ------------------------------
+// A read does not change the RAM (SubRam::read asserts !state and only writes its scratch, ram.rs:393-396): n reads at n addresses share the
+// keys and every packing and trace step; only the products with the address digits differ (and, in a bank, whose rows they read).  Such an
+// operation runs on buffers of its own (ctx.hpp ReadBufs), [n * ws][rows] GLWEs with the rows' stride, so that ciphertext y = k * ws + w is
+// word w of address k and every address-independent step is ONE launch over gy = n * ws.
+void reads_free(ReadBufs& L) {
+    void* bufs[] = {L.A, L.B, L.C, L.res, L.tmp, L.tmp2, L.prep};
+    for (void* p : bufs) if (p) hipFree(p);
+    if (L.h_res) hipHostFree(L.h_res);
+    L = ReadBufs{};
 }
-// The third arena is only needed where the alone packer levels run as the single-launch tail chain on the batch's rows (at most
-// TAIL_GROUPS ciphertexts: 2^13 with K * ws <= 4), whose source must survive the launch (pack_levels P0): allocated only then.
+// The third arena is only needed where the alone packer levels run as the single-launch tail chain on the operation's rows (at most
+// TAIL_GROUPS ciphertexts: 2^13 with n * ws <= 4), whose source must survive the launch (pack_levels P0): allocated only then.
 // (The very question pack_levels asks; the fused row chain, which would leave it no alone levels, excludes the Tail form: launch.hpp chain_form.)
 // n_ct: the operation's ciphertexts (a batch: K * ws; a bank's read list, whose context has the word count of the whole bank: n * its members' ws)
 bool third_arena_needed(const fheram_ctx* c, int n_ct) {
     return c->n2 == 2 && chain_form(c, ChainQuery{false, LOGN - ilog2_ceil(c->rows_glob), (int)c->rows, n_ct}).form == ChainForm::Tail;
 }
-bool batch_needs_third(const fheram_ctx* c, int K) { return third_arena_needed(c, K * c->ws); }
-// grows the batch buffers to K addresses (and adds the third arena when this batch needs it); on failure the context holds none of
-// them (and single reads are unaffected)
-int batch_reserve(fheram_ctx* c, int K) {
-    const bool third = batch_needs_third(c, K);
-    if (K <= c->batch_cap && (!third || c->d_bC)) return FHERAM_OK;
-    if (K < c->batch_cap) K = c->batch_cap;   // (only the third arena is missing: keep the capacity)
-    if (c->batch_cap) { HIPCHK(c, hipStreamSynchronize(c->stream)); batch_free(c); }
-    const size_t G = fheram_ctx::GLWE, nct = (size_t)K * c->ws, nrow = nct * c->rows;
+// grows the buffers to n addresses of ws ciphertexts (and adds the third arena when this operation needs it); on failure the owner holds
+// none of them (and every other operation is unaffected).  One address is the plain read on the RAM's own buffers: it needs the result
+// buffers only, so the arenas, the temporaries and the digit table wait for the first operation of several addresses.  Regrowing never
+// drops what existed.
+int reads_reserve(fheram_ctx* c, ReadBufs& L, int n, int ws) {
+    const bool work = n > 1, third = work && third_arena_needed(c, n * ws);
+    if (n <= L.cap && (!work || L.A) && (!third || L.C)) return FHERAM_OK;
+    if (n < L.cap) n = L.cap;   // (only the working buffers or the third arena are missing: keep the capacity)
+    const bool had_work = L.A != nullptr, had_third = L.C != nullptr;
+    if (L.cap) { HIPCHK(c, hipStreamSynchronize(c->stream)); reads_free(L); }
+    const size_t G = fheram_ctx::GLWE, nct = (size_t)n * ws, nrow = nct * c->rows;
     hipError_t e = hipSuccess;
     auto dev = [&](auto** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc((void**)p, bytes); };
-    dev(&c->d_bA, nrow * G * sizeof(int32_t));
-    dev(&c->d_bB, nrow * G * sizeof(int32_t));
-    if (third) dev(&c->d_bC, nrow * G * sizeof(int32_t));
-    dev(&c->d_bres, nct * G * sizeof(int32_t));
-    dev(&c->d_btmp, nct * G * sizeof(int32_t));
-    dev(&c->d_btmp2, nct * G * sizeof(int32_t));
-    dev(&c->d_bprep, (size_t)K * c->n_digits * fheram_ctx::GGSW * sizeof(double));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_bres, (nct * G + 1) * sizeof(int64_t), hipHostMallocMapped);   // + the monitor's maximum
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&c->d_h_bres, c->h_bres, 0);
-    if (e != hipSuccess) {
-        batch_free(c);
-        (void)hipGetLastError();   // the next op's error check must not see this allocation's failure
-        return fail(c, FHERAM_ERR_DEVICE, std::string("read batch buffers for ") + std::to_string(K) + " addresses: " + hipGetErrorString(e));
+    dev(&L.res, nct * G * sizeof(int32_t));
+    if (work || had_work) {
+        dev(&L.A, nrow * G * sizeof(int32_t));
+        dev(&L.B, nrow * G * sizeof(int32_t));
+        if (third || had_third) dev(&L.C, nrow * G * sizeof(int32_t));
+        dev(&L.tmp, nct * G * sizeof(int32_t));
+        dev(&L.tmp2, nct * G * sizeof(int32_t));
+        dev(&L.prep, (size_t)n * c->n_digits * fheram_ctx::GGSW * sizeof(double));
     }
-    c->batch_cap = K;
+    if (e == hipSuccess) e = hipHostMalloc((void**)&L.h_res, (nct * G + 1) * sizeof(int64_t), hipHostMallocMapped);   // + the monitor's maximum
+    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&L.d_h_res, L.h_res, 0);
+    if (e != hipSuccess) {
+        reads_free(L);
+        (void)hipGetLastError();   // the next op's error check must not see this allocation's failure
+        return fail(c, FHERAM_ERR_DEVICE, std::string("read buffers for ") + std::to_string(n) + " addresses: " + hipGetErrorString(e));
+    }
+    L.cap = n;
     return FHERAM_OK;
 }
-// The batch as an operand set and a view for read_impl: the digits' table is d_bprep, every address reads the context's rows and the
-// launches write batch arenas only.  The result of address k is at d_bres + k * ws GLWEs; rows == 1: the products land in d_btmp2.
-Opnds batch_opnds(fheram_ctx* c, const fheram_addr* const* addrs, int K) { return Opnds{c, &c->ram, addrs, K, c->ws, c->d_bprep, nullptr, (long)c->n_digits * (long)fheram_ctx::GGSW, false}; }
-RamView batch_view(const fheram_ctx* c) { return RamView{c->d_data, c->d_bA, c->d_bB, c->d_bC, nullptr, c->d_btmp2, c->d_btmp, c->d_btmp2, c->d_bres, nullptr, nullptr, nullptr}; }
+// The view of such an operation for read_impl: the context's rows (a bank's: the whole bank's, reached through the operand set's map), and
+// every launch writes the set's buffers only.  The result of address k is at res + k * ws GLWEs; rows == 1: the products land in tmp2.
+RamView reads_view(const fheram_ctx* c, const ReadBufs& L) { return RamView{c->d_data, L.A, L.B, L.C, nullptr, L.tmp2, L.tmp, L.tmp2, L.res, nullptr, nullptr, nullptr}; }
 
 // The one result export: every run (source, int32 count) is widened by the device into the pinned buffer h (device address d_h), back to
 // back, with the monitor's maximum as it stood then behind the last (the export kernel copies it there); out != nullptr: copied out.
@@ -302,6 +309,26 @@ int result_export(fheram_ctx* c, const ResRun* runs, int n_runs, int64_t* h, int
     const int rc = check_precision(c);
     if (rc == FHERAM_OK && out) std::memcpy(out, h, n * sizeof(int64_t));
     return rc;
+}
+
+// the results of ciphertexts [first, first + n_ct) of such an operation, widened into its pinned buffer; out: [n_ct][GLWE] int64
+int reads_export(fheram_ctx* c, const ReadBufs& L, size_t first, size_t n_ct, int64_t* out) {
+    const ResRun run{L.res + first * fheram_ctx::GLWE, n_ct * fheram_ctx::GLWE};
+    return result_export(c, &run, 1, L.h_res, L.d_h_res, out);
+}
+// n >= 2 reads as one operation on `L`: address k reads member (src_map >> 4k) & 15 of the context's rows.  kept(o): what the caller's
+// RAM(s) keep of it (where a single read would have left its result), enqueued behind the reads.
+// (Never captured: the launch sequence depends on n addresses, and a read's state bookkeeping is done as it is enqueued.)
+template <typename F>
+int read_many(fheram_ctx* c, ReadBufs& L, RamState* st, const fheram_addr* const* addrs, int n, int ws, unsigned src_map, bool bank, int64_t* out, F&& kept) {
+    int rc = reads_reserve(c, L, n, ws);
+    if (rc != FHERAM_OK) return rc;
+    const Opnds o = table_opnds(c, st, addrs, n, ws, L.prep, nullptr, src_map, bank);
+    rc = read_impl(o, reads_view(c, L), false);
+    if (rc != FHERAM_OK) return rc;
+    kept(o);
+    HIPCHK(c, hipGetLastError());
+    return out ? reads_export(c, L, 0, (size_t)n * ws, out) : FHERAM_OK;
 }
 
 // Ram::write (ram.rs:226-294) of every address of the operand set, in two stages and a side stage.

@@ -1,6 +1,6 @@
-// Included TWICE by kernels.hpp (no include guard): k_trace_tail (one read) and k_trace_tail_b (fheram_read_batch).
-//   FK_TAIL_NAME : kernel name;  FK_TAIL_ARGS : TailArgs or TailBatchArgs;  FK_TAIL_BATCH : 1 = the products' operands of ciphertext
-//   y are those of address y / ws (TailBatchArgs), 0 = one address
+// Included TWICE by kernels.hpp (no include guard): k_trace_tail (one read) and k_trace_tail_t (several addresses: a batch, a bank range, a read list).
+//   FK_TAIL_NAME : kernel name;  FK_TAIL_ARGS : TailArgs or TailTableArgs;  FK_TAIL_TABLE : 1 = the products' operands of ciphertext
+//   y are those of address y / ws (TailTableArgs), 0 = one address
 template <int SX, int SK, int SO>
 __global__ __launch_bounds__(T, T / 256) void FK_TAIL_NAME(FK_TAIL_ARGS ta) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -25,7 +25,7 @@ __global__ __launch_bounds__(T, T / 256) void FK_TAIL_NAME(FK_TAIL_ARGS ta) {
     const bool ep_member = m < GE;
     const long ct = (long)(g / ta.gx);
     const long cx = (long)(g % ta.gx);
-#if FK_TAIL_BATCH
+#if FK_TAIL_TABLE
     const long oset = (ct / ta.ws) * ta.opnd_stride;   // this ciphertext's address: its prepared digits
 #define FK_TAIL_OPND(i) (ta.ggsw[i] + oset)
 #else

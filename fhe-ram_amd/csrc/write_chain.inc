@@ -1,9 +1,9 @@
 // Included by kernels.hpp (no include guard): a row's write chain (ram.rs:612-646, see RowChainArgs in kernels.hpp), instantiated twice.
-//   FK_WRITE_CHAIN_NAME : kernel name;  FK_WRITE_CHAIN_ARGS / FK_WRITE_CHAIN_BATCH : RowChainArgs / 0, or RowChainBatchArgs / 1 for the
+//   FK_WRITE_CHAIN_NAME : kernel name;  FK_WRITE_CHAIN_ARGS / FK_WRITE_CHAIN_TABLE : RowChainArgs / 0, or RowChainTableArgs / 1 for the
 //   write chain of a bank (fheram_bank_write): ciphertext y = m * ws + w takes the inverse digits of member y / ws
-#if FK_WRITE_CHAIN_BATCH
+#if FK_WRITE_CHAIN_TABLE
 // recomputed where it is used rather than kept live across the steps (see FK_RC_OPND in chain_kernels.inc)
-#define FK_WC_OPND(i) (ra.ep.ggsw[i] + batch_opnd_offset(ra))
+#define FK_WC_OPND(i) (ra.ep.ggsw[i] + table_opnd_offset(ra))
 #else
 #define FK_WC_OPND(i) ra.ep.ggsw[i]
 #endif

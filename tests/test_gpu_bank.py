@@ -298,8 +298,8 @@ CLASSES = ["write_chain_launch", "read_chain_launch", "keyswitch_tail_launch", "
 
 
 def test_table_kernels_run_2_16(w16):
-    """M = 2 at ws = 4 is 8 ciphertexts = TAIL_GROUPS: the rows' chains of both members are ONE k_read_chain_b / k_write_chain_b launch
-    and the end of a read ONE k_trace_tail_b.  A bank that ran everything per member would show two launches of each."""
+    """M = 2 at ws = 4 is 8 ciphertexts = TAIL_GROUPS: the rows' chains of both members are ONE k_read_chain_t / k_write_chain_t launch
+    and the end of a read ONE k_trace_tail_t.  A bank that ran everything per member would show two launches of each."""
     w = w16
     M = 2
     rows = w.params.rows()
@@ -362,8 +362,59 @@ def test_wider_banks_end_in_the_mid_chain_2_16(w16, M):
     assert ms["launches"] > 0 and ms["fallbacks"] == 0, ms
 
 
+@pytest.fixture(scope="module")
+def w16x8(po):
+    """2^16 at word size 1, eight members: 16 rows each, 128 ciphertext rows in all"""
+    return World(po, 1 << 16, 8, word_size=1, seed=120, n_addr=3)
+
+
+@pytest.mark.parametrize("first,n", [(0, 8), (3, 5)], ids=["all-8", "members-3-to-7"])
+def test_eight_members_one_row_chain_2_16(w16x8, first, n):
+    """The smallest shape where a range's row chain is the fused launch with source-map entries 4..7 in use: 16 rows x 8 members, and
+    the sub-range [3, 8) of it (80 ciphertext rows, the identity map relative to the range's view).  read, read_prepare_write, write
+    and the read-back are each ONE read_chain_launch / write_chain_launch of rows * n blocks; every member of the range equals its
+    standalone Ram, every member outside it is untouched."""
+    w = w16x8
+    M, rows = 8, w.params.rows()
+    bank = w.new_bank(M)
+    rams = [w.new_ram(first + k) for k in range(n)]
+    outside = {m: member_snapshot(bank, m) for m in range(M) if not first <= m < first + n}
+    RDj = [(first + k) % 3 for k in range(n)]
+    WRj = [(2 * (first + k) + 1) % 3 for k in range(n)]
+    RDa, WRa = [w.addrs[j] for j in RDj], [w.addrs[j] for j in WRj]
+    vals, wct = w.words(n, seed=200 + first)
+
+    def one_chain(prof, cls):
+        assert prof[cls]["launches"] == 1 and prof[cls]["blocks"] == rows * n * w.ws, (cls, prof)
+
+    got, prof = profiled(bank, lambda: bank.read(RDa, w.keys, first=first), CLASSES)
+    one_chain(prof, "read_chain_launch")
+    for k in range(n):
+        assert np.array_equal(got[k], rams[k].read(RDa[k], w.keys)), k
+        w.check_word(got[k], w.data[first + k], RDj[k])
+    got, prof = profiled(bank, lambda: bank.read_prepare_write(WRa, w.keys, first=first), CLASSES)
+    one_chain(prof, "read_chain_launch")
+    for k in range(n):
+        assert np.array_equal(got[k], rams[k].read_prepare_write(WRa[k], w.keys)), k
+        assert_member_equals_ram(bank, first + k, rams[k], "rpw")
+    _, prof = profiled(bank, lambda: bank.write(wct, WRa, w.keys, first=first), CLASSES)
+    one_chain(prof, "write_chain_launch")
+    for k in range(n):
+        rams[k].write(wct[k], WRa[k], w.keys)
+        assert_member_equals_ram(bank, first + k, rams[k], "write")
+    got, prof = profiled(bank, lambda: bank.read(WRa, w.keys, first=first), CLASSES)
+    one_chain(prof, "read_chain_launch")
+    for k in range(n):
+        assert np.array_equal(got[k], rams[k].read(WRa[k], w.keys)), k
+        data2 = w.data[first + k].copy()
+        data2[w.ws * w.idx[WRj[k]]: w.ws * (w.idx[WRj[k]] + 1)] = vals[k]
+        w.check_word(got[k], data2, WRj[k], written=True)
+    for m, snap in outside.items():
+        assert_member_is(bank, m, snap, "outside the range")
+
+
 def test_tail_fallback_with_per_member_operands_2_16(w16):
-    """tail_test: the bank's k_trace_tail_b gives up late and the predicated k_read_chain_b behind it redoes coordinate 1's products
+    """tail_test: the bank's k_trace_tail_t gives up late and the predicated k_read_chain_t behind it redoes coordinate 1's products
     (operands of member y / ws) and the trace from the packed rows"""
     w = w16
     M = 2

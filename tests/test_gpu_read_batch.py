@@ -139,8 +139,8 @@ def test_one_row_and_readme_block(po, case):
 @pytest.fixture(scope="module", params=["source", "readme"])
 def w16(po, request):
     """2^16: coordinate 1 has two digits (base2d [[3,3,3,3],[3,1]]), so at K = 2 (8 ciphertexts) the batch's tail carries the
-    per-address products (k_trace_tail_b), and at K = 4 (16 rows x 16 ciphertexts) the row chains of all addresses are the one
-    fused launch (k_read_chain_bw).  "readme": the 5-limb trace keys (the <5, ...> instantiations)."""
+    per-address products (k_trace_tail_t), and at K = 4 (16 rows x 16 ciphertexts) the row chains of all addresses are the one
+    fused launch (k_read_chain_t).  "readme": the 5-limb trace keys (the <5, ...> instantiations)."""
     crypto = {} if request.param == "source" else {"k_glwe_pt": 9, "k_evk_trace": 85}
     return World(po, 1 << 16, seed=80, n_addr=4, **crypto)
 
@@ -168,7 +168,7 @@ def test_batched_kernels_2_16(w16):
 
 
 def test_tail_fallback_with_per_address_operands_2_16(w16):
-    """tail_test: the batch's k_trace_tail_b gives up late and the predicated k_read_chain_b behind it redoes coordinate 1's products
+    """tail_test: the batch's k_trace_tail_t gives up late and the predicated k_read_chain_t behind it redoes coordinate 1's products
     (operands of address y / ws) and the trace from the batch's packed rows"""
     w = w16
     ram = w.new_ram({"tail_test": 1})
@@ -182,6 +182,74 @@ def test_tail_fallback_with_per_address_operands_2_16(w16):
         for k, j in enumerate(sel):
             assert np.array_equal(got[k], seq[k]), (sel, k)
             w.check_word(got[k], j)
+
+
+def test_eight_addresses_one_row_chain_2_16(po):
+    """K = 8 at word size 1: the all-zero source map over all eight entries of k_read_chain_t (every entry reads the same 16 rows).
+    16 x 8 = 128 ciphertext rows are 256 workgroups when split by column, which a chip of 256 CUs still holds (launch.hpp pick_nco), so a
+    batch of this shape runs its products per address by default; with one workgroup per ciphertext (nco = 2) they are the ONE fused
+    launch of rows * 8 blocks.  Both against eight sequential reads, exactly."""
+    w = World(po, 1 << 16, word_size=1, seed=140, n_addr=8)
+    rows = w.ram.params.rows()
+    seq = [w.gpu_read(j) for j in range(8)]
+    for config in (None, {"nco": 2}):
+        ram = w.new_ram(config)
+        addrs = [w.pkg.Address(ram.params, list(g)) for g in w.addr_g]
+        own = [ram.read(a, w.keys).copy() for a in addrs]
+        ram.profile_enable(True)
+        ram.profile_reset()
+        got = ram.read_batch(addrs, w.keys)
+        prof = ram.profile_get("read_chain_launch")
+        ram.profile_enable(False)
+        print("read_batch K=8 2^16 ws=1", config, "read_chain_launch", prof)
+        for k in range(8):
+            assert np.array_equal(got[k], own[k]), (config, k)
+            assert np.array_equal(got[k], seq[k]), (config, k)
+        if config:
+            assert prof["launches"] == 1 and prof["blocks"] == rows * 8, prof
+    w.check_word(got[5], 5)
+    assert np.array_equal(got[7], w.oracle_read(7))
+
+
+def unsynced_flow(w, ram, sync):
+    """read_batch of two addresses left on the device, read_prepare_write, write and a read-back; sync: the host waits after every call"""
+    addrs = [w.pkg.Address(ram.params, list(g)) for g in w.addr_g[:3]]
+    for a in addrs:
+        a._device(ram)   # (the upload is a host wait of its own: before the flow)
+    wct = np.stack([w.o.glwe_encrypt_coeff0(17 + 5 * i, w.sk, 5200 + i, 5300 + i) for i in range(w.ws)])
+    wait = ram.sync if sync else (lambda: None)
+    ram.read_batch(addrs[:2], w.keys, download=False)
+    wait()
+    ram.read_prepare_write(addrs[2], w.keys, download=False)
+    wait()
+    ram.write(wct, addrs[2], w.keys)
+    wait()
+    return ram.read(addrs[2], w.keys).copy(), ram.store_encrypted(), ram.tree(0)
+
+
+def assert_unsynced_flow_equals_synced(w):
+    ram, ref = w.new_ram(), w.new_ram()
+    t0 = tail_stats(ram)
+    got = unsynced_flow(w, ram, False)
+    want = unsynced_flow(w, ref, True)
+    for g, x, what in zip(got, want, ("result", "rows", "tree")):
+        assert np.array_equal(g, x), (what, np.count_nonzero(g != x))
+    t1 = tail_stats(ram)
+    assert t1[0] > t0[0] and t1[1] == t0[1], (t0, t1)   # tail launches, and no fallback
+
+
+def test_batch_then_read_prepare_write_without_a_host_wait_2_14(w14):
+    """A batch of two (8 ciphertexts: its end is the tail launch), then — the host not waiting — read_prepare_write, which parks the gate
+    wave beside its launches, write and a read-back: result, rows and tree as with a host wait after every call, and the tail's
+    fallback never runs.  At 2^14 coordinate 1 has one digit, so the batch's tail is the trace alone (k_trace_tail)."""
+    assert_unsynced_flow_equals_synced(w14)
+
+
+def test_batch_then_read_prepare_write_without_a_host_wait_2_16(w16):
+    """The same where the batch's tail carries the per-address products (k_trace_tail_t, two digits: from 2^16 on) while its rows'
+    chains are not the fused launch: the fallback enqueued behind that tail is the whole-register-file k_read_chain_t, so the context
+    counts a wide launch as under way and the read_prepare_write behind it records ev_opstart for its gate wave."""
+    assert_unsynced_flow_equals_synced(w16)
 
 
 def test_2_18_against_committed_digests(po):

@@ -62,7 +62,7 @@ def ref14(w14):
 
 @pytest.fixture(scope="module")
 def w16(po):
-    """2^16: 16 rows, coordinate 1 has two digits: k_trace_tail_b at n * ws <= 8, the mid chain above it, the fused row chain"""
+    """2^16: 16 rows, coordinate 1 has two digits: k_trace_tail_t at n * ws <= 8, the mid chain above it, the fused row chain"""
     return World(po, 1 << 16, 2, seed=80, n_addr=3)
 
 
@@ -166,8 +166,8 @@ def test_forced_forms_equal_the_default_form(w14, w16, size, config):
 
 # ---- 5. the kernels that should run, do; 10. round-off --------------------------------------------------------------------------------------
 def test_list_kernels_run_2_16(w16, ref16):
-    """[1, 0] at ws = 4 is 8 ciphertexts: the rows' chains of both entries are ONE k_read_chain_lw launch — a permutation, which the
-    batch form's `y mod src_rows` cannot express — and the end of the read ONE k_trace_tail_b.  Four entries end in the mid chain."""
+    """[1, 0] at ws = 4 is 8 ciphertexts: the rows' chains of both entries are ONE k_read_chain_t launch — a permutation: the
+    source map neither a batch's (all 0) nor a range's (the identity) — and the end of the read ONE k_trace_tail_t.  Four entries end in the mid chain."""
     w = w16
     rows = w.params.rows()
     bank = w.new_bank(2)
@@ -193,7 +193,7 @@ def test_list_kernels_run_2_16(w16, ref16):
 
 
 def test_list_tail_fallback_2_16(w16, ref16):
-    """tail_test: the list's k_trace_tail_b gives up late, once, and the predicated k_read_chain_b behind it redoes coordinate 1's
+    """tail_test: the list's k_trace_tail_t gives up late, once, and the predicated k_read_chain_t behind it redoes coordinate 1's
     products (digits of entry y / ws) and the trace from the packed rows in the list's own arenas"""
     w = w16
     bank = w.new_bank(2, config={"tail_test": 1})

@@ -2,21 +2,23 @@
 //
 // hipLaunchKernelGGL is redefined as a recorder of (kernel, grid, workgroup, LDS bytes, stream side, argument bytes); with fake,
 // distinct addresses in the context's buffer fields the program calls trace_steps, ep_chain, pack_levels, the row-chain and tail launchers and the predicates path.hpp
-// derives from the same decision (Opnds::row_fuse for a context, a batch and a bank range; batch_needs_third; read_top's fuse_ep /
+// derives from the same decision (Opnds::row_fuse for a context, a batch and a bank range; third_arena_needed; read_top's fuse_ep /
 // gated) over a sweep of configurations, chain lengths, grids and buffer layouts.  Two trees dispatch alike exactly when their logs are
 // equal, so a change to a launch form is one `diff` away from its evidence:
 //
 //   hipcc -std=c++17 -O1 --offload-arch=gfx950 -ftrivial-auto-var-init=zero -Wno-unused-variable -Wno-unused-value -Wl,--unresolved-symbols=ignore-all -I fhe-ram_amd/csrc -I tools -o launch_log tools/launch_log.hip
-//   ./launch_log > profiles/chain_form_launch_log.txt      one digest line per configuration (FNV-1a over its launch lines)
+//   ./launch_log > chain_log.txt                           one digest line per configuration (FNV-1a over its launch lines); the committed
+//                                                          profiles/chain_form_launch_log.txt is the tree's of DESIGN.md 10.2, later ones are recorded by hash (10.5)
 //   ./launch_log 17                                        every launch line of configuration 17
 //
 // -ftrivial-auto-var-init=zero makes the padding of the argument structs part of a reproducible digest.  The include path names the
 // csrc/ to log; launch_log_shim.hpp (tools/ for this tree) reaches what has no name of its own there.
 // Trace chains are logged for 0 .. LOGN steps (the context has LOGN trace keys), product chains and the predicates for 0 .. CHAIN_MAX + 1.
 //
-// Second mode, the SEQUENCES themselves (path.hpp read_impl and the write triple) for a context, a batch and ranges of a bank's members:
+// Second mode, the SEQUENCES themselves (path.hpp read_impl and the write triple) for a context, a batch, ranges of a bank's members and
+// read lists of a bank of three:
 //
-//   ./launch_log path > profiles/ram_view_path_log.txt     one digest line per configuration
+//   ./launch_log path > path_log.txt                       one digest line per configuration (profiles/ram_view_path_log.txt: the tree's of DESIGN.md 10.4)
 //   ./launch_log path 17                                   every line of configuration 17
 //
 // Every buffer is a fake arena 4 GiB from the next, so an argument that points into one shows as a<arena>+<byte offset> behind the launch's
@@ -242,7 +244,7 @@ void run_config(fheram_ctx* c) {
         if (n >= 1 && n <= TAIL_EP_MAX && (gx == 1 || gx == 64) && (gy == 4 || gy == 8)) for (int v = 0; v < 2; v++) {
             rewind(c, as); cases++;
             head("row_chains", n, gx, gy, v);
-            const OpndTable t = v ? OpndTable{gy / 2, 1000, gy / 2} : OpndTable{};
+            const OpndTable t = v ? shim_table(gy) : OpndTable{};
             const GlweRef rows = ref(S, sy, sx), a = ref(A, sy, sx), part = ref(D, sx, 0), out = ref(C, sx, 0);
             launch_read_chain(c, rows, nullptr, a, c->d_prep, n, LOGN - ilog2_ceil((size_t)gx), gx, gy, t);
             launch_read_chain(c, rows, &rows, a, c->d_prep, n, LOGN - ilog2_ceil((size_t)gx), gx, gy, t);
@@ -263,8 +265,8 @@ void run_config(fheram_ctx* c) {
         tail_line("row_fuse (ctx, batch, bank) x n_tr", bits);
         c->rows = (size_t)gx; c->ws = 1; c->base2d[0].assign((size_t)std::max(n, 1), 1);
         bits = 0;
-        for (int lg = 0; lg <= LOGN; lg++) { c->rows_glob = (size_t)1 << lg; bits = bits * 2 + (batch_needs_third(c, gy) ? 1 : 0); }
-        tail_line("batch_needs_third x log2(rows)", bits);
+        for (int lg = 0; lg <= LOGN; lg++) { c->rows_glob = (size_t)1 << lg; bits = bits * 2 + (shim_needs_third(c, gy) ? 1 : 0); }
+        tail_line("third_arena_needed x log2(rows)", bits);
         tail_line("read_top tail (fuse_ep, gated)", shim_tail_top(c, gx * gy) ? 1 : 0);
         c->rows = c->rows_glob = 1; c->base2d[0].assign(3, 1);
     }
@@ -286,13 +288,12 @@ const Setting PATH_SETTINGS[] = {
 };
 const int PATH_LOG_MAX_ADDR[] = {12, 13, 14, 16, 18};
 
-// the buffers indexed by ciphertext: arena(i) for field i; the batch's: arena(16 + i)
+// the buffers indexed by ciphertext: arena(i) for field i; the batch's: arena(16 + i); a read list's: fake(64 + i)
 struct Field { const char* name; int32_t* fheram_ctx::*p; };
 const Field FIELDS[] = {{"data", &fheram_ctx::d_data}, {"scrA", &fheram_ctx::d_scrA}, {"scrB", &fheram_ctx::d_scrB}, {"scrC", &fheram_ctx::d_scrC},
                         {"scrD", &fheram_ctx::d_scrD}, {"tree", &fheram_ctx::d_tree}, {"res", &fheram_ctx::d_res}, {"tmp", &fheram_ctx::d_tmp},
                         {"tmp2", &fheram_ctx::d_tmp2}, {"w", &fheram_ctx::d_w}, {"part", &fheram_ctx::d_part}, {"trtop", &fheram_ctx::d_trtop}};
-const Field BATCH_FIELDS[] = {{"bA", &fheram_ctx::d_bA}, {"bB", &fheram_ctx::d_bB}, {"bC", &fheram_ctx::d_bC}, {"bres", &fheram_ctx::d_bres},
-                              {"btmp", &fheram_ctx::d_btmp}, {"btmp2", &fheram_ctx::d_btmp2}};
+const char* const READS_FIELDS[] = {"A", "B", "C", "res", "tmp", "tmp2"};   // (the shim's shim_batch_field / shim_list_field)
 
 fheram_ctx* make_path_ctx(unsigned* host_words, int lg, int ws, int s_evk, const Setting& st) {
     fheram_ctx* c = make_ctx(host_words);
@@ -313,10 +314,9 @@ fheram_ctx* make_path_ctx(unsigned* host_words, int lg, int ws, int s_evk, const
     c->d_atk_inv = fake<double*>(18); c->d_tsk = fake<double*>(19);
     c->ev_fork = fake<hipEvent_t>(20); c->ev_join = fake<hipEvent_t>(21); c->ev_inv[0] = fake<hipEvent_t>(22); c->ev_inv[1] = fake<hipEvent_t>(23);
     c->ev_wdone = fake<hipEvent_t>(24); c->ev_opstart = fake<hipEvent_t>(25);
-    c->d_bprep = fake<double*>(26);
+    shim_batch_prep(c, fake<double*>(26));
     for (int i = 0; i < 12; i++) c->*FIELDS[i].p = arena(i);
-    for (int i = 0; i < 6; i++) c->*BATCH_FIELDS[i].p = arena(16 + i);
-    c->batch_cap = 4;
+    for (int i = 0; i < 6; i++) shim_batch_field(c, i) = arena(16 + i);
     c->keys_loaded = true;
     c->cur = c->stream;
     st.apply(c);
@@ -370,11 +370,16 @@ void run_path_ctx(fheram_ctx* c) {
     op("ctx read a0"); shim_read(c, a[0], false); dump_ctx(c); synced(c);
     for (int K = 2; K <= 4; K += 2) {
         op("ctx read_batch K=" + std::to_string(K));
-        c->d_bC = batch_needs_third(c, K) ? arena(18) : nullptr;   // (as batch_reserve allocates it)
+        shim_batch_field(c, 2) = shim_needs_third(c, K) ? arena(18) : nullptr;   // (as the reserve allocates it)
         shim_batch(c, a, K);
-        launch_copy(c, ref(c->d_bres + (size_t)(K - 1) * c->ws * fheram_ctx::GLWE, (long)fheram_ctx::GLWE, 0), ref(c->d_res, (long)fheram_ctx::GLWE, 0), 1, c->ws);   // (fheram_read_batch)
         dump_ctx(c); synced(c);
     }
+    // a batch the host does not wait for, then a gated read_prepare_write: whether that one records ev_opstart (ctx.hpp wide_unsynced)
+    op("ctx read_batch K=2 (the host does not wait)");
+    shim_batch_field(c, 2) = shim_needs_third(c, 2) ? arena(18) : nullptr;
+    shim_batch(c, a, 2); dump_ctx(c);
+    op("ctx read_prepare_write a0 behind it"); shim_read(c, a[0], true); dump_ctx(c); synced(c);
+    op("ctx write a0"); shim_write(c, a[0], staging(c, FHERAM_OK)); dump_ctx(c);
     for (int k = 0; k < 4; k++) delete a[k];
 }
 void bank_step(fheram_bank* b, int first, int n, const fheram_addr* const* a, int stage_rc = FHERAM_OK) {
@@ -401,6 +406,17 @@ void run_path_bank(fheram_ctx* c, int M, int mws) {
         op("bank read_prepare_write [1, 3)"); shim_bank_read(b, 1, 2, a + 1, true); dump_bank(b); synced(c);
         op("bank write [0, 3) over both"); shim_bank_write(b, 0, 3, a, staging(c, FHERAM_OK)); dump_bank(b);
         op("bank read [2, 3)"); shim_bank_read(b, 2, 1, a + 2, false); dump_bank(b); synced(c);
+        // read lists: a permutation, and repeats over all three members
+        shim_list_prep(b, fake<double*>(70));
+        for (int i = 0; i < 6; i++) shim_list_field(b, i) = fake<int32_t*>(64 + i);
+        const int perm[] = {1, 0}, rep[] = {0, 0, 1, 2};
+        const fheram_addr* la[] = {a[0], a[1], a[2], a[0]};
+        for (int n : {2, 4}) {
+            if ((long)n * mws > 64) continue;
+            op(n == 2 ? "bank read_list [1, 0]" : "bank read_list [0, 0, 1, 2]");
+            shim_list_field(b, 2) = third_arena_needed(c, n * mws) ? fake<int32_t*>(66) : nullptr;   // (as the reserve allocates it)
+            shim_bank_list(b, n == 2 ? perm : rep, la, n); dump_bank(b); synced(c);
+        }
     }
     for (int k = 0; k < 3; k++) delete a[k];
     delete b;
@@ -411,9 +427,10 @@ int path_main(long only, unsigned* host_words) {
     if (only < 0) {
         std::string legend = "# arenas:";
         for (int i = 0; i < 12; i++) legend += std::string(" a") + std::to_string(32 + i) + "=" + FIELDS[i].name;
-        for (int i = 0; i < 6; i++) legend += std::string(" a") + std::to_string(48 + i) + "=" + BATCH_FIELDS[i].name;
+        for (int i = 0; i < 6; i++) legend += std::string(" a") + std::to_string(48 + i) + "=batch." + READS_FIELDS[i];
+        for (int i = 0; i < 6; i++) legend += std::string(" a") + std::to_string(64 + i) + "=list." + READS_FIELDS[i];
         std::puts(legend.c_str());
-        std::puts("# a13=prep a14=prep_inv a15=ggsw_tmp a16=ggsw_tmp2 a17=ggsw_inv a26=bprep a56..=address digits a60=bank prep a61=bank prep_inv; events: a20=fork a21=join a22,a23=inv a24=wdone a25=opstart");
+        std::puts("# a13=prep a14=prep_inv a15=ggsw_tmp a16=ggsw_tmp2 a17=ggsw_inv a26=batch.prep a56..=address digits a60=bank prep a61=bank prep_inv a70=list.prep; events: a20=fork a21=join a22,a23=inv a24=wdone a25=opstart");
     }
     long id = 0;
     for (int lg : PATH_LOG_MAX_ADDR) for (int ws : {1, 4}) for (int s_evk = 4; s_evk <= 5; s_evk++) for (const Setting& st : PATH_SETTINGS) {

@@ -13,7 +13,7 @@ synthetic normalised limbs from fixed seeds (as bench.py's).  Every timed list i
 Reported per list: the median of --reps repetitions of every leg (host clock around calls that end in a sync), the spread of the
 better baseline (p10..p90 of its repetitions over its median), the verdict of the acceptance rule of DESIGN.md 10 — the list beats
 the better baseline by more than that baseline's spread — and, from the launch profile of one further list, the share of the list's
-device time that the rows' chain (read_chain_launch: k_read_chain_lw) takes.
+device time that the rows' chain (read_chain_launch: k_read_chain_t) takes.
 
   python tools/read_list_bench.py --log-max-addr 18 --out profiles/read_list_2p18.json
 """
