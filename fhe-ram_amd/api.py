@@ -612,6 +612,19 @@ class GLWESecret:
             self._h = None
 
 
+def _c_config(config: Optional[dict]):
+    """fheram_config_default() with the switches of `config` set on top (fheram_config's field names); None for no config"""
+    if not config:
+        return None
+    cfg = _CConfig()
+    library().fheram_config_default(C.byref(cfg))
+    for k, v in config.items():
+        if k not in _CONFIG_FIELDS:
+            raise FheRamError(1, f"unknown execution switch {k!r}")
+        setattr(cfg, k, int(v))
+    return cfg
+
+
 class Ram:
     """ram.rs:25-29.  Owns the device-resident sub-RAMs, tree, packer scratch and prepared keys."""
 
@@ -625,13 +638,8 @@ class Ram:
         L = library()
         out = C.c_void_p()
         cp = self.params._c()
-        if config:
-            cfg = _CConfig()
-            L.fheram_config_default(C.byref(cfg))
-            for k, v in config.items():
-                if k not in _CONFIG_FIELDS:
-                    raise FheRamError(1, f"unknown execution switch {k!r}")
-                setattr(cfg, k, int(v))
+        cfg = _c_config(config)
+        if cfg is not None:
             rc = L.fheram_ctx_create_cfg(C.byref(cp), device, self.shard, self.n_shards, C.byref(cfg), C.byref(out))
         else:
             rc = L.fheram_ctx_create_sharded(C.byref(cp), device, self.shard, self.n_shards, C.byref(out))
@@ -1187,14 +1195,7 @@ class RamBank:
         L = library()
         out = C.c_void_p()
         cp = self.params._c()
-        cfg = None
-        if config:
-            cfg = _CConfig()
-            L.fheram_config_default(C.byref(cfg))
-            for k, v in config.items():
-                if k not in _CONFIG_FIELDS:
-                    raise FheRamError(1, f"unknown execution switch {k!r}")
-                setattr(cfg, k, int(v))
+        cfg = _c_config(config)
         rc = L.fheram_bank_create(C.byref(cp), device, self.n_members, C.byref(cfg) if cfg is not None else None, C.byref(out))
         if rc != 0:
             raise FheRamError(rc, L.fheram_bank_last_error(None).decode())

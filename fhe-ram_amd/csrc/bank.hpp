@@ -13,7 +13,7 @@
 //     product chains, n2 == 1).
 // Per-member state (the state flag, what read_prepare_write kept for the write, where the last result is) lives here, one RamState per
 // member; an operation runs on the merge of its range's (bank_merge) and hands the outcome back to every member of it (bank_assign).  The
-// context is never made to look like a range: after fheram_bank_create nothing here writes a field of it.  The write's inverse digits are
+// context is never made to look like a range: after fheram_bank_create nothing here writes a field of it (and create itself writes none of its switches).  The write's inverse digits are
 // never started early in a bank of more than one member (pre_inv shares d_prep_inv and d_tail_sync between members); a bank of ONE member
 // is a plain context in every respect.
 // A READ LIST (fheram_bank_read_list) is the general read: entry k reads member members[k], in any order and with repeats.  It is the same
@@ -166,17 +166,20 @@ int fheram_bank_create(const fheram_params* p, int device, int n_members, const 
         return fail(nullptr, FHERAM_ERR_INVALID_ARG, "n_members * word_size = " + std::to_string((uint64_t)n_members * p->word_size) + " exceeds 64, the ciphertext limit of the single-launch chains (k_chain_mid)");
     fheram_params wide = *p;
     wide.word_size = (uint32_t)n_members * p->word_size;
+    // more than one member: the write's inverse digits are never started early (header comment); 0 survives every rule of config_in_effect
+    fheram_config asked;
+    if (cfg) asked = *cfg; else fheram_config_default(&asked);
+    if (n_members > 1) asked.pre_inv = 0;
     fheram_ctx* c = nullptr;
-    const int rc = fheram_ctx_create_cfg(&wide, device, 0, 1, cfg, &c);   // the parameter checks, then "no HIP device"
+    const int rc = fheram_ctx_create_cfg(&wide, device, 0, 1, &asked, &c);   // the parameter checks, then "no HIP device"
     if (rc != FHERAM_OK) return rc;
     fheram_bank* b = new fheram_bank();
     b->c = c; b->M = n_members; b->mws = (int)p->word_size;
     c->ram.initialized = true;   // (per member: fheram_bank::ram)
-    if (n_members > 1) {
-        c->pre_inv = 0;
+    if (n_members > 1) {   // the operand tables: the context's resources, freed with it
         const size_t bytes = (size_t)n_members * c->n_digits * fheram_ctx::GGSW * sizeof(double);
-        hipError_t e = hipMalloc((void**)&b->d_prep, bytes);
-        if (e == hipSuccess) e = hipMalloc((void**)&b->d_prep_inv, bytes);
+        hipError_t e = c->res.device(&b->d_prep, bytes);
+        if (e == hipSuccess) e = c->res.device(&b->d_prep_inv, bytes);
         if (e != hipSuccess) {
             (void)hipGetLastError();
             fheram_bank_destroy(b);
@@ -188,13 +191,7 @@ int fheram_bank_create(const fheram_params* p, int device, int n_members, const 
 }
 void fheram_bank_destroy(fheram_bank* b) {
     if (!b) return;
-    if (b->c) {
-        hipSetDevice(b->c->device);
-        if (b->c->stream) hipStreamSynchronize(b->c->stream);
-        if (b->c->stream2) hipStreamSynchronize(b->c->stream2);
-    }
-    if (b->d_prep) hipFree(b->d_prep);
-    if (b->d_prep_inv) hipFree(b->d_prep_inv);
+    if (b->c) { hipSetDevice(b->c->device); for (hipStream_t s : {b->c->stream, b->c->stream2}) if (s) hipStreamSynchronize(s); }
     reads_free(b->list);
     fheram_ctx_destroy(b->c);
     delete b;

@@ -59,20 +59,64 @@ struct ReadBufs {
     int64_t *h_res = nullptr, *d_h_res = nullptr;   // pinned, device-visible: the results as int64 (+ the monitor's maximum), as fheram_ctx::h_res
 };
 
+// ---- the execution switches (include/fheram.h fheram_config): two pure host functions, no HIP call in them -------------------------------
+// The library defaults, without the environment (fheram_config_default adds the FHERAM_* overrides; a context's cfg starts from these).
+inline fheram_config config_builtin() {
+    fheram_config d{};
+    d.limb_split = 1; d.fine_split = 1; d.memo = 1; d.pre_inv = 1; d.tail = 1; d.tail_test = 0; d.mid = 2; d.mid_test = 0;
+    d.chain = 1; d.chain_y = 3; d.pair_z = 1; d.fuse = 1; d.graph = 0; d.safe = 0; d.nco = 0; d.tail_ep = 1; d.monitor = 1; d.reserved = 0;
+    return d;
+}
+// The switches IN EFFECT for a requested configuration: every field clamped to its values, then what `memo`, `graph` and `safe` imply for
+// the others, in this order (graph zeroes pre_inv before safe looks at it).  reserved comes out 0: fheram_ctx_create_cfg has refused anything else.
+inline fheram_config config_in_effect(const fheram_config& in) {
+    using C = fheram_config;
+    fheram_config e{};
+    for (int32_t C::*on_off : {&C::limb_split, &C::fine_split, &C::memo, &C::tail, &C::tail_ep, &C::mid_test, &C::chain, &C::pair_z, &C::fuse, &C::graph, &C::safe})
+        e.*on_off = in.*on_off ? 1 : 0;
+    for (int32_t C::*upto2 : {&C::tail_test, &C::mid, &C::monitor}) e.*upto2 = in.*upto2 < 0 ? 0 : (in.*upto2 > 2 ? 2 : in.*upto2);   // mid = 1: the <= 16 ciphertext split only
+    e.chain_y = in.chain_y ? 3 : 0;
+    e.nco = in.nco == 2 ? 2 : (in.nco == 1 ? 1 : 0);
+    e.pre_inv = e.memo ? (in.pre_inv == 2 ? 2 : (in.pre_inv ? 1 : 0)) : 0;
+    // a captured launch sequence must be a pure function of (context, address, op): under replay the write always
+    // computes its own inverse digits (whether a precompute matched is state the capture would freeze)
+    if (e.graph) e.pre_inv = 0;
+    // safe: ONE switch for a configuration that stays inside the HIP memory model — no launch with in-kernel hand-offs
+    // between workgroups (k_trace_tail, k_chain_mid: relaxed agent-scope atomics + drained stores + L1-bypassing loads on one
+    // XCD's L2) and no gate wave (k_tail_gate): dependent steps are kernel boundaries, the side work forks from an event.
+    // Same results (tests/test_gpu_golden.py); priced in profiles/r05_bench_safe.json.
+    if (e.safe) { e.tail = 0; e.tail_test = 0; e.mid = 0; e.mid_test = 0; if (e.pre_inv == 1) e.pre_inv = 2; }
+    // round-off monitor: one coefficient per thread and transform by default, every coefficient under `safe`
+    if (e.safe && e.monitor == 1) e.monitor = 2;
+    return e;
+}
+
+// Every device allocation, pinned host allocation and event a context makes (its bank's operand tables included), recorded as it is made:
+// release() gives all of them back, so nothing that allocates has a second line to remember.  Each helper returns the HIP call's status and records
+// only what succeeded (a failed call's pointer stays null).  No destructor: fheram_ctx_destroy calls release() on the context's device, streams drained.
+struct CtxResources {
+    std::vector<void*> dev, pinned;
+    std::vector<hipEvent_t> events;
+    template <typename T> hipError_t device(T** p, size_t bytes) { const hipError_t e = hipMalloc((void**)p, bytes); if (e == hipSuccess) dev.push_back(*p); return e; }
+    template <typename T> hipError_t host(T** p, size_t bytes, unsigned flags) { const hipError_t e = hipHostMalloc((void**)p, bytes, flags); if (e == hipSuccess) pinned.push_back(*p); return e; }
+    hipError_t event(hipEvent_t* ev, bool timing = false) {   // ordering events carry no time stamps
+        const hipError_t e = timing ? hipEventCreate(ev) : hipEventCreateWithFlags(ev, hipEventDisableTiming);
+        if (e == hipSuccess) events.push_back(*ev);
+        return e;
+    }
+    void release() {
+        for (hipEvent_t e : events) hipEventDestroy(e);
+        for (void* p : dev) hipFree(p);
+        for (void* p : pinned) hipHostFree(p);
+        events.clear(); dev.clear(); pinned.clear();
+    }
+};
+
 struct fheram_ctx {
+    // ---- parameters, and what is derived from them (never changed after creation) ----
     fheram_params p;
     int device = 0;
-    hipStream_t stream = nullptr;    // main stream: every op is ordered on it
-    hipStream_t stream2 = nullptr;   // side stream for work that is independent inside one op (write path)
-    hipStream_t cur = nullptr;       // stream the launchers currently enqueue on
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_xout = nullptr, ev_xin = nullptr;   // ordering against a caller's stream (fheram_stream_signal / _wait)
-    // the write in flight:
-    bool side_begun = false;                          // write_side_begin has been enqueued for it
-    bool trhi_in_C = false;                           // trace(ct_hi) of the local rows is in arena C (else A)
-    bool tree_rotate_pending = false;                 // write_top left the tree's rotated copy of ct_lo to write_rows
-    // derived from the parameters (never changed after creation)
-    int ws = 0, n2 = 0, n_digits = 0;
+    int ws = 0, n2 = 0, n_digits = 0, max_digits = 0;
     size_t rows = 0;        // GLWE rows per sub-RAM held by THIS context (all of them unless sharded)
     size_t rows_glob = 0;   // rows per sub-RAM of the whole RAM
     int shard = 0, n_shards = 1;   // row sharding: this context owns rows r = shard (mod n_shards)
@@ -85,7 +129,19 @@ struct fheram_ctx {
     static constexpr size_t GGSW = (size_t)DNUM_CT * 2 * GLWE4;            // elements of a GGSW
     static constexpr size_t EVK5 = (size_t)DNUM_GGSW * S_INV * 2 * N;      // inverse / tensor key
     static constexpr size_t GGSW5 = (size_t)DNUM_GGSW * 2 * S_INV * 2 * N; // one bit of an FheUint (N4)
-    // device: keys and tables, then the buffers indexed by ciphertext (the sequences of path.hpp reach the latter through a RamView only)
+    int cus = 256;
+    CtxResources res;       // every buffer and event below but the streams and `batch`: allocated through it, freed by its release()
+    // ---- streams and ordering events ----
+    hipStream_t stream = nullptr;    // main stream: every op is ordered on it
+    hipStream_t stream2 = nullptr;   // side stream for work that is independent inside one op (write path)
+    hipStream_t cur = nullptr;       // stream the launchers currently enqueue on
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    hipEvent_t ev_xout = nullptr, ev_xin = nullptr;   // ordering against a caller's stream (fheram_stream_signal / _wait)
+    // ---- the execution switches IN EFFECT (config_in_effect of what the caller asked for; include/fheram.h describes each).  After
+    //      creation only the two watches below write one: cfg.tail (off for good) and cfg.mid (off, re-armed after 256 ops) ----
+    fheram_config cfg = config_builtin();
+    bool wide = false;             // the launch being enqueued can never meet the gate wave (Ram::read, Ram::write: only read_prepare_write parks one): the chain kernels' 256-register variants
+    // ---- keys and tables ----
     double* d_tw = nullptr;
     double ninv = 0.0;
     double* d_atk = nullptr;       // [log_n] prepared trace keys
@@ -93,6 +149,10 @@ struct fheram_ctx {
     double* d_tsk = nullptr;
     int64_t gal[LOGN];
     bool keys_loaded = false;
+    //  Round-off monitor (fft_dev.hpp mon_note / RoMonitor; cfg.monitor): every rounding of an inverse transform reports |x - rint(x)|; the
+    //  context's maximum lives behind its twiddle table (d_tw[N]), and a pinned host word is set once it passed MON_LIMIT.
+    unsigned* h_ro_flag = nullptr; // pinned, device-visible: 1 = a round-off above MON_LIMIT was seen (sticky until fheram_roundoff_reset)
+    // ---- the RAM: the buffers indexed by ciphertext (the sequences of path.hpp reach them through a RamView only) ----
     int32_t* d_data = nullptr;     // [ws][rows] GLWE
     int32_t* d_tree = nullptr;     // [ws] GLWE (tree[0][0])
     int32_t* d_scrA = nullptr;     // [ws][rows]  ping-pong arenas: every fused kernel is out of place
@@ -103,32 +163,20 @@ struct fheram_ctx {
     int32_t* d_tmp = nullptr;      // [ws]
     int32_t* d_tmp2 = nullptr;     // [ws]
     int32_t* d_w = nullptr;        // [ws]
-    double* d_big = nullptr;       // [LIMB_SPLIT_MAX ciphertexts] un-normalised limbs of the limb-parallel path
-    double* d_big2 = nullptr;      // same, for launches on the side stream
-    int limb_split = 1;            // FHERAM_LIMB_SPLIT=0 disables the limb-parallel paths
-    int chain = 1;                 // FHERAM_CHAIN=0: one launch per step instead of one launch per dependent chain of fused steps
-    int chain_y = 3;               // 3: the intermediates of a trace chain as Y = ceil(A/2) with the closed-form normalisation, handed over through LDS and registers (ks_trace_l); 0 (FHERAM_CHAIN_Y=0): as int32 limbs through global memory (ks_run)
-    int fine_split = 1;            // FHERAM_FINE_SPLIT=0 disables the fine limb split (one workgroup per input and output limb)
-    int use_graph = 0;             // FHERAM_GRAPH=1: replay each op's launch sequence from a hipGraph (per address)
+    int32_t* d_trtop = nullptr;    // [ws]
     int32_t* d_part = nullptr;     // [ws]            this shard's partial pack / the un-rotated ct_lo
     int32_t* d_gat[3] = {nullptr, nullptr, nullptr};   // [n_shards][ws] gathered partials + ping-pong (root)
-    int nco = 0;                   // output columns per workgroup: 1 = split by column (2 workgroups per
-                                   // ciphertext), 2 = one workgroup, 0 = choose per launch from the batch size
-    int cus = 256;
+    RamState ram;                  // this context's RAM (a bank's context: unused, the members' are in fheram_bank)
+    ReadBufs batch;                // fheram_read_batch: its arenas, results and digit table (path.hpp reads_reserve / reads_view), sized by this context's word count
+    // ---- launcher scratch ----
+    double* d_big = nullptr;       // [LIMB_SPLIT_MAX ciphertexts] un-normalised limbs of the limb-parallel path
+    double* d_big2 = nullptr;      // same, for launches on the side stream
     double* d_prep = nullptr;      // [n_digits] prepared GGSW: coordinate ci at its first digit (write: inverse digits at 0)
     bool prep1_ready = false;      // coordinate 1 was prepared together with coordinate 0 (unsharded reads)
     int32_t* d_ggsw_tmp = nullptr; // [max digits per coordinate] std GGSW (inversion result)
     int32_t* d_ggsw_tmp2 = nullptr;
-    int max_digits = 0;
-    RamState ram;                  // this context's RAM (a bank's context: unused, the members' are in fheram_bank)
-    bool words_staged = false;
-    int memo = 1;                  // FHERAM_MEMO=0: a write recomputes what read_prepare_write could have kept (RamState::memo_top / memo_alone)
-    //  tail: the dependent trace chain at the end of a read as ONE launch with in-kernel hand-offs (k_trace_tail);
-    //        FHERAM_TAIL=0: one launch pair per step as before;  FHERAM_TAIL=2 / 3: test hooks, the launch gives up two steps before its end
-    //        and the fused fallback launch behind it does the work.
-    int tail = 1;
-    int tail_ep = 1;                   // coordinate 1's products (two digits or more) run inside that launch, in front of the trace steps (FHERAM_TAIL_EP=0: launches of their own)
-    int tail_test = 0;                 // FHERAM_TAIL=2 / 3: every launch gives up late; 3 keeps the watch below active
+    // ---- tail (cfg.tail): the dependent trace chain at the end of a read as ONE launch with in-kernel hand-offs (k_trace_tail);
+    //      cfg.tail_test: every launch gives up two steps before its end and the fused fallback launch behind it does the work ----
     unsigned tail_seq = 0;
     int tail_xoff = 0;                 // first XCD of this context's groups (0 or 4, alternating over contexts and processes)
     uint64_t tail_launches = 0;
@@ -139,10 +187,8 @@ struct fheram_ctx {
     unsigned tail_fb_mark = 0;
     uint64_t tail_launch_mark = 0;
     unsigned* d_tail_sync = nullptr;   // [8 groups][32] + abort generation, fallbacks taken
-    //  mid: dependent chains on 9..64 ciphertexts as ONE launch with in-kernel hand-offs (k_chain_mid); FHERAM_MID=0: launch
-    //       pairs per step as before; FHERAM_MID=2: test hook, every launch gives up late.  One sync block per stream.
-    int mid = 2;
-    int mid_test = 0;
+    // ---- mid (cfg.mid): dependent chains on 9..64 ciphertexts as ONE launch with in-kernel hand-offs (k_chain_mid); cfg.mid_test: every
+    //      launch gives up late.  One sync block per stream ----
     unsigned mid_seq = 0;
     uint64_t mid_launches = 0, mid_launch_mark = 0;
     unsigned mid_fb_mark = 0;
@@ -153,27 +199,20 @@ struct fheram_ctx {
     unsigned* d_mid_sync[2] = {nullptr, nullptr};   // [64 groups][32] + [_, ciphertexts redone]: main / side stream
     double* d_mid_big[2] = {nullptr, nullptr};      // [step parity][ciphertext x RS <= 64] x BIG_STRIDE doubles: k_chain_mid's partial limb polynomials
     double* d_mid_y[2] = {nullptr, nullptr};        // [2][64 groups][2][N] doubles: the chain's intermediates in the one-double form
+    // ---- the inverse-digit precompute (cfg.pre_inv) ----
     //  inv_id[ci]: d_prep_inv holds the prepared INVERSE digits of coordinate ci of the address with that id
     //              (CoordinatePrepared::prepare_inv, ram.rs:260-271,278-289): read_prepare_write — which is told the
     //              address the write will use — starts them on the (low-priority) side stream next to its trace chain,
     //              which is one launch holding 24 CUs on half of the XCDs: the rest of the chip is idle then.  A write
     //              with another address, or after new keys, computes them itself.  FHERAM_PRE_INV=0: always.
-    int pair_z = 1;                // FHERAM_PAIR_Z=0: the column-split packer combine with the limb-by-limb normalisation (k_keyswitch<KS_PAIR,...,1>) instead of k_pair_z
-    int fuse = 1;                  // FHERAM_FUSE=0: a row's product chain and trace chain as two launches (and the write's elementwise step as a third) instead of k_read_chain / k_write_chain
-    bool wide = false;             // the launch being enqueued can never meet the gate wave (Ram::read, Ram::write: only read_prepare_write parks one): the chain kernels' 256-register variants
-    int safe = 0;                  // FHERAM_SAFE=1: no in-kernel hand-offs between workgroups, no gate wave (fheram.hip)
-    //  Round-off monitor (fft_dev.hpp mon_note / RoMonitor): every rounding of an inverse transform reports |x - rint(x)|; the
-    //  context's maximum lives behind its twiddle table (d_tw[N]), and a pinned host word is set once it passed MON_LIMIT.
-    int monitor = 1;               // 0: nothing is reported or checked; 1 (default): one coefficient per thread and transform; 2 (`safe`): every coefficient
-    unsigned* h_ro_flag = nullptr; // pinned, device-visible: 1 = a round-off above MON_LIMIT was seen (sticky until fheram_roundoff_reset)
-    int pre_inv = 1;
     uint64_t inv_id[2] = {0, 0};
     double* d_prep_inv = nullptr;  // [n_digits] prepared GGSW
     int32_t* d_ggsw_inv = nullptr; // [n_digits] std GGSW: the inversion result on its way there (own scratch: runs beside anything)
     hipEvent_t ev_inv[2] = {nullptr, nullptr};
     bool inv_pending[2] = {false, false};   // a precompute of coordinate ci has been enqueued on the side stream and no write has consumed / overwritten it
     hipEvent_t ev_wdone = nullptr;          // recorded at the end of every write (main stream): the next precompute waits for it
-    // recorded on the main stream where a read_prepare_write STARTS (free there: nothing of the op has been enqueued yet); its gate wave waits for
+    bool wdone_pending = false;
+    // ---- ev_opstart: recorded on the main stream where a read_prepare_write STARTS (free there: nothing of the op has been enqueued yet); its gate wave waits for
     // it on the side stream.  A host that enqueues ops without waiting for them is ahead of the device: without this the gate wave could be
     // parked while the PREVIOUS op's 256-register chain launch is still being placed, and cost that launch a second round on one CU.
     // Only needed while a 256-register launch of an earlier op may still be waiting for its CUs: wide_unsynced = such a launch has been enqueued
@@ -186,10 +225,8 @@ struct fheram_ctx {
     // read behind the launch: derive_unsynced = such a launch has been enqueued and the host has not waited for the stream since; the next
     // gated read_prepare_write then records ev_opstart behind it, whatever wide_unsynced says.
     bool derive_unsynced = false;
-    bool wdone_pending = false;
-    int32_t* d_trtop = nullptr;    // [ws]
-    ReadBufs batch;                // fheram_read_batch: its arenas, results and digit table (path.hpp reads_reserve / reads_view), sized by this context's word count
-    int32_t* h_pin[2] = {nullptr, nullptr};   // pinned host staging (hand-over of int64 host buffers)
+    // ---- staging ----
+    int32_t* h_pin[2] = {nullptr, nullptr};   // pinned host staging (hand-over of int64 host buffers), made on first use (pin_init)
     hipEvent_t ev_pin[2] = {nullptr, nullptr};
     // the two hand-overs ON the path (result of a read out, words of a write in) have staging of their own:
     //  h_res: pinned, device-visible; an export kernel widens the result into it as int64 in the ABI's layout (no DMA
@@ -200,10 +237,15 @@ struct fheram_ctx {
     int32_t* h_w = nullptr;
     hipEvent_t ev_w = nullptr;
     bool w_busy = false;
-    // profiling
+    // ---- the write in flight ----
+    bool side_begun = false;                          // write_side_begin has been enqueued for it
+    bool trhi_in_C = false;                           // trace(ct_hi) of the local rows is in arena C (else A)
+    bool tree_rotate_pending = false;                 // write_top left the tree's rotated copy of ct_lo to write_rows
+    bool words_staged = false;
+    // ---- profiling, and the error string ----
     int profile = 0;               // 1: every launch class bracketed by HIP events; 2: only the chain launches themselves (two events per launch: leaves back-to-back submission intact)
     std::map<std::string, ProfCls> prof;
-    std::vector<hipEvent_t> ev_pool;
+    std::vector<hipEvent_t> ev_pool;   // events of collected launches, for reuse (get_event makes them through `res`)
     hipEvent_t t0 = nullptr, t1 = nullptr;
     std::string err;
 };
@@ -256,7 +298,7 @@ GlweRef ref(int32_t* p, long sy, long sx) { return GlweRef{p, sy, sx}; }
 
 hipEvent_t get_event(fheram_ctx* c) {
     if (!c->ev_pool.empty()) { hipEvent_t e = c->ev_pool.back(); c->ev_pool.pop_back(); return e; }
-    hipEvent_t e; hipEventCreate(&e); return e;
+    hipEvent_t e = nullptr; c->res.event(&e, true); return e;
 }
 struct ProfScope {
     fheram_ctx* c; ProfCls* cls = nullptr; hipEvent_t a = nullptr;
@@ -323,8 +365,8 @@ constexpr size_t PIN_CHUNK = (size_t)1 << 21;   // int32 elements per staging bu
 int pin_init(fheram_ctx* c) {
     if (c->h_pin[0]) return FHERAM_OK;
     for (int b = 0; b < 2; b++) {
-        HIPCHK(c, hipHostMalloc((void**)&c->h_pin[b], PIN_CHUNK * sizeof(int32_t), hipHostMallocDefault));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_pin[b], hipEventDisableTiming));
+        HIPCHK(c, c->res.host(&c->h_pin[b], PIN_CHUNK * sizeof(int32_t), hipHostMallocDefault));
+        HIPCHK(c, c->res.event(&c->ev_pin[b]));
     }
     return FHERAM_OK;
 }

@@ -24,9 +24,7 @@ const char* fheram_last_error(const fheram_ctx* c) { return c ? c->err.c_str() :
 // Library defaults, then FHERAM_* environment overrides (how the tests force every decomposition and hand-over form).
 void fheram_config_default(fheram_config* cfg) {
     if (!cfg) return;
-    fheram_config d{};
-    d.limb_split = 1; d.fine_split = 1; d.memo = 1; d.pre_inv = 1; d.tail = 1; d.tail_test = 0; d.mid = 2; d.mid_test = 0;
-    d.chain = 1; d.chain_y = 3; d.pair_z = 1; d.fuse = 1; d.graph = 0; d.safe = 0; d.nco = 0; d.tail_ep = 1; d.monitor = 1; d.reserved = 0;
+    fheram_config d = config_builtin();
     auto env = [](const char* n) { const char* v = getenv(n); return (v && v[0]) ? v[0] : '\0'; };
     if (env("FHERAM_LIMB_SPLIT") == '0') d.limb_split = 0;
     if (env("FHERAM_FINE_SPLIT") == '0') d.fine_split = 0;
@@ -133,47 +131,15 @@ int fheram_ctx_create_cfg(const fheram_params* p, int device, int shard, int n_s
         CCHK(hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, lo));
     }
     c->cur = c->stream;
-    CCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    CCHK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-    CCHK(hipEventCreateWithFlags(&c->ev_xout, hipEventDisableTiming));
-    CCHK(hipEventCreateWithFlags(&c->ev_xin, hipEventDisableTiming));
-    CCHK(hipEventCreate(&c->t0));
-    CCHK(hipEventCreate(&c->t1));
-    {
-        fheram_config cfg;
-        if (user_cfg) cfg = *user_cfg; else fheram_config_default(&cfg);
-        c->limb_split = cfg.limb_split ? 1 : 0;
-        c->fine_split = cfg.fine_split ? 1 : 0;
-        c->memo = cfg.memo ? 1 : 0;
-        c->pre_inv = c->memo ? (cfg.pre_inv == 2 ? 2 : (cfg.pre_inv ? 1 : 0)) : 0;
-        c->tail = cfg.tail ? 1 : 0;
-        static std::atomic<int> serial{0};
-        c->tail_xoff = ((serial++ + (int)getpid()) & 1) * (TAIL_GROUPS / 2);
-        c->tail_test = cfg.tail_test < 0 ? 0 : (cfg.tail_test > 2 ? 2 : cfg.tail_test);
-        c->tail_ep = cfg.tail_ep ? 1 : 0;
-        c->mid = cfg.mid < 0 ? 0 : (cfg.mid > 2 ? 2 : cfg.mid);   // 1: the <= 16 ciphertext split only
-        c->mid_test = cfg.mid_test ? 1 : 0;
-        c->chain = cfg.chain ? 1 : 0;
-        c->chain_y = cfg.chain_y ? 3 : 0;
-        c->pair_z = cfg.pair_z ? 1 : 0;
-        c->fuse = cfg.fuse ? 1 : 0;
-        c->use_graph = cfg.graph ? 1 : 0;
-        // a captured launch sequence must be a pure function of (context, address, op): under replay the write always
-        // computes its own inverse digits (whether a precompute matched is state the capture would freeze)
-        if (c->use_graph) c->pre_inv = 0;
-        // safe: ONE switch for a configuration that stays inside the HIP memory model — no launch with in-kernel hand-offs
-        // between workgroups (k_trace_tail, k_chain_mid: relaxed agent-scope atomics + drained stores + L1-bypassing loads on one
-        // XCD's L2) and no gate wave (k_tail_gate): dependent steps are kernel boundaries, the side work forks from an event.
-        // Same results (tests/test_gpu_golden.py); priced in profiles/r05_bench_safe.json.
-        c->safe = cfg.safe ? 1 : 0;
-        if (c->safe) { c->tail = 0; c->tail_test = 0; c->mid = 0; c->mid_test = 0; if (c->pre_inv == 1) c->pre_inv = 2; }
-        // round-off monitor: one coefficient per thread and transform by default, every coefficient under `safe`
-        c->monitor = cfg.monitor < 0 ? 0 : (cfg.monitor > 2 ? 2 : cfg.monitor);
-        if (c->safe && c->monitor == 1) c->monitor = 2;
-        c->nco = cfg.nco == 2 ? 2 : (cfg.nco == 1 ? 1 : 0);
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->cus = prop.multiProcessorCount;
-    }
+    for (hipEvent_t* ev : {&c->ev_fork, &c->ev_join, &c->ev_xout, &c->ev_xin}) CCHK(c->res.event(ev));
+    for (hipEvent_t* ev : {&c->t0, &c->t1}) CCHK(c->res.event(ev, true));
+    fheram_config asked;
+    if (user_cfg) asked = *user_cfg; else fheram_config_default(&asked);
+    c->cfg = config_in_effect(asked);
+    static std::atomic<int> serial{0};
+    c->tail_xoff = ((serial++ + (int)getpid()) & 1) * (TAIL_GROUPS / 2);
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) c->cus = prop.multiProcessorCount;
 #define LDSATTR(k) CCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES))
     LDSATTR(k_prepare);
     LDSATTR((&k_ext_product<3, 4, 1>));
@@ -226,58 +192,45 @@ int fheram_ctx_create_cfg(const fheram_params* p, int device, int shard, int n_s
     c->ninv = 1.0 / (double)NC;   // the inverse transform's 1/n, folded into every prepared operand (a power of two: exact)
     {   // the round-off monitor's words ride with the table (fft_dev.hpp TW_GLOBAL): mode in the first dword of slot 0, the maximum
         // at [N], the address of the pinned flag word at [N + 1]
-        CCHK(hipHostMalloc((void**)&c->h_ro_flag, 64, hipHostMallocDefault));
+        CCHK(c->res.host(&c->h_ro_flag, 64, hipHostMallocDefault));
         *c->h_ro_flag = 0;
-        const uint64_t mode = (uint64_t)c->monitor, flag_addr = (uint64_t)(size_t)c->h_ro_flag;
+        const uint64_t mode = (uint64_t)c->cfg.monitor, flag_addr = (uint64_t)(size_t)c->h_ro_flag;
         std::memcpy(&tw[0], &mode, 8);
         std::memcpy(&tw[N + 1], &flag_addr, 8);
     }
-    CCHK(hipMalloc(&c->d_tw, TW_GLOBAL * sizeof(double)));
+    CCHK(c->res.device(&c->d_tw, TW_GLOBAL * sizeof(double)));
     CCHK(hipMemcpy(c->d_tw, tw.data(), TW_GLOBAL * sizeof(double), hipMemcpyHostToDevice));
     const size_t G = fheram_ctx::GLWE, nrow = (size_t)c->ws * c->rows;
-    CCHK(hipMalloc(&c->d_atk, (size_t)LOGN * c->atk * sizeof(double)));
-    CCHK(hipMalloc(&c->d_atk_inv, fheram_ctx::EVK5 * sizeof(double)));
-    CCHK(hipMalloc(&c->d_tsk, fheram_ctx::EVK5 * sizeof(double)));
-    CCHK(hipMalloc(&c->d_data, nrow * G * sizeof(int32_t)));
-    CCHK(hipMalloc(&c->d_scrA, nrow * G * sizeof(int32_t)));
-    CCHK(hipMalloc(&c->d_scrB, nrow * G * sizeof(int32_t)));
-    CCHK(hipMalloc(&c->d_scrC, nrow * G * sizeof(int32_t)));
-    CCHK(hipMalloc(&c->d_scrD, nrow * G * sizeof(int32_t)));
-    CCHK(hipMalloc(&c->d_ggsw_tmp2, (size_t)c->max_digits * fheram_ctx::GGSW * sizeof(int32_t)));
-    CCHK(hipMalloc(&c->d_tmp2, (size_t)c->ws * G * sizeof(int32_t)));
-    CCHK(hipMalloc(&c->d_part, (size_t)c->ws * G * sizeof(int32_t)));
-    CCHK(hipMalloc(&c->d_big, (size_t)LIMB_SPLIT_MAX * BIG_STRIDE * sizeof(double)));
-    CCHK(hipMalloc(&c->d_big2, (size_t)LIMB_SPLIT_MAX * BIG_STRIDE * sizeof(double)));
-    if (n_shards > 1) for (int i = 0; i < 3; i++) CCHK(hipMalloc(&c->d_gat[i], (size_t)n_shards * c->ws * G * sizeof(int32_t)));
-    CCHK(hipMalloc(&c->d_tree, (size_t)c->ws * G * sizeof(int32_t)));
-    CCHK(hipMalloc(&c->d_res, (size_t)c->ws * G * sizeof(int32_t)));
-    CCHK(hipMalloc(&c->d_tmp, (size_t)c->ws * G * sizeof(int32_t)));
-    CCHK(hipMalloc(&c->d_w, (size_t)c->ws * G * sizeof(int32_t)));
-    CCHK(hipMalloc(&c->d_trtop, (size_t)c->ws * G * sizeof(int32_t)));
-    CCHK(hipMalloc(&c->d_prep, (size_t)std::max(c->n_digits, c->max_digits) * fheram_ctx::GGSW * sizeof(double)));
-    CCHK(hipMalloc(&c->d_ggsw_tmp, (size_t)c->max_digits * fheram_ctx::GGSW * sizeof(int32_t)));
+    CCHK(c->res.device(&c->d_atk, (size_t)LOGN * c->atk * sizeof(double)));
+    for (double** key : {&c->d_atk_inv, &c->d_tsk}) CCHK(c->res.device(key, fheram_ctx::EVK5 * sizeof(double)));
+    for (int32_t** arena : {&c->d_data, &c->d_scrA, &c->d_scrB, &c->d_scrC, &c->d_scrD}) CCHK(c->res.device(arena, nrow * G * sizeof(int32_t)));
+    CCHK(c->res.device(&c->d_ggsw_tmp2, (size_t)c->max_digits * fheram_ctx::GGSW * sizeof(int32_t)));
+    for (int32_t** ct : {&c->d_tmp2, &c->d_part}) CCHK(c->res.device(ct, (size_t)c->ws * G * sizeof(int32_t)));
+    for (double** big : {&c->d_big, &c->d_big2}) CCHK(c->res.device(big, (size_t)LIMB_SPLIT_MAX * BIG_STRIDE * sizeof(double)));
+    if (n_shards > 1) for (int i = 0; i < 3; i++) CCHK(c->res.device(&c->d_gat[i], (size_t)n_shards * c->ws * G * sizeof(int32_t)));
+    for (int32_t** ct : {&c->d_tree, &c->d_res, &c->d_tmp, &c->d_w, &c->d_trtop}) CCHK(c->res.device(ct, (size_t)c->ws * G * sizeof(int32_t)));
+    CCHK(c->res.device(&c->d_prep, (size_t)std::max(c->n_digits, c->max_digits) * fheram_ctx::GGSW * sizeof(double)));
+    CCHK(c->res.device(&c->d_ggsw_tmp, (size_t)c->max_digits * fheram_ctx::GGSW * sizeof(int32_t)));
     CCHK(hipMemset(c->d_tree, 0, (size_t)c->ws * G * sizeof(int32_t)));
-    CCHK(hipMalloc(&c->d_prep_inv, (size_t)c->n_digits * fheram_ctx::GGSW * sizeof(double)));
-    CCHK(hipMalloc(&c->d_ggsw_inv, (size_t)c->n_digits * fheram_ctx::GGSW * sizeof(int32_t)));
-    for (int i = 0; i < 2; i++) CCHK(hipEventCreateWithFlags(&c->ev_inv[i], hipEventDisableTiming));
-    CCHK(hipEventCreateWithFlags(&c->ev_wdone, hipEventDisableTiming));
-    CCHK(hipEventCreateWithFlags(&c->ev_opstart, hipEventDisableTiming));
-    CCHK(hipMalloc(&c->d_tail_sync, (size_t)(TAIL_GROUPS + 1) * 32 * sizeof(unsigned)));
+    CCHK(c->res.device(&c->d_prep_inv, (size_t)c->n_digits * fheram_ctx::GGSW * sizeof(double)));
+    CCHK(c->res.device(&c->d_ggsw_inv, (size_t)c->n_digits * fheram_ctx::GGSW * sizeof(int32_t)));
+    for (hipEvent_t* ev : {&c->ev_inv[0], &c->ev_inv[1], &c->ev_wdone, &c->ev_opstart}) CCHK(c->res.event(ev));
+    CCHK(c->res.device(&c->d_tail_sync, (size_t)(TAIL_GROUPS + 1) * 32 * sizeof(unsigned)));
     CCHK(hipMemset(c->d_tail_sync, 0, (size_t)(TAIL_GROUPS + 1) * 32 * sizeof(unsigned)));
     for (int i = 0; i < 2; i++) {
-        CCHK(hipMalloc(&c->d_mid_sync[i], (size_t)(MID_GROUPS_MAX + 1) * 32 * sizeof(unsigned)));
+        CCHK(c->res.device(&c->d_mid_sync[i], (size_t)(MID_GROUPS_MAX + 1) * 32 * sizeof(unsigned)));
         CCHK(hipMemset(c->d_mid_sync[i], 0, (size_t)(MID_GROUPS_MAX + 1) * 32 * sizeof(unsigned)));
-        CCHK(hipMalloc(&c->d_mid_y[i], (size_t)2 * MID_GROUPS_MAX * 2 * N * sizeof(double)));
-        CCHK(hipMalloc(&c->d_mid_big[i], (size_t)2 * MID_GROUPS_MAX * BIG_STRIDE * sizeof(double)));
+        CCHK(c->res.device(&c->d_mid_y[i], (size_t)2 * MID_GROUPS_MAX * 2 * N * sizeof(double)));
+        CCHK(c->res.device(&c->d_mid_big[i], (size_t)2 * MID_GROUPS_MAX * BIG_STRIDE * sizeof(double)));
     }
-    CCHK(hipHostMalloc((void**)&c->h_tail_fb, 64, hipHostMallocDefault));
+    CCHK(c->res.host(&c->h_tail_fb, 64, hipHostMallocDefault));
     *c->h_tail_fb = 0;
-    CCHK(hipHostMalloc((void**)&c->h_mid_fb, 128, hipHostMallocDefault));
+    CCHK(c->res.host(&c->h_mid_fb, 128, hipHostMallocDefault));
     memset(c->h_mid_fb, 0, 128);
-    CCHK(hipHostMalloc((void**)&c->h_res, ((size_t)c->ws * G + 1) * sizeof(int64_t), hipHostMallocMapped));   // + the monitor's maximum at export time
+    CCHK(c->res.host(&c->h_res, ((size_t)c->ws * G + 1) * sizeof(int64_t), hipHostMallocMapped));   // + the monitor's maximum at export time
     CCHK(hipHostGetDevicePointer((void**)&c->d_h_res, c->h_res, 0));
-    CCHK(hipHostMalloc((void**)&c->h_w, (size_t)c->ws * G * sizeof(int32_t), hipHostMallocDefault));
-    CCHK(hipEventCreateWithFlags(&c->ev_w, hipEventDisableTiming));
+    CCHK(c->res.host(&c->h_w, (size_t)c->ws * G * sizeof(int32_t), hipHostMallocDefault));
+    CCHK(c->res.event(&c->ev_w));
 #undef CCHK
     *out = c;
     return FHERAM_OK;
@@ -286,41 +239,18 @@ int fheram_ctx_create_cfg(const fheram_params* p, int device, int shard, int n_s
 void fheram_ctx_destroy(fheram_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
-    if (c->stream) hipStreamSynchronize(c->stream);
-    if (c->stream2) hipStreamSynchronize(c->stream2);
+    for (hipStream_t s : {c->stream, c->stream2}) if (s) hipStreamSynchronize(s);
     prof_collect(c);
     reads_free(c->batch);
-    if (c->ev_fork) hipEventDestroy(c->ev_fork);
-    if (c->ev_join) hipEventDestroy(c->ev_join);
-    for (int i = 0; i < 2; i++) if (c->ev_inv[i]) hipEventDestroy(c->ev_inv[i]);
-    if (c->ev_wdone) hipEventDestroy(c->ev_wdone);
-    if (c->ev_opstart) hipEventDestroy(c->ev_opstart);
-    if (c->ev_xout) hipEventDestroy(c->ev_xout);
-    if (c->ev_xin) hipEventDestroy(c->ev_xin);
-    if (c->stream2) hipStreamDestroy(c->stream2);
-    for (auto e : c->ev_pool) hipEventDestroy(e);
-    if (c->t0) hipEventDestroy(c->t0);
-    if (c->t1) hipEventDestroy(c->t1);
-    for (int b = 0; b < 2; b++) { if (c->ev_pin[b]) hipEventDestroy(c->ev_pin[b]); if (c->h_pin[b]) hipHostFree(c->h_pin[b]); }
-    void* bufs[] = {c->d_tw, c->d_atk, c->d_atk_inv, c->d_tsk, c->d_data, c->d_scrA, c->d_scrB, c->d_big, c->d_big2, c->d_scrC, c->d_scrD, c->d_ggsw_tmp2, c->d_tmp2, c->d_part, c->d_gat[0], c->d_gat[1], c->d_gat[2], c->d_tree, c->d_res, c->d_tmp, c->d_w, c->d_trtop, c->d_prep, c->d_ggsw_tmp, c->d_tail_sync, c->d_prep_inv, c->d_ggsw_inv, c->d_mid_sync[0], c->d_mid_sync[1], c->d_mid_y[0], c->d_mid_y[1], c->d_mid_big[0], c->d_mid_big[1]};
-    for (void* b : bufs) if (b) hipFree(b);
-    if (c->h_tail_fb) hipHostFree(c->h_tail_fb);
-    if (c->h_mid_fb) hipHostFree(c->h_mid_fb);
-    if (c->h_res) hipHostFree(c->h_res);
-    if (c->h_ro_flag) hipHostFree(c->h_ro_flag);
-    if (c->h_w) hipHostFree(c->h_w);
-    if (c->ev_w) hipEventDestroy(c->ev_w);
-    if (c->stream) hipStreamDestroy(c->stream);
+    c->res.release();
+    for (hipStream_t s : {c->stream2, c->stream}) if (s) hipStreamDestroy(s);   // (null in a context whose creation failed before it had them)
     delete c;
 }
 
 int fheram_ctx_config(const fheram_ctx* c, fheram_config* out) {
     if (!c || !out) return FHERAM_ERR_INVALID_ARG;
-    fheram_config d{};
-    d.limb_split = c->limb_split; d.fine_split = c->fine_split; d.memo = c->memo; d.pre_inv = c->pre_inv; d.tail = c->tail; d.tail_test = c->tail_test;
-    d.mid = c->mid; d.mid_test = c->mid_test; d.chain = c->chain; d.chain_y = c->chain_y; d.pair_z = c->pair_z; d.fuse = c->fuse;
-    d.graph = c->use_graph; d.safe = c->safe; d.nco = c->nco; d.monitor = c->monitor; d.tail_ep = c->tail_ep;
-    *out = d;
+    *out = c->cfg;   // what the two watches left of tail and mid included (launch.hpp)
+    out->reserved = 0;
     return FHERAM_OK;
 }
 
@@ -451,7 +381,7 @@ int fheram_roundoff_max(fheram_ctx* c, double* max_out) {
     double m = 0.0;
     HIPCHK(c, hipMemcpy(&m, c->d_tw + N, sizeof(double), hipMemcpyDeviceToHost));
     *max_out = m;
-    if (c->monitor && m > MON_LIMIT) __atomic_store_n(c->h_ro_flag, 1u, __ATOMIC_RELAXED);
+    if (c->cfg.monitor && m > MON_LIMIT) __atomic_store_n(c->h_ro_flag, 1u, __ATOMIC_RELAXED);
     return check_precision(c);
 }
 int fheram_roundoff_reset(fheram_ctx* c) {
@@ -533,7 +463,7 @@ int fheram_write(fheram_ctx* c, const int64_t* w, int n_w, const fheram_addr* ad
     // the part of a write that needs no words (trace(ct_hi) of every row, inverse of coordinate 0) is enqueued BEFORE the host
     // narrows the words: the GPU works while the host converts
     const Opnds o = one_addr(c, &addr);
-    if (w && !c->side_begun && !(c->use_graph && !c->profile)) write_side_begin(o, ctx_view(c));
+    if (w && !c->side_begun && !capturing(c)) write_side_begin(o, ctx_view(c));
     if (w) { rc = fheram_word_stage(c, w, n_w); if (rc != FHERAM_OK) { write_side_abort(c); return rc; } }
     rc = run_op(c, addr, 2, [&] {
         if (!c->side_begun) write_side_begin(o, ctx_view(c));   // (fheram_write_begin may have started it)
@@ -806,7 +736,7 @@ int fheram_mid_stats(fheram_ctx* c, uint64_t* launches, uint64_t* fallbacks) {
 }
 int fheram_mid_state(const fheram_ctx* c, int* enabled, uint64_t* times_disabled) {
     if (!c) return FHERAM_ERR_INVALID_ARG;
-    if (enabled) *enabled = c->mid;
+    if (enabled) *enabled = c->cfg.mid;
     if (times_disabled) *times_disabled = c->mid_disabled_count;
     return FHERAM_OK;
 }

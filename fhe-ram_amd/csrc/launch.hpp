@@ -22,7 +22,7 @@ void with_evk_wide(fheram_ctx* c, bool wide, F&& f) {
 // Under FHERAM_GRAPH=1 the enqueue functions run inside a stream capture: forked work has to be joined before the
 // capture ends, an event recorded inside one captured op cannot be waited on from another, and a launch that carries a
 // generation number (the single-launch chains) would replay it.
-bool capturing(const fheram_ctx* c) { return c->use_graph && !c->profile; }
+bool capturing(const fheram_ctx* c) { return c->cfg.graph && !c->profile; }
 
 // ---- kernel launchers ---------------------------------------------------------------------
 constexpr int LIMB_SPLIT_MAX = 64;   // ciphertexts per launch the limb-parallel path is used for (at most)
@@ -31,7 +31,7 @@ constexpr int EW_SLICES = 8;   // workgroups per ciphertext of the elementwise k
 // output column doubles the number of workgroups, which pays while the batch cannot fill the CUs.
 // one_wg: the caller's launch takes one workgroup per ciphertext wherever the context leaves the choice (chain_form)
 int pick_nco(const fheram_ctx* c, int gx, int gy, bool one_wg = false) {
-    if (c->nco != 0) return c->nco;
+    if (c->cfg.nco != 0) return c->cfg.nco;
     if (one_wg) return 2;
     return ((long)gx * gy * 2 <= c->cus) ? 1 : 2;
 }
@@ -46,12 +46,12 @@ void launch_prepare(fheram_ctx* c, const int32_t* in, double* out, int npoly, in
 // column split leaves most CUs idle.
 double* big_of(const fheram_ctx* c) { return c->cur == c->stream2 ? c->d_big2 : c->d_big; }
 bool use_limb_split(const fheram_ctx* c, int gx, int gy, int sk) {
-    return c->limb_split && (long)gx * gy <= LIMB_SPLIT_MAX && (long)gx * gy * 2 * sk <= c->cus;
+    return c->cfg.limb_split && (long)gx * gy <= LIMB_SPLIT_MAX && (long)gx * gy * 2 * sk <= c->cus;
 }
 // Fine limb split (k_keyswitch_fine / k_ext_product_fine): wgs workgroups per ciphertext, one forward and one
 // inverse transform each, while the whole launch still fits the chip in one wave of workgroups.
 bool use_fine_split(const fheram_ctx* c, int gx, int gy, int wgs) {
-    return c->limb_split && c->fine_split && (long)gx * gy * wgs <= c->cus && (long)gx * gy * wgs * N * 8 <= (long)LIMB_SPLIT_MAX * BIG_STRIDE * 8;
+    return c->cfg.limb_split && c->cfg.fine_split && (long)gx * gy * wgs <= c->cus && (long)gx * gy * wgs * N * 8 <= (long)LIMB_SPLIT_MAX * BIG_STRIDE * 8;
 }
 void launch_ep(fheram_ctx* c, GlweRef a, GlweRef res, const double* ggsw, int gx, int gy) {
     if (gx <= 0 || gy <= 0) return;
@@ -95,7 +95,7 @@ void launch_ks(fheram_ctx* c, const KsArgs& ka, int gx, int gy) {
     // have up to 1024 pairs, the split combine is 3 % faster per read than the spilling fused one was).
     constexpr bool FUSABLE = (SX == 3) && (MODE != KS_PAIR);
     if constexpr (MODE == KS_PAIR && SX == 3 && SO == 3) {
-        if (c->pair_z) {   // the column-split combine in closed form (k_pair_z)
+        if (c->cfg.pair_z) {   // the column-split combine in closed form (k_pair_z)
             hipLaunchKernelGGL((k_pair_z<SK>), dim3(gx, gy, 2), dim3(T), LDS_BYTES, c->cur, ka);
             return;
         }
@@ -172,21 +172,21 @@ ChainPlan chain_form(const fheram_ctx* c, const ChainQuery& q) {
     const long batch = (long)q.gx * q.gy;
     const int sk = q.ep ? 4 : c->s_evk;
     const bool len = q.n >= 2 && q.n <= CHAIN_MAX;
-    const bool handoff = q.handoff && len && c->limb_split &&
+    const bool handoff = q.handoff && len && c->cfg.limb_split &&
                          c->cus >= TAIL_GROUPS * 32 &&   // the whole chip (8 XCDs x 32 CUs): a partition could not hold the groups side by side
                          !capturing(c);                  // a captured launch would replay its generation number
-    if (handoff && !q.ep && !q.rotated && c->tail && c->fine_split && batch <= TAIL_GROUPS &&
+    if (handoff && !q.ep && !q.rotated && c->cfg.tail && c->cfg.fine_split && batch <= TAIL_GROUPS &&
         c->cur == c->stream &&   // every launch of a context shares d_tail_sync: main stream only
         2 * sk * 3 <= 32)        // the workgroups of a ciphertext fit the 32 CUs of one XCD (24 with 4-limb keys, 30 with 5)
         return {ChainForm::Tail, 0};
-    if (handoff && c->mid && batch > TAIL_GROUPS) {
+    if (handoff && c->cfg.mid && batch > TAIL_GROUPS) {
         if (batch <= 16) return {ChainForm::Mid, 1};
-        if (!q.ep && c->mid >= 2) {   // the coarser splits, of 2 * sk and sk members: trace chains only
+        if (!q.ep && c->cfg.mid >= 2) {   // the coarser splits, of 2 * sk and sk members: trace chains only
             if (batch <= 8 * (32 / (2 * sk))) return {ChainForm::Mid, 2};
             if (batch <= 8 * (32 / sk)) return {ChainForm::Mid, 3};
         }
     }
-    if (len && c->chain && pick_nco(c, q.gx, q.gy, q.one_wg) == 2 && !use_limb_split(c, q.gx, q.gy, sk) &&
+    if (len && c->cfg.chain && pick_nco(c, q.gx, q.gy, q.one_wg) == 2 && !use_limb_split(c, q.gx, q.gy, sk) &&
         !use_fine_split(c, q.gx, q.gy, q.ep ? 2 * 4 * 2 * 3 : 2 * sk * 3))
         return {ChainForm::Chain, 0};
     return {ChainForm::Steps, 0};
@@ -213,7 +213,7 @@ ChainPlan plan_chain(const fheram_ctx* c, ChainQuery q, GlweRef src, GlweRef dst
 // the single-launch mid chains, switched off because their launches kept giving up (fill_mid), are tried again 256 ops
 // later: a neighbour that held the CUs for a while does not cost the path its faster form for the context's life
 void mid_rearm(fheram_ctx* c) {
-    if (!c->mid && c->mid_saved && ++c->mid_off_ops >= 256) { c->mid = c->mid_saved; c->mid_saved = 0; c->mid_bad_windows = 0; c->mid_off_ops = 0; }
+    if (!c->cfg.mid && c->mid_saved && ++c->mid_off_ops >= 256) { c->cfg.mid = c->mid_saved; c->mid_saved = 0; c->mid_bad_windows = 0; c->mid_off_ops = 0; }
 }
 template <bool EP>
 void fill_mid(fheram_ctx* c, MidArgs& ma, GlweRef src, GlweRef dst, int n, int gx, int gy) {
@@ -227,18 +227,18 @@ void fill_mid(fheram_ctx* c, MidArgs& ma, GlweRef src, GlweRef dst, int n, int g
     // (counted, both streams) were redone.  One contended launch does not switch the path off, two bad windows in a row do
     // (fheram_mid_state); 256 ops later (mid_rearm) the single-launch form is tried again.
     c->mid_window_cts += (uint64_t)(gx * gy);
-    if (!c->mid_test && c->mid_launches - c->mid_launch_mark >= 64) {
+    if (!c->cfg.mid_test && c->mid_launches - c->mid_launch_mark >= 64) {
         const unsigned fb = __atomic_load_n(c->h_mid_fb, __ATOMIC_RELAXED) + __atomic_load_n(c->h_mid_fb + 16, __ATOMIC_RELAXED);
         const unsigned redone = fb - c->mid_fb_mark;
         const bool bad = (uint64_t)redone * 4u > c->mid_window_cts;
         c->mid_bad_windows = bad ? c->mid_bad_windows + 1 : 0;
-        if (c->mid && c->mid_bad_windows >= 2) { c->mid_saved = c->mid; c->mid = 0; c->mid_disabled_count++; }
+        if (c->cfg.mid && c->mid_bad_windows >= 2) { c->mid_saved = c->cfg.mid; c->cfg.mid = 0; c->mid_disabled_count++; }
         c->mid_fb_mark = fb;
         c->mid_launch_mark = c->mid_launches;
         c->mid_window_cts = 0;
     }
     ma.seq = c->mid_seq; ma.n = n; ma.n_ct = gx * gy; ma.gx = gx; ma.rot_mul = 0; ma.rot_base = 0;
-    ma.give_up_at = c->mid_test ? n - 2 : -1;
+    ma.give_up_at = c->cfg.mid_test ? n - 2 : -1;
 }
 // b: the buffers of the fallback chain (step i writes b[i & 1]; b[0] != src); the result lands in b[(n - 1) & 1], which may be src
 template <int SK, int RS, int LPM>
@@ -308,7 +308,7 @@ void launch_trace_chain(fheram_ctx* c, GlweRef src, const GlweRef (&b)[2], int s
     ca.base = ks_args(c, src, src, b[0], trace_key(c, start), c->gal[start], 0, rot_mul, rot_base);
     ca.buf[0] = b[0]; ca.buf[1] = b[1]; ca.n = n;
     for (int i = 0; i < n; i++) { ca.key[i] = trace_key(c, start + i); ca.ginv[i] = galois_inv_mod(galois_mod(c->gal[start + i])); }
-    const int yf = n >= 2 ? c->chain_y : 0;   // intermediates handed over as Y = ceil(A/2) through LDS and registers (ks_trace_l); 0: int32 limbs (ks_run)
+    const int yf = n >= 2 ? c->cfg.chain_y : 0;   // intermediates handed over as Y = ceil(A/2) through LDS and registers (ks_trace_l); 0: int32 limbs (ks_run)
     with_evk_wide(c, yf && c->wide, [&](auto sk, auto w) {
         constexpr int SK = decltype(sk)::value;
         if (!yf) hipLaunchKernelGGL((k_keyswitch_chain<3, SK, 3>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, ca);
@@ -327,7 +327,7 @@ constexpr unsigned SRC_MAP_IDENTITY = 0x76543210u;   // entry k reads member k
 // (chain_form: whether the trace chain's first step reads rotated input does not matter to it), in the variants that hand over through
 // LDS and registers.  one_wg: ChainQuery's.
 bool use_row_fuse(const fheram_ctx* c, int d, int n_tr, int gx, int gy, bool one_wg = false) {
-    return c->fuse && c->chain_y == 3 && !capturing(c) &&
+    return c->cfg.fuse && c->cfg.chain_y == 3 && !capturing(c) &&
            chain_form(c, ChainQuery{true, d, gx, gy, false, one_wg}).form == ChainForm::Chain &&
            chain_form(c, ChainQuery{false, n_tr, gx, gy, false, one_wg}).form == ChainForm::Chain;
 }
@@ -404,13 +404,13 @@ void launch_trace_tail(fheram_ctx* c, GlweRef src, const GlweRef (&b)[2], int st
     for (int i = 0; i < TAIL_EP_MAX; i++) ta.ggsw[i] = (prep && i < d) ? prep + (size_t)i * fheram_ctx::GGSW : nullptr;
     if (++c->tail_seq == 0) ++c->tail_seq;
     c->tail_launches++;
-    if (c->tail_test != 1 && c->tail_launches - c->tail_launch_mark >= 64) {
+    if (c->cfg.tail_test != 1 && c->tail_launches - c->tail_launch_mark >= 64) {
         const unsigned fb = *(volatile unsigned*)c->h_tail_fb;
-        if (fb - c->tail_fb_mark > 16) c->tail = 0;      // takes effect from the next chain on
+        if (fb - c->tail_fb_mark > 16) c->cfg.tail = 0;      // takes effect from the next chain on
         c->tail_fb_mark = fb;
         c->tail_launch_mark = c->tail_launches;
     }
-    ta.seq = c->tail_seq; ta.n = n; ta.n_ct = gx * gy; ta.gx = gx; ta.xoff = c->tail_xoff; ta.give_up_at = c->tail_test ? ta.n_ep + n - 2 : -1;   // late: every buffer but the source has been overwritten by then
+    ta.seq = c->tail_seq; ta.n = n; ta.n_ct = gx * gy; ta.gx = gx; ta.xoff = c->tail_xoff; ta.give_up_at = c->cfg.tail_test ? ta.n_ep + n - 2 : -1;   // late: every buffer but the source has been overwritten by then
     KsChainArgs ca;
     ca.base = ks_args(c, src, src, b[0], trace_key(c, start), c->gal[start], 0, 0, 0);
     ca.buf[0] = b[0]; ca.buf[1] = b[1]; ca.n = n;

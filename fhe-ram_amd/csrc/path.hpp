@@ -62,10 +62,10 @@ RamView ctx_view(const fheram_ctx* c) {
 // What an operation leaves on the host, once it has been enqueued — or replayed (run_op), which does not run the enqueue functions.
 // A read has one such function per stage, because the stages of a row-sharded RAM run on different contexts.
 void read_local_done(const fheram_ctx* c, RamState* st, bool prepare_write) {   // memo_alone: arena A keeps the rows after their alone levels (two coordinates only)
-    if (c->n2 == 2) st->memo_alone = (prepare_write && c->memo) ? LOGN - ilog2_ceil(c->rows_glob) : 0;
+    if (c->n2 == 2) st->memo_alone = (prepare_write && c->cfg.memo) ? LOGN - ilog2_ceil(c->rows_glob) : 0;
 }
 void read_top_done(fheram_ctx* c, RamState* st, bool prepare_write) {
-    st->memo_top = prepare_write && c->memo;          // trtop = trace(tree top), kept for the write
+    st->memo_top = prepare_write && c->cfg.memo;          // trtop = trace(tree top), kept for the write
     st->res_in_trtop = st->memo_top;
     c->prep1_ready = false;
 }
@@ -77,7 +77,7 @@ void write_done(fheram_ctx* c, RamState* st) { st->memo_top = false; st->memo_al
 // replayed, instead of being re-enqueued kernel by kernel.  (One address only; pre_inv is off under FHERAM_GRAPH=1, so inv_id stays 0.)
 template <typename F>
 int run_op(fheram_ctx* c, const fheram_addr* addr, int which, F&& enqueue) {
-    if (!c->use_graph || c->profile) return enqueue();
+    if (!capturing(c)) return enqueue();
     fheram_addr* a = const_cast<fheram_addr*>(addr);
     // what the enqueue function reads of the context's mutable state (a write resumes from what read_prepare_write kept —
     // or not, after a key load or with another address): a capture taken under another signature is not replayed
@@ -123,7 +123,7 @@ int read_local(const Opnds& o, const RamView& a, bool prepare_write, GlweRef* pa
     fheram_ctx* c = o.c;
     const int n = o.n, ws = o.ws, Y = o.Y(), R = (int)c->rows;
     c->wide = !prepare_write || n > 1;   // read_prepare_write parks the gate wave beside its launches (read_top): its chain kernels keep a wave slot free; several addresses never park one
-    if (n == 1 && prepare_write && c->pre_inv == 1 && !capturing(c) && (c->wide_unsynced || c->derive_unsynced)) {   // the gate wave may not be parked before this op's own launches start, nor its work read digits a derive launch is still writing (ctx.hpp: ev_opstart)
+    if (n == 1 && prepare_write && c->cfg.pre_inv == 1 && !capturing(c) && (c->wide_unsynced || c->derive_unsynced)) {   // the gate wave may not be parked before this op's own launches start, nor its work read digits a derive launch is still writing (ctx.hpp: ev_opstart)
         hipEventRecord(c->ev_opstart, c->stream);
         c->opstart_valid = true;
     }
@@ -178,7 +178,7 @@ int read_top(const Opnds& o, const RamView& a, bool prepare_write, int32_t* gath
     // coordinate 1's products inside the trace chain's launch (k_trace_tail's product steps): from two digits on (the fallback is the fused row chain)
     const int d1 = c->n2 == 2 ? (int)c->base2d[1].size() : 0;
     auto tail_top = [&] { return chain_form(c, ChainQuery{false, LOGN, 1, Y}).form == ChainForm::Tail; };   // the final trace: will it ask for the tail launch (as things stand now)
-    const bool fuse_ep = c->n2 == 2 && c->tail_ep && d1 >= 2 && d1 <= TAIL_EP_MAX && tail_top();
+    const bool fuse_ep = c->n2 == 2 && c->cfg.tail_ep && d1 >= 2 && d1 <= TAIL_EP_MAX && tail_top();
     GlweRef ep_out = ref(prepare_write ? a.tree : a.tmp2, G, 0);                          // read_prepare_write: tree[0] <- rotated packed row, ram.rs:525-527
     auto products1 = [&] { for (int k = 0; k < n; k++) ep_chain(c, o.slice(pk, k), o.slice(ep_out, k), o.slice(tmp, k), o.prep(k, 1), d1, 1, ws); };   // ram.rs:454 (not into res: the trace below runs out of place) / 525-527 + 502-504 (i = 1)
     if (c->n2 == 2) {
@@ -199,8 +199,8 @@ int read_top(const Opnds& o, const RamView& a, bool prepare_write, int32_t* gath
     // lowest priority, so that launch is placed first)
     // (only while the write's chains are one workgroup round on the chip: with several rounds — 2^21 on one GPU — the
     // earlier start of the write's main chain interleaves it with the side chain less favourably, write 8.57 -> 8.74 ms)
-    const bool pre = n == 1 && prepare_write && c->pre_inv && (long)c->rows * Y <= c->cus;
-    const bool gated = pre && c->pre_inv == 1 && !capturing(c) && tail_top();   // FHERAM_PRE_INV=2: event fork (A/B switch)
+    const bool pre = n == 1 && prepare_write && c->cfg.pre_inv && (long)c->rows * Y <= c->cus;
+    const bool gated = pre && c->cfg.pre_inv == 1 && !capturing(c) && tail_top();   // FHERAM_PRE_INV=2: event fork (A/B switch)
     if (pre && !gated)
         for (int ci = c->n2 - 1; ci >= 0; ci--) precompute_inverse(c, o.addrs[0], ci, ci == c->n2 - 1);   // coordinate 1 first: the write's head needs it first
     read_top_done(c, o.st, prepare_write);
@@ -305,7 +305,7 @@ int result_export(fheram_ctx* c, const ResRun* runs, int n_runs, int64_t* h, int
     c->wide_unsynced = c->derive_unsynced = false;
     double m;
     std::memcpy(&m, h + n, 8);
-    if (c->monitor && m > MON_LIMIT) __atomic_store_n(c->h_ro_flag, 1u, __ATOMIC_RELAXED);
+    if (c->cfg.monitor && m > MON_LIMIT) __atomic_store_n(c->h_ro_flag, 1u, __ATOMIC_RELAXED);
     const int rc = check_precision(c);
     if (rc == FHERAM_OK && out) std::memcpy(out, h, n * sizeof(int64_t));
     return rc;

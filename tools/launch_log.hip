@@ -26,6 +26,8 @@
 // the context's buffer fields and word count: a range's pointer arithmetic, and anything an operation leaves behind in the context, is in
 // the log.  What differs between trees — how a bank range is presented to the sequences, where the per-RAM state lives — is in the shim.
 // bank.hpp names entry points of fheram.hip that this program never calls: link with -Wl,--unresolved-symbols=ignore-all.
+// Third mode, `./launch_log config`: the switches IN EFFECT (ctx.hpp config_in_effect) for a list of requested configurations, one line per
+// input, both sides as departures from the built-in defaults D (profiles/ctx_config_in_effect.txt: the tree's of DESIGN.md 10.6).
 #include <hip/hip_runtime.h>
 #include <sys/mman.h>
 #include <cinttypes>
@@ -138,36 +140,36 @@ int32_t* arena(int k) { return fake<int32_t*>(32 + k); }
 struct Setting { const char* name; void (*apply)(fheram_ctx*); };
 const Setting SETTINGS[] = {
     {"default", [](fheram_ctx*) {}},
-    {"nco=1", [](fheram_ctx* c) { c->nco = 1; }},
-    {"nco=2", [](fheram_ctx* c) { c->nco = 2; }},
-    {"limb_split=0", [](fheram_ctx* c) { c->limb_split = 0; }},
-    {"fine_split=0", [](fheram_ctx* c) { c->fine_split = 0; }},
-    {"tail=0", [](fheram_ctx* c) { c->tail = 0; }},
-    {"tail_test=1", [](fheram_ctx* c) { c->tail_test = 1; }},
-    {"tail_test=2", [](fheram_ctx* c) { c->tail_test = 2; }},
-    {"tail_ep=0", [](fheram_ctx* c) { c->tail_ep = 0; }},
-    {"mid=0", [](fheram_ctx* c) { c->mid = 0; }},
-    {"mid=1", [](fheram_ctx* c) { c->mid = 1; }},
-    {"mid_test=1", [](fheram_ctx* c) { c->mid_test = 1; }},
-    {"chain=0", [](fheram_ctx* c) { c->chain = 0; }},
-    {"chain_y=0", [](fheram_ctx* c) { c->chain_y = 0; }},
-    {"fuse=0", [](fheram_ctx* c) { c->fuse = 0; }},
-    {"pair_z=0", [](fheram_ctx* c) { c->pair_z = 0; }},
-    {"safe", [](fheram_ctx* c) { c->safe = 1; c->tail = 0; c->tail_test = 0; c->mid = 0; c->mid_test = 0; }},
+    {"nco=1", [](fheram_ctx* c) { c->cfg.nco = 1; }},
+    {"nco=2", [](fheram_ctx* c) { c->cfg.nco = 2; }},
+    {"limb_split=0", [](fheram_ctx* c) { c->cfg.limb_split = 0; }},
+    {"fine_split=0", [](fheram_ctx* c) { c->cfg.fine_split = 0; }},
+    {"tail=0", [](fheram_ctx* c) { c->cfg.tail = 0; }},
+    {"tail_test=1", [](fheram_ctx* c) { c->cfg.tail_test = 1; }},
+    {"tail_test=2", [](fheram_ctx* c) { c->cfg.tail_test = 2; }},
+    {"tail_ep=0", [](fheram_ctx* c) { c->cfg.tail_ep = 0; }},
+    {"mid=0", [](fheram_ctx* c) { c->cfg.mid = 0; }},
+    {"mid=1", [](fheram_ctx* c) { c->cfg.mid = 1; }},
+    {"mid_test=1", [](fheram_ctx* c) { c->cfg.mid_test = 1; }},
+    {"chain=0", [](fheram_ctx* c) { c->cfg.chain = 0; }},
+    {"chain_y=0", [](fheram_ctx* c) { c->cfg.chain_y = 0; }},
+    {"fuse=0", [](fheram_ctx* c) { c->cfg.fuse = 0; }},
+    {"pair_z=0", [](fheram_ctx* c) { c->cfg.pair_z = 0; }},
+    {"safe", [](fheram_ctx* c) { c->cfg.safe = 1; c->cfg.tail = 0; c->cfg.tail_test = 0; c->cfg.mid = 0; c->cfg.mid_test = 0; }},
     {"wide", [](fheram_ctx* c) { c->wide = true; }},
     // the pairs the test suite forces
-    {"limb_split=0,nco=1", [](fheram_ctx* c) { c->limb_split = 0; c->nco = 1; }},
-    {"limb_split=0,nco=2", [](fheram_ctx* c) { c->limb_split = 0; c->nco = 2; }},
-    {"limb_split=0,nco=2,wide", [](fheram_ctx* c) { c->limb_split = 0; c->nco = 2; c->wide = true; }},
-    {"limb_split=0,nco=2,chain=0", [](fheram_ctx* c) { c->limb_split = 0; c->nco = 2; c->chain = 0; }},
-    {"limb_split=0,nco=2,chain_y=0", [](fheram_ctx* c) { c->limb_split = 0; c->nco = 2; c->chain_y = 0; }},
-    {"limb_split=0,nco=2,chain_y=0,wide", [](fheram_ctx* c) { c->limb_split = 0; c->nco = 2; c->chain_y = 0; c->wide = true; }},
-    {"limb_split=0,nco=2,fuse=0,pair_z=0", [](fheram_ctx* c) { c->limb_split = 0; c->nco = 2; c->fuse = 0; c->pair_z = 0; }},
-    {"chain_y=0,fuse=0,nco=2,limb_split=0", [](fheram_ctx* c) { c->chain_y = 0; c->fuse = 0; c->nco = 2; c->limb_split = 0; }},
-    {"mid=0,tail=0", [](fheram_ctx* c) { c->mid = 0; c->tail = 0; }},
-    {"tail_ep=0,tail_test=1", [](fheram_ctx* c) { c->tail_ep = 0; c->tail_test = 1; }},
-    {"nco=2,mid=0", [](fheram_ctx* c) { c->nco = 2; c->mid = 0; }},
-    {"nco=2,fine_split=0", [](fheram_ctx* c) { c->nco = 2; c->fine_split = 0; }},
+    {"limb_split=0,nco=1", [](fheram_ctx* c) { c->cfg.limb_split = 0; c->cfg.nco = 1; }},
+    {"limb_split=0,nco=2", [](fheram_ctx* c) { c->cfg.limb_split = 0; c->cfg.nco = 2; }},
+    {"limb_split=0,nco=2,wide", [](fheram_ctx* c) { c->cfg.limb_split = 0; c->cfg.nco = 2; c->wide = true; }},
+    {"limb_split=0,nco=2,chain=0", [](fheram_ctx* c) { c->cfg.limb_split = 0; c->cfg.nco = 2; c->cfg.chain = 0; }},
+    {"limb_split=0,nco=2,chain_y=0", [](fheram_ctx* c) { c->cfg.limb_split = 0; c->cfg.nco = 2; c->cfg.chain_y = 0; }},
+    {"limb_split=0,nco=2,chain_y=0,wide", [](fheram_ctx* c) { c->cfg.limb_split = 0; c->cfg.nco = 2; c->cfg.chain_y = 0; c->wide = true; }},
+    {"limb_split=0,nco=2,fuse=0,pair_z=0", [](fheram_ctx* c) { c->cfg.limb_split = 0; c->cfg.nco = 2; c->cfg.fuse = 0; c->cfg.pair_z = 0; }},
+    {"chain_y=0,fuse=0,nco=2,limb_split=0", [](fheram_ctx* c) { c->cfg.chain_y = 0; c->cfg.fuse = 0; c->cfg.nco = 2; c->cfg.limb_split = 0; }},
+    {"mid=0,tail=0", [](fheram_ctx* c) { c->cfg.mid = 0; c->cfg.tail = 0; }},
+    {"tail_ep=0,tail_test=1", [](fheram_ctx* c) { c->cfg.tail_ep = 0; c->cfg.tail_test = 1; }},
+    {"nco=2,mid=0", [](fheram_ctx* c) { c->cfg.nco = 2; c->cfg.mid = 0; }},
+    {"nco=2,fine_split=0", [](fheram_ctx* c) { c->cfg.nco = 2; c->cfg.fine_split = 0; }},
 };
 const int CUS[] = {64, 128, 256, 304};
 const int GX[] = {1, 2, 3, 4, 8, 9, 16, 17, 32, 64, 65, 128, 256, 512, 2048};
@@ -190,8 +192,8 @@ fheram_ctx* make_ctx(unsigned* host_words) {
 }
 // what a launch advances: every case starts from the same counters
 void rewind(fheram_ctx* c, const fheram_ctx* as) {
-    c->tail = as->tail; c->tail_seq = 0; c->tail_launches = c->tail_launch_mark = 0; c->tail_fb_mark = 0;
-    c->mid = as->mid; c->mid_seq = 0; c->mid_launches = c->mid_launch_mark = 0; c->mid_fb_mark = 0; c->mid_bad_windows = c->mid_saved = 0;
+    c->cfg.tail = as->cfg.tail; c->tail_seq = 0; c->tail_launches = c->tail_launch_mark = 0; c->tail_fb_mark = 0;
+    c->cfg.mid = as->cfg.mid; c->mid_seq = 0; c->mid_launches = c->mid_launch_mark = 0; c->mid_fb_mark = 0; c->mid_bad_windows = c->mid_saved = 0;
     c->mid_window_cts = c->mid_disabled_count = 0; c->wide_unsynced = false;
     c->prof.clear();
 }
@@ -276,15 +278,15 @@ void run_config(fheram_ctx* c) {
 // the switch settings the bank suite forces (tests/test_gpu_bank.py FORMS, as fheram_ctx_create_cfg derives them)
 const Setting PATH_SETTINGS[] = {
     {"default", [](fheram_ctx*) {}},
-    {"tail=0", [](fheram_ctx* c) { c->tail = 0; }},
-    {"tail_ep=0", [](fheram_ctx* c) { c->tail_ep = 0; }},
-    {"mid=0", [](fheram_ctx* c) { c->mid = 0; }},
-    {"fuse=0", [](fheram_ctx* c) { c->fuse = 0; }},
-    {"chain_y=0", [](fheram_ctx* c) { c->chain_y = 0; }},
-    {"memo=0", [](fheram_ctx* c) { c->memo = 0; c->pre_inv = 0; }},
-    {"pre_inv=0", [](fheram_ctx* c) { c->pre_inv = 0; }},
-    {"pre_inv=2", [](fheram_ctx* c) { c->pre_inv = 2; }},
-    {"safe", [](fheram_ctx* c) { c->safe = 1; c->tail = 0; c->tail_test = 0; c->mid = 0; c->mid_test = 0; c->pre_inv = 2; c->monitor = 2; }},
+    {"tail=0", [](fheram_ctx* c) { c->cfg.tail = 0; }},
+    {"tail_ep=0", [](fheram_ctx* c) { c->cfg.tail_ep = 0; }},
+    {"mid=0", [](fheram_ctx* c) { c->cfg.mid = 0; }},
+    {"fuse=0", [](fheram_ctx* c) { c->cfg.fuse = 0; }},
+    {"chain_y=0", [](fheram_ctx* c) { c->cfg.chain_y = 0; }},
+    {"memo=0", [](fheram_ctx* c) { c->cfg.memo = 0; c->cfg.pre_inv = 0; }},
+    {"pre_inv=0", [](fheram_ctx* c) { c->cfg.pre_inv = 0; }},
+    {"pre_inv=2", [](fheram_ctx* c) { c->cfg.pre_inv = 2; }},
+    {"safe", [](fheram_ctx* c) { c->cfg.safe = 1; c->cfg.tail = 0; c->cfg.tail_test = 0; c->cfg.mid = 0; c->cfg.mid_test = 0; c->cfg.pre_inv = 2; c->cfg.monitor = 2; }},
 };
 const int PATH_LOG_MAX_ADDR[] = {12, 13, 14, 16, 18};
 
@@ -393,7 +395,7 @@ void run_path_bank(fheram_ctx* c, int M, int mws) {
     fheram_bank* b = new fheram_bank();
     b->c = c; b->M = M; b->mws = mws;
     b->d_prep = fake<double*>(60); b->d_prep_inv = fake<double*>(61);
-    if (M > 1) c->pre_inv = 0;   // (fheram_bank_create)
+    if (M > 1) c->cfg.pre_inv = 0;   // (fheram_bank_create)
     shim_loaded(b);
     const fheram_addr* a[3];
     for (int k = 0; k < 3; k++) a[k] = make_addr(c, k);
@@ -452,9 +454,38 @@ int path_main(long only, unsigned* host_words) {
     return 0;
 }
 
+// ---- config mode: config_in_effect of each input ------------------------------------------------------------------------------------
+struct CfgField { const char* name; int32_t fheram_config::*p; };
+#define CFG_FIELD(f) {#f, &fheram_config::f}
+const CfgField CFG_FIELDS[] = {CFG_FIELD(limb_split), CFG_FIELD(fine_split), CFG_FIELD(memo), CFG_FIELD(pre_inv), CFG_FIELD(tail), CFG_FIELD(tail_test),
+                               CFG_FIELD(mid), CFG_FIELD(mid_test), CFG_FIELD(chain), CFG_FIELD(chain_y), CFG_FIELD(pair_z), CFG_FIELD(fuse),
+                               CFG_FIELD(graph), CFG_FIELD(safe), CFG_FIELD(nco), CFG_FIELD(tail_ep), CFG_FIELD(monitor)};
+const char* const CONFIG_INPUTS[] = {
+    "", "memo=0", "memo=0,pre_inv=2", "pre_inv=0", "pre_inv=2", "pre_inv=5", "pre_inv=-1", "graph=1", "graph=1,pre_inv=2", "safe=1", "safe=1,tail_test=2,mid_test=1",
+    "safe=1,monitor=0", "safe=1,pre_inv=0", "safe=1,graph=1", "mid=7", "mid=-1", "mid=1", "tail_test=5", "tail_test=-3", "tail=0,tail_test=1", "tail=-1",
+    "limb_split=7", "monitor=9", "monitor=-1", "nco=1", "nco=2", "nco=3", "nco=-1", "chain_y=1", "chain_y=0"};
+std::string departures(const fheram_config& cfg, const fheram_config* from) {   // from == nullptr: every field
+    std::string out;
+    for (const CfgField& f : CFG_FIELDS)
+        if (!from || cfg.*f.p != from->*f.p) out += (out.empty() ? "" : ", ") + std::string(f.name) + " " + std::to_string(cfg.*f.p);
+    return out.empty() ? "D" : out;
+}
+int config_main() {
+    const fheram_config D = config_builtin();
+    std::printf("D: %s\n", departures(D, nullptr).c_str());
+    for (const char* in : CONFIG_INPUTS) {
+        fheram_config asked = D;
+        for (const char* q = in; *q; q += std::strcspn(q, ","), q += *q == ',')   // name=value, comma-separated
+            for (const CfgField& f : CFG_FIELDS) { const size_t n = std::strlen(f.name); if (!std::strncmp(q, f.name, n) && q[n] == '=') asked.*f.p = std::atoi(q + n + 1); }
+        std::printf("%s -> %s\n", in[0] ? in : "(none)", departures(config_in_effect(asked), &D).c_str());
+    }
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
+    if (argc > 1 && !std::strcmp(argv[1], "config")) return config_main();
     const bool path = argc > 1 && !std::strcmp(argv[1], "path");
     const long only = argc > 1 + path ? std::atol(argv[1 + path]) : -1;
     unsigned* host_words = static_cast<unsigned*>(mmap(reinterpret_cast<void*>(0x7e0000000000ull), 4096, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_FIXED_NOREPLACE, -1, 0));
@@ -467,7 +498,7 @@ int main(int argc, char** argv) {
         fheram_ctx* c = make_ctx(host_words);
         c->cus = cus; c->s_evk = s_evk; c->atk = (size_t)fheram_ctx::DNUM_CT * s_evk * 2 * N;
         st.apply(c);
-        c->use_graph = graph; c->profile = profile;
+        c->cfg.graph = graph; c->profile = profile;
         c->cur = side ? c->stream2 : c->stream;
         ll::verbose = only >= 0;
         ll::digest = 0xcbf29ce484222325ull; ll::lines = 0;
