@@ -225,6 +225,12 @@ struct fheram_ctx {
     // read behind the launch: derive_unsynced = such a launch has been enqueued and the host has not waited for the stream since; the next
     // gated read_prepare_write then records ev_opstart behind it, whatever wide_unsynced says.
     bool derive_unsynced = false;
+    // main_idle: the host has waited for the main stream (main_waited: fheram_sync, fheram_timer_end, the result export) and nothing with an
+    // effect on memory has been enqueued on it since (main_enqueued: every operation's enqueue functions, the words' copy, the device-side
+    // hand-overs, the stream waits, a derive launch; a bare event record — fheram_timer_begin — changes nothing a later launch could depend on).
+    // The side stage of a write then has nothing to wait for on the main stream, and write_side_begin saves the fork event (a record and a
+    // cross-stream wait in front of the write's first kernel).  Whoever enqueues on the main stream without waiting for it at its end clears the flag.
+    bool main_idle = false;
     // ---- staging ----
     int32_t* h_pin[2] = {nullptr, nullptr};   // pinned host staging (hand-over of int64 host buffers), made on first use (pin_init)
     hipEvent_t ev_pin[2] = {nullptr, nullptr};
@@ -295,6 +301,10 @@ int check_precision(fheram_ctx* c) {
     } while (0)
 
 GlweRef ref(int32_t* p, long sy, long sx) { return GlweRef{p, sy, sx}; }
+
+// the host has just waited for everything enqueued on the main stream / something is being enqueued on it (fheram_ctx: wide_unsynced, derive_unsynced, main_idle)
+void main_waited(fheram_ctx* c) { c->wide_unsynced = c->derive_unsynced = false; c->main_idle = true; }
+void main_enqueued(fheram_ctx* c) { c->main_idle = false; }
 
 hipEvent_t get_event(fheram_ctx* c) {
     if (!c->ev_pool.empty()) { hipEvent_t e = c->ev_pool.back(); c->ev_pool.pop_back(); return e; }
@@ -412,6 +422,7 @@ int stage_words(fheram_ctx* c, int32_t* d_w, const int64_t* w, int n_ct) {
     if (c->w_busy) { HIPCHK(c, hipEventSynchronize(c->ev_w)); c->w_busy = false; }
     const size_t n = (size_t)n_ct * fheram_ctx::GLWE;
     if (!narrow(w, c->h_w, n)) return fail(c, FHERAM_ERR_RANGE, "limb out of the normalised range [-2^16, 2^16]");
+    main_enqueued(c);
     HIPCHK(c, hipMemcpyAsync(d_w, c->h_w, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipEventRecord(c->ev_w, c->stream));
     c->w_busy = true;

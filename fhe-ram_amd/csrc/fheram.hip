@@ -370,7 +370,7 @@ int fheram_sync(fheram_ctx* c) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
-    c->wide_unsynced = c->derive_unsynced = false;
+    main_waited(c);
     return check_precision(c);
 }
 int fheram_roundoff_max(fheram_ctx* c, double* max_out) {
@@ -481,12 +481,12 @@ namespace {
 // copies ws GLWEs between the context and a caller buffer: device int32 [ws][GLWE] or host int64
 int export_glwes(fheram_ctx* c, const int32_t* src, void* dst, int on_device, size_t n_glwe) {
     const size_t n = n_glwe * fheram_ctx::GLWE;
-    if (on_device) { HIPCHK(c, hipMemcpyAsync(dst, src, n * 4, hipMemcpyDeviceToDevice, c->stream)); return FHERAM_OK; }
+    if (on_device) { main_enqueued(c); HIPCHK(c, hipMemcpyAsync(dst, src, n * 4, hipMemcpyDeviceToDevice, c->stream)); return FHERAM_OK; }
     return download_i64(c, (int64_t*)dst, src, n);
 }
 int import_glwes(fheram_ctx* c, int32_t* dst, const void* src, int on_device, size_t n_glwe) {
     const size_t n = n_glwe * fheram_ctx::GLWE;
-    if (on_device) { HIPCHK(c, hipMemcpyAsync(dst, src, n * 4, hipMemcpyDeviceToDevice, c->stream)); return FHERAM_OK; }
+    if (on_device) { main_enqueued(c); HIPCHK(c, hipMemcpyAsync(dst, src, n * 4, hipMemcpyDeviceToDevice, c->stream)); return FHERAM_OK; }
     return upload_i64(c, dst, (const int64_t*)src, n);
 }
 }  // namespace
@@ -514,6 +514,7 @@ int fheram_read_partial(fheram_ctx* c, const fheram_addr* addr, int prepare_writ
 int fheram_stream_signal(fheram_ctx* c, void* hip_stream) {
     if (!c) return FHERAM_ERR_INVALID_ARG;
     HIPCHK(c, hipSetDevice(c->device));
+    main_enqueued(c);   // (the caller's stream now reads what the main stream wrote: the side stage of a write must not run ahead of it)
     HIPCHK(c, hipEventRecord(c->ev_xout, c->stream));
     HIPCHK(c, hipStreamWaitEvent((hipStream_t)hip_stream, c->ev_xout, 0));
     return FHERAM_OK;
@@ -522,6 +523,7 @@ int fheram_stream_wait(fheram_ctx* c, void* hip_stream) {
     if (!c) return FHERAM_ERR_INVALID_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipEventRecord(c->ev_xin, (hipStream_t)hip_stream));
+    main_enqueued(c);
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_xin, 0));
     return FHERAM_OK;
 }
@@ -697,7 +699,7 @@ int fheram_timer_end(fheram_ctx* c, float* ms) {
     HIPCHK(c, hipEventRecord(c->t1, c->stream));
     HIPCHK(c, hipEventSynchronize(c->t1));
     HIPCHK(c, hipEventElapsedTime(ms, c->t0, c->t1));
-    c->wide_unsynced = c->derive_unsynced = false;   // (t1 was recorded behind everything enqueued on the main stream)
+    main_waited(c);   // (t1 was recorded behind everything enqueued on the main stream)
     return check_precision(c);
 }
 int fheram_profile_enable(fheram_ctx* c, int on) {

@@ -12,7 +12,7 @@
 //   k_keyswitch_chain / k_ext_product_chain(_r)  the same chains on their own; k_pair_z  the column-split packer combine
 //   k_trace_tail / k_chain_mid  dependent chains on few ciphertexts with in-kernel hand-offs between workgroups of one XCD (k_trace_tail: coordinate 1's
 //                  products in front of the trace, round 6)
-//   chain_kernels.inc           k_keyswitch_chain / k_read_chain in two register budgets (included twice: 240 registers beside the gate wave, 256 otherwise;
+//   chain_kernels.inc           k_keyswitch_chain / k_read_chain in two register budgets (included twice: 248 registers beside the gate wave, 256 otherwise;
 //                               once more for k_read_chain_t, the read chain over several addresses: RowChainTableArgs)
 //   write_chain.inc             k_write_chain, and k_write_chain_t with a per-member operand table (fheram_bank_write)
 //   trace_tail.inc              k_trace_tail, and k_trace_tail_t with per-address products (several addresses)
@@ -279,10 +279,14 @@ __device__ __forceinline__ void mac_regs(double (&acc)[E], const double (&x)[E],
 // (BI = 1: the `for (b < BI)` loops of the two limb loops run once.  Written out as straight-line code they compile to
 // different device code, so they stay as they are until a change that is measured: DESIGN.md 10.3.)
 constexpr int BF = 3, BI = 1;
-// Register cap of the chain kernels (see k_keyswitch_chain): one workgroup per CU, two waves per SIMD; above 240 registers the
+// Register cap of the chain kernels (see k_keyswitch_chain): one workgroup per CU, two waves per SIMD; from 249 registers on the
 // two waves leave no room for the one-wave gate launch of read_prepare_write and the workgroup stays off that CU.
+// 248: a SIMD's file is 512 registers, allocated in units of 8; two waves of 248 leave 16, and the gate wave (k_tail_gate) needs ONE unit —
+// which is a requirement on that kernel, written down beside it and read off the build's resource report (make resource-usage).
+// (240 until round 7: k_read_chain<4,4> 93 -> 71 spilled registers, k_pair_z<4> 6 -> 0; no launch of read_prepare_write takes a second
+// round, profiles/r07_timeline.txt.)
 #ifndef FK_CHAIN_VGPRS
-#define FK_CHAIN_VGPRS 120   // the attribute counts in units of two on gfx90a+ (unified VGPR + AGPR file): 120 -> 240 registers: two waves leave 32 registers of a SIMD for a small third one
+#define FK_CHAIN_VGPRS 124   // the attribute counts in units of two on gfx90a+ (unified VGPR + AGPR file): 124 -> 248 registers: two waves leave 16 registers of a SIMD for a small third one
 #endif
 // ... and the same kernels with the whole register file (128 -> 256 registers), for the launches that can never meet the gate wave: it is
 // parked by read_prepare_write only, so Ram::read and Ram::write run the wide variants (k_read_chain<4,4>: 89 -> 19 spilled registers,
@@ -1597,7 +1601,8 @@ struct KsChainArgs {
 // Register budget: one workgroup per CU, two waves per SIMD.  At 249+ registers the two waves take a SIMD's whole register
 // file, and ANY other wave resident on the CU — the one-wave gate launch that read_prepare_write parks on the side stream is
 // enough — keeps the workgroup off that CU: a 256-workgroup launch on 256 CUs then runs in two rounds (+0.24 ms per
-// read_prepare_write, measured when the Y-form kernel first compiled to 250).  Capped so that a small wave still fits.
+// read_prepare_write, measured when the Y-form kernel first compiled to 250).  Capped at 248 (FK_CHAIN_VGPRS), so that a wave of at most
+// 8 registers — one allocation unit — still fits.
 // ---------------------------------------------------------------------------------------
 // k_pair_z (round 4): the packer combine (GLWEPacker, ram.rs:435,514; KS_PAIR of ks_run) split by output column, in the closed
 // form of ks_trace_z.  With A(v) = v_0 2^34 + v_1 2^17 + v_2 the integer a coefficient's limbs stand for and a' = rot(a, -t):
@@ -1751,6 +1756,10 @@ struct RowChainArgs {
     KsChainArgs ks;
     GlweRef hi, trhi;      // k_write_chain: the rows (ct_hi) and trace(ct_hi)
     int store_ep = 0;      // k_read_chain: the products' result is also stored (in-place products of read_prepare_write)
+    // k_write_chain: tree.p != nullptr: the workgroup of row 0 of every word also writes tree[y] = ct_lo[y] * X^tree_rho (ram.rs:629: the tree's copy
+    // of ct_lo, rotated by -rows), from the very ct_lo its first step is about to read — once per launch, in front of the step loop
+    GlweRef tree = {nullptr, 0, 0};
+    int tree_rho = 0;
 };
 // (defined in chain_kernels.inc, which is included twice: k_keyswitch_chain / k_read_chain capped at FK_CHAIN_VGPRS registers for the launches that may
 // meet the gate wave, k_keyswitch_chain_w / k_read_chain_w with the whole register file for those that cannot — the attribute wants a literal,
@@ -1856,6 +1865,9 @@ constexpr int TAIL_GROUPS = 8;
 // the address's digits behind a fheram_address_derive launch by ev_opstart, ctx.hpp derive_unsynced).  An event recorded on the main stream for the same
 // purpose delays the launch behind it by 7-13 us; a stream wait-value makes the command processor poll (slower still).
 constexpr int GATE_SPIN_MAX = 1 << 13;
+// REGISTERS: at most 8 VGPRs (one allocation unit; today 2).  The chain kernels it is parked beside are capped at 248 of a SIMD's 256 per wave
+// (FK_CHAIN_VGPRS): with 9 or more here, their workgroups would stay off the gate's CU and a 256-workgroup launch would take two rounds.  The
+// attribute cannot be asserted in the source: `make resource-usage` prints this kernel's count, and it is checked there.
 #ifndef FK_NO_PLAIN_KERNELS   // (cmux_chain.hip: a second translation unit takes the helpers and templates only)
 __global__ __launch_bounds__(64) void k_tail_gate(const unsigned* gate, unsigned seq) {
     if (threadIdx.x != 0) return;

@@ -72,18 +72,23 @@ void launch_ep(fheram_ctx* c, GlweRef a, GlweRef res, const double* ggsw, int gx
         hipLaunchKernelGGL((k_ext_product<3, 4, 2>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, a, res, ggsw, c->d_tw, big_of(c));
     }
 }
+// beside: the launch runs beside a latency-bound launch of the main stream and nothing waits for it soon (read_prepare_write's early inverse
+// digits, next to the trace tail): sized for its FOOTPRINT, not its latency — not the fine split (2 * SK * SX workgroups per ciphertext, which
+// take the CUs and the L2 the tail's groups hand over through), but the decomposition with the fewest workgroups that still ends in time: the
+// column split, 2 workgroups per ciphertext and no normalisation launch.  (Measured at 2^18 x 4, profiles/r07_experiments.txt 2: coordinate 1's
+// digits are ready 60 us before the op's last launch ends, coordinate 0's as the op ends; the limb-parallel form left the tail as slow as the fine one.)
 template <int MODE, int SX, int SK, int SO>
-void launch_ks(fheram_ctx* c, const KsArgs& ka, int gx, int gy) {
+void launch_ks(fheram_ctx* c, const KsArgs& ka, int gx, int gy, bool beside = false) {
     if (gx <= 0 || gy <= 0) return;
     ProfScope ps(c, "keyswitch", (uint64_t)gx * gy);
-    if (use_fine_split(c, gx, gy, 2 * SK * SX)) {
+    if (!beside && use_fine_split(c, gx, gy, 2 * SK * SX)) {
         KsArgs kb = ka;
         kb.big = big_of(c);
         hipLaunchKernelGGL((k_keyswitch_fine<MODE, SX, SK>), dim3(gx, gy, 2 * SK * SX), dim3(T), LDS_BYTES, c->cur, kb);
         hipLaunchKernelGGL((k_keyswitch_norm<MODE, SX, SK, SO, SX>), dim3(gx, gy, 2 * (N / 256)), dim3(256), 0, c->cur, kb);
         return;
     }
-    if (use_limb_split(c, gx, gy, SK)) {
+    if (!beside && use_limb_split(c, gx, gy, SK)) {
         KsArgs kb = ka;
         kb.big = big_of(c);
         hipLaunchKernelGGL((k_keyswitch<MODE, SX, SK, SO, 1, 1>), dim3(gx, gy, 2 * SK), dim3(T), LDS_BYTES, c->cur, kb);
@@ -373,7 +378,9 @@ void launch_read_chain(fheram_ctx* c, GlweRef src, const GlweRef* ep_store, Glwe
 }
 // write: trace steps 0 .. n_tr-1 of ct_lo * X^-row (src, read rotated), data <- normalize(data - trhi + that), d products in place
 // with a table (a bank range: every member its own rows): row y takes the inverse digits of member y / t.ws (k_write_chain_t, which reads no map)
-void launch_write_chain(fheram_ctx* c, GlweRef src, int rot_mul, int rot_base, GlweRef data, GlweRef trhi, const double* prep, int d, int n_tr, int gx, int gy, const OpndTable& t) {
+// tree != nullptr: the workgroup of row 0 of every y also writes (*tree)[y] = src[y] * X^tree_rho (the tree's rotated copy of ct_lo: no k_rotate launch behind)
+void launch_write_chain(fheram_ctx* c, GlweRef src, int rot_mul, int rot_base, GlweRef data, GlweRef trhi, const double* prep, int d, int n_tr, int gx, int gy, const OpndTable& t,
+                        const GlweRef* tree = nullptr, int tree_rho = 0) {
     ProfScope ps(c, "write_chain_launch", (uint64_t)gx * gy, 1);
     RowChainArgs ra;
     fill_row_chain(c, ra, prep, d, 0, n_tr);
@@ -381,6 +388,7 @@ void launch_write_chain(fheram_ctx* c, GlweRef src, int rot_mul, int rot_base, G
     ra.ks.buf[0] = ra.ks.buf[1] = data;                           // (no trace step stores)
     ra.hi = data; ra.trhi = trhi;
     ra.ep.src = data; ra.ep.buf[0] = ra.ep.buf[1] = data;         // only the last product stores: in place on the rows
+    if (tree) { ra.tree = *tree; ra.tree_rho = tree_rho; }
     c->wide_unsynced = true;                                      // (k_write_chain takes the whole register file)
     with_evk(c, [&](auto sk) {
         constexpr int SK = decltype(sk)::value;
@@ -523,19 +531,19 @@ void coordinate_prepare_all(fheram_ctx* c, const fheram_addr* addr, double* tabl
     launch_prepare(c, addr->d_ggsw, table, c->n_digits * (int)(fheram_ctx::GGSW / N));
 }
 // CoordinatePrepared::prepare_inv (coordinate_prepared.rs:121-142): GGSW(X^i) -> GGSW(X^-i).
-void ggsw_inverse(fheram_ctx* c, const int32_t* in, int32_t* tmp, int d) {
+void ggsw_inverse(fheram_ctx* c, const int32_t* in, int32_t* tmp, int d, bool beside = false) {
     const long g4 = (long)fheram_ctx::GLWE4;
     int32_t* inp = const_cast<int32_t*>(in);
     // GGSW::automorphism, column 0 of every row: res[r][0] = phi_-1(KS(in[r][0]))
     KsArgs ka = ks_args(c, ref(inp, (long)fheram_ctx::GGSW, 2 * g4), ref(inp, 0, 0), ref(tmp, (long)fheram_ctx::GGSW, 2 * g4), c->d_atk_inv, -1);
-    launch_ks<KS_AUTO, 4, 5, 4>(c, ka, fheram_ctx::DNUM_CT, d);
+    launch_ks<KS_AUTO, 4, 5, 4>(c, ka, fheram_ctx::DNUM_CT, d, beside);
     // row expansion with the tensor key: res[r][1] = KS_tsk(res[r][0].mask) + (0, res[r][0].body)
     KsArgs kt = ks_args(c, ref(tmp, (long)fheram_ctx::GGSW, 2 * g4), ref(tmp, 0, 0), ref(tmp + g4, (long)fheram_ctx::GGSW, 2 * g4), c->d_tsk, 1);
-    launch_ks<KS_TENSOR, 4, 5, 4>(c, kt, fheram_ctx::DNUM_CT, d);
+    launch_ks<KS_TENSOR, 4, 5, 4>(c, kt, fheram_ctx::DNUM_CT, d, beside);
 }
-void coordinate_prepare_inv(fheram_ctx* c, const fheram_addr* addr, int ci, int32_t* tmp, double* prep) {
+void coordinate_prepare_inv(fheram_ctx* c, const fheram_addr* addr, int ci, int32_t* tmp, double* prep, bool beside = false) {
     const int d = (int)c->base2d[ci].size();
-    ggsw_inverse(c, addr->d_ggsw + (size_t)coord_first_digit(c, ci) * fheram_ctx::GGSW, tmp, d);
+    ggsw_inverse(c, addr->d_ggsw + (size_t)coord_first_digit(c, ci) * fheram_ctx::GGSW, tmp, d, beside);
     launch_prepare(c, tmp, prep, d * (int)(fheram_ctx::GGSW / N));
 }
 
@@ -561,7 +569,7 @@ void precompute_inverse(fheram_ctx* c, const fheram_addr* addr, int ci, bool for
     }
     hipStream_t keep = c->cur;
     c->cur = c->stream2;
-    coordinate_prepare_inv(c, addr, ci, c->d_ggsw_inv + (size_t)coord_first_digit(c, ci) * fheram_ctx::GGSW, digits_of(c, c->d_prep_inv, ci));
+    coordinate_prepare_inv(c, addr, ci, c->d_ggsw_inv + (size_t)coord_first_digit(c, ci) * fheram_ctx::GGSW, digits_of(c, c->d_prep_inv, ci), true);
     hipEventRecord(c->ev_inv[ci], c->stream2);
     c->cur = keep;
     c->inv_id[ci] = addr->id;

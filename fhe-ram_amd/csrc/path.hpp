@@ -78,6 +78,7 @@ void write_done(fheram_ctx* c, RamState* st) { st->memo_top = false; st->memo_al
 template <typename F>
 int run_op(fheram_ctx* c, const fheram_addr* addr, int which, F&& enqueue) {
     if (!capturing(c)) return enqueue();
+    main_enqueued(c);   // (a replay runs no enqueue function)
     fheram_addr* a = const_cast<fheram_addr*>(addr);
     // what the enqueue function reads of the context's mutable state (a write resumes from what read_prepare_write kept —
     // or not, after a key load or with another address): a capture taken under another signature is not replayed
@@ -122,6 +123,7 @@ int check_common(fheram_ctx* c, const fheram_addr* addr) {
 int read_local(const Opnds& o, const RamView& a, bool prepare_write, GlweRef* packed_out, bool to_part) {
     fheram_ctx* c = o.c;
     const int n = o.n, ws = o.ws, Y = o.Y(), R = (int)c->rows;
+    main_enqueued(c);
     c->wide = !prepare_write || n > 1;   // read_prepare_write parks the gate wave beside its launches (read_top): its chain kernels keep a wave slot free; several addresses never park one
     if (n == 1 && prepare_write && c->cfg.pre_inv == 1 && !capturing(c) && (c->wide_unsynced || c->derive_unsynced)) {   // the gate wave may not be parked before this op's own launches start, nor its work read digits a derive launch is still writing (ctx.hpp: ev_opstart)
         hipEventRecord(c->ev_opstart, c->stream);
@@ -171,6 +173,7 @@ int read_local(const Opnds& o, const RamView& a, bool prepare_write, GlweRef* pa
 int read_top(const Opnds& o, const RamView& a, bool prepare_write, int32_t* gathered, GlweRef pk) {
     fheram_ctx* c = o.c;
     const int n = o.n, ws = o.ws, Y = o.Y();
+    main_enqueued(c);
     c->wide = !prepare_write || n > 1;
     const long G = (long)fheram_ctx::GLWE;
     GlweRef tmp = ref(a.tmp, G, 0);
@@ -302,7 +305,7 @@ int result_export(fheram_ctx* c, const ResRun* runs, int n_runs, int64_t* h, int
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
-    c->wide_unsynced = c->derive_unsynced = false;
+    main_waited(c);
     double m;
     std::memcpy(&m, h + n, 8);
     if (c->cfg.monitor && m > MON_LIMIT) __atomic_store_n(c->h_ro_flag, 1u, __ATOMIC_RELAXED);
@@ -336,6 +339,7 @@ int read_many(fheram_ctx* c, ReadBufs& L, RamState* st, const fheram_addr* const
 // coordinate-1 products: leaves the un-rotated ct_lo of every sub-RAM in d_part.
 int write_top(const Opnds& o, const RamView& v) {
     fheram_ctx* c = o.c;
+    main_enqueued(c);
     c->wide = true;             // (everything a write enqueues runs behind read_prepare_write's trace chain, whose placement releases the gate wave)
     const long G = (long)fheram_ctx::GLWE;
     const long sy = (long)c->rows * G;
@@ -378,8 +382,15 @@ void write_side_begin(const Opnds& o, const RamView& v) {
     c->wide = true;
     const long G = (long)fheram_ctx::GLWE;
     const long sy = (long)c->rows * G;
-    hipEventRecord(c->ev_fork, c->stream);            // everything before this write (rows after rpw)
-    hipStreamWaitEvent(c->stream2, c->ev_fork, 0);
+    // behind everything before this write (rows after rpw) — unless the host has waited for the main stream since its last enqueue
+    // (ctx.hpp main_idle): then there is nothing to fork from, and what the side stream still holds (the early inverse digits behind
+    // ev_wdone, their ev_inv) it orders itself.  A capture needs the fork to pull the side stream in; a shard of a row-sharded RAM keeps it
+    // (its main stream also carries the exchange with the other contexts, which this context's host waits do not cover).
+    if (!(c->main_idle && !capturing(c) && c->n_shards == 1)) {
+        hipEventRecord(c->ev_fork, c->stream);
+        hipStreamWaitEvent(c->stream2, c->ev_fork, 0);
+    }
+    main_enqueued(c);   // (the write this belongs to enqueues on the main stream next; a second side stage forks again)
     c->cur = c->stream2;
     if (c->n2 == 2) {                                 // every row of every address: ONE chain
         const int kept = o.st->memo_alone;   // > 0: arena A = the rows after trace steps 0 .. kept-1 (left there by read_prepare_write)
@@ -405,6 +416,7 @@ void write_side_abort(fheram_ctx* c) {
 // Stage 2 (every shard): write_mid_step on the local rows given ct_lo (in d_part), then write_last_step.
 int write_rows(const Opnds& o, const RamView& v) {
     fheram_ctx* c = o.c;
+    main_enqueued(c);
     c->wide = true;
     const long G = (long)fheram_ctx::GLWE;
     const long sy = (long)c->rows * G;
@@ -413,15 +425,19 @@ int write_rows(const Opnds& o, const RamView& v) {
     GlweRef trhi = ref(c->trhi_in_C ? v.C : v.A, sy, G), part = ref(v.part, G, 0);
     const int d0 = (int)c->base2d[0].size();
     const bool fuse = c->n2 == 2 && o.row_fuse(d0, LOGN, R);
+    // unsharded, the fused chain's workgroups of row 0 write the tree's rotated copy of ct_lo themselves (they read ct_lo anyway): a launch less
+    // behind the chain, for which the host waits.  A root's rows are every n_shards-th: it keeps the launch.
+    const bool rot_in_chain = fuse && c->tree_rotate_pending && c->n_shards == 1;
+    const GlweRef tree = ref(v.tree, G, 0);
     if (fuse) {
         // trace(ct_lo * X^-row), normalize(ct_hi - trace(ct_hi) + that) and write_last_step's products as ONE launch (k_write_chain; with a table:
         // row y takes the inverse digits of address y / ws); it needs trace(ct_hi) and the inverse digits of coordinate 0 from the side stream at
         // its start (that stream's chain holds every CU until then anyway)
         hipStreamWaitEvent(c->stream, c->ev_join, 0);
-        launch_write_chain(c, part, c->n_shards, c->shard, data, trhi, o.inv(0, 0), d0, LOGN, R, Y, o.table());   // ram.rs:612-646
+        launch_write_chain(c, part, c->n_shards, c->shard, data, trhi, o.inv(0, 0), d0, LOGN, R, Y, o.table(), rot_in_chain ? &tree : nullptr, -(int)c->rows_glob);   // ram.rs:612-646
     } else if (c->n2 == 2)
         trace_steps(c, part, B, D, 0, LOGN, R, Y, c->n_shards, c->shard);                      // tmp_a = trace(ct_lo * X^-row)   ram.rs:621,629
-    if (c->tree_rotate_pending) {   // root / unsharded: the tree's copy of ct_lo, rotated (see write_top)
+    if (c->tree_rotate_pending && !rot_in_chain) {   // root / unsharded: the tree's copy of ct_lo, rotated (see write_top)
         ProfScope ps(c, "elementwise", Y);
         hipLaunchKernelGGL((k_rotate<3>), dim3(1, Y, EW_SLICES), dim3(256), 0, c->cur, part, ref(v.tree, G, 0), -(int)c->rows_glob);
     }

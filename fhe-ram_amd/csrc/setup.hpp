@@ -569,6 +569,7 @@ int fheram_address_derive(fheram_ctx* c, const fheram_fheuint* const* fus, int n
     // ... and a later read_prepare_write must not let its side work read them before this launch has run: the gate wave in front of that
     // work gives up after a few ms, so the op records ev_opstart behind this launch (ctx.hpp derive_unsynced; read_local / read_top).
     c->derive_unsynced = true;
+    main_enqueued(c);
     return FHERAM_OK;
 }
 

@@ -12,6 +12,17 @@ __global__ __launch_bounds__(T, T / 256) __attribute__((amdgpu_num_vgpr(FK_WIDE_
     extern __shared__ __attribute__((aligned(16))) double lds[];
     RoMonitor ro_mon(lds, ra.ep.tw);
     double vc[E];   // (written by the first step before anything reads it)
+    if (ra.tree.p != nullptr && blockIdx.x == 0) {   // k_rotate's per-coefficient code on T threads: out = a * X^rho, out does not alias a
+        const int32_t* ap = at(ra.ks.base.a);
+        int32_t* op = at(ra.tree);
+        for (int idx = (int)threadIdx.x; idx < 2 * N; idx += T) {
+            const int col = idx >> LOGN, i = idx & (N - 1);
+            int src; bool sgn;
+            rot_src(i, ra.tree_rho, src, sgn);
+#pragma unroll
+            for (int j = 0; j < 3; j++) op[glwe_off(j, col) + i] = cneg(ap[glwe_off(j, col) + src], sgn);
+        }
+    }
     KsArgs ka = ra.ks.base;
 #pragma unroll 1
     for (int i = 0; i < ra.ks.n; i++) {          // n >= 2
