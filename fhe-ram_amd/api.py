@@ -175,6 +175,9 @@ _SYMBOLS = [
     ("fheram_bank_result_download", C.c_int, [C.c_void_p, C.c_int, C.c_int, I64P]),
     ("fheram_bank_read_list", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.c_int, I64P]),
     ("fheram_bank_read_list_result", C.c_int, [C.c_void_p, C.c_int, C.c_int, I64P]),
+    ("fheram_bank_read_prepare_write_list", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.c_int, I64P]),
+    ("fheram_bank_write_list", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.c_int, I64P]),
+    ("fheram_bank_selftest_fail_list_alloc", C.c_int, [C.c_void_p, C.c_int]),
     ("fheram_bank_sync", C.c_int, [C.c_void_p]),
     ("fheram_bank_roundoff_max", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     ("fheram_bank_roundoff_reset", C.c_int, [C.c_void_p]),
@@ -1329,6 +1332,45 @@ class RamBank:
         out = np.zeros((max(n, 1), p.word_size(), p.glwe_len()), dtype=np.int64)
         self._chk(library().fheram_bank_read_list_result(self._h, first, n, _p(out)))
         return out
+
+    def _list_args(self, what, members, addresses):
+        members, addresses = [int(m) for m in members], list(addresses)
+        if not members or len(addresses) != len(members):
+            raise FheRamError(1, f"{what} takes at least one member and as many addresses, got {len(members)} and {len(addresses)}")
+        if not all(isinstance(a, Address) for a in addresses):
+            raise FheRamError(1, "every entry must be an Address (a null address is refused)")
+        n = len(members)
+        return n, (C.c_int * n)(*members), (C.c_void_p * n)(*[a._bank(self) for a in addresses])
+
+    def read_prepare_write_list(self, members, addresses, keys: EvaluationKeysPrepared, download: bool = True):
+        """read_prepare_write of ANY set of members as ONE operation (fheram_bank_read_prepare_write_list), entry k on member members[k] at
+        addresses[k]: distinct members, any order, any subset (a RAM has one pending write, so a member named twice is refused).  int64
+        [n][word_size][GLWE], slice k equal to read_prepare_write([addresses[k]], keys, first=members[k]); every named member is then
+        prepared like any other (write_list, write on a range and result all work on it), members that are not named are untouched.
+        download=False: no host wait (result(first=m, n=1) later)."""
+        n, mem, arr = self._list_args("read_prepare_write_list", members, addresses)
+        self._use_keys(keys)
+        p = self.params
+        out = np.zeros((n, p.word_size(), p.glwe_len()), dtype=np.int64) if download else None
+        self._chk(library().fheram_bank_read_prepare_write_list(self._h, mem, arr, n, _p(out) if download else None))
+        return out
+
+    def write_list(self, members, words, addresses, keys: EvaluationKeysPrepared):
+        """write of ANY set of prepared members as ONE operation (fheram_bank_write_list): words [n][word_size][GLWE], entry k to member
+        members[k] at addresses[k]; the members may have been prepared by a list, a range or single calls.  Never waits for the device."""
+        n, mem, arr = self._list_args("write_list", members, addresses)
+        p = self.params
+        if words is None:
+            raise FheRamError(1, "null words")
+        w = _i64(words)
+        if w.size != n * p.word_size() * p.glwe_len():
+            raise FheRamError(1, f"w.len() != subrams.len() (ram.rs:243): expected {n} x {p.word_size()} GLWEs")
+        self._use_keys(keys)
+        self._chk(library().fheram_bank_write_list(self._h, mem, arr, n, _p(w)))
+
+    def selftest_fail_list_alloc(self, nth: int):
+        """self-test: the nth device allocation the write lists' buffers ask for from now on fails once (0: none)"""
+        self._chk(library().fheram_bank_selftest_fail_list_alloc(self._h, int(nth)))
 
     def derive_addresses(self, fheuints, addrs=None, sign: bool = False):
         """as Ram.derive_addresses, with integers and addresses bound to this bank (FheUintPrepared.from_host(bank, ...),

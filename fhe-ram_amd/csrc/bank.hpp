@@ -22,9 +22,30 @@
 // batch the map 0, 0, ...); the digits sit in a table of the list's own, and every launch writes buffers of the list's own (ReadBufs, the
 // very set a batch has: path.hpp read_many) — so the arenas, trtop and tree of a member that sits between read_prepare_write and write are not touched.  It runs on a scratch RamState; every named member is then left as a
 // read leaves it, with the result of the last entry that named it in its slice of d_res.
+// A WRITE LIST (fheram_bank_read_prepare_write_list / fheram_bank_write_list) is the general read_prepare_write / write: entry k works on
+// member members[k], distinct members in any order (a RAM has one pending write).  The same read_impl / write_side_begin / write_top /
+// write_rows on table_opnds with the members as the map and the bank's d_prep / d_prep_inv (n <= M), over the whole bank's rows: the table
+// chains read AND store the rows through the map (k_read_chain_m / k_write_chain_m, mapped_chains.hip), every launch without a table form goes
+// member by member through Opnds::rows.  Every other buffer of the view is dense, [n * mws], and the lists' own (WriteListBufs) — not the
+// read list's, so that a read list between the two halves destroys nothing.  Per-member hand-over: read_prepare_write copies every entry's
+// tree top and result into the member's own slots and sets its RamState, so ranges, single calls and downloads see a prepared member like
+// any other; a write list gathers tree and trace(top) from those slots and scatters the tree back.  The rows after the alone levels stay in
+// the lists' arena A: they count for a write list of the same members in the same order while every one of them still holds them (wl_holds).
+// A list of one member, or of a contiguous ascending run, IS the range operation.
 // Bank operations are never captured into a hipGraph: under graph = 1 they are enqueued directly, in the forms that mode selects.
 #pragma once
 #include "path.hpp"
+
+// The dense buffers of a read_prepare_write / write list: for `cap` entries of mws ciphertexts, allocated on first use, grown to the largest
+// list seen, freed with the bank.
+struct WriteListBufs {
+    int cap = 0;
+    int32_t *A = nullptr, *B = nullptr, *C = nullptr, *D = nullptr;   // [cap * mws][rows]
+    int32_t *part = nullptr, *tmp = nullptr, *tmp2 = nullptr, *res = nullptr, *tree = nullptr, *w = nullptr, *trtop = nullptr;   // [cap * mws]
+    // what the last read_prepare_write list left in A (RamState::memo_alone of a list): for kept_n entries with the map kept_map
+    int kept_alone = 0, kept_n = 0;
+    unsigned kept_map = 0;
+};
 
 struct fheram_bank {
     fheram_ctx* c = nullptr;      // word count M * mws; never row-sharded, never part of a group
@@ -34,6 +55,9 @@ struct fheram_bank {
     double* d_prep_inv = nullptr; // [n][n_digits] the inverse digits of the k-th address of the range being written      (M > 1)
     ReadBufs list;                // fheram_bank_read_list: buffers of its own (path.hpp reads_reserve), sized by mws
     int list_n = 0;               // entries of the last list (their results are in list.res); 0: none has run
+    WriteListBufs wl;             // fheram_bank_read_prepare_write_list / fheram_bank_write_list: buffers of their own, sized by mws
+    bool wl_holds[FHERAM_BANK_MAX] = {};   // member m is still as the list that filled wl.A left it (cleared by whatever touches the member)
+    int wl_fail_alloc = 0;        // fheram_bank_selftest_fail_list_alloc: the wl_fail_alloc-th next device allocation of wl fails (0: none)
 };
 
 namespace {
@@ -50,7 +74,7 @@ RamView bank_view(const fheram_bank* b, int first) {
 // and address k works on member k of the view
 Opnds bank_opnds(fheram_bank* b, RamState* st, const fheram_addr* const* addrs, int n) {
     if (n == 1) return one_addr(b->c, addrs, b->mws, st);
-    return table_opnds(b->c, st, addrs, n, b->mws, b->d_prep, b->d_prep_inv, SRC_MAP_IDENTITY, true);
+    return table_opnds(b->c, st, addrs, n, b->mws, b->d_prep, b->d_prep_inv, MEMBER_MAP_IDENTITY, true);
 }
 
 // ---- checks: the whole range (or list) before anything is enqueued --------------------------------------------------------------------
@@ -96,6 +120,7 @@ void bank_assign(fheram_bank* b, int first, int n, const RamState& s, bool state
         RamState& r = b->ram[m];
         r.state = state; r.memo_top = s.memo_top; r.memo_alone = s.memo_alone;
         if (new_result) r.res_in_trtop = s.res_in_trtop;
+        b->wl_holds[m] = false;
     }
 }
 // the results of members [first, first + n), widened into h_res by the device; out: [n][mws][GLWE] int64
@@ -153,6 +178,80 @@ int list_check(fheram_bank* b, const int* members, const fheram_addr* const* add
 }
 int list_result(fheram_bank* b, int first, int n, int64_t* out) { return reads_export(b->c, b->list, (size_t)first * b->mws, (size_t)n * b->mws, out); }
 
+// ---- the write lists -------------------------------------------------------------------------------------------------------------
+void wlist_free(WriteListBufs& L) {
+    void* bufs[] = {L.A, L.B, L.C, L.D, L.part, L.tmp, L.tmp2, L.res, L.tree, L.w, L.trtop};
+    for (void* p : bufs) if (p) hipFree(p);
+    L = WriteListBufs{};
+}
+// grows the buffers to n entries of ws ciphertexts; on failure the bank holds none of them (and every other operation is unaffected: what a
+// prepared member needs for its write is in its own slots).  Regrowing drops the kept arena, never a member's state.
+int wlist_reserve(fheram_ctx* c, WriteListBufs& L, int n, int ws, int* fail_alloc) {
+    if (n <= L.cap) return FHERAM_OK;
+    if (L.cap) { for (hipStream_t s : {c->stream, c->stream2}) HIPCHK(c, hipStreamSynchronize(s)); wlist_free(L); }
+    const size_t G = fheram_ctx::GLWE, nct = (size_t)n * ws, nrow = nct * c->rows;
+    hipError_t e = hipSuccess;
+    auto dev = [&](int32_t** p, size_t glwes) {
+        if (e != hipSuccess) return;
+        if (*fail_alloc > 0 && --*fail_alloc == 0) e = hipErrorOutOfMemory;   // (the self-test's: as the runtime reports an exhausted device)
+        else e = hipMalloc((void**)p, glwes * G * sizeof(int32_t));
+    };
+    for (int32_t** p : {&L.A, &L.B, &L.C, &L.D}) dev(p, nrow);
+    for (int32_t** p : {&L.part, &L.tmp, &L.tmp2, &L.res, &L.tree, &L.w, &L.trtop}) dev(p, nct);
+    if (e != hipSuccess) {
+        wlist_free(L);
+        (void)hipGetLastError();   // the next op's error check must not see this allocation's failure
+        return fail(c, FHERAM_ERR_DEVICE, std::string("buffers of a write list of ") + std::to_string(n) + " members: " + hipGetErrorString(e));
+    }
+    L.cap = n;
+    return FHERAM_OK;
+}
+RamView wlist_view(const fheram_bank* b) {
+    const WriteListBufs& L = b->wl;
+    return RamView{b->c->d_data, L.A, L.B, L.C, L.D, L.part, L.tmp, L.tmp2, L.res, L.tree, L.w, L.trtop};
+}
+unsigned wlist_map(const int* members, int n) {
+    unsigned map = 0;
+    for (int k = 0; k < n; k++) map |= (unsigned)members[k] << (4 * k);
+    return map;
+}
+// a list of one member or of a contiguous ascending run is the range [members[0], members[0] + n)
+bool wlist_is_range(const int* members, int n) {
+    for (int k = 1; k < n; k++) if (members[k] != members[0] + k) return false;
+    return true;
+}
+// the whole list before anything is enqueued; codes, order and messages as list_check.  want_state: 0 read_prepare_write, 1 write
+int wlist_check(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n, bool null_words, int want_state) {
+    if (!b) return FHERAM_ERR_INVALID_ARG;
+    fheram_ctx* c = b->c;
+    mid_rearm(c);
+    if (!members || !addrs || null_words) return fail(c, FHERAM_ERR_INVALID_ARG, want_state ? "null member list, null address list or null words" : "null member list or null address list");
+    if (n < 1 || n > b->M)
+        return fail(c, FHERAM_ERR_INVALID_ARG, "n = " + std::to_string(n) + " is outside [1, the bank's " + std::to_string(b->M) + " members]");
+    unsigned seen = 0;
+    for (int k = 0; k < n; k++) {
+        if (members[k] < 0 || members[k] >= b->M)
+            return fail(c, FHERAM_ERR_INVALID_ARG, "entry " + std::to_string(k) + " names member " + std::to_string(members[k]) + ", outside the bank's " + std::to_string(b->M) + " members");
+        if (seen & (1u << members[k]))
+            return fail(c, FHERAM_ERR_INVALID_ARG, "entry " + std::to_string(k) + " names member " + std::to_string(members[k]) + " a second time: a RAM has one pending write (ram.rs:196-294), so the members of a write list are distinct");
+        seen |= 1u << members[k];
+    }
+    const int rc = check_addrs(c, addrs, n);
+    if (rc != FHERAM_OK) return rc;
+    for (int k = 0; k < n; k++)
+        if (!b->ram[members[k]].initialized) return fail(c, FHERAM_ERR_UNINITIALIZED, "unitialized memory: self.data.len()=0 (member " + std::to_string(members[k]) + ")");
+    if (!c->keys_loaded) return fail(c, FHERAM_ERR_KEYS, "evaluation keys not loaded");
+    for (int k = 0; k < n; k++) {
+        if (want_state == 0 && b->ram[members[k]].state)
+            return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.read: internal state is true -> requires calling Memory.write (member " + std::to_string(members[k]) + ")");
+        if (want_state == 1 && !b->ram[members[k]].state)
+            return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.write: internal state is false -> requires calling Memory.read_prepare_write (member " + std::to_string(members[k]) + ")");
+    }
+    return FHERAM_OK;
+}
+// member m's [mws] slot of a per-ciphertext buffer of the context
+GlweRef member_slot(const fheram_bank* b, int32_t* buf, int m) { return ref(buf + (size_t)m * b->mws * fheram_ctx::GLWE, (long)fheram_ctx::GLWE, 0); }
+
 }  // namespace
 
 extern "C" {
@@ -193,6 +292,7 @@ void fheram_bank_destroy(fheram_bank* b) {
     if (!b) return;
     if (b->c) { hipSetDevice(b->c->device); for (hipStream_t s : {b->c->stream, b->c->stream2}) if (s) hipStreamSynchronize(s); }
     reads_free(b->list);
+    wlist_free(b->wl);
     fheram_ctx_destroy(b->c);
     delete b;
 }
@@ -204,7 +304,7 @@ int fheram_bank_keys_load(fheram_bank* b, const int64_t* gal_els, int n_gal, con
     if (!b) return FHERAM_ERR_INVALID_ARG;
     const int rc = fheram_keys_load(b->c, gal_els, n_gal, atk_glwe, atk_ggsw_inv, atk_ggsw_inv_p, tsk);
     if (rc != FHERAM_OK) return rc;
-    for (int m = 0; m < b->M; m++) { b->ram[m].memo_top = false; b->ram[m].memo_alone = 0; }   // kept traces are void with new keys
+    for (int m = 0; m < b->M; m++) { b->ram[m].memo_top = false; b->ram[m].memo_alone = 0; b->wl_holds[m] = false; }   // kept traces are void with new keys
     return FHERAM_OK;
 }
 int fheram_bank_ram_upload(fheram_bank* b, int member, const int64_t* rows) {
@@ -218,6 +318,7 @@ int fheram_bank_ram_upload(fheram_bank* b, int member, const int64_t* rows) {
     if (rc != FHERAM_OK) return rc;
     RamState& r = b->ram[member];
     r.initialized = true; r.state = false; r.memo_top = false; r.memo_alone = 0;
+    b->wl_holds[member] = false;
     return FHERAM_OK;
 }
 int fheram_bank_ram_download(fheram_bank* b, int member, int64_t* rows) {
@@ -333,6 +434,100 @@ int fheram_bank_read_list(fheram_bank* b, const int* members, const fheram_addr*
         }
         b->list_n = n;
     });
+}
+// n independent Ram::read_prepare_write (ram.rs:196-222), entry k on member members[k], as one operation (header comment: a write list).
+int fheram_bank_read_prepare_write_list(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n, int64_t* out) {
+    int rc = wlist_check(b, members, addrs, n, false, 0);
+    if (rc != FHERAM_OK) return rc;
+    if (wlist_is_range(members, n)) return bank_read_op(b, members[0], n, addrs, true, out);
+    fheram_ctx* c = b->c;
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = wlist_reserve(c, b->wl, n, b->mws, &b->wl_fail_alloc);
+    if (rc != FHERAM_OK) return rc;
+    WriteListBufs& L = b->wl;
+    L.kept_alone = 0;   // arena A is this list's from here on
+    RamState st{true, false, false, 0, false};
+    const Opnds o = table_opnds(c, &st, addrs, n, b->mws, b->d_prep, b->d_prep_inv, wlist_map(members, n), true);
+    rc = read_impl(o, wlist_view(b), true);
+    if (rc != FHERAM_OK) return rc;
+    // the hand-over: tree top and result into every member's own slots, where a range, a single call or a download looks for them
+    const long G = (long)fheram_ctx::GLWE;
+    ResRun runs[FHERAM_BANK_MAX];
+    for (int k = 0; k < n; k++) {
+        const int m = members[k];
+        if (c->n2 == 2) launch_copy(c, o.slice(ref(L.tree, G, 0), k), member_slot(b, c->d_tree, m), 1, b->mws);
+        int32_t* res_to = st.res_in_trtop ? c->d_trtop : c->d_res;
+        launch_copy(c, o.slice(ref(st.res_in_trtop ? L.trtop : L.res, G, 0), k), member_slot(b, res_to, m), 1, b->mws);
+        RamState& r = b->ram[m];
+        r.state = true; r.memo_top = st.memo_top; r.memo_alone = 0; r.res_in_trtop = st.res_in_trtop;   // (memo_alone is the context's arena: not this list's)
+        b->wl_holds[m] = st.memo_alone > 0;
+        runs[k] = ResRun{member_slot(b, res_to, m).p, (size_t)b->mws * fheram_ctx::GLWE};
+    }
+    L.kept_alone = st.memo_alone; L.kept_n = n; L.kept_map = o.member_map;
+    HIPCHK(c, hipGetLastError());
+    return out ? result_export(c, runs, n, c->h_res, c->d_h_res, out) : FHERAM_OK;
+}
+// n independent Ram::write (ram.rs:226-294), entry k of w to member members[k], as one operation (header comment: a write list).
+int fheram_bank_write_list(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n, const int64_t* w) {
+    int rc = wlist_check(b, members, addrs, n, !w, 1);
+    if (rc != FHERAM_OK) return rc;
+    if (wlist_is_range(members, n)) return fheram_bank_write(b, members[0], n, w, addrs);
+    fheram_ctx* c = b->c;
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = wlist_reserve(c, b->wl, n, b->mws, &b->wl_fail_alloc);
+    if (rc != FHERAM_OK) return rc;
+    WriteListBufs& L = b->wl;
+    const unsigned map = wlist_map(members, n);
+    // what the write resumes from: trace(top) when every member holds its own, the kept arena when it is this very list's
+    RamState st{true, true, true, 0, false};
+    bool holds = L.kept_alone > 0 && L.kept_n == n && L.kept_map == map;
+    for (int k = 0; k < n; k++) {
+        st.memo_top = st.memo_top && b->ram[members[k]].memo_top;
+        holds = holds && b->wl_holds[members[k]];
+    }
+    if (holds) st.memo_alone = L.kept_alone;
+    L.kept_alone = 0;   // consumed, or overwritten by this write's trace(ct_hi)
+    const Opnds o = table_opnds(c, &st, addrs, n, b->mws, b->d_prep, b->d_prep_inv, map, true);
+    const RamView v = wlist_view(b);
+    const long G = (long)fheram_ctx::GLWE;
+    // The gather: every member's tree top and trace(top) into the list's dense buffers — unless this very list prepared the members and
+    // all still hold it (holds): then L.tree and L.trtop are what the hand-over copied FROM, nothing has written them since (every list
+    // operation ends `holds`), no launch is needed, and write_side_begin may skip its fork event after a host wait as fheram_bank_write's
+    // does (main_idle).  With a gather the main stream has work again, so the side stage forks behind it: one event record.
+    if (!holds) {
+        main_enqueued(c);
+        for (int k = 0; k < n; k++) {
+            if (c->n2 == 2) launch_copy(c, member_slot(b, c->d_tree, members[k]), o.slice(ref(L.tree, G, 0), k), 1, b->mws);
+            if (st.memo_top) launch_copy(c, member_slot(b, c->d_trtop, members[k]), o.slice(ref(L.trtop, G, 0), k), 1, b->mws);
+        }
+    }
+    auto assign = [&](bool state) {
+        for (int k = 0; k < n; k++) {
+            RamState& r = b->ram[members[k]];
+            r.state = state; r.memo_top = st.memo_top; r.memo_alone = 0;
+            b->wl_holds[members[k]] = false;
+        }
+    };
+    write_side_begin(o, v);
+    rc = stage_words(c, v.w, w, n * b->mws);
+    if (rc != FHERAM_OK) {                          // (a limb out of range: nothing of the members has been touched)
+        write_side_abort(c);
+        assign(true);
+        return rc;
+    }
+    rc = write_top(o, v);
+    if (rc == FHERAM_OK) rc = write_rows(o, v);
+    if (rc == FHERAM_OK && c->n2 == 2)              // the scatter: the tree's new top (ct_lo, rotated) back into every member's slot
+        for (int k = 0; k < n; k++) launch_copy(c, o.slice(ref(L.tree, G, 0), k), member_slot(b, c->d_tree, members[k]), 1, b->mws);
+    assign(rc != FHERAM_OK);                                                                // ram.rs:648
+    if (rc != FHERAM_OK) return rc;
+    HIPCHK(c, hipGetLastError());
+    return FHERAM_OK;
+}
+int fheram_bank_selftest_fail_list_alloc(fheram_bank* b, int nth) {
+    if (!b || nth < 0) return FHERAM_ERR_INVALID_ARG;
+    b->wl_fail_alloc = nth;
+    return FHERAM_OK;
 }
 int fheram_bank_read_list_result(fheram_bank* b, int first, int n, int64_t* out) {
     if (!b) return FHERAM_ERR_INVALID_ARG;

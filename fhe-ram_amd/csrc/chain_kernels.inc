@@ -1,6 +1,7 @@
 // Included by kernels.hpp (no include guard): the chain kernels that exist in two register budgets.
 //   FK_KS_CHAIN_NAME / FK_READ_CHAIN_NAME : kernel names;  FK_VG : the literal for amdgpu_num_vgpr (units of two registers)
-//   FK_READ_CHAIN_ARGS / FK_READ_CHAIN_TABLE : RowChainArgs / 0, or RowChainTableArgs / 1 for the read chain over several addresses
+//   FK_READ_CHAIN_ARGS / FK_READ_CHAIN_TABLE : RowChainArgs / 0, or RowChainTableArgs / 1 for the read chain over several addresses (the
+//   source row through the member map), / 2 for that of a read_prepare_write list (the store_ep row through it as well)
 //   (that inclusion defines no FK_KS_CHAIN_NAME: the trace chain has no table form)
 #ifdef FK_KS_CHAIN_NAME
 // GLWE::trace(start, start + n) as ONE launch (see KsChainArgs in kernels.hpp)
@@ -68,13 +69,19 @@ __global__ __launch_bounds__(T, T / 256) __attribute__((amdgpu_num_vgpr(FK_VG)))
     {
         GlweRef in = ra.ep.src;
 #if FK_READ_CHAIN_TABLE
-        // the source row map(y / ws) * ws + y mod ws and the prepared digits of address y / ws: recomputed where they are used (a few
-        // scalar instructions) rather than kept live across the steps, at this kernel's scalar register pressure
+        // the member's row map(y / ws) * ws + y mod ws (the source, and where store_ep puts the products' result) and the prepared digits of
+        // address y / ws: recomputed where they are used (a few scalar instructions) rather than kept live across the steps, at this
+        // kernel's scalar register pressure
 #define FK_RC_OPND(i) (ra.ep.ggsw[i] + table_opnd_offset(ra))
-#define FK_RC_SRC(a) table_src_row(a, ra)
+#define FK_RC_ROW(a) table_member_row(a, ra)
 #else
 #define FK_RC_OPND(i) ra.ep.ggsw[i]
-#define FK_RC_SRC(a) a
+#define FK_RC_ROW(a) a
+#endif
+#if FK_READ_CHAIN_TABLE == 2
+#define FK_RC_STORE_ROW(a) table_member_row(a, ra)
+#else
+#define FK_RC_STORE_ROW(a) a
 #endif
 #pragma unroll 1
         for (int i = 0; i < ra.ep.n; i++) {      // n >= 2
@@ -82,13 +89,14 @@ __global__ __launch_bounds__(T, T / 256) __attribute__((amdgpu_num_vgpr(FK_VG)))
             int tid = vt((int)threadIdx.x);
             asm volatile("" : "+v"(tid));   // see k_ext_product_chain
             __builtin_assume(tid >= 0 && tid < T);
-            if (i == 0) ep_step_r<SG, 0, 1>(FK_RC_SRC(in), out, FK_RC_OPND(i), ra.ep.tw, lds, true, tid, vc);
+            if (i == 0) ep_step_r<SG, 0, 1>(FK_RC_ROW(in), out, FK_RC_OPND(i), ra.ep.tw, lds, true, tid, vc);
             else if (i + 1 < ra.ep.n) ep_step_r<SG, 1, 1>(in, out, FK_RC_OPND(i), ra.ep.tw, lds, false, tid, vc);
-            else ep_step_r<SG, 1, 3>(in, out, FK_RC_OPND(i), ra.ep.tw, lds, false, tid, vc, false, ra.store_ep != 0);
+            else ep_step_r<SG, 1, 3>(in, FK_RC_STORE_ROW(out), FK_RC_OPND(i), ra.ep.tw, lds, false, tid, vc, false, ra.store_ep != 0);   // (the only store of the products, and only under store_ep)
             in = out;
         }
 #undef FK_RC_OPND
-#undef FK_RC_SRC
+#undef FK_RC_ROW
+#undef FK_RC_STORE_ROW
     }
     KsArgs ka = ra.ks.base;
 #pragma unroll 1

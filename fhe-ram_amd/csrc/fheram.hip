@@ -184,6 +184,7 @@ int fheram_ctx_create_cfg(const fheram_params* p, int device, int shard, int n_s
     LDSATTR((&k_encrypt_sk<4, 0>)); LDSATTR((&k_encrypt_sk<4, 1>));
     LDSATTR((&k_encrypt_sk<5, 0>)); LDSATTR((&k_encrypt_sk<5, 1>));
     CCHK(cmux_chain_register());
+    CCHK(mapped_chains_register());
 #undef LDSATTR_KS
 #undef LDSATTR_KS4
 #undef LDSATTR

@@ -19,6 +19,9 @@
 //   cmux_chain.hip              k_cmux_chain: the CMux chains of Address::set_from_fheuint for K integers as one launch (fheram_address_derive),
 //                               a translation unit of its own (cmux_chain.hpp).  It includes this file for the helpers and templates, so a kernel
 //                               that is NOT a template must sit inside #ifndef FK_NO_PLAIN_KERNELS here (else the two units define it twice: a link error)
+//   mapped_chains.hip           k_read_chain_m / k_write_chain_m: the table row chains with the member map on their stores too (a bank's
+//                               read_prepare_write / write lists), a translation unit of its own likewise (mapped_chains.hpp); the bodies are the two
+//                               .inc files above, included a further time under FK_MAPPED_CHAINS
 //
 // Device GLWE layout: int32 [limb][col][N] (the host's int64 layout narrowed; limbs are
 // normalised to 17 bits so nothing is lost).  Prepared operands: double, transform domain,
@@ -1783,14 +1786,20 @@ struct RowChainArgs {
 #undef FK_READ_CHAIN_ARGS
 #undef FK_READ_CHAIN_TABLE
 // The TABLE form of the row chains: one launch over the rows of n addresses, y = k * ws + w (fheram_read_batch, a range of a bank's members,
-// fheram_bank_read_list).  Entry k = y / ws takes its prepared digits at ep.ggsw[i] + k * opnd_stride and reads the rows of member map(k) of
-// the source: row map(k) * ws + y mod ws.  A batch is the map 0,0,0,... (every entry reads the same rows), a bank range the identity
-// relative to its view, a list any map.  The map travels by value, four bits per entry: no table in device memory.  Instantiations of
-// their own, so that the single-address kernels carry no runtime field for it.
+// fheram_bank_read_list, the write lists).  Entry k = y / ws takes its prepared digits at ep.ggsw[i] + k * opnd_stride and works on the rows
+// of member map(k): row map(k) * ws + y mod ws.  k_read_chain_t applies the map to the source, k_write_chain_t to nothing (a range writes
+// the rows of its own view: the identity); the MAPPED forms k_read_chain_m / k_write_chain_m apply it wherever the chain reads OR writes
+// rows (the source and the in-place products' store; ct_hi and the last product's store) and are what a read_prepare_write / write list
+// of a bank launches.  Everything else stays per y.  A batch is the map 0,0,0,... (every entry reads the same rows; it never stores to
+// them), a bank range the identity relative to its view, a read list any map, a write list any map of distinct members.  The map travels
+// by value, four bits per entry: no table in device memory.  Instantiations of their own, so that the single-address kernels carry no
+// runtime field for it — and the mapped forms of their own, in a translation unit of their own (mapped_chains.hip, under FK_MAPPED_CHAINS),
+// because the mapped store costs k_read_chain_t<4, 4> forty spilled registers: a range, a batch and a read list run the
+// kernels they ran before.
 struct RowChainTableArgs : RowChainArgs {
     long opnd_stride = 0;
     int ws = 1;
-    unsigned src_map = 0;   // the member of entry k in bits [4k, 4k + 4)
+    unsigned member_map = 0;   // the member of entry k in bits [4k, 4k + 4)
 };
 static_assert(FHERAM_READ_BATCH_MAX <= 8 && FHERAM_BANK_MAX <= 8 && FHERAM_READ_LIST_MAX <= 8, "the source map holds eight entries of four bits");
 static_assert(FHERAM_BANK_MAX <= 16, "a member index fits four bits");
@@ -1799,11 +1808,11 @@ __device__ __forceinline__ long table_opnd_offset(const RowChainTableArgs& ra) {
     asm volatile("" : "+v"(y));   // opaque: recomputed at every use, never hoisted out of the step loop and kept live
     return (long)(__builtin_amdgcn_readfirstlane(y) / ra.ws) * ra.opnd_stride;
 }
-__device__ __forceinline__ GlweRef table_src_row(GlweRef a, const RowChainTableArgs& ra) {   // at(a) then reads row map(y / ws) * ws + y mod ws
+__device__ __forceinline__ GlweRef table_member_row(GlweRef a, const RowChainTableArgs& ra) {   // at(a) is then row map(y / ws) * ws + y mod ws, to read or to write
     int y = (int)blockIdx.y;
     asm volatile("" : "+v"(y));   // as table_opnd_offset: wave-uniform scalar work, recomputed where it is used
     const int k = __builtin_amdgcn_readfirstlane(y) / ra.ws;
-    const int m = (int)((ra.src_map >> (4 * k)) & 15u);
+    const int m = (int)((ra.member_map >> (4 * k)) & 15u);
     a.p += (long)((m - k) * ra.ws) * a.sy;   // m * ws + y mod ws - y
     return a;
 }
@@ -1815,13 +1824,21 @@ __device__ __forceinline__ GlweRef table_src_row(GlweRef a, const RowChainTableA
 #define FK_VG FK_WIDE_VGPRS
 #include "chain_kernels.inc"
 #undef FK_READ_CHAIN_NAME
+#ifdef FK_MAPPED_CHAINS   // (mapped_chains.hip only)
+#undef FK_READ_CHAIN_TABLE
+#define FK_READ_CHAIN_TABLE 2
+#define FK_READ_CHAIN_NAME k_read_chain_m
+#include "chain_kernels.inc"
+#undef FK_READ_CHAIN_NAME
+#endif
 #undef FK_VG
 #undef FK_READ_CHAIN_ARGS
 #undef FK_READ_CHAIN_TABLE
 
 // (defined in write_chain.inc, which is included twice: k_write_chain, and k_write_chain_t with a per-member operand table — the write
-// chain over the rows of the M members of a bank as ONE launch, y = m * ws + w: ct_lo from slot y, the shared trace keys, and the inverse
-// digits of coordinate 0 of member y / ws at ep.ggsw[i] + (y / ws) * opnd_stride.  The map is not read: every operand but the digits is per y.)
+// chain over the rows of n members of a bank as ONE launch, y = k * ws + w: ct_lo, trace(ct_hi) and the tree's copy from slot y, the shared
+// trace keys and the inverse digits of coordinate 0 of entry y / ws at ep.ggsw[i] + (y / ws) * opnd_stride; the map is not read: a range's
+// rows are per y — and k_write_chain_m, the same with the rows, ct_hi read and the last product stored, of member map(y / ws): table_member_row.)
 #define FK_WRITE_CHAIN_ARGS RowChainArgs
 #define FK_WRITE_CHAIN_TABLE 0
 #define FK_WRITE_CHAIN_NAME k_write_chain
@@ -1833,6 +1850,13 @@ __device__ __forceinline__ GlweRef table_src_row(GlweRef a, const RowChainTableA
 #define FK_WRITE_CHAIN_TABLE 1
 #define FK_WRITE_CHAIN_NAME k_write_chain_t
 #include "write_chain.inc"
+#ifdef FK_MAPPED_CHAINS   // (mapped_chains.hip only)
+#undef FK_WRITE_CHAIN_TABLE
+#undef FK_WRITE_CHAIN_NAME
+#define FK_WRITE_CHAIN_TABLE 2
+#define FK_WRITE_CHAIN_NAME k_write_chain_m
+#include "write_chain.inc"
+#endif
 #undef FK_WRITE_CHAIN_ARGS
 #undef FK_WRITE_CHAIN_TABLE
 #undef FK_WRITE_CHAIN_NAME

@@ -322,12 +322,18 @@ void launch_trace_chain(fheram_ctx* c, GlweRef src, const GlweRef (&b)[2], int s
     });
 }
 // The operand table of a launch over several addresses (path.hpp Opnds::table): gy = n * ws ciphertexts, ciphertext y takes the prepared
-// digits of address k = y / ws, which are `stride` elements apart from prep on, and reads the rows of member (src_map >> 4k) & 15 of the
-// rows source, row member * ws + y mod ws (all 0: every address reads the same rows, fheram_read_batch; the identity: its own, a bank range;
-// anything: fheram_bank_read_list).  ws == 0: one address, no table (the kernels without one).
-// src_map is read by launch_read_chain only: the write chain and the tail's fallback always run on rows of their own (row y is y).
-struct OpndTable { int ws = 0; long stride = 0; unsigned src_map = 0; };
-constexpr unsigned SRC_MAP_IDENTITY = 0x76543210u;   // entry k reads member k
+// digits of address k = y / ws, which are `stride` elements apart from prep on, and works on the rows of member (member_map >> 4k) & 15 of
+// the rows, row member * ws + y mod ws, as a source and as a destination (all 0: every address reads the same rows, fheram_read_batch; the
+// identity: its own, a bank range; anything: fheram_bank_read_list; any distinct members: the write lists).  ws == 0: one address, no table
+// (the kernels without one).
+// member_map is read by launch_read_chain (the source, the store_ep rows) and launch_write_chain (ct_hi, the last product's rows); the tail's
+// fallback runs on the operation's own per-y buffers and passes the identity.
+// store_mapped: the operation STORES rows through a map that is not the identity — the lists of read_prepare_write / write, and only they
+// (path.hpp Opnds::table) — so a launch that stores rows takes the mapped kernels (k_read_chain_m / k_write_chain_m); every other launch
+// the `_t` kernels, which do not map a store.
+struct OpndTable { int ws = 0; long stride = 0; unsigned member_map = 0; bool store_mapped = false; };
+constexpr unsigned MEMBER_MAP_IDENTITY = 0x76543210u;   // entry k works on member k
+bool map_is_identity(unsigned map, int n) { for (int k = 0; k < n; k++) if (((map >> (4 * k)) & 15u) != (unsigned)k) return false; return true; }
 // The two chains a row goes through back to back as ONE launch (k_read_chain / k_write_chain): both must be in the Chain form
 // (chain_form: whether the trace chain's first step reads rotated input does not matter to it), in the variants that hand over through
 // LDS and registers.  one_wg: ChainQuery's.
@@ -340,7 +346,7 @@ bool use_row_fuse(const fheram_ctx* c, int d, int n_tr, int gx, int gy, bool one
 RowChainTableArgs with_table(const RowChainArgs& ra, const OpndTable& t) {
     RowChainTableArgs rt;
     static_cast<RowChainArgs&>(rt) = ra;
-    rt.opnd_stride = t.stride; rt.ws = t.ws; rt.src_map = t.src_map;
+    rt.opnd_stride = t.stride; rt.ws = t.ws; rt.member_map = t.member_map;
     return rt;
 }
 void fill_row_chain(fheram_ctx* c, RowChainArgs& ra, const double* prep, int d, int start, int n_tr) {
@@ -351,7 +357,8 @@ void fill_row_chain(fheram_ctx* c, RowChainArgs& ra, const double* prep, int d, 
 }
 // read / read_prepare_write: d products of `src` with the prepared digits, then trace steps 0 .. n_tr-1 (the alone packer levels);
 // the result lands in dst; ep_store != nullptr: the products' result is also written there (in-place products of read_prepare_write)
-// with a table: row y reads src at row map(y / t.ws) * t.ws + y mod t.ws and the digits of address y / t.ws (k_read_chain_t)
+// with a table: row y reads src — and stores *ep_store — at row map(y / t.ws) * t.ws + y mod t.ws and takes the digits of address y / t.ws
+// (k_read_chain_t; k_read_chain_m where it stores and t.store_mapped)
 void launch_read_chain(fheram_ctx* c, GlweRef src, const GlweRef* ep_store, GlweRef dst, const double* prep, int d, int n_tr, int gx, int gy, const OpndTable& t) {
     ProfScope ps(c, "read_chain_launch", (uint64_t)gx * gy, 1);
     RowChainArgs ra;
@@ -364,6 +371,10 @@ void launch_read_chain(fheram_ctx* c, GlweRef src, const GlweRef* ep_store, Glwe
     ra.hi = dst; ra.trhi = dst;
     if (t.ws > 0) {   // several addresses: never beside the gate wave (read_local: wide), so the whole register file, as k_write_chain
         c->wide_unsynced = true;
+        if (ep_store && t.store_mapped) {   // a read_prepare_write list: the store goes through the map too
+            read_chain_m_launch(c->s_evk, dim3(gx, gy, 1), c->cur, with_table(ra, t));
+            return;
+        }
         with_evk(c, [&](auto sk) {
             constexpr int SK = decltype(sk)::value;
             hipLaunchKernelGGL((k_read_chain_t<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, with_table(ra, t));
@@ -377,7 +388,9 @@ void launch_read_chain(fheram_ctx* c, GlweRef src, const GlweRef* ep_store, Glwe
     });
 }
 // write: trace steps 0 .. n_tr-1 of ct_lo * X^-row (src, read rotated), data <- normalize(data - trhi + that), d products in place
-// with a table (a bank range: every member its own rows): row y takes the inverse digits of member y / t.ws (k_write_chain_t, which reads no map)
+// with a table (a bank range: every member its own rows; a write list: the rows of its members): row y takes the inverse digits of entry
+// y / t.ws and data (ct_hi, the products' store) at row map(y / t.ws) * t.ws + y mod t.ws; src, trhi and tree are per y (k_write_chain_t
+// k_write_chain_m under t.store_mapped)
 // tree != nullptr: the workgroup of row 0 of every y also writes (*tree)[y] = src[y] * X^tree_rho (the tree's rotated copy of ct_lo: no k_rotate launch behind)
 void launch_write_chain(fheram_ctx* c, GlweRef src, int rot_mul, int rot_base, GlweRef data, GlweRef trhi, const double* prep, int d, int n_tr, int gx, int gy, const OpndTable& t,
                         const GlweRef* tree = nullptr, int tree_rho = 0) {
@@ -390,6 +403,10 @@ void launch_write_chain(fheram_ctx* c, GlweRef src, int rot_mul, int rot_base, G
     ra.ep.src = data; ra.ep.buf[0] = ra.ep.buf[1] = data;         // only the last product stores: in place on the rows
     if (tree) { ra.tree = *tree; ra.tree_rho = tree_rho; }
     c->wide_unsynced = true;                                      // (k_write_chain takes the whole register file)
+    if (t.ws > 0 && t.store_mapped) {   // a write list
+        write_chain_m_launch(c->s_evk, dim3(gx, gy, 1), c->cur, with_table(ra, t));
+        return;
+    }
     with_evk(c, [&](auto sk) {
         constexpr int SK = decltype(sk)::value;
         if (t.ws > 0) hipLaunchKernelGGL((k_write_chain_t<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, with_table(ra, t));
@@ -442,7 +459,7 @@ void launch_trace_tail(fheram_ctx* c, GlweRef src, const GlweRef (&b)[2], int st
             tt.opnd_stride = t.stride; tt.ws = t.ws;
             hipLaunchKernelGGL((k_trace_tail_t<3, SK, 3>), groups, dim3(T), LDS_BYTES, c->cur, tt);
             c->wide_unsynced = true;
-            hipLaunchKernelGGL((k_read_chain_t<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, with_table(ra, OpndTable{t.ws, t.stride, SRC_MAP_IDENTITY}));
+            hipLaunchKernelGGL((k_read_chain_t<SK, 4>), dim3(gx, gy, 1), dim3(T), LDS_BYTES, c->cur, with_table(ra, OpndTable{t.ws, t.stride, MEMBER_MAP_IDENTITY}));
             return;
         }
         hipLaunchKernelGGL((k_trace_tail<3, SK, 3>), groups, dim3(T), LDS_BYTES, c->cur, ta);

@@ -1,9 +1,9 @@
 // Private to fheram.hip: Ram::read / read_prepare_write / write as launch sequences (reference: src/ram.rs).
 // ONE read sequence (read_local + read_top, together read_impl) and ONE write sequence (write_side_begin, write_top, write_rows), over an
 // operand set (Opnds: whose digits a product uses, whose RAM state it updates) and a view (RamView: the buffers it runs on).  The plain context, the stages of
-// a row-sharded RAM (fheram.hip, group.hpp), fheram_read_batch and fheram_bank_* (bank.hpp; its read list too) all run these; what is specific to one of them
+// a row-sharded RAM (fheram.hip, group.hpp), fheram_read_batch and fheram_bank_* (bank.hpp; its read list and write lists too) all run these; what is specific to one of them
 // is a visible condition in the sequence (n == 1: pre_inv, the gate wave, ev_opstart, ev_wdone, sharding, capture; a bank range or list: Opnds::bank in row_fuse).
-// Several addresses are ONE kind of operand set (table_opnds: a digit table and a source map) and several reads ONE buffer set (ReadBufs, read_many).
+// Several addresses are ONE kind of operand set (table_opnds: a digit table and a member map) and several reads ONE buffer set (ReadBufs, read_many).
 #pragma once
 #include "launch.hpp"
 
@@ -21,18 +21,22 @@ struct Opnds {
     int n, ws;
     double *tab, *tab_inv;   // (inverse) digits of address 0
     long stride;
-    // whose rows address k works on: member (src_map >> 4k) & 15 of the view's rows, four bits per address — what the table forms take by value
+    // whose rows address k works on: member (member_map >> 4k) & 15 of the view's rows, four bits per address — what the table forms take by value
     // (launch.hpp OpndTable).  n == 1 and fheram_read_batch: 0, every address the view's first ws rows; a bank range: the identity, address k
-    // reads and writes member k of the range; a bank's read list: its members, of the whole bank's rows (read-only)
-    unsigned src_map;
-    bool bank;               // a range or a read list of a bank of several members, n > 1: row_fuse
-    int member(int k) const { return (int)((src_map >> (4 * k)) & 15u); }
+    // reads and writes member k of the range; a bank's read list: its members, of the whole bank's rows (read-only); a bank's
+    // read_prepare_write / write list: its distinct members, of the whole bank's rows, read and written — every other buffer of its view is dense
+    unsigned member_map;
+    bool bank;               // a range or a list of a bank of several members, n > 1: row_fuse
+    int member(int k) const { return (int)((member_map >> (4 * k)) & 15u); }
+    // address k's rows are the view's k-th: a launch over all Y ciphertexts may touch the rows directly (else: one launch per address through rows())
+    bool rows_dense() const { return map_is_identity(member_map, n); }
     int Y() const { return n * ws; }
     double* prep(int k, int ci) const { return digits_of(c, tab + k * stride, ci); }
     double* inv(int k, int ci) const { return digits_of(c, tab_inv + k * stride, ci); }
     GlweRef slice(GlweRef r, int k) const { r.p += (long)k * ws * r.sy; return r; }   // address k's ws ciphertexts
     GlweRef rows(GlweRef r, int k) const { return slice(r, member(k)); }
-    OpndTable table() const { return n == 1 ? OpndTable{} : OpndTable{ws, stride, src_map}; }
+    // (store_mapped: a batch's and a read list's maps are not the identity either, but neither ever stores rows; it decides for the write lists)
+    OpndTable table() const { return n == 1 ? OpndTable{} : OpndTable{ws, stride, member_map, !rows_dense()}; }
     // The fused row chain (k_read_chain / k_write_chain) for this operation.  A lone context — and a batch like it — splits by column while
     // rows * ws * 2 workgroups still fit the chip (pick_nco), which rules the chain out; for a range of bank members the alternative to the ONE
     // launch with an operand table is not one column-split launch per step but one per MEMBER and step, so the range takes one workgroup
@@ -44,8 +48,8 @@ struct Opnds {
 Opnds one_addr(fheram_ctx* c, const fheram_addr* const* a, int ws, RamState* st) { return Opnds{c, st, a, 1, ws, c->d_prep, c->d_prep_inv, 0, 0, false}; }
 Opnds one_addr(fheram_ctx* c, const fheram_addr* const* a) { return one_addr(c, a, c->ws, &c->ram); }
 // n > 1 addresses of ws ciphertexts, their digits in a table ([n][n_digits] prepared GGSW; tab_inv: of a set that is written, else nullptr)
-Opnds table_opnds(fheram_ctx* c, RamState* st, const fheram_addr* const* addrs, int n, int ws, double* tab, double* tab_inv, unsigned src_map, bool bank) {
-    return Opnds{c, st, addrs, n, ws, tab, tab_inv, (long)c->n_digits * (long)fheram_ctx::GGSW, src_map, bank};
+Opnds table_opnds(fheram_ctx* c, RamState* st, const fheram_addr* const* addrs, int n, int ws, double* tab, double* tab_inv, unsigned member_map, bool bank) {
+    return Opnds{c, st, addrs, n, ws, tab, tab_inv, (long)c->n_digits * (long)fheram_ctx::GGSW, member_map, bank};
 }
 
 // An operation's VIEW: every buffer indexed by ciphertext y, from the operation's first.  The rows, the ping-pong arenas A / B with the third
@@ -144,8 +148,11 @@ int read_local(const Opnds& o, const RamView& a, bool prepare_write, GlweRef* pa
         for (int k = 0; k < n; k++)
             if (prepare_write) ep_chain(c, o.rows(row0, k), o.rows(row0, k), o.slice(ref(a.A, sy, 0), k), o.prep(k, 0), d0, 1, ws);   // ram.rs:502-504 (rows == 1)
             else ep_chain(c, o.rows(row0, k), o.slice(part, k), o.slice(ref(a.tmp, G, 0), k), o.prep(k, 0), d0, 1, ws);                 // ram.rs:451
-        *packed_out = prepare_write ? row0 : part;
-        if (prepare_write && to_part) launch_copy(c, row0, part, 1, Y);
+        // a list's members are not the view's first rows: the trace (read_top) takes them from a gathered copy in part
+        const bool gather = prepare_write && !o.rows_dense();
+        if (gather) for (int k = 0; k < n; k++) launch_copy(c, o.rows(row0, k), o.slice(part, k), 1, ws);
+        *packed_out = (prepare_write && !gather) ? row0 : part;
+        if (prepare_write && to_part && !gather) launch_copy(c, row0, part, 1, Y);
         return FHERAM_OK;
     }
     const int L0 = LOGN - ilog2_ceil(c->rows_glob);
@@ -160,7 +167,12 @@ int read_local(const Opnds& o, const RamView& a, bool prepare_write, GlweRef* pa
         for (int k = 0; k < n; k++)
             if (prepare_write) ep_chain(c, o.rows(data, k), o.rows(data, k), o.slice(A, k), o.prep(k, 0), d0, R, ws);   // ram.rs:502-504
             else ep_chain(c, o.rows(data, k), o.slice(A, k), o.slice(B, k), o.prep(k, 0), d0, R, ws);                   // ram.rs:429-434
-        packed = pack_levels(c, prepare_write ? a.rows : a.A, a.A, a.B, sy, G, (size_t)R, Y, L0, L0, keep, a.C, a.D);   // ram.rs:435-448 / 510-521
+        int32_t* leaves = prepare_write ? a.rows : a.A;
+        if (prepare_write && !o.rows_dense()) {   // a list where the fused chain does not run (forced off, or the default form up to 64 ciphertext rows, 2^14): the members' rows gathered into the fourth arena, which the alone levels only read
+            for (int k = 0; k < n; k++) launch_copy(c, o.rows(data, k), o.slice(ref(a.D, sy, G), k), R, ws);
+            leaves = a.D;
+        }
+        packed = pack_levels(c, leaves, a.A, a.B, sy, G, (size_t)R, Y, L0, L0, keep, a.C, a.D);   // ram.rs:435-448 / 510-521
     }
     *packed_out = ref(packed, sy, 0);
     if (to_part) launch_copy(c, *packed_out, part, 1, Y);
@@ -319,14 +331,14 @@ int reads_export(fheram_ctx* c, const ReadBufs& L, size_t first, size_t n_ct, in
     const ResRun run{L.res + first * fheram_ctx::GLWE, n_ct * fheram_ctx::GLWE};
     return result_export(c, &run, 1, L.h_res, L.d_h_res, out);
 }
-// n >= 2 reads as one operation on `L`: address k reads member (src_map >> 4k) & 15 of the context's rows.  kept(o): what the caller's
+// n >= 2 reads as one operation on `L`: address k reads member (member_map >> 4k) & 15 of the context's rows.  kept(o): what the caller's
 // RAM(s) keep of it (where a single read would have left its result), enqueued behind the reads.
 // (Never captured: the launch sequence depends on n addresses, and a read's state bookkeeping is done as it is enqueued.)
 template <typename F>
-int read_many(fheram_ctx* c, ReadBufs& L, RamState* st, const fheram_addr* const* addrs, int n, int ws, unsigned src_map, bool bank, int64_t* out, F&& kept) {
+int read_many(fheram_ctx* c, ReadBufs& L, RamState* st, const fheram_addr* const* addrs, int n, int ws, unsigned member_map, bool bank, int64_t* out, F&& kept) {
     int rc = reads_reserve(c, L, n, ws);
     if (rc != FHERAM_OK) return rc;
-    const Opnds o = table_opnds(c, st, addrs, n, ws, L.prep, nullptr, src_map, bank);
+    const Opnds o = table_opnds(c, st, addrs, n, ws, L.prep, nullptr, member_map, bank);
     rc = read_impl(o, reads_view(c, L), false);
     if (rc != FHERAM_OK) return rc;
     kept(o);
@@ -348,9 +360,15 @@ int write_top(const Opnds& o, const RamView& v) {
     // write_first_step (ram.rs:544-577): t <- normalize(t - trace(t) + w)
     GlweRef top = (c->n2 != 1) ? tree : ref(v.rows, sy, 0);
     GlweRef tr = tmp;
+    const bool by_member = c->n2 == 1 && !o.rows_dense();   // a list on one-row RAMs: the top is the member's row, one launch per address
     if (o.st->memo_top) tr = ref(v.trtop, G, 0);     // = trace(top), computed by read_prepare_write on this very ciphertext
+    else if (by_member) for (int k = 0; k < n; k++) trace_steps(c, o.rows(top, k), o.slice(tmp, k), o.slice(tmp2, k), 0, LOGN, 1, ws);
     else trace_steps(c, top, tmp, tmp2, 0, LOGN, 1, Y);
-    {
+    if (by_member) {
+        ProfScope ps(c, "elementwise", Y);
+        for (int k = 0; k < n; k++)
+            hipLaunchKernelGGL((k_sub_add_norm<3>), dim3(1, ws, EW_SLICES), dim3(256), 0, c->cur, o.rows(top, k), o.slice(tr, k), o.slice(wref, k), o.rows(top, k));
+    } else {
         ProfScope ps(c, "elementwise", Y);
         hipLaunchKernelGGL((k_sub_add_norm<3>), dim3(1, Y, EW_SLICES), dim3(256), 0, c->cur, top, tr, wref, top);
     }
@@ -396,6 +414,8 @@ void write_side_begin(const Opnds& o, const RamView& v) {
         const int kept = o.st->memo_alone;   // > 0: arena A = the rows after trace steps 0 .. kept-1 (left there by read_prepare_write)
         c->trhi_in_C = kept > 0 && (LOGN - kept) % 2 == 1;   // ping-pong A <-> C; an odd number of remaining steps ends in C
         if (kept > 0) trace_steps(c, ref(v.A, sy, G), ref(c->trhi_in_C ? v.C : v.A, sy, G), ref(c->trhi_in_C ? v.A : v.C, sy, G), kept, LOGN, (int)c->rows, o.Y());
+        else if (!o.rows_dense())   // a list with nothing kept: one chain per address, from the member's rows
+            for (int k = 0; k < o.n; k++) trace_steps(c, o.rows(ref(v.rows, sy, G), k), o.slice(ref(v.A, sy, G), k), o.slice(ref(v.C, sy, G), k), 0, LOGN, (int)c->rows, o.ws);
         else trace_steps(c, ref(v.rows, sy, G), ref(v.A, sy, G), ref(v.C, sy, G), 0, LOGN, (int)c->rows, o.Y());
         o.st->memo_alone = 0;
     }
@@ -445,9 +465,11 @@ int write_rows(const Opnds& o, const RamView& v) {
         hipStreamWaitEvent(c->stream, c->ev_join, 0);                                          // side stream: trace(ct_hi), inverse coordinate 0
         if (c->n2 == 2) {
             ProfScope ps(c, "elementwise", (uint64_t)R * Y);
-            hipLaunchKernelGGL((k_sub_add_norm<3>), dim3(R, Y, EW_SLICES), dim3(256), 0, c->cur, data, trhi, B, data);   // ram.rs:617,625-626
+            if (o.rows_dense()) hipLaunchKernelGGL((k_sub_add_norm<3>), dim3(R, Y, EW_SLICES), dim3(256), 0, c->cur, data, trhi, B, data);   // ram.rs:617,625-626
+            else for (int k = 0; k < n; k++)   // a list: the rows of member(k), everything else of address k
+                hipLaunchKernelGGL((k_sub_add_norm<3>), dim3(R, ws, EW_SLICES), dim3(256), 0, c->cur, o.rows(data, k), o.slice(trhi, k), o.slice(B, k), o.rows(data, k));
         }
-        for (int k = 0; k < n; k++) ep_chain(c, o.slice(data, k), o.slice(data, k), o.slice(A, k), o.inv(k, 0), d0, R, ws);   // ram.rs:644-646
+        for (int k = 0; k < n; k++) ep_chain(c, o.rows(data, k), o.rows(data, k), o.slice(A, k), o.inv(k, 0), d0, R, ws);   // ram.rs:644-646
     }
     // the next read_prepare_write's side work overwrites d_prep_inv: it is ordered behind this write by an event (the gate
     // launch in front of that work is time-bounded, so it cannot be the only ordering); a table's inverse digits have no such reader

@@ -1,11 +1,18 @@
 // Included by kernels.hpp (no include guard): a row's write chain (ram.rs:612-646, see RowChainArgs in kernels.hpp), instantiated twice.
 //   FK_WRITE_CHAIN_NAME : kernel name;  FK_WRITE_CHAIN_ARGS / FK_WRITE_CHAIN_TABLE : RowChainArgs / 0, or RowChainTableArgs / 1 for the
-//   write chain of a bank (fheram_bank_write): ciphertext y = m * ws + w takes the inverse digits of member y / ws
+//   write chain of a bank range (fheram_bank_write): ciphertext y = k * ws + w takes the inverse digits of entry y / ws, / 2 for that of
+//   a write list (fheram_bank_write_list): and the rows (ct_hi, the last product's store) of member map(y / ws); ct_lo, trace(ct_hi) and
+//   the tree's copy are per y in every form
 #if FK_WRITE_CHAIN_TABLE
-// recomputed where it is used rather than kept live across the steps (see FK_RC_OPND in chain_kernels.inc)
+// recomputed where they are used rather than kept live across the steps (see FK_RC_OPND in chain_kernels.inc)
 #define FK_WC_OPND(i) (ra.ep.ggsw[i] + table_opnd_offset(ra))
 #else
 #define FK_WC_OPND(i) ra.ep.ggsw[i]
+#endif
+#if FK_WRITE_CHAIN_TABLE == 2
+#define FK_WC_ROW(a) table_member_row(a, ra)
+#else
+#define FK_WC_ROW(a) a
 #endif
 template <int SK, int SG>   // (only ever launched by Ram::write: never beside the gate wave)
 __global__ __launch_bounds__(T, T / 256) __attribute__((amdgpu_num_vgpr(FK_WIDE_VGPRS))) void FK_WRITE_CHAIN_NAME(FK_WRITE_CHAIN_ARGS ra) {
@@ -34,7 +41,7 @@ __global__ __launch_bounds__(T, T / 256) __attribute__((amdgpu_num_vgpr(FK_WIDE_
         __builtin_assume(tid >= 0 && tid < T);
         if (i == 0) ks_trace_l<SK, false, 1>(ka, lds, true, tid, vc);
         else if (i + 1 < ra.ks.n) ks_trace_l<SK, true, 1>(ka, lds, false, tid, vc);
-        else { ka.b = ra.hi; ka.out = ra.trhi; ks_trace_l<SK, true, 2>(ka, lds, false, tid, vc); }
+        else { ka.b = FK_WC_ROW(ra.hi); ka.out = ra.trhi; ks_trace_l<SK, true, 2>(ka, lds, false, tid, vc); }
         ka.rot_mul = 0;
         ka.rot_base = 0;
     }
@@ -47,8 +54,9 @@ __global__ __launch_bounds__(T, T / 256) __attribute__((amdgpu_num_vgpr(FK_WIDE_
         __builtin_assume(tid >= 0 && tid < T);
         if (i == 0) ep_step_r<SG, 2, 1>(in, out, FK_WC_OPND(i), ra.ep.tw, lds, false, tid, vc);
         else if (i + 1 < ra.ep.n) ep_step_r<SG, 1, 1>(in, out, FK_WC_OPND(i), ra.ep.tw, lds, false, tid, vc);
-        else ep_step_r<SG, 1, 0>(in, out, FK_WC_OPND(i), ra.ep.tw, lds, false, tid, vc);
+        else ep_step_r<SG, 1, 0>(in, FK_WC_ROW(out), FK_WC_OPND(i), ra.ep.tw, lds, false, tid, vc);   // (the only store of the products: in place on the member's rows)
         in = out;
     }
 }
 #undef FK_WC_OPND
+#undef FK_WC_ROW

@@ -459,6 +459,32 @@ public:
         std::vector<const fheram_addr*> h = handles(addresses);
         chk(fheram_bank_write(bank_, first, (int)h.size(), flat.data(), h.data()));
     }
+    // read_prepare_write of ANY set of members as ONE operation (fheram_bank_read_prepare_write_list), entry k on member members[k] at
+    // *addresses[k]: distinct members (a RAM has one pending write), any order, any subset.  Result k is what
+    // read_prepare_write({addresses[k]}, keys, members[k]) returns; every named member is then prepared like any other.
+    std::vector<std::vector<Glwe>> read_prepare_write_list(const std::vector<int>& members, std::vector<Address*>& addresses, const EvaluationKeysPrepared& keys) {
+        if (members.empty() || addresses.size() != members.size())
+            throw Error(FHERAM_ERR_INVALID_ARG, "read_prepare_write_list takes at least one member and as many addresses");
+        use(keys);
+        std::vector<const fheram_addr*> h = handles(addresses);
+        std::vector<int64_t> out(h.size() * params.word_size() * glwe_len());
+        chk(fheram_bank_read_prepare_write_list(bank_, members.data(), h.data(), (int)h.size(), out.data()));
+        return split(out, h.size());
+    }
+    // w[k]: the word_size GLWEs written to member members[k] at *addresses[k] (fheram_bank_write_list); the members are in state 1,
+    // however they were prepared (a list, a range, single calls)
+    void write_list(const std::vector<int>& members, const std::vector<std::vector<Glwe>>& w, std::vector<Address*>& addresses, const EvaluationKeysPrepared& keys) {
+        if (members.empty() || addresses.size() != members.size() || w.size() != members.size())
+            throw Error(FHERAM_ERR_INVALID_ARG, "write_list takes at least one member, as many addresses and one word per member");
+        std::vector<int64_t> flat;
+        for (auto& word : w) {
+            if (word.size() != params.word_size()) throw Error(FHERAM_ERR_INVALID_ARG, "w.len() != subrams.len() (ram.rs:243)");
+            for (auto& g : word) flat.insert(flat.end(), g.begin(), g.end());
+        }
+        use(keys);
+        std::vector<const fheram_addr*> h = handles(addresses);
+        chk(fheram_bank_write_list(bank_, members.data(), h.data(), (int)h.size(), flat.data()));
+    }
     // an encrypted integer on the bank's device, from host ciphertexts [n_bits][fheram_fheuint_ggsw_len] (fheram_bank_fheuint_create)
     class FheUintPrepared {
     public:

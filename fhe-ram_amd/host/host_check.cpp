@@ -103,6 +103,29 @@ int main() {
             try { std::vector<fheram::Address*> bad = {&a0}; bank.read_list({2}, bad, bk); return 12; }
             catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 12; }
             std::printf("bank read list == single-member reads: ok\n");
+            // Bank::read_prepare_write_list / write_list on members {2, 0} of a bank of three against a twin driven member by member
+            fheram::Bank lists(bp, 3), twin(bp, 3);
+            for (int m = 0; m < 3; m++) { const auto r = synth(4 * lists.glwe_len()); lists.load_encrypted(m, r); twin.load_encrypted(m, r); }
+            std::vector<fheram::Address*> wa = {&a1, &a0};
+            const std::vector<int> wm = {2, 0};
+            std::vector<std::vector<fheram::Glwe>> words(2);
+            for (auto& word : words) for (int i = 0; i < 4; i++) word.push_back(synth(lists.glwe_len()));
+            const auto prepared = lists.read_prepare_write_list(wm, wa, bk);
+            if (prepared.size() != 2 || !lists.state(2) || !lists.state(0) || lists.state(1)) return 13;
+            for (size_t k = 0; k < wm.size(); k++) {
+                one[0] = wa[k];
+                if (twin.read_prepare_write(one, bk, wm[k])[0] != prepared[k]) { std::printf("read_prepare_write_list: entry %zu differs\n", k); return 13; }
+            }
+            lists.write_list(wm, words, wa, bk);
+            for (size_t k = 0; k < wm.size(); k++) {
+                one[0] = wa[k];
+                twin.write({words[k]}, one, bk, wm[k]);
+            }
+            for (int m = 0; m < 3; m++)
+                if (lists.state(m) || lists.store_encrypted(m) != twin.store_encrypted(m)) { std::printf("write_list: member %d differs\n", m); return 13; }
+            try { std::vector<fheram::Address*> dup = {&a0, &a1}; lists.read_prepare_write_list({1, 1}, dup, bk); return 14; }
+            catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 14; }
+            std::printf("bank write lists == single-member operations: ok\n");
         }
     } catch (const fheram::Error& e) {
         if (e.code != FHERAM_ERR_DEVICE) { std::printf("unexpected error %d: %s\n", e.code, e.what()); return 4; }

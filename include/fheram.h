@@ -317,7 +317,7 @@ int fheram_bank_result_download(fheram_bank* bank, int first, int n, int64_t* ou
  * changes nothing: null pointers, n out of range, a member index outside the bank, a foreign or empty address
  * (FHERAM_ERR_INVALID_ARG); a named member without rows (FHERAM_ERR_UNINITIALIZED); keys not loaded (FHERAM_ERR_KEYS); a named member
  * between read_prepare_write and write (FHERAM_ERR_STATE).  FHERAM_ERR_DEVICE: the list's buffers cannot be allocated (every other
- * operation still works).  There is no list form of read_prepare_write / write: a RAM has one pending write. */
+ * operation still works).  The write side's list form is fheram_bank_read_prepare_write_list / fheram_bank_write_list below. */
 #define FHERAM_READ_LIST_MAX 8
 /* K = n independent Ram::read (ram.rs:172-191), entry k on member members[k] at addrs[k], as ONE operation.
  * Any order, any repetition, any subset of the bank's members.  out: [n][word_size][GLWE], or NULL (no host wait). */
@@ -325,6 +325,32 @@ int fheram_bank_read_list(fheram_bank* bank, const int* members, const fheram_ad
 /* entries [first, first + n) of the LAST list, [n][word_size][GLWE]; for a list that was enqueued with out == NULL.
  * FHERAM_ERR_STATE before any list has run, FHERAM_ERR_INVALID_ARG for a slice outside the last list. */
 int fheram_bank_read_list_result(fheram_bank* bank, int first, int n, int64_t* out);
+/* A write list: read_prepare_write / write on ANY set of members as one operation — distinct members, any order, any subset (members
+ * {0, 2} of a bank of three: a register file and a data memory with a ROM between them), 1 <= n <= fheram_bank_size(bank); a RAM has
+ * one pending write (ram.rs:196-294), so no member is named twice.  The latency-bound ends of both halves are paid once for the list,
+ * and the rows' chains of all entries are one launch each, on the members' own rows.  The call is int64-identical to the n
+ * single-member calls fheram_bank_read_prepare_write(bank, members[k], 1, &addrs[k], ..) / fheram_bank_write(bank, members[k], 1, ..):
+ * slice k of out is member members[k]'s result, and afterwards every named member has the state flag, rows, tree level 0 and
+ * fheram_bank_result_download result of a standalone context driven the same way.  A write list may name any members in state 1,
+ * however they were prepared (a list, a range, a single call), and members prepared by a list may be written by ranges or single
+ * calls; what a write resumes from is an optimisation that never changes a result.  Members that are not named are untouched in every
+ * respect: one between read_prepare_write and write keeps what it kept, the results of the last read list stay readable, and a read
+ * list on other members may run between the two halves (the write lists run on buffers of their own, allocated on first use, grown
+ * to the largest list seen and freed with the bank).  A list of one entry is the plain single-member operation, a contiguous
+ * ascending run the range operation.  Neither call waits for the device (out == NULL for the first).
+ * Checked for the whole list before anything is enqueued, a refused call changes nothing: null pointers, n out of range, a member
+ * index outside the bank, a member named twice, a foreign or empty address (FHERAM_ERR_INVALID_ARG); a named member without rows
+ * (FHERAM_ERR_UNINITIALIZED); keys not loaded (FHERAM_ERR_KEYS); read_prepare_write naming a member in state 1, write naming a member
+ * in state 0 (FHERAM_ERR_STATE); a word limb out of range (FHERAM_ERR_RANGE, as fheram_bank_write: no row is touched and the members
+ * stay prepared).  FHERAM_ERR_DEVICE: the lists' buffers cannot be allocated (every other operation still works). */
+/* entry k: Ram::read_prepare_write (ram.rs:196-222) of member members[k] at addrs[k]; out: [n][word_size][GLWE] or NULL (no host wait) */
+int fheram_bank_read_prepare_write_list(fheram_bank* bank, const int* members, const fheram_addr* const* addrs, int n, int64_t* out);
+/* entry k: Ram::write (ram.rs:226-294) of w[k] ([n][word_size][GLWE]) to member members[k] at addrs[k] */
+int fheram_bank_write_list(fheram_bank* bank, const int* members, const fheram_addr* const* addrs, int n, const int64_t* w);
+/* Self-test of the FHERAM_ERR_DEVICE path of the two calls above (not on the RAM path): the nth device allocation their buffers ask for
+ * from now on fails once, as an exhausted device would make it (nth = 1: the next one; 0: none, which withdraws an earlier request).
+ * The buffers are eleven allocations, made when a list is longer than any before it. */
+int fheram_bank_selftest_fail_list_alloc(fheram_bank* bank, int nth);
 int fheram_bank_sync(fheram_bank* bank);
 /* one round-off monitor for the bank; FHERAM_ERR_PRECISION as for a context */
 int fheram_bank_roundoff_max(fheram_bank* bank, double* max_out);

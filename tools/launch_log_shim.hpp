@@ -4,8 +4,9 @@ namespace {
 // read_top's fuse_ep and gated ask whether the final trace over Y ciphertexts takes the tail launch (path.hpp read_top, tail_top)
 bool shim_tail_top(const fheram_ctx* c, int Y) { return chain_form(c, ChainQuery{false, LOGN, 1, Y}).form == ChainForm::Tail; }
 // an operand set for the predicates alone; own_rows: a context's (n == 1) or a bank range's, else a batch's
-Opnds shim_opnds(fheram_ctx* c, int n, int ws, bool own_rows) { return n == 1 ? one_addr(c, nullptr, ws, &c->ram) : table_opnds(c, &c->ram, nullptr, n, ws, nullptr, nullptr, own_rows ? SRC_MAP_IDENTITY : 0, own_rows); }
-// the operand table of the row_chains cases: gy ciphertexts as two addresses that read the same rows
+Opnds shim_opnds(fheram_ctx* c, int n, int ws, bool own_rows) { return n == 1 ? one_addr(c, nullptr, ws, &c->ram) : table_opnds(c, &c->ram, nullptr, n, ws, nullptr, nullptr, own_rows ? MEMBER_MAP_IDENTITY : 0, own_rows); }
+// the operand table of the row_chains cases: gy ciphertexts as two addresses that read the same rows (store_mapped off: the `_t` kernels,
+// which are what a batch and a range launch; the lists' `_m` kernels live in another translation unit and are not logged)
 OpndTable shim_table(int gy) { return OpndTable{gy / 2, 1000, 0}; }
 bool shim_needs_third(const fheram_ctx* c, int K) { return third_arena_needed(c, K * c->ws); }
 // the buffers of a batch and of a bank's read list: field i of launch_log.hip's READS_FIELDS, and the digit table
