@@ -1,68 +1,66 @@
 // Included by fheram.hip (same translation unit): fheram_bank — M RAMs of the same shape under ONE prepared key set, and Ram::read /
-// read_prepare_write / write (ram.rs:172-294) on a contiguous range of them as ONE operation, one address per member.
-// Ram objects are independent units (ram.rs:25-29; `&mut self` serialises per RAM only), so nothing orders operations on different RAMs.
+// read_prepare_write / write (ram.rs:172-294) on a SET of them as ONE operation, one address per member.  Ram objects are independent units
+// (ram.rs:25-29; `&mut self` serialises per RAM only), so nothing orders operations on different RAMs.
 //
-// Structure: ONE internal context whose word count is M * ws.  Rows, arenas, tree, results, words and temporaries are laid out
-// [M * ws][...], so ciphertext y = m * ws + w is word w of member m, and a member range [first, first + n) is a pointer offset plus
-// gy = n * ws: a RamView of its own (bank_view).  On that view the operation is path.hpp's read_impl / write_side_begin / write_top /
-// write_rows with the operand set of the range (bank_opnds):
-//   - a range of ONE member is the plain operation (one_addr), memo included;
-//   - a wider range has its digits in a table: every address-independent step is one launch over n * ws ciphertexts, the address-dependent
-//     products take the table where a table form exists (k_read_chain_t, k_trace_tail_t with its k_read_chain_t fallback,
-//     k_write_chain_t) and run one launch per member on the member's y-slice everywhere else (prepare, the GGSW inversion, the unfused
-//     product chains, n2 == 1).
-// Per-member state (the state flag, what read_prepare_write kept for the write, where the last result is) lives here, one RamState per
-// member; an operation runs on the merge of its range's (bank_merge) and hands the outcome back to every member of it (bank_assign).  The
-// context is never made to look like a range: after fheram_bank_create nothing here writes a field of it (and create itself writes none of its switches).  The write's inverse digits are
-// never started early in a bank of more than one member (pre_inv shares d_prep_inv and d_tail_sync between members); a bank of ONE member
-// is a plain context in every respect.
-// A READ LIST (fheram_bank_read_list) is the general read: entry k reads member members[k], in any order and with repeats.  It is the same
-// read_impl on the same kind of operand set (path.hpp table_opnds) with the members as its source map, over the whole bank's rows (one
-// member index per entry: Opnds::rows for the per-entry launches, k_read_chain_t for the rows' chain — a range is the identity map, a
-// batch the map 0, 0, ...); the digits sit in a table of the list's own, and every launch writes buffers of the list's own (ReadBufs, the
-// very set a batch has: path.hpp read_many) — so the arenas, trtop and tree of a member that sits between read_prepare_write and write are not touched.  It runs on a scratch RamState; every named member is then left as a
-// read leaves it, with the result of the last entry that named it in its slice of d_res.
-// A WRITE LIST (fheram_bank_read_prepare_write_list / fheram_bank_write_list) is the general read_prepare_write / write: entry k works on
-// member members[k], distinct members in any order (a RAM has one pending write).  The same read_impl / write_side_begin / write_top /
-// write_rows on table_opnds with the members as the map and the bank's d_prep / d_prep_inv (n <= M), over the whole bank's rows: the table
-// chains read AND store the rows through the map (k_read_chain_m / k_write_chain_m, mapped_chains.hip), every launch without a table form goes
-// member by member through Opnds::rows.  Every other buffer of the view is dense, [n * mws], and the lists' own (WriteListBufs) — not the
-// read list's, so that a read list between the two halves destroys nothing.  Per-member hand-over: read_prepare_write copies every entry's
-// tree top and result into the member's own slots and sets its RamState, so ranges, single calls and downloads see a prepared member like
-// any other; a write list gathers tree and trace(top) from those slots and scatters the tree back.  The rows after the alone levels stay in
-// the lists' arena A: they count for a write list of the same members in the same order while every one of them still holds them (wl_holds).
-// A list of one member, or of a contiguous ascending run, IS the range operation.
-// Bank operations are never captured into a hipGraph: under graph = 1 they are enqueued directly, in the forms that mode selects.
+// Storage: ONE internal context whose word count is M * ws.  Rows, arenas, tree, results, words and temporaries are laid out [M * ws][...],
+// so ciphertext y = m * ws + w is word w of member m.  Per-member state (the state flag, what read_prepare_write kept for the write, where
+// the last result is) lives here, one RamState per member.  After fheram_bank_create nothing here writes a field of the context.
+//
+// Every read_prepare_write and write — by range or by list — is one function over a MEMBER SET (MemberSet: entry k works on member
+// m[k]) and the set's PLAN (SetPlan): path.hpp's read_impl / write_all on the plan's view and operand set, from the plan's RAM state, whose
+// outcome set_assign hands back to every member.  There are two plans:
+//   - IN PLACE, for a range (one member, or a contiguous ascending run [first, first + n)): the view is the context's buffers from the
+//     range's first ciphertext (bank_view), a pointer offset plus gy = n * ws.  One member is the plain operation (one_addr), memo included;
+//     more have their digits in the bank's tables with the identity map: every address-independent step is one launch over n * ws
+//     ciphertexts, the products take the table where a table form exists and run member by member on the y-slice everywhere else.  The
+//     state is the merge of the members': what read_prepare_write kept counts only when every member holds it.
+//   - DENSE, for any other set of distinct members: the rows are the whole bank's, reached through the set's map (the table chains read
+//     AND store them through it: k_read_chain_m / k_write_chain_m; launches without a table form go member by member, Opnds::rows); every
+//     other buffer is the lists' own dense set `wl` (path.hpp dense_reserve) — not the read list's, so a read list between the two halves
+//     destroys nothing.  read_prepare_write hands every entry's tree top and result over into the member's own slots, so ranges, single
+//     calls and downloads see a prepared member like any other; a write gathers tree and trace(top) from those slots and scatters the tree
+//     back.  The rows after the alone levels stay in wl.A: they count (kept_*) for a write of the same members in the same order while
+//     every one of them still holds them (wl_holds) — then nothing is gathered either.
+// A READ LIST (fheram_bank_read_list) is the general read: members in any order, with repeats, so it is not a plan of the above but
+// path.hpp's read_many — the batch's function — with the set's map, on a dense set of its own (`list`) and a scratch state; every named
+// member is then left as a read leaves it (set_assign), with the result of the last entry that named it in its slice of d_res.
+// The write's inverse digits are never started early in a bank of more than one member (pre_inv shares d_prep_inv and d_tail_sync between
+// members); a bank of ONE member is a plain context in every respect.  Bank operations are never captured into a hipGraph: under graph = 1
+// they are enqueued directly, in the forms that mode selects.
 #pragma once
 #include "path.hpp"
-
-// The dense buffers of a read_prepare_write / write list: for `cap` entries of mws ciphertexts, allocated on first use, grown to the largest
-// list seen, freed with the bank.
-struct WriteListBufs {
-    int cap = 0;
-    int32_t *A = nullptr, *B = nullptr, *C = nullptr, *D = nullptr;   // [cap * mws][rows]
-    int32_t *part = nullptr, *tmp = nullptr, *tmp2 = nullptr, *res = nullptr, *tree = nullptr, *w = nullptr, *trtop = nullptr;   // [cap * mws]
-    // what the last read_prepare_write list left in A (RamState::memo_alone of a list): for kept_n entries with the map kept_map
-    int kept_alone = 0, kept_n = 0;
-    unsigned kept_map = 0;
-};
 
 struct fheram_bank {
     fheram_ctx* c = nullptr;      // word count M * mws; never row-sharded, never part of a group
     int M = 0, mws = 0;
     RamState ram[FHERAM_BANK_MAX];
-    double* d_prep = nullptr;     // [n][n_digits] prepared GGSW: the digits of the k-th address of the range being read   (M > 1)
-    double* d_prep_inv = nullptr; // [n][n_digits] the inverse digits of the k-th address of the range being written      (M > 1)
-    ReadBufs list;                // fheram_bank_read_list: buffers of its own (path.hpp reads_reserve), sized by mws
+    double* d_prep = nullptr;     // [n][n_digits] prepared GGSW: the digits of the k-th address of the set being read   (M > 1)
+    double* d_prep_inv = nullptr; // [n][n_digits] the inverse digits of the k-th address of the set being written      (M > 1)
+    DenseBufs list;               // fheram_bank_read_list: buffers of its own, sized by mws
     int list_n = 0;               // entries of the last list (their results are in list.res); 0: none has run
-    WriteListBufs wl;             // fheram_bank_read_prepare_write_list / fheram_bank_write_list: buffers of their own, sized by mws
-    bool wl_holds[FHERAM_BANK_MAX] = {};   // member m is still as the list that filled wl.A left it (cleared by whatever touches the member)
+    DenseBufs wl;                 // the dense plan's buffers (read_prepare_write / write lists), sized by mws
+    // what the last dense read_prepare_write left in wl.A (RamState::memo_alone of a list): for kept_n entries with the map kept_map ...
+    int kept_alone = 0, kept_n = 0;
+    unsigned kept_map = 0;
+    bool wl_holds[FHERAM_BANK_MAX] = {};   // ... and member m is still as that operation left it (cleared by whatever touches the member)
     int wl_fail_alloc = 0;        // fheram_bank_selftest_fail_list_alloc: the wl_fail_alloc-th next device allocation of wl fails (0: none)
 };
 
 namespace {
 
-// The buffers as one operation on members [first, first + n) sees them: each starts at the range's first ciphertext (Y = n * mws is the operand set's).
+static_assert(FHERAM_READ_LIST_MAX >= FHERAM_BANK_MAX && FHERAM_READ_LIST_MAX * 4 <= 32, "a member set has four bits of the map per entry");
+// The members an operation works on, entry by entry: a range [first, first + n), or a list (checked by the caller).
+struct MemberSet {
+    int n = 0;
+    int m[FHERAM_READ_LIST_MAX];
+    static MemberSet range(int first, int n) { MemberSet s; s.n = n; for (int k = 0; k < n; k++) s.m[k] = first + k; return s; }
+    static MemberSet list(const int* members, int n) { MemberSet s; s.n = n; for (int k = 0; k < n; k++) s.m[k] = members[k]; return s; }
+    // one member, or a contiguous ascending run: the range [m[0], m[0] + n)
+    bool is_range() const { for (int k = 1; k < n; k++) if (m[k] != m[0] + k) return false; return true; }
+    unsigned map() const { unsigned v = 0; for (int k = 0; k < n; k++) v |= (unsigned)m[k] << (4 * k); return v; }   // Opnds::member_map
+};
+
+// The buffers as one operation on members [first, ...) sees them in place: each starts at the range's first ciphertext.
 RamView bank_view(const fheram_bank* b, int first) {
     RamView v = ctx_view(b->c);
     const size_t o1 = (size_t)first * b->mws * fheram_ctx::GLWE, oR = o1 * b->c->rows;
@@ -70,14 +68,10 @@ RamView bank_view(const fheram_bank* b, int first) {
     for (int32_t** p : {&v.part, &v.tmp, &v.tmp2, &v.res, &v.tree, &v.w, &v.trtop}) *p += o1;
     return v;
 }
-// the operand set of an operation on a range: one member is the plain operation on the view; more have their digits in the bank's tables
-// and address k works on member k of the view
-Opnds bank_opnds(fheram_bank* b, RamState* st, const fheram_addr* const* addrs, int n) {
-    if (n == 1) return one_addr(b->c, addrs, b->mws, st);
-    return table_opnds(b->c, st, addrs, n, b->mws, b->d_prep, b->d_prep_inv, MEMBER_MAP_IDENTITY, true);
-}
+// member m's [mws] slot of a per-ciphertext buffer of the context
+GlweRef member_slot(const fheram_bank* b, int32_t* buf, int m) { return ref(buf + (size_t)m * b->mws * fheram_ctx::GLWE, (long)fheram_ctx::GLWE, 0); }
 
-// ---- checks: the whole range (or list) before anything is enqueued --------------------------------------------------------------------
+// ---- checks: the whole set before anything is enqueued.  Each form has its own front (null arguments, n, the members); all end here -------
 int check_addrs(fheram_ctx* c, const fheram_addr* const* addrs, int n) {
     for (int k = 0; k < n; k++) {
         if (!addrs[k] || addrs[k]->ctx != c) return fail(c, FHERAM_ERR_INVALID_ARG, "address " + std::to_string(k) + " is null or does not belong to this bank (layout mismatch, ram.rs:404)");
@@ -85,76 +79,35 @@ int check_addrs(fheram_ctx* c, const fheram_addr* const* addrs, int n) {
     }
     return FHERAM_OK;
 }
-int bank_check(fheram_bank* b, int first, int n, const fheram_addr* const* addrs, int want_state) {
-    if (!b) return FHERAM_ERR_INVALID_ARG;
+// the addresses (none: a result download), every member initialised, the keys, every member in the wanted state (0: read / read_prepare_write, 1: write, -1: any, keys or not)
+int members_ready(fheram_bank* b, const MemberSet& s, const fheram_addr* const* addrs, int want_state) {
     fheram_ctx* c = b->c;
-    mid_rearm(c);
-    if (first < 0 || n < 1 || first > b->M - n)
-        return fail(c, FHERAM_ERR_INVALID_ARG, "member range [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") is empty or outside the bank's " + std::to_string(b->M) + " members");
-    if (addrs) { const int rc = check_addrs(c, addrs, n); if (rc != FHERAM_OK) return rc; }
-    for (int m = first; m < first + n; m++)
-        if (!b->ram[m].initialized) return fail(c, FHERAM_ERR_UNINITIALIZED, "unitialized memory: self.data.len()=0 (member " + std::to_string(m) + ")");
+    if (addrs) { const int rc = check_addrs(c, addrs, s.n); if (rc != FHERAM_OK) return rc; }
+    for (int k = 0; k < s.n; k++)
+        if (!b->ram[s.m[k]].initialized) return fail(c, FHERAM_ERR_UNINITIALIZED, "unitialized memory: self.data.len()=0 (member " + std::to_string(s.m[k]) + ")");
     if (want_state < 0) return FHERAM_OK;
-    if (!addrs) return fail(c, FHERAM_ERR_INVALID_ARG, "null address list");
     if (!c->keys_loaded) return fail(c, FHERAM_ERR_KEYS, "evaluation keys not loaded");
-    for (int m = first; m < first + n; m++) {
-        if (want_state == 0 && b->ram[m].state)
-            return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.read: internal state is true -> requires calling Memory.write (member " + std::to_string(m) + ")");
-        if (want_state == 1 && !b->ram[m].state)
-            return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.write: internal state is false -> requires calling Memory.read_prepare_write (member " + std::to_string(m) + ")");
+    for (int k = 0; k < s.n; k++) {
+        if (want_state == 0 && b->ram[s.m[k]].state)
+            return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.read: internal state is true -> requires calling Memory.write (member " + std::to_string(s.m[k]) + ")");
+        if (want_state == 1 && !b->ram[s.m[k]].state)
+            return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.write: internal state is false -> requires calling Memory.read_prepare_write (member " + std::to_string(s.m[k]) + ")");
     }
     return FHERAM_OK;
 }
-// the RAM state an op on [first, first + n) starts from: what read_prepare_write kept counts only when every member of the range holds it
-RamState bank_merge(const fheram_bank* b, int first, int n, bool state) {
-    RamState s{true, state, true, b->ram[first].memo_alone, false};
-    for (int m = first; m < first + n; m++) {
-        s.memo_top = s.memo_top && b->ram[m].memo_top;
-        if (b->ram[m].memo_alone != s.memo_alone) s.memo_alone = 0;
-    }
-    return s;
-}
-// ... and what the op left of it, for every member of the range; new_result: the op was a read
-void bank_assign(fheram_bank* b, int first, int n, const RamState& s, bool state, bool new_result) {
-    for (int m = first; m < first + n; m++) {
-        RamState& r = b->ram[m];
-        r.state = state; r.memo_top = s.memo_top; r.memo_alone = s.memo_alone;
-        if (new_result) r.res_in_trtop = s.res_in_trtop;
-        b->wl_holds[m] = false;
-    }
-}
-// the results of members [first, first + n), widened into h_res by the device; out: [n][mws][GLWE] int64
-int bank_result(fheram_bank* b, int first, int n, int64_t* out) {
+// a range; null_args: what the entry point found missing (refused before the call counts for the mid re-arm: a range's always was)
+int range_check(fheram_bank* b, int first, int n, const fheram_addr* const* addrs, const char* null_args, int want_state, MemberSet* s) {
+    if (!b) return FHERAM_ERR_INVALID_ARG;
     fheram_ctx* c = b->c;
-    const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
-    ResRun runs[FHERAM_BANK_MAX];
-    int n_runs = 0;
-    for (int k = 0; k < n;) {      // one run per stretch of members whose result sits in the same buffer
-        int e = k + 1;
-        while (e < n && b->ram[first + e].res_in_trtop == b->ram[first + k].res_in_trtop) e++;
-        runs[n_runs++] = ResRun{(b->ram[first + k].res_in_trtop ? c->d_trtop : c->d_res) + (size_t)(first + k) * per, (size_t)(e - k) * per};
-        k = e;
-    }
-    return result_export(c, runs, n_runs, c->h_res, c->d_h_res, out);
+    if (null_args) return fail(c, FHERAM_ERR_INVALID_ARG, null_args);
+    mid_rearm(c);
+    if (first < 0 || n < 1 || first > b->M - n)
+        return fail(c, FHERAM_ERR_INVALID_ARG, "member range [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") is empty or outside the bank's " + std::to_string(b->M) + " members");
+    *s = MemberSet::range(first, n);
+    return members_ready(b, *s, addrs, want_state);
 }
-int bank_read_op(fheram_bank* b, int first, int n, const fheram_addr* const* addrs, bool prepare_write, int64_t* out) {
-    if (b && !addrs) return fail(b->c, FHERAM_ERR_INVALID_ARG, "null address list");
-    int rc = bank_check(b, first, n, addrs, 0);
-    if (rc != FHERAM_OK) return rc;
-    fheram_ctx* c = b->c;
-    HIPCHK(c, hipSetDevice(c->device));
-    RamState st = bank_merge(b, first, n, false);
-    rc = read_impl(bank_opnds(b, &st, addrs, n), bank_view(b, first), prepare_write);
-    bank_assign(b, first, n, st, rc == FHERAM_OK && prepare_write, true);                   // ram.rs:533
-    if (rc != FHERAM_OK) return rc;
-    HIPCHK(c, hipGetLastError());
-    return out ? bank_result(b, first, n, out) : FHERAM_OK;
-}
-
-
-// ---- the read list ---------------------------------------------------------------------------------------------------------------
-// the whole list before anything is enqueued; codes, order and messages as bank_check
-int list_check(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n) {
+// a read list: any members, in any order, with repeats
+int read_list_check(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n, MemberSet* s) {
     if (!b) return FHERAM_ERR_INVALID_ARG;
     fheram_ctx* c = b->c;
     mid_rearm(c);
@@ -166,62 +119,11 @@ int list_check(fheram_bank* b, const int* members, const fheram_addr* const* add
     for (int k = 0; k < n; k++)
         if (members[k] < 0 || members[k] >= b->M)
             return fail(c, FHERAM_ERR_INVALID_ARG, "entry " + std::to_string(k) + " names member " + std::to_string(members[k]) + ", outside the bank's " + std::to_string(b->M) + " members");
-    const int rc = check_addrs(c, addrs, n);
-    if (rc != FHERAM_OK) return rc;
-    for (int k = 0; k < n; k++)
-        if (!b->ram[members[k]].initialized) return fail(c, FHERAM_ERR_UNINITIALIZED, "unitialized memory: self.data.len()=0 (member " + std::to_string(members[k]) + ")");
-    if (!c->keys_loaded) return fail(c, FHERAM_ERR_KEYS, "evaluation keys not loaded");
-    for (int k = 0; k < n; k++)
-        if (b->ram[members[k]].state)
-            return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.read: internal state is true -> requires calling Memory.write (member " + std::to_string(members[k]) + ")");
-    return FHERAM_OK;
+    *s = MemberSet::list(members, n);
+    return members_ready(b, *s, addrs, 0);
 }
-int list_result(fheram_bank* b, int first, int n, int64_t* out) { return reads_export(b->c, b->list, (size_t)first * b->mws, (size_t)n * b->mws, out); }
-
-// ---- the write lists -------------------------------------------------------------------------------------------------------------
-void wlist_free(WriteListBufs& L) {
-    void* bufs[] = {L.A, L.B, L.C, L.D, L.part, L.tmp, L.tmp2, L.res, L.tree, L.w, L.trtop};
-    for (void* p : bufs) if (p) hipFree(p);
-    L = WriteListBufs{};
-}
-// grows the buffers to n entries of ws ciphertexts; on failure the bank holds none of them (and every other operation is unaffected: what a
-// prepared member needs for its write is in its own slots).  Regrowing drops the kept arena, never a member's state.
-int wlist_reserve(fheram_ctx* c, WriteListBufs& L, int n, int ws, int* fail_alloc) {
-    if (n <= L.cap) return FHERAM_OK;
-    if (L.cap) { for (hipStream_t s : {c->stream, c->stream2}) HIPCHK(c, hipStreamSynchronize(s)); wlist_free(L); }
-    const size_t G = fheram_ctx::GLWE, nct = (size_t)n * ws, nrow = nct * c->rows;
-    hipError_t e = hipSuccess;
-    auto dev = [&](int32_t** p, size_t glwes) {
-        if (e != hipSuccess) return;
-        if (*fail_alloc > 0 && --*fail_alloc == 0) e = hipErrorOutOfMemory;   // (the self-test's: as the runtime reports an exhausted device)
-        else e = hipMalloc((void**)p, glwes * G * sizeof(int32_t));
-    };
-    for (int32_t** p : {&L.A, &L.B, &L.C, &L.D}) dev(p, nrow);
-    for (int32_t** p : {&L.part, &L.tmp, &L.tmp2, &L.res, &L.tree, &L.w, &L.trtop}) dev(p, nct);
-    if (e != hipSuccess) {
-        wlist_free(L);
-        (void)hipGetLastError();   // the next op's error check must not see this allocation's failure
-        return fail(c, FHERAM_ERR_DEVICE, std::string("buffers of a write list of ") + std::to_string(n) + " members: " + hipGetErrorString(e));
-    }
-    L.cap = n;
-    return FHERAM_OK;
-}
-RamView wlist_view(const fheram_bank* b) {
-    const WriteListBufs& L = b->wl;
-    return RamView{b->c->d_data, L.A, L.B, L.C, L.D, L.part, L.tmp, L.tmp2, L.res, L.tree, L.w, L.trtop};
-}
-unsigned wlist_map(const int* members, int n) {
-    unsigned map = 0;
-    for (int k = 0; k < n; k++) map |= (unsigned)members[k] << (4 * k);
-    return map;
-}
-// a list of one member or of a contiguous ascending run is the range [members[0], members[0] + n)
-bool wlist_is_range(const int* members, int n) {
-    for (int k = 1; k < n; k++) if (members[k] != members[0] + k) return false;
-    return true;
-}
-// the whole list before anything is enqueued; codes, order and messages as list_check.  want_state: 0 read_prepare_write, 1 write
-int wlist_check(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n, bool null_words, int want_state) {
+// a read_prepare_write (want_state 0) or write (1, which also has words) list: distinct members, in any order
+int write_list_check(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n, bool null_words, int want_state, MemberSet* s) {
     if (!b) return FHERAM_ERR_INVALID_ARG;
     fheram_ctx* c = b->c;
     mid_rearm(c);
@@ -236,21 +138,119 @@ int wlist_check(fheram_bank* b, const int* members, const fheram_addr* const* ad
             return fail(c, FHERAM_ERR_INVALID_ARG, "entry " + std::to_string(k) + " names member " + std::to_string(members[k]) + " a second time: a RAM has one pending write (ram.rs:196-294), so the members of a write list are distinct");
         seen |= 1u << members[k];
     }
-    const int rc = check_addrs(c, addrs, n);
-    if (rc != FHERAM_OK) return rc;
-    for (int k = 0; k < n; k++)
-        if (!b->ram[members[k]].initialized) return fail(c, FHERAM_ERR_UNINITIALIZED, "unitialized memory: self.data.len()=0 (member " + std::to_string(members[k]) + ")");
-    if (!c->keys_loaded) return fail(c, FHERAM_ERR_KEYS, "evaluation keys not loaded");
-    for (int k = 0; k < n; k++) {
-        if (want_state == 0 && b->ram[members[k]].state)
-            return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.read: internal state is true -> requires calling Memory.write (member " + std::to_string(members[k]) + ")");
-        if (want_state == 1 && !b->ram[members[k]].state)
-            return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.write: internal state is false -> requires calling Memory.read_prepare_write (member " + std::to_string(members[k]) + ")");
+    *s = MemberSet::list(members, n);
+    return members_ready(b, *s, addrs, want_state);
+}
+
+// ---- the plan of a read_prepare_write / write on a member set (header comment) ----------------------------------------------------------
+// The RAM state the operation starts from.  In place: the merge of the members'.  Dense: trace(top) when every member holds its own, the
+// kept arena when it is this very set's and every member still holds it.
+RamState set_state(const fheram_bank* b, const MemberSet& s, bool dense, bool write) {
+    RamState st{true, write, true, dense ? 0 : b->ram[s.m[0]].memo_alone, false};
+    bool holds = dense && write && b->kept_alone > 0 && b->kept_n == s.n && b->kept_map == s.map();
+    for (int k = 0; k < s.n; k++) {
+        const RamState& r = b->ram[s.m[k]];
+        st.memo_top = st.memo_top && r.memo_top;
+        if (!dense && r.memo_alone != st.memo_alone) st.memo_alone = 0;
+        holds = holds && b->wl_holds[s.m[k]];
     }
+    if (holds) st.memo_alone = b->kept_alone;
+    return st;
+}
+struct SetPlan {
+    const bool dense;   // (its buffers reserved by the caller)
+    RamState st;
+    const RamView v;
+    const Opnds o;      // o.st points at st: a plan is built where it lives
+    SetPlan(fheram_bank* b, const MemberSet& s, const fheram_addr* const* addrs, bool write)
+        : dense(!s.is_range()), st(set_state(b, s, dense, write)), v(dense ? dense_view(b->c, b->wl) : bank_view(b, s.m[0])),
+          o(s.n == 1 ? one_addr(b->c, addrs, b->mws, &st)
+                     : table_opnds(b->c, &st, addrs, s.n, b->mws, b->d_prep, b->d_prep_inv, dense ? s.map() : MEMBER_MAP_IDENTITY, true)) {}
+    SetPlan(const SetPlan&) = delete;
+};
+// what the operation left, for every member of the set; new_result: it was a read.  A member's memo_alone speaks of the context's arena, so
+// a dense operation leaves 0 there and says in wl_holds whether the lists' arena holds the member's rows.
+void set_assign(fheram_bank* b, const MemberSet& s, const RamState& st, bool dense, bool state, bool new_result) {
+    for (int k = 0; k < s.n; k++) {
+        RamState& r = b->ram[s.m[k]];
+        r.state = state; r.memo_top = st.memo_top; r.memo_alone = dense ? 0 : st.memo_alone;
+        if (new_result) r.res_in_trtop = st.res_in_trtop;
+        b->wl_holds[s.m[k]] = dense && st.memo_alone > 0;
+    }
+}
+// the results of the set's members, widened into h_res by the device; out: [n][mws][GLWE] int64.  In place: one run per stretch of members
+// whose result sits in the same buffer; dense: one per entry.
+int set_result(fheram_bank* b, const MemberSet& s, bool dense, int64_t* out) {
+    fheram_ctx* c = b->c;
+    const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
+    ResRun runs[FHERAM_BANK_MAX];
+    int n_runs = 0;
+    for (int k = 0; k < s.n; k++) {
+        const int32_t* src = (b->ram[s.m[k]].res_in_trtop ? c->d_trtop : c->d_res) + (size_t)s.m[k] * per;
+        if (!dense && n_runs && runs[n_runs - 1].src + runs[n_runs - 1].n == src) runs[n_runs - 1].n += per;
+        else runs[n_runs++] = ResRun{src, per};
+    }
+    return result_export(c, runs, n_runs, c->h_res, c->d_h_res, out);
+}
+// Ram::read / read_prepare_write on every member of a checked set as one operation
+int bank_read_set(fheram_bank* b, const MemberSet& s, const fheram_addr* const* addrs, bool prepare_write, int64_t* out) {
+    fheram_ctx* c = b->c;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!s.is_range()) {
+        const int rc = dense_reserve(c, b->wl, s.n, b->mws, true, &b->wl_fail_alloc);
+        if (rc != FHERAM_OK) return rc;
+        b->kept_alone = 0;   // arena A is this operation's from here on
+    }
+    SetPlan p(b, s, addrs, false);
+    const int rc = read_impl(p.o, p.v, prepare_write);
+    if (rc == FHERAM_OK && p.dense) {   // the hand-over: tree top and result into every member's own slots, where a range, a single call or a download looks for them
+        const long G = (long)fheram_ctx::GLWE;
+        for (int k = 0; k < s.n; k++) {
+            if (c->n2 == 2) launch_copy(c, p.o.slice(ref(p.v.tree, G, 0), k), member_slot(b, c->d_tree, s.m[k]), 1, b->mws);
+            launch_copy(c, p.o.slice(ref(p.st.res_in_trtop ? p.v.trtop : p.v.res, G, 0), k), member_slot(b, p.st.res_in_trtop ? c->d_trtop : c->d_res, s.m[k]), 1, b->mws);
+        }
+        b->kept_alone = p.st.memo_alone; b->kept_n = s.n; b->kept_map = p.o.member_map;
+    }
+    set_assign(b, s, p.st, p.dense, rc == FHERAM_OK && prepare_write, true);                // ram.rs:533
+    if (rc != FHERAM_OK) return rc;
+    HIPCHK(c, hipGetLastError());
+    return out ? set_result(b, s, p.dense, out) : FHERAM_OK;
+}
+// Ram::write on every member of a checked set as one operation; stage(d_w, ciphertexts): path.hpp write_all
+template <typename S>
+int bank_write_set(fheram_bank* b, const MemberSet& s, const fheram_addr* const* addrs, S&& stage) {
+    fheram_ctx* c = b->c;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!s.is_range()) {
+        const int rc = dense_reserve(c, b->wl, s.n, b->mws, true, &b->wl_fail_alloc);
+        if (rc != FHERAM_OK) return rc;
+    }
+    SetPlan p(b, s, addrs, true);
+    const long G = (long)fheram_ctx::GLWE;
+    if (p.dense) {
+        // The gather: every member's tree top and trace(top) into the dense buffers — unless this very set prepared the members and all
+        // still hold it (the plan's state then resumes from the kept arena): then tree and trtop are what the hand-over copied FROM, nothing
+        // has written them since, no launch is needed, and write_side_begin may skip its fork event after a host wait as a range's does
+        // (main_idle).  With a gather the main stream has work again, so the side stage forks behind it: one event record.
+        const bool holds = p.st.memo_alone > 0;
+        b->kept_alone = 0;   // consumed, or overwritten by this write's trace(ct_hi)
+        if (!holds) {
+            main_enqueued(c);
+            for (int k = 0; k < s.n; k++) {
+                if (c->n2 == 2) launch_copy(c, member_slot(b, c->d_tree, s.m[k]), p.o.slice(ref(p.v.tree, G, 0), k), 1, b->mws);
+                if (p.st.memo_top) launch_copy(c, member_slot(b, c->d_trtop, s.m[k]), p.o.slice(ref(p.v.trtop, G, 0), k), 1, b->mws);
+            }
+        }
+    }
+    const int rc = write_all(p.o, p.v, stage);   // (refused words: nothing of the members has been touched)
+    if (rc == FHERAM_OK && p.dense && c->n2 == 2)   // the scatter: the tree's new top (ct_lo, rotated) back into every member's slot
+        for (int k = 0; k < s.n; k++) launch_copy(c, p.o.slice(ref(p.v.tree, G, 0), k), member_slot(b, c->d_tree, s.m[k]), 1, b->mws);
+    set_assign(b, s, p.st, p.dense, rc != FHERAM_OK, false);                                // ram.rs:648
+    if (rc != FHERAM_OK) return rc;
+    HIPCHK(c, hipGetLastError());
     return FHERAM_OK;
 }
-// member m's [mws] slot of a per-ciphertext buffer of the context
-GlweRef member_slot(const fheram_bank* b, int32_t* buf, int m) { return ref(buf + (size_t)m * b->mws * fheram_ctx::GLWE, (long)fheram_ctx::GLWE, 0); }
+int list_result(fheram_bank* b, int first, int n, int64_t* out) { return reads_export(b->c, b->list, (size_t)first * b->mws, (size_t)n * b->mws, out); }
 
 }  // namespace
 
@@ -291,8 +291,8 @@ int fheram_bank_create(const fheram_params* p, int device, int n_members, const 
 void fheram_bank_destroy(fheram_bank* b) {
     if (!b) return;
     if (b->c) { hipSetDevice(b->c->device); for (hipStream_t s : {b->c->stream, b->c->stream2}) if (s) hipStreamSynchronize(s); }
-    reads_free(b->list);
-    wlist_free(b->wl);
+    dense_free(b->list);
+    dense_free(b->wl);
     fheram_ctx_destroy(b->c);
     delete b;
 }
@@ -363,166 +363,72 @@ int fheram_bank_address_derive(fheram_bank* b, const fheram_fheuint* const* fus,
 }
 
 int fheram_bank_read(fheram_bank* b, int first, int n, const fheram_addr* const* addrs, int64_t* out) {
-    return bank_read_op(b, first, n, addrs, false, out);
+    MemberSet s;
+    const int rc = range_check(b, first, n, addrs, addrs ? nullptr : "null address list", 0, &s);
+    return rc == FHERAM_OK ? bank_read_set(b, s, addrs, false, out) : rc;
 }
 int fheram_bank_read_prepare_write(fheram_bank* b, int first, int n, const fheram_addr* const* addrs, int64_t* out) {
-    return bank_read_op(b, first, n, addrs, true, out);
+    MemberSet s;
+    const int rc = range_check(b, first, n, addrs, addrs ? nullptr : "null address list", 0, &s);
+    return rc == FHERAM_OK ? bank_read_set(b, s, addrs, true, out) : rc;
 }
 int fheram_bank_write(fheram_bank* b, int first, int n, const int64_t* w, const fheram_addr* const* addrs) {
-    if (b && (!addrs || !w)) return fail(b->c, FHERAM_ERR_INVALID_ARG, "null address list or null words");
-    int rc = bank_check(b, first, n, addrs, 1);
-    if (rc != FHERAM_OK) return rc;
-    fheram_ctx* c = b->c;
-    HIPCHK(c, hipSetDevice(c->device));
-    RamState st = bank_merge(b, first, n, true);
-    const Opnds o = bank_opnds(b, &st, addrs, n);
-    const RamView v = bank_view(b, first);
-    write_side_begin(o, v);                         // as fheram_write: the part that needs no words is enqueued before the host narrows them
-    rc = stage_words(c, v.w, w, n * b->mws);
-    if (rc != FHERAM_OK) {                          // (a limb out of range: nothing of the members has been touched)
-        write_side_abort(c);
-        bank_assign(b, first, n, st, true, false);
-        return rc;
-    }
-    rc = write_top(o, v);
-    if (rc == FHERAM_OK) rc = write_rows(o, v);
-    bank_assign(b, first, n, st, rc != FHERAM_OK, false);                                   // ram.rs:648
-    if (rc != FHERAM_OK) return rc;
-    HIPCHK(c, hipGetLastError());
-    return FHERAM_OK;
+    MemberSet s;
+    const int rc = range_check(b, first, n, addrs, (addrs && w) ? nullptr : "null address list or null words", 1, &s);
+    return rc == FHERAM_OK ? bank_write_set(b, s, addrs, [&](int32_t* d_w, int n_ct) { return stage_words(b->c, d_w, w, n_ct); }) : rc;
 }
 int fheram_bank_result_download(fheram_bank* b, int first, int n, int64_t* out) {
     if (!b) return FHERAM_ERR_INVALID_ARG;
     if (!out) return fail(b->c, FHERAM_ERR_INVALID_ARG, "null output");
-    const int rc = bank_check(b, first, n, nullptr, -1);
+    MemberSet s;
+    const int rc = range_check(b, first, n, nullptr, nullptr, -1, &s);
     if (rc != FHERAM_OK) return rc;
     HIPCHK(b->c, hipSetDevice(b->c->device));
-    return bank_result(b, first, n, out);
+    return set_result(b, s, false, out);
 }
 // K = n independent Ram::read (ram.rs:172-191), entry k on member members[k], as one operation: path.hpp read_many with the members as the
 // source map, on the list's own buffers and a scratch RamState.  What the sequence of those K single-member reads leaves: every named member
 // in state 0 with nothing kept for a write, the result of the last entry that named it where its own read would have left it (its slice of
 // d_res); every other member as it was.  A bank of one member has one source: the list is what fheram_read_batch runs.
 int fheram_bank_read_list(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n, int64_t* out) {
-    int rc = list_check(b, members, addrs, n);
+    MemberSet s;
+    int rc = read_list_check(b, members, addrs, n, &s);
     if (rc != FHERAM_OK) return rc;
     fheram_ctx* c = b->c;
     HIPCHK(c, hipSetDevice(c->device));
     const long G = (long)fheram_ctx::GLWE;
-    auto res_of = [&](int m) { return ref(c->d_res + (size_t)m * b->mws * G, G, 0); };
     b->list_n = 0;   // until this list is enqueued there is no last list: several entries overwrite res as they run (one entry only with its closing copy, but the rule is one)
     if (n == 1) {   // the plain single-member read; its result is also the list's
-        rc = reads_reserve(c, b->list, 1, b->mws);
-        if (rc == FHERAM_OK) rc = bank_read_op(b, members[0], 1, addrs, false, nullptr);
+        rc = dense_reserve(c, b->list, 1, b->mws);
+        if (rc == FHERAM_OK) rc = bank_read_set(b, s, addrs, false, nullptr);
         if (rc != FHERAM_OK) return rc;
-        launch_copy(c, res_of(members[0]), ref(b->list.res, G, 0), 1, b->mws);
+        launch_copy(c, member_slot(b, c->d_res, s.m[0]), ref(b->list.res, G, 0), 1, b->mws);
         b->list_n = 1;
         HIPCHK(c, hipGetLastError());
         return out ? list_result(b, 0, 1, out) : FHERAM_OK;
     }
     RamState st{true, false, false, 0, false};
-    unsigned map = 0;
-    for (int k = 0; k < n; k++) map |= (unsigned)members[k] << (4 * k);
-    return read_many(c, b->list, &st, addrs, n, b->mws, map, b->M > 1, out, [&](const Opnds& o) {
+    return read_many(c, b->list, &st, addrs, n, b->mws, s.map(), b->M > 1, out, [&](const Opnds& o) {
+        set_assign(b, s, st, false, false, true);   // every named member: as a read leaves it
         for (int m = 0; m < b->M; m++) {
             int last = -1;
-            for (int k = 0; k < n; k++) if (members[k] == m) last = k;
-            if (last < 0) continue;
-            RamState& r = b->ram[m];
-            r.state = false; r.memo_top = false; r.memo_alone = 0; r.res_in_trtop = false;
-            launch_copy(c, o.slice(ref(b->list.res, G, 0), last), res_of(m), 1, b->mws);
+            for (int k = 0; k < n; k++) if (s.m[k] == m) last = k;
+            if (last >= 0) launch_copy(c, o.slice(ref(b->list.res, G, 0), last), member_slot(b, c->d_res, m), 1, b->mws);
         }
         b->list_n = n;
     });
 }
-// n independent Ram::read_prepare_write (ram.rs:196-222), entry k on member members[k], as one operation (header comment: a write list).
+// n independent Ram::read_prepare_write (ram.rs:196-222), entry k on member members[k], as one operation (header comment)
 int fheram_bank_read_prepare_write_list(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n, int64_t* out) {
-    int rc = wlist_check(b, members, addrs, n, false, 0);
-    if (rc != FHERAM_OK) return rc;
-    if (wlist_is_range(members, n)) return bank_read_op(b, members[0], n, addrs, true, out);
-    fheram_ctx* c = b->c;
-    HIPCHK(c, hipSetDevice(c->device));
-    rc = wlist_reserve(c, b->wl, n, b->mws, &b->wl_fail_alloc);
-    if (rc != FHERAM_OK) return rc;
-    WriteListBufs& L = b->wl;
-    L.kept_alone = 0;   // arena A is this list's from here on
-    RamState st{true, false, false, 0, false};
-    const Opnds o = table_opnds(c, &st, addrs, n, b->mws, b->d_prep, b->d_prep_inv, wlist_map(members, n), true);
-    rc = read_impl(o, wlist_view(b), true);
-    if (rc != FHERAM_OK) return rc;
-    // the hand-over: tree top and result into every member's own slots, where a range, a single call or a download looks for them
-    const long G = (long)fheram_ctx::GLWE;
-    ResRun runs[FHERAM_BANK_MAX];
-    for (int k = 0; k < n; k++) {
-        const int m = members[k];
-        if (c->n2 == 2) launch_copy(c, o.slice(ref(L.tree, G, 0), k), member_slot(b, c->d_tree, m), 1, b->mws);
-        int32_t* res_to = st.res_in_trtop ? c->d_trtop : c->d_res;
-        launch_copy(c, o.slice(ref(st.res_in_trtop ? L.trtop : L.res, G, 0), k), member_slot(b, res_to, m), 1, b->mws);
-        RamState& r = b->ram[m];
-        r.state = true; r.memo_top = st.memo_top; r.memo_alone = 0; r.res_in_trtop = st.res_in_trtop;   // (memo_alone is the context's arena: not this list's)
-        b->wl_holds[m] = st.memo_alone > 0;
-        runs[k] = ResRun{member_slot(b, res_to, m).p, (size_t)b->mws * fheram_ctx::GLWE};
-    }
-    L.kept_alone = st.memo_alone; L.kept_n = n; L.kept_map = o.member_map;
-    HIPCHK(c, hipGetLastError());
-    return out ? result_export(c, runs, n, c->h_res, c->d_h_res, out) : FHERAM_OK;
+    MemberSet s;
+    const int rc = write_list_check(b, members, addrs, n, false, 0, &s);
+    return rc == FHERAM_OK ? bank_read_set(b, s, addrs, true, out) : rc;
 }
-// n independent Ram::write (ram.rs:226-294), entry k of w to member members[k], as one operation (header comment: a write list).
+// n independent Ram::write (ram.rs:226-294), entry k of w to member members[k], as one operation (header comment)
 int fheram_bank_write_list(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n, const int64_t* w) {
-    int rc = wlist_check(b, members, addrs, n, !w, 1);
-    if (rc != FHERAM_OK) return rc;
-    if (wlist_is_range(members, n)) return fheram_bank_write(b, members[0], n, w, addrs);
-    fheram_ctx* c = b->c;
-    HIPCHK(c, hipSetDevice(c->device));
-    rc = wlist_reserve(c, b->wl, n, b->mws, &b->wl_fail_alloc);
-    if (rc != FHERAM_OK) return rc;
-    WriteListBufs& L = b->wl;
-    const unsigned map = wlist_map(members, n);
-    // what the write resumes from: trace(top) when every member holds its own, the kept arena when it is this very list's
-    RamState st{true, true, true, 0, false};
-    bool holds = L.kept_alone > 0 && L.kept_n == n && L.kept_map == map;
-    for (int k = 0; k < n; k++) {
-        st.memo_top = st.memo_top && b->ram[members[k]].memo_top;
-        holds = holds && b->wl_holds[members[k]];
-    }
-    if (holds) st.memo_alone = L.kept_alone;
-    L.kept_alone = 0;   // consumed, or overwritten by this write's trace(ct_hi)
-    const Opnds o = table_opnds(c, &st, addrs, n, b->mws, b->d_prep, b->d_prep_inv, map, true);
-    const RamView v = wlist_view(b);
-    const long G = (long)fheram_ctx::GLWE;
-    // The gather: every member's tree top and trace(top) into the list's dense buffers — unless this very list prepared the members and
-    // all still hold it (holds): then L.tree and L.trtop are what the hand-over copied FROM, nothing has written them since (every list
-    // operation ends `holds`), no launch is needed, and write_side_begin may skip its fork event after a host wait as fheram_bank_write's
-    // does (main_idle).  With a gather the main stream has work again, so the side stage forks behind it: one event record.
-    if (!holds) {
-        main_enqueued(c);
-        for (int k = 0; k < n; k++) {
-            if (c->n2 == 2) launch_copy(c, member_slot(b, c->d_tree, members[k]), o.slice(ref(L.tree, G, 0), k), 1, b->mws);
-            if (st.memo_top) launch_copy(c, member_slot(b, c->d_trtop, members[k]), o.slice(ref(L.trtop, G, 0), k), 1, b->mws);
-        }
-    }
-    auto assign = [&](bool state) {
-        for (int k = 0; k < n; k++) {
-            RamState& r = b->ram[members[k]];
-            r.state = state; r.memo_top = st.memo_top; r.memo_alone = 0;
-            b->wl_holds[members[k]] = false;
-        }
-    };
-    write_side_begin(o, v);
-    rc = stage_words(c, v.w, w, n * b->mws);
-    if (rc != FHERAM_OK) {                          // (a limb out of range: nothing of the members has been touched)
-        write_side_abort(c);
-        assign(true);
-        return rc;
-    }
-    rc = write_top(o, v);
-    if (rc == FHERAM_OK) rc = write_rows(o, v);
-    if (rc == FHERAM_OK && c->n2 == 2)              // the scatter: the tree's new top (ct_lo, rotated) back into every member's slot
-        for (int k = 0; k < n; k++) launch_copy(c, o.slice(ref(L.tree, G, 0), k), member_slot(b, c->d_tree, members[k]), 1, b->mws);
-    assign(rc != FHERAM_OK);                                                                // ram.rs:648
-    if (rc != FHERAM_OK) return rc;
-    HIPCHK(c, hipGetLastError());
-    return FHERAM_OK;
+    MemberSet s;
+    const int rc = write_list_check(b, members, addrs, n, !w, 1, &s);
+    return rc == FHERAM_OK ? bank_write_set(b, s, addrs, [&](int32_t* d_w, int n_ct) { return stage_words(b->c, d_w, w, n_ct); }) : rc;
 }
 int fheram_bank_selftest_fail_list_alloc(fheram_bank* b, int nth) {
     if (!b || nth < 0) return FHERAM_ERR_INVALID_ARG;

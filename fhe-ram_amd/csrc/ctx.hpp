@@ -47,17 +47,18 @@ struct RamState {
     bool res_in_trtop = false;   // the last read / read_prepare_write left its result in d_trtop (else d_res)
 };
 
-// The buffers of a read of several addresses as one operation (fheram_read_batch: the context's; fheram_bank_read_list: the bank's, sized by
-// the members' word count, not by the context's, which is the whole bank's): for `cap` addresses of ws ciphertexts, allocated on first use,
-// grown to the largest operation seen (path.hpp reads_reserve), freed with their owner.  Ciphertext y = k * ws + w is word w of address k;
-// the arenas keep the rows' stride (sy = rows * GLWE).  Every launch of such an operation writes these only (path.hpp reads_view).
-struct ReadBufs {
+// The DENSE buffers of an operation on several addresses that does not run in place: every per-ciphertext and per-row buffer of a RamView
+// (path.hpp) but the rows, for `cap` addresses of ws ciphertexts.  Ciphertext y = k * ws + w is word w of address k; the arenas keep the
+// rows' stride (sy = rows * GLWE).  Three owners: fheram_read_batch (the context's `batch`), fheram_bank_read_list and the bank's
+// read_prepare_write / write lists (bank.hpp; sized by the members' word count, not by the context's, which is the whole bank's).
+// Allocated on first use with what the owner's operations need (path.hpp dense_reserve), grown to the largest operation seen, freed with
+// the owner; every launch of such an operation writes these only (path.hpp dense_view).
+struct DenseBufs {
     int cap = 0;
-    int32_t *A = nullptr, *B = nullptr;   // [cap * ws][rows]  ping-pong arenas (these, tmp, tmp2 and prep: from the first operation of several addresses on)
-    int32_t* C = nullptr;                 // [cap * ws][rows]  only where the alone levels run as the tail chain (path.hpp third_arena_needed)
-    int32_t *res = nullptr, *tmp = nullptr, *tmp2 = nullptr;   // [cap * ws]
-    double* prep = nullptr;               // [cap][n_digits] prepared GGSW: address k's digits
-    int64_t *h_res = nullptr, *d_h_res = nullptr;   // pinned, device-visible: the results as int64 (+ the monitor's maximum), as fheram_ctx::h_res
+    int32_t *A = nullptr, *B = nullptr, *C = nullptr, *D = nullptr;   // [cap * ws][rows]  reads: A and B from the first operation of several addresses on, C only where the alone levels run as the tail chain (path.hpp third_arena_needed), never D
+    int32_t *part = nullptr, *tmp = nullptr, *tmp2 = nullptr, *res = nullptr, *tree = nullptr, *w = nullptr, *trtop = nullptr;   // [cap * ws]  reads: res, and tmp / tmp2 with A and B
+    double* prep = nullptr;               // [cap][n_digits] prepared GGSW, address k's digits: reads only, with A and B (a bank's write lists use the bank's tables)
+    int64_t *h_res = nullptr, *d_h_res = nullptr;   // reads only — pinned, device-visible: the results as int64 (+ the monitor's maximum), as fheram_ctx::h_res
 };
 
 // ---- the execution switches (include/fheram.h fheram_config): two pure host functions, no HIP call in them -------------------------------
@@ -168,7 +169,7 @@ struct fheram_ctx {
     int32_t* d_part = nullptr;     // [ws]            this shard's partial pack / the un-rotated ct_lo
     int32_t* d_gat[3] = {nullptr, nullptr, nullptr};   // [n_shards][ws] gathered partials + ping-pong (root)
     RamState ram;                  // this context's RAM (a bank's context: unused, the members' are in fheram_bank)
-    ReadBufs batch;                // fheram_read_batch: its arenas, results and digit table (path.hpp reads_reserve / reads_view), sized by this context's word count
+    DenseBufs batch;               // fheram_read_batch: its arenas, results and digit table (path.hpp dense_reserve / dense_view), sized by this context's word count
     // ---- launcher scratch ----
     double* d_big = nullptr;       // [LIMB_SPLIT_MAX ciphertexts] un-normalised limbs of the limb-parallel path
     double* d_big2 = nullptr;      // same, for launches on the side stream

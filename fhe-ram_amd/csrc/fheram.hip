@@ -242,7 +242,7 @@ void fheram_ctx_destroy(fheram_ctx* c) {
     hipSetDevice(c->device);
     for (hipStream_t s : {c->stream, c->stream2}) if (s) hipStreamSynchronize(s);
     prof_collect(c);
-    reads_free(c->batch);
+    dense_free(c->batch);
     c->res.release();
     for (hipStream_t s : {c->stream2, c->stream}) if (s) hipStreamDestroy(s);   // (null in a context whose creation failed before it had them)
     delete c;

@@ -3,7 +3,7 @@
 // operand set (Opnds: whose digits a product uses, whose RAM state it updates) and a view (RamView: the buffers it runs on).  The plain context, the stages of
 // a row-sharded RAM (fheram.hip, group.hpp), fheram_read_batch and fheram_bank_* (bank.hpp; its read list and write lists too) all run these; what is specific to one of them
 // is a visible condition in the sequence (n == 1: pre_inv, the gate wave, ev_opstart, ev_wdone, sharding, capture; a bank range or list: Opnds::bank in row_fuse).
-// Several addresses are ONE kind of operand set (table_opnds: a digit table and a member map) and several reads ONE buffer set (ReadBufs, read_many).
+// Several addresses are ONE kind of operand set (table_opnds: a digit table and a member map) and several reads ONE buffer set (DenseBufs, read_many).
 #pragma once
 #include "launch.hpp"
 
@@ -54,7 +54,7 @@ Opnds table_opnds(fheram_ctx* c, RamState* st, const fheram_addr* const* addrs, 
 
 // An operation's VIEW: every buffer indexed by ciphertext y, from the operation's first.  The rows, the ping-pong arenas A / B with the third
 // and fourth (pack_levels P0 / P1; the write's trace(ct_hi)), the per-ciphertext buffers, and where the result goes.  The context's own
-// (ctx_view), those of a read of several addresses (reads_view below: a batch's or a read list's, never written through), or a range of a bank's members (bank.hpp bank_view).
+// (ctx_view), those of a read of several addresses (dense_view below: a batch's, a read list's or a write list's), or a range of a bank's members (bank.hpp bank_view).
 struct RamView {
     int32_t *rows, *A, *B, *C, *D;   // [Y][rows]
     int32_t *part, *tmp, *tmp2, *res, *tree, *w, *trtop;   // [Y]; part: the packed row where no arena holds it (rows == 1, a shard's partial) / the un-rotated ct_lo
@@ -253,13 +253,14 @@ int read_impl(const Opnds& o, const RamView& a, bool prepare_write) {
 // ---- several Ram::read (ram.rs:172-191) as one launch sequence: fheram_read_batch, fheram_bank_read_list ------------------------------
 // A read does not change the RAM (SubRam::read asserts !state and only writes its scratch, ram.rs:393-396): n reads at n addresses share the
 // keys and every packing and trace step; only the products with the address digits differ (and, in a bank, whose rows they read).  Such an
-// operation runs on buffers of its own (ctx.hpp ReadBufs), [n * ws][rows] GLWEs with the rows' stride, so that ciphertext y = k * ws + w is
-// word w of address k and every address-independent step is ONE launch over gy = n * ws.
-void reads_free(ReadBufs& L) {
-    void* bufs[] = {L.A, L.B, L.C, L.res, L.tmp, L.tmp2, L.prep};
+// operation runs on a dense buffer set of its own (ctx.hpp DenseBufs), [n * ws][rows] GLWEs with the rows' stride, so that ciphertext y = k * ws + w is
+// word w of address k and every address-independent step is ONE launch over gy = n * ws.  A bank's read_prepare_write / write lists run on
+// such a set too (bank.hpp), with every buffer of a view in it.
+void dense_free(DenseBufs& L) {
+    void* bufs[] = {L.A, L.B, L.C, L.D, L.part, L.tmp, L.tmp2, L.res, L.tree, L.w, L.trtop, L.prep};
     for (void* p : bufs) if (p) hipFree(p);
     if (L.h_res) hipHostFree(L.h_res);
-    L = ReadBufs{};
+    L = DenseBufs{};
 }
 // The third arena is only needed where the alone packer levels run as the single-launch tail chain on the operation's rows (at most
 // TAIL_GROUPS ciphertexts: 2^13 with n * ws <= 4), whose source must survive the launch (pack_levels P0): allocated only then.
@@ -268,41 +269,57 @@ void reads_free(ReadBufs& L) {
 bool third_arena_needed(const fheram_ctx* c, int n_ct) {
     return c->n2 == 2 && chain_form(c, ChainQuery{false, LOGN - ilog2_ceil(c->rows_glob), (int)c->rows, n_ct}).form == ChainForm::Tail;
 }
-// grows the buffers to n addresses of ws ciphertexts (and adds the third arena when this operation needs it); on failure the owner holds
-// none of them (and every other operation is unaffected).  One address is the plain read on the RAM's own buffers: it needs the result
-// buffers only, so the arenas, the temporaries and the digit table wait for the first operation of several addresses.  Regrowing never
-// drops what existed.
-int reads_reserve(fheram_ctx* c, ReadBufs& L, int n, int ws) {
-    const bool work = n > 1, third = work && third_arena_needed(c, n * ws);
+// Grows the set to n addresses of ws ciphertexts with what the caller's operation needs; on failure the owner holds none of it (and every
+// other operation is unaffected).  Regrowing never drops what existed, and keeps the capacity when only buffers are added.
+//   reads (a batch, a read list): the result and its pinned copy always.  One address is the plain read on the RAM's own buffers, so the
+//     arenas, the temporaries and the digit table wait for the first operation of several addresses, and the third arena for the first that needs it.
+//   all (a bank's write lists): the four arenas and the seven per-ciphertext buffers, in the view's order; the side stream may still be
+//     working on them; fail_alloc (the self-test's): the *fail_alloc-th of these allocations reports an exhausted device.
+int dense_reserve(fheram_ctx* c, DenseBufs& L, int n, int ws, bool all = false, int* fail_alloc = nullptr) {
+    const bool work = all || n > 1, third = all || (work && third_arena_needed(c, n * ws));
     if (n <= L.cap && (!work || L.A) && (!third || L.C)) return FHERAM_OK;
     if (n < L.cap) n = L.cap;   // (only the working buffers or the third arena are missing: keep the capacity)
-    const bool had_work = L.A != nullptr, had_third = L.C != nullptr;
-    if (L.cap) { HIPCHK(c, hipStreamSynchronize(c->stream)); reads_free(L); }
-    const size_t G = fheram_ctx::GLWE, nct = (size_t)n * ws, nrow = nct * c->rows;
-    hipError_t e = hipSuccess;
-    auto dev = [&](auto** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc((void**)p, bytes); };
-    dev(&L.res, nct * G * sizeof(int32_t));
-    if (work || had_work) {
-        dev(&L.A, nrow * G * sizeof(int32_t));
-        dev(&L.B, nrow * G * sizeof(int32_t));
-        if (third || had_third) dev(&L.C, nrow * G * sizeof(int32_t));
-        dev(&L.tmp, nct * G * sizeof(int32_t));
-        dev(&L.tmp2, nct * G * sizeof(int32_t));
-        dev(&L.prep, (size_t)n * c->n_digits * fheram_ctx::GGSW * sizeof(double));
+    const bool with_work = work || L.A, with_third = third || L.C;
+    if (L.cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (all) HIPCHK(c, hipStreamSynchronize(c->stream2));
+        dense_free(L);
     }
-    if (e == hipSuccess) e = hipHostMalloc((void**)&L.h_res, (nct * G + 1) * sizeof(int64_t), hipHostMallocMapped);   // + the monitor's maximum
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&L.d_h_res, L.h_res, 0);
+    const size_t ct = (size_t)n * ws * fheram_ctx::GLWE * sizeof(int32_t), row = ct * c->rows;
+    hipError_t e = hipSuccess;
+    auto dev = [&](auto** p, size_t bytes) {
+        if (e != hipSuccess) return;
+        if (fail_alloc && *fail_alloc > 0 && --*fail_alloc == 0) e = hipErrorOutOfMemory;   // (as the runtime reports an exhausted device)
+        else e = hipMalloc((void**)p, bytes);
+    };
+    if (all) {
+        for (int32_t** p : {&L.A, &L.B, &L.C, &L.D}) dev(p, row);
+        for (int32_t** p : {&L.part, &L.tmp, &L.tmp2, &L.res, &L.tree, &L.w, &L.trtop}) dev(p, ct);
+    } else {
+        dev(&L.res, ct);
+        if (with_work) {
+            for (int32_t** p : {&L.A, &L.B}) dev(p, row);
+            if (with_third) dev(&L.C, row);
+            for (int32_t** p : {&L.tmp, &L.tmp2}) dev(p, ct);
+            dev(&L.prep, (size_t)n * c->n_digits * fheram_ctx::GGSW * sizeof(double));
+        }
+        if (e == hipSuccess) e = hipHostMalloc((void**)&L.h_res, ct * 2 + sizeof(int64_t), hipHostMallocMapped);   // int64, + the monitor's maximum
+        if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&L.d_h_res, L.h_res, 0);
+    }
     if (e != hipSuccess) {
-        reads_free(L);
+        dense_free(L);
         (void)hipGetLastError();   // the next op's error check must not see this allocation's failure
-        return fail(c, FHERAM_ERR_DEVICE, std::string("read buffers for ") + std::to_string(n) + " addresses: " + hipGetErrorString(e));
+        return fail(c, FHERAM_ERR_DEVICE, (all ? "buffers of a write list of " + std::to_string(n) + " members: " : "read buffers for " + std::to_string(n) + " addresses: ") + hipGetErrorString(e));
     }
     L.cap = n;
     return FHERAM_OK;
 }
-// The view of such an operation for read_impl: the context's rows (a bank's: the whole bank's, reached through the operand set's map), and
-// every launch writes the set's buffers only.  The result of address k is at res + k * ws GLWEs; rows == 1: the products land in tmp2.
-RamView reads_view(const fheram_ctx* c, const ReadBufs& L) { return RamView{c->d_data, L.A, L.B, L.C, nullptr, L.tmp2, L.tmp, L.tmp2, L.res, nullptr, nullptr, nullptr}; }
+// The view of an operation on such a set: the context's rows (a bank's: the whole bank's, reached through the operand set's map), and
+// every launch writes the set's buffers only.  The result of address k is at res + k * ws GLWEs.  A set of reads has no part of its own
+// (rows == 1: the products land in tmp2) and no D, tree, w or trtop: a read names none of them.
+RamView dense_view(const fheram_ctx* c, const DenseBufs& L) {
+    return RamView{c->d_data, L.A, L.B, L.C, L.D, L.part ? L.part : L.tmp2, L.tmp, L.tmp2, L.res, L.tree, L.w, L.trtop};
+}
 
 // The one result export: every run (source, int32 count) is widened by the device into the pinned buffer h (device address d_h), back to
 // back, with the monitor's maximum as it stood then behind the last (the export kernel copies it there); out != nullptr: copied out.
@@ -327,7 +344,7 @@ int result_export(fheram_ctx* c, const ResRun* runs, int n_runs, int64_t* h, int
 }
 
 // the results of ciphertexts [first, first + n_ct) of such an operation, widened into its pinned buffer; out: [n_ct][GLWE] int64
-int reads_export(fheram_ctx* c, const ReadBufs& L, size_t first, size_t n_ct, int64_t* out) {
+int reads_export(fheram_ctx* c, const DenseBufs& L, size_t first, size_t n_ct, int64_t* out) {
     const ResRun run{L.res + first * fheram_ctx::GLWE, n_ct * fheram_ctx::GLWE};
     return result_export(c, &run, 1, L.h_res, L.d_h_res, out);
 }
@@ -335,11 +352,11 @@ int reads_export(fheram_ctx* c, const ReadBufs& L, size_t first, size_t n_ct, in
 // RAM(s) keep of it (where a single read would have left its result), enqueued behind the reads.
 // (Never captured: the launch sequence depends on n addresses, and a read's state bookkeeping is done as it is enqueued.)
 template <typename F>
-int read_many(fheram_ctx* c, ReadBufs& L, RamState* st, const fheram_addr* const* addrs, int n, int ws, unsigned member_map, bool bank, int64_t* out, F&& kept) {
-    int rc = reads_reserve(c, L, n, ws);
+int read_many(fheram_ctx* c, DenseBufs& L, RamState* st, const fheram_addr* const* addrs, int n, int ws, unsigned member_map, bool bank, int64_t* out, F&& kept) {
+    int rc = dense_reserve(c, L, n, ws);
     if (rc != FHERAM_OK) return rc;
     const Opnds o = table_opnds(c, st, addrs, n, ws, L.prep, nullptr, member_map, bank);
-    rc = read_impl(o, reads_view(c, L), false);
+    rc = read_impl(o, dense_view(c, L), false);
     if (rc != FHERAM_OK) return rc;
     kept(o);
     HIPCHK(c, hipGetLastError());
@@ -477,6 +494,18 @@ int write_rows(const Opnds& o, const RamView& v) {
     write_done(c, o.st);
     o.st->state = false;                                                                       // ram.rs:648
     return FHERAM_OK;
+}
+
+// A whole write that starts here (a bank's range or list; fheram_write keeps its own body: its side stage may have begun with the words
+// staged early, and it may be captured).  stage(d_w, ciphertexts) puts the words where the top takes them from, between the side stage —
+// which needs no words — and the top; a refusal (a limb out of range) comes before anything of the RAM has been touched.
+template <typename S>
+int write_all(const Opnds& o, const RamView& v, S&& stage) {
+    write_side_begin(o, v);
+    int rc = stage(v.w, o.Y());
+    if (rc != FHERAM_OK) { write_side_abort(o.c); return rc; }
+    rc = write_top(o, v);
+    return rc == FHERAM_OK ? write_rows(o, v) : rc;
 }
 
 }  // namespace

@@ -210,16 +210,20 @@ SMALL = [(12, 4, {}, [1, 0, 0]), (13, 4, {}, [1, 0]), (13, 4, {}, [0]), (13, 2, 
 _SMALL_WORLDS = {}
 
 
+def small_world(po, size, ws, crypto):
+    key = (size, ws, tuple(crypto))
+    if key not in _SMALL_WORLDS:
+        w = World(po, 1 << size, 2, word_size=ws, seed=200 + size + ws, n_addr=3, **crypto)
+        _SMALL_WORLDS[key] = (w, Ref(w, 2))
+    return _SMALL_WORLDS[key]
+
+
 @pytest.mark.parametrize("size,ws,crypto,members", SMALL, ids=["2p12-100", "2p13-10", "2p13-0", "2p13-ws2-10", "2p14-readme-10"])
 def test_one_row_two_rows_and_readme_keys(po, size, ws, crypto, members):
     """2^12: one row, one coordinate (n2 == 1, per-entry products on the mapped rows); 2^13: two rows, and at word size 2 the list [1, 0] is
     rows * n * ws = 8 ciphertext rows, so its alone levels run as the tail chain, whose source must survive: the list's third arena (at
     word size 4 they are 16 and run as the mid chain, on two arenas); the README block: the <5, 4> instantiation of the list kernel"""
-    key = (size, ws, tuple(crypto))
-    if key not in _SMALL_WORLDS:
-        w = World(po, 1 << size, 2, word_size=ws, seed=200 + size + ws, n_addr=3, **crypto)
-        _SMALL_WORLDS[key] = (w, Ref(w, 2))
-    w, ref = _SMALL_WORLDS[key]
+    w, ref = small_world(po, size, ws, crypto)
     bank = w.new_bank(2)
     js = list(range(len(members)))
     t0 = bank.tail_stats()
@@ -236,6 +240,48 @@ def test_one_row_two_rows_and_readme_keys(po, size, ws, crypto, members):
     for m in set(members):
         last = max(k for k, mk in enumerate(members) if mk == m)
         assert np.array_equal(bank.result(m, 1)[0], got[last]), m
+
+
+def test_buffer_set_walk_2_13(po):
+    """The three branches of the buffer set's reserve, at the smallest shape that has them (2^13, word size 2: two rows).  One entry needs
+    the result buffers only; [1, 0, 0] brings the working buffers (12 ciphertext rows: the mid chain, two arenas); [1, 0] fits the capacity
+    but its 8 ciphertext rows take the tail chain, so the third arena is added and the capacity kept; [1, 0, 0] again runs on the regrown
+    set.  Then the same walk through read_batch on a plain Ram: K = 1, 6, 2, 6 (K = 2 is the 8-row case: rows * K * ws = 8)."""
+    w, ref = small_world(po, 13, 2, {})
+    bank = w.new_bank(2)
+    got = None
+    for members in ([0], [1, 0, 0], [1, 0], [1, 0, 0]):
+        js = list(range(len(members)))
+        t0 = bank.tail_stats()
+        got = run_list(w, bank, members, js)
+        t1 = bank.tail_stats()
+        if members == [1, 0]:   # the alone levels of the rows (on the third arena) and the final trace; none gave up
+            assert t1["launches"] == t0["launches"] + 2, (t0, t1)
+        assert t1["fallbacks"] == t0["fallbacks"], (members, t0, t1)
+        for k, (m, j) in enumerate(zip(members, js)):
+            assert np.array_equal(got[k], ref.read(m, j)), (members, k)
+        got = got.copy()
+    assert np.array_equal(bank.list_result(0, 3), got)
+    assert np.array_equal(bank.list_result(1, 2), got[1:])
+    for m in range(2):
+        assert bank.state(m) is False
+        assert np.array_equal(bank.store_encrypted(m), ref.bank.store_encrypted(m)), m
+    ram = w.new_ram(0)
+    single = [ram.read(a, w.keys).copy() for a in w.addrs]
+    for m, j in ((0, 0), (0, 1), (0, 2)):   # (a bank's member is a Ram: the list's reference and the batch's agree)
+        assert np.array_equal(single[j], ref.read(m, j)), j
+    for sel in ([0], [0, 1, 2, 2, 1, 0], [1, 0], [0, 1, 2, 2, 1, 0]):
+        t0 = ram.tail_stats()
+        got = ram.read_batch([w.addrs[j] for j in sel], w.keys)
+        t1 = ram.tail_stats()
+        if len(sel) == 2:
+            assert t1["launches"] == t0["launches"] + 2, (t0, t1)
+        assert t1["fallbacks"] == t0["fallbacks"], (sel, t0, t1)
+        assert got.shape[0] == len(sel)
+        for k, j in enumerate(sel):
+            assert np.array_equal(got[k], single[j]), (sel, k)
+        assert np.array_equal(ram.result(), single[sel[-1]]), sel
+    assert np.array_equal(ram.store_encrypted(), ref.bank.store_encrypted(0))
 
 
 # ---- 7. derived addresses: ordered by the stream ------------------------------------------------------------------------------------------------

@@ -16,9 +16,12 @@
 // Trace chains are logged for 0 .. LOGN steps (the context has LOGN trace keys), product chains and the predicates for 0 .. CHAIN_MAX + 1.
 //
 // Second mode, the SEQUENCES themselves (path.hpp read_impl and the write triple) for a context, a batch, ranges of a bank's members and
-// read lists of a bank of three:
+// read lists and read_prepare_write / write lists of a bank of three; behind the configurations, in full: the REFUSALS of the bank's
+// checks (code, message and the mid re-arm count, one line per bad argument) and the RESERVE log of the dense buffer sets (hipMalloc and
+// its kin are recorders too: every allocation, free and stream wait of a sequence of reserves, and what the set holds afterwards):
 //
-//   ./launch_log path > path_log.txt                       one digest line per configuration (profiles/ram_view_path_log.txt: the tree's of DESIGN.md 10.4)
+//   ./launch_log path > path_log.txt                       one digest line per configuration, then the refusals and the reserves (profiles/ram_view_path_log.txt: the tree's
+//                                                          of DESIGN.md 10.4; profiles/member_set_path_log.txt: with the write lists, the refusals and the reserves, 10.7)
 //   ./launch_log path 17                                   every line of configuration 17
 //
 // Every buffer is a fake arena 4 GiB from the next, so an argument that points into one shows as a<arena>+<byte offset> behind the launch's
@@ -114,6 +117,34 @@ void record(const char* kernel, const char* site, dim3 g, dim3 b, size_t lds, hi
     if (path_mode) (arenas_in(l, &a, sizeof(a)), ...);
     line(l);
 }
+// the reserve log: the allocations, frees and stream waits (these in reserve_mode only) of one call; fail_nth: the fail_nth-th next allocation reports an exhausted device
+bool reserve_mode = false;
+int fail_nth = 0;
+unsigned n_alloc = 0;
+// (one line per call of the reserve log: its events in order, a run of equal events as "<event> x<count>")
+std::string call_events, last_event;
+unsigned last_count = 0;
+void flush_event() {
+    if (last_count) call_events += (call_events.empty() ? "" : ", ") + last_event + (last_count > 1 ? " x" + std::to_string(last_count) : "");
+    last_count = 0;
+}
+void call_event(const std::string& e) {
+    if (last_count && e == last_event) { last_count++; return; }
+    flush_event();
+    last_event = e; last_count = 1;
+}
+std::string take_events() { flush_event(); std::string e = call_events.empty() ? "nothing" : call_events; call_events.clear(); return e; }
+hipError_t alloc(void** p, size_t bytes, const char* kind) {
+    if (fail_nth > 0 && --fail_nth == 0) { call_event(std::string(kind) + " " + std::to_string(bytes) + " -> out of memory"); return hipErrorOutOfMemory; }
+    *p = reinterpret_cast<void*>((uintptr_t)0x100000000ull * (uintptr_t)(129 + n_alloc++ % 100));
+    call_event(std::string(kind) + " " + std::to_string(bytes));
+    return hipSuccess;
+}
+hipError_t release(const char* what) { call_event(what); return hipSuccess; }
+hipError_t sync(hipStream_t s) {
+    if (reserve_mode) call_event(s == main_stream ? "wait main" : "wait side");
+    return hipSuccess;
+}
 hipError_t event(const char* what, const void* ev, hipStream_t s) {
     if (path_mode) line(std::string("  ") + what + " " + arena_of((uint64_t)(uintptr_t)ev) + (s == main_stream ? " main" : " side"));
     return hipSuccess;
@@ -126,11 +157,24 @@ hipError_t event(const char* what, const void* ev, hipStream_t s) {
 #define hipEventCreate(e) (*(e) = nullptr, hipSuccess)
 #define hipEventRecord(e, s) ll::event("record", e, s)
 #define hipStreamWaitEvent(s, e, flags) ll::event("wait", e, s)
-#define hipStreamSynchronize(s) ((void)(s), hipSuccess)
+#define hipStreamSynchronize(s) ll::sync(s)
 #define hipGetLastError() hipSuccess
+#define hipSetDevice(d) ((void)(d), hipSuccess)
+// nothing is allocated: a fake address back, and a line in the reserve log
+#define hipMalloc(p, bytes) ll::alloc((void**)(p), bytes, "alloc")
+#define hipHostMalloc(p, bytes, flags) ll::alloc((void**)(p), bytes, "alloc pinned")
+#define hipHostGetDevicePointer(d, h, flags) (*(d) = (h), hipSuccess)
+#define hipFree(p) ll::release("free")
+#define hipHostFree(p) ll::release("free pinned")
 
 #include "bank.hpp"
 #include <launch_log_shim.hpp>   // (angle brackets: from the include path, not from beside this file)
+
+// the write lists' row chains launch from a translation unit of their own (mapped_chains.hip): here they are recorders like every other launch
+namespace fk {
+void read_chain_m_launch(int sk, dim3 grid, hipStream_t stream, const RowChainTableArgs& ra) { ll::record(("k_read_chain_m<" + std::to_string(sk) + ">").c_str(), "", grid, dim3(256), 0, stream, ra); }
+void write_chain_m_launch(int sk, dim3 grid, hipStream_t stream, const RowChainTableArgs& ra) { ll::record(("k_write_chain_m<" + std::to_string(sk) + ">").c_str(), "", grid, dim3(256), 0, stream, ra); }
+}  // namespace fk
 
 namespace {
 
@@ -296,6 +340,7 @@ const Field FIELDS[] = {{"data", &fheram_ctx::d_data}, {"scrA", &fheram_ctx::d_s
                         {"scrD", &fheram_ctx::d_scrD}, {"tree", &fheram_ctx::d_tree}, {"res", &fheram_ctx::d_res}, {"tmp", &fheram_ctx::d_tmp},
                         {"tmp2", &fheram_ctx::d_tmp2}, {"w", &fheram_ctx::d_w}, {"part", &fheram_ctx::d_part}, {"trtop", &fheram_ctx::d_trtop}};
 const char* const READS_FIELDS[] = {"A", "B", "C", "res", "tmp", "tmp2"};   // (the shim's shim_batch_field / shim_list_field)
+const char* const WL_FIELDS[] = {"A", "B", "C", "D", "part", "tmp", "tmp2", "res", "tree", "w", "trtop"};   // the write lists': fake(80 + i) (shim_wl_field)
 
 fheram_ctx* make_path_ctx(unsigned* host_words, int lg, int ws, int s_evk, const Setting& st) {
     fheram_ctx* c = make_ctx(host_words);
@@ -338,7 +383,9 @@ void dump_ctx(const fheram_ctx* c) {
     for (const Field& f : FIELDS) l += std::string(" ") + f.name + "=" + ll::arena_of((uint64_t)(uintptr_t)(c->*f.p));
     ll::line(l);
 }
+bool dump_wl = false;   // from the first write list on: what the bank remembers of the lists' arena
 void dump_bank(const fheram_bank* b) {
+    if (dump_wl) ll::line("  -> " + shim_wl_kept(b));
     for (int m = 0; m < b->M; m++) {
         const ShimState s = shim_state(b, m);
         char buf[128];
@@ -391,6 +438,46 @@ void bank_step(fheram_bank* b, int first, int n, const fheram_addr* const* a, in
     op("bank write" + r); shim_bank_write(b, first, n, a, staging(b->c, FHERAM_OK)); dump_bank(b);
     op("bank read" + r); shim_bank_read(b, first, n, a, false); dump_bank(b); synced(b->c);
 }
+// read_prepare_write / write on any member set of the bank of three: every path a list can take (kept rows, gather, refusal, range <-> list,
+// a read list between the halves); the host has waited (a result download) where `waited` says so, which is what lets a write skip its fork event
+std::string list_name(const int* m, int n) {
+    std::string s = "[";
+    for (int k = 0; k < n; k++) s += (k ? "," : "") + std::to_string(m[k]);
+    return s + "]";
+}
+void rpw_list(fheram_bank* b, const int* m, const fheram_addr* const* a, int n, bool waited = true) {
+    op("bank read_prepare_write_list " + list_name(m, n)); shim_bank_rpw_list(b, m, a, n); dump_bank(b); synced(b->c);
+    if (waited) main_waited(b->c);
+}
+void write_list(fheram_bank* b, const int* m, const fheram_addr* const* a, int n, int stage_rc = FHERAM_OK) {
+    op("bank write_list " + list_name(m, n) + (stage_rc != FHERAM_OK ? ", words refused" : "")); shim_bank_write_list(b, m, a, n, staging(b->c, stage_rc)); dump_bank(b);
+}
+void run_path_write_lists(fheram_bank* b, const fheram_addr* const* a) {
+    fheram_ctx* c = b->c;
+    dump_wl = true;
+    shim_wl_cap(b, 3);
+    for (int i = 0; i < 11; i++) shim_wl_field(b, i) = fake<int32_t*>(80 + i);
+    const int l20[] = {2, 0}, l02[] = {0, 2}, l10[] = {1, 0}, l210[] = {2, 1, 0}, l012[] = {0, 1, 2}, l11[] = {1, 1};
+    const fheram_addr* a2[] = {a[2], a[0]}, *a1[] = {a[1], a[1]};
+    // the same members in the same order: the rows are kept, nothing is gathered
+    rpw_list(b, l20, a2, 2); write_list(b, l20, a2, 2);
+    // permuted: a gather, and the kept rows do not count
+    rpw_list(b, l20, a2, 2); write_list(b, l02, a, 2);
+    // a range pending across a list; the list's words refused, then accepted
+    op("bank read_prepare_write [1, 2)"); shim_bank_read(b, 1, 1, a + 1, true); dump_bank(b); synced(c);
+    rpw_list(b, l02, a, 2); write_list(b, l02, a, 2, FHERAM_ERR_RANGE); write_list(b, l02, a, 2);
+    op("bank write [1, 2)"); shim_bank_write(b, 1, 1, a + 1, staging(c, FHERAM_OK)); dump_bank(b);
+    // prepared by range, written by list, and the other way round (a list of a contiguous ascending run IS the range)
+    op("bank read_prepare_write [0, 2)"); shim_bank_read(b, 0, 2, a, true); dump_bank(b); synced(c); main_waited(c);
+    write_list(b, l10, a, 2);
+    rpw_list(b, l210, a, 3);
+    op("bank write [0, 3)"); shim_bank_write(b, 0, 3, a, staging(c, FHERAM_OK)); dump_bank(b);
+    rpw_list(b, l012, a, 3); write_list(b, l012, a, 3);
+    // a read list between the two halves touches nothing of the lists'
+    rpw_list(b, l20, a2, 2);
+    op("bank read_list [1, 1]"); shim_list_field(b, 2) = third_arena_needed(c, 2 * b->mws) ? fake<int32_t*>(66) : nullptr; shim_bank_list(b, l11, a1, 2); dump_bank(b); synced(c); main_waited(c);
+    write_list(b, l20, a2, 2);
+}
 void run_path_bank(fheram_ctx* c, int M, int mws) {
     fheram_bank* b = new fheram_bank();
     b->c = c; b->M = M; b->mws = mws;
@@ -420,8 +507,152 @@ void run_path_bank(fheram_ctx* c, int M, int mws) {
             shim_bank_list(b, n == 2 ? perm : rep, la, n); dump_bank(b); synced(c);
         }
     }
+    if (M == 3) run_path_write_lists(b, a);
+    dump_wl = false;
     for (int k = 0; k < 3; k++) delete a[k];
     delete b;
+}
+
+// ---- the refusals: the bank's checks (not the entry points) with each bad argument of the range, read-list and write-list forms --------
+// Bank of three, member 1 between read_prepare_write and write.  One line per case: the code, the message (fheram_bank_last_error's text) and
+// how often the mid re-arm counted the call.
+template <typename F>
+void refuse(fheram_bank* b, const std::string& what, F&& check) {
+    fheram_ctx* c = b->c;
+    c->err.clear(); c->cfg.mid = 0; c->mid_saved = 2; c->mid_off_ops = 0;
+    const int rc = check();
+    ll::line(what + " -> " + std::to_string(rc) + " \"" + c->err + "\" rearm=" + std::to_string(c->mid_off_ops));
+}
+void run_refusals(unsigned* host_words) {
+    std::puts("# refusals: bank of three, word_size 2, member 1 pending; <case> -> <code> \"<message>\" rearm=<mid re-arm count>");
+    fheram_ctx* c = make_path_ctx(host_words, 13, 3 * 2, 4, PATH_SETTINGS[0]);
+    fheram_ctx* other = make_path_ctx(host_words, 13, 3 * 2, 4, PATH_SETTINGS[0]);
+    fheram_bank* b = new fheram_bank();
+    b->c = c; b->M = 3; b->mws = 2;
+    const fheram_addr* a[3];
+    for (int k = 0; k < 3; k++) a[k] = make_addr(c, k);
+    fheram_addr* foreign = make_addr(other, 0);
+    fheram_addr* empty = make_addr(c, 3);
+    empty->empty = true;
+    const int m012[] = {0, 1, 2}, m02[] = {0, 2}, m1[] = {1}, neg[] = {0, -1}, big[] = {0, 3}, twice[] = {2, 0, 2}, m11[] = {1, 1}, nine[] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const fheram_addr *good[] = {a[0], a[1], a[2], a[0], a[1], a[2], a[0], a[1], a[2]}, *with_null[] = {a[0], nullptr, a[2]}, *with_foreign[] = {a[0], foreign, a[2]}, *with_empty[] = {a[0], empty, a[2]};
+    auto ready = [&] { shim_loaded(b); c->keys_loaded = true; for (int m = 0; m < 3; m++) shim_set_state(b, m, m == 1); };
+    ready();
+    for (int want : {0, 1, -1}) {
+        const std::string w = want == 0 ? "range read" : want == 1 ? "range write" : "range result";
+        refuse(b, w + " null bank", [&] { return shim_check_range(nullptr, 0, 1, good, false, want); });
+        if (want >= 0) refuse(b, w + " null addrs", [&] { return shim_check_range(b, 0, 1, nullptr, false, want); });
+        if (want == 1) refuse(b, w + " null words", [&] { return shim_check_range(b, 1, 1, good, true, want); });
+        refuse(b, w + " n=0", [&] { return shim_check_range(b, 0, 0, good, false, want); });
+        refuse(b, w + " n=4", [&] { return shim_check_range(b, 0, 4, good, false, want); });
+        refuse(b, w + " first=-1", [&] { return shim_check_range(b, -1, 1, good, false, want); });
+        refuse(b, w + " first=3", [&] { return shim_check_range(b, 3, 1, good, false, want); });
+        refuse(b, w + " [2, 4)", [&] { return shim_check_range(b, 2, 2, good, false, want); });
+        if (want >= 0) {
+            refuse(b, w + " null address", [&] { return shim_check_range(b, 0, 3, with_null, false, want); });
+            refuse(b, w + " foreign address", [&] { return shim_check_range(b, 0, 3, with_foreign, false, want); });
+            refuse(b, w + " empty address", [&] { return shim_check_range(b, 0, 3, with_empty, false, want); });
+        }
+        shim_set_initialized(b, 2, false);
+        refuse(b, w + " member 2 uninitialised", [&] { return shim_check_range(b, 0, 3, good, false, want); });
+        ready(); c->keys_loaded = false;
+        refuse(b, w + " no keys", [&] { return shim_check_range(b, 0, 1, good, false, want); });
+        ready();
+        refuse(b, w + " [0, 3) over the pending member", [&] { return shim_check_range(b, 0, 3, good, false, want); });
+        refuse(b, w + " [1, 2) the pending member", [&] { return shim_check_range(b, 1, 1, good, false, want); });
+        refuse(b, w + " [2, 3) accepted or not", [&] { return shim_check_range(b, 2, 1, good, false, want); });
+    }
+    refuse(b, "read list null bank", [&] { return shim_check_rlist(nullptr, m02, good, 2); });
+    refuse(b, "read list null members", [&] { return shim_check_rlist(b, nullptr, good, 2); });
+    refuse(b, "read list null addrs", [&] { return shim_check_rlist(b, m02, nullptr, 2); });
+    refuse(b, "read list n=0", [&] { return shim_check_rlist(b, m02, good, 0); });
+    refuse(b, "read list n=9", [&] { return shim_check_rlist(b, nine, good, 9); });
+    refuse(b, "read list member -1", [&] { return shim_check_rlist(b, neg, good, 2); });
+    refuse(b, "read list member 3", [&] { return shim_check_rlist(b, big, good, 2); });
+    refuse(b, "read list null address", [&] { return shim_check_rlist(b, m012, with_null, 3); });
+    refuse(b, "read list foreign address", [&] { return shim_check_rlist(b, m012, with_foreign, 3); });
+    refuse(b, "read list empty address", [&] { return shim_check_rlist(b, m012, with_empty, 3); });
+    shim_set_initialized(b, 2, false);
+    refuse(b, "read list member 2 uninitialised", [&] { return shim_check_rlist(b, twice, good, 3); });
+    ready(); c->keys_loaded = false;
+    refuse(b, "read list no keys", [&] { return shim_check_rlist(b, m02, good, 2); });
+    ready();
+    refuse(b, "read list [1,1] the pending member", [&] { return shim_check_rlist(b, m11, good, 2); });
+    refuse(b, "read list [2,0,2] accepted", [&] { return shim_check_rlist(b, twice, good, 3); });
+    b->mws = 16;   // (a bank of 3 x 16 = 48 ciphertexts)
+    refuse(b, "read list n * word_size = 80", [&] { return shim_check_rlist(b, nine, good, 5); });
+    b->mws = 2;
+    for (int want : {0, 1}) {
+        const std::string w = want == 0 ? "read_prepare_write list" : "write list";
+        refuse(b, w + " null bank", [&] { return shim_check_wlist(nullptr, m02, good, 2, false, want); });
+        refuse(b, w + " null members", [&] { return shim_check_wlist(b, nullptr, good, 2, false, want); });
+        refuse(b, w + " null addrs", [&] { return shim_check_wlist(b, m02, nullptr, 2, false, want); });
+        if (want == 1) refuse(b, w + " null words", [&] { return shim_check_wlist(b, m1, good, 1, true, want); });
+        refuse(b, w + " n=0", [&] { return shim_check_wlist(b, m02, good, 0, false, want); });
+        refuse(b, w + " n=4", [&] { return shim_check_wlist(b, nine, good, 4, false, want); });
+        refuse(b, w + " member -1", [&] { return shim_check_wlist(b, neg, good, 2, false, want); });
+        refuse(b, w + " member 3", [&] { return shim_check_wlist(b, big, good, 2, false, want); });
+        refuse(b, w + " member 2 twice", [&] { return shim_check_wlist(b, twice, good, 3, false, want); });
+        refuse(b, w + " null address", [&] { return shim_check_wlist(b, m012, with_null, 3, false, want); });
+        refuse(b, w + " foreign address", [&] { return shim_check_wlist(b, m012, with_foreign, 3, false, want); });
+        refuse(b, w + " empty address", [&] { return shim_check_wlist(b, m012, with_empty, 3, false, want); });
+        shim_set_initialized(b, 2, false);
+        refuse(b, w + " member 2 uninitialised", [&] { return shim_check_wlist(b, m02, good, 2, false, want); });
+        ready(); c->keys_loaded = false;
+        refuse(b, w + " no keys", [&] { return shim_check_wlist(b, m02, good, 2, false, want); });
+        ready();
+        refuse(b, w + " [0,2]", [&] { return shim_check_wlist(b, m02, good, 2, false, want); });
+        refuse(b, w + " [1]", [&] { return shim_check_wlist(b, m1, good, 1, false, want); });
+        refuse(b, w + " [0,1,2]", [&] { return shim_check_wlist(b, m012, good, 3, false, want); });
+    }
+    for (int k = 0; k < 3; k++) delete a[k];
+    delete foreign; delete empty; delete b; delete c; delete other;
+}
+
+// ---- the reserve log: what a sequence of reserves allocates, frees and waits for, and what the set holds afterwards ----------------------
+// 2^13, word_size 2 (two rows: n * ws <= 4 ciphertexts take the tail chain on the rows, so n = 2 needs the third arena and n = 3 does not)
+void run_reserves(unsigned* host_words) {
+    std::puts("# reserves: 2^13, word_size 2; one line per call: every allocation (bytes), free and stream wait in order, then the code, the message, the capacity and the buffers held");
+    ll::reserve_mode = true;
+    (void)ll::take_events();
+    fheram_ctx* c = make_path_ctx(host_words, 13, 2, 4, PATH_SETTINGS[0]);
+    auto reads = [&](ShimReadSet& L, int n, int fail_nth) {
+        ll::fail_nth = fail_nth; c->err.clear();
+        const int rc = shim_reads_reserve(c, L, n, c->ws);
+        ll::fail_nth = 0;
+        ll::line("read set: reserve n=" + std::to_string(n) + (fail_nth ? ", allocation " + std::to_string(fail_nth) + " fails" : "") + ": " + ll::take_events() + " -> " +
+                 std::to_string(rc) + " \"" + c->err + "\" " + shim_reads_holds(L));
+    };
+    {
+        ShimReadSet L;
+        for (int n : {1, 3, 2, 3, 1}) reads(L, n, 0);
+        shim_reads_free(L); ll::line("read set: free: " + ll::take_events() + " -> " + shim_reads_holds(L));
+        for (int nth : {1, 4, 7}) {
+            reads(L, 3, nth);                    // a fresh set
+            reads(L, 1, 0); reads(L, 3, nth);    // growth
+            reads(L, 3, 0); reads(L, 2, nth);   // the third arena alone, the capacity kept
+            shim_reads_free(L); ll::line("read set: free: " + ll::take_events());
+        }
+    }
+    fheram_ctx* c3 = make_path_ctx(host_words, 13, 3 * 2, 4, PATH_SETTINGS[0]);
+    fheram_bank* b = new fheram_bank();
+    b->c = c3; b->M = 3; b->mws = 2;
+    auto wl = [&](int n, int nth) {
+        fheram_bank_selftest_fail_list_alloc(b, nth); c3->err.clear();
+        const int rc = shim_wl_reserve(b, n);
+        ll::line("write-list set: reserve n=" + std::to_string(n) + (nth ? ", fail_list_alloc " + std::to_string(nth) : "") + ": " + ll::take_events() + " -> " + std::to_string(rc) +
+                 " \"" + c3->err + "\" " + shim_wl_holds(b));
+    };
+    for (int n : {2, 3, 2}) wl(n, 0);
+    shim_wl_free(b); ll::line("write-list set: free: " + ll::take_events() + " -> " + shim_wl_holds(b));
+    for (int nth : {1, 5, 11, 12}) {
+        wl(3, nth);              // a fresh set (12: one more than the set has, so it stays armed)
+        wl(2, 0); wl(3, nth);    // growth
+        shim_wl_free(b); ll::line("write-list set: free: " + ll::take_events());
+        fheram_bank_selftest_fail_list_alloc(b, 0);
+    }
+    ll::reserve_mode = false;
+    delete b; delete c3; delete c;
 }
 
 int path_main(long only, unsigned* host_words) {
@@ -431,6 +662,7 @@ int path_main(long only, unsigned* host_words) {
         for (int i = 0; i < 12; i++) legend += std::string(" a") + std::to_string(32 + i) + "=" + FIELDS[i].name;
         for (int i = 0; i < 6; i++) legend += std::string(" a") + std::to_string(48 + i) + "=batch." + READS_FIELDS[i];
         for (int i = 0; i < 6; i++) legend += std::string(" a") + std::to_string(64 + i) + "=list." + READS_FIELDS[i];
+        for (int i = 0; i < 11; i++) legend += std::string(" a") + std::to_string(80 + i) + "=wl." + WL_FIELDS[i];
         std::puts(legend.c_str());
         std::puts("# a13=prep a14=prep_inv a15=ggsw_tmp a16=ggsw_tmp2 a17=ggsw_inv a26=batch.prep a56..=address digits a60=bank prep a61=bank prep_inv a70=list.prep; events: a20=fork a21=join a22,a23=inv a24=wdone a25=opstart");
     }
@@ -451,6 +683,7 @@ int path_main(long only, unsigned* host_words) {
         std::printf("config %ld: %" PRIu64 " operations, %" PRIu64 " lines, digest %016" PRIx64 "\n", id, path_ops, ll::lines, ll::digest);
         id++;
     }
+    if (only < 0) { ll::verbose = true; run_refusals(host_words); run_reserves(host_words); }
     return 0;
 }
 

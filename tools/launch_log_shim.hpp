@@ -6,11 +6,11 @@ bool shim_tail_top(const fheram_ctx* c, int Y) { return chain_form(c, ChainQuery
 // an operand set for the predicates alone; own_rows: a context's (n == 1) or a bank range's, else a batch's
 Opnds shim_opnds(fheram_ctx* c, int n, int ws, bool own_rows) { return n == 1 ? one_addr(c, nullptr, ws, &c->ram) : table_opnds(c, &c->ram, nullptr, n, ws, nullptr, nullptr, own_rows ? MEMBER_MAP_IDENTITY : 0, own_rows); }
 // the operand table of the row_chains cases: gy ciphertexts as two addresses that read the same rows (store_mapped off: the `_t` kernels,
-// which are what a batch and a range launch; the lists' `_m` kernels live in another translation unit and are not logged)
+// which are what a batch and a range launch; the lists' `_m` launchers are recorders of launch_log.hip's own, reached in path mode)
 OpndTable shim_table(int gy) { return OpndTable{gy / 2, 1000, 0}; }
 bool shim_needs_third(const fheram_ctx* c, int K) { return third_arena_needed(c, K * c->ws); }
 // the buffers of a batch and of a bank's read list: field i of launch_log.hip's READS_FIELDS, and the digit table
-int32_t*& reads_field(ReadBufs& L, int i) { int32_t** f[] = {&L.A, &L.B, &L.C, &L.res, &L.tmp, &L.tmp2}; return *f[i]; }
+int32_t*& reads_field(DenseBufs& L, int i) { int32_t** f[] = {&L.A, &L.B, &L.C, &L.res, &L.tmp, &L.tmp2}; return *f[i]; }
 int32_t*& shim_batch_field(fheram_ctx* c, int i) { return reads_field(c->batch, i); }
 int32_t*& shim_list_field(fheram_bank* b, int i) { return reads_field(b->list, i); }
 void shim_batch_prep(fheram_ctx* c, double* prep) { c->batch.prep = prep; c->batch.cap = 4; }
@@ -29,7 +29,7 @@ void shim_new_keys(fheram_ctx* c) { c->ram.memo_top = false; c->ram.memo_alone =
 int shim_read(fheram_ctx* c, const fheram_addr* addr, bool prepare_write) { return read_impl(one_addr(c, &addr), ctx_view(c), prepare_write); }
 int shim_batch(fheram_ctx* c, const fheram_addr* const* addrs, int K) {   // fheram_read_batch (read_many, the buffers being there)
     const Opnds o = table_opnds(c, &c->ram, addrs, K, c->ws, c->batch.prep, nullptr, 0, false);
-    const int rc = read_impl(o, reads_view(c, c->batch), false);
+    const int rc = read_impl(o, dense_view(c, c->batch), false);
     launch_copy(c, o.slice(ref(c->batch.res, (long)fheram_ctx::GLWE, 0), K - 1), ref(c->d_res, (long)fheram_ctx::GLWE, 0), 1, c->ws);
     return rc;
 }
@@ -43,41 +43,72 @@ int shim_write(fheram_ctx* c, const fheram_addr* addr, S&& staged) {   // fheram
     rc = write_top(o, v);
     return rc == FHERAM_OK ? write_rows(o, v) : rc;
 }
-int shim_bank_read(fheram_bank* b, int first, int n, const fheram_addr* const* addrs, bool prepare_write) {   // bank_read_op
-    RamState st = bank_merge(b, first, n, false);
-    const int rc = read_impl(bank_opnds(b, &st, addrs, n), bank_view(b, first), prepare_write);
-    bank_assign(b, first, n, st, rc == FHERAM_OK && prepare_write, true);
-    return rc;
-}
-int shim_bank_list(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n) {   // fheram_bank_read_list, n > 1 (read_many, the buffers being there)
+// The bank's operations are the bank's own functions, behind their checks: the buffers being there, the reserves allocate nothing, and
+// `staged` is the staging step of write_all.
+int shim_bank_read(fheram_bank* b, int first, int n, const fheram_addr* const* addrs, bool prepare_write) { return bank_read_set(b, MemberSet::range(first, n), addrs, prepare_write, nullptr); }
+template <typename S>
+int shim_bank_write(fheram_bank* b, int first, int n, const fheram_addr* const* addrs, S&& staged) { return bank_write_set(b, MemberSet::range(first, n), addrs, staged); }
+int shim_bank_rpw_list(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n) { return bank_read_set(b, MemberSet::list(members, n), addrs, true, nullptr); }
+template <typename S>
+int shim_bank_write_list(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n, S&& staged) { return bank_write_set(b, MemberSet::list(members, n), addrs, staged); }
+int shim_bank_list(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n) {   // fheram_bank_read_list, n > 1: its call of read_many without the reserve
+    const MemberSet s = MemberSet::list(members, n);
     RamState st{true, false, false, 0, false};
-    unsigned map = 0;
-    for (int k = 0; k < n; k++) map |= (unsigned)members[k] << (4 * k);
-    const Opnds o = table_opnds(b->c, &st, addrs, n, b->mws, b->list.prep, nullptr, map, b->M > 1);
-    const int rc = read_impl(o, reads_view(b->c, b->list), false);
-    const long G = (long)fheram_ctx::GLWE;
+    const Opnds o = table_opnds(b->c, &st, addrs, n, b->mws, b->list.prep, nullptr, s.map(), b->M > 1);
+    const int rc = read_impl(o, dense_view(b->c, b->list), false);
+    set_assign(b, s, st, false, false, true);
     for (int m = 0; m < b->M; m++) {
         int last = -1;
-        for (int k = 0; k < n; k++) if (members[k] == m) last = k;
-        if (last < 0) continue;
-        RamState& r = b->ram[m];
-        r.state = false; r.memo_top = false; r.memo_alone = 0; r.res_in_trtop = false;
-        launch_copy(b->c, o.slice(ref(b->list.res, G, 0), last), ref(b->c->d_res + (size_t)m * b->mws * G, G, 0), 1, b->mws);
+        for (int k = 0; k < n; k++) if (s.m[k] == m) last = k;
+        if (last >= 0) launch_copy(b->c, o.slice(ref(b->list.res, (long)fheram_ctx::GLWE, 0), last), member_slot(b, b->c->d_res, m), 1, b->mws);
     }
     return rc;
 }
-template <typename S>
-int shim_bank_write(fheram_bank* b, int first, int n, const fheram_addr* const* addrs, S&& staged) {   // fheram_bank_write
-    RamState st = bank_merge(b, first, n, true);
-    const Opnds o = bank_opnds(b, &st, addrs, n);
-    const RamView v = bank_view(b, first);
-    write_side_begin(o, v);
-    int rc = staged(v.w, n * b->mws);
-    if (rc != FHERAM_OK) { write_side_abort(b->c); bank_assign(b, first, n, st, true, false); return rc; }
-    rc = write_top(o, v);
-    if (rc == FHERAM_OK) rc = write_rows(o, v);
-    bank_assign(b, first, n, st, rc != FHERAM_OK, false);
-    return rc;
+
+// ---- the write lists: their buffers (field i of launch_log.hip's WL_FIELDS) and what the bank remembers of them --------------------------
+int32_t*& shim_wl_field(fheram_bank* b, int i) {
+    DenseBufs& L = b->wl;
+    int32_t** f[] = {&L.A, &L.B, &L.C, &L.D, &L.part, &L.tmp, &L.tmp2, &L.res, &L.tree, &L.w, &L.trtop};
+    return *f[i];
 }
+void shim_wl_cap(fheram_bank* b, int cap) { b->wl.cap = cap; }
+std::string shim_wl_kept(const fheram_bank* b) {
+    std::string s = "wl_holds=";
+    for (int m = 0; m < b->M; m++) s += b->wl_holds[m] ? '1' : '0';
+    char buf[96];
+    std::snprintf(buf, sizeof buf, " kept_alone=%d kept_n=%d kept_map=%#x", b->kept_alone, b->kept_n, b->kept_map);
+    return s + buf;
+}
+
+// ---- the refusals: the checks of the three forms as the entry points run them, and the state they look at -------------------------------
+void shim_set_state(fheram_bank* b, int m, bool state) { b->ram[m].state = state; }
+void shim_set_initialized(fheram_bank* b, int m, bool on) { b->ram[m].initialized = on; }
+int shim_check_range(fheram_bank* b, int first, int n, const fheram_addr* const* addrs, bool null_words, int want) {   // as the entry points call it
+    MemberSet s;
+    const char* null_args = want == 0 ? (addrs ? nullptr : "null address list") : want == 1 ? ((addrs && !null_words) ? nullptr : "null address list or null words") : nullptr;
+    return range_check(b, first, n, want < 0 ? nullptr : addrs, null_args, want, &s);
+}
+int shim_check_rlist(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n) { MemberSet s; return read_list_check(b, members, addrs, n, &s); }
+int shim_check_wlist(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n, bool null_words, int want) { MemberSet s; return write_list_check(b, members, addrs, n, null_words, want, &s); }
+
+// ---- the reserves: the two dense buffer sets ------------------------------------------------------------------------------------------
+using ShimReadSet = DenseBufs;
+int shim_reads_reserve(fheram_ctx* c, ShimReadSet& L, int n, int ws) { return dense_reserve(c, L, n, ws); }
+void shim_reads_free(ShimReadSet& L) { dense_free(L); }
+// the capacity and the buffers held: first those a set of that kind may hold, in the order of the struct this one replaced, then any other as "+<name>", which no log has
+std::string shim_held(const DenseBufs& L, bool all) {
+    using F = std::pair<const char*, const void*>;
+    const F wl[] = {{"A", L.A}, {"B", L.B}, {"C", L.C}, {"D", L.D}, {"part", L.part}, {"tmp", L.tmp}, {"tmp2", L.tmp2}, {"res", L.res}, {"tree", L.tree}, {"w", L.w}, {"trtop", L.trtop}};
+    const F reads[] = {{"A", L.A}, {"B", L.B}, {"C", L.C}, {"res", L.res}, {"tmp", L.tmp}, {"tmp2", L.tmp2}, {"prep", L.prep}, {"h_res", L.h_res}, {"d_h_res", L.d_h_res}};
+    const F not_wl[] = {{"prep", L.prep}, {"h_res", L.h_res}, {"d_h_res", L.d_h_res}}, not_reads[] = {{"D", L.D}, {"part", L.part}, {"tree", L.tree}, {"w", L.w}, {"trtop", L.trtop}};
+    std::string s = "cap=" + std::to_string(L.cap) + " holds";
+    auto add = [&](const F* f, size_t n, const char* sep) { for (size_t i = 0; i < n; i++) if (f[i].second) s += std::string(sep) + f[i].first; };
+    if (all) { add(wl, 11, " "); add(not_wl, 3, " +"); } else { add(reads, 9, " "); add(not_reads, 5, " +"); }
+    return s;
+}
+std::string shim_reads_holds(const ShimReadSet& L) { return shim_held(L, false); }
+int shim_wl_reserve(fheram_bank* b, int n) { return dense_reserve(b->c, b->wl, n, b->mws, true, &b->wl_fail_alloc); }
+void shim_wl_free(fheram_bank* b) { dense_free(b->wl); }
+std::string shim_wl_holds(const fheram_bank* b) { return shim_held(b->wl, true) + " fail_alloc=" + std::to_string(b->wl_fail_alloc); }
 
 }  // namespace
