@@ -29,6 +29,9 @@ READ_BATCH_MAX = 8   # FHERAM_READ_BATCH_MAX (include/fheram.h)
 BANK_MAX = 8         # FHERAM_BANK_MAX
 READ_LIST_MAX = 8    # FHERAM_READ_LIST_MAX
 DERIVE_MAX = 8       # FHERAM_DERIVE_MAX
+SELECT_BITS_MAX = 5  # FHERAM_SELECT_BITS_MAX
+SELECT_MAX = 8       # FHERAM_SELECT_MAX
+SRC_ZERO, SRC_HOST, SRC_MEMBER_RESULT, SRC_LIST_RESULT, SRC_SELECT_RESULT = 0, 1, 2, 3, 4   # FHERAM_SRC_*
 STATUS = {0: "OK", 1: "INVALID_ARG", 2: "STATE", 3: "UNINITIALIZED", 4: "KEYS", 5: "UNSUPPORTED", 6: "RANGE", 7: "DEVICE", 8: "PRECISION"}
 
 
@@ -48,6 +51,11 @@ class _CParams(C.Structure):
 
 _CONFIG_FIELDS = ("limb_split", "fine_split", "memo", "pre_inv", "tail", "tail_test", "mid", "mid_test", "chain", "chain_y", "pair_z",
                   "fuse", "graph", "safe", "nco", "tail_ep", "monitor", "reserved")
+
+
+class _CSelectSrc(C.Structure):
+    """fheram_select_src (include/fheram.h): where a candidate word of a select comes from"""
+    _fields_ = [("kind", C.c_int32), ("index", C.c_int32)]
 
 
 class _CConfig(C.Structure):
@@ -128,6 +136,16 @@ _SYMBOLS = [
     ("fheram_bank_fheuint_create", C.c_int, [C.c_void_p, I64P, C.c_int, C.POINTER(C.c_void_p)]),
     ("fheram_bank_address_alloc", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     ("fheram_bank_address_derive", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_selector_alloc", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_selector_create", C.c_int, [C.c_void_p, C.POINTER(I64P), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_selector_derive", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_selector_download", C.c_int, [C.c_void_p, C.c_void_p, I64P]),
+    ("fheram_selector_n_digits", C.c_int, [C.c_void_p]),
+    ("fheram_selector_destroy", None, [C.c_void_p]),
+    ("fheram_bank_select", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.POINTER(_CSelectSrc), I64P, I64P]),
+    ("fheram_bank_select_result", C.c_int, [C.c_void_p, C.c_int, C.c_int, I64P]),
+    ("fheram_bank_write_list_selected", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int)]),
+    ("fheram_bank_selftest_fail_select_alloc", C.c_int, [C.c_void_p, C.c_int]),
     ("fheram_timer_begin", C.c_int, [C.c_void_p]),
     ("fheram_timer_end", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("fheram_profile_enable", C.c_int, [C.c_void_p, C.c_int]),
@@ -550,6 +568,70 @@ def _derive_addresses(owner, fn, fheuints, addrs, sign):
         a._handles = {id(owner): a._handles[id(owner)]}
         a._derived_from = f                                            # the integer stays alive until the launch that reads it has run
     return addrs
+
+
+class Src:
+    """Where a candidate word of RamBank.select comes from (fheram_select_src): Src.member(m), Src.list(k), Src.select(k), Src.host(i), Src.zero()"""
+
+    def __init__(self, kind: int, index: int = 0):
+        self.kind, self.index = int(kind), int(index)
+
+    @classmethod
+    def zero(cls):
+        """all-zero ciphertexts"""
+        return cls(SRC_ZERO)
+
+    @classmethod
+    def host(cls, i: int):
+        """slot i of the call's host_words"""
+        return cls(SRC_HOST, i)
+
+    @classmethod
+    def member(cls, m: int):
+        """member m's last read / read_prepare_write result"""
+        return cls(SRC_MEMBER_RESULT, m)
+
+    @classmethod
+    def list(cls, k: int):
+        """entry k of the last read list"""
+        return cls(SRC_LIST_RESULT, k)
+
+    @classmethod
+    def select(cls, k: int):
+        """output k of the previous select"""
+        return cls(SRC_SELECT_RESULT, k)
+
+
+class Selector:
+    """The encrypted index of a select over up to 2^bits candidates (fheram_selector): the Address of a one-row RAM of max_addr = 2^bits on
+    a bank's device.  RamBank.selector(bits) makes one without digits, Selector.from_digits one from host std-form GGSW digits;
+    RamBank.derive_selectors fills either from bits of an encrypted integer."""
+
+    def __init__(self, bank: "RamBank", handle, bits: int):
+        self.bank, self._h, self.bits = bank, handle, int(bits)
+        self._derived_from = None
+
+    @classmethod
+    def from_digits(cls, bank: "RamBank", bits: int, ggsw_digits):
+        digits = [_i64(g).ravel() for g in ggsw_digits]
+        arr = (I64P * max(len(digits), 1))(*[_p(d) for d in digits])
+        out = C.c_void_p()
+        bank._chk(library().fheram_bank_selector_create(bank._h, arr, len(digits), int(bits), C.byref(out)))
+        return cls(bank, out.value, bits)
+
+    def n_digits(self) -> int:
+        return int(library().fheram_selector_n_digits(self._h))
+
+    def download(self) -> np.ndarray:
+        """the std-form GGSW digits, [n_digits][ggsw_len]"""
+        out = np.zeros((self.n_digits(), self.bank.params.ggsw_len()), dtype=np.int64)
+        self.bank._chk(library().fheram_bank_selector_download(self.bank._h, self._h, _p(out)))
+        return out
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _LIB is not None:
+            _LIB.fheram_selector_destroy(self._h)
+            self._h = None
 
 
 class _AddrHandle:
@@ -1376,6 +1458,78 @@ class RamBank:
         """as Ram.derive_addresses, with integers and addresses bound to this bank (FheUintPrepared.from_host(bank, ...),
         Address.alloc(bank)): a derived address is an ordinary bank address and may serve several members"""
         return _derive_addresses(self, library().fheram_bank_address_derive, fheuints, addrs, sign)
+
+    # -- oblivious select (include/fheram.h: pick a word by an encrypted index)
+    def selector(self, bits: int) -> Selector:
+        """a selector of `bits` bits with its buffers and no digits yet (fheram_bank_selector_alloc): what derive_selectors fills"""
+        out = C.c_void_p()
+        self._chk(library().fheram_bank_selector_alloc(self._h, int(bits), C.byref(out)))
+        return Selector(self, out.value, bits)
+
+    def derive_selectors(self, fheuints, first_bits, sels):
+        """sels[i] <- bits [first_bits[i], first_bits[i] + sels[i].bits) of fheuints[i] (fheram_bank_selector_derive): one launch per
+        distinct (first_bit, bits) pair, no allocation, no host wait, in place"""
+        fheuints, first_bits, sels = list(fheuints), [int(f) for f in first_bits], list(sels)
+        k = len(sels)
+        if not 1 <= k <= SELECT_MAX or len(fheuints) != k or len(first_bits) != k:
+            raise FheRamError(1, f"derive_selectors takes 1 to SELECT_MAX = {SELECT_MAX} selectors and as many integers and first bits")
+        if not all(isinstance(f, FheUintPrepared) for f in fheuints) or not all(isinstance(s, Selector) for s in sels):
+            raise FheRamError(1, "derive_selectors: every integer must be a FheUintPrepared and every selector a Selector")
+        fa, sa = (C.c_void_p * k)(*[f._h for f in fheuints]), (C.c_void_p * k)(*[s._h for s in sels])
+        self._chk(library().fheram_bank_selector_derive(self._h, fa, (C.c_int * k)(*first_bits), k, sa))
+        for s, f in zip(sels, fheuints):
+            s._derived_from = f   # the integer stays alive until the launch that reads it has run
+        return sels
+
+    def select(self, sels, candidates, host_words=None, download: bool = True, keys: Optional[EvaluationKeysPrepared] = None):
+        """n selects as ONE operation (fheram_bank_select): candidates[k] is the list of Src of select k, of which sels[k] picks one.
+        host_words: [..][word_size][GLWE], the slots Src.host(i) names.  int64 [n][word_size][GLWE]; download=False: no host wait
+        (select_result later).  keys: loaded first when given (else the bank's loaded keys).  No member, and no result of an earlier
+        read list, is touched."""
+        sels, candidates = list(sels), [list(c) for c in candidates]
+        n = len(sels)
+        if n < 1 or len(candidates) != n or not all(isinstance(s, Selector) for s in sels):
+            raise FheRamError(1, "select takes at least one Selector and one candidate list per selector")
+        flat = [s for c in candidates for s in c]
+        if not flat or not all(isinstance(s, Src) for s in flat):
+            raise FheRamError(1, "every candidate must be a Src")
+        p = self.params
+        per = p.word_size() * p.glwe_len()
+        hw = None
+        if host_words is not None:
+            hw = _i64(host_words)
+            slots = [s.index for s in flat if s.kind == SRC_HOST]
+            if slots and (min(slots) < 0 or (max(slots) + 1) * per > hw.size):
+                raise FheRamError(1, f"a host candidate names a slot outside host_words ({hw.size // per} slots of {p.word_size()} GLWEs)")
+        srcs = (_CSelectSrc * len(flat))(*[_CSelectSrc(s.kind, s.index) for s in flat])
+        if keys is not None:
+            self._use_keys(keys)
+        out = np.zeros((n, p.word_size(), p.glwe_len()), dtype=np.int64) if download else None
+        self._chk(library().fheram_bank_select(self._h, (C.c_void_p * n)(*[s._h for s in sels]), (C.c_int * n)(*[len(c) for c in candidates]), n,
+                                               srcs, _p(hw) if hw is not None else None, _p(out) if download else None))
+        return out
+
+    def select_result(self, first: int = 0, n: int = 1) -> np.ndarray:
+        """outputs [first, first + n) of the last select: int64 [n][word_size][GLWE]"""
+        first, n = int(first), int(n)
+        p = self.params
+        out = np.zeros((max(n, 1), p.word_size(), p.glwe_len()), dtype=np.int64)
+        self._chk(library().fheram_bank_select_result(self._h, first, n, _p(out)))
+        return out
+
+    def write_list_selected(self, members, picks, addresses, keys: EvaluationKeysPrepared):
+        """write_list whose words are outputs of the last select (fheram_bank_write_list_selected): entry k writes output picks[k] to
+        member members[k] at addresses[k]; the words never leave the device.  Never waits for the device."""
+        n, mem, arr = self._list_args("write_list_selected", members, addresses)
+        picks = [int(x) for x in picks]
+        if len(picks) != n:
+            raise FheRamError(1, f"write_list_selected: {n} members need {n} picks")
+        self._use_keys(keys)
+        self._chk(library().fheram_bank_write_list_selected(self._h, mem, arr, n, (C.c_int * n)(*picks)))
+
+    def selftest_fail_select_alloc(self, nth: int):
+        """self-test: the nth device allocation the select's buffers ask for from now on fails once (0: none)"""
+        self._chk(library().fheram_bank_selftest_fail_select_alloc(self._h, int(nth)))
 
     def result(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
         """the results of each member's last read / read_prepare_write"""

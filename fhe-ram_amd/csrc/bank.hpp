@@ -27,6 +27,8 @@
 // The write's inverse digits are never started early in a bank of more than one member (pre_inv shares d_prep_inv and d_tail_sync between
 // members); a bank of ONE member is a plain context in every respect.  Bank operations are never captured into a hipGraph: under graph = 1
 // they are enqueued directly, in the forms that mode selects.
+// The bank's oblivious select (fheram_bank_select and the write that takes its words from it) is select.hpp: it runs on buffers of its own
+// (`sel`) and reads, of what is here, only where a member's result and the last read list's results sit.
 #pragma once
 #include "path.hpp"
 
@@ -43,6 +45,9 @@ struct fheram_bank {
     int kept_alone = 0, kept_n = 0;
     unsigned kept_map = 0;
     bool wl_holds[FHERAM_BANK_MAX] = {};   // ... and member m is still as that operation left it (cleared by whatever touches the member)
+    SelectBufs sel;               // fheram_bank_select: buffers of its own (select.hpp)
+    int sel_n = 0, sel_fail_alloc = 0;   // outputs of the last select (in sel.res; 0: none has run); the self-test's failing allocation, as wl_fail_alloc
+    bool has_res[FHERAM_BANK_MAX] = {};  // member m has the result of a read / read_prepare_write in its slot (a select may take it as a candidate)
     int wl_fail_alloc = 0;        // fheram_bank_selftest_fail_list_alloc: the wl_fail_alloc-th next device allocation of wl fails (0: none)
 };
 
@@ -174,7 +179,7 @@ void set_assign(fheram_bank* b, const MemberSet& s, const RamState& st, bool den
     for (int k = 0; k < s.n; k++) {
         RamState& r = b->ram[s.m[k]];
         r.state = state; r.memo_top = st.memo_top; r.memo_alone = dense ? 0 : st.memo_alone;
-        if (new_result) r.res_in_trtop = st.res_in_trtop;
+        if (new_result) { r.res_in_trtop = st.res_in_trtop; b->has_res[s.m[k]] = true; }
         b->wl_holds[s.m[k]] = dense && st.memo_alone > 0;
     }
 }
@@ -293,6 +298,7 @@ void fheram_bank_destroy(fheram_bank* b) {
     if (b->c) { hipSetDevice(b->c->device); for (hipStream_t s : {b->c->stream, b->c->stream2}) if (s) hipStreamSynchronize(s); }
     dense_free(b->list);
     dense_free(b->wl);
+    select_free(b->sel);
     fheram_ctx_destroy(b->c);
     delete b;
 }

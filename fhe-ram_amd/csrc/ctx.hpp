@@ -344,6 +344,22 @@ void prof_collect(fheram_ctx* c) {
     }
 }
 
+// get_base_2d (base.rs:84-108): the digit plan of a RAM of max_addr words over the parameters' DECOMP_N, one vector of digit widths per coordinate
+std::vector<std::vector<int>> base_2d(uint64_t max_addr, const fheram_params& p) {
+    std::vector<std::vector<int>> plan;
+    uint32_t x = (uint32_t)(max_addr - 1), bits = 0;
+    while (x) { bits++; x >>= 1; }
+    while (bits != 0) {
+        std::vector<int> v;
+        for (uint32_t i = 0; i < p.n_decomp; i++) {
+            const uint32_t b = p.decomp_n[i];
+            if (b <= bits) { v.push_back((int)b); bits -= b; }
+            else { if (bits != 0) { v.push_back((int)bits); bits = 0; } break; }
+        }
+        plan.push_back(v);
+    }
+    return plan;
+}
 int ilog2_ceil(size_t x) { int k = 0; while (((size_t)1 << k) < x) k++; return k; }
 int galois_mod(int64_t g) { const int64_t m = 2 * N; return (int)(((g % m) + m) % m); }
 int galois_inv_mod(int g) {   // g odd; g^(N-1) = g^-1 mod 2N

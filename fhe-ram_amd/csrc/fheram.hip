@@ -97,19 +97,7 @@ int fheram_ctx_create_cfg(const fheram_params* p, int device, int shard, int n_s
         return fail(nullptr, FHERAM_ERR_INVALID_ARG, "row sharding needs a power-of-two number of rows >= n_shards (else: replicas only)");
     }
     c->rows = c->rows_glob / (size_t)n_shards;
-    {   // get_base_2d (base.rs:84-108)
-        uint32_t x = (uint32_t)(p->max_addr - 1), bits = 0;
-        while (x) { bits++; x >>= 1; }
-        while (bits != 0) {
-            std::vector<int> v;
-            for (uint32_t i = 0; i < p->n_decomp; i++) {
-                const uint32_t b = p->decomp_n[i];
-                if (b <= bits) { v.push_back((int)b); bits -= b; }
-                else { if (bits != 0) { v.push_back((int)bits); bits = 0; } break; }
-            }
-            c->base2d.push_back(v);
-        }
-    }
+    c->base2d = base_2d(p->max_addr, *p);   // get_base_2d (base.rs:84-108)
     c->n2 = (int)c->base2d.size();
     for (auto& v : c->base2d) { c->n_digits += (int)v.size(); c->max_digits = std::max(c->max_digits, (int)v.size()); }
     for (int i = 0; i < LOGN; i++) c->gal[i] = galois_element(i);
@@ -849,3 +837,4 @@ int fheram_device_info(const fheram_ctx* c, char* name, size_t name_len, int* cu
 #include "selftest.hpp"
 #include "group.hpp"
 #include "bank.hpp"
+#include "select.hpp"

@@ -321,6 +321,26 @@ RamView dense_view(const fheram_ctx* c, const DenseBufs& L) {
     return RamView{c->d_data, L.A, L.B, L.C, L.D, L.part ? L.part : L.tmp2, L.tmp, L.tmp2, L.res, L.tree, L.w, L.trtop};
 }
 
+// fheram_bank_select's own buffers (select.hpp): per output ciphertext the packed row, the products' output, two temporaries and the result;
+// the selectors' prepared digits; the staged host candidates.  Allocated on first use, grown to the largest call seen, freed with the bank.
+struct SelectBufs {
+    int cap = 0, prep_cap = 0, host_cap = 0;   // ciphertexts; prepared GGSW digits; ciphertexts of host candidates
+    int32_t *packed = nullptr, *ep = nullptr, *tmp = nullptr, *tmp2 = nullptr, *res = nullptr;   // [cap] GLWE
+    double* prep = nullptr;                                                                      // [prep_cap] prepared GGSW: select k's digits at k * n_digits
+    int64_t *h_res = nullptr, *d_h_res = nullptr;                                                // pinned, device-visible: the results as int64 (+ the monitor's maximum)
+    int32_t *d_host = nullptr, *h_host = nullptr;                                                // [host_cap] GLWE: host candidates, device / pinned
+    hipEvent_t ev_host = nullptr;                                                                // the last copy out of h_host
+    bool host_busy = false;
+};
+void select_free(SelectBufs& S) {
+    void* bufs[] = {S.packed, S.ep, S.tmp, S.tmp2, S.res, S.prep, S.d_host};
+    for (void* p : bufs) if (p) hipFree(p);
+    if (S.h_res) hipHostFree(S.h_res);
+    if (S.h_host) hipHostFree(S.h_host);
+    if (S.ev_host) hipEventDestroy(S.ev_host);
+    S = SelectBufs{};
+}
+
 // The one result export: every run (source, int32 count) is widened by the device into the pinned buffer h (device address d_h), back to
 // back, with the monitor's maximum as it stood then behind the last (the export kernel copies it there); out != nullptr: copied out.
 struct ResRun { const int32_t* src; size_t n; };

@@ -1,0 +1,341 @@
+// Included by fheram.hip (same translation unit): the oblivious select of a bank — pick one of m candidate words by an ENCRYPTED index,
+// on the device, and a write that takes its words from there.
+//
+// What is restated is the selection step the reference's select_store (store.rs:40-67) and select_rd (arithmetic.rs:212-231) share: "blind-
+// rotate a packed ciphertext by an encrypted index, then trace".  CONTRACT-COMPATIBLE ONLY, as fheram_address_derive is:
+// their callers (the BDD circuits, splice_u8 / splice_u16) are un-vendored and stay out of scope.  In this project's own arithmetic that step
+// is Ram::read on a ONE-ROW RAM (ram.rs:451,457, the rows == 1 path) of max_addr = 2^bits: the row packs candidate j at coefficient j,
+// the address is the index.  So:
+//   selector   the Address of such a RAM: the digits get_base_2d(2^bits) gives over the bank's DECOMP_N (one coordinate), each the GGSW of
+//              X^-v (Address::encrypt_sk's sign) in the layout of address digits; created from host digits or derived from bits
+//              [first_bit, first_bit + bits) of an encrypted integer by k_cmux_chain with that plan (one launch per distinct (first_bit, bits))
+//   pack       k_select_pack (select_pack.hip): one launch per call over n * ws output ciphertexts
+//   chain      the prepared selector digits (k_prepare), the products and the trace: what read_top enqueues for the second coordinate
+//              of a RAM of n * ws ciphertexts with a per-ciphertext operand table — the same launchers, so the same forms under every
+//              configuration (chain_form), `safe`, tail = 0 and fuse = 0 included
+// Everything runs on the bank's main stream and on buffers of the select's own (path.hpp SelectBufs): no member's rows, state flag, tree,
+// result or kept memo is touched, the last read list's results stay readable, and a member between read_prepare_write and write resumes
+// its write exactly as before.
+#pragma once
+#include "bank.hpp"
+#include "select_pack.hpp"
+
+struct fheram_selector {
+    fheram_bank* bank;   // owner (identity check only after creation)
+    int device, bits, n_digits;
+    int32_t* d_ggsw;     // [n_digits] std-form GGSW, int32 (the layout of address digits)
+    unsigned char rsh[FHERAM_SELECT_BITS_MAX], width[FHERAM_SELECT_BITS_MAX], lsh[FHERAM_SELECT_BITS_MAX];   // the digit plan (conversion.rs:45-62)
+    bool empty;          // fheram_bank_selector_alloc: no digits yet
+};
+
+namespace {
+
+static_assert(FHERAM_SELECT_MAX == SELECT_K_MAX && (1 << FHERAM_SELECT_BITS_MAX) == SELECT_CAND_MAX, "the argument struct of k_select_pack holds FHERAM_SELECT_MAX selects of 2^FHERAM_SELECT_BITS_MAX candidates");
+static_assert(FHERAM_SELECT_MAX <= DERIVE_K_MAX && FHERAM_SELECT_BITS_MAX <= DERIVE_DIGITS_MAX, "a selector derivation is one k_cmux_chain launch");
+
+// the selector of `bits` bits with its plan and its device buffer, no digits yet
+int selector_new(fheram_bank* b, int bits, fheram_selector** out) {
+    fheram_ctx* c = b->c;
+    if (bits < 1 || bits > FHERAM_SELECT_BITS_MAX)
+        return fail(c, FHERAM_ERR_INVALID_ARG, "bits = " + std::to_string(bits) + " is outside [1, FHERAM_SELECT_BITS_MAX = " + std::to_string(FHERAM_SELECT_BITS_MAX) + "]");
+    const std::vector<std::vector<int>> plan = base_2d((uint64_t)1 << bits, c->p);
+    if (plan.size() != 1)
+        return fail(c, FHERAM_ERR_UNSUPPORTED, "the bank's DECOMP_N gives a selector of " + std::to_string(bits) + " bits " + std::to_string(plan.size()) + " coordinates; a select is a read of a one-row RAM of one coordinate");
+    HIPCHK(c, hipSetDevice(c->device));
+    fheram_selector* s = new fheram_selector{b, c->device, bits, (int)plan[0].size(), nullptr, {}, {}, {}, true};
+    unsigned at = 0;
+    for (int d = 0; d < s->n_digits; d++) {   // one coordinate: bit_lsh and bit_rsh advance together
+        s->rsh[d] = s->lsh[d] = (unsigned char)at; s->width[d] = (unsigned char)plan[0][d];
+        at += (unsigned)plan[0][d];
+    }
+    const hipError_t e = hipMalloc(&s->d_ggsw, (size_t)s->n_digits * fheram_ctx::GGSW * sizeof(int32_t));
+    if (e != hipSuccess) { delete s; (void)hipGetLastError(); return fail(c, FHERAM_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+    *out = s;
+    return FHERAM_OK;
+}
+
+// Grows the select's buffers to n_ct output ciphertexts, n_prep prepared digits and n_host ciphertexts of host candidates.  The new set is
+// complete before the old one goes, and the last select's results move over: a failure leaves the bank as it was (FHERAM_ERR_DEVICE, and every
+// other operation — a smaller select too — still works).
+int select_reserve(fheram_bank* b, int n_ct, int n_prep, int n_host) {
+    fheram_ctx* c = b->c;
+    SelectBufs& S = b->sel;
+    if (n_ct <= S.cap && n_prep <= S.prep_cap && n_host <= S.host_cap) return FHERAM_OK;
+    SelectBufs nw;
+    nw.cap = std::max(n_ct, S.cap); nw.prep_cap = std::max(n_prep, S.prep_cap); nw.host_cap = std::max(n_host, S.host_cap);
+    const size_t ct = (size_t)nw.cap * fheram_ctx::GLWE * sizeof(int32_t);
+    hipError_t e = hipSuccess;
+    auto dev = [&](auto** p, size_t bytes) {
+        if (e != hipSuccess) return;
+        if (b->sel_fail_alloc > 0 && --b->sel_fail_alloc == 0) e = hipErrorOutOfMemory;   // (as the runtime reports an exhausted device)
+        else e = hipMalloc((void**)p, bytes);
+    };
+    for (int32_t** p : {&nw.packed, &nw.ep, &nw.tmp, &nw.tmp2, &nw.res}) dev(p, ct);
+    dev(&nw.prep, (size_t)nw.prep_cap * fheram_ctx::GGSW * sizeof(double));
+    if (nw.host_cap) dev(&nw.d_host, (size_t)nw.host_cap * fheram_ctx::GLWE * sizeof(int32_t));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&nw.h_res, ct * 2 + sizeof(int64_t), hipHostMallocMapped);   // int64, + the monitor's maximum
+    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&nw.d_h_res, nw.h_res, 0);
+    if (e == hipSuccess && nw.host_cap) e = hipHostMalloc((void**)&nw.h_host, (size_t)nw.host_cap * fheram_ctx::GLWE * sizeof(int32_t), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&nw.ev_host, hipEventDisableTiming);
+    if (e == hipSuccess && b->sel_n) e = hipMemcpyAsync(nw.res, S.res, (size_t)b->sel_n * b->mws * fheram_ctx::GLWE * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess && S.cap) e = hipStreamSynchronize(c->stream);   // whatever still reads or writes the old set
+    if (e != hipSuccess) {
+        select_free(nw);
+        (void)hipGetLastError();   // the next op's error check must not see this allocation's failure
+        return fail(c, FHERAM_ERR_DEVICE, "buffers of a select of " + std::to_string(n_ct) + " ciphertexts: " + hipGetErrorString(e));
+    }
+    select_free(S);
+    S = nw;
+    return FHERAM_OK;
+}
+
+// where candidate (kind, index) sits on the device: ws GLWEs (nullptr: ZERO)
+const int32_t* select_source(const fheram_bank* b, const fheram_select_src& s) {
+    const fheram_ctx* c = b->c;
+    const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
+    switch (s.kind) {
+    case FHERAM_SRC_HOST: return b->sel.d_host + (size_t)s.index * per;
+    case FHERAM_SRC_MEMBER_RESULT: return (b->ram[s.index].res_in_trtop ? c->d_trtop : c->d_res) + (size_t)s.index * per;   // (as set_result)
+    case FHERAM_SRC_LIST_RESULT: return b->list.res + (size_t)s.index * per;
+    case FHERAM_SRC_SELECT_RESULT: return b->sel.res + (size_t)s.index * per;
+    default: return nullptr;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int fheram_bank_selector_alloc(fheram_bank* b, int bits, fheram_selector** out) {
+    if (!b) return FHERAM_ERR_INVALID_ARG;
+    if (!out) return fail(b->c, FHERAM_ERR_INVALID_ARG, "null output");
+    *out = nullptr;
+    return selector_new(b, bits, out);
+}
+int fheram_bank_selector_create(fheram_bank* b, const int64_t* const* ggsw, int n_ggsw, int bits, fheram_selector** out) {
+    if (!b) return FHERAM_ERR_INVALID_ARG;
+    fheram_ctx* c = b->c;
+    if (!out) return fail(c, FHERAM_ERR_INVALID_ARG, "null output");
+    *out = nullptr;
+    if (!ggsw) return fail(c, FHERAM_ERR_INVALID_ARG, "null ggsw");
+    fheram_selector* s = nullptr;
+    int rc = selector_new(b, bits, &s);
+    if (rc != FHERAM_OK) return rc;
+    if (n_ggsw != s->n_digits) rc = fail(c, FHERAM_ERR_INVALID_ARG, "a selector of " + std::to_string(bits) + " bits has " + std::to_string(s->n_digits) + " digits, not " + std::to_string(n_ggsw));
+    for (int i = 0; i < n_ggsw && rc == FHERAM_OK; i++)
+        rc = ggsw[i] ? upload_i64(c, s->d_ggsw + (size_t)i * fheram_ctx::GGSW, ggsw[i], fheram_ctx::GGSW) : fail(c, FHERAM_ERR_INVALID_ARG, "null ggsw digit");
+    if (rc != FHERAM_OK) { fheram_selector_destroy(s); return rc; }
+    s->empty = false;
+    *out = s;
+    return FHERAM_OK;
+}
+// sels[i] <- the selector of bits [first_bit[i], first_bit[i] + bits_i) of fus[i]: Address::set_from_fheuint (conversion.rs:41-65) with the
+// selector's plan shifted by first_bit, through k_cmux_chain — one launch per distinct (first_bit, bits) pair, no allocation, no host wait,
+// in place.  Selector digits are read on the main stream only (fheram_bank_select prepares them there), so the launch is ordered by the stream.
+int fheram_bank_selector_derive(fheram_bank* b, const fheram_fheuint* const* fus, const int* first_bit, int n, fheram_selector* const* sels) {
+    if (!b) return FHERAM_ERR_INVALID_ARG;
+    fheram_ctx* c = b->c;
+    if (!fus || !first_bit || !sels) return fail(c, FHERAM_ERR_INVALID_ARG, "null integer list, bit list or selector list");
+    if (n < 1 || n > FHERAM_SELECT_MAX)
+        return fail(c, FHERAM_ERR_INVALID_ARG, "n = " + std::to_string(n) + " is outside [1, FHERAM_SELECT_MAX = " + std::to_string(FHERAM_SELECT_MAX) + "]");
+    for (int k = 0; k < n; k++) {   // every check for the whole list before anything is enqueued: a refused call changes no selector
+        if (!fus[k] || fus[k]->ctx != c) return fail(c, FHERAM_ERR_INVALID_ARG, "integer " + std::to_string(k) + " is null or belongs to another bank");
+        if (!sels[k] || sels[k]->bank != b) return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " is null or belongs to another bank");
+        if (first_bit[k] < 0 || first_bit[k] + sels[k]->bits > fus[k]->n_bits)
+            return fail(c, FHERAM_ERR_INVALID_ARG, "bits [" + std::to_string(first_bit[k]) + ", " + std::to_string(first_bit[k]) + " + " + std::to_string(sels[k]->bits) + ") of integer " + std::to_string(k) + " are beyond its " + std::to_string(fus[k]->n_bits) + " bits");
+        for (int q = 0; q < k; q++)
+            if (sels[q] == sels[k]) return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " appears twice in the list");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    c->cur = c->stream;
+    main_enqueued(c);
+    bool done[FHERAM_SELECT_MAX] = {};
+    for (int k = 0; k < n; k++) {
+        if (done[k]) continue;
+        CmuxChainArgs ca{};
+        ca.tw = c->d_tw;
+        ca.sign = 0;   // X^-v: what Ram::read accepts (address.rs:102-108)
+        const fheram_selector* s0 = sels[k];
+        for (int d = 0; d < s0->n_digits; d++) { ca.first[d] = (unsigned char)(first_bit[k] + s0->rsh[d]); ca.bits[d] = s0->width[d]; ca.lsh[d] = s0->lsh[d]; }
+        int K = 0;
+        for (int q = k; q < n; q++)
+            if (first_bit[q] == first_bit[k] && sels[q]->bits == s0->bits) { ca.fu[K] = fus[q]->d_prep; ca.out[K] = sels[q]->d_ggsw; K++; done[q] = true; }
+        const int rows = fheram_ctx::DNUM_CT * 2;
+        ProfScope ps(c, "derive", (uint64_t)K * s0->n_digits * rows);
+        cmux_chain_launch(dim3(rows, s0->n_digits, K), c->cur, ca);
+    }
+    HIPCHK(c, hipGetLastError());
+    for (int k = 0; k < n; k++) sels[k]->empty = false;
+    return FHERAM_OK;
+}
+int fheram_bank_selector_download(fheram_bank* b, const fheram_selector* s, int64_t* out) {
+    if (!b) return FHERAM_ERR_INVALID_ARG;
+    fheram_ctx* c = b->c;
+    if (!out) return fail(c, FHERAM_ERR_INVALID_ARG, "null output");
+    if (!s || s->bank != b) return fail(c, FHERAM_ERR_INVALID_ARG, "selector is null or belongs to another bank");
+    if (s->empty) return fail(c, FHERAM_ERR_INVALID_ARG, "empty selector: fheram_bank_selector_alloc without fheram_bank_selector_derive");
+    HIPCHK(c, hipSetDevice(c->device));
+    return download_i64(c, out, s->d_ggsw, (size_t)s->n_digits * fheram_ctx::GGSW);
+}
+int fheram_selector_n_digits(const fheram_selector* s) { return s ? s->n_digits : 0; }
+void fheram_selector_destroy(fheram_selector* s) {
+    if (!s) return;
+    hipSetDevice(s->device);
+    if (s->d_ggsw) hipFree(s->d_ggsw);   // hipFree waits for outstanding work on the buffer
+    delete s;
+}
+
+int fheram_bank_select(fheram_bank* b, const fheram_selector* const* sels, const int* n_cand, int n, const fheram_select_src* srcs,
+                       const int64_t* host_words, int64_t* out) {
+    if (!b) return FHERAM_ERR_INVALID_ARG;
+    fheram_ctx* c = b->c;
+    mid_rearm(c);
+    // ---- every check before anything is enqueued: a refused call changes nothing ----
+    if (!sels || !n_cand || !srcs) return fail(c, FHERAM_ERR_INVALID_ARG, "null selector list, candidate counts or sources");
+    if (n < 1 || n > FHERAM_SELECT_MAX)
+        return fail(c, FHERAM_ERR_INVALID_ARG, "n = " + std::to_string(n) + " is outside [1, FHERAM_SELECT_MAX = " + std::to_string(FHERAM_SELECT_MAX) + "]");
+    const int ws = b->mws, Y = n * ws;
+    if (Y > 64)
+        return fail(c, FHERAM_ERR_INVALID_ARG, "n * word_size = " + std::to_string(Y) + " exceeds 64, the ciphertext limit of the single-launch chains (k_chain_mid)");
+    int total = 0, n_host = 0;
+    for (int k = 0; k < n; k++) {
+        if (!sels[k] || sels[k]->bank != b) return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " is null or belongs to another bank");
+        if (sels[k]->empty) return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " is empty: fheram_bank_selector_alloc without fheram_bank_selector_derive");
+        if (sels[k]->bits != sels[0]->bits)
+            return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " has " + std::to_string(sels[k]->bits) + " bits, selector 0 " + std::to_string(sels[0]->bits) + ": the selects of one call share one digit count (the operand table's)");
+        if (n_cand[k] < 1 || n_cand[k] > (1 << sels[k]->bits))
+            return fail(c, FHERAM_ERR_INVALID_ARG, "select " + std::to_string(k) + " has " + std::to_string(n_cand[k]) + " candidates, outside [1, 2^bits = " + std::to_string(1 << sels[k]->bits) + "]");
+        total += n_cand[k];
+    }
+    bool need_list = false, need_sel = false;
+    for (int i = 0; i < total; i++) {
+        const fheram_select_src& s = srcs[i];
+        const std::string who = "source " + std::to_string(i);
+        switch (s.kind) {
+        case FHERAM_SRC_ZERO: break;
+        case FHERAM_SRC_HOST:
+            if (!host_words) return fail(c, FHERAM_ERR_INVALID_ARG, who + " is a host word and host_words is null");
+            if (s.index < 0 || s.index >= FHERAM_SELECT_MAX * (1 << FHERAM_SELECT_BITS_MAX)) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names host slot " + std::to_string(s.index) + ", outside [0, " + std::to_string(FHERAM_SELECT_MAX * (1 << FHERAM_SELECT_BITS_MAX)) + ")");
+            n_host = std::max(n_host, s.index + 1);
+            break;
+        case FHERAM_SRC_MEMBER_RESULT:
+            if (s.index < 0 || s.index >= b->M) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names member " + std::to_string(s.index) + ", outside the bank's " + std::to_string(b->M) + " members");
+            break;
+        case FHERAM_SRC_LIST_RESULT:
+            if (s.index < 0 || (b->list_n && s.index >= b->list_n)) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names entry " + std::to_string(s.index) + ", outside the last read list's " + std::to_string(b->list_n) + " entries");
+            need_list = true;
+            break;
+        case FHERAM_SRC_SELECT_RESULT:
+            if (s.index < 0 || (b->sel_n && s.index >= b->sel_n)) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names output " + std::to_string(s.index) + ", outside the last select's " + std::to_string(b->sel_n) + " outputs");
+            need_sel = true;
+            break;
+        default: return fail(c, FHERAM_ERR_INVALID_ARG, who + " has the unknown kind " + std::to_string(s.kind));
+        }
+    }
+    if (!c->keys_loaded) return fail(c, FHERAM_ERR_KEYS, "evaluation keys not loaded");
+    if (need_list && !b->list_n) return fail(c, FHERAM_ERR_STATE, "a source names the last read list and no read list has run on this bank");
+    if (need_sel && !b->sel_n) return fail(c, FHERAM_ERR_STATE, "a source names the last select and no select has run on this bank");
+    for (int i = 0; i < total; i++)
+        if (srcs[i].kind == FHERAM_SRC_MEMBER_RESULT && !b->has_res[srcs[i].index])
+            return fail(c, FHERAM_ERR_STATE, "source " + std::to_string(i) + " names the result of member " + std::to_string(srcs[i].index) + ", which has none yet");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int d = sels[0]->n_digits;
+    int rc = select_reserve(b, Y, n * d, n_host * ws);
+    if (rc != FHERAM_OK) return rc;
+    SelectBufs& S = b->sel;
+    const size_t per = (size_t)ws * fheram_ctx::GLWE;
+    if (n_host) {   // the host candidates, range-checked as write words are: only the slots a source names
+        if (S.host_busy) { HIPCHK(c, hipEventSynchronize(S.ev_host)); S.host_busy = false; }
+        std::vector<char> staged((size_t)n_host, 0);
+        for (int i = 0; i < total; i++) {
+            if (srcs[i].kind != FHERAM_SRC_HOST || staged[(size_t)srcs[i].index]) continue;
+            staged[(size_t)srcs[i].index] = 1;
+            if (!narrow(host_words + (size_t)srcs[i].index * per, S.h_host + (size_t)srcs[i].index * per, per))
+                return fail(c, FHERAM_ERR_RANGE, "limb out of the normalised range [-2^16, 2^16]");
+        }
+    }
+    // ---- enqueue ----
+    main_enqueued(c);
+    c->cur = c->stream;
+    c->wide = true;   // (as a write: whatever gate wave a read_prepare_write parked is released by that operation's own trace chain, which is ahead of this on the stream)
+    if (n_host) {
+        for (int sl = 0; sl < n_host; sl++) {
+            bool used = false;
+            for (int i = 0; i < total && !used; i++) used = srcs[i].kind == FHERAM_SRC_HOST && srcs[i].index == sl;
+            if (used) HIPCHK(c, hipMemcpyAsync(S.d_host + (size_t)sl * per, S.h_host + (size_t)sl * per, per * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        }
+        HIPCHK(c, hipEventRecord(S.ev_host, c->stream));
+        S.host_busy = true;
+    }
+    b->sel_n = 0;   // until this select is enqueued there is no last select
+    const long G = (long)fheram_ctx::GLWE;
+    {   // the pack: ONE launch, whatever n and m are
+        SelectPackArgs sa{};
+        sa.out = S.packed; sa.ws = ws;
+        for (int k = 0, i = 0; k < n; k++) {
+            sa.m[k] = n_cand[k];
+            for (int j = 0; j < n_cand[k]; j++, i++) sa.cand[k][j] = select_source(b, srcs[i]);
+        }
+        ProfScope ps(c, "select_pack", (uint64_t)Y);
+        select_pack_launch(dim3(1, Y, EW_SLICES), c->cur, sa);
+    }
+    // the selectors' digits, prepared: select k's at k * stride (CoordinatePrepared::prepare, coordinate_prepared.rs:104-116)
+    const long stride = (long)d * (long)fheram_ctx::GGSW;
+    for (int k = 0; k < n; k++) launch_prepare(c, sels[k]->d_ggsw, S.prep + k * stride, d * (int)(fheram_ctx::GGSW / N));
+    // Ram::read of the one-row RAM {packed} (ram.rs:451,457): the products with the digits in order, then trace(0, log N) — as read_top runs
+    // the second coordinate's products and the final trace of n * ws ciphertexts
+    const GlweRef packed = ref(S.packed, G, 0), ep = ref(S.ep, G, 0), tmp = ref(S.tmp, G, 0), res = ref(S.res, G, 0);
+    const OpndTable table = n == 1 ? OpndTable{} : OpndTable{ws, stride, MEMBER_MAP_IDENTITY, false};
+    auto slice = [&](GlweRef r, int k) { r.p += (long)k * ws * r.sy; return r; };
+    auto products = [&] { for (int k = 0; k < n; k++) ep_chain(c, slice(packed, k), slice(ep, k), slice(tmp, k), S.prep + k * stride, d, 1, ws); };
+    const bool fuse_ep = c->cfg.tail_ep && d >= 2 && d <= TAIL_EP_MAX && chain_form(c, ChainQuery{false, LOGN, 1, Y}).form == ChainForm::Tail;
+    GlweRef tb[2];
+    if (fuse_ep && chain_bufs(LOGN, ep, res, tmp, tb))
+        launch_trace_tail(c, packed, tb, 0, LOGN, 1, Y, S.prep, d, ep, false, table);
+    else {
+        products();
+        trace_steps(c, ep, res, tmp, 0, LOGN, 1, Y);
+    }
+    HIPCHK(c, hipGetLastError());
+    b->sel_n = n;
+    if (!out) return FHERAM_OK;
+    const ResRun run{S.res, (size_t)Y * fheram_ctx::GLWE};
+    return result_export(c, &run, 1, S.h_res, S.d_h_res, out);
+}
+int fheram_bank_select_result(fheram_bank* b, int first, int n, int64_t* out) {
+    if (!b) return FHERAM_ERR_INVALID_ARG;
+    fheram_ctx* c = b->c;
+    if (!out) return fail(c, FHERAM_ERR_INVALID_ARG, "null output");
+    if (!b->sel_n) return fail(c, FHERAM_ERR_STATE, "no select has run on this bank");
+    if (first < 0 || n < 1 || first > b->sel_n - n)
+        return fail(c, FHERAM_ERR_INVALID_ARG, "outputs [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") are empty or outside the last select's " + std::to_string(b->sel_n) + " outputs");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
+    const ResRun run{b->sel.res + (size_t)first * per, (size_t)n * per};
+    return result_export(c, &run, 1, b->sel.h_res, b->sel.d_h_res, out);
+}
+// n independent Ram::write, entry k's words = output picks[k] of the last select: bank_write_set with a stage that copies on the device
+// (no host wait, no range check: a select's outputs are normalised by construction)
+int fheram_bank_write_list_selected(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n, const int* picks) {
+    MemberSet s;
+    const int rc = write_list_check(b, members, addrs, n, !picks, 1, &s);
+    if (rc != FHERAM_OK) return rc;
+    fheram_ctx* c = b->c;
+    if (!b->sel_n) return fail(c, FHERAM_ERR_STATE, "no select has run on this bank");
+    for (int k = 0; k < n; k++)
+        if (picks[k] < 0 || picks[k] >= b->sel_n)
+            return fail(c, FHERAM_ERR_INVALID_ARG, "entry " + std::to_string(k) + " picks output " + std::to_string(picks[k]) + ", outside the last select's " + std::to_string(b->sel_n) + " outputs");
+    const long G = (long)fheram_ctx::GLWE;
+    return bank_write_set(b, s, addrs, [&](int32_t* d_w, int) {
+        main_enqueued(c);
+        for (int k = 0; k < n; k++) launch_copy(c, ref(b->sel.res + (size_t)picks[k] * b->mws * G, G, 0), ref(d_w + (size_t)k * b->mws * G, G, 0), 1, b->mws);
+        return (int)FHERAM_OK;
+    });
+}
+int fheram_bank_selftest_fail_select_alloc(fheram_bank* b, int nth) {
+    if (!b || nth < 0) return FHERAM_ERR_INVALID_ARG;
+    b->sel_fail_alloc = nth;
+    return FHERAM_OK;
+}
+
+}  // extern "C"

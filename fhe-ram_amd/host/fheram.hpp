@@ -512,6 +512,75 @@ public:
         chk(fheram_bank_address_derive(bank_, fh.data(), (int)fh.size(), sign ? 1 : 0, ah.data()));
         for (Address* a : addrs) a->digits.clear();
     }
+    // ---- oblivious select (include/fheram.h): pick one of the candidate words by an encrypted index, on the device
+    // the encrypted index over up to 2^bits candidates: from host std-form GGSW digits (fheram_bank_selector_create), or without digits, for derive_selectors
+    class Selector {
+    public:
+        Selector(Bank& bank, int bits) { bank.chk(fheram_bank_selector_alloc(bank.bank_, bits, &h_)); }
+        Selector(Bank& bank, int bits, const std::vector<std::vector<int64_t>>& digits) {
+            std::vector<const int64_t*> ptr;
+            for (auto& d : digits) ptr.push_back(d.data());
+            bank.chk(fheram_bank_selector_create(bank.bank_, ptr.data(), (int)ptr.size(), bits, &h_));
+        }
+        ~Selector() { if (h_) fheram_selector_destroy(h_); }
+        Selector(const Selector&) = delete;
+        int n_digits() const { return fheram_selector_n_digits(h_); }
+    private:
+        friend class Bank;
+        fheram_selector* h_ = nullptr;
+    };
+    // *sels[i] <- bits [first_bits[i], first_bits[i] + bits_i) of *fheuints[i] (fheram_bank_selector_derive): no allocation, no host wait
+    void derive_selectors(const std::vector<const FheUintPrepared*>& fheuints, const std::vector<int>& first_bits, const std::vector<Selector*>& sels) {
+        if (sels.empty() || sels.size() > FHERAM_SELECT_MAX || fheuints.size() != sels.size() || first_bits.size() != sels.size())
+            throw Error(FHERAM_ERR_INVALID_ARG, "derive_selectors takes 1 to FHERAM_SELECT_MAX selectors and as many integers and first bits");
+        std::vector<const fheram_fheuint*> fh;
+        std::vector<fheram_selector*> sh;
+        for (const FheUintPrepared* f : fheuints) { if (!f) throw Error(FHERAM_ERR_INVALID_ARG, "null integer"); fh.push_back(f->h_); }
+        for (Selector* x : sels) { if (!x) throw Error(FHERAM_ERR_INVALID_ARG, "null selector"); sh.push_back(x->h_); }
+        chk(fheram_bank_selector_derive(bank_, fh.data(), first_bits.data(), (int)sh.size(), sh.data()));
+    }
+    static fheram_select_src src_zero() { return {FHERAM_SRC_ZERO, 0}; }
+    static fheram_select_src src_host(int slot) { return {FHERAM_SRC_HOST, slot}; }           // slot of host_words
+    static fheram_select_src src_member(int member) { return {FHERAM_SRC_MEMBER_RESULT, member}; }
+    static fheram_select_src src_list(int entry) { return {FHERAM_SRC_LIST_RESULT, entry}; }
+    static fheram_select_src src_select(int output) { return {FHERAM_SRC_SELECT_RESULT, output}; }
+    // sels.size() selects as ONE operation (fheram_bank_select): *sels[k] picks one of candidates[k]; result k is the picked word.  The keys are
+    // those the bank has loaded (any earlier operation's).  download = false: no host wait, an empty result (select_result later).
+    std::vector<std::vector<Glwe>> select(const std::vector<const Selector*>& sels, const std::vector<std::vector<fheram_select_src>>& candidates,
+                                          const std::vector<std::vector<Glwe>>& host_words = {}, bool download = true) {
+        if (sels.empty() || candidates.size() != sels.size()) throw Error(FHERAM_ERR_INVALID_ARG, "select takes at least one selector and one candidate list per selector");
+        std::vector<const fheram_selector*> sh;
+        std::vector<int> n_cand;
+        std::vector<fheram_select_src> flat_src;
+        for (const Selector* x : sels) { if (!x) throw Error(FHERAM_ERR_INVALID_ARG, "null selector"); sh.push_back(x->h_); }
+        for (auto& c : candidates) { n_cand.push_back((int)c.size()); flat_src.insert(flat_src.end(), c.begin(), c.end()); }
+        std::vector<int64_t> flat;
+        for (auto& word : host_words) {
+            if (word.size() != params.word_size()) throw Error(FHERAM_ERR_INVALID_ARG, "a host candidate has word_size GLWEs");
+            for (auto& g : word) flat.insert(flat.end(), g.begin(), g.end());
+        }
+        for (auto& x : flat_src)
+            if (x.kind == FHERAM_SRC_HOST && (x.index < 0 || (size_t)x.index >= host_words.size())) throw Error(FHERAM_ERR_INVALID_ARG, "a host candidate names a slot outside host_words");
+        std::vector<int64_t> out(download ? sh.size() * params.word_size() * glwe_len() : 0);
+        chk(fheram_bank_select(bank_, sh.data(), n_cand.data(), (int)sh.size(), flat_src.data(), flat.empty() ? nullptr : flat.data(), download ? out.data() : nullptr));
+        return download ? split(out, sh.size()) : std::vector<std::vector<Glwe>>();
+    }
+    // outputs [first, first + n) of the last select (fheram_bank_select_result)
+    std::vector<std::vector<Glwe>> select_result(int first, int n) {
+        if (n < 1) throw Error(FHERAM_ERR_INVALID_ARG, "empty slice of the last select");
+        std::vector<int64_t> out((size_t)n * params.word_size() * glwe_len());
+        chk(fheram_bank_select_result(bank_, first, n, out.data()));
+        return split(out, (size_t)n);
+    }
+    // write_list whose words are outputs of the last select (fheram_bank_write_list_selected): output picks[k] to member members[k] at
+    // *addresses[k]; the words never leave the device
+    void write_selected(const std::vector<int>& members, const std::vector<int>& picks, std::vector<Address*>& addresses, const EvaluationKeysPrepared& keys) {
+        if (members.empty() || addresses.size() != members.size() || picks.size() != members.size())
+            throw Error(FHERAM_ERR_INVALID_ARG, "write_selected takes at least one member, as many addresses and one pick per member");
+        use(keys);
+        std::vector<const fheram_addr*> h = handles(addresses);
+        chk(fheram_bank_write_list_selected(bank_, members.data(), h.data(), (int)h.size(), picks.data()));
+    }
     void sync() { chk(fheram_bank_sync(bank_)); }
     double roundoff_max() { double m = 0.0; chk(fheram_bank_roundoff_max(bank_, &m)); return m; }
     struct ChainStats { uint64_t launches = 0, redone = 0; };

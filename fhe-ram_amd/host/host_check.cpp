@@ -126,6 +126,24 @@ int main() {
             try { std::vector<fheram::Address*> dup = {&a0, &a1}; lists.read_prepare_write_list({1, 1}, dup, bk); return 14; }
             catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 14; }
             std::printf("bank write lists == single-member operations: ok\n");
+            // Bank::select / write_selected: the conditional write of members {2, 0} with the picked words kept on the device, against the twin
+            // that downloads its select outputs and writes them with write_list (synthetic selector digits: the path is deterministic)
+            std::vector<std::vector<int64_t>> sd = {synth(3 * 2 * 4 * 2 * n)};
+            fheram::Bank::Selector ls0(lists, 1, sd), ls1(lists, 1, sd), ts0(twin, 1, sd), ts1(twin, 1, sd);
+            if (ls0.n_digits() != 1) return 15;
+            const std::vector<std::vector<fheram_select_src>> cand = {{fheram::Bank::src_member(2), fheram::Bank::src_host(0)}, {fheram::Bank::src_member(0), fheram::Bank::src_host(1)}};
+            lists.read_prepare_write_list(wm, wa, bk);
+            twin.read_prepare_write_list(wm, wa, bk);
+            if (!lists.select({&ls0, &ls1}, cand, words, false).empty()) return 15;
+            const auto picked = twin.select({&ts0, &ts1}, cand, words);
+            if (picked.size() != 2 || lists.select_result(0, 2) != picked) { std::printf("select: the two banks differ\n"); return 15; }
+            lists.write_selected(wm, {0, 1}, wa, bk);
+            twin.write_list(wm, picked, wa, bk);
+            for (int m = 0; m < 3; m++)
+                if (lists.state(m) || lists.store_encrypted(m) != twin.store_encrypted(m)) { std::printf("write_selected: member %d differs\n", m); return 15; }
+            try { lists.select({&ts0}, {{fheram::Bank::src_zero()}}); return 16; }   // a selector of another bank
+            catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 16; }
+            std::printf("bank select + write_selected == select, download, write_list: ok\n");
         }
     } catch (const fheram::Error& e) {
         if (e.code != FHERAM_ERR_DEVICE) { std::printf("unexpected error %d: %s\n", e.code, e.what()); return 4; }

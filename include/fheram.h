@@ -469,6 +469,68 @@ int fheram_bank_fheuint_create(fheram_bank* bank, const int64_t* bits, int n_bit
 int fheram_bank_address_alloc(fheram_bank* bank, fheram_addr** out);
 int fheram_bank_address_derive(fheram_bank* bank, const fheram_fheuint* const* fus, int n, int sign, fheram_addr* const* addrs);
 
+/* ---- Oblivious select on a bank: pick one of m candidate words by an ENCRYPTED index, on the device — a VM step's write enable
+ * (`enable ? new : old`), its store merge and result pick, and its moves between memories, without a host round trip.
+ * *** CONTRACT-COMPATIBLE ONLY *** (as fheram_address_derive above): what is restated is the selection step that the reference's
+ * select_store (store.rs:40-67) and select_rd (arithmetic.rs:212-231) share — "blind-rotate a packed ciphertext by an encrypted index,
+ * then trace" — in this library's own arithmetic, where it is exactly Ram::read (ram.rs:451,457) on a ONE-ROW RAM of max_addr = 2^bits
+ * whose row packs candidate j at coefficient j and whose address is the index.  Their callers (the BDD circuits, splice_u8 / splice_u16)
+ * are un-vendored and out of scope.
+ * A SELECTOR of `bits` bits is the Address of such a RAM: the digit plan get_base_2d(2^bits) gives over the bank's DECOMP_N (one
+ * coordinate; [3,3,3,3] gives [1] [2] [3] [3,1] [3,2] for bits = 1..5), each digit the GGSW of X^-v (the sign of Address::encrypt_sk,
+ * sign = 0 of fheram_address_derive) in the layout of address digits (k_ggsw_addr: 4 limbs, dnum 3). */
+#define FHERAM_SELECT_BITS_MAX 5          /* up to 32 candidates */
+#define FHERAM_SELECT_MAX 8               /* selects per call; n * word_size <= 64 as for the lists */
+typedef struct fheram_selector fheram_selector;
+/* buffers and no digits: fheram_bank_select refuses it (FHERAM_ERR_INVALID_ARG) until it has been derived */
+int fheram_bank_selector_alloc(fheram_bank* bank, int bits, fheram_selector** out);
+/* from n_ggsw host std-form digits (n_ggsw must be the plan's digit count: fheram_selector_n_digits) */
+int fheram_bank_selector_create(fheram_bank* bank, const int64_t* const* ggsw, int n_ggsw, int bits, fheram_selector** out);
+/* sels[i] <- bits [first_bit[i], first_bit[i] + bits_i) of fus[i], in place (a selector from _alloc, _create or an earlier derivation),
+ * through k_cmux_chain: one launch per distinct (first_bit, bits) pair, no allocation, no host wait; later selects are ordered behind it
+ * on the bank's stream.  The integers must stay alive until the bank has been synchronised.  Checked for the whole list before anything
+ * is enqueued, a refused call changes nothing (FHERAM_ERR_INVALID_ARG): null pointers, n outside [1, FHERAM_SELECT_MAX], a selector or
+ * integer of another bank, first_bit + bits beyond the integer's width, the same selector twice. */
+int fheram_bank_selector_derive(fheram_bank* bank, const fheram_fheuint* const* fus, const int* first_bit, int n, fheram_selector* const* sels);
+/* the std-form digits, [n_digits][fheram_ggsw_len] */
+int fheram_bank_selector_download(fheram_bank* bank, const fheram_selector* sel, int64_t* out);
+int fheram_selector_n_digits(const fheram_selector* sel);
+void fheram_selector_destroy(fheram_selector* sel);
+/* Where a candidate word (word_size GLWEs, each encrypting [v, 0, .., 0]) comes from. */
+enum { FHERAM_SRC_ZERO = 0,            /* all-zero ciphertexts                                                                */
+       FHERAM_SRC_HOST = 1,            /* slot `index` of host_words ([..][word_size][GLWE]), range-checked as write words are */
+       FHERAM_SRC_MEMBER_RESULT = 2,   /* member `index`'s last read / read_prepare_write result                              */
+       FHERAM_SRC_LIST_RESULT = 3,     /* entry `index` of the last read list                                                 */
+       FHERAM_SRC_SELECT_RESULT = 4 }; /* output `index` of the previous select call                                          */
+typedef struct fheram_select_src { int32_t kind, index; } fheram_select_src;
+/* n selects as ONE operation.  Select k has the candidates srcs[off_k .. off_k + n_cand[k]), off_k = the sum of the earlier n_cand, and
+ * for every word ciphertext y
+ *     packed_y = glwe_normalize( sum_{j < n_cand[k]} X^j * c_j[y] )          (one launch for the whole call: k_select_pack)
+ *     out_k[y] = Ram::read of the one-row RAM {packed_y} (max_addr = 2^bits) at sels[k]: the products with its digits in order, then
+ *                trace(0, log N) — the launches a read's top enqueues, in the forms the bank's configuration selects.
+ * The selected index i < n_cand[k] gives candidate i; an index >= n_cand[k] an encryption of 0.  All selectors of one call have the
+ * same `bits` (one digit count for the operand table).  out: [n][word_size][GLWE], or NULL (no host wait; fheram_bank_select_result later).
+ * The select runs on buffers of its own (allocated on first use, grown to the largest call, freed with the bank; FHERAM_ERR_DEVICE if
+ * that fails, every other operation still works): no member's rows, state flag, tree, result or kept memo changes — a member between
+ * read_prepare_write and write resumes its write exactly as before — and the last read list's results stay readable.
+ * Checked before anything is enqueued, a refused call changes nothing.  FHERAM_ERR_INVALID_ARG: null arguments, n outside
+ * [1, FHERAM_SELECT_MAX], n * word_size > 64, n_cand[k] outside [1, 2^bits], a foreign or underived selector, selectors of different
+ * bits, an unknown source kind, an index outside the bank, the last list or the last select, a HOST source with host_words == NULL;
+ * FHERAM_ERR_KEYS: keys not loaded; FHERAM_ERR_STATE: a MEMBER_RESULT member without a result, a LIST_RESULT / SELECT_RESULT source
+ * when no such operation has run; FHERAM_ERR_RANGE: a host limb out of range. */
+int fheram_bank_select(fheram_bank* bank, const fheram_selector* const* sels, const int* n_cand, int n,
+                       const fheram_select_src* srcs, const int64_t* host_words, int64_t* out /* [n][word_size][GLWE] or NULL */);
+/* outputs [first, first + n) of the LAST select; FHERAM_ERR_STATE before any select has run */
+int fheram_bank_select_result(fheram_bank* bank, int first, int n, int64_t* out);
+/* entry k: Ram::write (ram.rs:226-294) of output picks[k] of the last fheram_bank_select to member members[k] at addrs[k].  Checks and
+ * semantics are those of fheram_bank_write_list; the words are copied on the device (no host wait, no range check: a select's outputs
+ * are normalised by construction), and rows and results are int64-identical to fheram_bank_write_list given the downloaded outputs.
+ * Also FHERAM_ERR_STATE: no select has run; FHERAM_ERR_INVALID_ARG: a pick outside the last select. */
+int fheram_bank_write_list_selected(fheram_bank* bank, const int* members, const fheram_addr* const* addrs, int n, const int* picks);
+/* Self-test of fheram_bank_select's FHERAM_ERR_DEVICE path, as fheram_bank_selftest_fail_list_alloc: the nth device allocation its
+ * buffers ask for from now on fails once (0 withdraws the request). */
+int fheram_bank_selftest_fail_select_alloc(fheram_bank* bank, int nth);
+
 /* ---- Measurement hooks (bench.py).  HIP events recorded on the context's own stream. */
 int fheram_timer_begin(fheram_ctx* ctx);
 int fheram_timer_end(fheram_ctx* ctx, float* elapsed_ms);
