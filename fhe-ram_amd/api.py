@@ -32,6 +32,7 @@ DERIVE_MAX = 8       # FHERAM_DERIVE_MAX
 SELECT_BITS_MAX = 5  # FHERAM_SELECT_BITS_MAX
 SELECT_MAX = 8       # FHERAM_SELECT_MAX
 SRC_ZERO, SRC_HOST, SRC_MEMBER_RESULT, SRC_LIST_RESULT, SRC_SELECT_RESULT = 0, 1, 2, 3, 4   # FHERAM_SRC_*
+SELECT_FIELDS_MAX = 5   # FHERAM_SELECT_FIELDS_MAX
 STATUS = {0: "OK", 1: "INVALID_ARG", 2: "STATE", 3: "UNINITIALIZED", 4: "KEYS", 5: "UNSUPPORTED", 6: "RANGE", 7: "DEVICE", 8: "PRECISION"}
 
 
@@ -56,6 +57,11 @@ _CONFIG_FIELDS = ("limb_split", "fine_split", "memo", "pre_inv", "tail", "tail_t
 class _CSelectSrc(C.Structure):
     """fheram_select_src (include/fheram.h): where a candidate word of a select comes from"""
     _fields_ = [("kind", C.c_int32), ("index", C.c_int32)]
+
+
+class _CSelectLane(C.Structure):
+    """fheram_select_lane (include/fheram.h): GLWE `lane` of the word (kind, index)"""
+    _fields_ = [("kind", C.c_int32), ("index", C.c_int32), ("lane", C.c_int32), ("reserved", C.c_int32)]
 
 
 class _CConfig(C.Structure):
@@ -136,6 +142,12 @@ _SYMBOLS = [
     ("fheram_bank_fheuint_create", C.c_int, [C.c_void_p, I64P, C.c_int, C.POINTER(C.c_void_p)]),
     ("fheram_bank_address_alloc", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     ("fheram_bank_address_derive", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    ("fheram_address_derive_at", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_address_derive_at", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_select_lanes", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.POINTER(_CSelectLane), I64P, I64P]),
+    ("fheram_bank_selector_alloc_fields", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_selector_create_fields", C.c_int, [C.c_void_p, C.POINTER(I64P), C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_selector_derive_fields", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
     ("fheram_bank_selector_alloc", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     ("fheram_bank_selector_create", C.c_int, [C.c_void_p, C.POINTER(I64P), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     ("fheram_bank_selector_derive", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
@@ -546,10 +558,15 @@ class FheUintPrepared:
             self._h = None
 
 
-def _derive_addresses(owner, fn, fheuints, addrs, sign):
-    """Ram.derive_addresses / RamBank.derive_addresses: addrs[i] <- Address::set_from_fheuint(fheuints[i]) as ONE launch"""
+def _derive_addresses(owner, fn, fheuints, addrs, sign, first_bits=None, fn_at=None):   # fn_at: the NAME of the _derive_at entry point (looked up only when used: a build named by FHERAM_LIB may predate it)
+    """Ram.derive_addresses / RamBank.derive_addresses: addrs[i] <- Address::set_from_fheuint(fheuints[i]) as ONE launch; first_bits: the
+    address bits start at bit first_bits[i] of integer i (fheram_address_derive_at: one launch per distinct first bit)"""
     fheuints = list(fheuints)
     k = len(fheuints)
+    if first_bits is not None:
+        first_bits = [int(f) for f in first_bits]
+        if len(first_bits) != k:
+            raise FheRamError(1, f"derive_addresses: {k} integers need {k} first bits")
     if not 1 <= k <= DERIVE_MAX:
         raise FheRamError(1, f"derive_addresses takes 1 to DERIVE_MAX = {DERIVE_MAX} integers, got {k}")
     if not all(isinstance(f, FheUintPrepared) for f in fheuints):
@@ -562,7 +579,10 @@ def _derive_addresses(owner, fn, fheuints, addrs, sign):
             raise FheRamError(1, f"derive_addresses: {k} integers need {k} Address objects")
     handles = [a._bank(owner) if isinstance(owner, RamBank) else a._device(owner) for a in addrs]   # (an address made from host digits: created here)
     fa, aa = (C.c_void_p * k)(*[f._h for f in fheuints]), (C.c_void_p * k)(*handles)
-    owner._chk(fn(owner._h, fa, k, int(bool(sign)), aa))
+    if first_bits is None:
+        owner._chk(fn(owner._h, fa, k, int(bool(sign)), aa))
+    else:
+        owner._chk(getattr(library(), fn_at)(owner._h, fa, (C.c_int * max(k, 1))(*first_bits), k, int(bool(sign)), aa))
     for a, f in zip(addrs, fheuints):
         a._digits = None                                               # the host copy, and the handles on other devices, held the old digits
         a._handles = {id(owner): a._handles[id(owner)]}
@@ -602,13 +622,116 @@ class Src:
         return cls(SRC_SELECT_RESULT, k)
 
 
+class Lane:
+    """One byte ciphertext of a lane-mapped candidate of RamBank.select_lanes (fheram_select_lane): GLWE `lane` of the word a Src would
+    name.  Lane.zero(), Lane.host(i, lane), Lane.member(m, lane), Lane.list_entry(k, lane), Lane.select(k, lane)."""
+
+    def __init__(self, kind: int, index: int = 0, lane: int = 0, reserved: int = 0):
+        self.kind, self.index, self.lane, self.reserved = int(kind), int(index), int(lane), int(reserved)
+
+    def __eq__(self, other):
+        return isinstance(other, Lane) and (self.kind, self.index, self.lane, self.reserved) == (other.kind, other.index, other.lane, other.reserved)
+
+    def __hash__(self):
+        return hash((self.kind, self.index, self.lane, self.reserved))
+
+    def __repr__(self):
+        return f"Lane({self.kind}, {self.index}, {self.lane})"
+
+    @classmethod
+    def zero(cls):
+        """an all-zero ciphertext"""
+        return cls(SRC_ZERO)
+
+    @classmethod
+    def host(cls, i: int, lane: int):
+        """GLWE `lane` of slot i of the call's host_words"""
+        return cls(SRC_HOST, i, lane)
+
+    @classmethod
+    def member(cls, m: int, lane: int):
+        """GLWE `lane` of member m's last read / read_prepare_write result"""
+        return cls(SRC_MEMBER_RESULT, m, lane)
+
+    @classmethod
+    def list_entry(cls, k: int, lane: int):
+        """GLWE `lane` of entry k of the last read list"""
+        return cls(SRC_LIST_RESULT, k, lane)
+
+    @classmethod
+    def select(cls, k: int, lane: int):
+        """GLWE `lane` of output k of the previous select"""
+        return cls(SRC_SELECT_RESULT, k, lane)
+
+    @classmethod
+    def of(cls, src: Src, lane: int):
+        """GLWE `lane` of the word `src` names"""
+        return cls.zero() if src.kind == SRC_ZERO else cls(src.kind, src.index, lane)
+
+
+STORE_NONE, STORE_SB, STORE_SH, STORE_SW = 0, 1, 2, 3   # the `op` of store_merge_lanes (store.rs:87-142)
+LOAD_LW, LOAD_LBU, LOAD_LHU = 0, 1, 2                   # the `op` of load_extract_lanes
+
+
+def store_merge_lanes(x: Src, y: Src, word_size: int = 4):
+    """The candidates of the reference's select_store (store.rs:87-142) in its order, as lanes of two words: x = the register's word (the
+    bytes to store, from byte 0 up), y = the word the memory holds.  Candidate op + 4 * offset, op = NONE / SB / SH / SW, offset = the
+    low address bits, is y with
+        NONE  nothing replaced;
+        SB    byte `offset` <- x0;
+        SH    bytes offset, offset + 1 <- x0, x1    (offset 0 or 2);
+        SW    every byte <- x                       (offset 0).
+    The invalid combinations (a misaligned SH or SW) are all-ZERO candidates, and the two trailing ones (offset 3 with SH, SW) are left
+    out: 14 candidates [14][word_size], for a selector of 4 bits.  An index of 14 or 15 then selects zero too.  No GPU work."""
+    ws = int(word_size)
+    if ws != 4:
+        raise FheRamError(1, "store_merge_lanes restates the reference's 32-bit store merge: word_size = 4")
+    Y = [Lane.of(y, w) for w in range(ws)]
+    X = [Lane.of(x, w) for w in range(ws)]
+    zero = [Lane.zero()] * ws
+    out = []
+    for offset in range(4):
+        sb = list(Y)
+        sb[offset] = X[0]
+        if offset in (0, 2):
+            sh = list(Y)
+            sh[offset], sh[offset + 1] = X[0], X[1]
+        else:
+            sh = zero
+        out += [list(Y), sb, sh, list(X) if offset == 0 else zero]
+    return out[:14]
+
+
+def load_extract_lanes(y: Src, word_size: int = 4):
+    """The zero-extending loads as lanes of the word y the memory holds: candidate op + 4 * offset, op = LW / LBU / LHU (3: unused), is
+        LW    [y0, y1, y2, y3]               (offset 0)
+        LBU   [y_offset, 0, 0, 0]            (offset 0..3)
+        LHU   [y_offset, y_offset+1, 0, 0]   (offset 0 or 2)
+    and every other combination (a misaligned LW or LHU, op = 3) all ZERO; the trailing all-zero ones are left out: 14 candidates
+    [14][word_size], for a selector of 4 bits.  It has NO reference counterpart (the reference's loads go through its un-vendored BDD
+    circuits); sign-extending loads need bit operations inside a byte and are out of scope.  No GPU work."""
+    ws = int(word_size)
+    if ws != 4:
+        raise FheRamError(1, "load_extract_lanes is the 32-bit load: word_size = 4")
+    Y = [Lane.of(y, w) for w in range(ws)]
+    Z = Lane.zero()
+    zero = [Z] * ws
+    out = []
+    for offset in range(4):
+        out += [list(Y) if offset == 0 else zero, [Y[offset], Z, Z, Z], [Y[offset], Y[offset + 1], Z, Z] if offset in (0, 2) else zero, zero]
+    return out[:14]
+
+
 class Selector:
     """The encrypted index of a select over up to 2^bits candidates (fheram_selector): the Address of a one-row RAM of max_addr = 2^bits on
     a bank's device.  RamBank.selector(bits) makes one without digits, Selector.from_digits one from host std-form GGSW digits;
-    RamBank.derive_selectors fills either from bits of an encrypted integer."""
+    RamBank.derive_selectors fills either from bits of an encrypted integer.  A FIELD selector (RamBank.selector_fields,
+    Selector.from_digits_fields; `widths` is set) has one digit per field, each filled from an integer and a bit position of its own by
+    RamBank.derive_selector_fields."""
 
     def __init__(self, bank: "RamBank", handle, bits: int):
         self.bank, self._h, self.bits = bank, handle, int(bits)
+        self.widths = None   # a field selector: the widths of its digits
         self._derived_from = None
 
     @classmethod
@@ -618,6 +741,18 @@ class Selector:
         out = C.c_void_p()
         bank._chk(library().fheram_bank_selector_create(bank._h, arr, len(digits), int(bits), C.byref(out)))
         return cls(bank, out.value, bits)
+
+    @classmethod
+    def from_digits_fields(cls, bank: "RamBank", widths, ggsw_digits):
+        """a field selector (fheram_bank_selector_create_fields) from host std-form GGSW digits, one per field"""
+        widths = [int(x) for x in widths]
+        digits = [_i64(g).ravel() for g in ggsw_digits]
+        arr = (I64P * max(len(digits), 1))(*[_p(d) for d in digits])
+        out = C.c_void_p()
+        bank._chk(library().fheram_bank_selector_create_fields(bank._h, arr, len(digits), (C.c_int * max(len(widths), 1))(*widths), len(widths), C.byref(out)))
+        s = cls(bank, out.value, sum(widths))
+        s.widths = widths
+        return s
 
     def n_digits(self) -> int:
         return int(library().fheram_selector_n_digits(self._h))
@@ -923,12 +1058,14 @@ class Ram:
         self._chk(library().fheram_read_prepare_write(self._h, address._device(self), _p(out) if download else None))
         return out if download else None
 
-    def derive_addresses(self, fheuints, addrs=None, sign: bool = False):
+    def derive_addresses(self, fheuints, addrs=None, sign: bool = False, first_bits=None):
         """addrs[i] <- Address::set_from_fheuint(fheuints[i]) (conversion.rs:68-82) for 1 to DERIVE_MAX encrypted integers as ONE launch
         on this Ram's stream (fheram_address_derive): no allocation, no host wait; later operations that use the addresses are ordered
         behind it.  addrs: existing Address objects to overwrite in place (from Address.alloc, host digits, encrypt_sk or an earlier
-        derivation; no address twice), or None to allocate them.  sign=False: the convention Ram.read accepts.  Returns the addresses."""
-        return _derive_addresses(self, library().fheram_address_derive, fheuints, addrs, sign)
+        derivation; no address twice), or None to allocate them.  sign=False: the convention Ram.read accepts.  Returns the addresses.
+        first_bits: the address is read from bit first_bits[i] of integer i on (fheram_address_derive_at; a byte address keeps its lane
+        offset in bits [0, 2) and its word address above them), one launch per distinct first bit."""
+        return _derive_addresses(self, library().fheram_address_derive, fheuints, addrs, sign, first_bits, "fheram_address_derive_at")
 
     def write(self, w, address: Address, keys: EvaluationKeysPrepared):  # ram.rs:226
         self._use_keys(keys)
@@ -1454,10 +1591,10 @@ class RamBank:
         """self-test: the nth device allocation the write lists' buffers ask for from now on fails once (0: none)"""
         self._chk(library().fheram_bank_selftest_fail_list_alloc(self._h, int(nth)))
 
-    def derive_addresses(self, fheuints, addrs=None, sign: bool = False):
+    def derive_addresses(self, fheuints, addrs=None, sign: bool = False, first_bits=None):
         """as Ram.derive_addresses, with integers and addresses bound to this bank (FheUintPrepared.from_host(bank, ...),
         Address.alloc(bank)): a derived address is an ordinary bank address and may serve several members"""
-        return _derive_addresses(self, library().fheram_bank_address_derive, fheuints, addrs, sign)
+        return _derive_addresses(self, library().fheram_bank_address_derive, fheuints, addrs, sign, first_bits, "fheram_bank_address_derive_at")
 
     # -- oblivious select (include/fheram.h: pick a word by an encrypted index)
     def selector(self, bits: int) -> Selector:
@@ -1480,6 +1617,58 @@ class RamBank:
         for s, f in zip(sels, fheuints):
             s._derived_from = f   # the integer stays alive until the launch that reads it has run
         return sels
+
+    def selector_fields(self, widths) -> Selector:
+        """a field selector with its buffers and no digits yet (fheram_bank_selector_alloc_fields): digit d has widths[d] bits at bit offset
+        sum(widths[:d]); derive_selector_fields fills it"""
+        widths = [int(x) for x in widths]
+        out = C.c_void_p()
+        self._chk(library().fheram_bank_selector_alloc_fields(self._h, (C.c_int * max(len(widths), 1))(*widths), len(widths), C.byref(out)))
+        s = Selector(self, out.value, sum(widths))
+        s.widths = widths
+        return s
+
+    def derive_selector_fields(self, sel, fheuints, first_bits):
+        """digit d of the field selector `sel` <- bits [first_bits[d], first_bits[d] + widths[d]) of fheuints[d]
+        (fheram_bank_selector_derive_fields): one launch per field, no allocation, no host wait, in place"""
+        fheuints, first_bits = list(fheuints), [int(f) for f in first_bits]
+        if not isinstance(sel, Selector) or sel.widths is None:
+            raise FheRamError(1, "derive_selector_fields takes a field selector (RamBank.selector_fields, Selector.from_digits_fields)")
+        k = len(sel.widths)
+        if len(fheuints) != k or len(first_bits) != k or not all(isinstance(f, FheUintPrepared) for f in fheuints):
+            raise FheRamError(1, f"derive_selector_fields: a selector of {k} fields takes {k} FheUintPrepared and {k} first bits")
+        self._chk(library().fheram_bank_selector_derive_fields(self._h, sel._h, (C.c_void_p * k)(*[f._h for f in fheuints]), (C.c_int * k)(*first_bits)))
+        sel._derived_from = fheuints   # the integers stay alive until the launches that read them have run
+        return sel
+
+    def select_lanes(self, sels, candidates, host_words=None, download: bool = True, keys: Optional[EvaluationKeysPrepared] = None):
+        """n selects as ONE operation with lane-mapped candidates (fheram_bank_select_lanes): candidates[k][j] is a list of word_size Lane,
+        the byte ciphertexts candidate j of select k is assembled from (store_merge_lanes / load_extract_lanes build such lists).
+        Everything else is select's: host_words, download, keys, and it is the last select for select_result / write_list_selected."""
+        sels, candidates = list(sels), [[list(c) for c in cs] for cs in candidates]
+        n = len(sels)
+        if n < 1 or len(candidates) != n or not all(isinstance(s, Selector) for s in sels):
+            raise FheRamError(1, "select_lanes takes at least one Selector and one candidate list per selector")
+        p = self.params
+        ws = p.word_size()
+        words = [c for cs in candidates for c in cs]
+        if not words or not all(len(c) == ws and all(isinstance(l, Lane) for l in c) for c in words):
+            raise FheRamError(1, f"every candidate must be a list of word_size = {ws} Lane")
+        flat = [l for c in words for l in c]
+        per = ws * p.glwe_len()
+        hw = None
+        if host_words is not None:
+            hw = _i64(host_words)
+            slots = [l.index for l in flat if l.kind == SRC_HOST]
+            if slots and (min(slots) < 0 or (max(slots) + 1) * per > hw.size):
+                raise FheRamError(1, f"a host lane names a slot outside host_words ({hw.size // per} slots of {ws} GLWEs)")
+        lanes = (_CSelectLane * len(flat))(*[_CSelectLane(l.kind, l.index, l.lane, l.reserved) for l in flat])
+        if keys is not None:
+            self._use_keys(keys)
+        out = np.zeros((n, ws, p.glwe_len()), dtype=np.int64) if download else None
+        self._chk(library().fheram_bank_select_lanes(self._h, (C.c_void_p * n)(*[s._h for s in sels]), (C.c_int * n)(*[len(c) for c in candidates]), n,
+                                                     lanes, _p(hw) if hw is not None else None, _p(out) if download else None))
+        return out
 
     def select(self, sels, candidates, host_words=None, download: bool = True, keys: Optional[EvaluationKeysPrepared] = None):
         """n selects as ONE operation (fheram_bank_select): candidates[k] is the list of Src of select k, of which sels[k] picks one.

@@ -27,7 +27,7 @@
 // The write's inverse digits are never started early in a bank of more than one member (pre_inv shares d_prep_inv and d_tail_sync between
 // members); a bank of ONE member is a plain context in every respect.  Bank operations are never captured into a hipGraph: under graph = 1
 // they are enqueued directly, in the forms that mode selects.
-// The bank's oblivious select (fheram_bank_select and the write that takes its words from it) is select.hpp: it runs on buffers of its own
+// The bank's oblivious select (fheram_bank_select, fheram_bank_select_lanes and the write that takes its words from them) is select.hpp: it runs on buffers of its own
 // (`sel`) and reads, of what is here, only where a member's result and the last read list's results sit.
 #pragma once
 #include "path.hpp"
@@ -46,6 +46,7 @@ struct fheram_bank {
     unsigned kept_map = 0;
     bool wl_holds[FHERAM_BANK_MAX] = {};   // ... and member m is still as that operation left it (cleared by whatever touches the member)
     SelectBufs sel;               // fheram_bank_select: buffers of its own (select.hpp)
+    SelectLaneTable lanes;        // fheram_bank_select_lanes: the pointer table of its pack (allocated on the first lanes call)
     int sel_n = 0, sel_fail_alloc = 0;   // outputs of the last select (in sel.res; 0: none has run); the self-test's failing allocation, as wl_fail_alloc
     bool has_res[FHERAM_BANK_MAX] = {};  // member m has the result of a read / read_prepare_write in its slot (a select may take it as a candidate)
     int wl_fail_alloc = 0;        // fheram_bank_selftest_fail_list_alloc: the wl_fail_alloc-th next device allocation of wl fails (0: none)
@@ -299,6 +300,7 @@ void fheram_bank_destroy(fheram_bank* b) {
     dense_free(b->list);
     dense_free(b->wl);
     select_free(b->sel);
+    lane_table_free(b->lanes);
     fheram_ctx_destroy(b->c);
     delete b;
 }
@@ -366,6 +368,10 @@ int fheram_bank_address_alloc(fheram_bank* b, fheram_addr** out) {
 int fheram_bank_address_derive(fheram_bank* b, const fheram_fheuint* const* fus, int n, int sign, fheram_addr* const* addrs) {
     if (!b) return FHERAM_ERR_INVALID_ARG;
     return fheram_address_derive(b->c, fus, n, sign, addrs);
+}
+int fheram_bank_address_derive_at(fheram_bank* b, const fheram_fheuint* const* fus, const int* first_bit, int n, int sign, fheram_addr* const* addrs) {
+    if (!b) return FHERAM_ERR_INVALID_ARG;
+    return fheram_address_derive_at(b->c, fus, first_bit, n, sign, addrs);
 }
 
 int fheram_bank_read(fheram_bank* b, int first, int n, const fheram_addr* const* addrs, int64_t* out) {

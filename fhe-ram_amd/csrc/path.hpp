@@ -340,6 +340,20 @@ void select_free(SelectBufs& S) {
     if (S.ev_host) hipEventDestroy(S.ev_host);
     S = SelectBufs{};
 }
+// fheram_bank_select_lanes' pointer table (select_lanes.hpp): [64 output ciphertexts][32 candidates] pointers, 16 KiB, on the device and pinned.
+// Allocated whole on the first lanes call and freed with the bank; NOT among the buffers select_reserve counts and grows.
+struct SelectLaneTable {
+    const int32_t** d_tab = nullptr;   // what k_select_pack_lanes reads
+    const int32_t** h_tab = nullptr;   // pinned: what the host writes, copied by one hipMemcpyAsync per call
+    hipEvent_t ev = nullptr;           // the last copy out of h_tab
+    bool busy = false;
+};
+void lane_table_free(SelectLaneTable& L) {
+    if (L.d_tab) hipFree(L.d_tab);
+    if (L.h_tab) hipHostFree(L.h_tab);
+    if (L.ev) hipEventDestroy(L.ev);
+    L = SelectLaneTable{};
+}
 
 // The one result export: every run (source, int32 count) is widened by the device into the pinned buffer h (device address d_h), back to
 // back, with the monitor's maximum as it stood then behind the last (the export kernel copies it there); out != nullptr: copied out.

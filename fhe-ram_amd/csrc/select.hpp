@@ -9,7 +9,10 @@
 //   selector   the Address of such a RAM: the digits get_base_2d(2^bits) gives over the bank's DECOMP_N (one coordinate), each the GGSW of
 //              X^-v (Address::encrypt_sk's sign) in the layout of address digits; created from host digits or derived from bits
 //              [first_bit, first_bit + bits) of an encrypted integer by k_cmux_chain with that plan (one launch per distinct (first_bit, bits))
-//   pack       k_select_pack (select_pack.hip): one launch per call over n * ws output ciphertexts
+//              A FIELD selector (the _fields entry points) takes its plan from the caller's widths instead: digit d from an integer and a bit
+//              position of its own, one k_cmux_chain launch per field (the store merge indexes by op + 4 * offset: DESIGN.md 15)
+//   pack       k_select_pack (select_pack.hip): one launch per call over n * ws output ciphertexts; fheram_bank_select_lanes: k_select_pack_lanes
+//              (select_lanes.hip), every candidate assembled lane by lane through a pointer table in device memory
 //   chain      the prepared selector digits (k_prepare), the products and the trace: what read_top enqueues for the second coordinate
 //              of a RAM of n * ws ciphertexts with a per-ciphertext operand table — the same launchers, so the same forms under every
 //              configuration (chain_form), `safe`, tail = 0 and fuse = 0 included
@@ -19,6 +22,7 @@
 #pragma once
 #include "bank.hpp"
 #include "select_pack.hpp"
+#include "select_lanes.hpp"
 
 struct fheram_selector {
     fheram_bank* bank;   // owner (identity check only after creation)
@@ -26,12 +30,15 @@ struct fheram_selector {
     int32_t* d_ggsw;     // [n_digits] std-form GGSW, int32 (the layout of address digits)
     unsigned char rsh[FHERAM_SELECT_BITS_MAX], width[FHERAM_SELECT_BITS_MAX], lsh[FHERAM_SELECT_BITS_MAX];   // the digit plan (conversion.rs:45-62)
     bool empty;          // fheram_bank_selector_alloc: no digits yet
+    bool fields;         // made by a _fields call: the plan is the caller's widths, digit d derived from an integer and a bit offset of its own
 };
 
 namespace {
 
 static_assert(FHERAM_SELECT_MAX == SELECT_K_MAX && (1 << FHERAM_SELECT_BITS_MAX) == SELECT_CAND_MAX, "the argument struct of k_select_pack holds FHERAM_SELECT_MAX selects of 2^FHERAM_SELECT_BITS_MAX candidates");
 static_assert(FHERAM_SELECT_MAX <= DERIVE_K_MAX && FHERAM_SELECT_BITS_MAX <= DERIVE_DIGITS_MAX, "a selector derivation is one k_cmux_chain launch");
+static_assert(SELECT_LANES_SLICES == EW_SLICES && SELECT_LANES_CT_MAX == 64, "k_select_pack_lanes covers a ciphertext as the elementwise kernels do; a call has at most 64 output ciphertexts");
+static_assert(FHERAM_SELECT_FIELDS_MAX == FHERAM_SELECT_BITS_MAX, "a field has at least one bit");
 
 // the selector of `bits` bits with its plan and its device buffer, no digits yet
 int selector_new(fheram_bank* b, int bits, fheram_selector** out) {
@@ -42,13 +49,40 @@ int selector_new(fheram_bank* b, int bits, fheram_selector** out) {
     if (plan.size() != 1)
         return fail(c, FHERAM_ERR_UNSUPPORTED, "the bank's DECOMP_N gives a selector of " + std::to_string(bits) + " bits " + std::to_string(plan.size()) + " coordinates; a select is a read of a one-row RAM of one coordinate");
     HIPCHK(c, hipSetDevice(c->device));
-    fheram_selector* s = new fheram_selector{b, c->device, bits, (int)plan[0].size(), nullptr, {}, {}, {}, true};
+    fheram_selector* s = new fheram_selector{b, c->device, bits, (int)plan[0].size(), nullptr, {}, {}, {}, true, false};
     unsigned at = 0;
     for (int d = 0; d < s->n_digits; d++) {   // one coordinate: bit_lsh and bit_rsh advance together
         s->rsh[d] = s->lsh[d] = (unsigned char)at; s->width[d] = (unsigned char)plan[0][d];
         at += (unsigned)plan[0][d];
     }
     const hipError_t e = hipMalloc(&s->d_ggsw, (size_t)s->n_digits * fheram_ctx::GGSW * sizeof(int32_t));
+    if (e != hipSuccess) { delete s; (void)hipGetLastError(); return fail(c, FHERAM_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+    *out = s;
+    return FHERAM_OK;
+}
+
+// The selector whose digit d has widths[d] bits at bit offset sum(widths[0..d)): the Address of a one-row RAM of max_addr = 2^bits whose DECOMP_N
+// starts with `widths` (get_base_2d then gives [widths]), whatever the bank's own DECOMP_N is.  The plan comes from the caller, not from base_2d.
+int selector_new_fields(fheram_bank* b, const int* widths, int n_fields, fheram_selector** out) {
+    fheram_ctx* c = b->c;
+    if (!widths) return fail(c, FHERAM_ERR_INVALID_ARG, "null widths");
+    if (n_fields < 1 || n_fields > FHERAM_SELECT_FIELDS_MAX)
+        return fail(c, FHERAM_ERR_INVALID_ARG, "n_fields = " + std::to_string(n_fields) + " is outside [1, FHERAM_SELECT_FIELDS_MAX = " + std::to_string(FHERAM_SELECT_FIELDS_MAX) + "]");
+    int bits = 0;
+    for (int d = 0; d < n_fields; d++) {
+        if (widths[d] < 1) return fail(c, FHERAM_ERR_INVALID_ARG, "field " + std::to_string(d) + " has the width " + std::to_string(widths[d]) + ", below 1");
+        bits += widths[d];
+        if (bits > FHERAM_SELECT_BITS_MAX)
+            return fail(c, FHERAM_ERR_INVALID_ARG, "the widths sum to more than FHERAM_SELECT_BITS_MAX = " + std::to_string(FHERAM_SELECT_BITS_MAX) + " bits");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    fheram_selector* s = new fheram_selector{b, c->device, bits, n_fields, nullptr, {}, {}, {}, true, true};
+    unsigned at = 0;
+    for (int d = 0; d < n_fields; d++) {
+        s->rsh[d] = s->lsh[d] = (unsigned char)at; s->width[d] = (unsigned char)widths[d];
+        at += (unsigned)widths[d];
+    }
+    const hipError_t e = hipMalloc(&s->d_ggsw, (size_t)n_fields * fheram_ctx::GGSW * sizeof(int32_t));
     if (e != hipSuccess) { delete s; (void)hipGetLastError(); return fail(c, FHERAM_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e)); }
     *out = s;
     return FHERAM_OK;
@@ -102,6 +136,117 @@ const int32_t* select_source(const fheram_bank* b, const fheram_select_src& s) {
     }
 }
 
+// GLWE `lane` of that word: what one entry of k_select_pack_lanes' table points to
+const int32_t* select_source_lane(const fheram_bank* b, const fheram_select_lane& l) {
+    const int32_t* p = select_source(b, fheram_select_src{l.kind, l.index});
+    return p ? p + (size_t)l.lane * fheram_ctx::GLWE : nullptr;
+}
+
+// ---- what fheram_bank_select and fheram_bank_select_lanes share: the checks (every one before anything is enqueued) and everything behind the pack
+int select_check_sels(fheram_bank* b, const fheram_selector* const* sels, const int* n_cand, int n, int* total) {
+    fheram_ctx* c = b->c;
+    if (n < 1 || n > FHERAM_SELECT_MAX)
+        return fail(c, FHERAM_ERR_INVALID_ARG, "n = " + std::to_string(n) + " is outside [1, FHERAM_SELECT_MAX = " + std::to_string(FHERAM_SELECT_MAX) + "]");
+    const int Y = n * b->mws;
+    if (Y > 64)
+        return fail(c, FHERAM_ERR_INVALID_ARG, "n * word_size = " + std::to_string(Y) + " exceeds 64, the ciphertext limit of the single-launch chains (k_chain_mid)");
+    *total = 0;
+    for (int k = 0; k < n; k++) {
+        if (!sels[k] || sels[k]->bank != b) return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " is null or belongs to another bank");
+        if (sels[k]->empty) return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " is empty: fheram_bank_selector_alloc without fheram_bank_selector_derive");
+        if (sels[k]->bits != sels[0]->bits)
+            return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " has " + std::to_string(sels[k]->bits) + " bits, selector 0 " + std::to_string(sels[0]->bits) + ": the selects of one call share one digit count (the operand table's)");
+        if (sels[k]->n_digits != sels[0]->n_digits)   // (field selectors: the same bits in another number of digits)
+            return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " has " + std::to_string(sels[k]->n_digits) + " digits, selector 0 " + std::to_string(sels[0]->n_digits) + ": the operand table of one call has one stride");
+        if (n_cand[k] < 1 || n_cand[k] > (1 << sels[k]->bits))
+            return fail(c, FHERAM_ERR_INVALID_ARG, "select " + std::to_string(k) + " has " + std::to_string(n_cand[k]) + " candidates, outside [1, 2^bits = " + std::to_string(1 << sels[k]->bits) + "]");
+        *total += n_cand[k];
+    }
+    return FHERAM_OK;
+}
+struct SelectNeeds { bool list = false, sel = false; };
+// one (kind, index) of a source or a lane
+int select_check_source(fheram_bank* b, int kind, int index, const std::string& who, const int64_t* host_words, SelectNeeds& need) {
+    fheram_ctx* c = b->c;
+    switch (kind) {
+    case FHERAM_SRC_ZERO: break;
+    case FHERAM_SRC_HOST:
+        if (!host_words) return fail(c, FHERAM_ERR_INVALID_ARG, who + " is a host word and host_words is null");
+        if (index < 0 || index >= FHERAM_SELECT_MAX * (1 << FHERAM_SELECT_BITS_MAX)) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names host slot " + std::to_string(index) + ", outside [0, " + std::to_string(FHERAM_SELECT_MAX * (1 << FHERAM_SELECT_BITS_MAX)) + ")");
+        break;
+    case FHERAM_SRC_MEMBER_RESULT:
+        if (index < 0 || index >= b->M) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names member " + std::to_string(index) + ", outside the bank's " + std::to_string(b->M) + " members");
+        break;
+    case FHERAM_SRC_LIST_RESULT:
+        if (index < 0 || (b->list_n && index >= b->list_n)) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names entry " + std::to_string(index) + ", outside the last read list's " + std::to_string(b->list_n) + " entries");
+        need.list = true;
+        break;
+    case FHERAM_SRC_SELECT_RESULT:
+        if (index < 0 || (b->sel_n && index >= b->sel_n)) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names output " + std::to_string(index) + ", outside the last select's " + std::to_string(b->sel_n) + " outputs");
+        need.sel = true;
+        break;
+    default: return fail(c, FHERAM_ERR_INVALID_ARG, who + " has the unknown kind " + std::to_string(kind));
+    }
+    return FHERAM_OK;
+}
+int select_check_state(fheram_bank* b, const SelectNeeds& need) {
+    fheram_ctx* c = b->c;
+    if (!c->keys_loaded) return fail(c, FHERAM_ERR_KEYS, "evaluation keys not loaded");
+    if (need.list && !b->list_n) return fail(c, FHERAM_ERR_STATE, "a source names the last read list and no read list has run on this bank");
+    if (need.sel && !b->sel_n) return fail(c, FHERAM_ERR_STATE, "a source names the last select and no select has run on this bank");
+    return FHERAM_OK;
+}
+// Behind the pack (S.packed holds n * ws packed rows): the selectors' digits prepared, the products, the trace, the export
+int select_chain(fheram_bank* b, const fheram_selector* const* sels, int n, int64_t* out) {
+    fheram_ctx* c = b->c;
+    SelectBufs& S = b->sel;
+    const int ws = b->mws, Y = n * ws, d = sels[0]->n_digits;
+    const long G = (long)fheram_ctx::GLWE;
+    // the selectors' digits, prepared: select k's at k * stride (CoordinatePrepared::prepare, coordinate_prepared.rs:104-116)
+    const long stride = (long)d * (long)fheram_ctx::GGSW;
+    for (int k = 0; k < n; k++) launch_prepare(c, sels[k]->d_ggsw, S.prep + k * stride, d * (int)(fheram_ctx::GGSW / N));
+    // Ram::read of the one-row RAM {packed} (ram.rs:451,457): the products with the digits in order, then trace(0, log N) — as read_top runs
+    // the second coordinate's products and the final trace of n * ws ciphertexts
+    const GlweRef packed = ref(S.packed, G, 0), ep = ref(S.ep, G, 0), tmp = ref(S.tmp, G, 0), res = ref(S.res, G, 0);
+    const OpndTable table = n == 1 ? OpndTable{} : OpndTable{ws, stride, MEMBER_MAP_IDENTITY, false};
+    auto slice = [&](GlweRef r, int k) { r.p += (long)k * ws * r.sy; return r; };
+    auto products = [&] { for (int k = 0; k < n; k++) ep_chain(c, slice(packed, k), slice(ep, k), slice(tmp, k), S.prep + k * stride, d, 1, ws); };
+    const bool fuse_ep = c->cfg.tail_ep && d >= 2 && d <= TAIL_EP_MAX && chain_form(c, ChainQuery{false, LOGN, 1, Y}).form == ChainForm::Tail;
+    GlweRef tb[2];
+    if (fuse_ep && chain_bufs(LOGN, ep, res, tmp, tb))
+        launch_trace_tail(c, packed, tb, 0, LOGN, 1, Y, S.prep, d, ep, false, table);
+    else {
+        products();
+        trace_steps(c, ep, res, tmp, 0, LOGN, 1, Y);
+    }
+    HIPCHK(c, hipGetLastError());
+    b->sel_n = n;
+    if (!out) return FHERAM_OK;
+    const ResRun run{S.res, (size_t)Y * fheram_ctx::GLWE};
+    return result_export(c, &run, 1, S.h_res, S.d_h_res, out);
+}
+// the pointer table of the lanes pack: allocated whole on the first lanes call.  The self-test's failing allocation (fheram_bank_selftest_fail_select_alloc)
+// reaches the table's device allocation as the one AFTER those select_reserve makes in the same call.
+int lane_table_reserve(fheram_bank* b) {
+    fheram_ctx* c = b->c;
+    SelectLaneTable& L = b->lanes;
+    if (L.d_tab) return FHERAM_OK;
+    SelectLaneTable nw;
+    const size_t bytes = (size_t)SELECT_LANES_CT_MAX * SELECT_CAND_MAX * sizeof(const int32_t*);
+    hipError_t e;
+    if (b->sel_fail_alloc > 0 && --b->sel_fail_alloc == 0) e = hipErrorOutOfMemory;
+    else e = hipMalloc((void**)&nw.d_tab, bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&nw.h_tab, bytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&nw.ev, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        lane_table_free(nw);
+        (void)hipGetLastError();
+        return fail(c, FHERAM_ERR_DEVICE, std::string("pointer table of a lanes select: ") + hipGetErrorString(e));
+    }
+    L = nw;
+    return FHERAM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -129,6 +274,61 @@ int fheram_bank_selector_create(fheram_bank* b, const int64_t* const* ggsw, int 
     *out = s;
     return FHERAM_OK;
 }
+int fheram_bank_selector_alloc_fields(fheram_bank* b, const int* widths, int n_fields, fheram_selector** out) {
+    if (!b) return FHERAM_ERR_INVALID_ARG;
+    if (!out) return fail(b->c, FHERAM_ERR_INVALID_ARG, "null output");
+    *out = nullptr;
+    return selector_new_fields(b, widths, n_fields, out);
+}
+int fheram_bank_selector_create_fields(fheram_bank* b, const int64_t* const* ggsw, int n_ggsw, const int* widths, int n_fields, fheram_selector** out) {
+    if (!b) return FHERAM_ERR_INVALID_ARG;
+    fheram_ctx* c = b->c;
+    if (!out) return fail(c, FHERAM_ERR_INVALID_ARG, "null output");
+    *out = nullptr;
+    if (!ggsw) return fail(c, FHERAM_ERR_INVALID_ARG, "null ggsw");
+    fheram_selector* s = nullptr;
+    int rc = selector_new_fields(b, widths, n_fields, &s);
+    if (rc != FHERAM_OK) return rc;
+    if (n_ggsw != n_fields) rc = fail(c, FHERAM_ERR_INVALID_ARG, "a selector of " + std::to_string(n_fields) + " fields has as many digits, not " + std::to_string(n_ggsw));
+    for (int i = 0; i < n_ggsw && rc == FHERAM_OK; i++)
+        rc = ggsw[i] ? upload_i64(c, s->d_ggsw + (size_t)i * fheram_ctx::GGSW, ggsw[i], fheram_ctx::GGSW) : fail(c, FHERAM_ERR_INVALID_ARG, "null ggsw digit");
+    if (rc != FHERAM_OK) { fheram_selector_destroy(s); return rc; }
+    s->empty = false;
+    *out = s;
+    return FHERAM_OK;
+}
+// digit d of sel <- bits [first_bit[d], first_bit[d] + widths[d]) of fus[d], in place: the unchanged k_cmux_chain, ONE LAUNCH PER FIELD of grid
+// (6, 1, 1) with `out` advanced to the digit and the plan's entry 0 set to the field's (the argument struct holds one plan for all its integers, and
+// fields never share an lsh).  No allocation, no host wait; ordered by the bank's main stream as fheram_bank_selector_derive is.
+int fheram_bank_selector_derive_fields(fheram_bank* b, fheram_selector* sel, const fheram_fheuint* const* fus, const int* first_bit) {
+    if (!b) return FHERAM_ERR_INVALID_ARG;
+    fheram_ctx* c = b->c;
+    if (!sel || !fus || !first_bit) return fail(c, FHERAM_ERR_INVALID_ARG, "null selector, integer list or bit list");
+    if (sel->bank != b) return fail(c, FHERAM_ERR_INVALID_ARG, "the selector belongs to another bank");
+    if (!sel->fields) return fail(c, FHERAM_ERR_INVALID_ARG, "the selector was not made by fheram_bank_selector_alloc_fields / _create_fields");
+    for (int d = 0; d < sel->n_digits; d++) {   // every check before anything is enqueued: a refused call changes no digit
+        if (!fus[d] || fus[d]->ctx != c) return fail(c, FHERAM_ERR_INVALID_ARG, "integer " + std::to_string(d) + " is null or belongs to another bank");
+        if (first_bit[d] < 0 || first_bit[d] + sel->width[d] > fus[d]->n_bits)
+            return fail(c, FHERAM_ERR_INVALID_ARG, "bits [" + std::to_string(first_bit[d]) + ", " + std::to_string(first_bit[d]) + " + " + std::to_string(sel->width[d]) + ") of integer " + std::to_string(d) + " are beyond its " + std::to_string(fus[d]->n_bits) + " bits");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    c->cur = c->stream;
+    main_enqueued(c);
+    const int rows = fheram_ctx::DNUM_CT * 2;
+    for (int d = 0; d < sel->n_digits; d++) {
+        CmuxChainArgs ca{};
+        ca.tw = c->d_tw;
+        ca.sign = 0;   // X^-v: what Ram::read accepts (address.rs:102-108)
+        ca.fu[0] = fus[d]->d_prep;
+        ca.out[0] = sel->d_ggsw + (size_t)d * fheram_ctx::GGSW;
+        ca.first[0] = (unsigned char)first_bit[d]; ca.bits[0] = sel->width[d]; ca.lsh[0] = sel->lsh[d];
+        ProfScope ps(c, "derive", (uint64_t)rows);
+        cmux_chain_launch(dim3(rows, 1, 1), c->cur, ca);
+    }
+    HIPCHK(c, hipGetLastError());
+    sel->empty = false;
+    return FHERAM_OK;
+}
 // sels[i] <- the selector of bits [first_bit[i], first_bit[i] + bits_i) of fus[i]: Address::set_from_fheuint (conversion.rs:41-65) with the
 // selector's plan shifted by first_bit, through k_cmux_chain — one launch per distinct (first_bit, bits) pair, no allocation, no host wait,
 // in place.  Selector digits are read on the main stream only (fheram_bank_select prepares them there), so the launch is ordered by the stream.
@@ -141,6 +341,7 @@ int fheram_bank_selector_derive(fheram_bank* b, const fheram_fheuint* const* fus
     for (int k = 0; k < n; k++) {   // every check for the whole list before anything is enqueued: a refused call changes no selector
         if (!fus[k] || fus[k]->ctx != c) return fail(c, FHERAM_ERR_INVALID_ARG, "integer " + std::to_string(k) + " is null or belongs to another bank");
         if (!sels[k] || sels[k]->bank != b) return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " is null or belongs to another bank");
+        if (sels[k]->fields) return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " is a field selector: fheram_bank_selector_derive_fields derives it");
         if (first_bit[k] < 0 || first_bit[k] + sels[k]->bits > fus[k]->n_bits)
             return fail(c, FHERAM_ERR_INVALID_ARG, "bits [" + std::to_string(first_bit[k]) + ", " + std::to_string(first_bit[k]) + " + " + std::to_string(sels[k]->bits) + ") of integer " + std::to_string(k) + " are beyond its " + std::to_string(fus[k]->n_bits) + " bits");
         for (int q = 0; q < k; q++)
@@ -192,55 +393,24 @@ int fheram_bank_select(fheram_bank* b, const fheram_selector* const* sels, const
     mid_rearm(c);
     // ---- every check before anything is enqueued: a refused call changes nothing ----
     if (!sels || !n_cand || !srcs) return fail(c, FHERAM_ERR_INVALID_ARG, "null selector list, candidate counts or sources");
-    if (n < 1 || n > FHERAM_SELECT_MAX)
-        return fail(c, FHERAM_ERR_INVALID_ARG, "n = " + std::to_string(n) + " is outside [1, FHERAM_SELECT_MAX = " + std::to_string(FHERAM_SELECT_MAX) + "]");
-    const int ws = b->mws, Y = n * ws;
-    if (Y > 64)
-        return fail(c, FHERAM_ERR_INVALID_ARG, "n * word_size = " + std::to_string(Y) + " exceeds 64, the ciphertext limit of the single-launch chains (k_chain_mid)");
     int total = 0, n_host = 0;
-    for (int k = 0; k < n; k++) {
-        if (!sels[k] || sels[k]->bank != b) return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " is null or belongs to another bank");
-        if (sels[k]->empty) return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " is empty: fheram_bank_selector_alloc without fheram_bank_selector_derive");
-        if (sels[k]->bits != sels[0]->bits)
-            return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " has " + std::to_string(sels[k]->bits) + " bits, selector 0 " + std::to_string(sels[0]->bits) + ": the selects of one call share one digit count (the operand table's)");
-        if (n_cand[k] < 1 || n_cand[k] > (1 << sels[k]->bits))
-            return fail(c, FHERAM_ERR_INVALID_ARG, "select " + std::to_string(k) + " has " + std::to_string(n_cand[k]) + " candidates, outside [1, 2^bits = " + std::to_string(1 << sels[k]->bits) + "]");
-        total += n_cand[k];
-    }
-    bool need_list = false, need_sel = false;
+    int rc = select_check_sels(b, sels, n_cand, n, &total);
+    if (rc != FHERAM_OK) return rc;
+    const int ws = b->mws, Y = n * ws;
+    SelectNeeds need;
     for (int i = 0; i < total; i++) {
-        const fheram_select_src& s = srcs[i];
-        const std::string who = "source " + std::to_string(i);
-        switch (s.kind) {
-        case FHERAM_SRC_ZERO: break;
-        case FHERAM_SRC_HOST:
-            if (!host_words) return fail(c, FHERAM_ERR_INVALID_ARG, who + " is a host word and host_words is null");
-            if (s.index < 0 || s.index >= FHERAM_SELECT_MAX * (1 << FHERAM_SELECT_BITS_MAX)) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names host slot " + std::to_string(s.index) + ", outside [0, " + std::to_string(FHERAM_SELECT_MAX * (1 << FHERAM_SELECT_BITS_MAX)) + ")");
-            n_host = std::max(n_host, s.index + 1);
-            break;
-        case FHERAM_SRC_MEMBER_RESULT:
-            if (s.index < 0 || s.index >= b->M) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names member " + std::to_string(s.index) + ", outside the bank's " + std::to_string(b->M) + " members");
-            break;
-        case FHERAM_SRC_LIST_RESULT:
-            if (s.index < 0 || (b->list_n && s.index >= b->list_n)) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names entry " + std::to_string(s.index) + ", outside the last read list's " + std::to_string(b->list_n) + " entries");
-            need_list = true;
-            break;
-        case FHERAM_SRC_SELECT_RESULT:
-            if (s.index < 0 || (b->sel_n && s.index >= b->sel_n)) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names output " + std::to_string(s.index) + ", outside the last select's " + std::to_string(b->sel_n) + " outputs");
-            need_sel = true;
-            break;
-        default: return fail(c, FHERAM_ERR_INVALID_ARG, who + " has the unknown kind " + std::to_string(s.kind));
-        }
+        rc = select_check_source(b, srcs[i].kind, srcs[i].index, "source " + std::to_string(i), host_words, need);
+        if (rc != FHERAM_OK) return rc;
+        if (srcs[i].kind == FHERAM_SRC_HOST) n_host = std::max(n_host, srcs[i].index + 1);
     }
-    if (!c->keys_loaded) return fail(c, FHERAM_ERR_KEYS, "evaluation keys not loaded");
-    if (need_list && !b->list_n) return fail(c, FHERAM_ERR_STATE, "a source names the last read list and no read list has run on this bank");
-    if (need_sel && !b->sel_n) return fail(c, FHERAM_ERR_STATE, "a source names the last select and no select has run on this bank");
+    rc = select_check_state(b, need);
+    if (rc != FHERAM_OK) return rc;
     for (int i = 0; i < total; i++)
         if (srcs[i].kind == FHERAM_SRC_MEMBER_RESULT && !b->has_res[srcs[i].index])
             return fail(c, FHERAM_ERR_STATE, "source " + std::to_string(i) + " names the result of member " + std::to_string(srcs[i].index) + ", which has none yet");
     HIPCHK(c, hipSetDevice(c->device));
     const int d = sels[0]->n_digits;
-    int rc = select_reserve(b, Y, n * d, n_host * ws);
+    rc = select_reserve(b, Y, n * d, n_host * ws);
     if (rc != FHERAM_OK) return rc;
     SelectBufs& S = b->sel;
     const size_t per = (size_t)ws * fheram_ctx::GLWE;
@@ -268,7 +438,6 @@ int fheram_bank_select(fheram_bank* b, const fheram_selector* const* sels, const
         S.host_busy = true;
     }
     b->sel_n = 0;   // until this select is enqueued there is no last select
-    const long G = (long)fheram_ctx::GLWE;
     {   // the pack: ONE launch, whatever n and m are
         SelectPackArgs sa{};
         sa.out = S.packed; sa.ws = ws;
@@ -279,28 +448,85 @@ int fheram_bank_select(fheram_bank* b, const fheram_selector* const* sels, const
         ProfScope ps(c, "select_pack", (uint64_t)Y);
         select_pack_launch(dim3(1, Y, EW_SLICES), c->cur, sa);
     }
-    // the selectors' digits, prepared: select k's at k * stride (CoordinatePrepared::prepare, coordinate_prepared.rs:104-116)
-    const long stride = (long)d * (long)fheram_ctx::GGSW;
-    for (int k = 0; k < n; k++) launch_prepare(c, sels[k]->d_ggsw, S.prep + k * stride, d * (int)(fheram_ctx::GGSW / N));
-    // Ram::read of the one-row RAM {packed} (ram.rs:451,457): the products with the digits in order, then trace(0, log N) — as read_top runs
-    // the second coordinate's products and the final trace of n * ws ciphertexts
-    const GlweRef packed = ref(S.packed, G, 0), ep = ref(S.ep, G, 0), tmp = ref(S.tmp, G, 0), res = ref(S.res, G, 0);
-    const OpndTable table = n == 1 ? OpndTable{} : OpndTable{ws, stride, MEMBER_MAP_IDENTITY, false};
-    auto slice = [&](GlweRef r, int k) { r.p += (long)k * ws * r.sy; return r; };
-    auto products = [&] { for (int k = 0; k < n; k++) ep_chain(c, slice(packed, k), slice(ep, k), slice(tmp, k), S.prep + k * stride, d, 1, ws); };
-    const bool fuse_ep = c->cfg.tail_ep && d >= 2 && d <= TAIL_EP_MAX && chain_form(c, ChainQuery{false, LOGN, 1, Y}).form == ChainForm::Tail;
-    GlweRef tb[2];
-    if (fuse_ep && chain_bufs(LOGN, ep, res, tmp, tb))
-        launch_trace_tail(c, packed, tb, 0, LOGN, 1, Y, S.prep, d, ep, false, table);
-    else {
-        products();
-        trace_steps(c, ep, res, tmp, 0, LOGN, 1, Y);
+    return select_chain(b, sels, n, out);
+}
+// As fheram_bank_select with every candidate assembled lane by lane: the pack is k_select_pack_lanes over a pointer table in device memory
+// (select_lanes.hip), everything behind it is select_chain.
+int fheram_bank_select_lanes(fheram_bank* b, const fheram_selector* const* sels, const int* n_cand, int n, const fheram_select_lane* lanes,
+                             const int64_t* host_words, int64_t* out) {
+    if (!b) return FHERAM_ERR_INVALID_ARG;
+    fheram_ctx* c = b->c;
+    mid_rearm(c);
+    // ---- every check before anything is enqueued: a refused call changes nothing ----
+    if (!sels || !n_cand || !lanes) return fail(c, FHERAM_ERR_INVALID_ARG, "null selector list, candidate counts or lanes");
+    int total = 0, n_host = 0;
+    int rc = select_check_sels(b, sels, n_cand, n, &total);
+    if (rc != FHERAM_OK) return rc;
+    const int ws = b->mws, Y = n * ws, n_lanes = total * ws;
+    SelectNeeds need;
+    for (int i = 0; i < n_lanes; i++) {
+        const fheram_select_lane& l = lanes[i];
+        const std::string who = "lane " + std::to_string(i % ws) + " of candidate " + std::to_string(i / ws);
+        rc = select_check_source(b, l.kind, l.index, who, host_words, need);
+        if (rc != FHERAM_OK) return rc;
+        if (l.reserved != 0) return fail(c, FHERAM_ERR_INVALID_ARG, who + " has reserved = " + std::to_string(l.reserved) + ", not 0");
+        if (l.kind != FHERAM_SRC_ZERO && (l.lane < 0 || l.lane >= ws))
+            return fail(c, FHERAM_ERR_INVALID_ARG, who + " names lane " + std::to_string(l.lane) + ", outside the word's " + std::to_string(ws) + " ciphertexts");
+        if (l.kind == FHERAM_SRC_HOST) n_host = std::max(n_host, l.index + 1);
     }
-    HIPCHK(c, hipGetLastError());
-    b->sel_n = n;
-    if (!out) return FHERAM_OK;
-    const ResRun run{S.res, (size_t)Y * fheram_ctx::GLWE};
-    return result_export(c, &run, 1, S.h_res, S.d_h_res, out);
+    rc = select_check_state(b, need);
+    if (rc != FHERAM_OK) return rc;
+    for (int i = 0; i < n_lanes; i++)
+        if (lanes[i].kind == FHERAM_SRC_MEMBER_RESULT && !b->has_res[lanes[i].index])
+            return fail(c, FHERAM_ERR_STATE, "lane " + std::to_string(i % ws) + " of candidate " + std::to_string(i / ws) + " names the result of member " + std::to_string(lanes[i].index) + ", which has none yet");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int d = sels[0]->n_digits;
+    rc = select_reserve(b, Y, n * d, n_host * ws);
+    if (rc != FHERAM_OK) return rc;
+    rc = lane_table_reserve(b);
+    if (rc != FHERAM_OK) return rc;
+    SelectBufs& S = b->sel;
+    SelectLaneTable& L = b->lanes;
+    const size_t G = fheram_ctx::GLWE;
+    std::vector<char> staged((size_t)n_host * ws, 0);   // host ciphertext (slot, lane): named by a lane
+    if (n_host) {   // range-checked as write words are: only the ciphertexts a lane names
+        if (S.host_busy) { HIPCHK(c, hipEventSynchronize(S.ev_host)); S.host_busy = false; }
+        for (int i = 0; i < n_lanes; i++) {
+            if (lanes[i].kind != FHERAM_SRC_HOST) continue;
+            const size_t at = (size_t)lanes[i].index * ws + lanes[i].lane;
+            if (staged[at]) continue;
+            staged[at] = 1;
+            if (!narrow(host_words + at * G, S.h_host + at * G, G))
+                return fail(c, FHERAM_ERR_RANGE, "limb out of the normalised range [-2^16, 2^16]");
+        }
+    }
+    if (L.busy) { HIPCHK(c, hipEventSynchronize(L.ev)); L.busy = false; }   // the last call's copy out of the pinned table; no other host wait
+    SelectLanesArgs sa{};
+    sa.table = L.d_tab; sa.out = S.packed; sa.ws = ws;
+    for (int k = 0, i = 0; k < n; k++) {
+        sa.m[k] = n_cand[k];
+        for (int j = 0; j < n_cand[k]; j++, i++)
+            for (int w = 0; w < ws; w++) L.h_tab[(size_t)(k * ws + w) * SELECT_CAND_MAX + j] = select_source_lane(b, lanes[(size_t)i * ws + w]);
+    }
+    // ---- enqueue ----
+    main_enqueued(c);
+    c->cur = c->stream;
+    c->wide = true;   // (as fheram_bank_select)
+    if (n_host) {
+        for (size_t at = 0; at < staged.size(); at++)
+            if (staged[at]) HIPCHK(c, hipMemcpyAsync(S.d_host + at * G, S.h_host + at * G, G * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipEventRecord(S.ev_host, c->stream));
+        S.host_busy = true;
+    }
+    b->sel_n = 0;   // until this select is enqueued there is no last select
+    HIPCHK(c, hipMemcpyAsync(L.d_tab, L.h_tab, (size_t)Y * SELECT_CAND_MAX * sizeof(const int32_t*), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(L.ev, c->stream));
+    L.busy = true;
+    {   // the pack: ONE launch, whatever n, m and the lanes are
+        ProfScope ps(c, "select_pack", (uint64_t)Y);
+        select_lanes_launch(Y, c->cur, sa);
+    }
+    return select_chain(b, sels, n, out);
 }
 int fheram_bank_select_result(fheram_bank* b, int first, int n, int64_t* out) {
     if (!b) return FHERAM_ERR_INVALID_ARG;

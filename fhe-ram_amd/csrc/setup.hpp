@@ -512,9 +512,11 @@ int fheram_address_alloc(fheram_ctx* c, fheram_addr** out) {
     *out = a;
     return FHERAM_OK;
 }
-int fheram_address_derive(fheram_ctx* c, const fheram_fheuint* const* fus, int n, int sign, fheram_addr* const* addrs) {
-    if (!c) return FHERAM_ERR_INVALID_ARG;
-    if (!fus || !addrs) return fail(c, FHERAM_ERR_INVALID_ARG, "null integer or address list");
+}  // extern "C"
+namespace {
+// The one body of fheram_address_derive (first_bit == nullptr: every integer from bit 0) and fheram_address_derive_at: the plan's bit_rsh
+// advanced by first_bit[k], ONE launch per distinct first_bit (the argument struct holds one plan).
+int address_derive_body(fheram_ctx* c, const fheram_fheuint* const* fus, const int* first_bit, int n, int sign, fheram_addr* const* addrs) {
     if (n < 1 || n > FHERAM_DERIVE_MAX)
         return fail(c, FHERAM_ERR_INVALID_ARG, "n = " + std::to_string(n) + " is outside [1, FHERAM_DERIVE_MAX = " + std::to_string(FHERAM_DERIVE_MAX) + "]");
     static_assert(FHERAM_DERIVE_MAX == DERIVE_K_MAX, "the argument struct of k_cmux_chain holds FHERAM_DERIVE_MAX integers and addresses");
@@ -524,6 +526,8 @@ int fheram_address_derive(fheram_ctx* c, const fheram_fheuint* const* fus, int n
         if (!fus[k] || fus[k]->ctx != c) return fail(c, FHERAM_ERR_INVALID_ARG, "integer " + std::to_string(k) + " is null or belongs to another context");
         if (!addrs[k] || addrs[k]->ctx != c) return fail(c, FHERAM_ERR_INVALID_ARG, "address " + std::to_string(k) + " is null or belongs to another context");
         if ((int)bits > fus[k]->n_bits) return fail(c, FHERAM_ERR_INVALID_ARG, "the address plan is wider than the encrypted integer");
+        if (first_bit && (first_bit[k] < 0 || first_bit[k] > fus[k]->n_bits - (int)bits))
+            return fail(c, FHERAM_ERR_INVALID_ARG, "bits [" + std::to_string(first_bit[k]) + ", " + std::to_string(first_bit[k]) + " + " + std::to_string(bits) + ") of integer " + std::to_string(k) + " are beyond its " + std::to_string(fus[k]->n_bits) + " bits");
         for (int q = 0; q < k; q++)
             if (addrs[q] == addrs[k]) return fail(c, FHERAM_ERR_INVALID_ARG, "address " + std::to_string(k) + " appears twice in the list");
     }
@@ -533,13 +537,14 @@ int fheram_address_derive(fheram_ctx* c, const fheram_fheuint* const* fus, int n
     CmuxChainArgs ca{};
     ca.tw = c->d_tw;
     ca.sign = sign ? 1 : 0;
+    unsigned char rsh0[DERIVE_DIGITS_MAX] = {};   // the plan's own bit_rsh, before first_bit
     {
         int digit = 0;
         unsigned bit_rsh = 0;
         for (auto& base1d : c->base2d) {                                                      // conversion.rs:45
             unsigned bit_lsh = 0;                                                             // :46
             for (int bit_mask : base1d) {                                                     // :49
-                ca.first[digit] = (unsigned char)bit_rsh; ca.bits[digit] = (unsigned char)bit_mask; ca.lsh[digit] = (unsigned char)bit_lsh;
+                rsh0[digit] = ca.first[digit] = (unsigned char)bit_rsh; ca.bits[digit] = (unsigned char)bit_mask; ca.lsh[digit] = (unsigned char)bit_lsh;
                 bit_lsh += (unsigned)bit_mask;                                                // :61
                 bit_rsh += (unsigned)bit_mask;                                                // :62
                 digit++;
@@ -549,18 +554,22 @@ int fheram_address_derive(fheram_ctx* c, const fheram_fheuint* const* fus, int n
     // Work of an earlier operation that still reads these digits on the side stream: inverse digits started early by read_prepare_write
     // (precompute_inverse: ev_inv) and the side stage of a write that has begun and not yet joined (write_side_begin: ev_join).
     bool wait_inv[2] = {false, false};
-    for (int k = 0; k < n; k++) {
-        ca.fu[k] = fus[k]->d_prep;
-        ca.out[k] = addrs[k]->d_ggsw;
+    for (int k = 0; k < n; k++)
         for (int ci = 0; ci < 2; ci++) if (c->inv_pending[ci] && c->inv_id[ci] == addrs[k]->id) wait_inv[ci] = true;
-    }
     for (int ci = 0; ci < 2; ci++) if (wait_inv[ci]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_inv[ci], 0));
     if (c->side_begun) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
     c->cur = c->stream;
-    {
+    bool done[DERIVE_K_MAX] = {};
+    for (int k = 0; k < n; k++) {   // first_bit == nullptr, or all equal: the one launch over all n
+        if (done[k]) continue;
+        const int f0 = first_bit ? first_bit[k] : 0;
+        for (int d = 0; d < c->n_digits; d++) ca.first[d] = (unsigned char)(rsh0[d] + f0);
+        int K = 0;
+        for (int q = k; q < n; q++)
+            if ((first_bit ? first_bit[q] : 0) == f0) { ca.fu[K] = fus[q]->d_prep; ca.out[K] = addrs[q]->d_ggsw; K++; done[q] = true; }
         const int rows = fheram_ctx::DNUM_CT * 2;
-        ProfScope ps(c, "derive", (uint64_t)n * c->n_digits * rows);
-        cmux_chain_launch(dim3(rows, c->n_digits, n), c->cur, ca);
+        ProfScope ps(c, "derive", (uint64_t)K * c->n_digits * rows);
+        cmux_chain_launch(dim3(rows, c->n_digits, K), c->cur, ca);
     }
     HIPCHK(c, hipGetLastError());
     // The handle now names other digits: a fresh id, so that nothing the context remembers by identity (inverse digits started early for the
@@ -571,6 +580,19 @@ int fheram_address_derive(fheram_ctx* c, const fheram_fheuint* const* fus, int n
     c->derive_unsynced = true;
     main_enqueued(c);
     return FHERAM_OK;
+}
+}  // namespace
+extern "C" {
+int fheram_address_derive(fheram_ctx* c, const fheram_fheuint* const* fus, int n, int sign, fheram_addr* const* addrs) {
+    if (!c) return FHERAM_ERR_INVALID_ARG;
+    if (!fus || !addrs) return fail(c, FHERAM_ERR_INVALID_ARG, "null integer or address list");
+    return address_derive_body(c, fus, nullptr, n, sign, addrs);
+}
+// Address bits from an offset of the integer: a byte-addressed load takes its word address from bits [2, ..) and its lane from bits [0, 2)
+int fheram_address_derive_at(fheram_ctx* c, const fheram_fheuint* const* fus, const int* first_bit, int n, int sign, fheram_addr* const* addrs) {
+    if (!c) return FHERAM_ERR_INVALID_ARG;
+    if (!fus || !addrs || !first_bit) return fail(c, FHERAM_ERR_INVALID_ARG, "null integer, bit or address list");
+    return address_derive_body(c, fus, first_bit, n, sign, addrs);
 }
 
 }  // extern "C"

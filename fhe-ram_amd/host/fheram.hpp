@@ -252,10 +252,11 @@ public:
     // The same for 1 to FHERAM_DERIVE_MAX integers as ONE launch on this Ram's stream (fheram_address_derive): no allocation, no host wait;
     // later operations that use the addresses are ordered behind it.  *addrs[i] is overwritten in place when it already lives on this
     // Ram's device (whatever made it) and gets its device buffers here otherwise; its host digits are dropped.  No address twice.  The
-    // integers must stay alive until sync().
-    void derive(const std::vector<const FheUintPrepared*>& fheuints, const std::vector<Address*>& addrs, bool sign = false) {
-        if (fheuints.empty() || fheuints.size() > FHERAM_DERIVE_MAX || addrs.size() != fheuints.size())
-            throw Error(FHERAM_ERR_INVALID_ARG, "derive takes 1 to FHERAM_DERIVE_MAX integers and as many addresses");
+    // integers must stay alive until sync().  first_bits (one per integer, or none): the address bits start at bit first_bits[i] of integer i
+    // (fheram_address_derive_at: a byte address keeps its lane offset below its word address), one launch per distinct first bit.
+    void derive(const std::vector<const FheUintPrepared*>& fheuints, const std::vector<Address*>& addrs, bool sign = false, const std::vector<int>& first_bits = {}) {
+        if (fheuints.empty() || fheuints.size() > FHERAM_DERIVE_MAX || addrs.size() != fheuints.size() || (!first_bits.empty() && first_bits.size() != fheuints.size()))
+            throw Error(FHERAM_ERR_INVALID_ARG, "derive takes 1 to FHERAM_DERIVE_MAX integers, as many addresses and no or as many first bits");
         std::vector<const fheram_fheuint*> fh;
         std::vector<fheram_addr*> ah;
         for (const FheUintPrepared* f : fheuints) { if (!f) throw Error(FHERAM_ERR_INVALID_ARG, "null integer"); fh.push_back(f->h_); }
@@ -265,7 +266,8 @@ public:
             if (!a->h_) { chk(fheram_address_alloc(ctx_, &a->h_)); a->owner_ = this; }
             ah.push_back(a->h_);
         }
-        chk(fheram_address_derive(ctx_, fh.data(), (int)fh.size(), sign ? 1 : 0, ah.data()));
+        if (first_bits.empty()) chk(fheram_address_derive(ctx_, fh.data(), (int)fh.size(), sign ? 1 : 0, ah.data()));
+        else chk(fheram_address_derive_at(ctx_, fh.data(), first_bits.data(), (int)fh.size(), sign ? 1 : 0, ah.data()));
         for (Address* a : addrs) a->digits.clear();
     }
     // EvaluationKeys::encrypt_sk + EvaluationKeysPrepared::prepare, keys.rs:135-180,57-71: generated and
@@ -495,10 +497,10 @@ public:
         friend class Bank;
         fheram_fheuint* h_ = nullptr;
     };
-    // as Ram::derive (fheram_bank_address_derive): *addrs[i] becomes an ordinary address of this bank, which may serve several members
-    void derive(const std::vector<const FheUintPrepared*>& fheuints, const std::vector<Address*>& addrs, bool sign = false) {
-        if (fheuints.empty() || fheuints.size() > FHERAM_DERIVE_MAX || addrs.size() != fheuints.size())
-            throw Error(FHERAM_ERR_INVALID_ARG, "derive takes 1 to FHERAM_DERIVE_MAX integers and as many addresses");
+    // as Ram::derive (fheram_bank_address_derive / _derive_at): *addrs[i] becomes an ordinary address of this bank, which may serve several members
+    void derive(const std::vector<const FheUintPrepared*>& fheuints, const std::vector<Address*>& addrs, bool sign = false, const std::vector<int>& first_bits = {}) {
+        if (fheuints.empty() || fheuints.size() > FHERAM_DERIVE_MAX || addrs.size() != fheuints.size() || (!first_bits.empty() && first_bits.size() != fheuints.size()))
+            throw Error(FHERAM_ERR_INVALID_ARG, "derive takes 1 to FHERAM_DERIVE_MAX integers, as many addresses and no or as many first bits");
         std::vector<const fheram_fheuint*> fh;
         std::vector<fheram_addr*> ah;
         for (const FheUintPrepared* f : fheuints) { if (!f) throw Error(FHERAM_ERR_INVALID_ARG, "null integer"); fh.push_back(f->h_); }
@@ -509,7 +511,8 @@ public:
             if (!h) { chk(fheram_bank_address_alloc(bank_, &h)); addr_.emplace_back(a, h); }
             ah.push_back(h);
         }
-        chk(fheram_bank_address_derive(bank_, fh.data(), (int)fh.size(), sign ? 1 : 0, ah.data()));
+        if (first_bits.empty()) chk(fheram_bank_address_derive(bank_, fh.data(), (int)fh.size(), sign ? 1 : 0, ah.data()));
+        else chk(fheram_bank_address_derive_at(bank_, fh.data(), first_bits.data(), (int)fh.size(), sign ? 1 : 0, ah.data()));
         for (Address* a : addrs) a->digits.clear();
     }
     // ---- oblivious select (include/fheram.h): pick one of the candidate words by an encrypted index, on the device
@@ -522,13 +525,30 @@ public:
             for (auto& d : digits) ptr.push_back(d.data());
             bank.chk(fheram_bank_selector_create(bank.bank_, ptr.data(), (int)ptr.size(), bits, &h_));
         }
+        // a FIELD selector: digit d has widths[d] bits and may come from an integer and a bit position of its own (fheram_bank_selector_alloc_fields /
+        // _create_fields); without digits for derive_selector_fields, or from host std-form GGSW digits, one per field
+        Selector(Bank& bank, const std::vector<int>& widths) : fields_(widths.size()) { bank.chk(fheram_bank_selector_alloc_fields(bank.bank_, widths.data(), (int)widths.size(), &h_)); }
+        Selector(Bank& bank, const std::vector<int>& widths, const std::vector<std::vector<int64_t>>& digits) : fields_(widths.size()) {
+            std::vector<const int64_t*> ptr;
+            for (auto& d : digits) ptr.push_back(d.data());
+            bank.chk(fheram_bank_selector_create_fields(bank.bank_, ptr.data(), (int)ptr.size(), widths.data(), (int)widths.size(), &h_));
+        }
         ~Selector() { if (h_) fheram_selector_destroy(h_); }
         Selector(const Selector&) = delete;
         int n_digits() const { return fheram_selector_n_digits(h_); }
     private:
         friend class Bank;
         fheram_selector* h_ = nullptr;
+        size_t fields_ = 0;   // a field selector: its number of fields
     };
+    // digit d of the field selector <- bits [first_bits[d], first_bits[d] + widths[d]) of *fheuints[d] (fheram_bank_selector_derive_fields)
+    void derive_selector_fields(Selector& sel, const std::vector<const FheUintPrepared*>& fheuints, const std::vector<int>& first_bits) {
+        if (!sel.fields_ || fheuints.size() != sel.fields_ || first_bits.size() != sel.fields_)
+            throw Error(FHERAM_ERR_INVALID_ARG, "derive_selector_fields takes a field selector and one integer and one first bit per field");
+        std::vector<const fheram_fheuint*> fh;
+        for (const FheUintPrepared* f : fheuints) { if (!f) throw Error(FHERAM_ERR_INVALID_ARG, "null integer"); fh.push_back(f->h_); }
+        chk(fheram_bank_selector_derive_fields(bank_, sel.h_, fh.data(), first_bits.data()));
+    }
     // *sels[i] <- bits [first_bits[i], first_bits[i] + bits_i) of *fheuints[i] (fheram_bank_selector_derive): no allocation, no host wait
     void derive_selectors(const std::vector<const FheUintPrepared*>& fheuints, const std::vector<int>& first_bits, const std::vector<Selector*>& sels) {
         if (sels.empty() || sels.size() > FHERAM_SELECT_MAX || fheuints.size() != sels.size() || first_bits.size() != sels.size())
@@ -563,6 +583,34 @@ public:
             if (x.kind == FHERAM_SRC_HOST && (x.index < 0 || (size_t)x.index >= host_words.size())) throw Error(FHERAM_ERR_INVALID_ARG, "a host candidate names a slot outside host_words");
         std::vector<int64_t> out(download ? sh.size() * params.word_size() * glwe_len() : 0);
         chk(fheram_bank_select(bank_, sh.data(), n_cand.data(), (int)sh.size(), flat_src.data(), flat.empty() ? nullptr : flat.data(), download ? out.data() : nullptr));
+        return download ? split(out, sh.size()) : std::vector<std::vector<Glwe>>();
+    }
+    // GLWE `lane` of the word a source names (fheram_select_lane)
+    static fheram_select_lane lane_of(fheram_select_src src, int lane) { return {src.kind, src.index, src.kind == FHERAM_SRC_ZERO ? 0 : lane, 0}; }
+    // select with lane-mapped candidates (fheram_bank_select_lanes): candidates[k][j] is the word_size lanes candidate j of select k is assembled from
+    std::vector<std::vector<Glwe>> select_lanes(const std::vector<const Selector*>& sels, const std::vector<std::vector<std::vector<fheram_select_lane>>>& candidates,
+                                                const std::vector<std::vector<Glwe>>& host_words = {}, bool download = true) {
+        if (sels.empty() || candidates.size() != sels.size()) throw Error(FHERAM_ERR_INVALID_ARG, "select_lanes takes at least one selector and one candidate list per selector");
+        std::vector<const fheram_selector*> sh;
+        std::vector<int> n_cand;
+        std::vector<fheram_select_lane> flat_lanes;
+        for (const Selector* x : sels) { if (!x) throw Error(FHERAM_ERR_INVALID_ARG, "null selector"); sh.push_back(x->h_); }
+        for (auto& c : candidates) {
+            n_cand.push_back((int)c.size());
+            for (auto& word : c) {
+                if (word.size() != params.word_size()) throw Error(FHERAM_ERR_INVALID_ARG, "a candidate has word_size lanes");
+                flat_lanes.insert(flat_lanes.end(), word.begin(), word.end());
+            }
+        }
+        std::vector<int64_t> flat;
+        for (auto& word : host_words) {
+            if (word.size() != params.word_size()) throw Error(FHERAM_ERR_INVALID_ARG, "a host candidate has word_size GLWEs");
+            for (auto& g : word) flat.insert(flat.end(), g.begin(), g.end());
+        }
+        for (auto& x : flat_lanes)
+            if (x.kind == FHERAM_SRC_HOST && (x.index < 0 || (size_t)x.index >= host_words.size())) throw Error(FHERAM_ERR_INVALID_ARG, "a host lane names a slot outside host_words");
+        std::vector<int64_t> out(download ? sh.size() * params.word_size() * glwe_len() : 0);
+        chk(fheram_bank_select_lanes(bank_, sh.data(), n_cand.data(), (int)sh.size(), flat_lanes.data(), flat.empty() ? nullptr : flat.data(), download ? out.data() : nullptr));
         return download ? split(out, sh.size()) : std::vector<std::vector<Glwe>>();
     }
     // outputs [first, first + n) of the last select (fheram_bank_select_result)

@@ -61,6 +61,17 @@ int main() {
         for (size_t i = 0; i < 4; i++)
             if (((pt2[i * 3 * p.n()] - pt[i * 3 * p.n()]) & ((1 << 17) - 1)) != 0) { std::printf("derived address: word %zu differs\n", i); return 6; }
         std::printf("address derived from an encrypted integer reads the same word: ok\n");
+        {   // the same word again through a BYTE address: the word address sits above two lane-offset bits (fheram_address_derive_at, first_bit = 2)
+            fheram::Ram::FheUintPrepared byte_addr(ram, (idx << 2) | 3, dsk, xa, xe, 14);
+            fheram::Address at2;
+            ram.derive({&byte_addr}, {&at2}, false, {2});
+            std::vector<int64_t> pt3 = ram.decrypt(ram.read(at2, keys), dsk);
+            for (size_t i = 0; i < 4; i++)
+                if (((pt3[i * 3 * p.n()] - pt[i * 3 * p.n()]) & ((1 << 17) - 1)) != 0) { std::printf("address derived at bit 2: word %zu differs\n", i); return 6; }
+            try { ram.derive({&byte_addr}, {&at2}, false, {3}); return 6; }   // 3 + 12 bits are beyond the integer's 14
+            catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 6; }
+            std::printf("address derived from bit 2 of a byte address reads the same word: ok\n");
+        }
         // one handle over "two GPUs" (the same device twice: rehearsal): a group must refuse an operation before its keys
         // and RAM are loaded exactly as the single context does
         fheram::GroupRam grp(fheram::Parameters(4, {3, 3, 3, 3}, 1 << 13), {0, 0});   // two rows per sub-RAM: one per shard
@@ -144,6 +155,35 @@ int main() {
             try { lists.select({&ts0}, {{fheram::Bank::src_zero()}}); return 16; }   // a selector of another bank
             catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 16; }
             std::printf("bank select + write_selected == select, download, write_list: ok\n");
+            {   // Bank::select_lanes: identity lanes are select; swapped lanes are select on the host-assembled word; field selectors; derive at an offset
+                using B = fheram::Bank;
+                std::vector<std::vector<std::vector<fheram_select_lane>>> ident(2), swapped(1);
+                for (size_t k = 0; k < 2; k++)
+                    for (auto& src : cand[k]) { ident[k].emplace_back(); for (int w = 0; w < 4; w++) ident[k].back().push_back(B::lane_of(src, w)); }
+                if (lists.select_lanes({&ls0, &ls1}, ident, words) != twin.select({&ts0, &ts1}, cand, words)) { std::printf("select_lanes: identity lanes differ from select\n"); return 17; }
+                const int perm[4] = {1, 0, 3, 2};
+                swapped[0].emplace_back(); swapped[0].emplace_back();
+                for (int w = 0; w < 4; w++) { swapped[0][0].push_back(B::lane_of(B::src_host(0), perm[w])); swapped[0][1].push_back(B::lane_of(B::src_host(1), w)); }
+                std::vector<std::vector<fheram::Glwe>> shuffled = words;
+                for (int w = 0; w < 4; w++) shuffled[0][w] = words[0][perm[w]];
+                if (lists.select_lanes({&ls0}, swapped, words) != twin.select({&ts0}, {{B::src_host(0), B::src_host(1)}}, shuffled)) { std::printf("select_lanes: permuted lanes differ\n"); return 17; }
+                // a selector of two one-bit fields: from host digits, and derived field by field from two synthetic integers
+                const std::vector<std::vector<int64_t>> fd = {sd[0], synth(3 * 2 * 4 * 2 * n)};
+                B::Selector lf(lists, std::vector<int>{1, 1}, fd), tf(twin, std::vector<int>{1, 1}, fd), ld(lists, std::vector<int>{1, 1}), td(twin, std::vector<int>{1, 1});
+                if (lf.n_digits() != 2 || ld.n_digits() != 2) return 18;
+                const std::vector<std::vector<fheram_select_src>> four = {{B::src_host(0), B::src_host(1), B::src_zero(), B::src_member(0)}};
+                if (lists.select({&lf}, four, words) != twin.select({&tf}, four, words)) return 18;
+                const std::vector<int64_t> ia = synth(3 * 4 * 2 * 5 * 2 * n), ib = synth(2 * 4 * 2 * 5 * 2 * n);
+                B::FheUintPrepared la3(lists, ia, 3), lb2(lists, ib, 2), ta3(twin, ia, 3), tb2(twin, ib, 2);
+                lists.derive_selector_fields(ld, {&la3, &lb2}, {2, 0});
+                twin.derive_selector_fields(td, {&ta3, &tb2}, {2, 0});
+                if (lists.select({&ld}, four, words) != twin.select({&td}, four, words)) return 18;
+                try { lists.select({&ld, &ls0}, {four[0], four[0]}, words); return 18; }   // two bits in two digits beside one bit
+                catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 18; }
+                try { lists.derive_selector_fields(ld, {&la3, &lb2}, {2, 2}); return 18; }   // bit [2, 3) is beyond the second integer's 2 bits
+                catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 18; }
+                std::printf("bank select_lanes, field selectors: ok\n");
+            }
         }
     } catch (const fheram::Error& e) {
         if (e.code != FHERAM_ERR_DEVICE) { std::printf("unexpected error %d: %s\n", e.code, e.what()); return 4; }

@@ -468,6 +468,14 @@ int fheram_address_derive(fheram_ctx* ctx, const fheram_fheuint* const* fus, int
 int fheram_bank_fheuint_create(fheram_bank* bank, const int64_t* bits, int n_bits, fheram_fheuint** out);
 int fheram_bank_address_alloc(fheram_bank* bank, fheram_addr** out);
 int fheram_bank_address_derive(fheram_bank* bank, const fheram_fheuint* const* fus, int n, int sign, fheram_addr* const* addrs);
+/* Addresses from a BIT OFFSET of the integers: addrs[k] <- the address whose plan reads bits [first_bit[k], first_bit[k] + plan bits) of
+ * fus[k] — fheram_address_derive with the plan's bit_rsh advanced by first_bit[k] (a byte-addressed load or store takes its word
+ * address from bits [2, ..) and its lane offset from bits [0, 2) of the same integer).  One launch per DISTINCT first_bit; the checks,
+ * the stream ordering and the fresh address ids are fheram_address_derive's (one body), and with first_bit all zero the digits are
+ * fheram_address_derive's bit for bit.  Also FHERAM_ERR_INVALID_ARG: first_bit null, first_bit[k] < 0, first_bit[k] + plan bits beyond
+ * the integer's width. */
+int fheram_address_derive_at(fheram_ctx* ctx, const fheram_fheuint* const* fus, const int* first_bit, int n, int sign, fheram_addr* const* addrs);
+int fheram_bank_address_derive_at(fheram_bank* bank, const fheram_fheuint* const* fus, const int* first_bit, int n, int sign, fheram_addr* const* addrs);
 
 /* ---- Oblivious select on a bank: pick one of m candidate words by an ENCRYPTED index, on the device — a VM step's write enable
  * (`enable ? new : old`), its store merge and result pick, and its moves between memories, without a host round trip.
@@ -530,6 +538,49 @@ int fheram_bank_write_list_selected(fheram_bank* bank, const int* members, const
 /* Self-test of fheram_bank_select's FHERAM_ERR_DEVICE path, as fheram_bank_selftest_fail_list_alloc: the nth device allocation its
  * buffers ask for from now on fails once (0 withdraws the request). */
 int fheram_bank_selftest_fail_select_alloc(fheram_bank* bank, int nth);
+
+/* ---- Sub-word loads and stores: select candidates assembled LANE BY LANE, and selectors made of fields of different integers.
+ * *** CONTRACT-COMPATIBLE ONLY *** as the select above: the same selection step (Ram::read on a one-row RAM) with candidates put
+ * together from whole byte ciphertexts.  A word is word_size GLWEs, one per byte (sub-RAM w holds byte w of every word, ram.rs:334-380),
+ * so at byte granularity the 16 candidates [offset 0..3] x [NONE, SB, SH, SW] of the reference's select_store (store.rs:40-143) are lane
+ * shuffles of two words — "SB at offset 1" is [y0, x0, y2, y3] — and its un-vendored splice_u8 / splice_u16 reduce to moving ciphertexts.
+ * Zero-extending loads (LBU / LHU) are lane shuffles with ZERO lanes.  OUT OF SCOPE: sign-extending loads (LB / LH need bit operations
+ * inside a byte) and the BDD circuits. */
+/* GLWE `lane` of the word (kind, index); kind / index as fheram_select_src.  kind ZERO: an all-zero ciphertext, lane ignored. */
+typedef struct fheram_select_lane { int32_t kind, index, lane, reserved /* 0 */; } fheram_select_lane;
+/* fheram_bank_select with lane-mapped candidates.  lanes: [sum n_cand][word_size]; with L = lanes[(off_k + j) * word_size + w] for
+ * select k, candidate j, word ciphertext w (off_k = the sum of the earlier n_cand)
+ *     packed_{k,w} = glwe_normalize( sum_{j < n_cand[k]} X^j * source(L.kind, L.index)[L.lane] )     (one launch: k_select_pack_lanes)
+ * and then exactly what fheram_bank_select runs: the selectors' digits prepared, the products, trace(0, log N), in the forms the bank's
+ * configuration selects.  It IS the last select in every respect: fheram_bank_select_result, FHERAM_SRC_SELECT_RESULT and
+ * fheram_bank_write_list_selected work on it unchanged, and it touches no member's rows, state flag, tree, result or kept memo; the last
+ * read list's results stay readable.  With identity lanes (lane = w, one source per candidate) the outputs are int64-identical to
+ * fheram_bank_select on the same sources; for any lanes, to fheram_bank_select on HOST candidates assembled from the downloaded sources.
+ * The candidate pointers (up to 64 x 32) are a table in device memory, written by the host into a pinned buffer and copied by one
+ * asynchronous copy on the bank's stream; a call waits for the host only where the previous lanes call's copy has not yet left the
+ * pinned buffer (as host candidates do).  Table and pinned buffer are allocated on the first lanes call and freed with the bank
+ * (FHERAM_ERR_DEVICE if that fails; every other operation still works).  fheram_bank_selftest_fail_select_alloc reaches the table's
+ * device allocation as the one AFTER those the select's buffers ask for in the same call.
+ * Refusals are fheram_bank_select's, checked for the whole call before anything is enqueued (a refused call changes nothing), and
+ * FHERAM_ERR_INVALID_ARG also for: a lane outside [0, word_size) of a non-ZERO kind, reserved != 0.  HOST ciphertexts are range-checked
+ * as there (FHERAM_ERR_RANGE), only the ciphertexts (slot, lane) a lane names. */
+int fheram_bank_select_lanes(fheram_bank* bank, const fheram_selector* const* sels, const int* n_cand, int n,
+                             const fheram_select_lane* lanes, const int64_t* host_words, int64_t* out /* [n][word_size][GLWE] or NULL */);
+/* A FIELD SELECTOR: sum(widths) <= FHERAM_SELECT_BITS_MAX bits whose digit d has widths[d] bits at bit offset lsh_d = sum(widths[0..d)),
+ * and may come from an integer and a bit position of its own (the store merge indexes by op + 4 * offset: two fields of two integers).
+ * It is the Address of a one-row RAM of max_addr = 2^bits whose DECOMP_N starts with `widths` (get_base_2d then gives [widths], whatever
+ * the bank's own DECOMP_N is): digit d is the GGSW of X^-(v_d << lsh_d) in the layout of address digits.  fheram_bank_select and
+ * fheram_bank_select_lanes accept it; the selectors of one call share `bits` AND the digit count (the operand table has one stride).
+ * FHERAM_ERR_INVALID_ARG: null pointers, n_fields outside [1, FHERAM_SELECT_FIELDS_MAX], a width < 1, a sum above
+ * FHERAM_SELECT_BITS_MAX, n_ggsw != n_fields. */
+#define FHERAM_SELECT_FIELDS_MAX 5
+int fheram_bank_selector_alloc_fields(fheram_bank* bank, const int* widths, int n_fields, fheram_selector** out);
+int fheram_bank_selector_create_fields(fheram_bank* bank, const int64_t* const* ggsw, int n_ggsw, const int* widths, int n_fields, fheram_selector** out);
+/* digit d <- bits [first_bit[d], first_bit[d] + widths[d]) of fus[d] (n_fields integers, repeats allowed), in place: no allocation, no
+ * host wait, through the unchanged k_cmux_chain — one launch per field.  Checked before anything is enqueued (FHERAM_ERR_INVALID_ARG):
+ * null pointers, a selector or integer of another bank, a selector that no _fields call made, a field beyond its integer's width.
+ * (fheram_bank_selector_derive refuses a field selector.) */
+int fheram_bank_selector_derive_fields(fheram_bank* bank, fheram_selector* sel, const fheram_fheuint* const* fus, const int* first_bit);
 
 /* ---- Measurement hooks (bench.py).  HIP events recorded on the context's own stream. */
 int fheram_timer_begin(fheram_ctx* ctx);
