@@ -33,6 +33,9 @@ SELECT_BITS_MAX = 5  # FHERAM_SELECT_BITS_MAX
 SELECT_MAX = 8       # FHERAM_SELECT_MAX
 SRC_ZERO, SRC_HOST, SRC_MEMBER_RESULT, SRC_LIST_RESULT, SRC_SELECT_RESULT = 0, 1, 2, 3, 4   # FHERAM_SRC_*
 SELECT_FIELDS_MAX = 5   # FHERAM_SELECT_FIELDS_MAX
+DERIVE_LIST_MAX = 32          # FHERAM_DERIVE_LIST_MAX
+DERIVE_LIST_DIGITS_MAX = 64   # FHERAM_DERIVE_LIST_DIGITS_MAX
+DERIVE_ADDRESS, DERIVE_SELECTOR, DERIVE_FIELD = 0, 1, 2   # FHERAM_DERIVE_ADDRESS / _SELECTOR / _FIELD
 STATUS = {0: "OK", 1: "INVALID_ARG", 2: "STATE", 3: "UNINITIALIZED", 4: "KEYS", 5: "UNSUPPORTED", 6: "RANGE", 7: "DEVICE", 8: "PRECISION"}
 
 
@@ -62,6 +65,11 @@ class _CSelectSrc(C.Structure):
 class _CSelectLane(C.Structure):
     """fheram_select_lane (include/fheram.h): GLWE `lane` of the word (kind, index)"""
     _fields_ = [("kind", C.c_int32), ("index", C.c_int32), ("lane", C.c_int32), ("reserved", C.c_int32)]
+
+
+class _CDeriveItem(C.Structure):
+    """fheram_derive_item (include/fheram.h): one address, selector or selector field of a derive list"""
+    _fields_ = [("kind", C.c_int32), ("first_bit", C.c_int32), ("sign", C.c_int32), ("field", C.c_int32), ("fu", C.c_void_p), ("target", C.c_void_p)]
 
 
 class _CConfig(C.Structure):
@@ -208,6 +216,8 @@ _SYMBOLS = [
     ("fheram_bank_read_prepare_write_list", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.c_int, I64P]),
     ("fheram_bank_write_list", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.c_int, I64P]),
     ("fheram_bank_selftest_fail_list_alloc", C.c_int, [C.c_void_p, C.c_int]),
+    ("fheram_bank_derive_list", C.c_int, [C.c_void_p, C.POINTER(_CDeriveItem), C.c_int]),
+    ("fheram_bank_address_download", C.c_int, [C.c_void_p, C.c_void_p, I64P]),
     ("fheram_bank_sync", C.c_int, [C.c_void_p]),
     ("fheram_bank_roundoff_max", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     ("fheram_bank_roundoff_reset", C.c_int, [C.c_void_p]),
@@ -588,6 +598,39 @@ def _derive_addresses(owner, fn, fheuints, addrs, sign, first_bits=None, fn_at=N
         a._handles = {id(owner): a._handles[id(owner)]}
         a._derived_from = f                                            # the integer stays alive until the launch that reads it has run
     return addrs
+
+
+class Derive:
+    """One entry of RamBank.derive_list (fheram_derive_item): an address, a plain selector or the fields of a field selector, each from
+    an encrypted integer, a first bit and (an address) a sign of its own.  Derive.fields gives one item per digit of its selector."""
+
+    def __init__(self, kind: int, fu, target, first_bit: int = 0, sign: bool = False, field: int = 0):
+        self.kind, self.fu, self.target, self.first_bit, self.sign, self.field = int(kind), fu, target, int(first_bit), bool(sign), int(field)
+
+    @classmethod
+    def address(cls, fu, addr=None, first_bit: int = 0, sign: bool = False):
+        """addr <- the address read from bits [first_bit, ..) of fu; addr=None: derive_list allocates one (Address.alloc)"""
+        if not isinstance(fu, FheUintPrepared) or not (addr is None or isinstance(addr, Address)):
+            raise FheRamError(1, "Derive.address takes a FheUintPrepared and an Address (or None)")
+        return cls(DERIVE_ADDRESS, fu, addr, first_bit, sign)
+
+    @classmethod
+    def selector(cls, fu, sel, first_bit: int = 0):
+        """the plain selector sel <- bits [first_bit, first_bit + sel.bits) of fu"""
+        if not isinstance(fu, FheUintPrepared) or not isinstance(sel, Selector) or sel.widths is not None:
+            raise FheRamError(1, "Derive.selector takes a FheUintPrepared and a plain Selector (RamBank.selector, Selector.from_digits)")
+        return cls(DERIVE_SELECTOR, fu, sel, first_bit)
+
+    @classmethod
+    def fields(cls, sel, fus, first_bits):
+        """the field selector sel whole: digit d <- bits [first_bits[d], first_bits[d] + widths[d]) of fus[d]; a LIST of items"""
+        if not isinstance(sel, Selector) or sel.widths is None:
+            raise FheRamError(1, "Derive.fields takes a field selector (RamBank.selector_fields, Selector.from_digits_fields)")
+        fus, first_bits = list(fus), [int(f) for f in first_bits]
+        k = len(sel.widths)
+        if len(fus) != k or len(first_bits) != k or not all(isinstance(f, FheUintPrepared) for f in fus):
+            raise FheRamError(1, f"Derive.fields: a selector of {k} fields takes {k} FheUintPrepared and {k} first bits")
+        return [cls(DERIVE_FIELD, fus[d], sel, first_bits[d], False, d) for d in range(k)]
 
 
 class Src:
@@ -1595,6 +1638,49 @@ class RamBank:
         """as Ram.derive_addresses, with integers and addresses bound to this bank (FheUintPrepared.from_host(bank, ...),
         Address.alloc(bank)): a derived address is an ordinary bank address and may serve several members"""
         return _derive_addresses(self, library().fheram_bank_address_derive, fheuints, addrs, sign, first_bits, "fheram_bank_address_derive_at")
+
+    def derive_list(self, items):
+        """any mix of addresses, selectors and selector fields from encrypted integers as ONE launch (fheram_bank_derive_list): `items` are
+        Derive entries (the lists Derive.fields returns are flattened).  No host wait, in place; returns the targets in item order.  An
+        address item with addr=None gets an Address.alloc(bank): that allocation is this mirror's convenience, made after its own checks
+        and before the library call (which allocates nothing), and freed again if the library refuses the call."""
+        flat = []
+        for it in items:
+            flat.extend(it if isinstance(it, (list, tuple)) else [it])
+        if not all(isinstance(it, Derive) for it in flat):
+            raise FheRamError(1, "derive_list takes Derive entries (Derive.address, Derive.selector, Derive.fields)")
+        n = len(flat)
+        if not 1 <= n <= DERIVE_LIST_MAX:
+            raise FheRamError(1, f"derive_list takes 1 to DERIVE_LIST_MAX = {DERIVE_LIST_MAX} items, got {n}")
+        targets = [Address.alloc(self) if it.kind == DERIVE_ADDRESS and it.target is None else it.target for it in flat]
+        arr = (_CDeriveItem * n)()
+        for i, (it, t) in enumerate(zip(flat, targets)):
+            handle = t._bank(self) if it.kind == DERIVE_ADDRESS else t._h   # (an address made from host digits: created here)
+            arr[i] = _CDeriveItem(it.kind, it.first_bit, int(it.sign), it.field, it.fu._h, handle)
+        try:
+            self._chk(library().fheram_bank_derive_list(self._h, arr, n))
+        except FheRamError:
+            for it, t in zip(flat, targets):
+                if it.target is None:
+                    t._handles.clear()   # the addresses allocated above go with the refusal (their handles free the device buffers)
+            raise
+        fed = {}
+        for it, t in zip(flat, targets):
+            if it.kind == DERIVE_ADDRESS:
+                t._digits = None                                   # the host copy, and the handles on other devices, held the old digits
+                t._handles = {id(self): t._handles[id(self)]}
+            fed.setdefault(id(t), (t, []))[1].append(it.fu)
+        for t, fus in fed.values():
+            t._derived_from = fus if len(fus) > 1 else fus[0]      # the integers stay alive until the launch that reads them has run
+        return targets
+
+    def address_digits(self, addr: Address) -> np.ndarray:
+        """the std-form GGSW digits of a bank address, [n_digits][ggsw_len] (fheram_bank_address_download)"""
+        if not isinstance(addr, Address):
+            raise FheRamError(1, "address_digits takes an Address")
+        out = np.zeros((addr.base2d.as_1d().size(), self.params.ggsw_len()), dtype=np.int64)
+        self._chk(library().fheram_bank_address_download(self._h, addr._bank(self), _p(out)))
+        return out
 
     # -- oblivious select (include/fheram.h: pick a word by an encrypted index)
     def selector(self, bits: int) -> Selector:

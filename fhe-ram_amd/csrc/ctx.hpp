@@ -4,6 +4,7 @@
 #include "../../include/fheram.h"
 #include "kernels.hpp"
 #include "cmux_chain.hpp"
+#include "cmux_jobs.hpp"
 #include "mapped_chains.hpp"
 
 #include <algorithm>

@@ -172,6 +172,7 @@ int fheram_ctx_create_cfg(const fheram_params* p, int device, int shard, int n_s
     LDSATTR((&k_encrypt_sk<4, 0>)); LDSATTR((&k_encrypt_sk<4, 1>));
     LDSATTR((&k_encrypt_sk<5, 0>)); LDSATTR((&k_encrypt_sk<5, 1>));
     CCHK(cmux_chain_register());
+    CCHK(cmux_jobs_register());
     CCHK(mapped_chains_register());
 #undef LDSATTR_KS
 #undef LDSATTR_KS4
@@ -838,3 +839,4 @@ int fheram_device_info(const fheram_ctx* c, char* name, size_t name_len, int* cu
 #include "group.hpp"
 #include "bank.hpp"
 #include "select.hpp"
+#include "derive_list.hpp"

@@ -514,6 +514,40 @@ int fheram_address_alloc(fheram_ctx* c, fheram_addr** out) {
 }
 }  // extern "C"
 namespace {
+// What the derivations into addresses share (address_derive_body below; fheram_bank_derive_list, derive_list.hpp).
+// the context's digit plan: bit_rsh, bit_mask, bit_lsh of every digit (conversion.rs:45-62)
+void address_plan(const fheram_ctx* c, unsigned char* rsh, unsigned char* bits, unsigned char* lsh) {
+    int digit = 0;
+    unsigned bit_rsh = 0;
+    for (auto& base1d : c->base2d) {                                                      // conversion.rs:45
+        unsigned bit_lsh = 0;                                                             // :46
+        for (int bit_mask : base1d) {                                                     // :49
+            rsh[digit] = (unsigned char)bit_rsh; bits[digit] = (unsigned char)bit_mask; lsh[digit] = (unsigned char)bit_lsh;
+            bit_lsh += (unsigned)bit_mask;                                                // :61
+            bit_rsh += (unsigned)bit_mask;                                                // :62
+            digit++;
+        }
+    }
+}
+// Work of an earlier operation that still reads these digits on the side stream: inverse digits started early by read_prepare_write
+// (precompute_inverse: ev_inv) and the side stage of a write that has begun and not yet joined (write_side_begin: ev_join).
+int derive_wait_readers(fheram_ctx* c, fheram_addr* const* addrs, int n) {
+    bool wait_inv[2] = {false, false};
+    for (int k = 0; k < n; k++)
+        for (int ci = 0; ci < 2; ci++) if (c->inv_pending[ci] && c->inv_id[ci] == addrs[k]->id) wait_inv[ci] = true;
+    for (int ci = 0; ci < 2; ci++) if (wait_inv[ci]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_inv[ci], 0));
+    if (c->side_begun) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
+    return FHERAM_OK;
+}
+void derive_addresses_written(fheram_ctx* c, fheram_addr* const* addrs, int n) {
+    // The handle now names other digits: a fresh id, so that nothing the context remembers by identity (inverse digits started early for the
+    // old ones, run_op's signature) can be resumed.  The captured launch sequences stay: they read d_ggsw, which has not moved, when replayed.
+    for (int k = 0; k < n; k++) { addrs[k]->id = next_addr_id(); addrs[k]->empty = false; }
+    // ... and a later read_prepare_write must not let its side work read them before this launch has run: the gate wave in front of that
+    // work gives up after a few ms, so the op records ev_opstart behind this launch (ctx.hpp derive_unsynced; read_local / read_top).
+    c->derive_unsynced = true;
+    main_enqueued(c);
+}
 // The one body of fheram_address_derive (first_bit == nullptr: every integer from bit 0) and fheram_address_derive_at: the plan's bit_rsh
 // advanced by first_bit[k], ONE launch per distinct first_bit (the argument struct holds one plan).
 int address_derive_body(fheram_ctx* c, const fheram_fheuint* const* fus, const int* first_bit, int n, int sign, fheram_addr* const* addrs) {
@@ -538,26 +572,9 @@ int address_derive_body(fheram_ctx* c, const fheram_fheuint* const* fus, const i
     ca.tw = c->d_tw;
     ca.sign = sign ? 1 : 0;
     unsigned char rsh0[DERIVE_DIGITS_MAX] = {};   // the plan's own bit_rsh, before first_bit
-    {
-        int digit = 0;
-        unsigned bit_rsh = 0;
-        for (auto& base1d : c->base2d) {                                                      // conversion.rs:45
-            unsigned bit_lsh = 0;                                                             // :46
-            for (int bit_mask : base1d) {                                                     // :49
-                rsh0[digit] = ca.first[digit] = (unsigned char)bit_rsh; ca.bits[digit] = (unsigned char)bit_mask; ca.lsh[digit] = (unsigned char)bit_lsh;
-                bit_lsh += (unsigned)bit_mask;                                                // :61
-                bit_rsh += (unsigned)bit_mask;                                                // :62
-                digit++;
-            }
-        }
-    }
-    // Work of an earlier operation that still reads these digits on the side stream: inverse digits started early by read_prepare_write
-    // (precompute_inverse: ev_inv) and the side stage of a write that has begun and not yet joined (write_side_begin: ev_join).
-    bool wait_inv[2] = {false, false};
-    for (int k = 0; k < n; k++)
-        for (int ci = 0; ci < 2; ci++) if (c->inv_pending[ci] && c->inv_id[ci] == addrs[k]->id) wait_inv[ci] = true;
-    for (int ci = 0; ci < 2; ci++) if (wait_inv[ci]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_inv[ci], 0));
-    if (c->side_begun) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
+    address_plan(c, rsh0, ca.bits, ca.lsh);
+    const int rcw = derive_wait_readers(c, addrs, n);
+    if (rcw != FHERAM_OK) return rcw;
     c->cur = c->stream;
     bool done[DERIVE_K_MAX] = {};
     for (int k = 0; k < n; k++) {   // first_bit == nullptr, or all equal: the one launch over all n
@@ -572,13 +589,7 @@ int address_derive_body(fheram_ctx* c, const fheram_fheuint* const* fus, const i
         cmux_chain_launch(dim3(rows, c->n_digits, K), c->cur, ca);
     }
     HIPCHK(c, hipGetLastError());
-    // The handle now names other digits: a fresh id, so that nothing the context remembers by identity (inverse digits started early for the
-    // old ones, run_op's signature) can be resumed.  The captured launch sequences stay: they read d_ggsw, which has not moved, when replayed.
-    for (int k = 0; k < n; k++) { addrs[k]->id = next_addr_id(); addrs[k]->empty = false; }
-    // ... and a later read_prepare_write must not let its side work read them before this launch has run: the gate wave in front of that
-    // work gives up after a few ms, so the op records ev_opstart behind this launch (ctx.hpp derive_unsynced; read_local / read_top).
-    c->derive_unsynced = true;
-    main_enqueued(c);
+    derive_addresses_written(c, addrs, n);
     return FHERAM_OK;
 }
 }  // namespace

@@ -11,6 +11,7 @@
 #pragma once
 #include "../../include/fheram.h"
 
+#include <algorithm>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -558,6 +559,53 @@ public:
         for (const FheUintPrepared* f : fheuints) { if (!f) throw Error(FHERAM_ERR_INVALID_ARG, "null integer"); fh.push_back(f->h_); }
         for (Selector* x : sels) { if (!x) throw Error(FHERAM_ERR_INVALID_ARG, "null selector"); sh.push_back(x->h_); }
         chk(fheram_bank_selector_derive(bank_, fh.data(), first_bits.data(), (int)sh.size(), sh.data()));
+    }
+    // ---- the derive list (fheram_bank_derive_list): any mix of addresses, selectors and selector fields from encrypted integers as ONE launch
+    struct DeriveItem { int kind; const FheUintPrepared* fu; Address* addr; Selector* sel; int first_bit; bool sign; int field; };
+    // *addr <- the address read from bits [first_bit, ..) of fu
+    static DeriveItem derive_address(const FheUintPrepared& fu, Address& addr, int first_bit = 0, bool sign = false) { return {FHERAM_DERIVE_ADDRESS, &fu, &addr, nullptr, first_bit, sign, 0}; }
+    // the plain selector sel <- bits [first_bit, first_bit + bits) of fu
+    static DeriveItem derive_selector(const FheUintPrepared& fu, Selector& sel, int first_bit = 0) { return {FHERAM_DERIVE_SELECTOR, &fu, nullptr, &sel, first_bit, false, 0}; }
+    // digit `field` of the field selector sel <- bits [first_bit, first_bit + widths[field]) of fu; a call names every field of such a selector
+    static DeriveItem derive_field(const FheUintPrepared& fu, Selector& sel, int field, int first_bit = 0) { return {FHERAM_DERIVE_FIELD, &fu, nullptr, &sel, first_bit, false, field}; }
+    void derive_list(const std::vector<DeriveItem>& items) {
+        if (items.empty() || items.size() > FHERAM_DERIVE_LIST_MAX) throw Error(FHERAM_ERR_INVALID_ARG, "derive_list takes 1 to FHERAM_DERIVE_LIST_MAX items");
+        std::vector<fheram_derive_item> ci;
+        for (const DeriveItem& it : items) {
+            if (!it.fu || (it.kind == FHERAM_DERIVE_ADDRESS ? !it.addr : !it.sel)) throw Error(FHERAM_ERR_INVALID_ARG, "a derive item without its integer or target");
+            void* target = it.kind == FHERAM_DERIVE_ADDRESS ? nullptr : (void*)it.sel->h_;
+            if (it.kind == FHERAM_DERIVE_ADDRESS) {
+                fheram_addr* h = nullptr;
+                for (auto& kv : addr_) if (kv.first == it.addr) h = kv.second;
+                if (!h) { chk(fheram_bank_address_alloc(bank_, &h)); addr_.emplace_back(it.addr, h); }
+                target = h;
+            }
+            ci.push_back(fheram_derive_item{it.kind, it.first_bit, it.sign ? 1 : 0, it.field, it.fu->h_, target});
+        }
+        chk(fheram_bank_derive_list(bank_, ci.data(), (int)ci.size()));
+        for (const DeriveItem& it : items) if (it.kind == FHERAM_DERIVE_ADDRESS) it.addr->digits.clear();
+    }
+    // the std-form digits of an address of this bank, one vector per digit (fheram_bank_address_download)
+    std::vector<std::vector<int64_t>> address_digits(Address& a) {
+        // The digit count: the ABI has no bank form of fheram_n_digits, so it is get_base_2d's (base.rs:84-108) on the parameters alone — every
+        // coordinate takes the decomposition's widths in turn until the address bits run out.  A count the library disagrees with cannot pass
+        // unnoticed: fheram_bank_address_download fills n_digits of its own, and host_check.cpp compares the result's size.
+        size_t bits = 0, n_digits = 0;
+        for (size_t v = params.max_addr() - 1; v; v >>= 1) bits++;
+        while (bits) {
+            const size_t before = bits;
+            for (uint32_t i = 0; i < params.p.n_decomp && bits; i++) { bits -= std::min<size_t>(bits, params.p.decomp_n[i]); n_digits++; }
+            if (bits == before) throw Error(FHERAM_ERR_INVALID_ARG, "a decomposition without bits");
+        }
+        const size_t ggsw = fheram_ggsw_len(nullptr);   // (the layout's length: the library's own figure, which needs no context)
+        fheram_addr* h = nullptr;
+        for (auto& kv : addr_) if (kv.first == &a) h = kv.second;
+        if (!h) h = dev(a);
+        std::vector<int64_t> flat(n_digits * ggsw);
+        chk(fheram_bank_address_download(bank_, h, flat.data()));
+        std::vector<std::vector<int64_t>> out;
+        for (size_t d = 0; d < n_digits; d++) out.emplace_back(flat.begin() + d * ggsw, flat.begin() + (d + 1) * ggsw);
+        return out;
     }
     static fheram_select_src src_zero() { return {FHERAM_SRC_ZERO, 0}; }
     static fheram_select_src src_host(int slot) { return {FHERAM_SRC_HOST, slot}; }           // slot of host_words

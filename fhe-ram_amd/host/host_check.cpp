@@ -183,6 +183,22 @@ int main() {
                 try { lists.derive_selector_fields(ld, {&la3, &lb2}, {2, 2}); return 18; }   // bit [2, 3) is beyond the second integer's 2 bits
                 catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 18; }
                 std::printf("bank select_lanes, field selectors: ok\n");
+                {   // Bank::derive_list: an address at bit 2, a plain selector and the two fields in ONE launch, against the twin's three calls
+                    const std::vector<int64_t> ic = synth(14 * 4 * 2 * 5 * 2 * n);
+                    B::FheUintPrepared lc14(lists, ic, 14), tc14(twin, ic, 14);
+                    fheram::Address da, ta;
+                    B::Selector lp(lists, 1), tp(twin, 1);
+                    lists.derive_list({B::derive_address(lc14, da, 2), B::derive_selector(la3, lp, 1), B::derive_field(la3, ld, 0, 2), B::derive_field(lb2, ld, 1, 0)});
+                    twin.derive({&tc14}, {&ta}, false, {2});
+                    twin.derive_selectors({&ta3}, {1}, {&tp});
+                    twin.derive_selector_fields(td, {&ta3, &tb2}, {2, 0});
+                    if (lists.address_digits(da) != twin.address_digits(ta) || lists.address_digits(da).size() != 4) { std::printf("derive_list: the address differs\n"); return 19; }
+                    if (lists.select({&ld}, four, words) != twin.select({&td}, four, words)) return 19;
+                    if (lists.select({&lp}, {{B::src_host(0), B::src_host(1)}}, words) != twin.select({&tp}, {{B::src_host(0), B::src_host(1)}}, words)) return 19;
+                    try { lists.derive_list({B::derive_field(la3, ld, 0, 2)}); return 19; }   // a field selector is derived whole
+                    catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 19; }
+                    std::printf("bank derive_list == derive, derive_selectors, derive_selector_fields: ok\n");
+                }
             }
         }
     } catch (const fheram::Error& e) {

@@ -582,6 +582,41 @@ int fheram_bank_selector_create_fields(fheram_bank* bank, const int64_t* const* 
  * (fheram_bank_selector_derive refuses a field selector.) */
 int fheram_bank_selector_derive_fields(fheram_bank* bank, fheram_selector* sel, const fheram_fheuint* const* fus, const int* first_bit);
 
+/* ---- A step's addresses and selectors in ONE launch: the derive list.
+ * *** CONTRACT-COMPATIBLE ONLY *** as fheram_address_derive and the select above: the same conversion (Address::set_from_fheuint,
+ * conversion.rs:41-65), the same input type, the same digits.  fheram_address_derive_at issues one launch per distinct first_bit,
+ * fheram_bank_selector_derive one per distinct (first_bit, bits) pair and fheram_bank_selector_derive_fields one per field, because their
+ * kernel takes one digit plan for all its integers.  Here every item has an integer, a first bit and a sign of its own, and every output
+ * digit is a job of a kernel that takes a flat list of them (k_cmux_jobs): any mix of addresses, selectors and selector fields is exactly
+ * ONE launch of 6 * (digits over all items) workgroups.
+ * Every digit is int64-identical to what fheram_bank_address_derive_at, fheram_bank_selector_derive or
+ * fheram_bank_selector_derive_fields writes for the same integer, first bit, width and sign.  Targets are overwritten in place (from
+ * _alloc, _create or an earlier derivation); no allocation, no host wait; the same integer may feed any number of items; mixed signs and
+ * selector widths are allowed.  Ordering is that of the three calls: behind work of an earlier operation that still reads a named address,
+ * every named address gets a fresh identity, later operations of the bank are ordered behind the launch.  The integers must stay alive
+ * until the bank has been synchronised.
+ * Checked for the whole list before anything is enqueued, a refused call changes no target.  FHERAM_ERR_INVALID_ARG: null items, n outside
+ * [1, FHERAM_DERIVE_LIST_MAX], an unknown kind, a null or foreign integer or target, sign != 0 on a selector item, field != 0 on a
+ * non-FIELD item, first_bit < 0 or the item's bits beyond the integer's width, an address or plain selector named twice, SELECTOR naming
+ * a field selector or FIELD a plain one, field outside the selector's digits, a field selector of which the call names some digits but not
+ * all or one digit twice, more than FHERAM_DERIVE_LIST_DIGITS_MAX digits in total.  FHERAM_ERR_UNSUPPORTED: an address plan of more
+ * than 8 digits (as fheram_address_derive). */
+enum { FHERAM_DERIVE_ADDRESS = 0,    /* target: fheram_addr*     — all digits of the bank's address plan from bits [first_bit, ..) of fu */
+       FHERAM_DERIVE_SELECTOR = 1,   /* target: fheram_selector* — a plain selector's digits from bits [first_bit, first_bit + bits)     */
+       FHERAM_DERIVE_FIELD = 2 };    /* target: fheram_selector* — digit `field` of a field selector from bits [first_bit, + widths[field]) */
+typedef struct fheram_derive_item {
+    int32_t kind, first_bit;
+    int32_t sign;    /* ADDRESS: as fheram_address_derive; otherwise must be 0 (selectors are X^-v) */
+    int32_t field;   /* FIELD: the digit; otherwise must be 0 */
+    const fheram_fheuint* fu;
+    void* target;
+} fheram_derive_item;                       /* 32 bytes */
+#define FHERAM_DERIVE_LIST_MAX 32           /* items per call */
+#define FHERAM_DERIVE_LIST_DIGITS_MAX 64    /* digits over all items of a call (each is 6 workgroups) */
+int fheram_bank_derive_list(fheram_bank* bank, const fheram_derive_item* items, int n);
+/* the std-form digits of a bank address, [n_digits][fheram_ggsw_len]: the bank form of fheram_address_download (refuses an empty address) */
+int fheram_bank_address_download(fheram_bank* bank, const fheram_addr* addr, int64_t* out);
+
 /* ---- Measurement hooks (bench.py).  HIP events recorded on the context's own stream. */
 int fheram_timer_begin(fheram_ctx* ctx);
 int fheram_timer_end(fheram_ctx* ctx, float* elapsed_ms);
