@@ -228,6 +228,7 @@ _SYMBOLS = [
     ("fheram_bank_profile_reset", C.c_int, [C.c_void_p]),
     ("fheram_selftest_convolve", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int]),
     ("fheram_selftest_convolve_rounded", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_double]),
+    ("fheram_selftest_limb_forms", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 ]
 
 
@@ -1312,6 +1313,17 @@ class Ram:
         out = np.zeros((2, self.params.n()), dtype=np.float64)
         ip = lambda v: v.ctypes.data_as(C.POINTER(C.c_int32))   # noqa: E731
         self._chk(library().fheram_selftest_convolve_rounded(self._h, a.shape[0], ip(a), ip(g), out.ctypes.data_as(C.POINTER(C.c_double)), float(operand_scale)))
+        return out
+
+    # -- self-test of the limb arithmetic (tests/test_gpu_limb_forms.py)
+    LIMB_FORM_IN, LIMB_FORM_OUT = 10, 6
+
+    def selftest_limb_forms(self, form: int, inputs):
+        """one coefficient of limb form `form` (csrc/limb_forms_eval.hpp) per row of `inputs` [n][10] (exact integers as doubles): -> [n][6]"""
+        inputs = np.ascontiguousarray(inputs, dtype=np.float64).reshape(-1, self.LIMB_FORM_IN)
+        out = np.zeros((inputs.shape[0], self.LIMB_FORM_OUT), dtype=np.float64)
+        dp = lambda v: v.ctypes.data_as(C.POINTER(C.c_double))   # noqa: E731
+        self._chk(library().fheram_selftest_limb_forms(self._h, int(form), inputs.shape[0], dp(inputs), dp(out)))
         return out
 
     def bench_chain(self, kind: int, batch: int, n: int, iters: int) -> float:

@@ -46,16 +46,8 @@ __device__ __forceinline__ void cmux_step(int32_t* acc, const double* __restrict
             int32_t* op = acc + glwe_off(j < SA ? j : 0, co);
 #pragma unroll
             for (int k = 0; k < E; k++) {
-                const double v = a[0][k] + (double)carry[k];
-                const double cy = carry_of(v);
-                carry[k] = (int)cy;
-                if (j < SA) {   // (workgroup uniform) row <- normalize(row + product), limb j
-                    const int ev = (int)digit_of(v, cy);
-                    const double v2 = (double)(op[tid + T * k] + ev) + (double)carry2[k];
-                    const double c2 = carry_of(v2);
-                    carry2[k] = (int)c2;
-                    op[tid + T * k] = (int)digit_of(v2, c2);
-                }
+                const double ed = cmux_product_digit(a[0][k], carry[k]);
+                if (j < SA) op[tid + T * k] = cmux_row_digit(op[tid + T * k], (int)ed, carry2[k]);   // (workgroup uniform) row <- normalize(row + product), limb j
             }
         }
     }

@@ -31,6 +31,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
+#include "limb_forms.hpp"   // the base-2^17 limb arithmetic (carry_of, digit_of, normalize_coeff, digit17, rsh1_coeff, ...): one text for host and device
 
 namespace fk {
 
@@ -575,48 +576,6 @@ __device__ __forceinline__ void twiddles_commit(const TwRegs& r, double* tw_lds,
 #pragma unroll
     for (int k = 0; k < E; k++) tw_lds[tid + T * k] = (k == 0 && tid == 1) ? 0.0 : r.v[k];   // (see load_twiddles)
     __syncthreads();
-}
-
-// ---- base-2^17 limb arithmetic on exact-integer doubles ------------------
-constexpr int BASE2K = 17;
-constexpr double TWO_B = 131072.0;         // 2^17
-constexpr double INV_TWO_B = 1.0 / 131072.0;
-
-// carry(x) = floor((x + 2^16) / 2^17);  digit(x) = x - carry*2^17 in [-2^16, 2^16)
-__device__ __forceinline__ double carry_of(double x) { return __builtin_floor(__builtin_fma(x, INV_TWO_B, 0.5)); }
-__device__ __forceinline__ double digit_of(double x, double c) { return __builtin_fma(-c, TWO_B, x); }
-
-// vec_znx_big_normalize for one coefficient: in[0..SI) -> out[0..SO), SI >= SO.
-template <int SI, int SO>
-__device__ __forceinline__ void normalize_coeff(const double (&in)[SI], double (&out)[SO]) {
-    double c = 0.0;
-#pragma unroll
-    for (int j = SI - 1; j >= 0; j--) {
-        const double v = in[j] + c;
-        c = carry_of(v);
-        if (j < SO) out[j] = digit_of(v, c);
-    }
-}
-
-// integer digit helpers (int32 is enough: all operands are sums of a few 17-bit digits)
-__device__ __forceinline__ int digit17(int v) { return (int)((unsigned)v << 15) >> 15; }
-
-// vec_znx_rsh_inplace(k = 1) on one coefficient of S limbs (see oracle/znx.hpp rsh_inplace):
-// shift by one limb, then normalise with lsh = 16.
-template <int S>
-__device__ __forceinline__ void rsh1_coeff(const int (&x)[S], int (&y)[S]) {
-    int d = -(x[S - 1] & 1);
-    int c = (x[S - 1] - d) >> 1;
-#pragma unroll
-    for (int j = S - 1; j >= 1; j--) {
-        const int src = x[j - 1];
-        d = -(src & 1);
-        const int cr = (src - d) >> 1;
-        const int dpc = d * 65536 + c;
-        y[j] = digit17(dpc);
-        c = cr + ((dpc - y[j]) >> 17);
-    }
-    y[0] = digit17(c);
 }
 
 }  // namespace fk

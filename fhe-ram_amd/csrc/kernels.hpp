@@ -996,14 +996,7 @@ __global__ __launch_bounds__(T, T / 256) void k_keyswitch(KsArgs ka) {
 //   IN_Y  : the input is in that form (else: an int32 GLWE, read rotated by X^-rho, write path ram.rs:621,629)
 //   OUT_Y : the output is written in that form (else: an int32 GLWE)
 // ---------------------------------------------------------------------------------------
-constexpr double TWO_2B = 17179869184.0;   // 2^34
-// c = q * 2^17 + d with d in [-2^16, 2^16): returns d, leaves q in c
-__device__ __forceinline__ double take_digit(double& c) {
-    const double q = carry_of(c);
-    const double d = digit_of(c, q);
-    c = q;
-    return d;
-}
+// (TWO_2B, take_digit, whole3, ceil_half, y_of3, digits3, digit3_r: limb_forms.hpp)
 
 // ---------------------------------------------------------------------------------------
 // ks_trace_z (round 4): the same trace step with the normalisation in CLOSED FORM — one accumulator per coefficient and
@@ -1028,23 +1021,15 @@ __device__ __forceinline__ double take_digit(double& c) {
 // barriers and LDS round trips as the three forward transforms always did, and (iv, round 5) a second accumulator pair and two operand
 // register sets: the operand stream runs under the transforms (ks_trace_l).
 // ---------------------------------------------------------------------------------------
-constexpr double TWO_51 = 2251799813685248.0;          // 2^51
-constexpr double INV_TWO_51 = 1.0 / 2251799813685248.0;
-constexpr double INV_TWO_2B = 1.0 / 17179869184.0;      // 2^-34
-constexpr double WIN_C = 65536.0 + 8589934592.0 + 1125899906842624.0;   // 2^16 + 2^33 + 2^50
-// centred remainder of x modulo 2^17 / 2^34 (x an exact integer)
-__device__ __forceinline__ double cmod17(double x) { return __builtin_fma(-__builtin_floor(__builtin_fma(x, INV_TWO_B, 0.5)), TWO_B, x); }
-__device__ __forceinline__ double cmod34(double x) { return __builtin_fma(-__builtin_floor(__builtin_fma(x, INV_TWO_2B, 0.5)), TWO_2B, x); }
-// V -> the integer whose balanced base-2^17 digits are the three output limbs (top carry dropped)
-__device__ __forceinline__ double window51(double v) { return __builtin_fma(-__builtin_floor(__builtin_fma(v, INV_TWO_51, WIN_C * INV_TWO_51)), TWO_51, v); }
+// (the constants, cmod17, cmod34, window51 and the per-coefficient fold_limb_1: limb_forms.hpp)
 // adds output limb j's contribution to V (SO = 3 output limbs; limbs j >= 3 go through the extra-carry e first)
 template <int SK>
 __device__ __forceinline__ void fold_limb(double (&od)[E], double (&ec)[E], const double (&acc)[E], int j) {
-    // (j is wave uniform: one scalar branch per limb, not per coefficient)
+    // (j is wave uniform: one scalar branch per limb, not per coefficient; E-wide, branch by branch, what fold_limb_1 — limb_forms.hpp — does for one)
     if (j >= 3) {
         if (SK >= 5 && j < SK - 1) {
 #pragma unroll
-            for (int k = 0; k < E; k++) ec[k] = carry_of(acc[k] + ec[k]);
+            for (int k = 0; k < E; k++) ec[k] = fold_extra_carry(acc[k], ec[k]);
         } else {
 #pragma unroll
             for (int k = 0; k < E; k++) ec[k] = carry_of(acc[k]);
@@ -1058,10 +1043,10 @@ __device__ __forceinline__ void fold_limb(double (&od)[E], double (&ec)[E], cons
         for (int k = 0; k < E; k++) od[k] += acc[k];
     } else if (j == 1) {
 #pragma unroll
-        for (int k = 0; k < E; k++) od[k] = __builtin_fma(cmod34(acc[k]), TWO_B, od[k]);
+        for (int k = 0; k < E; k++) od[k] = fold_limb1(od[k], acc[k]);
     } else {
 #pragma unroll
-        for (int k = 0; k < E; k++) od[k] = __builtin_fma(cmod17(acc[k]), TWO_2B, od[k]);
+        for (int k = 0; k < E; k++) od[k] = fold_limb0(od[k], acc[k]);
     }
 }
 // for 4 limbs the extra carry lives inside the call for limb 3: no state between limbs (16 registers that stay free)
@@ -1105,9 +1090,7 @@ __device__ __forceinline__ void ks_trace_l(const KsArgs& ka, double* lds, bool l
     const int sstep = (T * ka.ginv) & (2 * N - 1);
 
     auto y_of = [](const RawX<KS_TRACE, SX>& r) {
-        double a_ = __builtin_fma(__builtin_fma((double)r.a[0], TWO_B, (double)r.a[1]), TWO_B, (double)r.a[2]);
-        a_ = r.neg ? -a_ : a_;                                       // the rotation's sign comes before the shift
-        return __builtin_floor(__builtin_fma(a_, 0.5, 0.5));        // ceil(A / 2)
+        return y_of3(r.a[0], r.a[1], r.a[2], r.neg);   // ceil(+-A / 2): the rotation's sign comes before the shift
     };
     auto load_column = [&](int col, double (&y)[E]) {
         if constexpr (IN_Y) {
@@ -1147,12 +1130,11 @@ __device__ __forceinline__ void ks_trace_l(const KsArgs& ka, double* lds, bool l
 #pragma unroll
         for (int k = 0; k < E; k++) {
             const bool ng = sidx >= N;
-            double c = stage2[sidx & (N - 1)];
-            const double d2 = take_digit(c);
-            const double d1 = take_digit(c);
+            double d0, d1, d2;
+            digits3(stage2[sidx & (N - 1)], d0, d1, d2);
             xh[2][k] = ng ? -d2 : d2;
             xh[1][k] = ng ? -d1 : d1;
-            xh[0][k] = ng ? -c : c;
+            xh[0][k] = ng ? -d0 : d0;
             sidx = (sidx + sstep) & (2 * N - 1);
         }
     }
@@ -1341,19 +1323,19 @@ __device__ __forceinline__ void ks_trace_l(const KsArgs& ka, double* lds, bool l
                     const double l0 = (double)gload_i32(q + glwe_off(0, co), (unsigned)(tid + T * k) * 4u);
                     const double l1 = (double)gload_i32(q + glwe_off(1, co), (unsigned)(tid + T * k) * 4u);
                     const double l2 = (double)gload_i32(q + glwe_off(2, co), (unsigned)(tid + T * k) * 4u);
-                    return __builtin_fma(__builtin_fma(l0, TWO_B, l1), TWO_B, l2);
+                    return whole3(l0, l1, l2);
                 };
-                const double an = window51(whole(hp) - whole(tp) + a_);
+                const double an = write_post(whole(hp), whole(tp), a_);
                 if (co == 1) y1n[k] = an; else vc[k] = an;
             } else if constexpr (OUT_Y) {
-                const double yn = __builtin_floor(__builtin_fma(a_, 0.5, 0.5));
+                const double yn = ceil_half(a_);
                 if (co == 1) y1n[k] = yn; else vc[k] = yn;      // nothing goes to global memory between the steps of a chain
             } else {
-                const double d2 = take_digit(a_);
-                const double d1 = take_digit(a_);
+                double d0, d1, d2;
+                digits3(a_, d0, d1, d2);
                 gstore_i32(op + glwe_off(2, co), (unsigned)(tid + T * k) * 4u, (int)d2);
                 gstore_i32(op + glwe_off(1, co), (unsigned)(tid + T * k) * 4u, (int)d1);
-                gstore_i32(op + glwe_off(0, co), (unsigned)(tid + T * k) * 4u, (int)a_);
+                gstore_i32(op + glwe_off(0, co), (unsigned)(tid + T * k) * 4u, (int)d0);
             }
         }
     }
@@ -1391,10 +1373,7 @@ __device__ __forceinline__ void ep_step_r(GlweRef a, GlweRef res, const double* 
     auto digits_of = [&](const double (&av)[E], double (&x)[SA][E]) {
 #pragma unroll
         for (int k = 0; k < E; k++) {
-            double c = av[k];
-            x[2][k] = take_digit(c);
-            x[1][k] = take_digit(c);
-            x[0][k] = c;            // A lies in the digit window: the second quotient IS the top digit
+            digits3(av[k], x[0][k], x[1][k], x[2][k]);   // A lies in the digit window: the second quotient IS the top digit
         }
     };
     auto load_limbs = [&](int col, double (&x)[SA][E]) {
@@ -1537,21 +1516,21 @@ __device__ __forceinline__ void ep_step_r(GlweRef a, GlweRef res, const double* 
                 // to a trace step: Y = ceil(A / 2); the mask column (first) into buffer 2 in natural order — the inverse transforms
                 // leave that buffer alone, every wave is through the forward transforms, nobody parks in this step, and the barriers
                 // of the other column's transforms publish it —, the body column (last) in registers
-                const double yn = __builtin_floor(__builtin_fma(a_, 0.5, 0.5));
+                const double yn = ceil_half(a_);
                 if (co == 1) data[2 * LDS_DATA + tid + T * k] = yn; else ac[k] = yn;
                 if (store_i32) {
-                    const double d2 = take_digit(a_);
-                    const double d1 = take_digit(a_);
+                    double d0, d1, d2;
+                    digits3(a_, d0, d1, d2);
                     gstore_i32(rp + glwe_off(2, co), (unsigned)(tid + T * k) * 4u, (int)d2);
                     gstore_i32(rp + glwe_off(1, co), (unsigned)(tid + T * k) * 4u, (int)d1);
-                    gstore_i32(rp + glwe_off(0, co), (unsigned)(tid + T * k) * 4u, (int)a_);
+                    gstore_i32(rp + glwe_off(0, co), (unsigned)(tid + T * k) * 4u, (int)d0);
                 }
             } else {
-                const double d2 = take_digit(a_);
-                const double d1 = take_digit(a_);
+                double d0, d1, d2;
+                digits3(a_, d0, d1, d2);
                 gstore_i32(rp + glwe_off(2, co), (unsigned)(tid + T * k) * 4u, (int)d2);
                 gstore_i32(rp + glwe_off(1, co), (unsigned)(tid + T * k) * 4u, (int)d1);
-                gstore_i32(rp + glwe_off(0, co), (unsigned)(tid + T * k) * 4u, (int)a_);
+                gstore_i32(rp + glwe_off(0, co), (unsigned)(tid + T * k) * 4u, (int)d0);
             }
         }
     }
@@ -1646,9 +1625,9 @@ __global__ __launch_bounds__(T, T / 256) __attribute__((amdgpu_num_vgpr(FK_CHAIN
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int k = 0; k < E; k++) {
-            const double va = __builtin_fma(__builtin_fma((double)rw[k].a[0], TWO_B, (double)rw[k].a[1]), TWO_B, (double)rw[k].a[2]);
+            const double va = whole3(rw[k].a[0], rw[k].a[1], rw[k].a[2]);
             aa[k] = rw[k].neg ? -va : va;
-            ab[k] = __builtin_fma(__builtin_fma((double)rw[k].b[0], TWO_B, (double)rw[k].b[1]), TWO_B, (double)rw[k].b[2]);
+            ab[k] = whole3(rw[k].b[0], rw[k].b[1], rw[k].b[2]);
         }
     };
     double u[E];        // window51(Yu) of this column
@@ -1657,15 +1636,15 @@ __global__ __launch_bounds__(T, T / 256) __attribute__((amdgpu_num_vgpr(FK_CHAIN
         load_ab(1, aa, ab);
 #pragma unroll
         for (int k = 0; k < E; k++) {
-            mstage[tid + T * k] = __builtin_floor(__builtin_fma(aa[k] - ab[k], 0.5, 0.5));
-            if (co == 1) u[k] = window51(__builtin_floor(__builtin_fma(aa[k] + ab[k], 0.5, 0.5)));
+            mstage[tid + T * k] = ceil_half(aa[k] - ab[k]);
+            if (co == 1) u[k] = pair_sum(aa[k], ab[k]);
         }
         if (co == 0) {
             load_ab(0, aa, ab);
 #pragma unroll
             for (int k = 0; k < E; k++) {
-                bstage[tid + T * k] = window51(__builtin_floor(__builtin_fma(aa[k] - ab[k], 0.5, 0.5)));
-                u[k] = window51(__builtin_floor(__builtin_fma(aa[k] + ab[k], 0.5, 0.5)));
+                bstage[tid + T * k] = pair_diff(aa[k], ab[k]);
+                u[k] = pair_sum(aa[k], ab[k]);
             }
         }
     }
@@ -1677,10 +1656,8 @@ __global__ __launch_bounds__(T, T / 256) __attribute__((amdgpu_num_vgpr(FK_CHAIN
 #pragma unroll
         for (int k = 0; k < E; k++) {
             const bool ng = sidx >= N;
-            double c = mstage[sidx & (N - 1)];
-            const double d2 = take_digit(c);
-            const double d1 = take_digit(c);
-            const double d0 = cmod17(c);         // the limbs' top digit is wrapped (|Yx| reaches 2^50: the quotient can be +-2^16)
+            double d0, d1, d2;
+            digits3_wrapped(mstage[sidx & (N - 1)], d0, d1, d2);   // the limbs' top digit is wrapped (|Yx| reaches 2^50: the quotient can be +-2^16)
             xh[2][k] = ng ? -d2 : d2;
             xh[1][k] = ng ? -d1 : d1;
             xh[0][k] = ng ? -d0 : d0;
@@ -1730,15 +1707,14 @@ __global__ __launch_bounds__(T, T / 256) __attribute__((amdgpu_num_vgpr(FK_CHAIN
     }
 #pragma unroll
     for (int k = 0; k < E; k++) {
-        double r_ = window51(u[k] - window51(od[k]));
-        const double d2 = take_digit(r_);
-        const double d1 = take_digit(r_);
+        double d0, d1, d2;
+        digits3(pair_out(u[k], od[k]), d0, d1, d2);
         int dst = tid + T * k + ka.t;
         const bool ng = dst >= N;
         if (ng) dst -= N;
         gstore_i32(op + glwe_off(2, co), (unsigned)dst * 4u, cneg((int)d2, ng));
         gstore_i32(op + glwe_off(1, co), (unsigned)dst * 4u, cneg((int)d1, ng));
-        gstore_i32(op + glwe_off(0, co), (unsigned)dst * 4u, cneg((int)r_, ng));
+        gstore_i32(op + glwe_off(0, co), (unsigned)dst * 4u, cneg((int)d0, ng));
     }
 }
 
@@ -2399,6 +2375,7 @@ __global__ __launch_bounds__(T, T / 256) void k_chain_mid(MidArgs ma) {
             a = neg ? -a : a;
             return __builtin_floor(__builtin_fma(a, 0.5, 0.5));
         };
+        // (raw_double is whole3 / y_of3 and digit_r is digit3_r of limb_forms.hpp, typed out: calling them changes this kernel's device code)
         // digit r of c (c = the one-double form): digits leave from the least significant end
         auto digit_r = [&](double c) -> double {
             double d = take_digit(c);

@@ -5,8 +5,14 @@
 // inverse transform ends with on the path — so the host can compare them with exact integer arithmetic and report the
 // round-off that the rounding has to absorb (< 1/2 is correctness; the measured margin is what the test pins).
 // Nothing on the RAM path calls this entry point.
+//
+// The limb half of the exactness contract has its own entry point: fheram_selftest_limb_forms runs limb_form_eval
+// (limb_forms_eval.hpp) — the scalar forms of limb_forms.hpp that the kernels call, compiled with the library's own flags —
+// on one coefficient per thread, and tests/test_gpu_limb_forms.py compares the outputs with exact integers and, bit for bit,
+// with a host build of the same text.
 #pragma once
 #include "ctx.hpp"
+#include "limb_forms_eval.hpp"
 
 namespace fk {
 
@@ -69,9 +75,39 @@ __global__ __launch_bounds__(T) void k_selftest_convolve(const int32_t* __restri
         for (int k = 0; k < E; k++) out[(long)b * N + tid + T * k] = acc[b][k];
 }
 
+// one coefficient of `form` per thread: in [n][LF_IN], out [n][LF_OUT]
+__global__ __launch_bounds__(256) void k_selftest_limb_forms(int form, int n, const double* __restrict__ in, double* __restrict__ out) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double o[LF_OUT];
+#pragma unroll
+    for (int q = 0; q < LF_OUT; q++) o[q] = 0.0;
+    limb_form_eval(form, in + i * LF_IN, o);
+#pragma unroll
+    for (int q = 0; q < LF_OUT; q++) out[i * LF_OUT + q] = o[q];
+}
+
 }  // namespace fk
 
 extern "C" {
+
+int fheram_selftest_limb_forms(fheram_ctx* c, int form, int n, const double* in, double* out) {
+    if (!c || form < 0 || form >= fk::LF_FORMS || n <= 0 || n > (1 << 20) || !in || !out) return fail(c, FHERAM_ERR_INVALID_ARG, "bad argument (form: see limb_forms_eval.hpp; n <= 2^20)");
+    HIPCHK(c, hipSetDevice(c->device));
+    double* d = nullptr;
+    const size_t ni = (size_t)n * fk::LF_IN, no = (size_t)n * fk::LF_OUT;
+    HIPCHK(c, hipMalloc(&d, (ni + no) * sizeof(double)));
+    hipError_t e = hipMemcpy(d, in, ni * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(fk::k_selftest_limb_forms, dim3((n + 255) / 256), dim3(256), 0, c->stream, form, n, d, d + ni);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(out, d + ni, no * sizeof(double), hipMemcpyDeviceToHost);
+    hipFree(d);
+    if (e != hipSuccess) return fail(c, FHERAM_ERR_DEVICE, std::string("selftest: ") + hipGetErrorString(e));
+    return FHERAM_OK;
+}
 
 namespace {
 int selftest_run(fheram_ctx* c, int n_terms, const int32_t* a, const int32_t* g, double* out, int singles, bool rounded, double scale);

@@ -669,6 +669,11 @@ int fheram_selftest_convolve(fheram_ctx* ctx, int n_terms, const int32_t* a, con
  * sums.  operand_scale multiplies the prepared operands (1.0: the path's arithmetic; 0.5 makes every odd sum a half-integer,
  * which is how tests/test_gpu_fft.py drives the monitor over its limit and checks FHERAM_ERR_PRECISION). */
 int fheram_selftest_convolve_rounded(fheram_ctx* ctx, int n_terms, const int32_t* a, const int32_t* g, double* out, double operand_scale);
+/* Self-test of the limb arithmetic (csrc/limb_forms.hpp: the limb walk, rsh(1) and the closed-form normalisation of the chain
+ * kernels, as the scalar functions the kernels call).  One coefficient of `form` (csrc/limb_forms_eval.hpp: LimbForm, 0..13)
+ * per thread: in[n][10] and out[n][6] doubles holding exact integers, n <= 2^20; outputs a form does not produce are 0.
+ * The caller compares with exact integer arithmetic (tests/test_gpu_limb_forms.py).  Not on the RAM path. */
+int fheram_selftest_limb_forms(fheram_ctx* ctx, int form, int n, const double* in, double* out);
 
 #ifdef __cplusplus
 }

@@ -277,9 +277,10 @@ def test_rsh1_closed_form(po):
     """vec_znx_rsh(1) (oracle/znx.hpp rsh_inplace; GLWE::trace / GLWEPacker, ram.rs:435,457) equals the centred base-2^17
     digits of ceil(A / 2), A = a_0*2^34 + a_1*2^17 + a_2 — the form the HIP trace chains hand their intermediate
     ciphertexts over in (csrc/kernels.hpp ks_trace_y).  Every floating-point operation of that form is exact (powers of
-    two, +0.5, floor, differences of exact values), so numpy float64 reproduces the device arithmetic; compared digit for
-    digit with the oracle on random limbs and on the extremes (+-2^16, the un-normalised +2^16 a rotation's negation
-    produces, odd / even tails)."""
+    two, +0.5, floor, differences of exact values); compared digit for digit with the oracle on random limbs and on the
+    extremes (+-2^16, the un-normalised +2^16 a rotation's negation produces, odd / even tails).  This checks the FORMULA, restated
+    in numpy; the device text (csrc/limb_forms.hpp rsh1_coeff, y_of3, digits3_wrapped) is checked by tests/test_limb_forms.py (host
+    build) and tests/test_gpu_limb_forms.py (device build) against exact integers."""
     o = po.Oracle(po.OParams(log_n=4, max_addr=16, decomp_n=[2, 2]))
     n, B = 16, 2.0 ** 17
     rng = np.random.default_rng(1)
@@ -345,7 +346,8 @@ def _digits(a):
 def test_closed_form_normalisation_of_big_limbs(po):
     """vec_znx_big_normalize of SK un-normalised limbs into 3 digits (4 -> 3 and 5 -> 3: the trace keys of both parameter blocks; the
     external product's 4 -> 3) equals the digits of window51(e + big_2 + cmod34(big_1) 2^17 + cmod17(big_0) 2^34) with e the rounded carry
-    of the extra limbs: random limbs up to the worst-case magnitude 2^47, values on rounding ties, all-extreme limbs."""
+    of the extra limbs: random limbs up to the worst-case magnitude 2^47, values on rounding ties, all-extreme limbs.  The formula, restated
+    in numpy; the device text (csrc/limb_forms.hpp fold_limb_1, window51) is checked by tests/test_limb_forms.py and tests/test_gpu_limb_forms.py."""
     o = po.Oracle(po.OParams(log_n=4, max_addr=16, decomp_n=[2, 2]))
     n = 16
     rng = np.random.default_rng(4)
@@ -373,7 +375,8 @@ def test_closed_form_normalisation_of_big_limbs(po):
 
 def test_closed_form_trace_step_post_step(po):
     """The post-step of a trace step, a <- rsh1(a) + phi(KS(rsh1(a))) normalised (ram.rs:457,514,616): limbs of rsh1(a) added to the big
-    limbs, normalised limb by limb by the oracle, against window51(Y + e + big_2 + ...) with Y = ceil(A / 2) (ks_trace_z)."""
+    limbs, normalised limb by limb by the oracle, against window51(Y + e + big_2 + ...) with Y = ceil(A / 2) (ks_trace_z).  The formula, restated
+    in numpy; the device text (csrc/limb_forms.hpp: the CLOSED forms) is checked by tests/test_limb_forms.py and tests/test_gpu_limb_forms.py."""
     o = po.Oracle(po.OParams(log_n=4, max_addr=16, decomp_n=[2, 2]))
     n = 16
     rng = np.random.default_rng(5)
@@ -399,7 +402,8 @@ def test_closed_form_trace_step_post_step(po):
 def test_closed_form_pair_combine_and_write_elementwise(po):
     """k_pair_z: rsh1 of a limb-wise SUM / DIFFERENCE of two ciphertexts (un-normalised limbs up to +-2^17) equals the digits of
     window51(ceil((A(a) +- A(b)) / 2)), and normalize(u - tmp) of two normalised limb vectors equals the digits of window51(U - T);
-    k_write_chain: normalize(h - t + b) equals the digits of window51(A(h) - A(t) + A(b)) (ram.rs:617,625-626)."""
+    k_write_chain: normalize(h - t + b) equals the digits of window51(A(h) - A(t) + A(b)) (ram.rs:617,625-626).  The formulas, restated in numpy;
+    the device text (csrc/limb_forms.hpp pair_sum, pair_diff, pair_out, write_post) is checked by tests/test_limb_forms.py and tests/test_gpu_limb_forms.py."""
     o = po.Oracle(po.OParams(log_n=4, max_addr=16, decomp_n=[2, 2]))
     n = 16
     rng = np.random.default_rng(6)
