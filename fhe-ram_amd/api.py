@@ -32,6 +32,7 @@ DERIVE_MAX = 8       # FHERAM_DERIVE_MAX
 SELECT_BITS_MAX = 5  # FHERAM_SELECT_BITS_MAX
 SELECT_MAX = 8       # FHERAM_SELECT_MAX
 SRC_ZERO, SRC_HOST, SRC_MEMBER_RESULT, SRC_LIST_RESULT, SRC_SELECT_RESULT = 0, 1, 2, 3, 4   # FHERAM_SRC_*
+SRC_REGS_RESULT, SRC_REGS_OLD = 5, 6   # FHERAM_SRC_REGS_RESULT / _REGS_OLD: a bank's register files
 SELECT_FIELDS_MAX = 5   # FHERAM_SELECT_FIELDS_MAX
 DERIVE_LIST_MAX = 32          # FHERAM_DERIVE_LIST_MAX
 DERIVE_LIST_DIGITS_MAX = 64   # FHERAM_DERIVE_LIST_DIGITS_MAX
@@ -166,6 +167,18 @@ _SYMBOLS = [
     ("fheram_bank_select_result", C.c_int, [C.c_void_p, C.c_int, C.c_int, I64P]),
     ("fheram_bank_write_list_selected", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int)]),
     ("fheram_bank_selftest_fail_select_alloc", C.c_int, [C.c_void_p, C.c_int]),
+    ("fheram_bank_regs_create", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    ("fheram_regs_destroy", None, [C.c_void_p]),
+    ("fheram_regs_bits", C.c_int, [C.c_void_p]),
+    ("fheram_bank_regs_state", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("fheram_bank_regs_upload", C.c_int, [C.c_void_p, C.c_void_p, I64P]),
+    ("fheram_bank_regs_download", C.c_int, [C.c_void_p, C.c_void_p, I64P]),
+    ("fheram_bank_regs_pack", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(_CSelectSrc), I64P]),
+    ("fheram_bank_regs_read", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int, I64P]),
+    ("fheram_bank_regs_result", C.c_int, [C.c_void_p, C.c_int, C.c_int, I64P]),
+    ("fheram_bank_regs_read_prepare_write", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, I64P]),
+    ("fheram_bank_regs_old_result", C.c_int, [C.c_void_p, I64P]),
+    ("fheram_bank_regs_write", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _CSelectSrc, I64P]),
     ("fheram_timer_begin", C.c_int, [C.c_void_p]),
     ("fheram_timer_end", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("fheram_profile_enable", C.c_int, [C.c_void_p, C.c_int]),
@@ -665,6 +678,16 @@ class Src:
         """output k of the previous select"""
         return cls(SRC_SELECT_RESULT, k)
 
+    @classmethod
+    def regs(cls, k: int):
+        """output k of the bank's last RegFile.read"""
+        return cls(SRC_REGS_RESULT, k)
+
+    @classmethod
+    def regs_old(cls):
+        """the result of the bank's last RegFile.read_prepare_write: the word the pending register write replaces"""
+        return cls(SRC_REGS_OLD, 0)
+
 
 class Lane:
     """One byte ciphertext of a lane-mapped candidate of RamBank.select_lanes (fheram_select_lane): GLWE `lane` of the word a Src would
@@ -706,6 +729,16 @@ class Lane:
     def select(cls, k: int, lane: int):
         """GLWE `lane` of output k of the previous select"""
         return cls(SRC_SELECT_RESULT, k, lane)
+
+    @classmethod
+    def regs(cls, k: int, lane: int):
+        """GLWE `lane` of output k of the bank's last RegFile.read"""
+        return cls(SRC_REGS_RESULT, k, lane)
+
+    @classmethod
+    def regs_old(cls, lane: int):
+        """GLWE `lane` of the result of the bank's last RegFile.read_prepare_write"""
+        return cls(SRC_REGS_OLD, 0, lane)
 
     @classmethod
     def of(cls, src: Src, lane: int):
@@ -811,6 +844,105 @@ class Selector:
         if getattr(self, "_h", None) and _LIB is not None:
             _LIB.fheram_selector_destroy(self._h)
             self._h = None
+
+
+class RegFile:
+    """A register file of a bank (fheram_regs): a one-row RAM of 2^bits words of the bank's word_size that lives beside the members and is
+    read and written by the bank's Selectors.  Made by RamBank.regfile(bits).  load / pack make it readable; read runs several reads as
+    one operation; read_prepare_write and write are the two halves of a register write, whose word comes from any Src."""
+
+    def __init__(self, bank: "RamBank", handle, bits: int):
+        self.bank, self._h, self.bits = bank, handle, int(bits)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _LIB is not None:
+            _LIB.fheram_regs_destroy(self._h)
+            self._h = None
+
+    def _row(self):
+        p = self.bank.params
+        return np.zeros((p.word_size(), p.glwe_len()), dtype=np.int64)
+
+    def _sel(self, sel, what):
+        if not isinstance(sel, Selector):
+            raise FheRamError(1, f"RegFile.{what} takes a Selector")
+        return sel
+
+    def load(self, row: np.ndarray):
+        """row: [word_size][GLWE], Ram::encrypt_sk's output for the one-row RAM of max_addr = 2^bits (fheram_bank_regs_upload)"""
+        row = _i64(row)
+        if row.size != self._row().size:
+            raise FheRamError(1, f"invalid data: expected {self.bank.params.word_size()}x1 GLWE rows (ram.rs:144-155)")
+        self.bank._chk(library().fheram_bank_regs_upload(self.bank._h, self._h, _p(row)))
+
+    def store(self) -> np.ndarray:
+        """the row, [word_size][GLWE] (fheram_bank_regs_download)"""
+        out = self._row()
+        self.bank._chk(library().fheram_bank_regs_download(self.bank._h, self._h, _p(out)))
+        return out
+
+    def pack(self, sources, host_words=None):
+        """row <- the pack of RamBank.select over `sources` (a list of 1..2^bits Src), word j at coefficient j (fheram_bank_regs_pack);
+        [Src.zero()] * 2**bits is the all-zero register file"""
+        sources = list(sources)
+        if not sources or not all(isinstance(s, Src) for s in sources):
+            raise FheRamError(1, "RegFile.pack takes a non-empty list of Src")
+        hw = self.bank._host_words(host_words, [s.index for s in sources if s.kind == SRC_HOST])
+        srcs = (_CSelectSrc * len(sources))(*[_CSelectSrc(s.kind, s.index) for s in sources])
+        self.bank._chk(library().fheram_bank_regs_pack(self.bank._h, self._h, len(sources), srcs, _p(hw) if hw is not None else None))
+
+    def read(self, sels, download: bool = True, keys: Optional["EvaluationKeysPrepared"] = None):
+        """len(sels) reads of the register file as ONE operation (fheram_bank_regs_read): int64 [n][word_size][GLWE]; download=False: no
+        host wait (RamBank.regs_result / RegFile.result later)"""
+        sels = [self._sel(s, "read") for s in sels]
+        n = len(sels)
+        if n < 1:
+            raise FheRamError(1, "RegFile.read takes at least one Selector")
+        if keys is not None:
+            self.bank._use_keys(keys)
+        p = self.bank.params
+        out = np.zeros((n, p.word_size(), p.glwe_len()), dtype=np.int64) if download else None
+        self.bank._chk(library().fheram_bank_regs_read(self.bank._h, self._h, (C.c_void_p * n)(*[s._h for s in sels]), n, _p(out) if download else None))
+        return out
+
+    def result(self, first: int = 0, n: int = 1) -> np.ndarray:
+        """outputs [first, first + n) of the bank's last register read (fheram_bank_regs_result)"""
+        first, n = int(first), int(n)
+        p = self.bank.params
+        out = np.zeros((max(n, 1), p.word_size(), p.glwe_len()), dtype=np.int64)
+        self.bank._chk(library().fheram_bank_regs_result(self.bank._h, first, n, _p(out)))
+        return out
+
+    def read_prepare_write(self, sel, download: bool = True, keys: Optional["EvaluationKeysPrepared"] = None):
+        """the first half of a register write (fheram_bank_regs_read_prepare_write): the OLD word, int64 [word_size][GLWE]; download=False:
+        no host wait (old_result later)"""
+        sel = self._sel(sel, "read_prepare_write")
+        if keys is not None:
+            self.bank._use_keys(keys)
+        out = self._row() if download else None
+        self.bank._chk(library().fheram_bank_regs_read_prepare_write(self.bank._h, self._h, sel._h, _p(out) if download else None))
+        return out
+
+    def old_result(self) -> np.ndarray:
+        """the result of the bank's last register read_prepare_write (fheram_bank_regs_old_result)"""
+        out = self._row()
+        self.bank._chk(library().fheram_bank_regs_old_result(self.bank._h, _p(out)))
+        return out
+
+    def write(self, sel, src, host_words=None, keys: Optional["EvaluationKeysPrepared"] = None):
+        """the second half (fheram_bank_regs_write): the word `src` names (any Src; Src.host(i): slot i of host_words) is written at the
+        index read_prepare_write prepared.  Never waits for the device."""
+        sel = self._sel(sel, "write")
+        if not isinstance(src, Src):
+            raise FheRamError(1, "RegFile.write takes the word as a Src")
+        hw = self.bank._host_words(host_words, [src.index] if src.kind == SRC_HOST else [])
+        if keys is not None:
+            self.bank._use_keys(keys)
+        self.bank._chk(library().fheram_bank_regs_write(self.bank._h, self._h, sel._h, _CSelectSrc(src.kind, src.index), _p(hw) if hw is not None else None))
+
+    def state(self) -> bool:
+        """True between read_prepare_write and write"""
+        return bool(library().fheram_bank_regs_state(self.bank._h, self._h))
 
 
 class _AddrHandle:
@@ -1813,6 +1945,23 @@ class RamBank:
             raise FheRamError(1, f"write_list_selected: {n} members need {n} picks")
         self._use_keys(keys)
         self._chk(library().fheram_bank_write_list_selected(self._h, mem, arr, n, (C.c_int * n)(*picks)))
+
+    # -- register files (include/fheram.h: a one-row RAM read and written by selectors)
+    def regfile(self, bits: int) -> RegFile:
+        """a register file of 2^bits words with every device buffer it will need (fheram_bank_regs_create); RegFile.load / pack fill it"""
+        out = C.c_void_p()
+        self._chk(library().fheram_bank_regs_create(self._h, int(bits), C.byref(out)))
+        return RegFile(self, out.value, bits)
+
+    def _host_words(self, host_words, slots):
+        """host_words as int64, with the named slots inside it"""
+        if host_words is None:
+            return None
+        hw = _i64(host_words)
+        per = self.params.word_size() * self.params.glwe_len()
+        if slots and (min(slots) < 0 or (max(slots) + 1) * per > hw.size):
+            raise FheRamError(1, f"a host source names a slot outside host_words ({hw.size // per} slots of {self.params.word_size()} GLWEs)")
+        return hw
 
     def selftest_fail_select_alloc(self, nth: int):
         """self-test: the nth device allocation the select's buffers ask for from now on fails once (0: none)"""

@@ -32,6 +32,8 @@
 #pragma once
 #include "path.hpp"
 
+struct fheram_regs;   // a register file of the bank (regs.hpp)
+
 struct fheram_bank {
     fheram_ctx* c = nullptr;      // word count M * mws; never row-sharded, never part of a group
     int M = 0, mws = 0;
@@ -50,9 +52,20 @@ struct fheram_bank {
     int sel_n = 0, sel_fail_alloc = 0;   // outputs of the last select (in sel.res; 0: none has run); the self-test's failing allocation, as wl_fail_alloc
     bool has_res[FHERAM_BANK_MAX] = {};  // member m has the result of a read / read_prepare_write in its slot (a select may take it as a candidate)
     int wl_fail_alloc = 0;        // fheram_bank_selftest_fail_list_alloc: the wl_fail_alloc-th next device allocation of wl fails (0: none)
+    // the register files (regs.hpp): what they share, the live ones, the outputs of the last fheram_bank_regs_read (in regs.res; 0: none has
+    // run) and where the last fheram_bank_regs_read_prepare_write left its result (the kept trace of regs_old_owner; nullptr: none has run)
+    RegsBufs regs;
+    std::vector<fheram_regs*> regfiles;
+    int regs_n = 0;
+    const int32_t* regs_old = nullptr;
+    const fheram_regs* regs_old_owner = nullptr;
 };
 
 namespace {
+
+// regs.hpp: new keys void what every register file kept; a destroyed bank takes its register files' device buffers with it
+void regs_keys_changed(fheram_bank* b);
+void regs_bank_release(fheram_bank* b);
 
 static_assert(FHERAM_READ_LIST_MAX >= FHERAM_BANK_MAX && FHERAM_READ_LIST_MAX * 4 <= 32, "a member set has four bits of the map per entry");
 // The members an operation works on, entry by entry: a range [first, first + n), or a list (checked by the caller).
@@ -301,6 +314,7 @@ void fheram_bank_destroy(fheram_bank* b) {
     dense_free(b->wl);
     select_free(b->sel);
     lane_table_free(b->lanes);
+    regs_bank_release(b);
     fheram_ctx_destroy(b->c);
     delete b;
 }
@@ -313,6 +327,7 @@ int fheram_bank_keys_load(fheram_bank* b, const int64_t* gal_els, int n_gal, con
     const int rc = fheram_keys_load(b->c, gal_els, n_gal, atk_glwe, atk_ggsw_inv, atk_ggsw_inv_p, tsk);
     if (rc != FHERAM_OK) return rc;
     for (int m = 0; m < b->M; m++) { b->ram[m].memo_top = false; b->ram[m].memo_alone = 0; b->wl_holds[m] = false; }   // kept traces are void with new keys
+    regs_keys_changed(b);
     return FHERAM_OK;
 }
 int fheram_bank_ram_upload(fheram_bank* b, int member, const int64_t* rows) {

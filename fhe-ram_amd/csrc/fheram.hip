@@ -839,4 +839,5 @@ int fheram_device_info(const fheram_ctx* c, char* name, size_t name_len, int* cu
 #include "group.hpp"
 #include "bank.hpp"
 #include "select.hpp"
+#include "regs.hpp"
 #include "derive_list.hpp"

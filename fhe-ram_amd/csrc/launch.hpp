@@ -558,10 +558,13 @@ void ggsw_inverse(fheram_ctx* c, const int32_t* in, int32_t* tmp, int d, bool be
     KsArgs kt = ks_args(c, ref(tmp, (long)fheram_ctx::GGSW, 2 * g4), ref(tmp, 0, 0), ref(tmp + g4, (long)fheram_ctx::GGSW, 2 * g4), c->d_tsk, 1);
     launch_ks<KS_TENSOR, 4, 5, 4>(c, kt, fheram_ctx::DNUM_CT, d, beside);
 }
-void coordinate_prepare_inv(fheram_ctx* c, const fheram_addr* addr, int ci, int32_t* tmp, double* prep, bool beside = false) {
-    const int d = (int)c->base2d[ci].size();
-    ggsw_inverse(c, addr->d_ggsw + (size_t)coord_first_digit(c, ci) * fheram_ctx::GGSW, tmp, d, beside);
+// of d digits wherever they are (a coordinate of an address; a selector's, regs.hpp)
+void coordinate_prepare_inv(fheram_ctx* c, const int32_t* digits, int d, int32_t* tmp, double* prep, bool beside = false) {
+    ggsw_inverse(c, digits, tmp, d, beside);
     launch_prepare(c, tmp, prep, d * (int)(fheram_ctx::GGSW / N));
+}
+void coordinate_prepare_inv(fheram_ctx* c, const fheram_addr* addr, int ci, int32_t* tmp, double* prep, bool beside = false) {
+    coordinate_prepare_inv(c, addr->d_ggsw + (size_t)coord_first_digit(c, ci) * fheram_ctx::GGSW, (int)c->base2d[ci].size(), tmp, prep, beside);
 }
 
 // read_prepare_write: start the inverse digits of coordinate ci on the side stream (they depend on the address and the

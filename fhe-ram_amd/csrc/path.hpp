@@ -355,6 +355,27 @@ void lane_table_free(SelectLaneTable& L) {
     L = SelectLaneTable{};
 }
 
+// What a bank's register files share (regs.hpp): the buffers of fheram_bank_regs_read — per output ciphertext the fanned-out row, the
+// products' output, a temporary and the result, for REGS_CT_MAX ciphertexts; the prepared digits of its selectors — the pinned result
+// buffer and the staged host words of a pack or a write.  Allocated whole by the bank's first fheram_bank_regs_create, freed with the bank.
+struct RegsBufs {
+    int cap = 0;                                                                  // ciphertexts of a read: min(FHERAM_SELECT_MAX * word_size, 64); 0: not allocated
+    int32_t *fan = nullptr, *ep = nullptr, *tmp = nullptr, *res = nullptr;        // [cap] GLWE
+    double* prep = nullptr;                                                       // [FHERAM_SELECT_MAX * FHERAM_SELECT_BITS_MAX] prepared GGSW: read k's digits at k * n_digits
+    int64_t *h_res = nullptr, *d_h_res = nullptr;                                 // pinned, device-visible: the results as int64 (+ the monitor's maximum)
+    int32_t *d_host = nullptr, *h_host = nullptr;                                 // [2^FHERAM_SELECT_BITS_MAX * word_size] GLWE: host words, device / pinned
+    hipEvent_t ev_host = nullptr;                                                 // the last copy out of h_host
+    bool host_busy = false;
+};
+void regs_bufs_free(RegsBufs& R) {
+    void* bufs[] = {R.fan, R.ep, R.tmp, R.res, R.prep, R.d_host};
+    for (void* p : bufs) if (p) hipFree(p);
+    if (R.h_res) hipHostFree(R.h_res);
+    if (R.h_host) hipHostFree(R.h_host);
+    if (R.ev_host) hipEventDestroy(R.ev_host);
+    R = RegsBufs{};
+}
+
 // The one result export: every run (source, int32 count) is widened by the device into the pinned buffer h (device address d_h), back to
 // back, with the monitor's maximum as it stood then behind the last (the export kernel copies it there); out != nullptr: copied out.
 struct ResRun { const int32_t* src; size_t n; };

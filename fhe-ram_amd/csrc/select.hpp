@@ -123,18 +123,22 @@ int select_reserve(fheram_bank* b, int n_ct, int n_prep, int n_host) {
     return FHERAM_OK;
 }
 
-// where candidate (kind, index) sits on the device: ws GLWEs (nullptr: ZERO)
-const int32_t* select_source(const fheram_bank* b, const fheram_select_src& s) {
+// where candidate (kind, index) sits on the device: ws GLWEs (nullptr: ZERO); d_host: the staged host words (a select's own; a register
+// file's pack and write stage theirs in the register files' buffer)
+const int32_t* select_source(const fheram_bank* b, const fheram_select_src& s, const int32_t* d_host) {
     const fheram_ctx* c = b->c;
     const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
     switch (s.kind) {
-    case FHERAM_SRC_HOST: return b->sel.d_host + (size_t)s.index * per;
+    case FHERAM_SRC_HOST: return d_host + (size_t)s.index * per;
     case FHERAM_SRC_MEMBER_RESULT: return (b->ram[s.index].res_in_trtop ? c->d_trtop : c->d_res) + (size_t)s.index * per;   // (as set_result)
     case FHERAM_SRC_LIST_RESULT: return b->list.res + (size_t)s.index * per;
     case FHERAM_SRC_SELECT_RESULT: return b->sel.res + (size_t)s.index * per;
+    case FHERAM_SRC_REGS_RESULT: return b->regs.res + (size_t)s.index * per;
+    case FHERAM_SRC_REGS_OLD: return b->regs_old;
     default: return nullptr;
     }
 }
+const int32_t* select_source(const fheram_bank* b, const fheram_select_src& s) { return select_source(b, s, b->sel.d_host); }
 
 // GLWE `lane` of that word: what one entry of k_select_pack_lanes' table points to
 const int32_t* select_source_lane(const fheram_bank* b, const fheram_select_lane& l) {
@@ -164,7 +168,7 @@ int select_check_sels(fheram_bank* b, const fheram_selector* const* sels, const 
     }
     return FHERAM_OK;
 }
-struct SelectNeeds { bool list = false, sel = false; };
+struct SelectNeeds { bool list = false, sel = false, regs = false, regs_old = false; };
 // one (kind, index) of a source or a lane
 int select_check_source(fheram_bank* b, int kind, int index, const std::string& who, const int64_t* host_words, SelectNeeds& need) {
     fheram_ctx* c = b->c;
@@ -185,21 +189,32 @@ int select_check_source(fheram_bank* b, int kind, int index, const std::string& 
         if (index < 0 || (b->sel_n && index >= b->sel_n)) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names output " + std::to_string(index) + ", outside the last select's " + std::to_string(b->sel_n) + " outputs");
         need.sel = true;
         break;
+    case FHERAM_SRC_REGS_RESULT:
+        if (index < 0 || (b->regs_n && index >= b->regs_n)) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names output " + std::to_string(index) + ", outside the last register read's " + std::to_string(b->regs_n) + " outputs");
+        need.regs = true;
+        break;
+    case FHERAM_SRC_REGS_OLD:
+        if (index != 0) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names index " + std::to_string(index) + " of the last register read_prepare_write, which has one result: index 0");
+        need.regs_old = true;
+        break;
     default: return fail(c, FHERAM_ERR_INVALID_ARG, who + " has the unknown kind " + std::to_string(kind));
     }
     return FHERAM_OK;
 }
-int select_check_state(fheram_bank* b, const SelectNeeds& need) {
+int select_check_state(fheram_bank* b, const SelectNeeds& need, bool keys = true) {
     fheram_ctx* c = b->c;
-    if (!c->keys_loaded) return fail(c, FHERAM_ERR_KEYS, "evaluation keys not loaded");
+    if (keys && !c->keys_loaded) return fail(c, FHERAM_ERR_KEYS, "evaluation keys not loaded");
     if (need.list && !b->list_n) return fail(c, FHERAM_ERR_STATE, "a source names the last read list and no read list has run on this bank");
     if (need.sel && !b->sel_n) return fail(c, FHERAM_ERR_STATE, "a source names the last select and no select has run on this bank");
+    if (need.regs && !b->regs_n) return fail(c, FHERAM_ERR_STATE, "a source names the last register read and no fheram_bank_regs_read has run on this bank");
+    if (need.regs_old && !b->regs_old) return fail(c, FHERAM_ERR_STATE, "a source names the last register read_prepare_write and none has run on this bank (or its register file is gone)");
     return FHERAM_OK;
 }
-// Behind the pack (S.packed holds n * ws packed rows): the selectors' digits prepared, the products, the trace, the export
-int select_chain(fheram_bank* b, const fheram_selector* const* sels, int n, int64_t* out) {
+// n independent Ram::read of one-row RAMs as one operation, on the caller's buffers (S.packed holds the n * ws rows): the selectors' digits
+// prepared, the products, the trace.  A select's chain (its packed candidates) and a register file's read (the fanned-out row, regs.hpp).
+struct OneRowBufs { int32_t *packed, *ep, *tmp, *res; double* prep; };
+void one_row_reads(fheram_bank* b, const OneRowBufs& S, const fheram_selector* const* sels, int n) {
     fheram_ctx* c = b->c;
-    SelectBufs& S = b->sel;
     const int ws = b->mws, Y = n * ws, d = sels[0]->n_digits;
     const long G = (long)fheram_ctx::GLWE;
     // the selectors' digits, prepared: select k's at k * stride (CoordinatePrepared::prepare, coordinate_prepared.rs:104-116)
@@ -219,6 +234,13 @@ int select_chain(fheram_bank* b, const fheram_selector* const* sels, int n, int6
         products();
         trace_steps(c, ep, res, tmp, 0, LOGN, 1, Y);
     }
+}
+// Behind the pack (S.packed holds n * ws packed rows): that chain, the export
+int select_chain(fheram_bank* b, const fheram_selector* const* sels, int n, int64_t* out) {
+    fheram_ctx* c = b->c;
+    SelectBufs& S = b->sel;
+    const int Y = n * b->mws;
+    one_row_reads(b, OneRowBufs{S.packed, S.ep, S.tmp, S.res, S.prep}, sels, n);
     HIPCHK(c, hipGetLastError());
     b->sel_n = n;
     if (!out) return FHERAM_OK;

@@ -518,6 +518,7 @@ public:
     }
     // ---- oblivious select (include/fheram.h): pick one of the candidate words by an encrypted index, on the device
     // the encrypted index over up to 2^bits candidates: from host std-form GGSW digits (fheram_bank_selector_create), or without digits, for derive_selectors
+    class RegFile;
     class Selector {
     public:
         Selector(Bank& bank, int bits) { bank.chk(fheram_bank_selector_alloc(bank.bank_, bits, &h_)); }
@@ -539,6 +540,7 @@ public:
         int n_digits() const { return fheram_selector_n_digits(h_); }
     private:
         friend class Bank;
+        friend class RegFile;
         fheram_selector* h_ = nullptr;
         size_t fields_ = 0;   // a field selector: its number of fields
     };
@@ -677,6 +679,64 @@ public:
         std::vector<const fheram_addr*> h = handles(addresses);
         chk(fheram_bank_write_list_selected(bank_, members.data(), h.data(), (int)h.size(), picks.data()));
     }
+    // ---- a register file (include/fheram.h): a one-row RAM of 2^bits words beside the members, read and written by the bank's selectors
+    static fheram_select_src src_regs(int output) { return {FHERAM_SRC_REGS_RESULT, output}; }   // output of the bank's last RegFile::read
+    static fheram_select_src src_regs_old() { return {FHERAM_SRC_REGS_OLD, 0}; }                 // the bank's last RegFile::read_prepare_write result
+    class RegFile {
+    public:
+        RegFile(Bank& bank, int bits) : bank_(bank) { bank.chk(fheram_bank_regs_create(bank.bank_, bits, &h_)); }
+        ~RegFile() { if (h_) fheram_regs_destroy(h_); }
+        RegFile(const RegFile&) = delete;
+        int bits() const { return fheram_regs_bits(h_); }
+        bool state() const { return fheram_bank_regs_state(bank_.bank_, h_) != 0; }
+        // row: [word_size][GLWE], Ram::encrypt_sk's output for the one-row RAM of max_addr = 2^bits
+        void load(const std::vector<int64_t>& row) {
+            if (row.size() != bank_.params.word_size() * bank_.glwe_len()) throw Error(FHERAM_ERR_INVALID_ARG, "invalid data: expected word_size x 1 GLWE rows (ram.rs:144-155)");
+            bank_.chk(fheram_bank_regs_upload(bank_.bank_, h_, row.data()));
+        }
+        std::vector<int64_t> store() {
+            std::vector<int64_t> row(bank_.params.word_size() * bank_.glwe_len());
+            bank_.chk(fheram_bank_regs_download(bank_.bank_, h_, row.data()));
+            return row;
+        }
+        // row <- the pack of Bank::select over `sources`, word j at coefficient j
+        void pack(const std::vector<fheram_select_src>& sources, const std::vector<std::vector<Glwe>>& host_words = {}) {
+            const std::vector<int64_t> flat = bank_.flat_words(sources, host_words);
+            bank_.chk(fheram_bank_regs_pack(bank_.bank_, h_, (int)sources.size(), sources.data(), flat.empty() ? nullptr : flat.data()));
+        }
+        // sels.size() reads as ONE operation; download = false: no host wait, an empty result (result later)
+        std::vector<std::vector<Glwe>> read(const std::vector<const Selector*>& sels, bool download = true) {
+            std::vector<const fheram_selector*> sh;
+            for (const Selector* x : sels) { if (!x) throw Error(FHERAM_ERR_INVALID_ARG, "null selector"); sh.push_back(x->h_); }
+            std::vector<int64_t> out(download ? sh.size() * bank_.params.word_size() * bank_.glwe_len() : 0);
+            bank_.chk(fheram_bank_regs_read(bank_.bank_, h_, sh.data(), (int)sh.size(), download ? out.data() : nullptr));
+            return download ? bank_.split(out, sh.size()) : std::vector<std::vector<Glwe>>();
+        }
+        std::vector<std::vector<Glwe>> result(int first, int n) {
+            if (n < 1) throw Error(FHERAM_ERR_INVALID_ARG, "empty slice of the last register read");
+            std::vector<int64_t> out((size_t)n * bank_.params.word_size() * bank_.glwe_len());
+            bank_.chk(fheram_bank_regs_result(bank_.bank_, first, n, out.data()));
+            return bank_.split(out, (size_t)n);
+        }
+        // the two halves of a register write: the OLD word; then the word `src` names, written at the prepared index
+        std::vector<Glwe> read_prepare_write(const Selector& sel, bool download = true) {
+            std::vector<int64_t> out(download ? bank_.params.word_size() * bank_.glwe_len() : 0);
+            bank_.chk(fheram_bank_regs_read_prepare_write(bank_.bank_, h_, sel.h_, download ? out.data() : nullptr));
+            return download ? bank_.split(out, 1)[0] : std::vector<Glwe>();
+        }
+        std::vector<Glwe> old_result() {
+            std::vector<int64_t> out(bank_.params.word_size() * bank_.glwe_len());
+            bank_.chk(fheram_bank_regs_old_result(bank_.bank_, out.data()));
+            return bank_.split(out, 1)[0];
+        }
+        void write(const Selector& sel, fheram_select_src src, const std::vector<std::vector<Glwe>>& host_words = {}) {
+            const std::vector<int64_t> flat = bank_.flat_words({src}, host_words);
+            bank_.chk(fheram_bank_regs_write(bank_.bank_, h_, sel.h_, src, flat.empty() ? nullptr : flat.data()));
+        }
+    private:
+        Bank& bank_;
+        fheram_regs* h_ = nullptr;
+    };
     void sync() { chk(fheram_bank_sync(bank_)); }
     double roundoff_max() { double m = 0.0; chk(fheram_bank_roundoff_max(bank_, &m)); return m; }
     struct ChainStats { uint64_t launches = 0, redone = 0; };
@@ -685,6 +745,17 @@ public:
 
 private:
     fheram_bank* bank_ = nullptr;
+    // host_words back to back, with every HOST slot the sources name inside them
+    std::vector<int64_t> flat_words(const std::vector<fheram_select_src>& sources, const std::vector<std::vector<Glwe>>& host_words) const {
+        std::vector<int64_t> flat;
+        for (auto& word : host_words) {
+            if (word.size() != params.word_size()) throw Error(FHERAM_ERR_INVALID_ARG, "a host word has word_size GLWEs");
+            for (auto& g : word) flat.insert(flat.end(), g.begin(), g.end());
+        }
+        for (auto& x : sources)
+            if (x.kind == FHERAM_SRC_HOST && (x.index < 0 || (size_t)x.index >= host_words.size())) throw Error(FHERAM_ERR_INVALID_ARG, "a host source names a slot outside host_words");
+        return flat;
+    }
     const EvaluationKeysPrepared* keys_ = nullptr;
     std::vector<std::pair<const Address*, fheram_addr*>> addr_;   // device copies bound to the bank, by host address object
     void chk(int rc) { if (rc != FHERAM_OK) throw Error(rc, fheram_bank_last_error(bank_)); }

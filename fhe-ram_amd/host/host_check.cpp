@@ -199,6 +199,31 @@ int main() {
                     catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 19; }
                     std::printf("bank derive_list == derive, derive_selectors, derive_selector_fields: ok\n");
                 }
+                {   // Bank::RegFile: a register file of 2 words, every call once; a packed one reads as the select on the same sources does
+                    B::RegFile lr(lists, 1), tr(twin, 1);
+                    if (lr.bits() != 1 || lr.state()) return 20;
+                    const auto row = synth(4 * lists.glwe_len());
+                    lr.load(row);
+                    tr.load(row);
+                    if (lr.store() != row) { std::printf("RegFile: the row differs from what was loaded\n"); return 20; }
+                    if (!lr.read({&ls0, &ls1}, false).empty()) return 20;
+                    if (lr.result(0, 2) != tr.read({&ts0, &ts1})) { std::printf("RegFile::read: the two banks differ\n"); return 20; }
+                    lr.read_prepare_write(ls0, false);
+                    if (!lr.state() || lr.old_result() != tr.read_prepare_write(ts0)) { std::printf("RegFile::read_prepare_write: the two banks differ\n"); return 20; }
+                    lr.write(ls0, B::src_host(1), words);
+                    tr.write(ts0, B::src_host(1), words);
+                    if (lr.state() || lr.store() != tr.store()) { std::printf("RegFile::write: the two banks differ\n"); return 20; }
+                    lr.read_prepare_write(ls0, false);
+                    lr.write(ls0, B::src_regs_old());   // the old word put back, on the device
+                    lr.pack({B::src_host(0), B::src_regs(1)}, words);
+                    const auto want = lists.select({&ls0}, {{B::src_host(0), B::src_regs(1)}}, words);   // (before the read below replaces the last register read)
+                    if (lr.read({&ls0}) != want) { std::printf("RegFile::pack + read differs from select\n"); return 20; }
+                    try { lr.read({&ts0}); return 21; }   // a selector of another bank
+                    catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 21; }
+                    try { lr.write(ls0, B::src_zero()); return 21; }   // no read_prepare_write before
+                    catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_STATE) return 21; }
+                    std::printf("bank register file: read, read_prepare_write, write, pack: ok\n");
+                }
             }
         }
     } catch (const fheram::Error& e) {

@@ -510,6 +510,9 @@ enum { FHERAM_SRC_ZERO = 0,            /* all-zero ciphertexts                  
        FHERAM_SRC_MEMBER_RESULT = 2,   /* member `index`'s last read / read_prepare_write result                              */
        FHERAM_SRC_LIST_RESULT = 3,     /* entry `index` of the last read list                                                 */
        FHERAM_SRC_SELECT_RESULT = 4 }; /* output `index` of the previous select call                                          */
+/* two more kinds, of a bank's register files (below); valid wherever a fheram_select_src or a fheram_select_lane is taken */
+#define FHERAM_SRC_REGS_RESULT 5       /* output `index` of the bank's last fheram_bank_regs_read                              */
+#define FHERAM_SRC_REGS_OLD 6          /* the bank's last fheram_bank_regs_read_prepare_write result; index must be 0          */
 typedef struct fheram_select_src { int32_t kind, index; } fheram_select_src;
 /* n selects as ONE operation.  Select k has the candidates srcs[off_k .. off_k + n_cand[k]), off_k = the sum of the earlier n_cand, and
  * for every word ciphertext y
@@ -616,6 +619,65 @@ typedef struct fheram_derive_item {
 int fheram_bank_derive_list(fheram_bank* bank, const fheram_derive_item* items, int n);
 /* the std-form digits of a bank address, [n_digits][fheram_ggsw_len]: the bank form of fheram_address_download (refuses an empty address) */
 int fheram_bank_address_download(fheram_bank* bank, const fheram_addr* addr, int64_t* out);
+
+/* ---- A bank's REGISTER FILE: a one-row RAM of 2^bits words that is read and written by selectors.
+ * *** CONTRACT-COMPATIBLE ONLY *** as the select above.  A 32-word register file held as a bank member has the bank's shape and pays the
+ * members' row chains on every access; but a select already IS Ram::read on a one-row RAM of max_addr = 2^bits whose row packs word j at
+ * coefficient j.  A register file is that row made persistent, with a write side: its operations are Ram::read / read_prepare_write /
+ * write (ram.rs:172-294, the rows == 1, one-coordinate path) of a RAM of max_addr = 2^bits, 1 <= bits <= FHERAM_SELECT_BITS_MAX, of
+ * the bank's word_size.  Row w packs byte w of word j at coefficient j: [word_size][GLWE], what Ram::encrypt_sk of that RAM gives.
+ * It lives on a bank beside the members, under the bank's keys, stream, configuration and round-off monitor.  Its addresses are the
+ * bank's selectors — accepted when the selector belongs to the bank, is not empty and has bits == fheram_regs_bits(regs); plain and
+ * field selectors alike — so rs1, rs2 and rd come out of the instruction word in the derive list's one launch.  Its results feed the
+ * selects, and a write takes its word from any source kind.  No member's rows, state flag, tree, result or kept memo changes; the last
+ * read list's and the last select's results stay readable; selects, read lists and member operations may run between
+ * read_prepare_write and write, and a member between its own two halves resumes exactly as before.  fheram_bank_keys_load voids what a
+ * register file kept for its write (the write then recomputes it).
+ * Every check runs before anything is enqueued and a refused call changes nothing.  Common refusals — FHERAM_ERR_INVALID_ARG: null
+ * arguments, a register file of another bank, a foreign or empty selector, a selector of other bits, an unknown source kind or a bad
+ * index; FHERAM_ERR_UNINITIALIZED: no upload or pack yet; FHERAM_ERR_KEYS: keys not loaded; FHERAM_ERR_STATE: read, pack or
+ * read_prepare_write between read_prepare_write and write, write outside it. */
+typedef struct fheram_regs fheram_regs;
+/* Every device buffer the register file will ever need is allocated here (the row, the kept trace, two temporaries, its prepared and
+ * inverse digits); what the bank's register files share (the buffers of a read of FHERAM_SELECT_MAX outputs, the result and host-word
+ * staging) by the bank's first create.  No operation allocates afterwards.  FHERAM_ERR_DEVICE if an allocation fails (the bank is as it
+ * was).  A bank may hold any number of register files.
+ * Who frees: fheram_regs_destroy frees the register file's device buffers while its bank lives.  fheram_bank_destroy frees the device
+ * buffers of every register file still alive and detaches it; such a handle is then good for fheram_regs_destroy only, which releases
+ * it.  Either order is safe.  Destroying the register file whose read_prepare_write was the bank's last voids FHERAM_SRC_REGS_OLD. */
+int fheram_bank_regs_create(fheram_bank* bank, int bits, fheram_regs** out);
+void fheram_regs_destroy(fheram_regs* regs);
+int fheram_regs_bits(const fheram_regs* regs);
+/* 1 between read_prepare_write and write */
+int fheram_bank_regs_state(const fheram_bank* bank, const fheram_regs* regs);
+/* row: [word_size][GLWE] host int64.  Upload is range-checked as fheram_bank_ram_upload is (FHERAM_ERR_RANGE), makes the register file
+ * readable, sets state 0 and voids anything kept — also between read_prepare_write and write, as fheram_bank_ram_upload. */
+int fheram_bank_regs_upload(fheram_bank* bank, fheram_regs* regs, const int64_t* row);
+int fheram_bank_regs_download(fheram_bank* bank, const fheram_regs* regs, int64_t* row);
+/* row_w <- glwe_normalize( sum_{j < n_cand} X^j * source(srcs[j])[w] ), 1 <= n_cand <= 2^bits: exactly the pack of fheram_bank_select
+ * (the same kernel, the same source checks) written into the register file; 2^bits ZERO sources give the all-zero register file with no
+ * host encryption.  HOST slots are [0, 2^FHERAM_SELECT_BITS_MAX) of host_words, range-checked (FHERAM_ERR_RANGE).  Sets state 0; needs
+ * no keys.  No host wait beyond the previous call's copy out of the pinned staging buffer. */
+int fheram_bank_regs_pack(fheram_bank* bank, fheram_regs* regs, int n_cand, const fheram_select_src* srcs, const int64_t* host_words);
+/* n independent Ram::read of the row as ONE operation, 1 <= n <= FHERAM_SELECT_MAX, n * word_size <= 64; all selectors share the digit
+ * count.  The row is fanned out to the n * word_size chain inputs by one launch, then runs what fheram_bank_select runs behind its pack:
+ * the digits prepared, the products, trace(0, log N), in the forms the bank's configuration selects.  out: [n][word_size][GLWE] or NULL
+ * (no host wait; fheram_bank_regs_result later).  The row and the state flag do not change.  The outputs are the bank's "last register
+ * read": FHERAM_SRC_REGS_RESULT names them until the next fheram_bank_regs_read of any register file of the bank. */
+int fheram_bank_regs_read(fheram_bank* bank, const fheram_regs* regs, const fheram_selector* const* sels, int n, int64_t* out);
+/* outputs [first, first + n) of the bank's last register read; FHERAM_ERR_STATE before any has run */
+int fheram_bank_regs_result(fheram_bank* bank, int first, int n, int64_t* out);
+/* Ram::read_prepare_write (ram.rs:196-222): the products with the selector's digits in place on the row (ram.rs:502-504), then
+ * trace(0, log N) of the rotated row, which is the result — the OLD word — and is kept for the write (memo = 0: the write recomputes
+ * it).  The state becomes 1.  out: [word_size][GLWE] or NULL (no host wait; fheram_bank_regs_old_result later).  The result is the
+ * bank's FHERAM_SRC_REGS_OLD until the next fheram_bank_regs_read_prepare_write of any register file of the bank. */
+int fheram_bank_regs_read_prepare_write(fheram_bank* bank, fheram_regs* regs, const fheram_selector* sel, int64_t* out);
+int fheram_bank_regs_old_result(fheram_bank* bank, int64_t* out);
+/* Ram::write (ram.rs:226-294) of ONE word taken on the device from `src` (any kind; HOST: slot src.index of host_words, range-checked as
+ * write words are, FHERAM_ERR_RANGE — a refused word leaves the register file prepared and untouched): row <- normalize(row -
+ * trace(row) + w), the selector's inverse digits, the products with them.  No host wait.  The state becomes 0.  Writing FHERAM_SRC_REGS_OLD
+ * puts the old word back; `enable ? new : old` is a select over [REGS_OLD, HOST] whose output is written as FHERAM_SRC_SELECT_RESULT. */
+int fheram_bank_regs_write(fheram_bank* bank, fheram_regs* regs, const fheram_selector* sel, fheram_select_src src, const int64_t* host_words);
 
 /* ---- Measurement hooks (bench.py).  HIP events recorded on the context's own stream. */
 int fheram_timer_begin(fheram_ctx* ctx);
