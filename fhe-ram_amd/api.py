@@ -33,6 +33,9 @@ SELECT_BITS_MAX = 5  # FHERAM_SELECT_BITS_MAX
 SELECT_MAX = 8       # FHERAM_SELECT_MAX
 SRC_ZERO, SRC_HOST, SRC_MEMBER_RESULT, SRC_LIST_RESULT, SRC_SELECT_RESULT = 0, 1, 2, 3, 4   # FHERAM_SRC_*
 SRC_REGS_RESULT, SRC_REGS_OLD = 5, 6   # FHERAM_SRC_REGS_RESULT / _REGS_OLD: a bank's register files
+SRC_TABLE_RESULT = 8   # FHERAM_SRC_TABLE_RESULT: a bank's tables (kind 7 is unknown)
+TABLE_BITS_MAX = 12             # FHERAM_TABLE_BITS_MAX
+SELECTOR_WIDE_DIGITS_MAX = 5    # FHERAM_SELECTOR_WIDE_DIGITS_MAX
 SELECT_FIELDS_MAX = 5   # FHERAM_SELECT_FIELDS_MAX
 DERIVE_LIST_MAX = 32          # FHERAM_DERIVE_LIST_MAX
 DERIVE_LIST_DIGITS_MAX = 64   # FHERAM_DERIVE_LIST_DIGITS_MAX
@@ -179,6 +182,17 @@ _SYMBOLS = [
     ("fheram_bank_regs_read_prepare_write", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, I64P]),
     ("fheram_bank_regs_old_result", C.c_int, [C.c_void_p, I64P]),
     ("fheram_bank_regs_write", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _CSelectSrc, I64P]),
+    ("fheram_bank_table_create", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    ("fheram_table_destroy", None, [C.c_void_p]),
+    ("fheram_table_bits", C.c_int, [C.c_void_p]),
+    ("fheram_bank_table_upload", C.c_int, [C.c_void_p, C.c_void_p, I64P]),
+    ("fheram_bank_table_download", C.c_int, [C.c_void_p, C.c_void_p, I64P]),
+    ("fheram_bank_table_load_plain", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t]),
+    ("fheram_bank_table_read", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, I64P]),
+    ("fheram_bank_table_result", C.c_int, [C.c_void_p, C.c_int, C.c_int, I64P]),
+    ("fheram_bank_table_selector_alloc", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_table_selector_create", C.c_int, [C.c_void_p, C.POINTER(I64P), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_table_selector_alloc_fields", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
     ("fheram_timer_begin", C.c_int, [C.c_void_p]),
     ("fheram_timer_end", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("fheram_profile_enable", C.c_int, [C.c_void_p, C.c_int]),
@@ -688,6 +702,11 @@ class Src:
         """the result of the bank's last RegFile.read_prepare_write: the word the pending register write replaces"""
         return cls(SRC_REGS_OLD, 0)
 
+    @classmethod
+    def table(cls, k: int):
+        """output k of the bank's last RamBank.table_read"""
+        return cls(SRC_TABLE_RESULT, k)
+
 
 class Lane:
     """One byte ciphertext of a lane-mapped candidate of RamBank.select_lanes (fheram_select_lane): GLWE `lane` of the word a Src would
@@ -739,6 +758,11 @@ class Lane:
     def regs_old(cls, lane: int):
         """GLWE `lane` of the result of the bank's last RegFile.read_prepare_write"""
         return cls(SRC_REGS_OLD, 0, lane)
+
+    @classmethod
+    def table(cls, k: int, lane: int):
+        """GLWE `lane` of output k of the bank's last RamBank.table_read"""
+        return cls(SRC_TABLE_RESULT, k, lane)
 
     @classmethod
     def of(cls, src: Src, lane: int):
@@ -943,6 +967,47 @@ class RegFile:
     def state(self) -> bool:
         """True between read_prepare_write and write"""
         return bool(library().fheram_bank_regs_state(self.bank._h, self._h))
+
+
+class Table:
+    """A table of a bank (fheram_table): a READ-ONLY one-row RAM of 2^bits words, bits <= TABLE_BITS_MAX = 12, of the bank's word_size that
+    lives beside the members and the register files — an instruction ROM, or a lookup table indexed by an encrypted field.  Made by
+    RamBank.table(bits).  load (an encrypted row) or load_plain (public bytes, no host encryption) make it readable; RamBank.table_read
+    reads any tables of the bank at wide Selectors (RamBank.table_selector) as one operation."""
+
+    def __init__(self, bank: "RamBank", handle, bits: int):
+        self.bank, self._h, self.bits = bank, handle, int(bits)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _LIB is not None:
+            _LIB.fheram_table_destroy(self._h)
+            self._h = None
+
+    def _row(self):
+        p = self.bank.params
+        return np.zeros((p.word_size(), p.glwe_len()), dtype=np.int64)
+
+    def load(self, row: np.ndarray):
+        """row: [word_size][GLWE], Ram::encrypt_sk's output for the one-row RAM of max_addr = 2^bits (fheram_bank_table_upload)"""
+        row = _i64(row)
+        if row.size != self._row().size:
+            raise FheRamError(1, f"invalid data: expected {self.bank.params.word_size()}x1 GLWE rows (ram.rs:144-155)")
+        self.bank._chk(library().fheram_bank_table_upload(self.bank._h, self._h, _p(row)))
+
+    def load_plain(self, data):
+        """public contents, 2^bits * word_size bytes in Ram::encrypt_sk's layout (byte w of word j at data[j * word_size + w]), as the
+        trivial ciphertext: no host encryption, no keys, no secret (fheram_bank_table_load_plain)"""
+        data = np.ascontiguousarray(np.asarray(data, dtype=np.uint8).ravel())
+        want = (1 << self.bits) * self.bank.params.word_size()
+        if data.size != want:
+            raise FheRamError(1, f"invalid data: a table of {self.bits} bits takes 2^bits * word_size = {want} bytes, got {data.size}")
+        self.bank._chk(library().fheram_bank_table_load_plain(self.bank._h, self._h, data.ctypes.data_as(C.POINTER(C.c_uint8)), data.size))
+
+    def download(self) -> np.ndarray:
+        """the row, [word_size][GLWE] (fheram_bank_table_download)"""
+        out = self._row()
+        self.bank._chk(library().fheram_bank_table_download(self.bank._h, self._h, _p(out)))
+        return out
 
 
 class _AddrHandle:
@@ -1952,6 +2017,62 @@ class RamBank:
         out = C.c_void_p()
         self._chk(library().fheram_bank_regs_create(self._h, int(bits), C.byref(out)))
         return RegFile(self, out.value, bits)
+
+    # -- tables (include/fheram.h: read-only one-row RAMs of up to 4096 words, read by wide selectors)
+    def table(self, bits: int) -> Table:
+        """a table of 2^bits words, bits <= TABLE_BITS_MAX, with every device buffer it will need (fheram_bank_table_create); Table.load /
+        load_plain fill it"""
+        out = C.c_void_p()
+        self._chk(library().fheram_bank_table_create(self._h, int(bits), C.byref(out)))
+        return Table(self, out.value, bits)
+
+    def table_selector(self, bits: int, ggsw_digits=None) -> Selector:
+        """a WIDE selector of up to TABLE_BITS_MAX bits: without digits (fheram_bank_table_selector_alloc; derive_selectors / derive_list
+        fill it), or from host std-form GGSW digits (fheram_bank_table_selector_create).  select and RegFile refuse it above
+        SELECT_BITS_MAX bits."""
+        out = C.c_void_p()
+        if ggsw_digits is None:
+            self._chk(library().fheram_bank_table_selector_alloc(self._h, int(bits), C.byref(out)))
+        else:
+            digits = [_i64(g).ravel() for g in ggsw_digits]
+            arr = (I64P * max(len(digits), 1))(*[_p(d) for d in digits])
+            self._chk(library().fheram_bank_table_selector_create(self._h, arr, len(digits), int(bits), C.byref(out)))
+        return Selector(self, out.value, bits)
+
+    def table_selector_fields(self, widths) -> Selector:
+        """a wide FIELD selector without digits (fheram_bank_table_selector_alloc_fields): up to SELECTOR_WIDE_DIGITS_MAX fields whose
+        widths sum to at most TABLE_BITS_MAX; derive_selector_fields / Derive.fields fill it"""
+        widths = [int(x) for x in widths]
+        out = C.c_void_p()
+        self._chk(library().fheram_bank_table_selector_alloc_fields(self._h, (C.c_int * max(len(widths), 1))(*widths), len(widths), C.byref(out)))
+        s = Selector(self, out.value, sum(widths))
+        s.widths = widths
+        return s
+
+    def table_read(self, tables, sels, download: bool = True, keys: Optional[EvaluationKeysPrepared] = None):
+        """len(sels) reads as ONE operation (fheram_bank_table_read): entry k reads tables[k] at sels[k]; the same Table may appear several
+        times and several Tables may share a call.  int64 [n][word_size][GLWE]; download=False: no host wait (table_result later)"""
+        tables, sels = list(tables), list(sels)
+        n = len(sels)
+        if n < 1 or len(tables) != n:
+            raise FheRamError(1, "table_read takes at least one Selector and one Table per selector")
+        if not all(isinstance(t, Table) for t in tables) or not all(isinstance(s, Selector) for s in sels):
+            raise FheRamError(1, "table_read takes Tables and Selectors")
+        if keys is not None:
+            self._use_keys(keys)
+        p = self.params
+        out = np.zeros((n, p.word_size(), p.glwe_len()), dtype=np.int64) if download else None
+        self._chk(library().fheram_bank_table_read(self._h, (C.c_void_p * n)(*[t._h for t in tables]), (C.c_void_p * n)(*[s._h for s in sels]), n,
+                                                   _p(out) if download else None))
+        return out
+
+    def table_result(self, first: int = 0, n: int = 1) -> np.ndarray:
+        """outputs [first, first + n) of the bank's last table read (fheram_bank_table_result)"""
+        first, n = int(first), int(n)
+        p = self.params
+        out = np.zeros((max(n, 1), p.word_size(), p.glwe_len()), dtype=np.int64)
+        self._chk(library().fheram_bank_table_result(self._h, first, n, _p(out)))
+        return out
 
     def _host_words(self, host_words, slots):
         """host_words as int64, with the named slots inside it"""

@@ -33,6 +33,7 @@
 #include "path.hpp"
 
 struct fheram_regs;   // a register file of the bank (regs.hpp)
+struct fheram_table;  // a table of the bank (table.hpp)
 
 struct fheram_bank {
     fheram_ctx* c = nullptr;      // word count M * mws; never row-sharded, never part of a group
@@ -59,6 +60,10 @@ struct fheram_bank {
     int regs_n = 0;
     const int32_t* regs_old = nullptr;
     const fheram_regs* regs_old_owner = nullptr;
+    // the tables (table.hpp): what they share, the live ones, the outputs of the last fheram_bank_table_read (in tabs.res; 0: none has run)
+    TableBufs tabs;
+    std::vector<fheram_table*> tables;
+    int table_n = 0;
 };
 
 namespace {
@@ -66,6 +71,8 @@ namespace {
 // regs.hpp: new keys void what every register file kept; a destroyed bank takes its register files' device buffers with it
 void regs_keys_changed(fheram_bank* b);
 void regs_bank_release(fheram_bank* b);
+// table.hpp: a destroyed bank takes its tables' device buffers with it
+void table_bank_release(fheram_bank* b);
 
 static_assert(FHERAM_READ_LIST_MAX >= FHERAM_BANK_MAX && FHERAM_READ_LIST_MAX * 4 <= 32, "a member set has four bits of the map per entry");
 // The members an operation works on, entry by entry: a range [first, first + n), or a list (checked by the caller).
@@ -315,6 +322,7 @@ void fheram_bank_destroy(fheram_bank* b) {
     select_free(b->sel);
     lane_table_free(b->lanes);
     regs_bank_release(b);
+    table_bank_release(b);
     fheram_ctx_destroy(b->c);
     delete b;
 }

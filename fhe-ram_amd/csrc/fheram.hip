@@ -840,4 +840,5 @@ int fheram_device_info(const fheram_ctx* c, char* name, size_t name_len, int* cu
 #include "bank.hpp"
 #include "select.hpp"
 #include "regs.hpp"
+#include "table.hpp"
 #include "derive_list.hpp"

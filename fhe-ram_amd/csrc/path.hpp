@@ -376,6 +376,27 @@ void regs_bufs_free(RegsBufs& R) {
     R = RegsBufs{};
 }
 
+// What a bank's tables share (table.hpp): the buffers of fheram_bank_table_read — per output ciphertext the gathered row, the products'
+// output, a temporary and the result; the prepared digits of its selectors — the pinned result buffer and the staged bytes of a
+// fheram_bank_table_load_plain.  Allocated whole by the bank's first fheram_bank_table_create, freed with the bank.
+struct TableBufs {
+    int cap = 0;                                                                  // ciphertexts of a read: min(FHERAM_SELECT_MAX * word_size, 64); 0: not allocated
+    int32_t *fan = nullptr, *ep = nullptr, *tmp = nullptr, *res = nullptr;        // [cap] GLWE
+    double* prep = nullptr;                                                       // [FHERAM_SELECT_MAX * FHERAM_SELECTOR_WIDE_DIGITS_MAX] prepared GGSW: read k's digits at k * n_digits
+    int64_t *h_res = nullptr, *d_h_res = nullptr;                                 // pinned, device-visible: the results as int64 (+ the monitor's maximum)
+    uint8_t *d_data = nullptr, *h_data = nullptr;                                 // [2^FHERAM_TABLE_BITS_MAX * word_size] bytes of a load_plain, device / pinned
+    hipEvent_t ev_data = nullptr;                                                 // the last copy out of h_data
+    bool data_busy = false;
+};
+void table_bufs_free(TableBufs& B) {
+    void* bufs[] = {B.fan, B.ep, B.tmp, B.res, B.prep, B.d_data};
+    for (void* p : bufs) if (p) hipFree(p);
+    if (B.h_res) hipHostFree(B.h_res);
+    if (B.h_data) hipHostFree(B.h_data);
+    if (B.ev_data) hipEventDestroy(B.ev_data);
+    B = TableBufs{};
+}
+
 // The one result export: every run (source, int32 count) is widened by the device into the pinned buffer h (device address d_h), back to
 // back, with the monitor's maximum as it stood then behind the last (the export kernel copies it there); out != nullptr: copied out.
 struct ResRun { const int32_t* src; size_t n; };

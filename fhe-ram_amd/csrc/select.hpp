@@ -40,14 +40,20 @@ static_assert(FHERAM_SELECT_MAX <= DERIVE_K_MAX && FHERAM_SELECT_BITS_MAX <= DER
 static_assert(SELECT_LANES_SLICES == EW_SLICES && SELECT_LANES_CT_MAX == 64, "k_select_pack_lanes covers a ciphertext as the elementwise kernels do; a call has at most 64 output ciphertexts");
 static_assert(FHERAM_SELECT_FIELDS_MAX == FHERAM_SELECT_BITS_MAX, "a field has at least one bit");
 
-// the selector of `bits` bits with its plan and its device buffer, no digits yet
-int selector_new(fheram_bank* b, int bits, fheram_selector** out) {
+static_assert(FHERAM_SELECTOR_WIDE_DIGITS_MAX == FHERAM_SELECT_BITS_MAX && FHERAM_SELECTOR_WIDE_DIGITS_MAX == FHERAM_SELECT_FIELDS_MAX, "a selector's plan arrays hold FHERAM_SELECTOR_WIDE_DIGITS_MAX digits, a wide selector's too");
+static_assert(FHERAM_TABLE_BITS_MAX == LOGN && FHERAM_SELECTOR_WIDE_DIGITS_MAX <= DERIVE_DIGITS_MAX, "a row holds N words; a wide selector's derivation is one k_cmux_chain launch");
+
+// the selector of `bits` bits with its plan and its device buffer, no digits yet.  bits_max: FHERAM_SELECT_BITS_MAX, or FHERAM_TABLE_BITS_MAX
+// for a WIDE selector (table.hpp: the address of a table), whose plan may then be longer than the plan arrays
+int selector_new(fheram_bank* b, int bits, fheram_selector** out, int bits_max = FHERAM_SELECT_BITS_MAX, const char* max_name = "FHERAM_SELECT_BITS_MAX") {
     fheram_ctx* c = b->c;
-    if (bits < 1 || bits > FHERAM_SELECT_BITS_MAX)
-        return fail(c, FHERAM_ERR_INVALID_ARG, "bits = " + std::to_string(bits) + " is outside [1, FHERAM_SELECT_BITS_MAX = " + std::to_string(FHERAM_SELECT_BITS_MAX) + "]");
+    if (bits < 1 || bits > bits_max)
+        return fail(c, FHERAM_ERR_INVALID_ARG, "bits = " + std::to_string(bits) + " is outside [1, " + max_name + " = " + std::to_string(bits_max) + "]");
     const std::vector<std::vector<int>> plan = base_2d((uint64_t)1 << bits, c->p);
     if (plan.size() != 1)
         return fail(c, FHERAM_ERR_UNSUPPORTED, "the bank's DECOMP_N gives a selector of " + std::to_string(bits) + " bits " + std::to_string(plan.size()) + " coordinates; a select is a read of a one-row RAM of one coordinate");
+    if ((int)plan[0].size() > FHERAM_SELECTOR_WIDE_DIGITS_MAX)
+        return fail(c, FHERAM_ERR_UNSUPPORTED, "the bank's DECOMP_N gives a selector of " + std::to_string(bits) + " bits " + std::to_string(plan[0].size()) + " digits, more than FHERAM_SELECTOR_WIDE_DIGITS_MAX = " + std::to_string(FHERAM_SELECTOR_WIDE_DIGITS_MAX));
     HIPCHK(c, hipSetDevice(c->device));
     fheram_selector* s = new fheram_selector{b, c->device, bits, (int)plan[0].size(), nullptr, {}, {}, {}, true, false};
     unsigned at = 0;
@@ -63,7 +69,7 @@ int selector_new(fheram_bank* b, int bits, fheram_selector** out) {
 
 // The selector whose digit d has widths[d] bits at bit offset sum(widths[0..d)): the Address of a one-row RAM of max_addr = 2^bits whose DECOMP_N
 // starts with `widths` (get_base_2d then gives [widths]), whatever the bank's own DECOMP_N is.  The plan comes from the caller, not from base_2d.
-int selector_new_fields(fheram_bank* b, const int* widths, int n_fields, fheram_selector** out) {
+int selector_new_fields(fheram_bank* b, const int* widths, int n_fields, fheram_selector** out, int bits_max = FHERAM_SELECT_BITS_MAX, const char* max_name = "FHERAM_SELECT_BITS_MAX") {
     fheram_ctx* c = b->c;
     if (!widths) return fail(c, FHERAM_ERR_INVALID_ARG, "null widths");
     if (n_fields < 1 || n_fields > FHERAM_SELECT_FIELDS_MAX)
@@ -72,8 +78,8 @@ int selector_new_fields(fheram_bank* b, const int* widths, int n_fields, fheram_
     for (int d = 0; d < n_fields; d++) {
         if (widths[d] < 1) return fail(c, FHERAM_ERR_INVALID_ARG, "field " + std::to_string(d) + " has the width " + std::to_string(widths[d]) + ", below 1");
         bits += widths[d];
-        if (bits > FHERAM_SELECT_BITS_MAX)
-            return fail(c, FHERAM_ERR_INVALID_ARG, "the widths sum to more than FHERAM_SELECT_BITS_MAX = " + std::to_string(FHERAM_SELECT_BITS_MAX) + " bits");
+        if (bits > bits_max)
+            return fail(c, FHERAM_ERR_INVALID_ARG, std::string("the widths sum to more than ") + max_name + " = " + std::to_string(bits_max) + " bits");
     }
     HIPCHK(c, hipSetDevice(c->device));
     fheram_selector* s = new fheram_selector{b, c->device, bits, n_fields, nullptr, {}, {}, {}, true, true};
@@ -135,6 +141,7 @@ const int32_t* select_source(const fheram_bank* b, const fheram_select_src& s, c
     case FHERAM_SRC_SELECT_RESULT: return b->sel.res + (size_t)s.index * per;
     case FHERAM_SRC_REGS_RESULT: return b->regs.res + (size_t)s.index * per;
     case FHERAM_SRC_REGS_OLD: return b->regs_old;
+    case FHERAM_SRC_TABLE_RESULT: return b->tabs.res + (size_t)s.index * per;
     default: return nullptr;
     }
 }
@@ -158,6 +165,8 @@ int select_check_sels(fheram_bank* b, const fheram_selector* const* sels, const 
     for (int k = 0; k < n; k++) {
         if (!sels[k] || sels[k]->bank != b) return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " is null or belongs to another bank");
         if (sels[k]->empty) return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " is empty: fheram_bank_selector_alloc without fheram_bank_selector_derive");
+        if (sels[k]->bits > FHERAM_SELECT_BITS_MAX)   // a wide selector (table.hpp): the pack holds 2^FHERAM_SELECT_BITS_MAX candidates
+            return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " has " + std::to_string(sels[k]->bits) + " bits, more than FHERAM_SELECT_BITS_MAX = " + std::to_string(FHERAM_SELECT_BITS_MAX) + ": a wide selector addresses a table (fheram_bank_table_read)");
         if (sels[k]->bits != sels[0]->bits)
             return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " has " + std::to_string(sels[k]->bits) + " bits, selector 0 " + std::to_string(sels[0]->bits) + ": the selects of one call share one digit count (the operand table's)");
         if (sels[k]->n_digits != sels[0]->n_digits)   // (field selectors: the same bits in another number of digits)
@@ -168,7 +177,7 @@ int select_check_sels(fheram_bank* b, const fheram_selector* const* sels, const 
     }
     return FHERAM_OK;
 }
-struct SelectNeeds { bool list = false, sel = false, regs = false, regs_old = false; };
+struct SelectNeeds { bool list = false, sel = false, regs = false, regs_old = false, table = false; };
 // one (kind, index) of a source or a lane
 int select_check_source(fheram_bank* b, int kind, int index, const std::string& who, const int64_t* host_words, SelectNeeds& need) {
     fheram_ctx* c = b->c;
@@ -197,6 +206,10 @@ int select_check_source(fheram_bank* b, int kind, int index, const std::string& 
         if (index != 0) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names index " + std::to_string(index) + " of the last register read_prepare_write, which has one result: index 0");
         need.regs_old = true;
         break;
+    case FHERAM_SRC_TABLE_RESULT:
+        if (index < 0 || (b->table_n && index >= b->table_n)) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names output " + std::to_string(index) + ", outside the last table read's " + std::to_string(b->table_n) + " outputs");
+        need.table = true;
+        break;
     default: return fail(c, FHERAM_ERR_INVALID_ARG, who + " has the unknown kind " + std::to_string(kind));
     }
     return FHERAM_OK;
@@ -208,6 +221,7 @@ int select_check_state(fheram_bank* b, const SelectNeeds& need, bool keys = true
     if (need.sel && !b->sel_n) return fail(c, FHERAM_ERR_STATE, "a source names the last select and no select has run on this bank");
     if (need.regs && !b->regs_n) return fail(c, FHERAM_ERR_STATE, "a source names the last register read and no fheram_bank_regs_read has run on this bank");
     if (need.regs_old && !b->regs_old) return fail(c, FHERAM_ERR_STATE, "a source names the last register read_prepare_write and none has run on this bank (or its register file is gone)");
+    if (need.table && !b->table_n) return fail(c, FHERAM_ERR_STATE, "a source names the last table read and no fheram_bank_table_read has run on this bank");
     return FHERAM_OK;
 }
 // n independent Ram::read of one-row RAMs as one operation, on the caller's buffers (S.packed holds the n * ws rows): the selectors' digits

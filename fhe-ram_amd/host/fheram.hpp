@@ -535,6 +535,15 @@ public:
             for (auto& d : digits) ptr.push_back(d.data());
             bank.chk(fheram_bank_selector_create_fields(bank.bank_, ptr.data(), (int)ptr.size(), widths.data(), (int)widths.size(), &h_));
         }
+        // a WIDE selector, the address of a Table: up to FHERAM_TABLE_BITS_MAX bits (fheram_bank_table_selector_alloc / _create / _alloc_fields)
+        struct Wide {};
+        Selector(Bank& bank, Wide, int bits) { bank.chk(fheram_bank_table_selector_alloc(bank.bank_, bits, &h_)); }
+        Selector(Bank& bank, Wide, int bits, const std::vector<std::vector<int64_t>>& digits) {
+            std::vector<const int64_t*> ptr;
+            for (auto& d : digits) ptr.push_back(d.data());
+            bank.chk(fheram_bank_table_selector_create(bank.bank_, ptr.data(), (int)ptr.size(), bits, &h_));
+        }
+        Selector(Bank& bank, Wide, const std::vector<int>& widths) : fields_(widths.size()) { bank.chk(fheram_bank_table_selector_alloc_fields(bank.bank_, widths.data(), (int)widths.size(), &h_)); }
         ~Selector() { if (h_) fheram_selector_destroy(h_); }
         Selector(const Selector&) = delete;
         int n_digits() const { return fheram_selector_n_digits(h_); }
@@ -737,6 +746,51 @@ public:
         Bank& bank_;
         fheram_regs* h_ = nullptr;
     };
+    // ---- a table (include/fheram.h): a READ-ONLY one-row RAM of 2^bits words, bits <= FHERAM_TABLE_BITS_MAX, beside the members and the
+    // register files — an instruction ROM or a lookup table — read at wide selectors (Selector::Wide)
+    static fheram_select_src src_table(int output) { return {FHERAM_SRC_TABLE_RESULT, output}; }   // output of the bank's last table_read
+    class Table {
+    public:
+        Table(Bank& bank, int bits) : bank_(bank) { bank.chk(fheram_bank_table_create(bank.bank_, bits, &h_)); }
+        ~Table() { if (h_) fheram_table_destroy(h_); }
+        Table(const Table&) = delete;
+        int bits() const { return fheram_table_bits(h_); }
+        // row: [word_size][GLWE], Ram::encrypt_sk's output for the one-row RAM of max_addr = 2^bits
+        void load(const std::vector<int64_t>& row) {
+            if (row.size() != bank_.params.word_size() * bank_.glwe_len()) throw Error(FHERAM_ERR_INVALID_ARG, "invalid data: expected word_size x 1 GLWE rows (ram.rs:144-155)");
+            bank_.chk(fheram_bank_table_upload(bank_.bank_, h_, row.data()));
+        }
+        // public bytes (2^bits * word_size, Ram::encrypt_sk's layout) as the trivial ciphertext: no host encryption, no keys
+        void load_plain(const std::vector<uint8_t>& data) { bank_.chk(fheram_bank_table_load_plain(bank_.bank_, h_, data.data(), data.size())); }
+        std::vector<int64_t> download() {
+            std::vector<int64_t> row(bank_.params.word_size() * bank_.glwe_len());
+            bank_.chk(fheram_bank_table_download(bank_.bank_, h_, row.data()));
+            return row;
+        }
+    private:
+        friend class Bank;
+        Bank& bank_;
+        fheram_table* h_ = nullptr;
+    };
+    // sels.size() reads as ONE operation (fheram_bank_table_read): entry k reads *tables[k] at *sels[k]; download = false: no host wait, an
+    // empty result (table_result later)
+    std::vector<std::vector<Glwe>> table_read(const std::vector<const Table*>& tables, const std::vector<const Selector*>& sels, bool download = true) {
+        if (sels.empty() || tables.size() != sels.size()) throw Error(FHERAM_ERR_INVALID_ARG, "table_read takes at least one selector and one table per selector");
+        std::vector<const fheram_table*> th;
+        std::vector<const fheram_selector*> sh;
+        for (const Table* t : tables) { if (!t) throw Error(FHERAM_ERR_INVALID_ARG, "null table"); th.push_back(t->h_); }
+        for (const Selector* x : sels) { if (!x) throw Error(FHERAM_ERR_INVALID_ARG, "null selector"); sh.push_back(x->h_); }
+        std::vector<int64_t> out(download ? sh.size() * params.word_size() * glwe_len() : 0);
+        chk(fheram_bank_table_read(bank_, th.data(), sh.data(), (int)sh.size(), download ? out.data() : nullptr));
+        return download ? split(out, sh.size()) : std::vector<std::vector<Glwe>>();
+    }
+    // outputs [first, first + n) of the last table read (fheram_bank_table_result)
+    std::vector<std::vector<Glwe>> table_result(int first, int n) {
+        if (n < 1) throw Error(FHERAM_ERR_INVALID_ARG, "empty slice of the last table read");
+        std::vector<int64_t> out((size_t)n * params.word_size() * glwe_len());
+        chk(fheram_bank_table_result(bank_, first, n, out.data()));
+        return split(out, (size_t)n);
+    }
     void sync() { chk(fheram_bank_sync(bank_)); }
     double roundoff_max() { double m = 0.0; chk(fheram_bank_roundoff_max(bank_, &m)); return m; }
     struct ChainStats { uint64_t launches = 0, redone = 0; };

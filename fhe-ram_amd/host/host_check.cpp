@@ -224,6 +224,37 @@ int main() {
                     catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_STATE) return 21; }
                     std::printf("bank register file: read, read_prepare_write, write, pack: ok\n");
                 }
+                {   // Bank::Table: a table of 2 words reads as a register file holding the same row does; a ROM of 4096 public words at a wide selector
+                    B::Table lt(lists, 1), rom(lists, 12);
+                    B::RegFile lr(lists, 1);
+                    if (lt.bits() != 1 || rom.bits() != 12) return 22;
+                    const auto row = synth(4 * lists.glwe_len());
+                    lt.load(row);
+                    lr.load(row);
+                    if (lt.download() != row) { std::printf("Table: the row differs from what was loaded\n"); return 22; }
+                    if (!lists.table_read({&lt, &lt}, {&ls0, &ls1}, false).empty()) return 22;
+                    if (lists.table_result(0, 2) != lr.read({&ls0, &ls1})) { std::printf("table_read differs from RegFile::read of the same row\n"); return 22; }
+                    const std::vector<std::vector<fheram::Glwe>> hw = {lists.table_result(1, 1)[0], words[0]};
+                    if (lists.select({&ls0}, {{B::src_table(1), B::src_host(1)}}, hw) != lists.select({&ls0}, {{B::src_host(0), B::src_host(1)}}, hw)) { std::printf("src_table differs from the downloaded output\n"); return 22; }
+                    std::vector<uint8_t> bytes(4096 * 4);
+                    for (size_t i = 0; i < bytes.size(); i++) bytes[i] = (uint8_t)(i * 37 + 11);
+                    rom.load_plain(bytes);
+                    const auto plain = rom.download();
+                    for (size_t i = 0; i < n; i++) if (plain[n + i] != 0) { std::printf("Table::load_plain: a mask limb is not zero\n"); return 22; }
+                    const std::vector<int64_t> ipc = synth(14 * 4 * 2 * 5 * 2 * n);
+                    B::FheUintPrepared pc(lists, ipc, 14);
+                    B::Selector fetch(lists, B::Selector::Wide{}, 12), f66(lists, B::Selector::Wide{}, std::vector<int>{6, 6});
+                    if (fetch.n_digits() != 4 || f66.n_digits() != 2) return 22;
+                    lists.derive_list({B::derive_selector(pc, fetch, 2), B::derive_field(pc, f66, 0, 2), B::derive_field(pc, f66, 1, 8)});
+                    if (lists.table_read({&rom, &rom}, {&fetch, &fetch}).size() != 2 || lists.table_read({&rom}, {&f66}).size() != 1) return 22;
+                    try { lists.select({&fetch}, {{B::src_zero()}}); return 23; }   // a wide selector: the pack holds 32 candidates
+                    catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 23; }
+                    try { lists.table_read({&lt}, {&fetch}); return 23; }   // 12 bits at a table of 1
+                    catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 23; }
+                    try { B::Selector narrow(lists, 6); return 23; }   // fheram_bank_selector_alloc keeps its bound
+                    catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 23; }
+                    std::printf("bank table: load, load_plain, table_read, table_result, wide selectors: ok\n");
+                }
             }
         }
     } catch (const fheram::Error& e) {

@@ -489,6 +489,7 @@ int fheram_bank_address_derive_at(fheram_bank* bank, const fheram_fheuint* const
  * sign = 0 of fheram_address_derive) in the layout of address digits (k_ggsw_addr: 4 limbs, dnum 3). */
 #define FHERAM_SELECT_BITS_MAX 5          /* up to 32 candidates */
 #define FHERAM_SELECT_MAX 8               /* selects per call; n * word_size <= 64 as for the lists */
+#define FHERAM_SELECTOR_WIDE_DIGITS_MAX 5 /* digits of a WIDE selector (the address of a table, below): what a selector's plan holds */
 typedef struct fheram_selector fheram_selector;
 /* buffers and no digits: fheram_bank_select refuses it (FHERAM_ERR_INVALID_ARG) until it has been derived */
 int fheram_bank_selector_alloc(fheram_bank* bank, int bits, fheram_selector** out);
@@ -513,6 +514,8 @@ enum { FHERAM_SRC_ZERO = 0,            /* all-zero ciphertexts                  
 /* two more kinds, of a bank's register files (below); valid wherever a fheram_select_src or a fheram_select_lane is taken */
 #define FHERAM_SRC_REGS_RESULT 5       /* output `index` of the bank's last fheram_bank_regs_read                              */
 #define FHERAM_SRC_REGS_OLD 6          /* the bank's last fheram_bank_regs_read_prepare_write result; index must be 0          */
+/* one more, of a bank's tables (below); valid in the same places.  (Kind 7 is unknown.) */
+#define FHERAM_SRC_TABLE_RESULT 8      /* output `index` of the bank's last fheram_bank_table_read                             */
 typedef struct fheram_select_src { int32_t kind, index; } fheram_select_src;
 /* n selects as ONE operation.  Select k has the candidates srcs[off_k .. off_k + n_cand[k]), off_k = the sum of the earlier n_cand, and
  * for every word ciphertext y
@@ -678,6 +681,67 @@ int fheram_bank_regs_old_result(fheram_bank* bank, int64_t* out);
  * trace(row) + w), the selector's inverse digits, the products with them.  No host wait.  The state becomes 0.  Writing FHERAM_SRC_REGS_OLD
  * puts the old word back; `enable ? new : old` is a select over [REGS_OLD, HOST] whose output is written as FHERAM_SRC_SELECT_RESULT. */
 int fheram_bank_regs_write(fheram_bank* bank, fheram_regs* regs, const fheram_selector* sel, fheram_select_src src, const int64_t* host_words);
+
+/* ---- A bank's TABLES: read-only one-row RAMs of up to 4096 words, read by selectors — an instruction ROM, or a lookup table indexed
+ * by an encrypted field.
+ * *** CONTRACT-COMPATIBLE ONLY *** as the select and the register file above.  A row is one GLWE of N = 4096 coefficients, so a one-row
+ * RAM holds up to 2^12 words; a program of a few thousand instructions held as a bank member has the bank's shape and pays the
+ * members' row chains on every fetch.  A table is a one-row RAM of 2^bits words, 1 <= bits <= FHERAM_TABLE_BITS_MAX (= log N), of the
+ * bank's word_size: its read is Ram::read (ram.rs:172-191, the rows == 1, one-coordinate path) of a RAM of max_addr = 2^bits.  Row w
+ * packs byte w of word j at coefficient j: [word_size][GLWE], what Ram::encrypt_sk of that RAM gives.  It lives on a bank beside the
+ * members and the register files, under the bank's keys, main stream, configuration and round-off monitor; it has no write side.
+ * Its addresses are WIDE SELECTORS: ordinary fheram_selector handles of up to FHERAM_TABLE_BITS_MAX bits, made by the
+ * fheram_bank_table_selector_* calls below (fheram_bank_selector_alloc / _create / _alloc_fields keep refusing more than
+ * FHERAM_SELECT_BITS_MAX bits).  The plan is get_base_2d(2^bits) over the bank's DECOMP_N ([3,3,3,3] gives [3,3] [3,3,1] [3,3,2]
+ * [3,3,3] [3,3,3,1] [3,3,3,2] [3,3,3,3] for bits = 6..12), or the caller's widths.  FHERAM_ERR_UNSUPPORTED: more than one coordinate, or
+ * more than FHERAM_SELECTOR_WIDE_DIGITS_MAX digits.  fheram_bank_selector_derive, _derive_fields, fheram_bank_derive_list (SELECTOR and
+ * FIELD items), _download, fheram_selector_n_digits and fheram_selector_destroy take a wide selector unchanged, so a fetch index is
+ * bits [2, 2 + bits) of the pc in the derive list's one launch.  fheram_bank_select and fheram_bank_select_lanes refuse a selector of
+ * more than FHERAM_SELECT_BITS_MAX bits (FHERAM_ERR_INVALID_ARG: their pack holds 32 candidates); a register file refuses it by its
+ * bits rule.
+ * No member's rows, state flag, tree, result or kept memo changes, no register file's row or state; the last read list's, select's
+ * and register read's results stay readable.  Every check runs before anything is enqueued and a refused call changes nothing.
+ * FHERAM_ERR_INVALID_ARG: null arguments, a table or selector of another bank, an empty selector, a selector whose bits are not the
+ * table's, selectors of different digit counts, n out of range, a wrong data_len; FHERAM_ERR_UNINITIALIZED: no upload or load yet;
+ * FHERAM_ERR_KEYS: keys not loaded. */
+#define FHERAM_TABLE_BITS_MAX 12          /* up to 4096 words: one per coefficient of the row */
+typedef struct fheram_table fheram_table;
+/* Every device buffer the table will ever need (the row: word_size GLWEs) is allocated here; what the bank's tables share (the buffers
+ * of a read of FHERAM_SELECT_MAX outputs, the prepared digits of 8 selectors x 5 digits, the pinned result and the staging of
+ * load_plain) by the bank's first create.  No operation allocates afterwards.  FHERAM_ERR_DEVICE if an allocation fails (the bank is
+ * as it was).  A bank may hold any number of tables.
+ * Who frees: as a register file.  fheram_table_destroy frees the table's row while its bank lives; fheram_bank_destroy frees the rows
+ * of every table still alive and detaches it; such a handle is then good for fheram_table_destroy only, which releases it.  Either
+ * order is safe. */
+int fheram_bank_table_create(fheram_bank* bank, int bits, fheram_table** out);
+void fheram_table_destroy(fheram_table* table);
+int fheram_table_bits(const fheram_table* table);
+/* row: [word_size][GLWE] host int64.  Upload is range-checked as fheram_bank_regs_upload is (FHERAM_ERR_RANGE) and makes the table
+ * readable. */
+int fheram_bank_table_upload(fheram_bank* bank, fheram_table* table, const int64_t* row);
+int fheram_bank_table_download(fheram_bank* bank, const fheram_table* table, int64_t* row);
+/* PUBLIC contents with no host encryption: data_len = 2^bits * word_size bytes in the layout fheram_ram_encrypt_sk takes (byte w of
+ * word j at data[j * word_size + w]).  The row becomes the TRIVIAL ciphertext of those bytes: every mask limb 0, the body the plaintext
+ * limbs Ram::encrypt_sk encodes (ram.rs:358-368) — int64-identical to fheram_ram_encrypt_sk of a RAM of max_addr = 2^bits with all-zero
+ * mask and noise.  One kernel writes it from a pinned staging buffer; the only host wait is for the previous call's copy out of that
+ * buffer.  Needs no keys and no secret.  Makes the table readable. */
+int fheram_bank_table_load_plain(fheram_bank* bank, fheram_table* table, const uint8_t* data, size_t data_len);
+/* n independent reads as ONE operation: entry k is Ram::read of tables[k] at sels[k].  The same table may be named several times and
+ * several tables may share a call; 1 <= n <= FHERAM_SELECT_MAX, n * word_size <= 64; sels[k] has the bits of tables[k], and all
+ * selectors of a call share the digit count (one stride of the operand table) — the tables of a call may differ in bits.  One launch
+ * gathers row w of tables[k] to chain input k * word_size + w, then runs what fheram_bank_select runs behind its pack: the digits
+ * prepared, the products, trace(0, log N), in the forms the bank's configuration selects.  out: [n][word_size][GLWE] or NULL (no host
+ * wait; fheram_bank_table_result later).  The outputs are the bank's "last table read": FHERAM_SRC_TABLE_RESULT names them until the
+ * next fheram_bank_table_read. */
+int fheram_bank_table_read(fheram_bank* bank, const fheram_table* const* tables, const fheram_selector* const* sels, int n,
+                           int64_t* out /* [n][word_size][GLWE] or NULL */);
+/* outputs [first, first + n) of the bank's last table read; FHERAM_ERR_STATE before any has run */
+int fheram_bank_table_result(fheram_bank* bank, int first, int n, int64_t* out);
+/* WIDE selectors (header of this section): 1 <= bits <= FHERAM_TABLE_BITS_MAX; sum(widths) <= FHERAM_TABLE_BITS_MAX and
+ * n_fields <= FHERAM_SELECTOR_WIDE_DIGITS_MAX.  Otherwise fheram_bank_selector_alloc / _create / _alloc_fields. */
+int fheram_bank_table_selector_alloc(fheram_bank* bank, int bits, fheram_selector** out);
+int fheram_bank_table_selector_create(fheram_bank* bank, const int64_t* const* ggsw, int n_ggsw, int bits, fheram_selector** out);
+int fheram_bank_table_selector_alloc_fields(fheram_bank* bank, const int* widths, int n_fields, fheram_selector** out);
 
 /* ---- Measurement hooks (bench.py).  HIP events recorded on the context's own stream. */
 int fheram_timer_begin(fheram_ctx* ctx);

@@ -1,9 +1,10 @@
 // tools/launch_log.hip: what this tree's csrc/ has no name for, and what it names differently from another tree.
 namespace {
 
-// bank.hpp's hooks into regs.hpp, which this program does not include: its banks hold no register files
+// bank.hpp's hooks into regs.hpp and table.hpp, which this program does not include: its banks hold no register files and no tables
 void regs_keys_changed(fheram_bank*) {}
 void regs_bank_release(fheram_bank*) {}
+void table_bank_release(fheram_bank*) {}
 
 // read_top's fuse_ep and gated ask whether the final trace over Y ciphertexts takes the tail launch (path.hpp read_top, tail_top)
 bool shim_tail_top(const fheram_ctx* c, int Y) { return chain_form(c, ChainQuery{false, LOGN, 1, Y}).form == ChainForm::Tail; }
