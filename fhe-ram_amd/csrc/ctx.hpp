@@ -6,6 +6,7 @@
 #include "cmux_chain.hpp"
 #include "cmux_jobs.hpp"
 #include "mapped_chains.hpp"
+#include "tail_wait.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -189,7 +190,12 @@ struct fheram_ctx {
     unsigned* h_tail_fb = nullptr;     // pinned, device-visible
     unsigned tail_fb_mark = 0;
     uint64_t tail_launch_mark = 0;
-    unsigned* d_tail_sync = nullptr;   // [8 groups][32] + abort generation, fallbacks taken
+    unsigned* d_tail_sync = nullptr;   // [8 groups][32] + abort generation, fallbacks taken, gate, groups gone
+    //  done words: the tail's last workgroup to leave tells the host so (tail_wait.hpp): fheram_sync ends on them when a read-type
+    //  operation's tail and its predicated fallback are the last thing on the main stream, instead of on the end of both kernels
+    unsigned* h_tail_done = nullptr;   // pinned, device-visible: [0] done, [16] gave up
+    unsigned* d_h_tail_done = nullptr; // device address of h_tail_done
+    TailWait tail_wait;
     // ---- mid (cfg.mid): dependent chains on 9..64 ciphertexts as ONE launch with in-kernel hand-offs (k_chain_mid); cfg.mid_test: every
     //      launch gives up late.  One sync block per stream ----
     unsigned mid_seq = 0;
@@ -306,8 +312,8 @@ int check_precision(fheram_ctx* c) {
 GlweRef ref(int32_t* p, long sy, long sx) { return GlweRef{p, sy, sx}; }
 
 // the host has just waited for everything enqueued on the main stream / something is being enqueued on it (fheram_ctx: wide_unsynced, derive_unsynced, main_idle)
-void main_waited(fheram_ctx* c) { c->wide_unsynced = c->derive_unsynced = false; c->main_idle = true; }
-void main_enqueued(fheram_ctx* c) { c->main_idle = false; }
+void main_waited(fheram_ctx* c) { c->wide_unsynced = c->derive_unsynced = false; c->main_idle = true; c->tail_wait.waited(); }
+void main_enqueued(fheram_ctx* c) { c->main_idle = false; c->tail_wait.enqueued(); }
 
 hipEvent_t get_event(fheram_ctx* c) {
     if (!c->ev_pool.empty()) { hipEvent_t e = c->ev_pool.back(); c->ev_pool.pop_back(); return e; }

@@ -215,6 +215,11 @@ int fheram_ctx_create_cfg(const fheram_params* p, int device, int shard, int n_s
     }
     CCHK(c->res.host(&c->h_tail_fb, 64, hipHostMallocDefault));
     *c->h_tail_fb = 0;
+    CCHK(c->res.host(&c->h_tail_done, 128, hipHostMallocMapped));
+    memset(c->h_tail_done, 0, 128);
+    CCHK(hipHostGetDevicePointer((void**)&c->d_h_tail_done, c->h_tail_done, 0));
+    c->tail_wait.done = c->h_tail_done; c->tail_wait.gave_up = c->h_tail_done + 16;
+    if (const char* e = std::getenv("FHERAM_TAIL_POLL_US")) c->tail_wait.bound_us = std::atol(e);   // 0: one look, < 0: never (tail_wait.hpp)
     CCHK(c->res.host(&c->h_mid_fb, 128, hipHostMallocDefault));
     memset(c->h_mid_fb, 0, 128);
     CCHK(c->res.host(&c->h_res, ((size_t)c->ws * G + 1) * sizeof(int64_t), hipHostMallocMapped));   // + the monitor's maximum at export time
@@ -358,7 +363,11 @@ int fheram_result_download(fheram_ctx* c, int64_t* out) {
 int fheram_sync(fheram_ctx* c) {
     if (!c) return FHERAM_ERR_INVALID_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    // a read-type operation whose tail launch and predicated fallback are the last thing on the main stream is complete when the tail's
+    // workgroups have all left without giving up (tail_wait.hpp): the fallback then writes nothing (k_read_chain returns before it touches
+    // anything; k_keyswitch_chain's monitor has seen nothing and flushes nothing) and finishes behind the host's back.  A device error
+    // keeps the word from being written: the bound runs out and the stream wait reports it — as the next one anywhere does, being sticky.
+    if (!c->tail_wait.poll()) HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
     main_waited(c);
     return check_precision(c);
@@ -393,7 +402,9 @@ int fheram_read(fheram_ctx* c, const fheram_addr* addr, int64_t* out) {
     rc = run_op(c, addr, 0, [&] { return read_impl(one_addr(c, &addr), ctx_view(c), false); });
     if (rc != FHERAM_OK) return rc;
     HIPCHK(c, hipGetLastError());
-    return out ? fheram_result_download(c, out) : FHERAM_OK;
+    if (out) return fheram_result_download(c, out);
+    c->tail_wait.arm();   // nothing enqueued behind read_top's last launch: fheram_sync may end on the tail's done word
+    return FHERAM_OK;
 }
 // K independent Ram::read (ram.rs:172-191) as one operation: path.hpp read_impl over K addresses, on the batch's arenas
 int fheram_read_batch(fheram_ctx* c, const fheram_addr* const* addrs, int n_addr, int64_t* out) {
@@ -413,7 +424,9 @@ int fheram_read_batch(fheram_ctx* c, const fheram_addr* const* addrs, int n_addr
         rc = run_op(c, addrs[0], 0, [&] { return read_impl(one_addr(c, addrs), ctx_view(c), false); });
         if (rc != FHERAM_OK) return rc;
         HIPCHK(c, hipGetLastError());
-        return out ? fheram_result_download(c, out) : FHERAM_OK;
+        if (out) return fheram_result_download(c, out);
+        c->tail_wait.arm();
+        return FHERAM_OK;
     }
     // every address reads the same rows (the map 0, 0, ...); what K reads leave behind: the last address's result where a read leaves it
     // (RamState::res_in_trtop = false; nothing is kept for a write)
@@ -431,7 +444,9 @@ int fheram_read_prepare_write(fheram_ctx* c, const fheram_addr* addr, int64_t* o
     if (rc != FHERAM_OK) return rc;
     c->ram.state = true;                                                                  // ram.rs:533
     HIPCHK(c, hipGetLastError());
-    return out ? fheram_result_download(c, out) : FHERAM_OK;
+    if (out) return fheram_result_download(c, out);
+    c->tail_wait.arm();   // nothing enqueued behind read_top's last launch: fheram_sync may end on the tail's done word
+    return FHERAM_OK;
 }
 int fheram_word_stage(fheram_ctx* c, const int64_t* w, int n_w) {
     if (!c || !w) return FHERAM_ERR_INVALID_ARG;

@@ -1856,7 +1856,7 @@ __device__ __forceinline__ GlweRef table_member_row(GlweRef a, const RowChainTab
 // products + trace steps on one workgroup per ciphertext).  Measured and removed the same round (profiles/r06_experiments.txt 3, 7): ONE hand-off per
 // step with the closed-form contributions added by L2 atomics, and the last pair levels of the packing tree as steps of this launch.
 //   grid (8 * 2*SK*SX): group g = (b - xoff) % 8 = ciphertext (x = g % gx, y = g / gx), member m = b / 8 = ((co*SK + (SK-1-j))*SX + r)
-//   sync: [group][32] words: arrivals, leavers, XCC mask;  sync[8*32] = abort generation
+//   sync: [group][32] words: arrivals, leavers, XCC mask;  sync[8*32] = abort generation, + 1 fallbacks taken, + 2 the gate, + 3 groups gone (the done word)
 // ---------------------------------------------------------------------------------------
 constexpr int TAIL_GROUPS = 8;
 // One wave on the side stream that holds back what is enqueued behind it until the single-launch trace chain of
@@ -1895,6 +1895,9 @@ struct TailArgs {
     int n_ep = 0;
     const double* ggsw[4];           // prepared digits of the coordinate
     GlweRef ep_out;                  // where the last product's result goes = the trace chain's source (read_prepare_write: tree[0], ram.rs:526); not src, not buf[]
+    // two host-mapped words (nullptr: none): [0] <- seq once the launch's last workgroup has left, [16] <- seq by a workgroup whose group gave up
+    // (tail_wait.hpp: the host's wait ends on them instead of on the end of this kernel and of the predicated launch behind it)
+    unsigned* host_done = nullptr;
 };
 constexpr int TAIL_EP_MAX = 4;
 __device__ __forceinline__ int xcc_id() {

@@ -426,6 +426,7 @@ void launch_trace_tail(fheram_ctx* c, GlweRef src, const GlweRef (&b)[2], int st
     TailArgs ta;
     ta.src = src; ta.buf[0] = b[0]; ta.buf[1] = b[1]; ta.tw = c->d_tw; ta.big = big_of(c); ta.sync = c->d_tail_sync;
     ta.n_ep = prep ? d : 0; ta.ep_out = ep_out;
+    ta.host_done = c->d_h_tail_done;
     for (int i = 0; i < TAIL_EP_MAX; i++) ta.ggsw[i] = (prep && i < d) ? prep + (size_t)i * fheram_ctx::GGSW : nullptr;
     if (++c->tail_seq == 0) ++c->tail_seq;
     c->tail_launches++;

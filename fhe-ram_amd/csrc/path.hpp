@@ -236,6 +236,9 @@ int read_top(const Opnds& o, const RamView& a, bool prepare_write, int32_t* gath
         const unsigned seq = c->tail_launches != tl0 ? c->tail_seq : 0;                // 0: no such launch after all -> event fork
         for (int ci = c->n2 - 1; ci >= 0; ci--) precompute_inverse(c, o.addrs[0], ci, ci == c->n2 - 1, seq);
     }
+    // the tail launch and its fallback are the last launches of this function on the main stream (behind them: at most an event record):
+    // a caller that enqueues nothing more arms the host's short cut on that generation (tail_wait.hpp)
+    c->tail_wait.note_top(c->tail_launches != tl0 ? c->tail_seq : 0);
     return FHERAM_OK;
 }
 int read_impl(const Opnds& o, const RamView& a, bool prepare_write) {

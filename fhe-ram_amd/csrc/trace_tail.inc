@@ -11,7 +11,6 @@ __global__ __launch_bounds__(T, T / 256) void FK_TAIL_NAME(FK_TAIL_ARGS ta) {
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0)   // the last block: every block of the launch has been placed (k_tail_gate)
         __hip_atomic_store(ta.sync + TAIL_GROUPS * 32 + 2, ta.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (g >= ta.n_ct) return;
-    RoMonitor ro_mon(lds, ta.tw);
     const int tid = vt((int)threadIdx.x);
     double* tw = lds;
     double* data = lds + LDS_TW;
@@ -19,6 +18,10 @@ __global__ __launch_bounds__(T, T / 256) void FK_TAIL_NAME(FK_TAIL_ARGS ta) {
     int* flag = reinterpret_cast<int*>(data + 2 * LDS_DATA);   // the third exchange buffer is not used here
     unsigned* ctr = ta.sync + g * 32;
     unsigned* abortp = ta.sync + TAIL_GROUPS * 32;
+    const int n_ep = ta.n_ep, n_all = ta.n_ep + ta.n;
+    int s = 0;   // (lives past the step loop: s < n_all there = this workgroup left early, its group gave up)
+    {   // the monitor's scope (not indented): its flush comes BEFORE the workgroup counts itself as gone, so the host words below are the launch's last stores
+    RoMonitor ro_mon(lds, ta.tw);
     const int r = m % SX, zz = m / SX;
     const int j = SK - 1 - zz % SK, co = zz / SK;                 // this member in a trace step
     const int je = SG - 1 - zz % SG, coe = zz / SG;               // ... and in a product (m < GE)
@@ -32,7 +35,6 @@ __global__ __launch_bounds__(T, T / 256) void FK_TAIL_NAME(FK_TAIL_ARGS ta) {
 #define FK_TAIL_OPND(i) ta.ggsw[i]
 #endif
     double* const big0 = ta.big + (long)g * BIG_STRIDE * SX;   // + step parity * TAIL_GROUPS * BIG_STRIDE * SX (see the normalisation phase)
-    const int n_ep = ta.n_ep, n_all = ta.n_ep + ta.n;
     OpRegs kop, kop1;                 // the operand(s) of the coming step: a trace key polynomial, or the two GGSW polynomials of a product
     if (n_ep > 0) {
         if (ep_member) {
@@ -51,7 +53,7 @@ __global__ __launch_bounds__(T, T / 256) void FK_TAIL_NAME(FK_TAIL_ARGS ta) {
     // step s_ writes: a product the ping-pong buffers (the last one ep_out), trace step t = s_ - n_ep buf[t & 1]
     auto out_of = [&](int s_) -> GlweRef { return s_ < n_ep ? (s_ == n_ep - 1 ? ta.ep_out : ta.buf[s_ & 1]) : ta.buf[(s_ - n_ep) & 1]; };
 #pragma unroll 1
-    for (int s = 0; s < n_all; s++) {
+    for (; s < n_all; s++) {
         const GlweRef rin = (s == 0) ? ta.src : out_of(s - 1);
         const GlweRef rout = out_of(s);
         const int32_t* ap = rin.p + ct * rin.sy + cx * rin.sx;
@@ -262,8 +264,17 @@ __global__ __launch_bounds__(T, T / 256) void FK_TAIL_NAME(FK_TAIL_ARGS ta) {
         }
         TSTAMP(7);
     }
+    }   // (ro_mon: every wave has flushed its maximum)
     // the last workgroup of the group to leave (every one passes here exactly once, given up or not) rewinds the
     // group's words for the next launch: nobody can still be waiting on them
+    // The two host words (ta.host_done: [0] done, [16] gave up; host/tail_wait.hpp reads them): a workgroup that leaves early says so
+    // before it is counted as gone; the last group to be gone — one more counter, across the launch's n_ct active groups, sync[8*32 + 3] —
+    // publishes the launch's generation behind a system-scope fence.  The host then knows, without waiting for the end of this kernel and of
+    // the predicated launch behind it, that every store of the launch is done and that the fallback will not run.
+    if (ta.host_done) {
+        if (s < n_all && tid == 0) __hip_atomic_store(ta.host_done + 16, ta.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every wave: its last step's stores, its monitor flush and that word have been performed
+    }
     __syncthreads();
     if (tid == 0) {
         const unsigned old = __hip_atomic_fetch_add(ctr + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -271,6 +282,14 @@ __global__ __launch_bounds__(T, T / 256) void FK_TAIL_NAME(FK_TAIL_ARGS ta) {
             __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(ctr + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(ctr + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (ta.host_done) {
+                const unsigned gone = __hip_atomic_fetch_add(abortp + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (gone == (unsigned)(ta.n_ct - 1)) {
+                    __hip_atomic_store(abortp + 3, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __threadfence_system();
+                    __hip_atomic_store(ta.host_done, ta.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                }
+            }
         }
     }
 }
