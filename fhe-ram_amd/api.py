@@ -256,6 +256,8 @@ _SYMBOLS = [
     ("fheram_selftest_convolve", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int]),
     ("fheram_selftest_convolve_rounded", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_double]),
     ("fheram_selftest_limb_forms", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("fheram_selftest_forms", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                        C.c_int, C.c_double, C.POINTER(C.c_double)]),
 ]
 
 
@@ -1511,6 +1513,27 @@ class Ram:
         ip = lambda v: v.ctypes.data_as(C.POINTER(C.c_int32))   # noqa: E731
         self._chk(library().fheram_selftest_convolve_rounded(self._h, a.shape[0], ip(a), ip(g), out.ctypes.data_as(C.POINTER(C.c_double)), float(operand_scale)))
         return out
+
+    # -- self-test of every transform form the kernels call (tests/test_gpu_fft_forms.py)
+    SELFTEST_FORMS = ("skew<1,1>", "skew<2,1>", "skew<1,0> alternating", "skew<1,0> behind fwd", "skew<1,2>", "skew<2,2>",
+                      "inv1_hooked<2>", "inv2_hooked<2>", "five-limb units")
+
+    def selftest_forms(self, a, g, inv_form: int, fwd_polys: int = 2, rounded: bool = False, operand_scale: float = 1.0, spectra: bool = False):
+        """a, g: [K][R][N] int32 -> out [K][2][N]: per batch the two sums of selftest_convolve, through ntt_fwd<fwd_polys> and inverse form
+        `inv_form` (index into SELFTEST_FORMS), the batches one after the other in the same exchange buffers; raw doubles, or
+        rounded through the round-off monitor.  spectra: also return the forward launch's scratch [2][K][R][N]."""
+        n = self.params.n()
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        g = np.ascontiguousarray(g, dtype=np.int32)
+        assert a.ndim == 3 and a.shape == g.shape and a.shape[2] == n
+        k, r = a.shape[0], a.shape[1]
+        out = np.zeros((k, 2, n), dtype=np.float64)
+        sp = np.zeros((2, k, r, n), dtype=np.float64) if spectra else None
+        ip = lambda v: v.ctypes.data_as(C.POINTER(C.c_int32))   # noqa: E731
+        dp = lambda v: v.ctypes.data_as(C.POINTER(C.c_double)) if v is not None else None   # noqa: E731
+        self._chk(library().fheram_selftest_forms(self._h, int(fwd_polys), int(inv_form), r, k, ip(a), ip(g), dp(out), int(bool(rounded)),
+                                                  float(operand_scale), dp(sp)))
+        return (out, sp) if spectra else out
 
     # -- self-test of the limb arithmetic (tests/test_gpu_limb_forms.py)
     LIMB_FORM_IN, LIMB_FORM_OUT = 10, 6

@@ -296,6 +296,10 @@ __device__ __forceinline__ void nat_in(d2 (&y)[4], const double (&a)[E]) {
 // transform — which of the thread's eight is a compile-time choice of the call site (SEL), so the sites of a kernel cover
 // different classes tid + 512 k —, 2 all eight (fheram_config.monitor = 2, what `safe` selects: +2.9 % of a step, the
 // sampled form +0.x %: profiles/r06_experiments.txt).
+// Mode 1 is a SAMPLE, not a guarantee.  The classes observed: fft_inv_skew 0, 3 (and 6 for a third polynomial), fft_inv1_hooked 5
+// (MSEL), fft_inv2_hooked 1 and 4 (MSEL, MSEL + 3); classes 2 and 7 are observed nowhere.  In either mode |x - rint(x)| <= 1/2:
+// an error e >= 1/2 reads as 1 - e, so MON_LIMIT is a sound alarm only below 5/8.  include/fheram.h (FHERAM_ERR_PRECISION) and
+// DESIGN.md §2 say the same, and tests/test_gpu_fft_forms.py pins the table (SITE_SEL): change all of them together.
 #ifndef FK_MONITOR
 #define FK_MONITOR 1     // 0: compiled out (A/B measurements only)
 #endif
@@ -497,14 +501,14 @@ __device__ __forceinline__ void fft_inv1_hooked(double (&x)[1][E], const double*
 }
 
 // ---- TWO inverse transforms half a phase apart with work of the caller's between their phases (six places) ------------------------------
-template <int FENCE, int MSEL = 1, class Hook>
+template <int FENCE, bool ROUND = true, int MSEL = 1, class Hook>
 __device__ __forceinline__ void fft_inv2_hooked(double (&x)[2][E], const double* tw_, double* d0, double* d1, int tid, Hook&& hook) {
     const d2* tw = reinterpret_cast<const d2*>(tw_);
     d2* const buf[2] = {reinterpret_cast<d2*>(d0), reinterpret_cast<d2*>(d1)};
     const XAddr xa = xaddr(tid);
     d2 y[2][4];
     Tw7 t2, t1; Tw5 t0;
-    const unsigned mon = mon_mode(tw_);
+    const unsigned mon = ROUND ? mon_mode(tw_) : 0u;
     tw_p2(t2, tw, xa);
     dom_in(y[0], x[0]); dom_in(y[1], x[1]);
     if constexpr (FENCE == 1) lds_barrier();
@@ -528,9 +532,9 @@ __device__ __forceinline__ void fft_inv2_hooked(double (&x)[2][E], const double*
     x0a_r(y[0], buf[0], xa);
     x0a_r(y[1], buf[1], xa);
     FK_HOOK(4);
-    i_pass3(y[0], t0); nat_out<true, MSEL>(y[0], x[0], tw_, tid, mon);
+    i_pass3(y[0], t0); nat_out<ROUND, MSEL>(y[0], x[0], tw_, tid, mon);
     FK_HOOK(5);
-    i_pass3(y[1], t0); nat_out<true, (MSEL + 3) % E>(y[1], x[1], tw_, tid, mon);
+    i_pass3(y[1], t0); nat_out<ROUND, (MSEL + 3) % E>(y[1], x[1], tw_, tid, mon);
 #undef FK_HOOK
     if constexpr (FENCE == 2) sb_arrive_free(sb_addr(tw_));
 }

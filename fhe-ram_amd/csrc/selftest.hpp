@@ -6,6 +6,10 @@
 // round-off that the rounding has to absorb (< 1/2 is correctness; the measured margin is what the test pins).
 // Nothing on the RAM path calls this entry point.
 //
+// fheram_selftest_forms (below; kernels in selftest_forms.hip) does the same for EVERY inverse form the kernels call — the unfenced
+// and free-counter forms, the hooked forms with multiply-accumulates and operand loads between their phases — over several batches
+// in the same exchange buffers, raw or rounded through the monitor: tests/test_gpu_fft_forms.py.
+//
 // The limb half of the exactness contract has its own entry point: fheram_selftest_limb_forms runs limb_form_eval
 // (limb_forms_eval.hpp) — the scalar forms of limb_forms.hpp that the kernels call, compiled with the library's own flags —
 // on one coefficient per thread, and tests/test_gpu_limb_forms.py compares the outputs with exact integers and, bit for bit,
@@ -13,6 +17,7 @@
 #pragma once
 #include "ctx.hpp"
 #include "limb_forms_eval.hpp"
+#include "selftest_forms.hpp"
 
 namespace fk {
 
@@ -145,5 +150,36 @@ int selftest_run(fheram_ctx* c, int n_terms, const int32_t* a, const int32_t* g,
     return rounded ? check_precision(c) : FHERAM_OK;
 }
 }  // namespace
+
+int fheram_selftest_forms(fheram_ctx* c, int fwd_polys, int inv_form, int n_terms, int n_batches, const int32_t* a, const int32_t* g, double* out,
+                          int rounded, double operand_scale, double* spectra) {
+    if (!c || fwd_polys < 1 || fwd_polys > fk::BMAX || inv_form < 0 || inv_form >= fk::SF_FORMS || n_terms <= 0 || n_terms > 8 || (n_terms & 1) ||
+        n_batches < 1 || n_batches > 4 || !a || !g || !out)
+        return fail(c, FHERAM_ERR_INVALID_ARG, "bad argument (fwd_polys 1..3; inv_form: SelftestForm of selftest_forms.hpp; n_terms: even, <= 8; n_batches 1..4)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int n_a = n_batches * n_terms, n_all = 2 * n_a;
+    const size_t nb = (size_t)n_a * fk::N * sizeof(int32_t), ns = (size_t)n_all * fk::N * sizeof(double), no = (size_t)n_batches * 2 * fk::N * sizeof(double);
+    int32_t* d = nullptr;
+    double* dsp = nullptr;
+    double* dout = nullptr;
+    HIPCHK(c, hipMalloc(&d, 2 * nb));
+    hipError_t e = hipMalloc(&dsp, ns);
+    if (e == hipSuccess) e = hipMalloc(&dout, no);
+    if (e == hipSuccess) e = hipMemcpy(d, a, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + (size_t)n_a * fk::N, g, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const double gscale = c->ninv * operand_scale;
+        e = fk::selftest_forms_fwd_launch(c->stream, fwd_polys, d, dsp, c->d_tw, gscale, n_a);
+    }
+    if (e == hipSuccess) e = fk::selftest_forms_inv_launch(c->stream, inv_form, rounded != 0, dsp, dsp + (size_t)n_a * fk::N, d, dout, c->d_tw, n_batches, n_terms);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(out, dout, no, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && spectra) e = hipMemcpy(spectra, dsp, ns, hipMemcpyDeviceToHost);
+    hipFree(d);
+    if (dsp) hipFree(dsp);
+    if (dout) hipFree(dout);
+    if (e != hipSuccess) return fail(c, FHERAM_ERR_DEVICE, std::string("selftest: ") + hipGetErrorString(e));
+    return rounded ? check_precision(c) : FHERAM_OK;
+}
 
 }  // extern "C"

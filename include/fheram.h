@@ -130,8 +130,23 @@ int fheram_sync(fheram_ctx* ctx);
 /* ---- The exactness contract, checked.  The reference multiplies with Poulpy's FFT64 backend and rounds (examples/fhe-ram.rs:3-7);
  * so does csrc/fft_dev.hpp: the rounded output of an inverse transform is the exact integer only while the accumulated FP64
  * round-off stays below 1/2.  No a-priori bound below 1/2 is known for six accumulated terms of extreme limbs (measured worst
- * case found by search 0.25: DESIGN.md §2), so every rounding on the path reports |x - rint(x)| to a per-context monitor
- * (fheram_config.monitor: one coefficient per thread and transform by default, every coefficient under `safe`).
+ * case found by search 0.25: DESIGN.md §2), so the roundings on the path report |x - rint(x)| to a per-context monitor
+ * (fheram_config.monitor).  What it observes depends on the mode:
+ *   monitor = 2 (what `safe` selects): every coefficient of every rounding.
+ *   monitor = 1 (the default): a SAMPLE — one coefficient class per rounding site, class k = the coefficients j with j / 512 == k
+ *     (a thread's k-th of eight), fixed at compile time (csrc/fft_dev.hpp):
+ *         fft_inv_skew      first polynomial 0, second 3 (third 6)
+ *         fft_inv1_hooked   5
+ *         fft_inv2_hooked   first polynomial 1, second 4
+ *     Classes 2 and 7 are observed nowhere, and a round-off confined to unobserved coefficients passes unseen.  Mode 1 detects the
+ *     onset of a loss of precision that spreads over a polynomial (as accumulated FFT round-off does); it is not a guarantee for
+ *     every coefficient (tests/test_gpu_fft_forms.py pins the table: a plant outside the sampled class returns FHERAM_OK).
+ *   In both modes the observed quantity |x - rint(x)| cannot exceed 1/2: a true error e >= 1/2 reads as 1 - e (and the integer is
+ *   already wrong), so the limit of 3/8 is a sound alarm only for errors below 5/8 — it catches round-off as it grows towards
+ *   1/2, not an arbitrary corruption.
+ *   After FHERAM_ERR_PRECISION from fheram_read_prepare_write or fheram_write (or the calls that wait for them) the RAM's rows
+ *   are not to be trusted: the write has stored, or is storing, integers rounded from values the contract no longer covers.  Load
+ *   the rows again; fheram_roundoff_reset only clears the flag.
  *   fheram_roundoff_max: waits for the context's streams; *max_out = the largest round-off seen since creation / the last reset;
  *                        returns FHERAM_ERR_PRECISION if it exceeds 3/8 — halfway between the largest round-off a search over
  *                        extreme operands has produced (1/4, tools/fft_search.hip) and failure (1/2); max_out is still written.
@@ -800,6 +815,21 @@ int fheram_selftest_convolve_rounded(fheram_ctx* ctx, int n_terms, const int32_t
  * per thread: in[n][10] and out[n][6] doubles holding exact integers, n <= 2^20; outputs a form does not produce are 0.
  * The caller compares with exact integer arithmetic (tests/test_gpu_limb_forms.py).  Not on the RAM path. */
 int fheram_selftest_limb_forms(fheram_ctx* ctx, int form, int n, const double* in, double* out);
+/* Self-test of EVERY transform form the kernels call (csrc/selftest.hpp: SelftestForm), each under the buffer discipline of its call
+ * sites: the forward transforms one, two or three at a time (fwd_polys), and inv_form =
+ *   0 fft_inv_skew<1, 1>    1 fft_inv_skew<2, 1>    2 fft_inv_skew<1, 0> on alternating buffers    3 fft_inv_skew<1, 0> behind a forward
+ *   transform in the same buffer    4 fft_inv_skew<1, 2>    5 fft_inv_skew<2, 2>    6 fft_inv1_hooked<2> twice per batch in one buffer
+ *   7 fft_inv2_hooked<2>    8 pair, pair, two singles, pair: both hooked forms in the same buffers under one free counter.
+ * a, g: [n_batches][n_terms][N] int32 (n_terms even, <= 8; 1 <= n_batches <= 4); out: [n_batches][2][N] doubles, per batch the two
+ * sums of fheram_selftest_convolve.  One workgroup transforms the batches one after the other in the same exchange buffers and takes
+ * batch i + 1's products while batch i is transformed (inside the hooks of forms 6..8), so a race in the reuse of the buffers shows
+ * as a batch that differs from the same operands run alone.  Every form computes the same doubles: inv_form 1 with one batch
+ * is fheram_selftest_convolve bit for bit.  rounded = 0: raw doubles; rounded != 0: the path's rounding, through the round-off
+ * monitor, with FHERAM_ERR_PRECISION as fheram_selftest_convolve_rounded returns it (operand_scale as there).  spectra (may be NULL):
+ * [2][n_batches][n_terms][N] doubles, the transform-domain a and the prepared g as the forward launch left them.
+ * The caller compares with exact integers and across forms (tests/test_gpu_fft_forms.py).  Not on the RAM path. */
+int fheram_selftest_forms(fheram_ctx* ctx, int fwd_polys, int inv_form, int n_terms, int n_batches, const int32_t* a, const int32_t* g, double* out,
+                          int rounded, double operand_scale, double* spectra);
 
 #ifdef __cplusplus
 }
