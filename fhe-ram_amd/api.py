@@ -193,6 +193,20 @@ _SYMBOLS = [
     ("fheram_bank_table_selector_alloc", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     ("fheram_bank_table_selector_create", C.c_int, [C.c_void_p, C.POINTER(I64P), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     ("fheram_bank_table_selector_alloc_fields", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_secret_create", C.c_int, [C.c_void_p, I64P, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_keys_encrypt_sk", C.c_int, [C.c_void_p, C.c_void_p, I64P, I64P, I64P]),
+    ("fheram_bank_address_encrypt_sk", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, I64P, I64P, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_fheuint_encrypt_sk", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, I64P, I64P, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_glwe_encrypt_sk", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, I64P, C.c_int, C.c_int, I64P, I64P, I64P]),
+    ("fheram_bank_glwe_decrypt", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, I64P, I64P]),
+    ("fheram_bank_ram_encrypt_sk", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, I64P, I64P]),
+    ("fheram_bank_regs_encrypt_sk", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, I64P, I64P]),
+    ("fheram_bank_table_encrypt_sk", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, I64P, I64P]),
+    ("fheram_bank_selector_encrypt_sk", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, I64P, I64P]),
+    ("fheram_bank_source_decrypt", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_CSelectSrc), C.c_int, I64P, I64P, C.POINTER(C.c_double)]),
+    ("fheram_bank_ram_decrypt", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    ("fheram_bank_regs_decrypt", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    ("fheram_bank_table_decrypt", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     ("fheram_timer_begin", C.c_int, [C.c_void_p]),
     ("fheram_timer_end", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("fheram_profile_enable", C.c_int, [C.c_void_p, C.c_int]),
@@ -417,9 +431,14 @@ class EvaluationKeysPrepared:
         noise = np.concatenate([source_xe.gaussian(n4 * n, noise_scale(p.k_evk_trace(), b2k)),
                                 source_xe.gaussian(n5 * n, noise_scale(p.k_evk_ggsw_inv(), b2k))])
         L = library()
-        atk_len, inv_len = L.fheram_atk_len(ram._h), L.fheram_evk_inv_len(ram._h)
+        if isinstance(ram, RamBank):   # (fheram_bank_keys_encrypt_sk: the same keys from the same draws, on the bank)
+            atk_len, inv_len = p.dnum_ct() * s4 * 2 * n, p.dnum_ggsw() * s5 * 2 * n
+            fn = L.fheram_bank_keys_encrypt_sk
+        else:
+            atk_len, inv_len = L.fheram_atk_len(ram._h), L.fheram_evk_inv_len(ram._h)
+            fn = L.fheram_keys_encrypt_sk
         std = np.zeros(p.log_n * atk_len + 2 * inv_len, dtype=np.int64) if keep_std else None
-        ram._chk(L.fheram_keys_encrypt_sk(ram._h, sk._h, _p(mask), _p(noise), _p(std) if keep_std else None))
+        ram._chk(fn(ram._h, sk._h, _p(mask), _p(noise), _p(std) if keep_std else None))
         gal = galois_elements(p.log_n)
         if keep_std:
             o = p.log_n * atk_len
@@ -469,7 +488,8 @@ class Address:
         mask = source_xa.uniform_limbs(n_glwe * size * n)
         noise = source_xe.gaussian(n_glwe * n, noise_scale(p.k_ggsw_addr(), b2k))
         out = C.c_void_p()
-        ram._chk(library().fheram_address_encrypt_sk(ram._h, sk._h, int(value), _p(mask), _p(noise), C.byref(out)))
+        fn = library().fheram_bank_address_encrypt_sk if isinstance(ram, RamBank) else library().fheram_address_encrypt_sk
+        ram._chk(fn(ram._h, sk._h, int(value), _p(mask), _p(noise), C.byref(out)))
         self._digits = None
         self._handles = {id(ram): _AddrHandle(out.value, ram)}
         return self
@@ -582,7 +602,8 @@ class FheUintPrepared:
         mask = source_xa.uniform_limbs(n_glwe * size * n)
         noise = source_xe.gaussian(n_glwe * n, noise_scale(k, b2k))
         out = C.c_void_p()
-        ram._chk(library().fheram_fheuint_encrypt_sk(ram._h, sk._h, int(value), n_bits, _p(mask), _p(noise), C.byref(out)))
+        fn = library().fheram_bank_fheuint_encrypt_sk if isinstance(ram, RamBank) else library().fheram_fheuint_encrypt_sk
+        ram._chk(fn(ram._h, sk._h, int(value), n_bits, _p(mask), _p(noise), C.byref(out)))
         return cls(ram, out.value, n_bits)
 
     def download(self) -> np.ndarray:
@@ -860,6 +881,23 @@ class Selector:
     def n_digits(self) -> int:
         return int(library().fheram_selector_n_digits(self._h))
 
+    def encrypt_sk(self, value: int, sk: "GLWESecret", source_xa, source_xe):
+        """fills this selector, in place, with Address::encrypt_sk's digits of `value` for the one-row RAM of max_addr = 2^bits over the
+        handle's own plan (fheram_bank_selector_encrypt_sk); the sources draw in the address's order"""
+        value = int(value)
+        if not isinstance(sk, GLWESecret):
+            raise FheRamError(1, "Selector.encrypt_sk takes a GLWESecret")
+        if not 0 <= value < (1 << 32):   # (a value of 2^bits or more is the library's refusal, address.rs:98)
+            raise FheRamError(1, f"Selector.encrypt_sk: {value} is not an unsigned 32-bit value")
+        p = self.bank.params
+        n, b2k = p.n(), p.basek()
+        size = -(-p.k_ggsw_addr() // b2k)
+        n_glwe = self.n_digits() * p.dnum_ct() * 2
+        mask = source_xa.uniform_limbs(n_glwe * size * n)
+        noise = source_xe.gaussian(n_glwe * n, noise_scale(p.k_ggsw_addr(), b2k))
+        self.bank._chk(library().fheram_bank_selector_encrypt_sk(self.bank._h, sk._h, self._h, value, _p(mask), _p(noise)))
+        self._derived_from = None
+
     def download(self) -> np.ndarray:
         """the std-form GGSW digits, [n_digits][ggsw_len]"""
         out = np.zeros((self.n_digits(), self.bank.params.ggsw_len()), dtype=np.int64)
@@ -900,6 +938,15 @@ class RegFile:
         if row.size != self._row().size:
             raise FheRamError(1, f"invalid data: expected {self.bank.params.word_size()}x1 GLWE rows (ram.rs:144-155)")
         self.bank._chk(library().fheram_bank_regs_upload(self.bank._h, self._h, _p(row)))
+
+    def encrypt_sk(self, data, sk: "GLWESecret", source_xa, source_xe):
+        """Ram::encrypt_sk of the one-row RAM of max_addr = 2^bits, straight into the row (fheram_bank_regs_encrypt_sk).  data: 2^bits *
+        word_size bytes, byte w of word j at data[j * word_size + w]; the sources draw in that small RAM's order."""
+        self.bank._one_row_encrypt(library().fheram_bank_regs_encrypt_sk, self, self.bits, data, sk, source_xa, source_xe)
+
+    def decrypt(self, sk: "GLWESecret"):
+        """every word, decrypted and decoded on the device (fheram_bank_regs_decrypt): (values int32 [2^bits][word_size], worst log2 noise)"""
+        return self.bank._one_row_decrypt(library().fheram_bank_regs_decrypt, self, self.bits, sk)
 
     def store(self) -> np.ndarray:
         """the row, [word_size][GLWE] (fheram_bank_regs_download)"""
@@ -996,6 +1043,15 @@ class Table:
             raise FheRamError(1, f"invalid data: expected {self.bank.params.word_size()}x1 GLWE rows (ram.rs:144-155)")
         self.bank._chk(library().fheram_bank_table_upload(self.bank._h, self._h, _p(row)))
 
+    def encrypt_sk(self, data, sk: "GLWESecret", source_xa, source_xe):
+        """Ram::encrypt_sk of the one-row RAM of max_addr = 2^bits, straight into the row (fheram_bank_table_encrypt_sk).  data: 2^bits *
+        word_size bytes, byte w of word j at data[j * word_size + w]; the sources draw in that small RAM's order."""
+        self.bank._one_row_encrypt(library().fheram_bank_table_encrypt_sk, self, self.bits, data, sk, source_xa, source_xe)
+
+    def decrypt(self, sk: "GLWESecret"):
+        """every word, decrypted and decoded on the device (fheram_bank_table_decrypt): (values int32 [2^bits][word_size], worst log2 noise)"""
+        return self.bank._one_row_decrypt(library().fheram_bank_table_decrypt, self, self.bits, sk)
+
     def load_plain(self, data):
         """public contents, 2^bits * word_size bytes in Ram::encrypt_sk's layout (byte w of word j at data[j * word_size + w]), as the
         trivial ciphertext: no host encryption, no keys, no secret (fheram_bank_table_load_plain)"""
@@ -1060,13 +1116,14 @@ def noise_scale(k: int, base2k: int = 17) -> float:
 
 
 class GLWESecret:
-    """GLWESecret + GLWESecretPrepared (examples/fhe-ram.rs:49-59) on a Ram's device: coefficients in {-1,0,1}."""
+    """GLWESecret + GLWESecretPrepared (examples/fhe-ram.rs:49-59) on a Ram's or a RamBank's device: coefficients in {-1,0,1}."""
 
     def __init__(self, ram: "Ram", sk):
         self.ram = ram
         self._h = None
         out = C.c_void_p()
-        ram._chk(library().fheram_secret_create(ram._h, _p(_i64(sk)), C.byref(out)))
+        fn = library().fheram_bank_secret_create if isinstance(ram, RamBank) else library().fheram_secret_create
+        ram._chk(fn(ram._h, _p(_i64(sk)), C.byref(out)))
         self._h = out.value
 
     def __del__(self):
@@ -2106,6 +2163,97 @@ class RamBank:
         if slots and (min(slots) < 0 or (max(slots) + 1) * per > hw.size):
             raise FheRamError(1, f"a host source names a slot outside host_words ({hw.size // per} slots of {self.params.word_size()} GLWEs)")
         return hw
+
+    # -- the setup side: encrypt and decrypt on the bank's device, sampling on the host
+    def _secret(self, sk):
+        if not isinstance(sk, GLWESecret):
+            raise FheRamError(1, "the bank's setup calls take a GLWESecret (GLWESecret(bank, sk))")
+        return sk._h
+
+    def _rows_draws(self, rows: int, source_xa, source_xe):
+        """the draws of Ram::encrypt_sk for `rows` rows per word, in the reference's order (word-major, then row)"""
+        p = self.params
+        n, b2k = p.n(), p.basek()
+        size = -(-p.k_glwe_ct() // b2k)
+        ws = p.word_size()
+        mask = source_xa.uniform_limbs(ws * rows * size * n)
+        noise = source_xe.gaussian(ws * rows * n, noise_scale(p.k_glwe_ct(), b2k))
+        return mask, noise
+
+    def _one_row_encrypt(self, fn, obj, bits: int, data, sk, source_xa, source_xe):
+        data = np.ascontiguousarray(np.asarray(data, dtype=np.uint8).ravel())
+        skh = self._secret(sk)
+        mask, noise = self._rows_draws(1, source_xa, source_xe)
+        self._chk(fn(self._h, obj._h, skh, data.ctypes.data_as(C.POINTER(C.c_uint8)), data.size, _p(mask), _p(noise)))
+
+    def _one_row_decrypt(self, fn, obj, bits: int, sk):
+        skh = self._secret(sk)
+        values = np.zeros(((1 << bits), self.params.word_size()), dtype=np.int32)
+        worst = C.c_double()
+        self._chk(fn(self._h, obj._h, skh, values.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(worst)))
+        return values, float(worst.value)
+
+    def encrypt_sk(self, member: int, data, sk: GLWESecret, source_xa, source_xe):
+        """Ram::encrypt_sk (ram.rs:129-167) of one member, straight into its rows (fheram_bank_ram_encrypt_sk).  data: max_addr *
+        word_size bytes; the sources draw in the reference's order, as Ram.encrypt_sk's."""
+        data = np.ascontiguousarray(np.asarray(data, dtype=np.uint8).ravel())
+        skh = self._secret(sk)
+        mask, noise = self._rows_draws(self.params.rows(), source_xa, source_xe)
+        self._chk(library().fheram_bank_ram_encrypt_sk(self._h, self._member(member), skh, data.ctypes.data_as(C.POINTER(C.c_uint8)), data.size,
+                                                       _p(mask), _p(noise)))
+
+    def glwe_encrypt_sk(self, sk: GLWESecret, n_glwe: int, size: int, k: int, pt, pt_col: int, source_xa, source_xe):
+        """Ram.glwe_encrypt_sk on the bank's secret (fheram_bank_glwe_encrypt_sk)"""
+        n = self.params.n()
+        mask = source_xa.uniform_limbs(n_glwe * size * n)
+        noise = source_xe.gaussian(n_glwe * n, noise_scale(k, self.params.basek()))
+        out = np.zeros((n_glwe, size * 2 * n), dtype=np.int64)
+        pt_size = 0
+        if pt is not None:
+            pt = _i64(pt).reshape(n_glwe, -1, n)
+            pt_size = pt.shape[1]
+        self._chk(library().fheram_bank_glwe_encrypt_sk(self._h, self._secret(sk), n_glwe, size, k, _p(pt) if pt is not None else None,
+                                                        pt_size, pt_col, _p(mask), _p(noise), _p(out)))
+        return out
+
+    def glwe_decrypt(self, sk: GLWESecret, cts, size: int = 3):
+        """Ram.glwe_decrypt on the bank's secret (fheram_bank_glwe_decrypt): normalised plaintext limbs [n_glwe][size][N]"""
+        n = self.params.n()
+        cts = _i64(cts).reshape(-1, size * 2 * n)
+        pt = np.zeros((cts.shape[0], size, n), dtype=np.int64)
+        self._chk(library().fheram_bank_glwe_decrypt(self._h, self._secret(sk), cts.shape[0], size, _p(cts), _p(pt)))
+        return pt
+
+    encrypt_word = Ram.encrypt_word      # (the example's encrypt_glwe: one GLWE per byte, through glwe_encrypt_sk above)
+    decrypt_coeff = Ram.decrypt_coeff    # (the example's decrypt_glwe + noise metric on downloaded ciphertexts, through glwe_decrypt above)
+
+    def decrypt_sources(self, sk: GLWESecret, srcs, wants=None):
+        """decrypts and decodes, on the device, coefficient 0 of the words `srcs` name (Src.member / list / select / regs / regs_old /
+        table; fheram_bank_source_decrypt): (values, log2 noise), int64 and float64 [n][word_size].  wants: [n][word_size] expected values,
+        or None (the decoded value itself is the expectation).  Nothing on the device changes."""
+        srcs = list(srcs)
+        if not srcs or not all(isinstance(s, Src) for s in srcs):
+            raise FheRamError(1, "decrypt_sources takes a non-empty list of Src")
+        n, ws = len(srcs), self.params.word_size()
+        if wants is not None:
+            wants = _i64(wants)
+            if wants.size != n * ws:
+                raise FheRamError(1, f"wants must hold {n} x {ws} values")
+        values = np.zeros((n, ws), dtype=np.int64)
+        noise = np.zeros((n, ws), dtype=np.float64)
+        arr = (_CSelectSrc * n)(*[_CSelectSrc(s.kind, s.index) for s in srcs])
+        self._chk(library().fheram_bank_source_decrypt(self._h, self._secret(sk), arr, n, _p(wants) if wants is not None else None, _p(values),
+                                                       noise.ctypes.data_as(C.POINTER(C.c_double))))
+        return values, noise
+
+    def decrypt(self, member: int, sk: GLWESecret):
+        """every word of one member, decrypted and decoded on the device (fheram_bank_ram_decrypt): (values int32 [max_addr][word_size],
+        worst log2 noise against each coefficient's own decoded value)"""
+        skh = self._secret(sk)
+        values = np.zeros((self.params.max_addr(), self.params.word_size()), dtype=np.int32)
+        worst = C.c_double()
+        self._chk(library().fheram_bank_ram_decrypt(self._h, self._member(member), skh, values.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(worst)))
+        return values, float(worst.value)
 
     def selftest_fail_select_alloc(self, nth: int):
         """self-test: the nth device allocation the select's buffers ask for from now on fails once (0: none)"""

@@ -856,4 +856,5 @@ int fheram_device_info(const fheram_ctx* c, char* name, size_t name_len, int* cu
 #include "select.hpp"
 #include "regs.hpp"
 #include "table.hpp"
+#include "bank_setup.hpp"
 #include "derive_list.hpp"

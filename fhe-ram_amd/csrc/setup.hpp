@@ -190,29 +190,43 @@ int fheram_glwe_decrypt(fheram_ctx* c, const fheram_secret* sk, int n_glwe, int 
     return rc;
 }
 
-int fheram_ram_encrypt_sk(fheram_ctx* c, const fheram_secret* sk, const uint8_t* data, size_t data_len,
-                          const int64_t* mask, const int64_t* noise) {
-    if (!c) return FHERAM_ERR_INVALID_ARG;
+}  // extern "C"
+namespace {
+// The one body of Ram::encrypt_sk (ram.rs:129-167, SubRam::encrypt_sk ram.rs:334-380) for every RAM shape the library holds rows of: the
+// context's own (fheram_ram_encrypt_sk), a bank member's, and the one-row RAMs of max_addr = 2^bits a register file or a table is
+// (bank_setup.hpp).  data: max_addr * ws bytes; the rows [ws][rows][GLWE] are encrypted straight into d_rows; mask / noise cover the rows
+// this holder owns (global rows shard + x * n_shards).  check_draws: every mask limb and noise coefficient is range-checked before
+// anything is staged, so that a refused call changes nothing (the bank's rule); without it a bad draw is refused at its own chunk.
+struct RamShape { size_t ws, rows, max_addr; int shard, n_shards; };
+int ram_encrypt_body(fheram_ctx* c, const fheram_secret* sk, const uint8_t* data, size_t data_len, const int64_t* mask, const int64_t* noise,
+                     const RamShape& sh, int32_t* d_rows, bool check_draws) {
     if (!data || !mask || !noise) return fail(c, FHERAM_ERR_INVALID_ARG, "null argument");
-    const size_t ws = (size_t)c->ws;
+    const size_t ws = sh.ws;
     if (data_len % ws != 0) return fail(c, FHERAM_ERR_INVALID_ARG, "invalid data: data.len()%ram_chunks != 0");            // ram.rs:144-148
-    if (data_len / ws != c->p.max_addr) return fail(c, FHERAM_ERR_INVALID_ARG, "invalid data: data.len()/ram_chunks != max_addr");   // ram.rs:150-155
+    if (data_len / ws != sh.max_addr) return fail(c, FHERAM_ERR_INVALID_ARG, "invalid data: data.len()/ram_chunks != max_addr");   // ram.rs:150-155
     const int k = (int)c->p.k_glwe_ct, S = fheram_ctx::S_CT;
     int rc = check_setup_args(c, sk, S, k);
     if (rc != FHERAM_OK) return rc;
     const int k_pt = (int)c->p.k_glwe_pt, size_pt = (k_pt + BASE2K - 1) / BASE2K;
     if (k_pt <= 0 || k_pt > 8 + BASE2K || size_pt > S) return fail(c, FHERAM_ERR_UNSUPPORTED, "k_glwe_pt out of range");
+    if (check_draws) {
+        int64_t bad = 0;
+        const size_t n_noise = ws * sh.rows * N, n_mask = n_noise * S;
+        for (size_t i = 0; i < n_mask; i++) bad |= (mask[i] > 65535) | (mask[i] < -65536);
+        for (size_t i = 0; i < n_noise; i++) bad |= (noise[i] >= NOISE_LIM) | (noise[i] <= -NOISE_LIM);
+        if (bad) return fail(c, FHERAM_ERR_RANGE, "mask limb outside [-2^16, 2^16) or |noise| >= 2^30");
+    }
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t G = fheram_ctx::GLWE, max_addr = c->p.max_addr;
+    const size_t G = fheram_ctx::GLWE, max_addr = sh.max_addr;
     const size_t CH = 256;   // rows staged per launch
-    std::vector<int32_t> pre(std::min(CH, c->rows) * G);
+    std::vector<int32_t> pre(std::min(CH, sh.rows) * G);
     int32_t limbs[4];
     for (size_t w = 0; w < ws; w++)                         // de-interleave by word, ram.rs:161-164
-        for (size_t x0 = 0; x0 < c->rows; x0 += CH) {       // chunks of N addresses per row, ram.rs:358-379
-            const size_t nx = std::min(CH, c->rows - x0);
+        for (size_t x0 = 0; x0 < sh.rows; x0 += CH) {       // chunks of N addresses per row, ram.rs:358-379
+            const size_t nx = std::min(CH, sh.rows - x0);
             std::fill(pre.begin(), pre.begin() + nx * G, 0);
             for (size_t x = 0; x < nx; x++) {
-                const size_t r = (size_t)c->shard + (x0 + x) * (size_t)c->n_shards;   // global row
+                const size_t r = (size_t)sh.shard + (x0 + x) * (size_t)sh.n_shards;   // global row
                 int32_t* pg = pre.data() + x * G;
                 for (size_t q = 0; q < (size_t)N; q++) {
                     const size_t a = r * N + q;
@@ -220,13 +234,58 @@ int fheram_ram_encrypt_sk(fheram_ctx* c, const fheram_secret* sk, const uint8_t*
                     encode_value((int64_t)(int8_t)data[a * ws + w], k_pt, size_pt, limbs);
                     for (int j = 0; j < size_pt; j++) pg[(size_t)(j * 2) * N + q] = limbs[j];
                 }
-                const size_t gi = w * c->rows + x0 + x;
+                const size_t gi = w * sh.rows + x0 + x;
                 if (!stage_random(pg, S, k, mask + gi * S * N, noise + gi * N))
                     return fail(c, FHERAM_ERR_RANGE, "mask limb outside [-2^16, 2^16) or |noise| >= 2^30");
             }
-            rc = encrypt_staged(c, sk->d_hat, c->d_data + (w * c->rows + x0) * G, pre, nullptr, (int)nx, S);
+            rc = encrypt_staged(c, sk->d_hat, d_rows + (w * sh.rows + x0) * G, pre, nullptr, (int)nx, S);
             if (rc != FHERAM_OK) return rc;
         }
+    return FHERAM_OK;
+}
+
+// The one body of Address::encrypt_sk's digits (address.rs:99-107 -> Coordinate::encrypt_sk, coordinate.rs:146-176) for every digit plan:
+// the context's (fheram_address_encrypt_sk) and a selector's own (fheram_bank_selector_encrypt_sk, bank_setup.hpp).  Digit d of the plan is
+// the GGSW of X^-chunk_d, chunk_d = ((value >> rsh_d) mod 2^width_d) << lsh_d, negated only where its coordinate's value is not zero
+// (coord_d: the coordinate digit d belongs to; coord_rsh / coord_bits: where the coordinate's value sits in `value`).  mask
+// [n_digits][3][2][4][N], noise [n_digits][3][2][N], digit-major; the digits are encrypted straight into d_ggsw.
+struct DigitPlan {
+    int n_digits = 0;
+    unsigned char rsh[32] = {}, width[32] = {}, lsh[32] = {};
+    unsigned char coord_rsh[32] = {}, coord_bits[32] = {};   // per digit: its coordinate's first bit and width in `value`
+};
+int digits_encrypt_body(fheram_ctx* c, const fheram_secret* sk, uint32_t value, const DigitPlan& pl, const int64_t* mask, const int64_t* noise,
+                        int32_t* d_ggsw) {
+    const int S = fheram_ctx::S_ADDR, k = (int)c->p.k_ggsw_addr, D = fheram_ctx::DNUM_CT;
+    const size_t glen = fheram_ctx::GLWE4;
+    const int n = pl.n_digits * D * 2;
+    std::vector<int32_t> pre((size_t)n * glen, 0), pt1((size_t)n * S * N, 0);
+    int gi = 0;
+    for (int d = 0; d < pl.n_digits; d++) {
+        const size_t rem_c = ((size_t)value >> pl.coord_rsh[d]) & (((size_t)1 << pl.coord_bits[d]) - 1);   // value of this coordinate; encrypted NEGATED (address.rs:104)
+        const bool neg = rem_c != 0;
+        const size_t chunk = (((size_t)value >> pl.rsh[d]) & (((size_t)1 << pl.width[d]) - 1)) << pl.lsh[d];   // coordinate.rs:146-176
+        const size_t pos = (neg && chunk != 0) ? (size_t)N - chunk : chunk;
+        const int32_t sgn = (neg && chunk != 0) ? -1 : 1;                // X^-chunk = -X^(N-chunk)
+        for (int r = 0; r < D; r++)
+            for (int ci = 0; ci < 2; ci++, gi++) {
+                int32_t* pg = pre.data() + (size_t)gi * glen;
+                if (ci == 0) pg[(size_t)(r * 2) * N + pos] = sgn;        // row r: m * 2^-((r+1)*base2k)
+                else pt1[((size_t)gi * S + r) * N + pos] = sgn;          //        m * s * ..., added to the mask column
+                if (!stage_random(pg, S, k, mask + (size_t)gi * S * N, noise + (size_t)gi * N))
+                    return fail(c, FHERAM_ERR_RANGE, "mask limb outside [-2^16, 2^16) or |noise| >= 2^30");
+            }
+    }
+    return encrypt_staged(c, sk->d_hat, d_ggsw, pre, &pt1, n, S);
+}
+}  // namespace
+extern "C" {
+
+int fheram_ram_encrypt_sk(fheram_ctx* c, const fheram_secret* sk, const uint8_t* data, size_t data_len,
+                          const int64_t* mask, const int64_t* noise) {
+    if (!c) return FHERAM_ERR_INVALID_ARG;
+    const int rc = ram_encrypt_body(c, sk, data, data_len, mask, noise, RamShape{(size_t)c->ws, c->rows, (size_t)c->p.max_addr, c->shard, c->n_shards}, c->d_data, false);
+    if (rc != FHERAM_OK) return rc;
     c->ram.initialized = true; c->ram.state = false;
     return FHERAM_OK;
 }
@@ -236,49 +295,30 @@ int fheram_address_encrypt_sk(fheram_ctx* c, const fheram_secret* sk, uint32_t v
     if (!c || !out) return FHERAM_ERR_INVALID_ARG;
     *out = nullptr;
     if (!mask || !noise) return fail(c, FHERAM_ERR_INVALID_ARG, "null argument");
-    const int S = fheram_ctx::S_ADDR, k = (int)c->p.k_ggsw_addr, D = fheram_ctx::DNUM_CT;
-    int rc = check_setup_args(c, sk, S, k);
+    int rc = check_setup_args(c, sk, fheram_ctx::S_ADDR, (int)c->p.k_ggsw_addr);
     if (rc != FHERAM_OK) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    {   // debug_assert!(self.base2d.max() > value) (address.rs:98)
-        unsigned bits = 0;
-        for (auto& b1 : c->base2d) for (int b : b1) bits += (unsigned)b;
-        if (bits < 32 && ((uint64_t)value >> bits) != 0)
-            return fail(c, FHERAM_ERR_INVALID_ARG, "self.base2d.max() > value (address.rs:98): address does not fit the digit plan");
-    }
-    const size_t glen = fheram_ctx::GLWE4;
-    const int n = c->n_digits * D * 2;
-    std::vector<int32_t> pre((size_t)n * glen, 0), pt1((size_t)n * S * N, 0);
-    size_t remain = value;
-    int gi = 0;
-    for (auto& base1d : c->base2d) {                                     // Address::encrypt_sk, address.rs:99-107
-        unsigned tot = 0;
+    DigitPlan pl;   // the context's plan, coordinate by coordinate (conversion.rs:45-62)
+    unsigned bits = 0;
+    for (auto& base1d : c->base2d) {
+        unsigned tot = 0, lsh = 0;
         for (int b : base1d) tot += (unsigned)b;
-        const size_t max = (size_t)1 << tot;
-        size_t rem_c = remain & (max - 1);                               // value of this coordinate; encrypted NEGATED (address.rs:104)
-        remain /= max;
-        const bool neg = rem_c != 0;
-        unsigned tot_base = 0;
-        for (int b : base1d) {                                           // Coordinate::encrypt_sk, coordinate.rs:146-176
-            const size_t chunk = (rem_c & (((size_t)1 << b) - 1)) << tot_base;
-            const size_t pos = (neg && chunk != 0) ? (size_t)N - chunk : chunk;
-            const int32_t sgn = (neg && chunk != 0) ? -1 : 1;            // X^-chunk = -X^(N-chunk)
-            for (int r = 0; r < D; r++)
-                for (int ci = 0; ci < 2; ci++, gi++) {
-                    int32_t* pg = pre.data() + (size_t)gi * glen;
-                    if (ci == 0) pg[(size_t)(r * 2) * N + pos] = sgn;    // row r: m * 2^-((r+1)*base2k)
-                    else pt1[((size_t)gi * S + r) * N + pos] = sgn;      //        m * s * ..., added to the mask column
-                    if (!stage_random(pg, S, k, mask + (size_t)gi * S * N, noise + (size_t)gi * N))
-                        return fail(c, FHERAM_ERR_RANGE, "mask limb outside [-2^16, 2^16) or |noise| >= 2^30");
-                }
-            rem_c >>= b;
-            tot_base += (unsigned)b;
+        for (int b : base1d) {
+            if (pl.n_digits >= 32) return fail(c, FHERAM_ERR_UNSUPPORTED, "digit plans of more than 32 digits");
+            const int d = pl.n_digits++;
+            pl.rsh[d] = (unsigned char)(bits + lsh); pl.width[d] = (unsigned char)b; pl.lsh[d] = (unsigned char)lsh;
+            pl.coord_rsh[d] = (unsigned char)bits; pl.coord_bits[d] = (unsigned char)tot;
+            lsh += (unsigned)b;
         }
+        bits += tot;
     }
+    // debug_assert!(self.base2d.max() > value) (address.rs:98)
+    if (bits < 32 && ((uint64_t)value >> bits) != 0)
+        return fail(c, FHERAM_ERR_INVALID_ARG, "self.base2d.max() > value (address.rs:98): address does not fit the digit plan");
     fheram_addr* a = new fheram_addr{c, nullptr, c->n_digits, c->device};
     hipError_t e = hipMalloc(&a->d_ggsw, (size_t)c->n_digits * fheram_ctx::GGSW * sizeof(int32_t));
     if (e != hipSuccess) { delete a; return fail(c, FHERAM_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e)); }
-    rc = encrypt_staged(c, sk->d_hat, a->d_ggsw, pre, &pt1, n, S);
+    rc = digits_encrypt_body(c, sk, value, pl, mask, noise, a->d_ggsw);
     if (rc != FHERAM_OK) { fheram_address_destroy(a); return rc; }
     *out = a;
     return FHERAM_OK;

@@ -488,10 +488,31 @@ public:
         std::vector<const fheram_addr*> h = handles(addresses);
         chk(fheram_bank_write_list(bank_, members.data(), h.data(), (int)h.size(), flat.data()));
     }
+    // ---- the setup side of a bank (include/fheram.h, "Setup side of a bank"): what Ram's setup side is to a context.  Sampling stays on the
+    // host (Source); every call waits for the device.
+    // GLWESecret + GLWESecretPrepared on the bank's device (fheram_bank_secret_create); the bank or the secret may go first
+    class Secret {
+    public:
+        Secret(Bank& bank, const std::vector<int64_t>& sk) { bank.chk(fheram_bank_secret_create(bank.bank_, sk.data(), &h_)); }
+        ~Secret() { if (h_) fheram_secret_destroy(h_); }
+        Secret(const Secret&) = delete;
+    private:
+        friend class Bank;
+        fheram_secret* h_ = nullptr;
+    };
     // an encrypted integer on the bank's device, from host ciphertexts [n_bits][fheram_fheuint_ggsw_len] (fheram_bank_fheuint_create)
     class FheUintPrepared {
     public:
         FheUintPrepared(Bank& bank, const std::vector<int64_t>& bits, int n_bits) { bank.chk(fheram_bank_fheuint_create(bank.bank_, bits.data(), n_bits, &h_)); }
+        // FheUintPrepared::encrypt_sk (conversion.rs:160-168) with the caller's samplers (fheram_bank_fheuint_encrypt_sk)
+        FheUintPrepared(Bank& bank, uint32_t value, const Secret& sk, Source& source_xa, Source& source_xe, int n_bits = 32) {
+            const size_t n = bank.params.n(), b = bank.params.basek(), k = bank.params.p.k_evk_ggsw_inv;
+            const size_t size = (k + b - 1) / b, dnum = (bank.params.p.k_ggsw_addr + b - 1) / b, glwes = (size_t)n_bits * dnum * 2;
+            std::vector<int64_t> mask(glwes * size * n), noise(glwes * n);
+            source_xa.uniform_limbs(mask.data(), mask.size());
+            source_xe.gaussian(noise.data(), noise.size(), noise_scale((uint32_t)k, (uint32_t)b));
+            bank.chk(fheram_bank_fheuint_encrypt_sk(bank.bank_, sk.h_, value, n_bits, mask.data(), noise.data(), &h_));
+        }
         ~FheUintPrepared() { if (h_) fheram_fheuint_destroy(h_); }
         FheUintPrepared(const FheUintPrepared&) = delete;
     private:
@@ -547,6 +568,15 @@ public:
         ~Selector() { if (h_) fheram_selector_destroy(h_); }
         Selector(const Selector&) = delete;
         int n_digits() const { return fheram_selector_n_digits(h_); }
+        // fills the selector, in place, with Address::encrypt_sk's digits of `value` over its own plan (fheram_bank_selector_encrypt_sk)
+        void encrypt_sk(Bank& bank, uint32_t value, const Secret& sk, Source& source_xa, Source& source_xe) {
+            const size_t n = bank.params.n(), b = bank.params.basek(), size = (bank.params.p.k_ggsw_addr + b - 1) / b;
+            const size_t glwes = (size_t)n_digits() * ((bank.params.k_glwe_ct() + b - 1) / b) * 2;   // dnum_ct rows x 2
+            std::vector<int64_t> mask(glwes * size * n), noise(glwes * n);
+            source_xa.uniform_limbs(mask.data(), mask.size());
+            source_xe.gaussian(noise.data(), noise.size(), noise_scale(bank.params.p.k_ggsw_addr, (uint32_t)b));
+            bank.chk(fheram_bank_selector_encrypt_sk(bank.bank_, sk.h_, h_, value, mask.data(), noise.data()));
+        }
     private:
         friend class Bank;
         friend class RegFile;
@@ -596,11 +626,8 @@ public:
         chk(fheram_bank_derive_list(bank_, ci.data(), (int)ci.size()));
         for (const DeriveItem& it : items) if (it.kind == FHERAM_DERIVE_ADDRESS) it.addr->digits.clear();
     }
-    // the std-form digits of an address of this bank, one vector per digit (fheram_bank_address_download)
-    std::vector<std::vector<int64_t>> address_digits(Address& a) {
-        // The digit count: the ABI has no bank form of fheram_n_digits, so it is get_base_2d's (base.rs:84-108) on the parameters alone — every
-        // coordinate takes the decomposition's widths in turn until the address bits run out.  A count the library disagrees with cannot pass
-        // unnoticed: fheram_bank_address_download fills n_digits of its own, and host_check.cpp compares the result's size.
+    // the digits of an address of this bank: get_base_2d's count (base.rs:84-108) on the parameters alone (address_digits says why)
+    size_t plan_digits() const {
         size_t bits = 0, n_digits = 0;
         for (size_t v = params.max_addr() - 1; v; v >>= 1) bits++;
         while (bits) {
@@ -608,6 +635,14 @@ public:
             for (uint32_t i = 0; i < params.p.n_decomp && bits; i++) { bits -= std::min<size_t>(bits, params.p.decomp_n[i]); n_digits++; }
             if (bits == before) throw Error(FHERAM_ERR_INVALID_ARG, "a decomposition without bits");
         }
+        return n_digits;
+    }
+    // the std-form digits of an address of this bank, one vector per digit (fheram_bank_address_download)
+    std::vector<std::vector<int64_t>> address_digits(Address& a) {
+        // The digit count: the ABI has no bank form of fheram_n_digits, so it is get_base_2d's (base.rs:84-108) on the parameters alone — every
+        // coordinate takes the decomposition's widths in turn until the address bits run out.  A count the library disagrees with cannot pass
+        // unnoticed: fheram_bank_address_download fills n_digits of its own, and host_check.cpp compares the result's size.
+        const size_t n_digits = plan_digits();
         const size_t ggsw = fheram_ggsw_len(nullptr);   // (the layout's length: the library's own figure, which needs no context)
         fheram_addr* h = nullptr;
         for (auto& kv : addr_) if (kv.first == &a) h = kv.second;
@@ -742,6 +777,18 @@ public:
             const std::vector<int64_t> flat = bank_.flat_words({src}, host_words);
             bank_.chk(fheram_bank_regs_write(bank_.bank_, h_, sel.h_, src, flat.empty() ? nullptr : flat.data()));
         }
+        // Ram::encrypt_sk of the one-row RAM of max_addr = 2^bits, straight into the row: data = 2^bits * word_size bytes
+        void encrypt_sk(const std::vector<uint8_t>& data, const Secret& sk, Source& source_xa, Source& source_xe) {
+            std::vector<int64_t> mask, noise;
+            bank_.rows_draws(1, source_xa, source_xe, mask, noise);
+            bank_.chk(fheram_bank_regs_encrypt_sk(bank_.bank_, h_, sk.h_, data.data(), data.size(), mask.data(), noise.data()));
+        }
+        // every word, decrypted and decoded on the device: [2^bits][word_size]; worst (optional): the worst log2 noise against the decoded values
+        std::vector<int32_t> decrypt(const Secret& sk, double* worst = nullptr) {
+            std::vector<int32_t> values(((size_t)1 << bits()) * bank_.params.word_size());
+            bank_.chk(fheram_bank_regs_decrypt(bank_.bank_, h_, sk.h_, values.data(), worst));
+            return values;
+        }
     private:
         Bank& bank_;
         fheram_regs* h_ = nullptr;
@@ -767,6 +814,18 @@ public:
             bank_.chk(fheram_bank_table_download(bank_.bank_, h_, row.data()));
             return row;
         }
+        // Ram::encrypt_sk of the one-row RAM of max_addr = 2^bits, straight into the row: data = 2^bits * word_size bytes
+        void encrypt_sk(const std::vector<uint8_t>& data, const Secret& sk, Source& source_xa, Source& source_xe) {
+            std::vector<int64_t> mask, noise;
+            bank_.rows_draws(1, source_xa, source_xe, mask, noise);
+            bank_.chk(fheram_bank_table_encrypt_sk(bank_.bank_, h_, sk.h_, data.data(), data.size(), mask.data(), noise.data()));
+        }
+        // every word, decrypted and decoded on the device: [2^bits][word_size]; worst (optional): the worst log2 noise against the decoded values
+        std::vector<int32_t> decrypt(const Secret& sk, double* worst = nullptr) {
+            std::vector<int32_t> values(((size_t)1 << bits()) * bank_.params.word_size());
+            bank_.chk(fheram_bank_table_decrypt(bank_.bank_, h_, sk.h_, values.data(), worst));
+            return values;
+        }
     private:
         friend class Bank;
         Bank& bank_;
@@ -791,6 +850,82 @@ public:
         chk(fheram_bank_table_result(bank_, first, n, out.data()));
         return split(out, (size_t)n);
     }
+    // ---- the setup side, continued: keys, members, addresses, words; decryption of what the bank leaves on the device
+    // EvaluationKeys::encrypt_sk + prepare on the bank (fheram_bank_keys_encrypt_sk); `keys` is marked as the set in use (its std forms stay empty)
+    void encrypt_keys(EvaluationKeysPrepared& keys, const Secret& sk, Source& source_xa, Source& source_xe) {
+        const size_t n = params.n(), b = params.basek();
+        const size_t s4 = (params.p.k_evk_trace + b - 1) / b, s5 = (params.p.k_evk_ggsw_inv + b - 1) / b;
+        const size_t dnum_ct = (params.k_glwe_ct() + b - 1) / b, dnum_ggsw = (params.p.k_ggsw_addr + b - 1) / b;   // parameters.rs:273-279
+        const size_t n4 = params.p.log_n * dnum_ct, n5 = 2 * dnum_ggsw;
+        std::vector<int64_t> mask((n4 * s4 + n5 * s5) * n), noise((n4 + n5) * n);
+        source_xa.uniform_limbs(mask.data(), n4 * s4 * n);
+        source_xa.uniform_limbs(mask.data() + n4 * s4 * n, n5 * s5 * n);
+        source_xe.gaussian(noise.data(), n4 * n, noise_scale(params.p.k_evk_trace, params.basek()));
+        source_xe.gaussian(noise.data() + n4 * n, n5 * n, noise_scale(params.p.k_evk_ggsw_inv, params.basek()));
+        chk(fheram_bank_keys_encrypt_sk(bank_, sk.h_, mask.data(), noise.data(), nullptr));
+        keys_ = &keys;
+    }
+    // Ram::encrypt_sk of one member, straight into its rows (fheram_bank_ram_encrypt_sk): data = max_addr * word_size bytes
+    void encrypt_sk(int member, const std::vector<uint8_t>& data, const Secret& sk, Source& source_xa, Source& source_xe) {
+        std::vector<int64_t> mask, noise;
+        rows_draws((params.max_addr() + params.n() - 1) / params.n(), source_xa, source_xe, mask, noise);
+        chk(fheram_bank_ram_encrypt_sk(bank_, member, sk.h_, data.data(), data.size(), mask.data(), noise.data()));
+    }
+    // Address::encrypt_sk on the bank (fheram_bank_address_encrypt_sk): *a becomes an ordinary address of this bank
+    void encrypt_address(Address& a, uint32_t value, const Secret& sk, Source& source_xa, Source& source_xe) {
+        const size_t n = params.n(), b = params.basek(), size = (params.p.k_ggsw_addr + b - 1) / b;
+        const size_t glwes = (size_t)plan_digits() * ((params.k_glwe_ct() + b - 1) / b) * 2;   // dnum_ct rows x 2
+        std::vector<int64_t> mask(glwes * size * n), noise(glwes * n);
+        source_xa.uniform_limbs(mask.data(), mask.size());
+        source_xe.gaussian(noise.data(), noise.size(), noise_scale(params.p.k_ggsw_addr, (uint32_t)b));
+        fheram_addr* h = nullptr;
+        chk(fheram_bank_address_encrypt_sk(bank_, sk.h_, value, mask.data(), noise.data(), &h));
+        for (auto& kv : addr_) if (kv.first == &a) { fheram_address_destroy(kv.second); kv.second = h; h = nullptr; }
+        if (h) addr_.emplace_back(&a, h);
+        a.digits.clear();
+    }
+    // encrypt_glwe of the example (examples/fhe-ram.rs:179-210) on the bank's secret: one GLWE per byte, value on coefficient 0 at precision k_pt
+    std::vector<Glwe> encrypt_word(const std::vector<uint8_t>& bytes, const Secret& sk, Source& source_xa, Source& source_xe) {
+        const size_t n = params.n(), b = params.basek(), size = (params.k_glwe_ct() + b - 1) / b, k_pt = params.p.k_glwe_pt, size_pt = (k_pt + b - 1) / b;
+        std::vector<int64_t> pt(bytes.size() * size_pt * n, 0), mask(bytes.size() * size * n), noise(bytes.size() * n), out(bytes.size() * size * 2 * n);
+        for (size_t i = 0; i < bytes.size(); i++) {   // encode_coeff_i64(value, k_pt, 0)
+            int64_t x = (int64_t)((uint64_t)bytes[i] << (size_pt * b - k_pt));
+            for (size_t j = size_pt; j-- > 0;) {
+                const int64_t half = (int64_t)1 << (b - 1), d = ((x + half) & (((int64_t)1 << b) - 1)) - half;
+                pt[(i * size_pt + j) * n] = d;
+                x = (x - d) >> b;
+            }
+        }
+        source_xa.uniform_limbs(mask.data(), mask.size());
+        source_xe.gaussian(noise.data(), noise.size(), noise_scale(params.k_glwe_ct(), (uint32_t)b));
+        chk(fheram_bank_glwe_encrypt_sk(bank_, sk.h_, (int)bytes.size(), (int)size, (int)params.k_glwe_ct(), pt.data(), (int)size_pt, 0, mask.data(), noise.data(), out.data()));
+        std::vector<Glwe> res;
+        for (size_t i = 0; i < bytes.size(); i++) res.emplace_back(out.begin() + i * glwe_len(), out.begin() + (i + 1) * glwe_len());
+        return res;
+    }
+    // GLWE::decrypt of downloaded ciphertexts on the bank's secret (fheram_bank_glwe_decrypt): normalised plaintext limbs [n][size][N]
+    std::vector<int64_t> decrypt(const std::vector<Glwe>& cts, const Secret& sk) {
+        std::vector<int64_t> flat, pt(cts.size() * glwe_len() / 2);
+        for (auto& g : cts) flat.insert(flat.end(), g.begin(), g.end());
+        chk(fheram_bank_glwe_decrypt(bank_, sk.h_, (int)cts.size(), (int)(glwe_len() / (2 * params.n())), flat.data(), pt.data()));
+        return pt;
+    }
+    // coefficient 0 of the words `srcs` name (src_member / src_list / src_select / src_regs / src_regs_old / src_table), decrypted and decoded on
+    // the device (fheram_bank_source_decrypt): values [n][word_size]; wants: the expected values or empty; log2_noise (optional): [n][word_size]
+    std::vector<int64_t> decrypt_sources(const Secret& sk, const std::vector<fheram_select_src>& srcs, const std::vector<int64_t>& wants = {}, std::vector<double>* log2_noise = nullptr) {
+        const size_t cnt = srcs.size() * params.word_size();
+        if (srcs.empty() || (!wants.empty() && wants.size() != cnt)) throw Error(FHERAM_ERR_INVALID_ARG, "decrypt_sources takes at least one source and no or n x word_size wants");
+        std::vector<int64_t> values(cnt);
+        if (log2_noise) log2_noise->assign(cnt, 0.0);
+        chk(fheram_bank_source_decrypt(bank_, sk.h_, srcs.data(), (int)srcs.size(), wants.empty() ? nullptr : wants.data(), values.data(), log2_noise ? log2_noise->data() : nullptr));
+        return values;
+    }
+    // every word of one member, decrypted and decoded on the device (fheram_bank_ram_decrypt): [max_addr][word_size]
+    std::vector<int32_t> decrypt(int member, const Secret& sk, double* worst = nullptr) {
+        std::vector<int32_t> values(params.max_addr() * params.word_size());
+        chk(fheram_bank_ram_decrypt(bank_, member, sk.h_, values.data(), worst));
+        return values;
+    }
     void sync() { chk(fheram_bank_sync(bank_)); }
     double roundoff_max() { double m = 0.0; chk(fheram_bank_roundoff_max(bank_, &m)); return m; }
     struct ChainStats { uint64_t launches = 0, redone = 0; };
@@ -799,6 +934,13 @@ public:
 
 private:
     fheram_bank* bank_ = nullptr;
+    // the draws of Ram::encrypt_sk for `rows` rows per word, in the reference's order
+    void rows_draws(size_t rows, Source& source_xa, Source& source_xe, std::vector<int64_t>& mask, std::vector<int64_t>& noise) const {
+        const size_t n = params.n(), glwes = params.word_size() * rows, size = (params.k_glwe_ct() + params.basek() - 1) / params.basek();
+        mask.resize(glwes * size * n); noise.resize(glwes * n);
+        source_xa.uniform_limbs(mask.data(), mask.size());
+        source_xe.gaussian(noise.data(), noise.size(), noise_scale(params.k_glwe_ct(), params.basek()));
+    }
     // host_words back to back, with every HOST slot the sources name inside them
     std::vector<int64_t> flat_words(const std::vector<fheram_select_src>& sources, const std::vector<std::vector<Glwe>>& host_words) const {
         std::vector<int64_t> flat;

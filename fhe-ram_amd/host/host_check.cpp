@@ -78,6 +78,52 @@ int main() {
         if (grp.size() != 2) return 8;
         try { fheram::Address a2; grp.read(a2, fheram::EvaluationKeysPrepared()); return 9; }
         catch (const fheram::Error& e) { std::printf("group refused as the reference would: %s\n", e.what()); }
+        {   // the setup side of a bank, every call once with the noiseless sampler: the bank needs no twin context and no host encryption, and
+            // what it leaves on the device is decrypted and decoded there
+            using B = fheram::Bank;
+            const fheram::Parameters sp(2, {3, 3, 3, 3}, 1 << 12);
+            B sb(sp, 2);
+            B::Secret bsk(sb, sk);
+            fheram::EvaluationKeysPrepared bkeys;
+            sb.encrypt_keys(bkeys, bsk, xa, xe);
+            std::vector<uint8_t> d0((size_t)(1 << 12) * 2), rd(32 * 2), td(128 * 2);
+            for (size_t i = 0; i < d0.size(); i++) d0[i] = (uint8_t)(i * 5 + 1);
+            for (size_t i = 0; i < rd.size(); i++) rd[i] = (uint8_t)(i * 3 + 2);
+            for (size_t i = 0; i < td.size(); i++) td[i] = (uint8_t)(i * 11 + 7);
+            auto plain = [](uint8_t b) { return (int)((int8_t)(uint8_t)(b << 5) >> 5); };   // the byte's low 3 bits, centred
+            for (int m = 0; m < 2; m++) sb.encrypt_sk(m, d0, bsk, xa, xe);
+            B::RegFile rf(sb, 5);
+            B::Table tb(sb, 7);
+            rf.encrypt_sk(rd, bsk, xa, xe);
+            tb.encrypt_sk(td, bsk, xa, xe);
+            double worst = 0.0;
+            const std::vector<int32_t> mv = sb.decrypt(1, bsk, &worst), rv = rf.decrypt(bsk), tv = tb.decrypt(bsk);
+            if (mv.size() != d0.size() || rv.size() != rd.size() || tv.size() != td.size()) return 24;
+            for (size_t i = 0; i < d0.size(); i++) if (mv[i] != plain(d0[i])) { std::printf("Bank::decrypt: byte %zu decodes to %d\n", i, mv[i]); return 24; }
+            for (size_t i = 0; i < rd.size(); i++) if (rv[i] != plain(rd[i])) { std::printf("RegFile::decrypt: byte %zu decodes to %d\n", i, rv[i]); return 24; }
+            for (size_t i = 0; i < td.size(); i++) if (tv[i] != plain(td[i])) { std::printf("Table::decrypt: byte %zu decodes to %d\n", i, tv[i]); return 24; }
+            if (worst > -40.0) { std::printf("Bank::decrypt: worst log2 noise %.2f of a noiseless member\n", worst); return 24; }
+            fheram::Address ba, bd;
+            sb.encrypt_address(ba, 777, bsk, xa, xe);
+            B::FheUintPrepared bfu(sb, 778u, bsk, xa, xe, 12);
+            sb.derive({&bfu}, {&bd});
+            B::Selector s5(sb, 5), s7(sb, B::Selector::Wide{}, 7);
+            s5.encrypt_sk(sb, 19, bsk, xa, xe);
+            s7.encrypt_sk(sb, 100, bsk, xa, xe);
+            std::vector<fheram::Address*> at_ba = {&ba}, at_bd = {&bd};
+            sb.read(at_ba, bkeys, 0);
+            sb.read_list({1}, at_bd, bkeys);
+            rf.read({&s5}, false);
+            sb.table_read({&tb}, {&s7}, false);
+            std::vector<double> nz;
+            const std::vector<int64_t> got = sb.decrypt_sources(bsk, {B::src_member(0), B::src_list(0), B::src_regs(0), B::src_table(0)}, {}, &nz);
+            const uint8_t want[8] = {d0[777 * 2], d0[777 * 2 + 1], d0[778 * 2], d0[778 * 2 + 1], rd[19 * 2], rd[19 * 2 + 1], td[100 * 2], td[100 * 2 + 1]};
+            for (size_t i = 0; i < 8; i++)
+                if (got[i] != plain(want[i]) || nz[i] > -4.0) { std::printf("Bank::decrypt_sources: value %zu is %lld (log2 noise %.2f), want %d\n", i, (long long)got[i], nz[i], plain(want[i])); return 24; }
+            const std::vector<int64_t> wpt = sb.decrypt(sb.encrypt_word({5, 200}, bsk, xa, xe), bsk);
+            if (((wpt[0] - (int64_t)plain(5) * (1 << 14)) & ((1 << 17) - 1)) != 0 || ((wpt[3 * sp.n()] - (int64_t)plain(200) * (1 << 14)) & ((1 << 17) - 1)) != 0) return 24;
+            std::printf("bank setup side: keys, members, register file, table, address, integer, selectors, words, decrypt on the device: ok\n");
+        }
         {   // Bank::read_list on a bank of two members: slice k is what the single-member read of members[k] returns, in any order and
             // with repeats; afterwards the bank is where those reads leave it.  Synthetic normalised limbs (the path is deterministic).
             const fheram::Parameters bp(4, {3, 3, 3, 3}, 1 << 12);

@@ -758,6 +758,61 @@ int fheram_bank_table_selector_alloc(fheram_bank* bank, int bits, fheram_selecto
 int fheram_bank_table_selector_create(fheram_bank* bank, const int64_t* const* ggsw, int n_ggsw, int bits, fheram_selector** out);
 int fheram_bank_table_selector_alloc_fields(fheram_bank* bank, const int* widths, int n_fields, fheram_selector** out);
 
+/* ---- Setup side of a bank: what "Setup side on the device" above is to a context, for a bank — so that a bank needs no
+ * twin context and no host encryption — and the decryption of what a bank leaves on the device.  SAMPLING STAYS ON THE HOST, exactly as
+ * there: the caller hands over mask limbs and noise polynomials, the same draws give the same ciphertexts.  Every call waits for the
+ * device (both streams idle before and after).  Every check runs before anything is enqueued or staged: a refused call changes nothing.
+ * (These declarations stand here and not beside the context's because they need the bank's handle types.) */
+/* fheram_secret_create on the bank's context: the secret is bound to the bank, freed with fheram_secret_destroy; destroying the bank
+ * first or the secret first are both safe. */
+int fheram_bank_secret_create(fheram_bank* bank, const int64_t* sk, fheram_secret** out);
+/* fheram_keys_encrypt_sk: the same keys from the same draws; afterwards everything fheram_bank_keys_load voids is void (what the members
+ * and the register files kept for a write). */
+int fheram_bank_keys_encrypt_sk(fheram_bank* bank, const fheram_secret* sk, const int64_t* mask, const int64_t* noise, int64_t* std_out);
+/* fheram_address_encrypt_sk / fheram_fheuint_encrypt_sk: an ordinary bank address / integer. */
+int fheram_bank_address_encrypt_sk(fheram_bank* bank, const fheram_secret* sk, uint32_t value, const int64_t* mask, const int64_t* noise,
+                                   fheram_addr** out);
+int fheram_bank_fheuint_encrypt_sk(fheram_bank* bank, const fheram_secret* sk, uint32_t value, int n_bits, const int64_t* mask,
+                                   const int64_t* noise, fheram_fheuint** out);
+/* fheram_glwe_encrypt_sk / fheram_glwe_decrypt on the bank's secret: the words of fheram_bank_write* and HOST candidates, and the
+ * decryption of downloaded results. */
+int fheram_bank_glwe_encrypt_sk(fheram_bank* bank, const fheram_secret* sk, int n_glwe, int size, int k, const int64_t* pt, int pt_size,
+                                int pt_col, const int64_t* mask, const int64_t* noise, int64_t* out);
+int fheram_bank_glwe_decrypt(fheram_bank* bank, const fheram_secret* sk, int n_glwe, int size, const int64_t* ct, int64_t* pt);
+/* Ram::encrypt_sk (ram.rs:129-167) of ONE member, straight into its rows: data = max_addr * word_size bytes, mask
+ * [word_size][rows][3][N], noise [word_size][rows][N] — int64-identical to fheram_ram_encrypt_sk on a context of the bank's
+ * fheram_params.  The member ends as fheram_bank_ram_upload leaves it; every other member is untouched.  Refusals: fheram_ram_encrypt_sk's
+ * ("invalid data: ..."), "no such member". */
+int fheram_bank_ram_encrypt_sk(fheram_bank* bank, int member, const fheram_secret* sk, const uint8_t* data, size_t data_len,
+                               const int64_t* mask, const int64_t* noise);
+/* The row of a register file / a table: Ram::encrypt_sk for the one-row RAM of max_addr = 2^bits — byte w of word j at coefficient j,
+ * zero behind word 2^bits - 1.  data = 2^bits * word_size bytes, mask [word_size][3][N], noise [word_size][N].  The object ends as
+ * fheram_bank_regs_upload / fheram_bank_table_upload leave it. */
+int fheram_bank_regs_encrypt_sk(fheram_bank* bank, fheram_regs* regs, const fheram_secret* sk, const uint8_t* data, size_t data_len,
+                                const int64_t* mask, const int64_t* noise);
+int fheram_bank_table_encrypt_sk(fheram_bank* bank, fheram_table* table, const fheram_secret* sk, const uint8_t* data, size_t data_len,
+                                 const int64_t* mask, const int64_t* noise);
+/* Fills an existing selector of any kind (plain, fields, wide; empty or not: overwritten like a derivation) with the digits
+ * Address::encrypt_sk (address.rs:86-109) gives for the one-row RAM of max_addr = 2^bits over the plan the handle stores: digit d = GGSW
+ * of X^-(((value >> rsh_d) mod 2^width_d) << lsh_d).  mask [n_digits][3][2][4][N], noise [n_digits][3][2][N], digit-major.
+ * FHERAM_ERR_INVALID_ARG: value >= 2^bits, a selector or secret of another bank. */
+int fheram_bank_selector_encrypt_sk(fheram_bank* bank, const fheram_secret* sk, fheram_selector* sel, uint32_t value, const int64_t* mask,
+                                    const int64_t* noise);
+/* Decrypts and decodes, ON THE DEVICE (k_decrypt_decode), coefficient 0 of the word_size ciphertexts of each of n words named as a
+ * select's candidates are — kinds MEMBER_RESULT, LIST_RESULT, SELECT_RESULT, REGS_RESULT, REGS_OLD, TABLE_RESULT (HOST and ZERO:
+ * FHERAM_ERR_INVALID_ARG); n * word_size <= 64.  want [n][word_size] or NULL (the decoded value itself is the expectation); values
+ * [n][word_size]: decode_coeff_i64 / 2^(k - k_pt), rounded half away from zero; log2_noise [n][word_size] or NULL: log2|res - (want <<
+ * (k - k_pt))| - k (-inf for 0), the example's metric (examples/fhe-ram.rs:224-237).  No result buffer, row, state flag or memo changes. */
+int fheram_bank_source_decrypt(fheram_bank* bank, const fheram_secret* sk, const fheram_select_src* srcs, int n, const int64_t* want,
+                               int64_t* values, double* log2_noise);
+/* The same for every data coefficient of every row of a member / a register file / a table: values = max_addr * word_size (2^bits *
+ * word_size) int32 in the interleaved order of the encrypting call's data; worst_log2_noise (may be NULL): the maximum over them of the
+ * metric against each coefficient's own decoded value — the margin to a decode failure.  FHERAM_ERR_UNINITIALIZED: no rows yet;
+ * FHERAM_ERR_STATE: between read_prepare_write and write (the rows are rotated).  Rows, state and memos are unchanged. */
+int fheram_bank_ram_decrypt(fheram_bank* bank, int member, const fheram_secret* sk, int32_t* values, double* worst_log2_noise);
+int fheram_bank_regs_decrypt(fheram_bank* bank, const fheram_regs* regs, const fheram_secret* sk, int32_t* values, double* worst_log2_noise);
+int fheram_bank_table_decrypt(fheram_bank* bank, const fheram_table* table, const fheram_secret* sk, int32_t* values, double* worst_log2_noise);
+
 /* ---- Measurement hooks (bench.py).  HIP events recorded on the context's own stream. */
 int fheram_timer_begin(fheram_ctx* ctx);
 int fheram_timer_end(fheram_ctx* ctx, float* elapsed_ms);
