@@ -24,6 +24,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
 I64P = C.POINTER(C.c_int64)
+builtins_list = list   # (RamBank.read_mix names its first group `list`)
 
 READ_BATCH_MAX = 8   # FHERAM_READ_BATCH_MAX (include/fheram.h)
 BANK_MAX = 8         # FHERAM_BANK_MAX
@@ -37,6 +38,7 @@ SRC_TABLE_RESULT = 8   # FHERAM_SRC_TABLE_RESULT: a bank's tables (kind 7 is unk
 TABLE_BITS_MAX = 12             # FHERAM_TABLE_BITS_MAX
 SELECTOR_WIDE_DIGITS_MAX = 5    # FHERAM_SELECTOR_WIDE_DIGITS_MAX
 SELECT_FIELDS_MAX = 5   # FHERAM_SELECT_FIELDS_MAX
+MIX_MAX = 8             # FHERAM_MIX_MAX
 DERIVE_LIST_MAX = 32          # FHERAM_DERIVE_LIST_MAX
 DERIVE_LIST_DIGITS_MAX = 64   # FHERAM_DERIVE_LIST_DIGITS_MAX
 DERIVE_ADDRESS, DERIVE_SELECTOR, DERIVE_FIELD = 0, 1, 2   # FHERAM_DERIVE_ADDRESS / _SELECTOR / _FIELD
@@ -74,6 +76,13 @@ class _CSelectLane(C.Structure):
 class _CDeriveItem(C.Structure):
     """fheram_derive_item (include/fheram.h): one address, selector or selector field of a derive list"""
     _fields_ = [("kind", C.c_int32), ("first_bit", C.c_int32), ("sign", C.c_int32), ("field", C.c_int32), ("fu", C.c_void_p), ("target", C.c_void_p)]
+
+
+class _CMixReads(C.Structure):
+    """fheram_mix_reads (include/fheram.h): the three groups of a fheram_bank_read_mix"""
+    _fields_ = [("members", C.POINTER(C.c_int)), ("addrs", C.POINTER(C.c_void_p)), ("n_list", C.c_int),
+                ("tables", C.POINTER(C.c_void_p)), ("table_sels", C.POINTER(C.c_void_p)), ("n_table", C.c_int),
+                ("regs", C.c_void_p), ("reg_sels", C.POINTER(C.c_void_p)), ("n_regs", C.c_int)]
 
 
 class _CConfig(C.Structure):
@@ -193,6 +202,7 @@ _SYMBOLS = [
     ("fheram_bank_table_selector_alloc", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     ("fheram_bank_table_selector_create", C.c_int, [C.c_void_p, C.POINTER(I64P), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     ("fheram_bank_table_selector_alloc_fields", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_read_mix", C.c_int, [C.c_void_p, C.POINTER(_CMixReads), I64P, I64P, I64P]),
     ("fheram_bank_secret_create", C.c_int, [C.c_void_p, I64P, C.POINTER(C.c_void_p)]),
     ("fheram_bank_keys_encrypt_sk", C.c_int, [C.c_void_p, C.c_void_p, I64P, I64P, I64P]),
     ("fheram_bank_address_encrypt_sk", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, I64P, I64P, C.POINTER(C.c_void_p)]),
@@ -2153,6 +2163,53 @@ class RamBank:
         out = np.zeros((max(n, 1), p.word_size(), p.glwe_len()), dtype=np.int64)
         self._chk(library().fheram_bank_table_result(self._h, first, n, _p(out)))
         return out
+
+    def read_mix(self, list=None, tables=None, regs=None, download: bool = True, keys: Optional[EvaluationKeysPrepared] = None):
+        """a read list, a table read and a register read as ONE operation with one top (fheram_bank_read_mix).
+        list = (members, addresses), tables = (tables, selectors), regs = (regfile, selectors); a group may be left out (None, or empty
+        lists) but not all three, and the groups hold at most MIX_MAX entries together.  Entry k of a group equals output k of
+        read_list / table_read / RegFile.read, and the bank is left where that sequence leaves it (list_result, table_result and
+        RegFile.result read the groups' outputs; a group left out keeps its kind's last outputs).  Returns (list, table, regs): int64
+        [n][word_size][GLWE] per group, None for a group left out; download=False: no host wait, (None, None, None)."""
+        members, addresses = (builtins_list(list[0]), builtins_list(list[1])) if list is not None else ([], [])
+        tabs, tsels = (builtins_list(tables[0]), builtins_list(tables[1])) if tables is not None else ([], [])
+        regfile, rsels = (regs[0], builtins_list(regs[1])) if regs is not None else (None, [])
+        if len(addresses) != len(members) or len(tsels) != len(tabs):
+            raise FheRamError(1, f"read_mix takes as many addresses as members and as many selectors as tables, got {len(members)} / {len(addresses)} and {len(tabs)} / {len(tsels)}")
+        nl, nt, nr = len(members), len(tabs), len(rsels)
+        if nl + nt + nr < 1:
+            raise FheRamError(1, "read_mix takes at least one read: all three groups are empty")
+        if nl + nt + nr > MIX_MAX:
+            raise FheRamError(1, f"read_mix takes at most MIX_MAX = {MIX_MAX} entries in all, got {nl + nt + nr}")
+        if not all(isinstance(a, Address) for a in addresses):
+            raise FheRamError(1, "every list entry must be an Address (a null address is refused)")
+        if not all(isinstance(t, Table) for t in tabs) or not all(isinstance(s, Selector) for s in tsels + rsels):
+            raise FheRamError(1, "read_mix takes Tables and Selectors")
+        if nr and not isinstance(regfile, RegFile):
+            raise FheRamError(1, "the regs group of read_mix takes a RegFile")
+        members = [int(m) for m in members]
+        for m in members:
+            self._member(m)
+        if keys is not None:
+            self._use_keys(keys)
+        cm = _CMixReads()
+        keep = []   # the arrays the struct points to
+
+        def arr(ctype, values):
+            a = (ctype * max(len(values), 1))(*values)
+            keep.append(a)
+            return a
+
+        if nl:
+            cm.members, cm.addrs, cm.n_list = arr(C.c_int, members), arr(C.c_void_p, [a._bank(self) for a in addresses]), nl
+        if nt:
+            cm.tables, cm.table_sels, cm.n_table = arr(C.c_void_p, [t._h for t in tabs]), arr(C.c_void_p, [s._h for s in tsels]), nt
+        if nr:
+            cm.regs, cm.reg_sels, cm.n_regs = regfile._h, arr(C.c_void_p, [s._h for s in rsels]), nr
+        p = self.params
+        outs = [np.zeros((n, p.word_size(), p.glwe_len()), dtype=np.int64) if (download and n) else None for n in (nl, nt, nr)]
+        self._chk(library().fheram_bank_read_mix(self._h, C.byref(cm), *[_p(o) if o is not None else None for o in outs]))
+        return tuple(outs)
 
     def _host_words(self, host_words, slots):
         """host_words as int64, with the named slots inside it"""

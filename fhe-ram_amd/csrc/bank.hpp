@@ -64,6 +64,9 @@ struct fheram_bank {
     TableBufs tabs;
     std::vector<fheram_table*> tables;
     int table_n = 0;
+    // fheram_bank_read_mix (mix.hpp): its buffers, and where the last operation of each kind left its outputs (its own set, or the mix's)
+    MixBufs mix;
+    ResHome list_home, table_home, regs_home;
 };
 
 namespace {
@@ -276,7 +279,12 @@ int bank_write_set(fheram_bank* b, const MemberSet& s, const fheram_addr* const*
     HIPCHK(c, hipGetLastError());
     return FHERAM_OK;
 }
-int list_result(fheram_bank* b, int first, int n, int64_t* out) { return reads_export(b->c, b->list, (size_t)first * b->mws, (size_t)n * b->mws, out); }
+int list_result(fheram_bank* b, int first, int n, int64_t* out) {
+    const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
+    const ResRun run{b->list_home.res + (size_t)first * per, (size_t)n * per};
+    return result_export(b->c, &run, 1, b->list_home.h, b->list_home.d_h, out);
+}
+void list_home_own(fheram_bank* b) { b->list_home = ResHome{b->list.res, b->list.h_res, b->list.d_h_res, -1}; }
 
 }  // namespace
 
@@ -323,6 +331,7 @@ void fheram_bank_destroy(fheram_bank* b) {
     lane_table_free(b->lanes);
     regs_bank_release(b);
     table_bank_release(b);
+    mix_bufs_free(b->mix);
     fheram_ctx_destroy(b->c);
     delete b;
 }
@@ -439,6 +448,7 @@ int fheram_bank_read_list(fheram_bank* b, const int* members, const fheram_addr*
         if (rc != FHERAM_OK) return rc;
         launch_copy(c, member_slot(b, c->d_res, s.m[0]), ref(b->list.res, G, 0), 1, b->mws);
         b->list_n = 1;
+        list_home_own(b);
         HIPCHK(c, hipGetLastError());
         return out ? list_result(b, 0, 1, out) : FHERAM_OK;
     }
@@ -451,6 +461,7 @@ int fheram_bank_read_list(fheram_bank* b, const int* members, const fheram_addr*
             if (last >= 0) launch_copy(c, o.slice(ref(b->list.res, G, 0), last), member_slot(b, c->d_res, m), 1, b->mws);
         }
         b->list_n = n;
+        list_home_own(b);
     });
 }
 // n independent Ram::read_prepare_write (ram.rs:196-222), entry k on member members[k], as one operation (header comment)

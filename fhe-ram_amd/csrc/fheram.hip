@@ -858,3 +858,4 @@ int fheram_device_info(const fheram_ctx* c, char* name, size_t name_len, int* cu
 #include "table.hpp"
 #include "bank_setup.hpp"
 #include "derive_list.hpp"
+#include "mix.hpp"

@@ -400,6 +400,30 @@ void table_bufs_free(TableBufs& B) {
     B = TableBufs{};
 }
 
+// fheram_bank_read_mix's own buffers (mix.hpp): per ciphertext of the shared top the products' output, a temporary and THREE result
+// buffers — a mix writes the one that holds no empty group's last outputs — and the pinned result buffer.  The digits of its one-row
+// groups are prepared into the tables' and the register files' own (TableBufs::prep, RegsBufs::prep: a group that is not empty has its
+// object, so they exist).  Allocated whole by the bank's first fheram_bank_read_mix, freed with the bank.
+struct MixBufs {
+    int cap = 0;                                                                  // ciphertexts: min(FHERAM_MIX_MAX * word_size, 64); 0: not allocated
+    int32_t *ep = nullptr, *tmp = nullptr, *res[3] = {nullptr, nullptr, nullptr}; // [cap] GLWE
+    int64_t *h_res = nullptr, *d_h_res = nullptr;                                 // pinned, device-visible: the results as int64 (+ the monitor's maximum)
+};
+void mix_bufs_free(MixBufs& M) {
+    void* bufs[] = {M.ep, M.tmp, M.res[0], M.res[1], M.res[2]};
+    for (void* p : bufs) if (p) hipFree(p);
+    if (M.h_res) hipHostFree(M.h_res);
+    M = MixBufs{};
+}
+// Where the last read list / table read / register read of a bank left its outputs: the operation's own buffer set, or the mix's when a
+// fheram_bank_read_mix ran that kind last.  select_source and the three _result downloads follow it.  mix_slot: which of the mix's
+// result buffers (-1: none of them).
+struct ResHome {
+    const int32_t* res = nullptr;                    // output 0 of the kind
+    int64_t *h = nullptr, *d_h = nullptr;            // the pinned buffer a download of it goes through
+    int mix_slot = -1;
+};
+
 // The one result export: every run (source, int32 count) is widened by the device into the pinned buffer h (device address d_h), back to
 // back, with the monitor's maximum as it stood then behind the last (the export kernel copies it there); out != nullptr: copied out.
 struct ResRun { const int32_t* src; size_t n; };

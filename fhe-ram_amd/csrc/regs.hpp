@@ -321,6 +321,7 @@ int fheram_bank_regs_read(fheram_bank* b, const fheram_regs* r, const fheram_sel
     one_row_reads(b, OneRowBufs{R.fan, R.ep, R.tmp, R.res, R.prep}, sels, n);
     HIPCHK(c, hipGetLastError());
     b->regs_n = n;
+    b->regs_home = ResHome{R.res, R.h_res, R.d_h_res, -1};
     if (!out) return FHERAM_OK;
     const ResRun run{R.res, (size_t)Y * fheram_ctx::GLWE};
     return result_export(c, &run, 1, R.h_res, R.d_h_res, out);
@@ -334,8 +335,8 @@ int fheram_bank_regs_result(fheram_bank* b, int first, int n, int64_t* out) {
         return fail(c, FHERAM_ERR_INVALID_ARG, "outputs [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") are empty or outside the last register read's " + std::to_string(b->regs_n) + " outputs");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
-    const ResRun run{b->regs.res + (size_t)first * per, (size_t)n * per};
-    return result_export(c, &run, 1, b->regs.h_res, b->regs.d_h_res, out);
+    const ResRun run{b->regs_home.res + (size_t)first * per, (size_t)n * per};
+    return result_export(c, &run, 1, b->regs_home.h, b->regs_home.d_h, out);
 }
 // Ram::read_prepare_write (ram.rs:196-222) of the one-row RAM (header comment)
 int fheram_bank_regs_read_prepare_write(fheram_bank* b, fheram_regs* r, const fheram_selector* sel, int64_t* out) {

@@ -137,11 +137,11 @@ const int32_t* select_source(const fheram_bank* b, const fheram_select_src& s, c
     switch (s.kind) {
     case FHERAM_SRC_HOST: return d_host + (size_t)s.index * per;
     case FHERAM_SRC_MEMBER_RESULT: return (b->ram[s.index].res_in_trtop ? c->d_trtop : c->d_res) + (size_t)s.index * per;   // (as set_result)
-    case FHERAM_SRC_LIST_RESULT: return b->list.res + (size_t)s.index * per;
+    case FHERAM_SRC_LIST_RESULT: return b->list_home.res + (size_t)s.index * per;   // (the kind's own buffers, or the last mix's: path.hpp ResHome)
     case FHERAM_SRC_SELECT_RESULT: return b->sel.res + (size_t)s.index * per;
-    case FHERAM_SRC_REGS_RESULT: return b->regs.res + (size_t)s.index * per;
+    case FHERAM_SRC_REGS_RESULT: return b->regs_home.res + (size_t)s.index * per;
     case FHERAM_SRC_REGS_OLD: return b->regs_old;
-    case FHERAM_SRC_TABLE_RESULT: return b->tabs.res + (size_t)s.index * per;
+    case FHERAM_SRC_TABLE_RESULT: return b->table_home.res + (size_t)s.index * per;
     default: return nullptr;
     }
 }

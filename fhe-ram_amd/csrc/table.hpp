@@ -228,6 +228,7 @@ int fheram_bank_table_read(fheram_bank* b, const fheram_table* const* tables, co
     one_row_reads(b, OneRowBufs{B.fan, B.ep, B.tmp, B.res, B.prep}, sels, n);
     HIPCHK(c, hipGetLastError());
     b->table_n = n;
+    b->table_home = ResHome{B.res, B.h_res, B.d_h_res, -1};
     if (!out) return FHERAM_OK;
     const ResRun run{B.res, (size_t)Y * fheram_ctx::GLWE};
     return result_export(c, &run, 1, B.h_res, B.d_h_res, out);
@@ -241,8 +242,8 @@ int fheram_bank_table_result(fheram_bank* b, int first, int n, int64_t* out) {
         return fail(c, FHERAM_ERR_INVALID_ARG, "outputs [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") are empty or outside the last table read's " + std::to_string(b->table_n) + " outputs");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
-    const ResRun run{b->tabs.res + (size_t)first * per, (size_t)n * per};
-    return result_export(c, &run, 1, b->tabs.h_res, b->tabs.d_h_res, out);
+    const ResRun run{b->table_home.res + (size_t)first * per, (size_t)n * per};
+    return result_export(c, &run, 1, b->table_home.h, b->table_home.d_h, out);
 }
 
 // WIDE selectors: the selectors of select.hpp with the table's bound on the bits (selector_new says what else is refused)

@@ -1,6 +1,9 @@
-// Included TWICE by kernels.hpp (no include guard): k_trace_tail (one read) and k_trace_tail_t (several addresses: a batch, a bank range, a read list).
-//   FK_TAIL_NAME : kernel name;  FK_TAIL_ARGS : TailArgs or TailTableArgs;  FK_TAIL_TABLE : 1 = the products' operands of ciphertext
-//   y are those of address y / ws (TailTableArgs), 0 = one address
+// Included TWICE by kernels.hpp (no include guard): k_trace_tail (one read) and k_trace_tail_t (several addresses: a batch, a bank range, a read list),
+// and a third time by mix.hip: k_trace_tail_x (fheram_bank_read_mix: every ciphertext its own source, digits and product count).
+//   FK_TAIL_NAME : kernel name;  FK_TAIL_ARGS : TailArgs, TailTableArgs or TailMixArgs;  FK_TAIL_TABLE : 1 = the products' operands of ciphertext
+//   y are those of address y / ws (TailTableArgs), 0 = one address, 2 = group g reads its source pointer, the pointer to its prepared
+//   digits and its own product count from ta.x (mix.hpp MixGroupArgs; one ciphertext per group, gx = 1): n_ep is uniform within a group and
+//   groups never wait for each other, so nothing else changes
 template <int SX, int SK, int SO>
 __global__ __launch_bounds__(T, T / 256) void FK_TAIL_NAME(FK_TAIL_ARGS ta) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -18,7 +21,11 @@ __global__ __launch_bounds__(T, T / 256) void FK_TAIL_NAME(FK_TAIL_ARGS ta) {
     int* flag = reinterpret_cast<int*>(data + 2 * LDS_DATA);   // the third exchange buffer is not used here
     unsigned* ctr = ta.sync + g * 32;
     unsigned* abortp = ta.sync + TAIL_GROUPS * 32;
+#if FK_TAIL_TABLE == 2
+    const int n_ep = ta.x.n_ep[g], n_all = n_ep + ta.n;
+#else
     const int n_ep = ta.n_ep, n_all = ta.n_ep + ta.n;
+#endif
     int s = 0;   // (lives past the step loop: s < n_all there = this workgroup left early, its group gave up)
     {   // the monitor's scope (not indented): its flush comes BEFORE the workgroup counts itself as gone, so the host words below are the launch's last stores
     RoMonitor ro_mon(lds, ta.tw);
@@ -28,11 +35,16 @@ __global__ __launch_bounds__(T, T / 256) void FK_TAIL_NAME(FK_TAIL_ARGS ta) {
     const bool ep_member = m < GE;
     const long ct = (long)(g / ta.gx);
     const long cx = (long)(g % ta.gx);
-#if FK_TAIL_TABLE
+#if FK_TAIL_TABLE == 2
+#define FK_TAIL_OPND(i) (ta.x.ggsw[g] + (long)(i) * ta.x.ggsw_stride)
+#define FK_TAIL_SRC GlweRef{const_cast<int32_t*>(ta.x.src[g]), 0, 0}   // the ciphertext itself: a packed row in an arena, a table's row, a register file's
+#elif FK_TAIL_TABLE
     const long oset = (ct / ta.ws) * ta.opnd_stride;   // this ciphertext's address: its prepared digits
 #define FK_TAIL_OPND(i) (ta.ggsw[i] + oset)
+#define FK_TAIL_SRC ta.src
 #else
 #define FK_TAIL_OPND(i) ta.ggsw[i]
+#define FK_TAIL_SRC ta.src
 #endif
     double* const big0 = ta.big + (long)g * BIG_STRIDE * SX;   // + step parity * TAIL_GROUPS * BIG_STRIDE * SX (see the normalisation phase)
     OpRegs kop, kop1;                 // the operand(s) of the coming step: a trace key polynomial, or the two GGSW polynomials of a product
@@ -54,7 +66,7 @@ __global__ __launch_bounds__(T, T / 256) void FK_TAIL_NAME(FK_TAIL_ARGS ta) {
     auto out_of = [&](int s_) -> GlweRef { return s_ < n_ep ? (s_ == n_ep - 1 ? ta.ep_out : ta.buf[s_ & 1]) : ta.buf[(s_ - n_ep) & 1]; };
 #pragma unroll 1
     for (; s < n_all; s++) {
-        const GlweRef rin = (s == 0) ? ta.src : out_of(s - 1);
+        const GlweRef rin = (s == 0) ? FK_TAIL_SRC : out_of(s - 1);
         const GlweRef rout = out_of(s);
         const int32_t* ap = rin.p + ct * rin.sy + cx * rin.sx;
         int32_t* op = rout.p + ct * rout.sy + cx * rout.sx;
@@ -294,3 +306,4 @@ __global__ __launch_bounds__(T, T / 256) void FK_TAIL_NAME(FK_TAIL_ARGS ta) {
     }
 }
 #undef FK_TAIL_OPND
+#undef FK_TAIL_SRC

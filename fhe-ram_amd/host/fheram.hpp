@@ -790,6 +790,7 @@ public:
             return values;
         }
     private:
+        friend class Bank;
         Bank& bank_;
         fheram_regs* h_ = nullptr;
     };
@@ -849,6 +850,38 @@ public:
         std::vector<int64_t> out((size_t)n * params.word_size() * glwe_len());
         chk(fheram_bank_table_result(bank_, first, n, out.data()));
         return split(out, (size_t)n);
+    }
+    // ---- mixed reads (include/fheram.h): a read list, a table read and a register read as ONE operation with one top.  A group
+    // may be empty (regs: nullptr and no selectors) but not all three; at most FHERAM_MIX_MAX entries in all.  Entry k of a group equals
+    // output k of read_list / table_read / RegFile::read, and list_result / table_result / RegFile::result read the groups' outputs afterwards.
+    struct MixResult { std::vector<std::vector<Glwe>> list, table, regs; };   // (download = false: all empty)
+    MixResult read_mix(const std::vector<int>& members, std::vector<Address*>& addresses, const std::vector<const Table*>& tables,
+                       const std::vector<const Selector*>& table_sels, const RegFile* regs, const std::vector<const Selector*>& reg_sels,
+                       const EvaluationKeysPrepared& keys, bool download = true) {
+        if (addresses.size() != members.size() || table_sels.size() != tables.size())
+            throw Error(FHERAM_ERR_INVALID_ARG, "read_mix takes as many addresses as members and as many selectors as tables");
+        const size_t nl = members.size(), nt = tables.size(), nr = reg_sels.size();
+        if (nl + nt + nr < 1) throw Error(FHERAM_ERR_INVALID_ARG, "read_mix takes at least one read: all three groups are empty");
+        if (nl + nt + nr > FHERAM_MIX_MAX) throw Error(FHERAM_ERR_INVALID_ARG, "read_mix takes at most FHERAM_MIX_MAX entries in all");
+        if (nr && !regs) throw Error(FHERAM_ERR_INVALID_ARG, "the regs group of read_mix takes a register file");
+        use(keys);
+        std::vector<const fheram_addr*> ah = handles(addresses);
+        std::vector<const fheram_table*> th;
+        std::vector<const fheram_selector*> tsh, rsh;
+        for (const Table* t : tables) { if (!t) throw Error(FHERAM_ERR_INVALID_ARG, "null table"); th.push_back(t->h_); }
+        for (const Selector* x : table_sels) { if (!x) throw Error(FHERAM_ERR_INVALID_ARG, "null selector"); tsh.push_back(x->h_); }
+        for (const Selector* x : reg_sels) { if (!x) throw Error(FHERAM_ERR_INVALID_ARG, "null selector"); rsh.push_back(x->h_); }
+        const fheram_mix_reads reads{members.data(), ah.data(), (int)nl, th.data(), tsh.data(), (int)nt, nr ? regs->h_ : nullptr, rsh.data(), (int)nr};
+        const size_t one = params.word_size() * glwe_len();
+        std::vector<int64_t> lo(download ? nl * one : 0), to(download ? nt * one : 0), ro(download ? nr * one : 0);
+        chk(fheram_bank_read_mix(bank_, &reads, lo.empty() ? nullptr : lo.data(), to.empty() ? nullptr : to.data(), ro.empty() ? nullptr : ro.data()));
+        MixResult res;
+        if (download) {
+            if (nl) res.list = split(lo, nl);
+            if (nt) res.table = split(to, nt);
+            if (nr) res.regs = split(ro, nr);
+        }
+        return res;
     }
     // ---- the setup side, continued: keys, members, addresses, words; decryption of what the bank leaves on the device
     // EvaluationKeys::encrypt_sk + prepare on the bank (fheram_bank_keys_encrypt_sk); `keys` is marked as the set in use (its std forms stay empty)

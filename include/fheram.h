@@ -758,6 +758,39 @@ int fheram_bank_table_selector_alloc(fheram_bank* bank, int bits, fheram_selecto
 int fheram_bank_table_selector_create(fheram_bank* bank, const int64_t* const* ggsw, int n_ggsw, int bits, fheram_selector** out);
 int fheram_bank_table_selector_alloc_fields(fheram_bank* bank, const int* widths, int n_fields, fheram_selector** out);
 
+/* ---- MIXED READS: a read list, a table read and a register read of one bank as ONE operation.
+ * *** CONTRACT-COMPATIBLE ONLY *** as its three parts are.  The reads of a VM step — the fetch from a table, rs1 / rs2 from the
+ * register file, the data read of a member — take their addresses and selectors from one derive list launch and do not depend on each
+ * other; as three calls each ends in its own pass through the latency-bound end of a read.  Here the groups go their own ways until
+ * every ciphertext is a packed row and then share one top: with at most 8 ciphertexts whose digit counts are 0 or 2..4 that is ONE
+ * launch (the products of every ciphertext and the trace), otherwise the products entry by entry and one trace over all of them.
+ * A call names up to three groups, any of which may be empty (n = 0; its pointers are then not read) but not all three:
+ *   list   members[n_list], addrs[n_list]        the rules of fheram_bank_read_list
+ *   table  tables[n_table], table_sels[n_table]  the rules of fheram_bank_table_read (all selectors of the group share the digit count)
+ *   regs   regs, reg_sels[n_regs]                the rules of fheram_bank_regs_read
+ * with n_list + n_table + n_regs <= FHERAM_MIX_MAX and (n_list + n_table + n_regs) * word_size <= 64.  Every check runs before anything
+ * is enqueued and a refused call changes nothing; each group is refused with the codes of its single call, the totals (and a null
+ * argument, a negative count) with FHERAM_ERR_INVALID_ARG.
+ * Entry k of a group is int64-identical to output k of that group's single call, and the bank is left exactly where the sequence
+ * read_list(list), table_read(table), regs_read(regs) leaves it: FHERAM_SRC_LIST_RESULT / _TABLE_RESULT / _REGS_RESULT name the outputs
+ * of their groups and fheram_bank_read_list_result / _table_result / _regs_result download them; the kinds of EMPTY groups keep their
+ * last outputs; no row, state flag, tree, memo, select result or REGS_OLD changes, and a member or a register file between its two
+ * halves resumes as before.  list_out / table_out / regs_out: [n][word_size][GLWE] of the group, each may be NULL; with all three NULL
+ * the call waits for nothing.  The mix's buffers are allocated whole by the bank's first call (FHERAM_ERR_DEVICE if that fails). */
+#define FHERAM_MIX_MAX 8
+typedef struct fheram_mix_reads {
+    const int* members;                        /* list: [n_list] */
+    const fheram_addr* const* addrs;           /*       [n_list] */
+    int n_list;
+    const fheram_table* const* tables;         /* table: [n_table] */
+    const fheram_selector* const* table_sels;  /*        [n_table] */
+    int n_table;
+    const fheram_regs* regs;                   /* regs: ONE register file */
+    const fheram_selector* const* reg_sels;    /*       [n_regs] */
+    int n_regs;
+} fheram_mix_reads;
+int fheram_bank_read_mix(fheram_bank* bank, const fheram_mix_reads* reads, int64_t* list_out, int64_t* table_out, int64_t* regs_out);
+
 /* ---- Setup side of a bank: what "Setup side on the device" above is to a context, for a bank — so that a bank needs no
  * twin context and no host encryption — and the decryption of what a bank leaves on the device.  SAMPLING STAYS ON THE HOST, exactly as
  * there: the caller hands over mask limbs and noise polynomials, the same draws give the same ciphertexts.  Every call waits for the
