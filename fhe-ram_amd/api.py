@@ -85,6 +85,12 @@ class _CMixReads(C.Structure):
                 ("regs", C.c_void_p), ("reg_sels", C.POINTER(C.c_void_p)), ("n_regs", C.c_int)]
 
 
+class _CMixPrepares(C.Structure):
+    """fheram_mix_prepares (include/fheram.h): the prepare list and the register file of a fheram_bank_read_prepare_write_mix"""
+    _fields_ = [("members", C.POINTER(C.c_int)), ("addrs", C.POINTER(C.c_void_p)), ("n_list", C.c_int),
+                ("regs", C.c_void_p), ("reg_sel", C.c_void_p)]
+
+
 class _CConfig(C.Structure):
     """fheram_config (include/fheram.h): the execution switches of a context"""
     _fields_ = [(f, C.c_int32) for f in _CONFIG_FIELDS]
@@ -203,6 +209,7 @@ _SYMBOLS = [
     ("fheram_bank_table_selector_create", C.c_int, [C.c_void_p, C.POINTER(I64P), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     ("fheram_bank_table_selector_alloc_fields", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
     ("fheram_bank_read_mix", C.c_int, [C.c_void_p, C.POINTER(_CMixReads), I64P, I64P, I64P]),
+    ("fheram_bank_read_prepare_write_mix", C.c_int, [C.c_void_p, C.POINTER(_CMixReads), C.POINTER(_CMixPrepares), I64P, I64P, I64P, I64P, I64P]),
     ("fheram_bank_secret_create", C.c_int, [C.c_void_p, I64P, C.POINTER(C.c_void_p)]),
     ("fheram_bank_keys_encrypt_sk", C.c_int, [C.c_void_p, C.c_void_p, I64P, I64P, I64P]),
     ("fheram_bank_address_encrypt_sk", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, I64P, I64P, C.POINTER(C.c_void_p)]),
@@ -2171,27 +2178,36 @@ class RamBank:
         read_list / table_read / RegFile.read, and the bank is left where that sequence leaves it (list_result, table_result and
         RegFile.result read the groups' outputs; a group left out keeps its kind's last outputs).  Returns (list, table, regs): int64
         [n][word_size][GLWE] per group, None for a group left out; download=False: no host wait, (None, None, None)."""
+        cm, keep, counts = RamBank._mix_reads(self, "read_mix", list, tables, regs, 0)
+        if sum(counts) < 1:
+            raise FheRamError(1, "read_mix takes at least one read: all three groups are empty")
+        if keys is not None:
+            self._use_keys(keys)
+        p = self.params
+        outs = [np.zeros((n, p.word_size(), p.glwe_len()), dtype=np.int64) if (download and n) else None for n in counts]
+        self._chk(library().fheram_bank_read_mix(self._h, C.byref(cm), *[_p(o) if o is not None else None for o in outs]))
+        return tuple(outs)
+
+    def _mix_reads(self, who, list, tables, regs, n_more):
+        """the three read groups of read_mix / read_prepare_write_mix as the C struct, refused here as the library would refuse them;
+        n_more: the entries the call has besides.  Returns (struct, the arrays it points to, (n_list, n_table, n_regs))."""
         members, addresses = (builtins_list(list[0]), builtins_list(list[1])) if list is not None else ([], [])
         tabs, tsels = (builtins_list(tables[0]), builtins_list(tables[1])) if tables is not None else ([], [])
         regfile, rsels = (regs[0], builtins_list(regs[1])) if regs is not None else (None, [])
         if len(addresses) != len(members) or len(tsels) != len(tabs):
-            raise FheRamError(1, f"read_mix takes as many addresses as members and as many selectors as tables, got {len(members)} / {len(addresses)} and {len(tabs)} / {len(tsels)}")
+            raise FheRamError(1, f"{who} takes as many addresses as members and as many selectors as tables, got {len(members)} / {len(addresses)} and {len(tabs)} / {len(tsels)}")
         nl, nt, nr = len(members), len(tabs), len(rsels)
-        if nl + nt + nr < 1:
-            raise FheRamError(1, "read_mix takes at least one read: all three groups are empty")
-        if nl + nt + nr > MIX_MAX:
-            raise FheRamError(1, f"read_mix takes at most MIX_MAX = {MIX_MAX} entries in all, got {nl + nt + nr}")
+        if nl + nt + nr + n_more > MIX_MAX:
+            raise FheRamError(1, f"{who} takes at most MIX_MAX = {MIX_MAX} entries in all, got {nl + nt + nr + n_more}")
         if not all(isinstance(a, Address) for a in addresses):
             raise FheRamError(1, "every list entry must be an Address (a null address is refused)")
         if not all(isinstance(t, Table) for t in tabs) or not all(isinstance(s, Selector) for s in tsels + rsels):
-            raise FheRamError(1, "read_mix takes Tables and Selectors")
+            raise FheRamError(1, f"{who} takes Tables and Selectors")
         if nr and not isinstance(regfile, RegFile):
-            raise FheRamError(1, "the regs group of read_mix takes a RegFile")
+            raise FheRamError(1, f"the regs group of {who} takes a RegFile")
         members = [int(m) for m in members]
         for m in members:
             self._member(m)
-        if keys is not None:
-            self._use_keys(keys)
         cm = _CMixReads()
         keep = []   # the arrays the struct points to
 
@@ -2206,9 +2222,49 @@ class RamBank:
             cm.tables, cm.table_sels, cm.n_table = arr(C.c_void_p, [t._h for t in tabs]), arr(C.c_void_p, [s._h for s in tsels]), nt
         if nr:
             cm.regs, cm.reg_sels, cm.n_regs = regfile._h, arr(C.c_void_p, [s._h for s in rsels]), nr
+        return cm, keep, (nl, nt, nr)
+
+    def read_prepare_write_mix(self, list=None, tables=None, regs=None, prepare_list=None, prepare_regs=None, download: bool = True,
+                               keys: Optional[EvaluationKeysPrepared] = None):
+        """the reads of a step and the first halves of its writes under ONE top (fheram_bank_read_prepare_write_mix).
+        list / tables / regs: the read groups of read_mix, all of which may be left out; prepare_list = (members, addresses): distinct
+        members, as read_prepare_write_list; prepare_regs = (regfile, selector): as RegFile.read_prepare_write.  At least one of the two,
+        and at most MIX_MAX entries in all (the register file counts 1).  Equals read_mix, read_prepare_write_list,
+        RegFile.read_prepare_write in that order, in every output and in what is left on the bank; a member may be read and prepared in
+        one call (the read sees the rows before the preparation), and so may the register file.  Returns (list, table, regs, prepared
+        list, prepared regs): int64 [n][word_size][GLWE] per read group, the OLD words [n][word_size][GLWE] of the prepare list and the
+        OLD register word [word_size][GLWE]; None for what is left out; download=False: no host wait, five times None."""
+        pmembers, paddresses = (builtins_list(prepare_list[0]), builtins_list(prepare_list[1])) if prepare_list is not None else ([], [])
+        pregfile, psel = prepare_regs if prepare_regs is not None else (None, None)
+        npl, npr = len(pmembers), 1 if prepare_regs is not None else 0
+        if len(paddresses) != npl:
+            raise FheRamError(1, f"read_prepare_write_mix takes as many addresses as prepared members, got {npl} / {len(paddresses)}")
+        if npl + npr < 1:
+            raise FheRamError(1, "read_prepare_write_mix takes at least one preparation: no prepare list and no register file (that is read_mix)")
+        cm, keep, counts = RamBank._mix_reads(self, "read_prepare_write_mix", list, tables, regs, npl + npr)
+        if not all(isinstance(a, Address) for a in paddresses):
+            raise FheRamError(1, "every prepare list entry must be an Address (a null address is refused)")
+        if npr and not (isinstance(pregfile, RegFile) and isinstance(psel, Selector)):
+            raise FheRamError(1, "prepare_regs of read_prepare_write_mix takes a RegFile and a Selector")
+        pmembers = [int(m) for m in pmembers]
+        for m in pmembers:
+            self._member(m)
+        if len(set(pmembers)) != npl:
+            raise FheRamError(1, "the members of a prepare list are distinct: a RAM has one pending write")
+        if keys is not None:
+            self._use_keys(keys)
+        cp = _CMixPrepares()
+        if npl:
+            am, aa = (C.c_int * npl)(*pmembers), (C.c_void_p * npl)(*[a._bank(self) for a in paddresses])
+            keep += [am, aa]
+            cp.members, cp.addrs, cp.n_list = am, aa, npl
+        if npr:
+            cp.regs, cp.reg_sel = pregfile._h, psel._h
         p = self.params
-        outs = [np.zeros((n, p.word_size(), p.glwe_len()), dtype=np.int64) if (download and n) else None for n in (nl, nt, nr)]
-        self._chk(library().fheram_bank_read_mix(self._h, C.byref(cm), *[_p(o) if o is not None else None for o in outs]))
+        shape = (p.word_size(), p.glwe_len())
+        outs = [np.zeros((n,) + shape, dtype=np.int64) if (download and n) else None for n in counts + (npl,)]
+        outs.append(np.zeros(shape, dtype=np.int64) if (download and npr) else None)
+        self._chk(library().fheram_bank_read_prepare_write_mix(self._h, C.byref(cm), C.byref(cp), *[_p(o) if o is not None else None for o in outs]))
         return tuple(outs)
 
     def _host_words(self, host_words, slots):

@@ -151,12 +151,10 @@ int read_list_check(fheram_bank* b, const int* members, const fheram_addr* const
     *s = MemberSet::list(members, n);
     return members_ready(b, *s, addrs, 0);
 }
-// a read_prepare_write (want_state 0) or write (1, which also has words) list: distinct members, in any order
-int write_list_check(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n, bool null_words, int want_state, MemberSet* s) {
-    if (!b) return FHERAM_ERR_INVALID_ARG;
+// the members of a read_prepare_write / write list, behind the null arguments: n, each in range and named once, then what every set ends in
+// (fheram_bank_read_prepare_write_mix checks its prepare list with this)
+int write_list_members(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n, int want_state, MemberSet* s) {
     fheram_ctx* c = b->c;
-    mid_rearm(c);
-    if (!members || !addrs || null_words) return fail(c, FHERAM_ERR_INVALID_ARG, want_state ? "null member list, null address list or null words" : "null member list or null address list");
     if (n < 1 || n > b->M)
         return fail(c, FHERAM_ERR_INVALID_ARG, "n = " + std::to_string(n) + " is outside [1, the bank's " + std::to_string(b->M) + " members]");
     unsigned seen = 0;
@@ -169,6 +167,14 @@ int write_list_check(fheram_bank* b, const int* members, const fheram_addr* cons
     }
     *s = MemberSet::list(members, n);
     return members_ready(b, *s, addrs, want_state);
+}
+// a read_prepare_write (want_state 0) or write (1, which also has words) list: distinct members, in any order
+int write_list_check(fheram_bank* b, const int* members, const fheram_addr* const* addrs, int n, bool null_words, int want_state, MemberSet* s) {
+    if (!b) return FHERAM_ERR_INVALID_ARG;
+    fheram_ctx* c = b->c;
+    mid_rearm(c);
+    if (!members || !addrs || null_words) return fail(c, FHERAM_ERR_INVALID_ARG, want_state ? "null member list, null address list or null words" : "null member list or null address list");
+    return write_list_members(b, members, addrs, n, want_state, s);
 }
 
 // ---- the plan of a read_prepare_write / write on a member set (header comment) ----------------------------------------------------------

@@ -404,13 +404,19 @@ void table_bufs_free(TableBufs& B) {
 // buffers — a mix writes the one that holds no empty group's last outputs — and the pinned result buffer.  The digits of its one-row
 // groups are prepared into the tables' and the register files' own (TableBufs::prep, RegsBufs::prep: a group that is not empty has its
 // object, so they exist).  Allocated whole by the bank's first fheram_bank_read_mix, freed with the bank.
+// fheram_bank_read_prepare_write_mix adds three, allocated whole by the bank's first such call: a fourth result buffer for a call without
+// reads (all three others may hold an empty kind's last outputs then), the digits of a prepare list of ONE member (the context's own
+// slots may hold those of a read list of one entry until the top has run) and the packed row of such a read list where the prepare
+// list works on the same member's arenas.
 struct MixBufs {
     int cap = 0;                                                                  // ciphertexts: min(FHERAM_MIX_MAX * word_size, 64); 0: not allocated
     int32_t *ep = nullptr, *tmp = nullptr, *res[3] = {nullptr, nullptr, nullptr}; // [cap] GLWE
     int64_t *h_res = nullptr, *d_h_res = nullptr;                                 // pinned, device-visible: the results as int64 (+ the monitor's maximum)
+    int32_t *own = nullptr, *keep = nullptr;                                      // [cap] / [word_size] GLWE (read_prepare_write_mix; nullptr: not allocated)
+    double* prep = nullptr;                                                       // [n_digits] prepared GGSW (read_prepare_write_mix)
 };
 void mix_bufs_free(MixBufs& M) {
-    void* bufs[] = {M.ep, M.tmp, M.res[0], M.res[1], M.res[2]};
+    void* bufs[] = {M.ep, M.tmp, M.res[0], M.res[1], M.res[2], M.own, M.keep, M.prep};
     for (void* p : bufs) if (p) hipFree(p);
     if (M.h_res) hipHostFree(M.h_res);
     M = MixBufs{};

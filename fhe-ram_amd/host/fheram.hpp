@@ -883,6 +883,45 @@ public:
         }
         return res;
     }
+    // ---- the reads of a step and the first halves of its writes under ONE top (include/fheram.h).  The read groups are
+    // read_mix's and may all be empty; prep_members / prep_addresses: distinct members, as read_prepare_write_list; prep_regs / prep_sel: as
+    // RegFile::read_prepare_write (nullptr, nullptr: none).  At least one preparation, at most FHERAM_MIX_MAX entries in all (the register
+    // file counts 1).  Equals read_mix, read_prepare_write_list, RegFile::read_prepare_write in that order.
+    struct PrepareMixResult { MixResult reads; std::vector<std::vector<Glwe>> prep_list; std::vector<Glwe> prep_regs; };   // the OLD words
+    PrepareMixResult read_prepare_write_mix(const std::vector<int>& members, std::vector<Address*>& addresses, const std::vector<const Table*>& tables,
+                                            const std::vector<const Selector*>& table_sels, const RegFile* regs, const std::vector<const Selector*>& reg_sels,
+                                            const std::vector<int>& prep_members, std::vector<Address*>& prep_addresses, RegFile* prep_regs,
+                                            const Selector* prep_sel, const EvaluationKeysPrepared& keys, bool download = true) {
+        if (addresses.size() != members.size() || table_sels.size() != tables.size() || prep_addresses.size() != prep_members.size())
+            throw Error(FHERAM_ERR_INVALID_ARG, "read_prepare_write_mix takes as many addresses as members and as many selectors as tables");
+        const size_t nl = members.size(), nt = tables.size(), nr = reg_sels.size(), np = prep_members.size(), npr = prep_regs ? 1 : 0;
+        if (np + npr < 1) throw Error(FHERAM_ERR_INVALID_ARG, "read_prepare_write_mix takes at least one preparation (without one it is read_mix)");
+        if (nl + nt + nr + np + npr > FHERAM_MIX_MAX) throw Error(FHERAM_ERR_INVALID_ARG, "read_prepare_write_mix takes at most FHERAM_MIX_MAX entries in all");
+        if (nr && !regs) throw Error(FHERAM_ERR_INVALID_ARG, "the regs group of read_prepare_write_mix takes a register file");
+        if ((prep_regs != nullptr) != (prep_sel != nullptr)) throw Error(FHERAM_ERR_INVALID_ARG, "a prepared register file takes one selector");
+        use(keys);
+        std::vector<const fheram_addr*> ah = handles(addresses), pah = handles(prep_addresses);
+        std::vector<const fheram_table*> th;
+        std::vector<const fheram_selector*> tsh, rsh;
+        for (const Table* t : tables) { if (!t) throw Error(FHERAM_ERR_INVALID_ARG, "null table"); th.push_back(t->h_); }
+        for (const Selector* x : table_sels) { if (!x) throw Error(FHERAM_ERR_INVALID_ARG, "null selector"); tsh.push_back(x->h_); }
+        for (const Selector* x : reg_sels) { if (!x) throw Error(FHERAM_ERR_INVALID_ARG, "null selector"); rsh.push_back(x->h_); }
+        const fheram_mix_reads reads{members.data(), ah.data(), (int)nl, th.data(), tsh.data(), (int)nt, nr ? regs->h_ : nullptr, rsh.data(), (int)nr};
+        const fheram_mix_prepares prepares{prep_members.data(), pah.data(), (int)np, npr ? prep_regs->h_ : nullptr, npr ? prep_sel->h_ : nullptr};
+        const size_t one = params.word_size() * glwe_len();
+        std::vector<int64_t> lo(download ? nl * one : 0), to(download ? nt * one : 0), ro(download ? nr * one : 0), po(download ? np * one : 0), pr(download ? npr * one : 0);
+        auto ptr = [](std::vector<int64_t>& v) { return v.empty() ? nullptr : v.data(); };
+        chk(fheram_bank_read_prepare_write_mix(bank_, &reads, &prepares, ptr(lo), ptr(to), ptr(ro), ptr(po), ptr(pr)));
+        PrepareMixResult res;
+        if (download) {
+            if (nl) res.reads.list = split(lo, nl);
+            if (nt) res.reads.table = split(to, nt);
+            if (nr) res.reads.regs = split(ro, nr);
+            if (np) res.prep_list = split(po, np);
+            if (npr) res.prep_regs = split(pr, 1)[0];
+        }
+        return res;
+    }
     // ---- the setup side, continued: keys, members, addresses, words; decryption of what the bank leaves on the device
     // EvaluationKeys::encrypt_sk + prepare on the bank (fheram_bank_keys_encrypt_sk); `keys` is marked as the set in use (its std forms stay empty)
     void encrypt_keys(EvaluationKeysPrepared& keys, const Secret& sk, Source& source_xa, Source& source_xe) {

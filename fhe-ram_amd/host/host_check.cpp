@@ -270,6 +270,31 @@ int main() {
                     catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_STATE) return 21; }
                     std::printf("bank register file: read, read_prepare_write, write, pack: ok\n");
                 }
+                {   // Bank::read_prepare_write_mix: a read of member 1 and of the register file, the preparation of member 0 and of that
+                    // register file under ONE top, against the twin's three calls; then both halves' writes
+                    B::RegFile lr(lists, 1), tr(twin, 1);
+                    const auto row = synth(4 * lists.glwe_len());
+                    lr.load(row);
+                    tr.load(row);
+                    std::vector<fheram::Address*> ra = {&a1}, pa = {&a0};
+                    const auto mixed = lists.read_prepare_write_mix({1}, ra, {}, {}, &lr, {&ls1}, {0}, pa, &lr, &ls0, bk);
+                    const auto t_reads = twin.read_mix({1}, ra, {}, {}, &tr, {&ts1}, bk);
+                    const auto t_list = twin.read_prepare_write_list({0}, pa, bk);
+                    const auto t_old = tr.read_prepare_write(ts0);
+                    if (mixed.reads.list != t_reads.list || mixed.reads.regs != t_reads.regs) { std::printf("read_prepare_write_mix: the reads differ\n"); return 25; }
+                    if (mixed.prep_list != t_list || mixed.prep_regs != t_old) { std::printf("read_prepare_write_mix: the old words differ\n"); return 25; }
+                    if (!lists.state(0) || lists.state(1) || !lr.state() || lr.old_result() != t_old) return 25;
+                    lists.write_list({0}, {words[0]}, pa, bk);
+                    twin.write_list({0}, {words[0]}, pa, bk);
+                    lr.write(ls0, B::src_regs_old());
+                    tr.write(ts0, B::src_regs_old());
+                    for (int m = 0; m < 3; m++)
+                        if (lists.state(m) || lists.store_encrypted(m) != twin.store_encrypted(m)) { std::printf("read_prepare_write_mix + write_list: member %d differs\n", m); return 25; }
+                    if (lr.state() || lr.store() != tr.store()) { std::printf("read_prepare_write_mix + RegFile::write: the two banks differ\n"); return 25; }
+                    try { std::vector<fheram::Address*> none; lists.read_prepare_write_mix({1}, ra, {}, {}, nullptr, {}, {}, none, nullptr, nullptr, bk); return 26; }   // no preparation: that is read_mix
+                    catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 26; }
+                    std::printf("bank read_prepare_write_mix == read_mix, read_prepare_write_list, RegFile::read_prepare_write: ok\n");
+                }
                 {   // Bank::Table: a table of 2 words reads as a register file holding the same row does; a ROM of 4096 public words at a wide selector
                     B::Table lt(lists, 1), rom(lists, 12);
                     B::RegFile lr(lists, 1);

@@ -790,6 +790,35 @@ typedef struct fheram_mix_reads {
     int n_regs;
 } fheram_mix_reads;
 int fheram_bank_read_mix(fheram_bank* bank, const fheram_mix_reads* reads, int64_t* list_out, int64_t* table_out, int64_t* regs_out);
+/* The reads of a step AND the first halves of its writes under ONE top.  *** CONTRACT-COMPATIBLE ONLY ***, as its parts
+ * are.  A step's writes — the data memory's read_prepare_write, the register file's (rd) — take their address and selector from the same
+ * derive list launch as its reads and end in a top of their own each; here the prepared ciphertexts join the reads' in one top, laid out
+ * [list | table | regs | prepared list | prepared register file], and ONE launch behind it hands over what a read_prepare_write keeps.
+ * The call is int64-identical to the sequence
+ *   fheram_bank_read_mix(reads)                                    if reads names a read
+ *   fheram_bank_read_prepare_write_list(members, addrs, n_list)    if n_list > 0
+ *   fheram_bank_regs_read_prepare_write(regs, reg_sel)             if regs is not NULL
+ * in every output and in everything that sequence leaves on the bank: rows, tree level 0, state flags and result slots of the members,
+ * the register file's rotated row, state and kept trace (FHERAM_SRC_REGS_OLD), the read groups' last outputs (empty kinds keep theirs).
+ * A member may be read and prepared in one call: its read sees the rows before the preparation; reads->regs may be prepares->regs: its
+ * reads see the row before rd's products land in it.  Every later operation behaves as after the sequence, except that a prepare list of
+ * ONE member starts no early inverse digits (a lone read_prepare_write does, on a bank of one member): its write computes them, as the
+ * write after a list of several does.
+ * All entries together — the reads, n_list and 1 for the register file — number at most FHERAM_MIX_MAX, and that total times word_size
+ * at most 64.  Every check runs before anything is enqueued and a refused call changes nothing; each group is refused with the codes of
+ * its single call, the totals, a null `prepares`, a negative count and a `prepares` that names nothing (that is fheram_bank_read_mix)
+ * with FHERAM_ERR_INVALID_ARG.  reads == NULL: no reads.  list_out / table_out / regs_out: as fheram_bank_read_mix; prep_list_out:
+ * [n_list][word_size][GLWE], the OLD words; prep_regs_out: [word_size][GLWE], the OLD register word; each may be NULL, with all five NULL
+ * the call waits for nothing.  What the operation adds to the mix's buffers is allocated whole by the bank's first such call. */
+typedef struct fheram_mix_prepares {
+    const int* members;                 /* list: [n_list], the rules of fheram_bank_read_prepare_write_list (distinct members) */
+    const fheram_addr* const* addrs;    /*       [n_list] */
+    int n_list;
+    fheram_regs* regs;                  /* regs: ONE register file and ONE selector (a register file has one pending write); NULL: none */
+    const fheram_selector* reg_sel;
+} fheram_mix_prepares;
+int fheram_bank_read_prepare_write_mix(fheram_bank* bank, const fheram_mix_reads* reads, const fheram_mix_prepares* prepares,
+                                       int64_t* list_out, int64_t* table_out, int64_t* regs_out, int64_t* prep_list_out, int64_t* prep_regs_out);
 
 /* ---- Setup side of a bank: what "Setup side on the device" above is to a context, for a bank — so that a bank needs no
  * twin context and no host encryption — and the decryption of what a bank leaves on the device.  SAMPLING STAYS ON THE HOST, exactly as
