@@ -35,6 +35,8 @@ SELECT_MAX = 8       # FHERAM_SELECT_MAX
 SRC_ZERO, SRC_HOST, SRC_MEMBER_RESULT, SRC_LIST_RESULT, SRC_SELECT_RESULT = 0, 1, 2, 3, 4   # FHERAM_SRC_*
 SRC_REGS_RESULT, SRC_REGS_OLD = 5, 6   # FHERAM_SRC_REGS_RESULT / _REGS_OLD: a bank's register files
 SRC_TABLE_RESULT = 8   # FHERAM_SRC_TABLE_RESULT: a bank's tables (kind 7 is unknown)
+SRC_PEEK_RESULT = 10   # FHERAM_SRC_PEEK_RESULT: a bank's last peek or poke at public addresses (kinds 7 and 9 are unknown)
+PEEK_MAX = 16          # FHERAM_PEEK_MAX
 TABLE_BITS_MAX = 12             # FHERAM_TABLE_BITS_MAX
 SELECTOR_WIDE_DIGITS_MAX = 5    # FHERAM_SELECTOR_WIDE_DIGITS_MAX
 SELECT_FIELDS_MAX = 5   # FHERAM_SELECT_FIELDS_MAX
@@ -208,6 +210,12 @@ _SYMBOLS = [
     ("fheram_bank_table_selector_alloc", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     ("fheram_bank_table_selector_create", C.c_int, [C.c_void_p, C.POINTER(I64P), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     ("fheram_bank_table_selector_alloc_fields", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_ram_load_plain", C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t]),
+    ("fheram_bank_regs_load_plain", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t]),
+    ("fheram_bank_peek", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.c_int, I64P]),
+    ("fheram_bank_peek_result", C.c_int, [C.c_void_p, C.c_int, C.c_int, I64P]),
+    ("fheram_bank_poke", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.c_int, C.POINTER(_CSelectSrc), I64P]),
+    ("fheram_bank_selftest_fail_public_alloc", C.c_int, [C.c_void_p, C.c_int]),
     ("fheram_bank_read_mix", C.c_int, [C.c_void_p, C.POINTER(_CMixReads), I64P, I64P, I64P]),
     ("fheram_bank_read_prepare_write_mix", C.c_int, [C.c_void_p, C.POINTER(_CMixReads), C.POINTER(_CMixPrepares), I64P, I64P, I64P, I64P, I64P]),
     ("fheram_bank_secret_create", C.c_int, [C.c_void_p, I64P, C.POINTER(C.c_void_p)]),
@@ -747,6 +755,11 @@ class Src:
         """output k of the bank's last RamBank.table_read"""
         return cls(SRC_TABLE_RESULT, k)
 
+    @classmethod
+    def peek(cls, k: int):
+        """output k of the bank's last RamBank.peek (or the old word k of its last RamBank.poke)"""
+        return cls(SRC_PEEK_RESULT, k)
+
 
 class Lane:
     """One byte ciphertext of a lane-mapped candidate of RamBank.select_lanes (fheram_select_lane): GLWE `lane` of the word a Src would
@@ -803,6 +816,11 @@ class Lane:
     def table(cls, k: int, lane: int):
         """GLWE `lane` of output k of the bank's last RamBank.table_read"""
         return cls(SRC_TABLE_RESULT, k, lane)
+
+    @classmethod
+    def peek(cls, k: int, lane: int):
+        """GLWE `lane` of output k of the bank's last RamBank.peek / poke"""
+        return cls(SRC_PEEK_RESULT, k, lane)
 
     @classmethod
     def of(cls, src: Src, lane: int):
@@ -964,6 +982,15 @@ class RegFile:
     def decrypt(self, sk: "GLWESecret"):
         """every word, decrypted and decoded on the device (fheram_bank_regs_decrypt): (values int32 [2^bits][word_size], worst log2 noise)"""
         return self.bank._one_row_decrypt(library().fheram_bank_regs_decrypt, self, self.bits, sk)
+
+    def load_plain(self, data):
+        """public contents, 2^bits * word_size bytes in Ram::encrypt_sk's layout (byte w of word j at data[j * word_size + w]), as the
+        trivial ciphertext: no host encryption, no keys, no secret (fheram_bank_regs_load_plain)"""
+        data = np.ascontiguousarray(np.asarray(data, dtype=np.uint8).ravel())
+        want = (1 << self.bits) * self.bank.params.word_size()
+        if data.size != want:
+            raise FheRamError(1, f"invalid data: a register file of {self.bits} bits takes 2^bits * word_size = {want} bytes, got {data.size}")
+        self.bank._chk(library().fheram_bank_regs_load_plain(self.bank._h, self._h, data.ctypes.data_as(C.POINTER(C.c_uint8)), data.size))
 
     def store(self) -> np.ndarray:
         """the row, [word_size][GLWE] (fheram_bank_regs_download)"""
@@ -2170,6 +2197,93 @@ class RamBank:
         out = np.zeros((max(n, 1), p.word_size(), p.glwe_len()), dtype=np.int64)
         self._chk(library().fheram_bank_table_result(self._h, first, n, _p(out)))
         return out
+
+    # -- the public side (include/fheram.h): plain image loads, peek and poke at public addresses
+    def load_plain(self, member: int, data, first_row: int = 0):
+        """public bytes into the rows of one member from first_row on, as the trivial ciphertexts (fheram_bank_ram_load_plain): no host
+        encryption, no keys, no secret.  data: whole words in Ram::encrypt_sk's layout (byte w of word j at data[j * word_size + w]),
+        word 0 of data at address first_row * N; it covers whole rows, or ends where the member does.  first_row = 0 with
+        max_addr * word_size bytes loads the whole member, which becomes readable as after load_encrypted."""
+        p = self.params
+        member = self._member(member)
+        data = np.ascontiguousarray(np.asarray(data, dtype=np.uint8).ravel())
+        first_row, ws, n = int(first_row), p.word_size(), p.n()
+        if not 0 <= first_row < p.rows():
+            raise FheRamError(1, f"row {first_row} is outside the member's {p.rows()} rows")
+        if data.size == 0 or data.size % ws:
+            raise FheRamError(1, f"invalid data: {data.size} bytes are not a positive number of words of word_size = {ws} bytes")
+        words = data.size // ws
+        last = first_row * n + words
+        if last > p.max_addr() or (last % n and last != p.max_addr()):
+            raise FheRamError(1, f"invalid data: {words} words from row {first_row} on neither fill whole rows nor end at max_addr = {p.max_addr()}")
+        n_rows = -(-words // n)
+        self._chk(library().fheram_bank_ram_load_plain(self._h, member, first_row, n_rows, data.ctypes.data_as(C.POINTER(C.c_uint8)), data.size))
+
+    def _public_entries(self, what, members, addresses):
+        members, addresses = [int(m) for m in members], [int(a) for a in addresses]
+        n = len(members)
+        if not 1 <= n <= PEEK_MAX or len(addresses) != n:
+            raise FheRamError(1, f"{what} takes 1 to PEEK_MAX = {PEEK_MAX} members and as many addresses, got {len(members)} and {len(addresses)}")
+        if n * self.params.word_size() > 64:
+            raise FheRamError(1, f"{what}: n * word_size = {n * self.params.word_size()} exceeds 64")
+        for m in members:
+            self._member(m)
+        for a in addresses:
+            if not 0 <= a < self.params.max_addr():
+                raise FheRamError(1, f"{what}: address {a} is outside max_addr = {self.params.max_addr()}")
+        return n, (C.c_int * n)(*members), (C.c_uint64 * n)(*addresses)
+
+    def peek(self, members, addresses, download: bool = True, keys: Optional[EvaluationKeysPrepared] = None):
+        """len(members) reads at PUBLIC word addresses as ONE operation (fheram_bank_peek): entry k reads member members[k] at
+        addresses[k]; members and addresses may repeat.  int64 [n][word_size][GLWE], each an encryption of [v, 0, .., 0]; download=False:
+        no host wait (peek_result later).  Nothing of the bank changes but the last peek (Src.peek(k))."""
+        n, mem, adr = self._public_entries("peek", members, addresses)
+        if keys is not None:
+            self._use_keys(keys)
+        p = self.params
+        out = np.zeros((n, p.word_size(), p.glwe_len()), dtype=np.int64) if download else None
+        self._chk(library().fheram_bank_peek(self._h, mem, adr, n, _p(out) if download else None))
+        return out
+
+    def peek_result(self, first: int = 0, n: int = 1) -> np.ndarray:
+        """outputs [first, first + n) of the bank's last peek, or the old words of its last poke (fheram_bank_peek_result)"""
+        first, n = int(first), int(n)
+        p = self.params
+        out = np.zeros((max(n, 1), p.word_size(), p.glwe_len()), dtype=np.int64)
+        self._chk(library().fheram_bank_peek_result(self._h, first, n, _p(out)))
+        return out
+
+    def poke(self, members, addresses, words=None, srcs=None, keys: Optional[EvaluationKeysPrepared] = None):
+        """len(members) writes at PUBLIC word addresses as ONE operation (fheram_bank_poke): entry k writes at addresses[k] of member
+        members[k]; the (member, address) pairs are distinct.  Either words: int64 [n][word_size][GLWE] host ciphertexts, entry k's at
+        k — or srcs: one Src per entry, with words the host_words its Src.host(i) name.  Every entry sees the rows as they were
+        before the call; the OLD words are the last peek afterwards (peek_result, Src.peek(k)).  Never waits for the device."""
+        n, mem, adr = self._public_entries("poke", members, addresses)
+        if len(set(zip(mem, adr))) != n:
+            raise FheRamError(1, "the targets of a poke are distinct (member, address) pairs")
+        if srcs is None:
+            if words is None:
+                raise FheRamError(1, "poke takes words, or srcs")
+            srcs = [Src.host(k) for k in range(n)]
+            if _i64(words).size != n * self.params.word_size() * self.params.glwe_len():
+                raise FheRamError(1, f"poke: expected {n} x {self.params.word_size()} GLWEs of words")
+        srcs = list(srcs)
+        if len(srcs) != n or not all(isinstance(s, Src) for s in srcs):
+            raise FheRamError(1, f"poke takes one Src per entry, got {len(srcs)} for {n} entries")
+        slots = [s.index for s in srcs if s.kind == SRC_HOST]
+        if slots and words is None:
+            raise FheRamError(1, "a host source needs words")
+        if slots and max(slots) >= PEEK_MAX:
+            raise FheRamError(1, f"a poke takes host slots [0, PEEK_MAX = {PEEK_MAX})")
+        hw = self._host_words(words, slots)
+        if keys is not None:
+            self._use_keys(keys)
+        arr = (_CSelectSrc * n)(*[_CSelectSrc(s.kind, s.index) for s in srcs])
+        self._chk(library().fheram_bank_poke(self._h, mem, adr, n, arr, _p(hw) if hw is not None else None))
+
+    def selftest_fail_public_alloc(self, nth: int):
+        """self-test: the nth device allocation the public side's buffers ask for from now on fails once (0: none)"""
+        self._chk(library().fheram_bank_selftest_fail_public_alloc(self._h, int(nth)))
 
     def read_mix(self, list=None, tables=None, regs=None, download: bool = True, keys: Optional[EvaluationKeysPrepared] = None):
         """a read list, a table read and a register read as ONE operation with one top (fheram_bank_read_mix).

@@ -67,6 +67,10 @@ struct fheram_bank {
     // fheram_bank_read_mix (mix.hpp): its buffers, and where the last operation of each kind left its outputs (its own set, or the mix's)
     MixBufs mix;
     ResHome list_home, table_home, regs_home;
+    // the public side (public_io.hpp): its buffers, and the outputs of the last fheram_bank_peek / _poke (in pub.res[pub.cur]; 0: none has run)
+    PublicBufs pub;
+    int peek_n = 0;
+    int pub_fail_alloc = 0;       // fheram_bank_selftest_fail_public_alloc: the pub_fail_alloc-th next device allocation of pub fails (0: none)
 };
 
 namespace {
@@ -338,6 +342,7 @@ void fheram_bank_destroy(fheram_bank* b) {
     regs_bank_release(b);
     table_bank_release(b);
     mix_bufs_free(b->mix);
+    public_bufs_free(b->pub);
     fheram_ctx_destroy(b->c);
     delete b;
 }

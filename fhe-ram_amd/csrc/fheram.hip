@@ -856,6 +856,7 @@ int fheram_device_info(const fheram_ctx* c, char* name, size_t name_len, int* cu
 #include "select.hpp"
 #include "regs.hpp"
 #include "table.hpp"
+#include "public_io.hpp"
 #include "bank_setup.hpp"
 #include "derive_list.hpp"
 #include "mix.hpp"

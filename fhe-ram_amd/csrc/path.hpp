@@ -400,6 +400,31 @@ void table_bufs_free(TableBufs& B) {
     B = TableBufs{};
 }
 
+// A bank's public side (public_io.hpp): the buffers of fheram_bank_peek / _poke — per ciphertext the gathered, rotated row, a temporary
+// and TWO result buffers (an operation writes the one that does not hold the last outputs: res[cur] does) — the pinned result buffer, the
+// host words of a poke, and the staged bytes of a fheram_bank_ram_load_plain / _regs_load_plain.  Allocated whole by the bank's first
+// such call, freed with the bank.
+struct PublicBufs {
+    int cap = 0;                                                                  // ciphertexts of a call: min(FHERAM_PEEK_MAX * word_size, 64); 0: not allocated
+    int32_t *fan = nullptr, *tmp = nullptr, *res[2] = {nullptr, nullptr};         // [cap] GLWE
+    int cur = 0;
+    int64_t *h_res = nullptr, *d_h_res = nullptr;                                 // pinned, device-visible: the results as int64 (+ the monitor's maximum)
+    int32_t *d_host = nullptr, *h_host = nullptr;                                 // [FHERAM_PEEK_MAX * word_size] GLWE: host words, device / pinned
+    uint8_t *d_data = nullptr, *h_data = nullptr;                                 // [rows * N * word_size] bytes of a load_plain, device / pinned
+    hipEvent_t ev_host = nullptr, ev_data = nullptr;                              // the last copy out of h_host / h_data
+    bool host_busy = false, data_busy = false;
+};
+void public_bufs_free(PublicBufs& P) {
+    void* bufs[] = {P.fan, P.tmp, P.res[0], P.res[1], P.d_host, P.d_data};
+    for (void* p : bufs) if (p) hipFree(p);
+    if (P.h_res) hipHostFree(P.h_res);
+    if (P.h_host) hipHostFree(P.h_host);
+    if (P.h_data) hipHostFree(P.h_data);
+    if (P.ev_host) hipEventDestroy(P.ev_host);
+    if (P.ev_data) hipEventDestroy(P.ev_data);
+    P = PublicBufs{};
+}
+
 // fheram_bank_read_mix's own buffers (mix.hpp): per ciphertext of the shared top the products' output, a temporary and THREE result
 // buffers — a mix writes the one that holds no empty group's last outputs — and the pinned result buffer.  The digits of its one-row
 // groups are prepared into the tables' and the register files' own (TableBufs::prep, RegsBufs::prep: a group that is not empty has its

@@ -142,6 +142,7 @@ const int32_t* select_source(const fheram_bank* b, const fheram_select_src& s, c
     case FHERAM_SRC_REGS_RESULT: return b->regs_home.res + (size_t)s.index * per;
     case FHERAM_SRC_REGS_OLD: return b->regs_old;
     case FHERAM_SRC_TABLE_RESULT: return b->table_home.res + (size_t)s.index * per;
+    case FHERAM_SRC_PEEK_RESULT: return b->pub.res[b->pub.cur] + (size_t)s.index * per;
     default: return nullptr;
     }
 }
@@ -177,7 +178,7 @@ int select_check_sels(fheram_bank* b, const fheram_selector* const* sels, const 
     }
     return FHERAM_OK;
 }
-struct SelectNeeds { bool list = false, sel = false, regs = false, regs_old = false, table = false; };
+struct SelectNeeds { bool list = false, sel = false, regs = false, regs_old = false, table = false, peek = false; };
 // one (kind, index) of a source or a lane
 int select_check_source(fheram_bank* b, int kind, int index, const std::string& who, const int64_t* host_words, SelectNeeds& need) {
     fheram_ctx* c = b->c;
@@ -210,6 +211,10 @@ int select_check_source(fheram_bank* b, int kind, int index, const std::string& 
         if (index < 0 || (b->table_n && index >= b->table_n)) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names output " + std::to_string(index) + ", outside the last table read's " + std::to_string(b->table_n) + " outputs");
         need.table = true;
         break;
+    case FHERAM_SRC_PEEK_RESULT:
+        if (index < 0 || (b->peek_n && index >= b->peek_n)) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names output " + std::to_string(index) + ", outside the last peek's " + std::to_string(b->peek_n) + " outputs");
+        need.peek = true;
+        break;
     default: return fail(c, FHERAM_ERR_INVALID_ARG, who + " has the unknown kind " + std::to_string(kind));
     }
     return FHERAM_OK;
@@ -222,6 +227,7 @@ int select_check_state(fheram_bank* b, const SelectNeeds& need, bool keys = true
     if (need.regs && !b->regs_n) return fail(c, FHERAM_ERR_STATE, "a source names the last register read and no fheram_bank_regs_read has run on this bank");
     if (need.regs_old && !b->regs_old) return fail(c, FHERAM_ERR_STATE, "a source names the last register read_prepare_write and none has run on this bank (or its register file is gone)");
     if (need.table && !b->table_n) return fail(c, FHERAM_ERR_STATE, "a source names the last table read and no fheram_bank_table_read has run on this bank");
+    if (need.peek && !b->peek_n) return fail(c, FHERAM_ERR_STATE, "a source names the last peek and no fheram_bank_peek or fheram_bank_poke has run on this bank");
     return FHERAM_OK;
 }
 // n independent Ram::read of one-row RAMs as one operation, on the caller's buffers (S.packed holds the n * ws rows): the selectors' digits

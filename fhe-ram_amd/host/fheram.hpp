@@ -851,6 +851,38 @@ public:
         chk(fheram_bank_table_result(bank_, first, n, out.data()));
         return split(out, (size_t)n);
     }
+    // ---- the public side (include/fheram.h): plain image loads, peek and poke at PUBLIC word addresses
+    static fheram_select_src src_peek(int output) { return {FHERAM_SRC_PEEK_RESULT, output}; }   // output of the bank's last peek / old word of its last poke
+    // public bytes (whole words, Ram::encrypt_sk's layout) into the rows of one member from first_row on, as the trivial ciphertexts: no host
+    // encryption, no keys.  data covers whole rows, or ends where the member does; first_row = 0 with max_addr words loads the whole member.
+    void load_plain(int member, const std::vector<uint8_t>& data, size_t first_row = 0) {
+        const size_t ws = params.word_size(), n = params.n(), words = data.size() / ws;
+        if (data.empty() || data.size() % ws) throw Error(FHERAM_ERR_INVALID_ARG, "invalid data: not a positive number of words");
+        chk(fheram_bank_ram_load_plain(bank_, member, first_row, (words + n - 1) / n, data.data(), data.size()));
+    }
+    void load_plain(RegFile& regs, const std::vector<uint8_t>& data) { chk(fheram_bank_regs_load_plain(bank_, regs.h_, data.data(), data.size())); }
+    // members.size() reads at public addresses as ONE operation (fheram_bank_peek); download = false: no host wait, an empty result (peek_result later)
+    std::vector<std::vector<Glwe>> peek(const std::vector<int>& members, const std::vector<uint64_t>& addresses, bool download = true) {
+        if (members.empty() || addresses.size() != members.size()) throw Error(FHERAM_ERR_INVALID_ARG, "peek takes at least one member and one address per member");
+        std::vector<int64_t> out(download ? members.size() * params.word_size() * glwe_len() : 0);
+        chk(fheram_bank_peek(bank_, members.data(), addresses.data(), (int)members.size(), download ? out.data() : nullptr));
+        return download ? split(out, members.size()) : std::vector<std::vector<Glwe>>();
+    }
+    std::vector<std::vector<Glwe>> peek_result(int first, int n) {
+        if (n < 1) throw Error(FHERAM_ERR_INVALID_ARG, "empty slice of the last peek");
+        std::vector<int64_t> out((size_t)n * params.word_size() * glwe_len());
+        chk(fheram_bank_peek_result(bank_, first, n, out.data()));
+        return split(out, (size_t)n);
+    }
+    // members.size() writes at public addresses as ONE operation (fheram_bank_poke): entry k writes the word srcs[k] names (src_host(i): slot i
+    // of host_words); the old words are the last peek afterwards.  Never waits for the device.
+    void poke(const std::vector<int>& members, const std::vector<uint64_t>& addresses, const std::vector<fheram_select_src>& srcs,
+              const std::vector<std::vector<Glwe>>& host_words = {}) {
+        if (members.empty() || addresses.size() != members.size() || srcs.size() != members.size())
+            throw Error(FHERAM_ERR_INVALID_ARG, "poke takes at least one member, and one address and one source per member");
+        const std::vector<int64_t> flat = flat_words(srcs, host_words);
+        chk(fheram_bank_poke(bank_, members.data(), addresses.data(), (int)members.size(), srcs.data(), flat.empty() ? nullptr : flat.data()));
+    }
     // ---- mixed reads (include/fheram.h): a read list, a table read and a register read as ONE operation with one top.  A group
     // may be empty (regs: nullptr and no selectors) but not all three; at most FHERAM_MIX_MAX entries in all.  Entry k of a group equals
     // output k of read_list / table_read / RegFile::read, and list_result / table_result / RegFile::result read the groups' outputs afterwards.

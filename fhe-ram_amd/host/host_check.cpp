@@ -326,6 +326,29 @@ int main() {
                     catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 23; }
                     std::printf("bank table: load, load_plain, table_read, table_result, wide selectors: ok\n");
                 }
+                {   // the public side: a public image into member 1 of both banks, a peek, a poke of a host word and of the old word back
+                    std::vector<uint8_t> image(4096 * 4);
+                    for (size_t i = 0; i < image.size(); i++) image[i] = (uint8_t)(i * 29 + 5);
+                    lists.load_plain(1, image);
+                    twin.load_plain(1, image);
+                    const auto rows = lists.store_encrypted(1);
+                    for (size_t i = 0; i < n; i++) if (rows[n + i] != 0) { std::printf("load_plain: a mask limb is not zero\n"); return 27; }
+                    if (!lists.peek({1, 1}, {7, 4095}, false).empty()) return 27;
+                    if (lists.peek_result(0, 2) != twin.peek({1, 1}, {7, 4095})) { std::printf("peek: the two banks differ\n"); return 27; }
+                    if (lists.store_encrypted(1) != rows) { std::printf("peek changed the rows\n"); return 27; }
+                    lists.poke({1}, {7}, {B::src_host(1)}, words);
+                    twin.poke({1}, {7}, {B::src_host(1)}, words);
+                    if (lists.store_encrypted(1) != twin.store_encrypted(1) || lists.store_encrypted(1) == rows) { std::printf("poke: the two banks differ\n"); return 27; }
+                    lists.poke({1}, {7}, {B::src_peek(0)});   // the old word put back, on the device
+                    B::RegFile lr(lists, 1);
+                    lists.load_plain(lr, std::vector<uint8_t>(image.begin(), image.begin() + 8));
+                    if (lr.state() || lr.store().size() != 4 * lists.glwe_len()) return 27;
+                    try { lists.poke({1, 1}, {7, 7}, {B::src_zero(), B::src_zero()}); return 28; }   // one target twice
+                    catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 28; }
+                    try { lists.peek({1}, {4096}); return 28; }   // an address outside the member
+                    catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 28; }
+                    std::printf("bank public side: load_plain, peek, peek_result, poke: ok\n");
+                }
             }
         }
     } catch (const fheram::Error& e) {

@@ -758,6 +758,67 @@ int fheram_bank_table_selector_alloc(fheram_bank* bank, int bits, fheram_selecto
 int fheram_bank_table_selector_create(fheram_bank* bank, const int64_t* const* ggsw, int n_ggsw, int bits, fheram_selector** out);
 int fheram_bank_table_selector_alloc_fields(fheram_bank* bank, const int* widths, int n_fields, fheram_selector** out);
 
+/* ---- THE PUBLIC SIDE of a bank: plain image loads, and one word read (peek) or written (poke) at a PUBLIC address.
+ * *** CONTRACT-COMPATIBLE ONLY *** as the select, the register file and the tables are.  The server that hosts a bank has no secret
+ * key: it loads a public program or data image, places input buffers and fetches result buffers at addresses everybody knows.  With a
+ * public address a = r * N + q nothing is hidden, and the reference's operations collapse to row r: a read is "rotate row r by -q,
+ * trace" (ram.rs:451,457 without the products), a write is write_first_step's normalize(a - b + c) (ram.rs:574-576) on that one row.
+ * None of it pays the row chains over every row that an oblivious operation at a trivial GGSW address pays.
+ * Everything runs on the bank's main stream.  The public side's buffers — two result buffers of min(FHERAM_PEEK_MAX * word_size, 64)
+ * GLWEs (an operation writes the one that does not hold the last outputs), the gathered rows and a temporary of the same size, the
+ * pinned result buffer, FHERAM_PEEK_MAX host-word slots and the byte staging buffers of one member — are allocated whole by the
+ * first of these calls and freed with the bank (FHERAM_ERR_DEVICE if that fails; every other operation still works).  No later
+ * operation allocates.  Every check runs before anything is enqueued and a refused call changes nothing. */
+#define FHERAM_PEEK_MAX 16             /* entries of one peek or poke; n * word_size <= 64 as for the lists */
+/* one more source kind: output `index` of the bank's last fheram_bank_peek or fheram_bank_poke; valid wherever a fheram_select_src or a
+ * fheram_select_lane is taken (select, select_lanes, regs_pack, regs_write, poke, source_decrypt), FHERAM_ERR_STATE before any has run.
+ * (Kind 9 is unknown, as kind 7 is: callers rely on both being refused with FHERAM_ERR_INVALID_ARG.) */
+#define FHERAM_SRC_PEEK_RESULT 10
+/* PUBLIC bytes into rows [first_row, first_row + n_rows) of one member with no host encryption and no int64 image: the rows become
+ * the TRIVIAL ciphertexts Ram::encrypt_sk's encoding gives with an all-zero mask and zero noise (every mask limb 0, the body the
+ * plaintext limbs of ram.rs:358-368), the rule of fheram_bank_table_load_plain.  data: the words [first_row * N, min(max_addr,
+ * (first_row + n_rows) * N)) in the layout fheram_ram_encrypt_sk takes (byte w of word j at data[j * word_size + w]; sub-RAM w holds
+ * byte w of every word, row r coefficient q holds word r * N + q); data_len = that word count * word_size; a ragged last row is
+ * zero-padded.  The bytes are staged row by row into a pinned buffer, copied once and turned into rows by ONE launch (k_rows_plain);
+ * the only host wait is for the previous plain load's copy out of the pinned buffer.  Needs no keys and no secret.
+ * A whole-member load (first_row = 0, n_rows = fheram_rows) acts as fheram_bank_ram_upload does: the member becomes readable, its
+ * state flag is cleared and whatever an earlier operation kept of its rows is void.  A row range needs a member that has rows
+ * (FHERAM_ERR_UNINITIALIZED) and is not between read_prepare_write and write (FHERAM_ERR_STATE), and voids the same.
+ * FHERAM_ERR_INVALID_ARG: no such member, null data, a row range that is empty or outside the member, a data_len that does not match. */
+int fheram_bank_ram_load_plain(fheram_bank* bank, int member, size_t first_row, size_t n_rows, const uint8_t* data, size_t data_len);
+/* the register file's twin: data_len = 2^bits * word_size bytes; acts as fheram_bank_regs_upload does */
+int fheram_bank_regs_load_plain(fheram_bank* bank, fheram_regs* regs, const uint8_t* data, size_t data_len);
+/* n reads at PUBLIC word addresses as ONE operation: with addrs[k] = r_k * N + q_k, for every word ciphertext y
+ *     out_k[y] = trace(0, log N)( glwe_rotate(-q_k, rows[members[k]][y][r_k]) )
+ * an encryption of [v, 0, .., 0], the form every read result has.  One launch gathers the n * word_size rotated ciphertexts
+ * (k_peek_gather), then ONE trace runs over all of them in the form the bank's configuration selects (the single tail launch up to 8
+ * ciphertexts).  1 <= n <= FHERAM_PEEK_MAX, n * word_size <= 64; members and addresses may repeat.  It changes no row, state flag,
+ * tree, result slot or memo.  out: [n][word_size][GLWE] or NULL (no host wait; fheram_bank_peek_result later).  The outputs are the
+ * bank's "last peek": FHERAM_SRC_PEEK_RESULT names them until the next fheram_bank_peek or fheram_bank_poke.
+ * FHERAM_ERR_INVALID_ARG: null pointers, n or n * word_size out of range, a member outside the bank, an address >= max_addr;
+ * FHERAM_ERR_UNINITIALIZED: a member without rows; FHERAM_ERR_KEYS: keys not loaded; FHERAM_ERR_STATE: a member between
+ * read_prepare_write and write (its rows are rotated). */
+int fheram_bank_peek(fheram_bank* bank, const int* members, const uint64_t* addrs, int n, int64_t* out /* [n][word_size][GLWE] or NULL */);
+/* outputs [first, first + n) of the bank's last peek (or the old words of its last poke); FHERAM_ERR_STATE before any has run */
+int fheram_bank_peek_result(fheram_bank* bank, int first, int n, int64_t* out);
+/* n writes at PUBLIC word addresses as ONE operation: entry k writes the word srcs[k] names — any kind a select candidate may have,
+ * HOST (slot index < FHERAM_PEEK_MAX of host_words) included, checked and staged as fheram_bank_regs_write checks and stages its
+ * source — at addrs[k] of members[k].  All entries see the rows as they are before the call: for every touched (member, row r, word
+ * ciphertext y), with j over the entries that fall in that row,
+ *     R' = glwe_normalize( R - sum_j glwe_rotate(+q_j, t_j[y]) + sum_j glwe_rotate(+q_j, w_j[y]) )
+ * where t_j is the peek of entry j, computed by the same gather and trace, and w_j the written word.  ONE more launch (k_poke_merge)
+ * does the whole merge.  The t_j stay readable as the last peek — the OLD words, as read_prepare_write returns them
+ * (fheram_bank_peek_result, FHERAM_SRC_PEEK_RESULT); a PEEK_RESULT source of the call itself names the outputs of the peek or poke
+ * BEFORE it.  No host wait beyond the staging of host words.  What an earlier operation kept of the rows of every touched member is
+ * void, as after an upload; untouched members and rows do not change.  The (member, address) pairs must be distinct.
+ * Refusals as fheram_bank_peek's, and FHERAM_ERR_INVALID_ARG: null sources, a target named twice, an unknown source kind or index, a
+ * HOST source with host_words == NULL; FHERAM_ERR_STATE: a source kind whose operation has not run, a MEMBER_RESULT member without a
+ * result; FHERAM_ERR_RANGE: a host limb out of range. */
+int fheram_bank_poke(fheram_bank* bank, const int* members, const uint64_t* addrs, int n, const fheram_select_src* srcs, const int64_t* host_words);
+/* Self-test of the public side's FHERAM_ERR_DEVICE path, as fheram_bank_selftest_fail_select_alloc: the nth device allocation its
+ * buffers ask for from now on fails once (0 withdraws the request). */
+int fheram_bank_selftest_fail_public_alloc(fheram_bank* bank, int nth);
+
 /* ---- MIXED READS: a read list, a table read and a register read of one bank as ONE operation.
  * *** CONTRACT-COMPATIBLE ONLY *** as its three parts are.  The reads of a VM step — the fetch from a table, rs1 / rs2 from the
  * register file, the data read of a member — take their addresses and selectors from one derive list launch and do not depend on each
