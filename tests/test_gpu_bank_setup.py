@@ -75,7 +75,7 @@ def shared(w13):
 
 
 def field_oracle(w, max_addr, decomp):
-    ob = w.po.Oracle(w.po.OParams(max_addr=max_addr, word_size=w.ws, decomp_n=decomp))
+    ob = w.po.Oracle(w.oparams(max_addr, decomp_n=decomp))
     return ob, ob.keys_prepare(w.evk)
 
 

@@ -27,8 +27,8 @@ PADDED = {(2, 2): (16, [2, 2, 2, 2, 2, 2]), (1, 3): (16, [1, 3, 2, 3, 3]), (2, 3
 class LaneWorld(SelWorld):
     """a SelWorld plus the oracles of field selectors and the host-side assembly of lane-mapped candidates"""
 
-    def __init__(self, po, max_addr, n_members, word_size, seed):
-        super().__init__(po, max_addr, n_members, word_size, seed)
+    def __init__(self, po, max_addr, n_members, word_size, seed, **crypto):
+        super().__init__(po, max_addr, n_members, word_size, seed, **crypto)
         self._field, self._fdigits = {}, {}
 
     def field_oracle(self, widths):
@@ -38,7 +38,7 @@ class LaneWorld(SelWorld):
             max_addr, padded = PADDED[key]
             assert max_addr == 1 << sum(widths) and sum(padded) == 12
             assert self.po.get_base_2d(max_addr, padded) == [list(widths)]   # a plan the oracle reads differently fails here, loudly
-            ob = self.po.Oracle(self.po.OParams(max_addr=max_addr, word_size=self.ws, decomp_n=padded))
+            ob = self.po.Oracle(self.oparams(max_addr, decomp_n=padded))
             assert ob.n_digits == len(widths)
             self._field[key] = (ob, ob.keys_prepare(self.evk))
         return self._field[key]

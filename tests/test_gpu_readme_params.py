@@ -1,8 +1,12 @@
 """The parameter block of the reference's README (README.md:17-34): K_PT = 9, K_EVK = 5 * BASEK for every evaluation key
 — 5-limb trace / packing keys instead of the source constants' 4 (parameters.rs:17).  The published 450 ms / 1200 ms were
-taken with this block (README.md:36), so the bench can be run on it (`bench.py --params readme`); here every op the
-5-limb keys reach is compared with the oracle bit for bit, and the example flow runs at MAX_ADDR = 2^14 (the committed
-digests at 2^14 and 2^18 are reproduced by tests/test_gpu_golden.py)."""
+taken with this block (README.md:36), so the bench can be run on it (`bench.py --params readme`); here every op of a
+CONTEXT that the 5-limb keys reach is compared with the oracle bit for bit, and the example flow runs at MAX_ADDR = 2^14
+(the committed digests at 2^14 and 2^18 are reproduced by tests/test_gpu_golden.py).  The bank operations meet the block
+elsewhere: ranges, lists and batches in test_gpu_bank.py (the `w16` fixture), test_gpu_read_batch.py, test_gpu_read_list.py,
+test_gpu_write_list.py and test_gpu_write_rotate_fused.py; read_mix, read_prepare_write_mix, select, select_lanes, the register
+file, table_read, peek / poke / plain loads and the setup side in test_gpu_readme_bank.py; extreme limbs through the 5-limb
+chain kernels and the mix top in test_gpu_extremes_readme.py."""
 import numpy as np
 import pytest
 

@@ -24,14 +24,18 @@ N_BITS = 32
 class SelWorld(World):
     """a World plus what a select needs of the oracle: small oracles of max_addr = 2^b, encrypted integers, selector digits"""
 
-    def __init__(self, po, max_addr, n_members, word_size, seed):
-        super().__init__(po, max_addr, n_members, word_size=word_size, seed=seed, n_addr=3)
+    def __init__(self, po, max_addr, n_members, word_size, seed, **crypto):
+        super().__init__(po, max_addr, n_members, word_size=word_size, seed=seed, n_addr=3, **crypto)
         self._small, self._ints, self._digits, self._cand = {}, {}, {}, {}
 
+    def oparams(self, max_addr, **over):
+        """OParams of another shape under this world's crypto block (its keys have that block's limb counts); `over` wins"""
+        return self.po.OParams(**{**self.crypto, "max_addr": max_addr, "word_size": self.ws, **over})
+
     def small(self, b):
-        """(oracle of max_addr = 2^b with this world's word size, its prepared keys)"""
+        """(oracle of max_addr = 2^b with this world's word size and crypto block, its prepared keys)"""
         if b not in self._small:
-            ob = self.po.Oracle(self.po.OParams(max_addr=1 << b, word_size=self.ws))
+            ob = self.po.Oracle(self.oparams(1 << b))
             self._small[b] = (ob, ob.keys_prepare(self.evk))
         return self._small[b]
 

@@ -183,7 +183,7 @@ def test_field_selector_of_two_six_bit_fields(w2, bank2):
     another, through the derive list and through fheram_bank_selector_derive_fields"""
     w, pkg, D = w2, w2.pkg, w2.pkg.Derive
     assert w.po.get_base_2d(1 << 12, [6, 6]) == [[6, 6]]
-    ob = w.po.Oracle(w.po.OParams(max_addr=1 << 12, word_size=w.ws, decomp_n=[6, 6]))
+    ob = w.po.Oracle(w.oparams(1 << 12, decomp_n=[6, 6]))
     okeys = ob.keys_prepare(w.evk)
     fa, fb = (pkg.FheUintPrepared.from_host(bank2, w.bits(v)) for v in (VALUE, VALUE_B))
     digits = ob.address_from_fheuint(np.concatenate([w.bits(VALUE)[3:9], w.bits(VALUE_B)[11:17]]), sign=False)
@@ -213,7 +213,7 @@ class PlanWorld(SelWorld):
 
     def small(self, b):
         if b not in self._small:
-            ob = self.po.Oracle(self.po.OParams(max_addr=1 << b, word_size=self.ws, decomp_n=self.plan))
+            ob = self.po.Oracle(self.oparams(1 << b, decomp_n=self.plan))
             self._small[b] = (ob, ob.keys_prepare(self.evk))
         return self._small[b]
 
