@@ -28,12 +28,20 @@
 // members); a bank of ONE member is a plain context in every respect.  Bank operations are never captured into a hipGraph: under graph = 1
 // they are enqueued directly, in the forms that mode selects.
 // The bank's oblivious select (fheram_bank_select, fheram_bank_select_lanes and the write that takes its words from them) is select.hpp: it runs on buffers of its own
-// (`sel`) and reads, of what is here, only where a member's result and the last read list's results sit.
+// (`sel`) and reads, of what is here, only where a member's result and the last outputs of each kind (LastOutputs) sit.
 #pragma once
 #include "path.hpp"
 
 struct fheram_regs;   // a register file of the bank (regs.hpp)
 struct fheram_table;  // a table of the bank (table.hpp)
+
+// The kinds of operation whose outputs stay readable until the next of the kind: a select candidate may name them (FHERAM_SRC_*_RESULT)
+// and a _result entry point downloads them.  One record per kind says how many there are and where they sit.
+enum LastKind { LAST_LIST, LAST_SELECT, LAST_REGS, LAST_TABLE, LAST_PEEK, LAST_KINDS };
+struct LastOutputs {
+    int n = 0;        // outputs of the last operation of the kind; 0: none has run
+    ResHome home;     // where they are: the kind's own buffer set, or the mix's (path.hpp)
+};
 
 struct fheram_bank {
     fheram_ctx* c = nullptr;      // word count M * mws; never row-sharded, never part of a group
@@ -42,7 +50,7 @@ struct fheram_bank {
     double* d_prep = nullptr;     // [n][n_digits] prepared GGSW: the digits of the k-th address of the set being read   (M > 1)
     double* d_prep_inv = nullptr; // [n][n_digits] the inverse digits of the k-th address of the set being written      (M > 1)
     DenseBufs list;               // fheram_bank_read_list: buffers of its own, sized by mws
-    int list_n = 0;               // entries of the last list (their results are in list.res); 0: none has run
+    LastOutputs last[LAST_KINDS]; // the last read list, select, register read, table read and peek / poke (each set by whatever finishes one: the single calls, the mixes)
     DenseBufs wl;                 // the dense plan's buffers (read_prepare_write / write lists), sized by mws
     // what the last dense read_prepare_write left in wl.A (RamState::memo_alone of a list): for kept_n entries with the map kept_map ...
     int kept_alone = 0, kept_n = 0;
@@ -50,26 +58,20 @@ struct fheram_bank {
     bool wl_holds[FHERAM_BANK_MAX] = {};   // ... and member m is still as that operation left it (cleared by whatever touches the member)
     SelectBufs sel;               // fheram_bank_select: buffers of its own (select.hpp)
     SelectLaneTable lanes;        // fheram_bank_select_lanes: the pointer table of its pack (allocated on the first lanes call)
-    int sel_n = 0, sel_fail_alloc = 0;   // outputs of the last select (in sel.res; 0: none has run); the self-test's failing allocation, as wl_fail_alloc
+    int sel_fail_alloc = 0;       // the self-test's failing allocation, as wl_fail_alloc
     bool has_res[FHERAM_BANK_MAX] = {};  // member m has the result of a read / read_prepare_write in its slot (a select may take it as a candidate)
     int wl_fail_alloc = 0;        // fheram_bank_selftest_fail_list_alloc: the wl_fail_alloc-th next device allocation of wl fails (0: none)
-    // the register files (regs.hpp): what they share, the live ones, the outputs of the last fheram_bank_regs_read (in regs.res; 0: none has
-    // run) and where the last fheram_bank_regs_read_prepare_write left its result (the kept trace of regs_old_owner; nullptr: none has run)
-    RegsBufs regs;
+    // the register files (regs.hpp): what they share, the live ones, and — beside the records above, with ONE result — where the last
+    // fheram_bank_regs_read_prepare_write left its (the kept trace of regs_old_owner; nullptr: none has run)
+    OneRowSet regs;
     std::vector<fheram_regs*> regfiles;
-    int regs_n = 0;
     const int32_t* regs_old = nullptr;
     const fheram_regs* regs_old_owner = nullptr;
-    // the tables (table.hpp): what they share, the live ones, the outputs of the last fheram_bank_table_read (in tabs.res; 0: none has run)
-    TableBufs tabs;
+    // the tables (table.hpp): what they share, the live ones
+    OneRowSet tabs;
     std::vector<fheram_table*> tables;
-    int table_n = 0;
-    // fheram_bank_read_mix (mix.hpp): its buffers, and where the last operation of each kind left its outputs (its own set, or the mix's)
-    MixBufs mix;
-    ResHome list_home, table_home, regs_home;
-    // the public side (public_io.hpp): its buffers, and the outputs of the last fheram_bank_peek / _poke (in pub.res[pub.cur]; 0: none has run)
-    PublicBufs pub;
-    int peek_n = 0;
+    MixBufs mix;                  // fheram_bank_read_mix (mix.hpp)
+    PublicBufs pub;               // the public side (public_io.hpp)
     int pub_fail_alloc = 0;       // fheram_bank_selftest_fail_public_alloc: the pub_fail_alloc-th next device allocation of pub fails (0: none)
 };
 
@@ -289,12 +291,35 @@ int bank_write_set(fheram_bank* b, const MemberSet& s, const fheram_addr* const*
     HIPCHK(c, hipGetLastError());
     return FHERAM_OK;
 }
-int list_result(fheram_bank* b, int first, int n, int64_t* out) {
+// ---- the last outputs of a kind: the words its messages use, and the one download --------------------------------------------------------
+struct LastKindText {
+    int src;                       // the FHERAM_SRC_* kind that names them
+    const char *unit, *units;      // what one of them is called
+    const char *last, *of_last;    // the operation: as a source names it, as its _result entry point does
+    const char* none;              // "... on this bank": none has run
+};
+const LastKindText LAST_TEXT[LAST_KINDS] = {
+    {FHERAM_SRC_LIST_RESULT, "entry", "entries", "read list", "list", "no read list has run"},
+    {FHERAM_SRC_SELECT_RESULT, "output", "outputs", "select", "select", "no select has run"},
+    {FHERAM_SRC_REGS_RESULT, "output", "outputs", "register read", "register read", "no fheram_bank_regs_read has run"},
+    {FHERAM_SRC_TABLE_RESULT, "output", "outputs", "table read", "table read", "no fheram_bank_table_read has run"},
+    {FHERAM_SRC_PEEK_RESULT, "output", "outputs", "peek", "peek", "no fheram_bank_peek or fheram_bank_poke has run"},
+};
+// outputs [first, first + n) of the last operation of the kind, behind the entry point's null-bank test
+int last_result(fheram_bank* b, LastKind kind, int first, int n, int64_t* out) {
+    fheram_ctx* c = b->c;
+    const LastOutputs& L = b->last[kind];
+    const LastKindText& t = LAST_TEXT[kind];
+    if (!out) return fail(c, FHERAM_ERR_INVALID_ARG, "null output");
+    if (!L.n) return fail(c, FHERAM_ERR_STATE, std::string(t.none) + " on this bank");
+    if (first < 0 || n < 1 || first > L.n - n)
+        return fail(c, FHERAM_ERR_INVALID_ARG, std::string(t.units) + " [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") are empty or outside the last " + t.of_last + "'s " + std::to_string(L.n) + " " + t.units);
+    HIPCHK(c, hipSetDevice(c->device));
     const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
-    const ResRun run{b->list_home.res + (size_t)first * per, (size_t)n * per};
-    return result_export(b->c, &run, 1, b->list_home.h, b->list_home.d_h, out);
+    const ResRun run{L.home.res + (size_t)first * per, (size_t)n * per};
+    return result_export(c, &run, 1, L.home.h, L.home.d_h, out);
 }
-void list_home_own(fheram_bank* b) { b->list_home = ResHome{b->list.res, b->list.h_res, b->list.d_h_res, -1}; }
+void list_done(fheram_bank* b, int n) { b->last[LAST_LIST] = LastOutputs{n, ResHome{b->list.res, b->list.h_res, b->list.d_h_res, -1}}; }
 
 }  // namespace
 
@@ -452,16 +477,15 @@ int fheram_bank_read_list(fheram_bank* b, const int* members, const fheram_addr*
     fheram_ctx* c = b->c;
     HIPCHK(c, hipSetDevice(c->device));
     const long G = (long)fheram_ctx::GLWE;
-    b->list_n = 0;   // until this list is enqueued there is no last list: several entries overwrite res as they run (one entry only with its closing copy, but the rule is one)
+    b->last[LAST_LIST].n = 0;   // until this list is enqueued there is no last list: several entries overwrite res as they run (one entry only with its closing copy, but the rule is one)
     if (n == 1) {   // the plain single-member read; its result is also the list's
         rc = dense_reserve(c, b->list, 1, b->mws);
         if (rc == FHERAM_OK) rc = bank_read_set(b, s, addrs, false, nullptr);
         if (rc != FHERAM_OK) return rc;
         launch_copy(c, member_slot(b, c->d_res, s.m[0]), ref(b->list.res, G, 0), 1, b->mws);
-        b->list_n = 1;
-        list_home_own(b);
+        list_done(b, 1);
         HIPCHK(c, hipGetLastError());
-        return out ? list_result(b, 0, 1, out) : FHERAM_OK;
+        return out ? last_result(b, LAST_LIST, 0, 1, out) : FHERAM_OK;
     }
     RamState st{true, false, false, 0, false};
     return read_many(c, b->list, &st, addrs, n, b->mws, s.map(), b->M > 1, out, [&](const Opnds& o) {
@@ -471,8 +495,7 @@ int fheram_bank_read_list(fheram_bank* b, const int* members, const fheram_addr*
             for (int k = 0; k < n; k++) if (s.m[k] == m) last = k;
             if (last >= 0) launch_copy(c, o.slice(ref(b->list.res, G, 0), last), member_slot(b, c->d_res, m), 1, b->mws);
         }
-        b->list_n = n;
-        list_home_own(b);
+        list_done(b, n);
     });
 }
 // n independent Ram::read_prepare_write (ram.rs:196-222), entry k on member members[k], as one operation (header comment)
@@ -493,14 +516,7 @@ int fheram_bank_selftest_fail_list_alloc(fheram_bank* b, int nth) {
     return FHERAM_OK;
 }
 int fheram_bank_read_list_result(fheram_bank* b, int first, int n, int64_t* out) {
-    if (!b) return FHERAM_ERR_INVALID_ARG;
-    fheram_ctx* c = b->c;
-    if (!out) return fail(c, FHERAM_ERR_INVALID_ARG, "null output");
-    if (!b->list_n) return fail(c, FHERAM_ERR_STATE, "no read list has run on this bank");
-    if (first < 0 || n < 1 || first > b->list_n - n)
-        return fail(c, FHERAM_ERR_INVALID_ARG, "entries [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") are empty or outside the last list's " + std::to_string(b->list_n) + " entries");
-    HIPCHK(c, hipSetDevice(c->device));
-    return list_result(b, first, n, out);
+    return b ? last_result(b, LAST_LIST, first, n, out) : FHERAM_ERR_INVALID_ARG;
 }
 int fheram_bank_sync(fheram_bank* b) { return b ? fheram_sync(b->c) : FHERAM_ERR_INVALID_ARG; }
 int fheram_bank_roundoff_max(fheram_bank* b, double* max_out) { return b ? fheram_roundoff_max(b->c, max_out) : FHERAM_ERR_INVALID_ARG; }

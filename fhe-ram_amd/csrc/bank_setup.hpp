@@ -207,7 +207,7 @@ int fheram_bank_source_decrypt(fheram_bank* b, const fheram_secret* sk, const fh
         return fail(c, FHERAM_ERR_INVALID_ARG, "n = " + std::to_string(n) + ": n * word_size is outside [1, 64]");
     int rc = decrypt_check(c, sk);
     if (rc != FHERAM_OK) return rc;
-    SelectNeeds need;
+    unsigned need = 0;
     for (int i = 0; i < n; i++) {
         const std::string who = "source " + std::to_string(i);
         if (srcs[i].kind == FHERAM_SRC_HOST || srcs[i].kind == FHERAM_SRC_ZERO)

@@ -16,8 +16,8 @@
 //                  chain_form gives it (Tail without products, Mid, Chain, Steps).
 // CONTRACT-COMPATIBLE ONLY, as its parts are: entry k of a group is int64-identical to output k of that group's single
 // call, and the bank is left where the sequence read_list, table_read, regs_read leaves it.  The outputs live in the mix's own buffers;
-// where the last operation of a kind left its outputs is the bank's ResHome of that kind (path.hpp), which select_source and the three
-// _result downloads follow.  An empty group leaves its kind's last outputs readable: the mix has three result buffers and writes the one
+// where the last operation of a kind left its outputs is the bank's LastOutputs record of that kind (bank.hpp), which select_source and
+// the _result downloads follow.  An empty group leaves its kind's last outputs readable: the mix has three result buffers and writes the one
 // no empty kind's home is in.  Buffers are allocated whole by the first call; no operation allocates (the list group grows the read
 // list's dense set as fheram_bank_read_list does).
 //
@@ -85,13 +85,8 @@ int mix_reserve(fheram_bank* b) {
     const size_t ct = (size_t)nw.cap * fheram_ctx::GLWE * sizeof(int32_t);
     hipError_t e = mix_register();
     for (int32_t** p : {&nw.ep, &nw.tmp, &nw.res[0], &nw.res[1], &nw.res[2]}) if (e == hipSuccess) e = hipMalloc((void**)p, ct);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&nw.h_res, ct * 2 + sizeof(int64_t), hipHostMallocMapped);   // int64, + the monitor's maximum
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&nw.d_h_res, nw.h_res, 0);
-    if (e != hipSuccess) {
-        mix_bufs_free(nw);
-        (void)hipGetLastError();   // the next op's error check must not see this allocation's failure
-        return fail(c, FHERAM_ERR_DEVICE, std::string("buffers of the bank's mixed reads: ") + hipGetErrorString(e));
-    }
+    if (e == hipSuccess) e = pinned_result(&nw.h_res, &nw.d_h_res, ct);
+    if (e != hipSuccess) { mix_bufs_free(nw); return reserve_failed(c, e, "buffers of the bank's mixed reads"); }
     b->mix = nw;
     return FHERAM_OK;
 }
@@ -108,9 +103,8 @@ int mix_reserve_prepares(fheram_bank* b) {
     if (e == hipSuccess) e = hipMalloc((void**)&keep, (size_t)b->mws * glwe);
     if (e == hipSuccess) e = hipMalloc((void**)&prep, (size_t)c->n_digits * fheram_ctx::GGSW * sizeof(double));
     if (e != hipSuccess) {
-        for (void* p : {(void*)own, (void*)keep, (void*)prep}) if (p) hipFree(p);
-        (void)hipGetLastError();   // the next op's error check must not see this allocation's failure
-        return fail(c, FHERAM_ERR_DEVICE, std::string("buffers of the bank's mixed read_prepare_write: ") + hipGetErrorString(e));
+        bufs_free({own, keep, prep}, {}, {});
+        return reserve_failed(c, e, "buffers of the bank's mixed read_prepare_write");
     }
     M.own = own; M.keep = keep; M.prep = prep;
     return FHERAM_OK;
@@ -203,31 +197,14 @@ int mix_check_reads(fheram_bank* b, const fheram_mix_reads* r, MemberSet* s) {
     }
     if (nt) {   // ... of fheram_bank_table_read
         if (!r->tables || !r->table_sels) return fail(c, FHERAM_ERR_INVALID_ARG, "null table list or null selector list");
-        for (int k = 0; k < nt; k++) {
-            const std::string who = "table selector " + std::to_string(k);
-            const int rc = table_check_handle(b, r->tables[k], "table " + std::to_string(k));
-            if (rc != FHERAM_OK) return rc;
-            const fheram_selector* sel = r->table_sels[k];
-            if (!sel || sel->bank != b) return fail(c, FHERAM_ERR_INVALID_ARG, who + " is null or belongs to another bank");
-            if (sel->empty) return fail(c, FHERAM_ERR_INVALID_ARG, who + " is empty: fheram_bank_table_selector_alloc without fheram_bank_selector_derive");
-            if (sel->bits != r->tables[k]->bits) return fail(c, FHERAM_ERR_INVALID_ARG, who + " has " + std::to_string(sel->bits) + " bits, table " + std::to_string(k) + " " + std::to_string(r->tables[k]->bits));
-            if (sel->n_digits != r->table_sels[0]->n_digits)
-                return fail(c, FHERAM_ERR_INVALID_ARG, who + " has " + std::to_string(sel->n_digits) + " digits, table selector 0 " + std::to_string(r->table_sels[0]->n_digits) + ": all selectors of the group share the digit count");
-        }
-        for (int k = 0; k < nt; k++)
-            if (!r->tables[k]->initialized) return fail(c, FHERAM_ERR_UNINITIALIZED, "unitialized memory: table " + std::to_string(k) + " has had no fheram_bank_table_upload or fheram_bank_table_load_plain");
+        const int rc = table_check_reads(b, r->tables, r->table_sels, nt, "table selector ", "all selectors of the group share the digit count");
+        if (rc != FHERAM_OK) return rc;
     }
     if (nr) {   // ... of fheram_bank_regs_read
         int rc = regs_check_handle(b, r->regs);
         if (rc != FHERAM_OK) return rc;
         if (!r->reg_sels) return fail(c, FHERAM_ERR_INVALID_ARG, "null selector list");
-        for (int k = 0; k < nr; k++) {
-            rc = regs_check_selector(b, r->regs, r->reg_sels[k], "register selector " + std::to_string(k));
-            if (rc != FHERAM_OK) return rc;
-            if (r->reg_sels[k]->n_digits != r->reg_sels[0]->n_digits)
-                return fail(c, FHERAM_ERR_INVALID_ARG, "register selector " + std::to_string(k) + " has " + std::to_string(r->reg_sels[k]->n_digits) + " digits, register selector 0 " + std::to_string(r->reg_sels[0]->n_digits) + ": all selectors of the group share the digit count");
-        }
-        rc = regs_check_ready(b, r->regs, 0);
+        rc = regs_check_reads(b, r->regs, r->reg_sels, nr, "register selector ", "all selectors of the group share the digit count");
         if (rc != FHERAM_OK) return rc;
     }
     return FHERAM_OK;
@@ -249,7 +226,8 @@ int mix_run(fheram_bank* b, const fheram_mix_reads* r, const MemberSet& s, const
         rc = dense_reserve(c, b->wl, np, ws, true, &b->wl_fail_alloc);
         if (rc != FHERAM_OK) return rc;
     }
-    if (nl) b->list_n = 0;   // until this mix is enqueued its kinds have no last outputs (as the single calls)
+    LastOutputs* const last = b->last;
+    if (nl) last[LAST_LIST].n = 0;   // until this mix is enqueued its kinds have no last outputs (as the single calls)
     if (nl > 1) {
         rc = dense_reserve(c, b->list, nl, ws);
         if (rc != FHERAM_OK) return rc;
@@ -259,15 +237,14 @@ int mix_run(fheram_bank* b, const fheram_mix_reads* r, const MemberSet& s, const
     // the result buffer no EMPTY kind's last outputs live in (at most two of the three are taken while a read group is not empty; a call
     // without reads has the fourth)
     int slot = 0;
-    auto taken = [&](int q) {
-        return (!nl && b->list_n && b->list_home.mix_slot == q) || (!nt && b->table_n && b->table_home.mix_slot == q) || (!nr && b->regs_n && b->regs_home.mix_slot == q);
-    };
+    auto holds = [&](int cnt, LastKind kind, int q) { return !cnt && last[kind].n && last[kind].home.mix_slot == q; };
+    auto taken = [&](int q) { return holds(nl, LAST_LIST, q) || holds(nt, LAST_TABLE, q) || holds(nr, LAST_REGS, q); };
     const bool reads = nl + nt + nr > 0;
     while (reads && taken(slot)) slot++;
     int32_t* const resbuf = reads ? M.res[slot] : M.own;
     regs_begin(c);
-    if (nt) b->table_n = 0;
-    if (nr) b->regs_n = 0;
+    if (nt) last[LAST_TABLE].n = 0;
+    if (nr) last[LAST_REGS].n = 0;
     const long G = (long)fheram_ctx::GLWE;
     const size_t per = (size_t)ws * fheram_ctx::GLWE;
     MixEntry ent[FHERAM_MIX_MAX];
@@ -390,15 +367,14 @@ int mix_run(fheram_bank* b, const fheram_mix_reads* r, const MemberSet& s, const
             for (int k = 0; k < nl; k++) if (s.m[k] == m) last = k;
             if (last >= 0) hand(slice(res, last), member_slot(b, c->d_res, m));
         }
-        b->list_n = nl;
-        b->list_home = ResHome{resbuf, M.h_res, M.d_h_res, slot};
+        last[LAST_LIST] = LastOutputs{nl, ResHome{resbuf, M.h_res, M.d_h_res, slot}};
     }
     if (p) {
         ProfScope ps(c, "elementwise", (uint64_t)sa.n * ws);
         mix_scatter_launch(ws, c->cur, sa);
     }
-    if (nt) { b->table_n = nt; b->table_home = ResHome{resbuf + (size_t)nl * per, M.h_res, M.d_h_res, slot}; }
-    if (nr) { b->regs_n = nr; b->regs_home = ResHome{resbuf + (size_t)(nl + nt) * per, M.h_res, M.d_h_res, slot}; }
+    if (nt) last[LAST_TABLE] = LastOutputs{nt, ResHome{resbuf + (size_t)nl * per, M.h_res, M.d_h_res, slot}};
+    if (nr) last[LAST_REGS] = LastOutputs{nr, ResHome{resbuf + (size_t)(nl + nt) * per, M.h_res, M.d_h_res, slot}};
     HIPCHK(c, hipGetLastError());
     // 5. ONE export for the groups the caller wants
     ResRun runs[5];

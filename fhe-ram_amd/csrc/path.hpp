@@ -253,6 +253,45 @@ int read_impl(const Opnds& o, const RamView& a, bool prepare_write) {
     return rc;
 }
 
+// ---- what every buffer set below shares: the dense sets' and those of the bank's one-row operations (select.hpp, regs.hpp, table.hpp, public_io.hpp, mix.hpp) ----
+// HOST BYTES ON THEIR WAY TO THE DEVICE: a device buffer, its pinned twin, the event of the last copy out of the twin and whether one
+// is in flight.  The owner allocates the three in the order of its own set (device buffers first, then pinned, then events) and frees
+// them with bufs_free; a call waits for the last copy (stage_wait), fills the twin, copies on the main stream and records (stage_record).
+struct HostStage {
+    unsigned char *d = nullptr, *h = nullptr;
+    hipEvent_t ev = nullptr;
+    bool busy = false;
+    template <typename T> T* dev() const { return reinterpret_cast<T*>(d); }
+    template <typename T> T* host() const { return reinterpret_cast<T*>(h); }
+    hipError_t pin(size_t bytes) { return hipHostMalloc((void**)&h, bytes, hipHostMallocDefault); }
+    hipError_t event() { return hipEventCreateWithFlags(&ev, hipEventDisableTiming); }
+};
+int stage_wait(fheram_ctx* c, HostStage& s) {   // the last call's copy out of the pinned twin; no other host wait
+    if (s.busy) { HIPCHK(c, hipEventSynchronize(s.ev)); s.busy = false; }
+    return FHERAM_OK;
+}
+int stage_record(fheram_ctx* c, HostStage& s) {
+    HIPCHK(c, hipEventRecord(s.ev, c->stream));
+    s.busy = true;
+    return FHERAM_OK;
+}
+// a set's buffers: the device ones, then the pinned ones, then the events
+void bufs_free(std::initializer_list<void*> device, std::initializer_list<void*> pinned, std::initializer_list<hipEvent_t> events) {
+    for (void* p : device) if (p) hipFree(p);
+    for (void* p : pinned) if (p) hipHostFree(p);
+    for (hipEvent_t e : events) if (e) hipEventDestroy(e);
+}
+// the pinned, device-visible buffer a set's results are exported through: ct bytes of int32 as int64, + the monitor's maximum
+hipError_t pinned_result(int64_t** h, int64_t** d_h, size_t ct) {
+    const hipError_t e = hipHostMalloc((void**)h, ct * 2 + sizeof(int64_t), hipHostMallocMapped);
+    return e == hipSuccess ? hipHostGetDevicePointer((void**)d_h, *h, 0) : e;
+}
+// a reserve that failed, its new set freed: the next op's error check must not see this allocation's failure
+int reserve_failed(fheram_ctx* c, hipError_t e, const std::string& what) {
+    (void)hipGetLastError();
+    return fail(c, FHERAM_ERR_DEVICE, what + ": " + hipGetErrorString(e));
+}
+
 // ---- several Ram::read (ram.rs:172-191) as one launch sequence: fheram_read_batch, fheram_bank_read_list ------------------------------
 // A read does not change the RAM (SubRam::read asserts !state and only writes its scratch, ram.rs:393-396): n reads at n addresses share the
 // keys and every packing and trace step; only the products with the address digits differ (and, in a bank, whose rows they read).  Such an
@@ -260,9 +299,7 @@ int read_impl(const Opnds& o, const RamView& a, bool prepare_write) {
 // word w of address k and every address-independent step is ONE launch over gy = n * ws.  A bank's read_prepare_write / write lists run on
 // such a set too (bank.hpp), with every buffer of a view in it.
 void dense_free(DenseBufs& L) {
-    void* bufs[] = {L.A, L.B, L.C, L.D, L.part, L.tmp, L.tmp2, L.res, L.tree, L.w, L.trtop, L.prep};
-    for (void* p : bufs) if (p) hipFree(p);
-    if (L.h_res) hipHostFree(L.h_res);
+    bufs_free({L.A, L.B, L.C, L.D, L.part, L.tmp, L.tmp2, L.res, L.tree, L.w, L.trtop, L.prep}, {L.h_res}, {});
     L = DenseBufs{};
 }
 // The third arena is only needed where the alone packer levels run as the single-launch tail chain on the operation's rows (at most
@@ -306,13 +343,11 @@ int dense_reserve(fheram_ctx* c, DenseBufs& L, int n, int ws, bool all = false, 
             for (int32_t** p : {&L.tmp, &L.tmp2}) dev(p, ct);
             dev(&L.prep, (size_t)n * c->n_digits * fheram_ctx::GGSW * sizeof(double));
         }
-        if (e == hipSuccess) e = hipHostMalloc((void**)&L.h_res, ct * 2 + sizeof(int64_t), hipHostMallocMapped);   // int64, + the monitor's maximum
-        if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&L.d_h_res, L.h_res, 0);
+        if (e == hipSuccess) e = pinned_result(&L.h_res, &L.d_h_res, ct);
     }
     if (e != hipSuccess) {
         dense_free(L);
-        (void)hipGetLastError();   // the next op's error check must not see this allocation's failure
-        return fail(c, FHERAM_ERR_DEVICE, (all ? "buffers of a write list of " + std::to_string(n) + " members: " : "read buffers for " + std::to_string(n) + " addresses: ") + hipGetErrorString(e));
+        return reserve_failed(c, e, all ? "buffers of a write list of " + std::to_string(n) + " members" : "read buffers for " + std::to_string(n) + " addresses");
     }
     L.cap = n;
     return FHERAM_OK;
@@ -331,73 +366,52 @@ struct SelectBufs {
     int32_t *packed = nullptr, *ep = nullptr, *tmp = nullptr, *tmp2 = nullptr, *res = nullptr;   // [cap] GLWE
     double* prep = nullptr;                                                                      // [prep_cap] prepared GGSW: select k's digits at k * n_digits
     int64_t *h_res = nullptr, *d_h_res = nullptr;                                                // pinned, device-visible: the results as int64 (+ the monitor's maximum)
-    int32_t *d_host = nullptr, *h_host = nullptr;                                                // [host_cap] GLWE: host candidates, device / pinned
-    hipEvent_t ev_host = nullptr;                                                                // the last copy out of h_host
-    bool host_busy = false;
+    HostStage host;                                                                              // [host_cap] GLWE: host candidates
 };
 void select_free(SelectBufs& S) {
-    void* bufs[] = {S.packed, S.ep, S.tmp, S.tmp2, S.res, S.prep, S.d_host};
-    for (void* p : bufs) if (p) hipFree(p);
-    if (S.h_res) hipHostFree(S.h_res);
-    if (S.h_host) hipHostFree(S.h_host);
-    if (S.ev_host) hipEventDestroy(S.ev_host);
+    bufs_free({S.packed, S.ep, S.tmp, S.tmp2, S.res, S.prep, S.host.d}, {S.h_res, S.host.h}, {S.host.ev});
     S = SelectBufs{};
 }
-// fheram_bank_select_lanes' pointer table (select_lanes.hpp): [64 output ciphertexts][32 candidates] pointers, 16 KiB, on the device and pinned.
+// fheram_bank_select_lanes' pointer table (select_lanes.hpp): [64 output ciphertexts][32 candidates] pointers, 16 KiB — what
+// k_select_pack_lanes reads, and the pinned twin the host writes, copied by one hipMemcpyAsync per call.
 // Allocated whole on the first lanes call and freed with the bank; NOT among the buffers select_reserve counts and grows.
-struct SelectLaneTable {
-    const int32_t** d_tab = nullptr;   // what k_select_pack_lanes reads
-    const int32_t** h_tab = nullptr;   // pinned: what the host writes, copied by one hipMemcpyAsync per call
-    hipEvent_t ev = nullptr;           // the last copy out of h_tab
-    bool busy = false;
-};
+using SelectLaneTable = HostStage;
 void lane_table_free(SelectLaneTable& L) {
-    if (L.d_tab) hipFree(L.d_tab);
-    if (L.h_tab) hipHostFree(L.h_tab);
-    if (L.ev) hipEventDestroy(L.ev);
+    bufs_free({L.d}, {L.h}, {L.ev});
     L = SelectLaneTable{};
 }
 
-// What a bank's register files share (regs.hpp): the buffers of fheram_bank_regs_read — per output ciphertext the fanned-out row, the
-// products' output, a temporary and the result, for REGS_CT_MAX ciphertexts; the prepared digits of its selectors — the pinned result
-// buffer and the staged host words of a pack or a write.  Allocated whole by the bank's first fheram_bank_regs_create, freed with the bank.
-struct RegsBufs {
+// What a bank's register files share (regs.hpp), and what its tables share (table.hpp): the buffers of n reads of one-row RAMs as one
+// operation — per output ciphertext the fanned-out or gathered row, the products' output, a temporary and the result; the prepared
+// digits of its selectors — the pinned result buffer, and one host stage: the host words of a register file's pack or write, the bytes
+// of a table's load_plain.  Allocated whole by the bank's first fheram_bank_regs_create / fheram_bank_table_create, freed with the bank.
+struct OneRowSet {
     int cap = 0;                                                                  // ciphertexts of a read: min(FHERAM_SELECT_MAX * word_size, 64); 0: not allocated
     int32_t *fan = nullptr, *ep = nullptr, *tmp = nullptr, *res = nullptr;        // [cap] GLWE
-    double* prep = nullptr;                                                       // [FHERAM_SELECT_MAX * FHERAM_SELECT_BITS_MAX] prepared GGSW: read k's digits at k * n_digits
+    double* prep = nullptr;                                                       // [FHERAM_SELECT_MAX * the kind's digit limit] prepared GGSW: read k's digits at k * n_digits
     int64_t *h_res = nullptr, *d_h_res = nullptr;                                 // pinned, device-visible: the results as int64 (+ the monitor's maximum)
-    int32_t *d_host = nullptr, *h_host = nullptr;                                 // [2^FHERAM_SELECT_BITS_MAX * word_size] GLWE: host words, device / pinned
-    hipEvent_t ev_host = nullptr;                                                 // the last copy out of h_host
-    bool host_busy = false;
+    HostStage stage;                                                              // register files: [2^FHERAM_SELECT_BITS_MAX * word_size] GLWE; tables: [2^FHERAM_TABLE_BITS_MAX * word_size] bytes
 };
-void regs_bufs_free(RegsBufs& R) {
-    void* bufs[] = {R.fan, R.ep, R.tmp, R.res, R.prep, R.d_host};
-    for (void* p : bufs) if (p) hipFree(p);
-    if (R.h_res) hipHostFree(R.h_res);
-    if (R.h_host) hipHostFree(R.h_host);
-    if (R.ev_host) hipEventDestroy(R.ev_host);
-    R = RegsBufs{};
+void one_row_free(OneRowSet& S) {
+    bufs_free({S.fan, S.ep, S.tmp, S.res, S.prep, S.stage.d}, {S.h_res, S.stage.h}, {S.stage.ev});
+    S = OneRowSet{};
 }
-
-// What a bank's tables share (table.hpp): the buffers of fheram_bank_table_read — per output ciphertext the gathered row, the products'
-// output, a temporary and the result; the prepared digits of its selectors — the pinned result buffer and the staged bytes of a
-// fheram_bank_table_load_plain.  Allocated whole by the bank's first fheram_bank_table_create, freed with the bank.
-struct TableBufs {
-    int cap = 0;                                                                  // ciphertexts of a read: min(FHERAM_SELECT_MAX * word_size, 64); 0: not allocated
-    int32_t *fan = nullptr, *ep = nullptr, *tmp = nullptr, *res = nullptr;        // [cap] GLWE
-    double* prep = nullptr;                                                       // [FHERAM_SELECT_MAX * FHERAM_SELECTOR_WIDE_DIGITS_MAX] prepared GGSW: read k's digits at k * n_digits
-    int64_t *h_res = nullptr, *d_h_res = nullptr;                                 // pinned, device-visible: the results as int64 (+ the monitor's maximum)
-    uint8_t *d_data = nullptr, *h_data = nullptr;                                 // [2^FHERAM_TABLE_BITS_MAX * word_size] bytes of a load_plain, device / pinned
-    hipEvent_t ev_data = nullptr;                                                 // the last copy out of h_data
-    bool data_busy = false;
-};
-void table_bufs_free(TableBufs& B) {
-    void* bufs[] = {B.fan, B.ep, B.tmp, B.res, B.prep, B.d_data};
-    for (void* p : bufs) if (p) hipFree(p);
-    if (B.h_res) hipHostFree(B.h_res);
-    if (B.h_data) hipHostFree(B.h_data);
-    if (B.ev_data) hipEventDestroy(B.ev_data);
-    B = TableBufs{};
+// prep_digits: the digits one selector of the kind may have; stage_bytes: its host stage; what: the set, for the failure's message
+int one_row_reserve(fheram_ctx* c, OneRowSet& S, int ws, int prep_digits, size_t stage_bytes, const char* what) {
+    if (S.cap) return FHERAM_OK;
+    OneRowSet nw;
+    nw.cap = std::min(FHERAM_SELECT_MAX * ws, 64);
+    const size_t ct = (size_t)nw.cap * fheram_ctx::GLWE * sizeof(int32_t);
+    hipError_t e = hipSuccess;
+    for (int32_t** p : {&nw.fan, &nw.ep, &nw.tmp, &nw.res}) if (e == hipSuccess) e = hipMalloc((void**)p, ct);
+    if (e == hipSuccess) e = hipMalloc((void**)&nw.prep, (size_t)FHERAM_SELECT_MAX * prep_digits * fheram_ctx::GGSW * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&nw.stage.d, stage_bytes);
+    if (e == hipSuccess) e = pinned_result(&nw.h_res, &nw.d_h_res, ct);
+    if (e == hipSuccess) e = nw.stage.pin(stage_bytes);
+    if (e == hipSuccess) e = nw.stage.event();
+    if (e != hipSuccess) { one_row_free(nw); return reserve_failed(c, e, what); }
+    S = nw;
+    return FHERAM_OK;
 }
 
 // A bank's public side (public_io.hpp): the buffers of fheram_bank_peek / _poke — per ciphertext the gathered, rotated row, a temporary
@@ -409,25 +423,17 @@ struct PublicBufs {
     int32_t *fan = nullptr, *tmp = nullptr, *res[2] = {nullptr, nullptr};         // [cap] GLWE
     int cur = 0;
     int64_t *h_res = nullptr, *d_h_res = nullptr;                                 // pinned, device-visible: the results as int64 (+ the monitor's maximum)
-    int32_t *d_host = nullptr, *h_host = nullptr;                                 // [FHERAM_PEEK_MAX * word_size] GLWE: host words, device / pinned
-    uint8_t *d_data = nullptr, *h_data = nullptr;                                 // [rows * N * word_size] bytes of a load_plain, device / pinned
-    hipEvent_t ev_host = nullptr, ev_data = nullptr;                              // the last copy out of h_host / h_data
-    bool host_busy = false, data_busy = false;
+    HostStage host;                                                               // [FHERAM_PEEK_MAX * word_size] GLWE: host words
+    HostStage data;                                                               // [rows * N * word_size] bytes of a load_plain
 };
 void public_bufs_free(PublicBufs& P) {
-    void* bufs[] = {P.fan, P.tmp, P.res[0], P.res[1], P.d_host, P.d_data};
-    for (void* p : bufs) if (p) hipFree(p);
-    if (P.h_res) hipHostFree(P.h_res);
-    if (P.h_host) hipHostFree(P.h_host);
-    if (P.h_data) hipHostFree(P.h_data);
-    if (P.ev_host) hipEventDestroy(P.ev_host);
-    if (P.ev_data) hipEventDestroy(P.ev_data);
+    bufs_free({P.fan, P.tmp, P.res[0], P.res[1], P.host.d, P.data.d}, {P.h_res, P.host.h, P.data.h}, {P.host.ev, P.data.ev});
     P = PublicBufs{};
 }
 
 // fheram_bank_read_mix's own buffers (mix.hpp): per ciphertext of the shared top the products' output, a temporary and THREE result
 // buffers — a mix writes the one that holds no empty group's last outputs — and the pinned result buffer.  The digits of its one-row
-// groups are prepared into the tables' and the register files' own (TableBufs::prep, RegsBufs::prep: a group that is not empty has its
+// groups are prepared into the tables' and the register files' own (OneRowSet::prep: a group that is not empty has its
 // object, so they exist).  Allocated whole by the bank's first fheram_bank_read_mix, freed with the bank.
 // fheram_bank_read_prepare_write_mix adds three, allocated whole by the bank's first such call: a fourth result buffer for a call without
 // reads (all three others may hold an empty kind's last outputs then), the digits of a prepare list of ONE member (the context's own
@@ -441,14 +447,11 @@ struct MixBufs {
     double* prep = nullptr;                                                       // [n_digits] prepared GGSW (read_prepare_write_mix)
 };
 void mix_bufs_free(MixBufs& M) {
-    void* bufs[] = {M.ep, M.tmp, M.res[0], M.res[1], M.res[2], M.own, M.keep, M.prep};
-    for (void* p : bufs) if (p) hipFree(p);
-    if (M.h_res) hipHostFree(M.h_res);
+    bufs_free({M.ep, M.tmp, M.res[0], M.res[1], M.res[2], M.own, M.keep, M.prep}, {M.h_res}, {});
     M = MixBufs{};
 }
-// Where the last read list / table read / register read of a bank left its outputs: the operation's own buffer set, or the mix's when a
-// fheram_bank_read_mix ran that kind last.  select_source and the three _result downloads follow it.  mix_slot: which of the mix's
-// result buffers (-1: none of them).
+// Where the last operation of a kind left its outputs (bank.hpp LastOutputs): the operation's own buffer set, or the mix's when a
+// fheram_bank_read_mix ran that kind last.  mix_slot: which of the mix's result buffers (-1: none of them).
 struct ResHome {
     const int32_t* res = nullptr;                    // output 0 of the kind
     int64_t *h = nullptr, *d_h = nullptr;            // the pinned buffer a download of it goes through

@@ -81,19 +81,14 @@ int pub_reserve(fheram_bank* b) {
         else e = hipMalloc((void**)p, bytes);
     };
     for (int32_t** p : {&nw.fan, &nw.tmp, &nw.res[0], &nw.res[1]}) dev(p, ct);
-    dev(&nw.d_host, host);
-    dev(&nw.d_data, data);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&nw.h_res, ct * 2 + sizeof(int64_t), hipHostMallocMapped);   // int64, + the monitor's maximum
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&nw.d_h_res, nw.h_res, 0);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&nw.h_host, host, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&nw.h_data, data, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&nw.ev_host, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&nw.ev_data, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        public_bufs_free(nw);
-        (void)hipGetLastError();   // the next op's error check must not see this allocation's failure
-        return fail(c, FHERAM_ERR_DEVICE, std::string("buffers of the bank's public side: ") + hipGetErrorString(e));
-    }
+    dev(&nw.host.d, host);
+    dev(&nw.data.d, data);
+    if (e == hipSuccess) e = pinned_result(&nw.h_res, &nw.d_h_res, ct);
+    if (e == hipSuccess) e = nw.host.pin(host);
+    if (e == hipSuccess) e = nw.data.pin(data);
+    if (e == hipSuccess) e = nw.host.event();
+    if (e == hipSuccess) e = nw.data.event();
+    if (e != hipSuccess) { public_bufs_free(nw); return reserve_failed(c, e, "buffers of the bank's public side"); }
     b->pub = nw;
     return FHERAM_OK;
 }
@@ -113,21 +108,22 @@ int pub_load_rows(fheram_bank* b, int32_t* rows, long w_stride, int n_rows, size
     fheram_ctx* c = b->c;
     PublicBufs& P = b->pub;
     const size_t row_bytes = (size_t)N * b->mws, have = n_words * (size_t)b->mws, all = (size_t)n_rows * row_bytes;
-    if (P.data_busy) { HIPCHK(c, hipEventSynchronize(P.ev_data)); P.data_busy = false; }   // the last call's copy out of the pinned buffer; no other host wait
+    int rc = stage_wait(c, P.data);
+    if (rc != FHERAM_OK) return rc;
     for (size_t o = 0; o < all; o += row_bytes) {
         const size_t n = o < have ? std::min(row_bytes, have - o) : 0;
-        if (n) std::memcpy(P.h_data + o, data + o, n);
-        if (n < row_bytes) std::memset(P.h_data + o + n, 0, row_bytes - n);
+        if (n) std::memcpy(P.data.h + o, data + o, n);
+        if (n < row_bytes) std::memset(P.data.h + o + n, 0, row_bytes - n);
     }
     // ---- enqueue ----
     main_enqueued(c);
     c->cur = c->stream;
-    HIPCHK(c, hipMemcpyAsync(P.d_data, P.h_data, all, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(P.ev_data, c->stream));
-    P.data_busy = true;
+    HIPCHK(c, hipMemcpyAsync(P.data.d, P.data.h, all, hipMemcpyHostToDevice, c->stream));
+    rc = stage_record(c, P.data);
+    if (rc != FHERAM_OK) return rc;
     {
         const int k_pt = (int)c->p.k_glwe_pt;
-        const RowsPlainArgs ra{P.d_data, rows, w_stride, b->mws, (long)n_words, k_pt, (k_pt + BASE2K - 1) / BASE2K};
+        const RowsPlainArgs ra{P.data.d, rows, w_stride, b->mws, (long)n_words, k_pt, (k_pt + BASE2K - 1) / BASE2K};
         ProfScope ps(c, "elementwise", (uint64_t)n_rows * b->mws);
         rows_plain_launch(n_rows, c->cur, ra);
     }
@@ -181,7 +177,11 @@ int32_t* pub_peek_enqueue(fheram_bank* b, const int* members, const uint64_t* ad
     trace_steps(c, ref(P.fan, G, 0), ref(res, G, 0), ref(P.tmp, G, 0), 0, LOGN, 1, Y);   // ram.rs:457
     return res;
 }
-void pub_peek_done(fheram_bank* b, int n) { b->pub.cur ^= 1; b->peek_n = n; }
+void pub_peek_done(fheram_bank* b, int n) {
+    PublicBufs& P = b->pub;
+    P.cur ^= 1;
+    b->last[LAST_PEEK] = LastOutputs{n, ResHome{P.res[P.cur], P.h_res, P.d_h_res, -1}};
+}
 
 }  // namespace
 
@@ -262,16 +262,7 @@ int fheram_bank_selftest_fail_public_alloc(fheram_bank* b, int nth) {
     return FHERAM_OK;
 }
 int fheram_bank_peek_result(fheram_bank* b, int first, int n, int64_t* out) {
-    if (!b) return FHERAM_ERR_INVALID_ARG;
-    fheram_ctx* c = b->c;
-    if (!out) return fail(c, FHERAM_ERR_INVALID_ARG, "null output");
-    if (!b->peek_n) return fail(c, FHERAM_ERR_STATE, "no fheram_bank_peek or fheram_bank_poke has run on this bank");
-    if (first < 0 || n < 1 || first > b->peek_n - n)
-        return fail(c, FHERAM_ERR_INVALID_ARG, "outputs [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") are empty or outside the last peek's " + std::to_string(b->peek_n) + " outputs");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
-    const ResRun run{b->pub.res[b->pub.cur] + (size_t)first * per, (size_t)n * per};
-    return result_export(c, &run, 1, b->pub.h_res, b->pub.d_h_res, out);
+    return b ? last_result(b, LAST_PEEK, first, n, out) : FHERAM_ERR_INVALID_ARG;
 }
 int fheram_bank_poke(fheram_bank* b, const int* members, const uint64_t* addrs, int n, const fheram_select_src* srcs, const int64_t* host_words) {
     if (!b) return FHERAM_ERR_INVALID_ARG;
@@ -285,56 +276,24 @@ int fheram_bank_poke(fheram_bank* b, const int* members, const uint64_t* addrs, 
         for (int j = 0; j < k; j++)
             if (members[j] == members[k] && addrs[j] == addrs[k])
                 return fail(c, FHERAM_ERR_INVALID_ARG, "entry " + std::to_string(k) + " names address " + std::to_string(addrs[k]) + " of member " + std::to_string(members[k]) + " a second time: the targets of a poke are distinct");
-    // the sources, as fheram_bank_regs_write checks its own (regs.hpp regs_check_sources), with the public side's PUB_MAX host slots
     int n_host = 0;
-    {
-        SelectNeeds need;
-        for (int k = 0; k < n; k++) {
-            const std::string who = "source " + std::to_string(k);
-            rc = select_check_source(b, srcs[k].kind, srcs[k].index, who, host_words, need);
-            if (rc != FHERAM_OK) return rc;
-            if (srcs[k].kind != FHERAM_SRC_HOST) continue;
-            if (srcs[k].index >= PUB_MAX)
-                return fail(c, FHERAM_ERR_INVALID_ARG, who + " names host slot " + std::to_string(srcs[k].index) + ", outside the [0, " + std::to_string(PUB_MAX) + ") a poke takes");
-            n_host = std::max(n_host, srcs[k].index + 1);
-        }
-        rc = select_check_state(b, need, true);
-        if (rc != FHERAM_OK) return rc;
-        for (int k = 0; k < n; k++)
-            if (srcs[k].kind == FHERAM_SRC_MEMBER_RESULT && !b->has_res[srcs[k].index])
-                return fail(c, FHERAM_ERR_STATE, "source " + std::to_string(k) + " names the result of member " + std::to_string(srcs[k].index) + ", which has none yet");
-    }
+    rc = sources_check(b, srcs, n, host_words, PUB_MAX, "a poke takes", true, &n_host);   // the public side stages PUB_MAX host slots
+    if (rc != FHERAM_OK) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     rc = pub_reserve(b);
     if (rc != FHERAM_OK) return rc;
     PublicBufs& P = b->pub;
     const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
-    if (n_host) {   // the host slots the sources name: range-checked into the pinned buffer (a refusal comes before anything is enqueued)
-        if (P.host_busy) { HIPCHK(c, hipEventSynchronize(P.ev_host)); P.host_busy = false; }
-        bool staged[PUB_MAX] = {};
-        for (int k = 0; k < n; k++) {
-            if (srcs[k].kind != FHERAM_SRC_HOST || staged[srcs[k].index]) continue;
-            staged[srcs[k].index] = true;
-            if (!narrow(host_words + (size_t)srcs[k].index * per, P.h_host + (size_t)srcs[k].index * per, per))
-                return fail(c, FHERAM_ERR_RANGE, "limb out of the normalised range [-2^16, 2^16]");
-        }
-    }
+    rc = host_words_stage(b, P.host, srcs, n, n_host, host_words);
+    if (rc != FHERAM_OK) return rc;
     // ---- enqueue ----
     regs_begin(c);
-    if (n_host) {
-        bool copied[PUB_MAX] = {};
-        for (int k = 0; k < n; k++) {
-            if (srcs[k].kind != FHERAM_SRC_HOST || copied[srcs[k].index]) continue;
-            copied[srcs[k].index] = true;
-            HIPCHK(c, hipMemcpyAsync(P.d_host + (size_t)srcs[k].index * per, P.h_host + (size_t)srcs[k].index * per, per * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        }
-        HIPCHK(c, hipEventRecord(P.ev_host, c->stream));
-        P.host_busy = true;
-    }
+    rc = host_words_copy(b, P.host, srcs, n, n_host);
+    if (rc != FHERAM_OK) return rc;
     PokeMergeArgs ma{};
     // the words, where they sit NOW: a PEEK_RESULT source names the outputs this call's own peek is about to succeed
     const int32_t* words[PUB_MAX];
-    for (int k = 0; k < n; k++) words[k] = select_source(b, srcs[k], P.d_host);
+    for (int k = 0; k < n; k++) words[k] = select_source(b, srcs[k], P.host.dev<int32_t>());
     const int32_t* t = pub_peek_enqueue(b, members, addrs, n);
     // the touched rows, each with its entries side by side
     int n_touched = 0, n_ent = 0;

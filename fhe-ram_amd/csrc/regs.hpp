@@ -13,7 +13,7 @@
 //                       inverse digits (coordinate_prepare_inv on its digits), the products with them in place (ram.rs:644-646)
 // Everything runs on the bank's main stream.  A register file owns its device buffers (the row, the kept trace, two temporaries, its
 // prepared digits, its inverse digits), all allocated by fheram_bank_regs_create; what the register files of a bank share (path.hpp
-// RegsBufs) is allocated by the bank's first create.  No operation allocates.  No member's rows, state flag, tree, result or kept memo is
+// OneRowSet) is allocated by the bank's first create.  No operation allocates.  No member's rows, state flag, tree, result or kept memo is
 // touched, nor the last read list's or the last select's results.
 //
 // This file has two parts: what regs.hip (the kernels' translation unit) and fheram.hip share — the argument structs and the launchers —
@@ -74,31 +74,11 @@ void regs_keys_changed(fheram_bank* b) {
 void regs_bank_release(fheram_bank* b) {
     for (fheram_regs* r : b->regfiles) { regs_free_device(r); r->bank = nullptr; r->initialized = false; }
     b->regfiles.clear();
-    regs_bufs_free(b->regs);
+    one_row_free(b->regs);
 }
-// what the register files of a bank share, whole (path.hpp RegsBufs)
+// what the register files of a bank share, whole (path.hpp OneRowSet): the stage holds the 2^FHERAM_SELECT_BITS_MAX host words of a pack or a write
 int regs_bufs_reserve(fheram_bank* b) {
-    fheram_ctx* c = b->c;
-    if (b->regs.cap) return FHERAM_OK;
-    RegsBufs nw;
-    nw.cap = std::min(FHERAM_SELECT_MAX * b->mws, REGS_CT_MAX);
-    const size_t ct = (size_t)nw.cap * fheram_ctx::GLWE * sizeof(int32_t);
-    const size_t host = (size_t)(1 << FHERAM_SELECT_BITS_MAX) * b->mws * fheram_ctx::GLWE * sizeof(int32_t);
-    hipError_t e = hipSuccess;
-    for (int32_t** p : {&nw.fan, &nw.ep, &nw.tmp, &nw.res}) if (e == hipSuccess) e = hipMalloc((void**)p, ct);
-    if (e == hipSuccess) e = hipMalloc((void**)&nw.prep, (size_t)FHERAM_SELECT_MAX * FHERAM_SELECT_BITS_MAX * fheram_ctx::GGSW * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&nw.d_host, host);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&nw.h_res, ct * 2 + sizeof(int64_t), hipHostMallocMapped);   // int64, + the monitor's maximum
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&nw.d_h_res, nw.h_res, 0);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&nw.h_host, host, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&nw.ev_host, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        regs_bufs_free(nw);
-        (void)hipGetLastError();   // the next op's error check must not see this allocation's failure
-        return fail(c, FHERAM_ERR_DEVICE, std::string("buffers of the bank's register files: ") + hipGetErrorString(e));
-    }
-    b->regs = nw;
-    return FHERAM_OK;
+    return one_row_reserve(b->c, b->regs, b->mws, FHERAM_SELECT_BITS_MAX, (size_t)(1 << FHERAM_SELECT_BITS_MAX) * b->mws * fheram_ctx::GLWE * sizeof(int32_t), "buffers of the bank's register files");
 }
 // the handle: null, of another bank (or of a destroyed one)
 int regs_check_handle(fheram_bank* b, const fheram_regs* r) {
@@ -107,10 +87,9 @@ int regs_check_handle(fheram_bank* b, const fheram_regs* r) {
 }
 // a selector as the address of register file r
 int regs_check_selector(fheram_bank* b, const fheram_regs* r, const fheram_selector* s, const std::string& who) {
-    fheram_ctx* c = b->c;
-    if (!s || s->bank != b) return fail(c, FHERAM_ERR_INVALID_ARG, who + " is null or belongs to another bank");
-    if (s->empty) return fail(c, FHERAM_ERR_INVALID_ARG, who + " is empty: fheram_bank_selector_alloc without fheram_bank_selector_derive");
-    if (s->bits != r->bits) return fail(c, FHERAM_ERR_INVALID_ARG, who + " has " + std::to_string(s->bits) + " bits, the register file " + std::to_string(r->bits));
+    const int rc = selector_check(b, s, who);
+    if (rc != FHERAM_OK) return rc;
+    if (s->bits != r->bits) return fail(b->c, FHERAM_ERR_INVALID_ARG, who + " has " + std::to_string(s->bits) + " bits, the register file " + std::to_string(r->bits));
     return FHERAM_OK;
 }
 // initialised, the keys, the wanted state (0: read / read_prepare_write, 1: write)
@@ -124,58 +103,35 @@ int regs_check_ready(fheram_bank* b, const fheram_regs* r, int want_state) {
         return fail(c, FHERAM_ERR_STATE, "invalid call to Memory.write: internal state is false -> requires calling Memory.read_prepare_write (register file)");
     return FHERAM_OK;
 }
-// The sources of a pack or a write, as fheram_bank_select checks its own: kind and index, what a kind needs to have run, a member's result.
-// A host slot is one of the 2^FHERAM_SELECT_BITS_MAX the register files stage.  n_host: slots [0, n_host) cover every slot named.
+// The sources of a pack or a write (select.hpp sources_check): a host slot is one of the 2^FHERAM_SELECT_BITS_MAX the register files stage
 int regs_check_sources(fheram_bank* b, const fheram_select_src* srcs, int n, const int64_t* host_words, bool keys, int* n_host) {
-    fheram_ctx* c = b->c;
-    SelectNeeds need;
-    *n_host = 0;
-    for (int i = 0; i < n; i++) {
-        const std::string who = "source " + std::to_string(i);
-        const int rc = select_check_source(b, srcs[i].kind, srcs[i].index, who, host_words, need);
+    return sources_check(b, srcs, n, host_words, 1 << FHERAM_SELECT_BITS_MAX, "a register file takes", keys, n_host);
+}
+// n reads of register file r as one operation, behind the handle and the list: every selector, then the state.  who: what a selector is
+// called ("selector ", the mix's "register selector "); digits_tail: why two selectors may not differ in digits, in the caller's words
+int regs_check_reads(fheram_bank* b, const fheram_regs* r, const fheram_selector* const* sels, int n, const std::string& who, const char* digits_tail) {
+    for (int k = 0; k < n; k++) {
+        const int rc = regs_check_selector(b, r, sels[k], who + std::to_string(k));
         if (rc != FHERAM_OK) return rc;
-        if (srcs[i].kind != FHERAM_SRC_HOST) continue;
-        if (srcs[i].index >= (1 << FHERAM_SELECT_BITS_MAX))
-            return fail(c, FHERAM_ERR_INVALID_ARG, who + " names host slot " + std::to_string(srcs[i].index) + ", outside the [0, " + std::to_string(1 << FHERAM_SELECT_BITS_MAX) + ") a register file takes");
-        *n_host = std::max(*n_host, srcs[i].index + 1);
+        if (sels[k]->n_digits != sels[0]->n_digits)   // (field selectors: the same bits in another number of digits)
+            return fail(b->c, FHERAM_ERR_INVALID_ARG, who + std::to_string(k) + " has " + std::to_string(sels[k]->n_digits) + " digits, " + who + "0 " + std::to_string(sels[0]->n_digits) + ": " + digits_tail);
     }
-    const int rc = select_check_state(b, need, keys);
-    if (rc != FHERAM_OK) return rc;
-    for (int i = 0; i < n; i++)
-        if (srcs[i].kind == FHERAM_SRC_MEMBER_RESULT && !b->has_res[srcs[i].index])
-            return fail(c, FHERAM_ERR_STATE, "source " + std::to_string(i) + " names the result of member " + std::to_string(srcs[i].index) + ", which has none yet");
-    return FHERAM_OK;
+    return regs_check_ready(b, r, 0);
 }
-// the host slots the sources name: range-checked into the pinned buffer (a refusal comes before anything is enqueued) ...
-int regs_stage_host(fheram_bank* b, const fheram_select_src* srcs, int n, int n_host, const int64_t* host_words) {
+// one row up or down: a register file's, a table's (table.hpp)
+int row_upload(fheram_bank* b, int32_t* dst, const int64_t* row) {
     fheram_ctx* c = b->c;
-    RegsBufs& R = b->regs;
-    if (!n_host) return FHERAM_OK;
-    const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
-    if (R.host_busy) { HIPCHK(c, hipEventSynchronize(R.ev_host)); R.host_busy = false; }
-    std::vector<char> staged((size_t)n_host, 0);
-    for (int i = 0; i < n; i++) {
-        if (srcs[i].kind != FHERAM_SRC_HOST || staged[(size_t)srcs[i].index]) continue;
-        staged[(size_t)srcs[i].index] = 1;
-        if (!narrow(host_words + (size_t)srcs[i].index * per, R.h_host + (size_t)srcs[i].index * per, per))
-            return fail(c, FHERAM_ERR_RANGE, "limb out of the normalised range [-2^16, 2^16]");
-    }
-    return FHERAM_OK;
+    if (!row) return fail(c, FHERAM_ERR_INVALID_ARG, "null row");
+    HIPCHK(c, hipSetDevice(c->device));
+    return upload_i64(c, dst, row, (size_t)b->mws * fheram_ctx::GLWE);
 }
-// ... and copied to the device on the bank's stream
-int regs_copy_host(fheram_bank* b, const fheram_select_src* srcs, int n, int n_host) {
+int row_download(fheram_bank* b, const int32_t* src, bool initialized, const char* uninitialized, int64_t* row) {
     fheram_ctx* c = b->c;
-    RegsBufs& R = b->regs;
-    if (!n_host) return FHERAM_OK;
-    const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
-    for (int sl = 0; sl < n_host; sl++) {
-        bool used = false;
-        for (int i = 0; i < n && !used; i++) used = srcs[i].kind == FHERAM_SRC_HOST && srcs[i].index == sl;
-        if (used) HIPCHK(c, hipMemcpyAsync(R.d_host + (size_t)sl * per, R.h_host + (size_t)sl * per, per * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    }
-    HIPCHK(c, hipEventRecord(R.ev_host, c->stream));
-    R.host_busy = true;
-    return FHERAM_OK;
+    if (!row) return fail(c, FHERAM_ERR_INVALID_ARG, "null row");
+    if (!initialized) return fail(c, FHERAM_ERR_UNINITIALIZED, uninitialized);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int rc = download_i64(c, row, src, (size_t)b->mws * fheram_ctx::GLWE);
+    return rc == FHERAM_OK ? check_precision(c) : rc;
 }
 void regs_begin(fheram_ctx* c) {
     main_enqueued(c);
@@ -231,26 +187,16 @@ int fheram_bank_regs_state(const fheram_bank* b, const fheram_regs* r) { return 
 
 int fheram_bank_regs_upload(fheram_bank* b, fheram_regs* r, const int64_t* row) {
     if (!b) return FHERAM_ERR_INVALID_ARG;
-    fheram_ctx* c = b->c;
     int rc = regs_check_handle(b, r);
-    if (rc != FHERAM_OK) return rc;
-    if (!row) return fail(c, FHERAM_ERR_INVALID_ARG, "null row");
-    HIPCHK(c, hipSetDevice(c->device));
-    rc = upload_i64(c, r->row, row, (size_t)b->mws * fheram_ctx::GLWE);
+    if (rc == FHERAM_OK) rc = row_upload(b, r->row, row);
     if (rc != FHERAM_OK) return rc;
     r->initialized = true; r->state = false; r->memo = false;
     return FHERAM_OK;
 }
 int fheram_bank_regs_download(fheram_bank* b, const fheram_regs* r, int64_t* row) {
     if (!b) return FHERAM_ERR_INVALID_ARG;
-    fheram_ctx* c = b->c;
-    int rc = regs_check_handle(b, r);
-    if (rc != FHERAM_OK) return rc;
-    if (!row) return fail(c, FHERAM_ERR_INVALID_ARG, "null row");
-    if (!r->initialized) return fail(c, FHERAM_ERR_UNINITIALIZED, "unitialized memory: the register file has had no fheram_bank_regs_upload or fheram_bank_regs_pack");
-    HIPCHK(c, hipSetDevice(c->device));
-    rc = download_i64(c, row, r->row, (size_t)b->mws * fheram_ctx::GLWE);
-    return rc == FHERAM_OK ? check_precision(c) : rc;
+    const int rc = regs_check_handle(b, r);
+    return rc == FHERAM_OK ? row_download(b, r->row, r->initialized, "unitialized memory: the register file has had no fheram_bank_regs_upload or fheram_bank_regs_pack", row) : rc;
 }
 // row <- glwe_normalize(sum_j X^j * c_j[w]): the pack of fheram_bank_select (k_select_pack, one launch) into the register file
 int fheram_bank_regs_pack(fheram_bank* b, fheram_regs* r, int n_cand, const fheram_select_src* srcs, const int64_t* host_words) {
@@ -269,16 +215,16 @@ int fheram_bank_regs_pack(fheram_bank* b, fheram_regs* r, int n_cand, const fher
     if (r->initialized && r->state)
         return fail(c, FHERAM_ERR_STATE, "the register file is between read_prepare_write and write: a pack would drop the pending write (fheram_bank_regs_upload resets)");
     HIPCHK(c, hipSetDevice(c->device));
-    rc = regs_stage_host(b, srcs, n_cand, n_host, host_words);
+    rc = host_words_stage(b, b->regs.stage, srcs, n_cand, n_host, host_words);
     if (rc != FHERAM_OK) return rc;
     // ---- enqueue ----
     regs_begin(c);
-    rc = regs_copy_host(b, srcs, n_cand, n_host);
+    rc = host_words_copy(b, b->regs.stage, srcs, n_cand, n_host);
     if (rc != FHERAM_OK) return rc;
     {
         SelectPackArgs sa{};
         sa.out = r->row; sa.ws = b->mws; sa.m[0] = n_cand;
-        for (int j = 0; j < n_cand; j++) sa.cand[0][j] = select_source(b, srcs[j], b->regs.d_host);
+        for (int j = 0; j < n_cand; j++) sa.cand[0][j] = select_source(b, srcs[j], b->regs.stage.dev<int32_t>());
         ProfScope ps(c, "select_pack", (uint64_t)b->mws);
         select_pack_launch(dim3(1, b->mws, EW_SLICES), c->cur, sa);
     }
@@ -300,19 +246,13 @@ int fheram_bank_regs_read(fheram_bank* b, const fheram_regs* r, const fheram_sel
     const int ws = b->mws, Y = n * ws;
     if (Y > REGS_CT_MAX)
         return fail(c, FHERAM_ERR_INVALID_ARG, "n * word_size = " + std::to_string(Y) + " exceeds 64, the ciphertext limit of the single-launch chains (k_chain_mid)");
-    for (int k = 0; k < n; k++) {
-        rc = regs_check_selector(b, r, sels[k], "selector " + std::to_string(k));
-        if (rc != FHERAM_OK) return rc;
-        if (sels[k]->n_digits != sels[0]->n_digits)   // (field selectors: the same bits in another number of digits)
-            return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " has " + std::to_string(sels[k]->n_digits) + " digits, selector 0 " + std::to_string(sels[0]->n_digits) + ": the operand table of one call has one stride");
-    }
-    rc = regs_check_ready(b, r, 0);
+    rc = regs_check_reads(b, r, sels, n, "selector ", "the operand table of one call has one stride");
     if (rc != FHERAM_OK) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     // ---- enqueue ----
-    RegsBufs& R = b->regs;
+    OneRowSet& R = b->regs;
     regs_begin(c);
-    b->regs_n = 0;   // until this read is enqueued there is no last register read
+    b->last[LAST_REGS].n = 0;   // until this read is enqueued there is no last register read
     {
         RegsFanArgs fa{r->row, R.fan, ws};
         ProfScope ps(c, "elementwise", (uint64_t)Y);
@@ -320,23 +260,13 @@ int fheram_bank_regs_read(fheram_bank* b, const fheram_regs* r, const fheram_sel
     }
     one_row_reads(b, OneRowBufs{R.fan, R.ep, R.tmp, R.res, R.prep}, sels, n);
     HIPCHK(c, hipGetLastError());
-    b->regs_n = n;
-    b->regs_home = ResHome{R.res, R.h_res, R.d_h_res, -1};
+    b->last[LAST_REGS] = LastOutputs{n, ResHome{R.res, R.h_res, R.d_h_res, -1}};
     if (!out) return FHERAM_OK;
     const ResRun run{R.res, (size_t)Y * fheram_ctx::GLWE};
     return result_export(c, &run, 1, R.h_res, R.d_h_res, out);
 }
 int fheram_bank_regs_result(fheram_bank* b, int first, int n, int64_t* out) {
-    if (!b) return FHERAM_ERR_INVALID_ARG;
-    fheram_ctx* c = b->c;
-    if (!out) return fail(c, FHERAM_ERR_INVALID_ARG, "null output");
-    if (!b->regs_n) return fail(c, FHERAM_ERR_STATE, "no fheram_bank_regs_read has run on this bank");
-    if (first < 0 || n < 1 || first > b->regs_n - n)
-        return fail(c, FHERAM_ERR_INVALID_ARG, "outputs [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") are empty or outside the last register read's " + std::to_string(b->regs_n) + " outputs");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
-    const ResRun run{b->regs_home.res + (size_t)first * per, (size_t)n * per};
-    return result_export(c, &run, 1, b->regs_home.h, b->regs_home.d_h, out);
+    return b ? last_result(b, LAST_REGS, first, n, out) : FHERAM_ERR_INVALID_ARG;
 }
 // Ram::read_prepare_write (ram.rs:196-222) of the one-row RAM (header comment)
 int fheram_bank_regs_read_prepare_write(fheram_bank* b, fheram_regs* r, const fheram_selector* sel, int64_t* out) {
@@ -388,11 +318,11 @@ int fheram_bank_regs_write(fheram_bank* b, fheram_regs* r, const fheram_selector
     if (rc == FHERAM_OK) rc = regs_check_ready(b, r, 1);
     if (rc != FHERAM_OK) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    rc = regs_stage_host(b, &src, 1, n_host, host_words);   // a refused word: the register file stays prepared and untouched
+    rc = host_words_stage(b, b->regs.stage, &src, 1, n_host, host_words);   // a refused word: the register file stays prepared and untouched
     if (rc != FHERAM_OK) return rc;
     // ---- enqueue ----
     regs_begin(c);
-    rc = regs_copy_host(b, &src, 1, n_host);
+    rc = host_words_copy(b, b->regs.stage, &src, 1, n_host);
     if (rc != FHERAM_OK) return rc;
     const int ws = b->mws, d = sel->n_digits;
     const long G = (long)fheram_ctx::GLWE;
@@ -402,7 +332,7 @@ int fheram_bank_regs_write(fheram_bank* b, fheram_regs* r, const fheram_selector
     {   // write_first_step (ram.rs:544-577): row <- normalize(row - trace(row) + w)
         RegsMergeArgs ma{};
         ma.row = r->row; ma.tr = tr;
-        const int32_t* w = select_source(b, src, b->regs.d_host);
+        const int32_t* w = select_source(b, src, b->regs.stage.dev<int32_t>());
         for (int i = 0; i < ws; i++) ma.src[i] = w ? w + (size_t)i * G : nullptr;
         ProfScope ps(c, "elementwise", (uint64_t)ws);
         regs_merge_launch(ws, c->cur, ma);

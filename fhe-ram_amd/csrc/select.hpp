@@ -43,7 +43,23 @@ static_assert(FHERAM_SELECT_FIELDS_MAX == FHERAM_SELECT_BITS_MAX, "a field has a
 static_assert(FHERAM_SELECTOR_WIDE_DIGITS_MAX == FHERAM_SELECT_BITS_MAX && FHERAM_SELECTOR_WIDE_DIGITS_MAX == FHERAM_SELECT_FIELDS_MAX, "a selector's plan arrays hold FHERAM_SELECTOR_WIDE_DIGITS_MAX digits, a wide selector's too");
 static_assert(FHERAM_TABLE_BITS_MAX == LOGN && FHERAM_SELECTOR_WIDE_DIGITS_MAX <= DERIVE_DIGITS_MAX, "a row holds N words; a wide selector's derivation is one k_cmux_chain launch");
 
-// the selector of `bits` bits with its plan and its device buffer, no digits yet.  bits_max: FHERAM_SELECT_BITS_MAX, or FHERAM_TABLE_BITS_MAX
+// what both forms of a new selector end in: the handle with its plan — digit d has widths[d] bits at bit offset sum(widths[0..d)); one
+// coordinate: bit_lsh and bit_rsh advance together — and its device buffer, no digits yet
+int selector_alloc(fheram_bank* b, int bits, const int* widths, int n_digits, bool fields, fheram_selector** out) {
+    fheram_ctx* c = b->c;
+    HIPCHK(c, hipSetDevice(c->device));
+    fheram_selector* s = new fheram_selector{b, c->device, bits, n_digits, nullptr, {}, {}, {}, true, fields};
+    unsigned at = 0;
+    for (int d = 0; d < n_digits; d++) {
+        s->rsh[d] = s->lsh[d] = (unsigned char)at; s->width[d] = (unsigned char)widths[d];
+        at += (unsigned)widths[d];
+    }
+    const hipError_t e = hipMalloc(&s->d_ggsw, (size_t)n_digits * fheram_ctx::GGSW * sizeof(int32_t));
+    if (e != hipSuccess) { delete s; return reserve_failed(c, e, "hipMalloc"); }
+    *out = s;
+    return FHERAM_OK;
+}
+// the selector of `bits` bits, its plan the bank's DECOMP_N's.  bits_max: FHERAM_SELECT_BITS_MAX, or FHERAM_TABLE_BITS_MAX
 // for a WIDE selector (table.hpp: the address of a table), whose plan may then be longer than the plan arrays
 int selector_new(fheram_bank* b, int bits, fheram_selector** out, int bits_max = FHERAM_SELECT_BITS_MAX, const char* max_name = "FHERAM_SELECT_BITS_MAX") {
     fheram_ctx* c = b->c;
@@ -54,17 +70,7 @@ int selector_new(fheram_bank* b, int bits, fheram_selector** out, int bits_max =
         return fail(c, FHERAM_ERR_UNSUPPORTED, "the bank's DECOMP_N gives a selector of " + std::to_string(bits) + " bits " + std::to_string(plan.size()) + " coordinates; a select is a read of a one-row RAM of one coordinate");
     if ((int)plan[0].size() > FHERAM_SELECTOR_WIDE_DIGITS_MAX)
         return fail(c, FHERAM_ERR_UNSUPPORTED, "the bank's DECOMP_N gives a selector of " + std::to_string(bits) + " bits " + std::to_string(plan[0].size()) + " digits, more than FHERAM_SELECTOR_WIDE_DIGITS_MAX = " + std::to_string(FHERAM_SELECTOR_WIDE_DIGITS_MAX));
-    HIPCHK(c, hipSetDevice(c->device));
-    fheram_selector* s = new fheram_selector{b, c->device, bits, (int)plan[0].size(), nullptr, {}, {}, {}, true, false};
-    unsigned at = 0;
-    for (int d = 0; d < s->n_digits; d++) {   // one coordinate: bit_lsh and bit_rsh advance together
-        s->rsh[d] = s->lsh[d] = (unsigned char)at; s->width[d] = (unsigned char)plan[0][d];
-        at += (unsigned)plan[0][d];
-    }
-    const hipError_t e = hipMalloc(&s->d_ggsw, (size_t)s->n_digits * fheram_ctx::GGSW * sizeof(int32_t));
-    if (e != hipSuccess) { delete s; (void)hipGetLastError(); return fail(c, FHERAM_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e)); }
-    *out = s;
-    return FHERAM_OK;
+    return selector_alloc(b, bits, plan[0].data(), (int)plan[0].size(), false, out);
 }
 
 // The selector whose digit d has widths[d] bits at bit offset sum(widths[0..d)): the Address of a one-row RAM of max_addr = 2^bits whose DECOMP_N
@@ -81,16 +87,30 @@ int selector_new_fields(fheram_bank* b, const int* widths, int n_fields, fheram_
         if (bits > bits_max)
             return fail(c, FHERAM_ERR_INVALID_ARG, std::string("the widths sum to more than ") + max_name + " = " + std::to_string(bits_max) + " bits");
     }
-    HIPCHK(c, hipSetDevice(c->device));
-    fheram_selector* s = new fheram_selector{b, c->device, bits, n_fields, nullptr, {}, {}, {}, true, true};
-    unsigned at = 0;
-    for (int d = 0; d < n_fields; d++) {
-        s->rsh[d] = s->lsh[d] = (unsigned char)at; s->width[d] = (unsigned char)widths[d];
-        at += (unsigned)widths[d];
-    }
-    const hipError_t e = hipMalloc(&s->d_ggsw, (size_t)n_fields * fheram_ctx::GGSW * sizeof(int32_t));
-    if (e != hipSuccess) { delete s; (void)hipGetLastError(); return fail(c, FHERAM_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+    return selector_alloc(b, bits, widths, n_fields, true, out);
+}
+// The second half of every _create entry point: the output and the digits there at all ...
+int selector_create_args(fheram_bank* b, const int64_t* const* ggsw, fheram_selector** out) {
+    if (!out) return fail(b->c, FHERAM_ERR_INVALID_ARG, "null output");
+    *out = nullptr;
+    if (!ggsw) return fail(b->c, FHERAM_ERR_INVALID_ARG, "null ggsw");
+    return FHERAM_OK;
+}
+// ... and the new selector s filled with them (wrong_count: what to say when there are not as many as its plan has); a failure destroys s
+int selector_fill(fheram_bank* b, fheram_selector* s, const int64_t* const* ggsw, int n_ggsw, const std::string& wrong_count, fheram_selector** out) {
+    fheram_ctx* c = b->c;
+    int rc = n_ggsw != s->n_digits ? fail(c, FHERAM_ERR_INVALID_ARG, wrong_count) : (int)FHERAM_OK;
+    for (int i = 0; i < n_ggsw && rc == FHERAM_OK; i++)
+        rc = ggsw[i] ? upload_i64(c, s->d_ggsw + (size_t)i * fheram_ctx::GGSW, ggsw[i], fheram_ctx::GGSW) : fail(c, FHERAM_ERR_INVALID_ARG, "null ggsw digit");
+    if (rc != FHERAM_OK) { fheram_selector_destroy(s); return rc; }
+    s->empty = false;
     *out = s;
+    return FHERAM_OK;
+}
+// a selector an operation takes: the bank's, and with digits (alloc_name: the entry point that made it empty)
+int selector_check(fheram_bank* b, const fheram_selector* s, const std::string& who, const char* alloc_name = "fheram_bank_selector_alloc") {
+    if (!s || s->bank != b) return fail(b->c, FHERAM_ERR_INVALID_ARG, who + " is null or belongs to another bank");
+    if (s->empty) return fail(b->c, FHERAM_ERR_INVALID_ARG, who + " is empty: " + alloc_name + " without fheram_bank_selector_derive");
     return FHERAM_OK;
 }
 
@@ -112,41 +132,40 @@ int select_reserve(fheram_bank* b, int n_ct, int n_prep, int n_host) {
     };
     for (int32_t** p : {&nw.packed, &nw.ep, &nw.tmp, &nw.tmp2, &nw.res}) dev(p, ct);
     dev(&nw.prep, (size_t)nw.prep_cap * fheram_ctx::GGSW * sizeof(double));
-    if (nw.host_cap) dev(&nw.d_host, (size_t)nw.host_cap * fheram_ctx::GLWE * sizeof(int32_t));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&nw.h_res, ct * 2 + sizeof(int64_t), hipHostMallocMapped);   // int64, + the monitor's maximum
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&nw.d_h_res, nw.h_res, 0);
-    if (e == hipSuccess && nw.host_cap) e = hipHostMalloc((void**)&nw.h_host, (size_t)nw.host_cap * fheram_ctx::GLWE * sizeof(int32_t), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&nw.ev_host, hipEventDisableTiming);
-    if (e == hipSuccess && b->sel_n) e = hipMemcpyAsync(nw.res, S.res, (size_t)b->sel_n * b->mws * fheram_ctx::GLWE * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream);
+    if (nw.host_cap) dev(&nw.host.d, (size_t)nw.host_cap * fheram_ctx::GLWE * sizeof(int32_t));
+    if (e == hipSuccess) e = pinned_result(&nw.h_res, &nw.d_h_res, ct);
+    if (e == hipSuccess && nw.host_cap) e = nw.host.pin((size_t)nw.host_cap * fheram_ctx::GLWE * sizeof(int32_t));
+    if (e == hipSuccess) e = nw.host.event();
+    LastOutputs& last = b->last[LAST_SELECT];
+    if (e == hipSuccess && last.n) e = hipMemcpyAsync(nw.res, S.res, (size_t)last.n * b->mws * fheram_ctx::GLWE * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess && S.cap) e = hipStreamSynchronize(c->stream);   // whatever still reads or writes the old set
-    if (e != hipSuccess) {
-        select_free(nw);
-        (void)hipGetLastError();   // the next op's error check must not see this allocation's failure
-        return fail(c, FHERAM_ERR_DEVICE, "buffers of a select of " + std::to_string(n_ct) + " ciphertexts: " + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) { select_free(nw); return reserve_failed(c, e, "buffers of a select of " + std::to_string(n_ct) + " ciphertexts"); }
     select_free(S);
     S = nw;
+    last.home = ResHome{S.res, S.h_res, S.d_h_res, -1};   // the last select's outputs have moved
     return FHERAM_OK;
 }
 
+// the kind of last outputs a source kind names (-1: none of them)
+int last_kind_of(int src_kind) {
+    for (int k = 0; k < LAST_KINDS; k++) if (LAST_TEXT[k].src == src_kind) return k;
+    return -1;
+}
 // where candidate (kind, index) sits on the device: ws GLWEs (nullptr: ZERO); d_host: the staged host words (a select's own; a register
-// file's pack and write stage theirs in the register files' buffer)
+// file's pack and write and a poke stage theirs in their own sets)
 const int32_t* select_source(const fheram_bank* b, const fheram_select_src& s, const int32_t* d_host) {
     const fheram_ctx* c = b->c;
     const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
+    const int last = last_kind_of(s.kind);
+    if (last >= 0) return b->last[last].home.res + (size_t)s.index * per;   // (the kind's own buffers, or the last mix's: path.hpp ResHome)
     switch (s.kind) {
     case FHERAM_SRC_HOST: return d_host + (size_t)s.index * per;
     case FHERAM_SRC_MEMBER_RESULT: return (b->ram[s.index].res_in_trtop ? c->d_trtop : c->d_res) + (size_t)s.index * per;   // (as set_result)
-    case FHERAM_SRC_LIST_RESULT: return b->list_home.res + (size_t)s.index * per;   // (the kind's own buffers, or the last mix's: path.hpp ResHome)
-    case FHERAM_SRC_SELECT_RESULT: return b->sel.res + (size_t)s.index * per;
-    case FHERAM_SRC_REGS_RESULT: return b->regs_home.res + (size_t)s.index * per;
     case FHERAM_SRC_REGS_OLD: return b->regs_old;
-    case FHERAM_SRC_TABLE_RESULT: return b->table_home.res + (size_t)s.index * per;
-    case FHERAM_SRC_PEEK_RESULT: return b->pub.res[b->pub.cur] + (size_t)s.index * per;
     default: return nullptr;
     }
 }
-const int32_t* select_source(const fheram_bank* b, const fheram_select_src& s) { return select_source(b, s, b->sel.d_host); }
+const int32_t* select_source(const fheram_bank* b, const fheram_select_src& s) { return select_source(b, s, b->sel.host.dev<int32_t>()); }
 
 // GLWE `lane` of that word: what one entry of k_select_pack_lanes' table points to
 const int32_t* select_source_lane(const fheram_bank* b, const fheram_select_lane& l) {
@@ -164,8 +183,8 @@ int select_check_sels(fheram_bank* b, const fheram_selector* const* sels, const 
         return fail(c, FHERAM_ERR_INVALID_ARG, "n * word_size = " + std::to_string(Y) + " exceeds 64, the ciphertext limit of the single-launch chains (k_chain_mid)");
     *total = 0;
     for (int k = 0; k < n; k++) {
-        if (!sels[k] || sels[k]->bank != b) return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " is null or belongs to another bank");
-        if (sels[k]->empty) return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " is empty: fheram_bank_selector_alloc without fheram_bank_selector_derive");
+        const int rc = selector_check(b, sels[k], "selector " + std::to_string(k));
+        if (rc != FHERAM_OK) return rc;
         if (sels[k]->bits > FHERAM_SELECT_BITS_MAX)   // a wide selector (table.hpp): the pack holds 2^FHERAM_SELECT_BITS_MAX candidates
             return fail(c, FHERAM_ERR_INVALID_ARG, "selector " + std::to_string(k) + " has " + std::to_string(sels[k]->bits) + " bits, more than FHERAM_SELECT_BITS_MAX = " + std::to_string(FHERAM_SELECT_BITS_MAX) + ": a wide selector addresses a table (fheram_bank_table_read)");
         if (sels[k]->bits != sels[0]->bits)
@@ -178,10 +197,18 @@ int select_check_sels(fheram_bank* b, const fheram_selector* const* sels, const 
     }
     return FHERAM_OK;
 }
-struct SelectNeeds { bool list = false, sel = false, regs = false, regs_old = false, table = false, peek = false; };
-// one (kind, index) of a source or a lane
-int select_check_source(fheram_bank* b, int kind, int index, const std::string& who, const int64_t* host_words, SelectNeeds& need) {
+// one (kind, index) of a source or a lane; need: bit k for the last outputs of kind k, bit LAST_KINDS for the last register read_prepare_write
+constexpr unsigned NEED_REGS_OLD = 1u << LAST_KINDS;
+int select_check_source(fheram_bank* b, int kind, int index, const std::string& who, const int64_t* host_words, unsigned& need) {
     fheram_ctx* c = b->c;
+    const int last = last_kind_of(kind);
+    if (last >= 0) {
+        const int n = b->last[last].n;
+        const LastKindText& t = LAST_TEXT[last];
+        if (index < 0 || (n && index >= n)) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names " + t.unit + " " + std::to_string(index) + ", outside the last " + t.last + "'s " + std::to_string(n) + " " + t.units);
+        need |= 1u << last;
+        return FHERAM_OK;
+    }
     switch (kind) {
     case FHERAM_SRC_ZERO: break;
     case FHERAM_SRC_HOST:
@@ -191,44 +218,76 @@ int select_check_source(fheram_bank* b, int kind, int index, const std::string& 
     case FHERAM_SRC_MEMBER_RESULT:
         if (index < 0 || index >= b->M) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names member " + std::to_string(index) + ", outside the bank's " + std::to_string(b->M) + " members");
         break;
-    case FHERAM_SRC_LIST_RESULT:
-        if (index < 0 || (b->list_n && index >= b->list_n)) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names entry " + std::to_string(index) + ", outside the last read list's " + std::to_string(b->list_n) + " entries");
-        need.list = true;
-        break;
-    case FHERAM_SRC_SELECT_RESULT:
-        if (index < 0 || (b->sel_n && index >= b->sel_n)) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names output " + std::to_string(index) + ", outside the last select's " + std::to_string(b->sel_n) + " outputs");
-        need.sel = true;
-        break;
-    case FHERAM_SRC_REGS_RESULT:
-        if (index < 0 || (b->regs_n && index >= b->regs_n)) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names output " + std::to_string(index) + ", outside the last register read's " + std::to_string(b->regs_n) + " outputs");
-        need.regs = true;
-        break;
     case FHERAM_SRC_REGS_OLD:
         if (index != 0) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names index " + std::to_string(index) + " of the last register read_prepare_write, which has one result: index 0");
-        need.regs_old = true;
-        break;
-    case FHERAM_SRC_TABLE_RESULT:
-        if (index < 0 || (b->table_n && index >= b->table_n)) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names output " + std::to_string(index) + ", outside the last table read's " + std::to_string(b->table_n) + " outputs");
-        need.table = true;
-        break;
-    case FHERAM_SRC_PEEK_RESULT:
-        if (index < 0 || (b->peek_n && index >= b->peek_n)) return fail(c, FHERAM_ERR_INVALID_ARG, who + " names output " + std::to_string(index) + ", outside the last peek's " + std::to_string(b->peek_n) + " outputs");
-        need.peek = true;
+        need |= NEED_REGS_OLD;
         break;
     default: return fail(c, FHERAM_ERR_INVALID_ARG, who + " has the unknown kind " + std::to_string(kind));
     }
     return FHERAM_OK;
 }
-int select_check_state(fheram_bank* b, const SelectNeeds& need, bool keys = true) {
+// the keys, and every kind a source named has run (in the order the kinds were added: list, select, regs, regs-old, table, peek)
+int select_check_state(fheram_bank* b, unsigned need, bool keys = true) {
     fheram_ctx* c = b->c;
     if (keys && !c->keys_loaded) return fail(c, FHERAM_ERR_KEYS, "evaluation keys not loaded");
-    if (need.list && !b->list_n) return fail(c, FHERAM_ERR_STATE, "a source names the last read list and no read list has run on this bank");
-    if (need.sel && !b->sel_n) return fail(c, FHERAM_ERR_STATE, "a source names the last select and no select has run on this bank");
-    if (need.regs && !b->regs_n) return fail(c, FHERAM_ERR_STATE, "a source names the last register read and no fheram_bank_regs_read has run on this bank");
-    if (need.regs_old && !b->regs_old) return fail(c, FHERAM_ERR_STATE, "a source names the last register read_prepare_write and none has run on this bank (or its register file is gone)");
-    if (need.table && !b->table_n) return fail(c, FHERAM_ERR_STATE, "a source names the last table read and no fheram_bank_table_read has run on this bank");
-    if (need.peek && !b->peek_n) return fail(c, FHERAM_ERR_STATE, "a source names the last peek and no fheram_bank_peek or fheram_bank_poke has run on this bank");
+    for (int k = 0; k < LAST_KINDS; k++) {
+        if (k == LAST_TABLE && (need & NEED_REGS_OLD) && !b->regs_old)
+            return fail(c, FHERAM_ERR_STATE, "a source names the last register read_prepare_write and none has run on this bank (or its register file is gone)");
+        if ((need >> k & 1u) && !b->last[k].n) return fail(c, FHERAM_ERR_STATE, std::string("a source names the last ") + LAST_TEXT[k].last + " and " + LAST_TEXT[k].none + " on this bank");
+    }
     return FHERAM_OK;
+}
+// The sources of a select, a register file's pack or write, a poke: kind and index of each, the caller's own limit on host slots
+// (slot_limit; 0: the select's, which select_check_source has applied), what a kind needs to have run, a member's result.
+// n_host: slots [0, n_host) cover every slot named.
+int sources_check(fheram_bank* b, const fheram_select_src* srcs, int n, const int64_t* host_words, int slot_limit, const char* limit_text, bool keys, int* n_host) {
+    fheram_ctx* c = b->c;
+    unsigned need = 0;
+    *n_host = 0;
+    for (int i = 0; i < n; i++) {
+        const std::string who = "source " + std::to_string(i);
+        const int rc = select_check_source(b, srcs[i].kind, srcs[i].index, who, host_words, need);
+        if (rc != FHERAM_OK) return rc;
+        if (srcs[i].kind != FHERAM_SRC_HOST) continue;
+        if (slot_limit && srcs[i].index >= slot_limit)
+            return fail(c, FHERAM_ERR_INVALID_ARG, who + " names host slot " + std::to_string(srcs[i].index) + ", outside the [0, " + std::to_string(slot_limit) + ") " + limit_text);
+        *n_host = std::max(*n_host, srcs[i].index + 1);
+    }
+    const int rc = select_check_state(b, need, keys);
+    if (rc != FHERAM_OK) return rc;
+    for (int i = 0; i < n; i++)
+        if (srcs[i].kind == FHERAM_SRC_MEMBER_RESULT && !b->has_res[srcs[i].index])
+            return fail(c, FHERAM_ERR_STATE, "source " + std::to_string(i) + " names the result of member " + std::to_string(srcs[i].index) + ", which has none yet");
+    return FHERAM_OK;
+}
+// the host slots the sources name, whole words: range-checked as write words are into the stage's pinned twin (a refusal comes before
+// anything is enqueued) ...
+int host_words_stage(fheram_bank* b, HostStage& st, const fheram_select_src* srcs, int n, int n_host, const int64_t* host_words) {
+    fheram_ctx* c = b->c;
+    if (!n_host) return FHERAM_OK;
+    const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
+    const int rc = stage_wait(c, st);
+    if (rc != FHERAM_OK) return rc;
+    std::vector<char> staged((size_t)n_host, 0);
+    for (int i = 0; i < n; i++) {
+        if (srcs[i].kind != FHERAM_SRC_HOST || staged[(size_t)srcs[i].index]) continue;
+        staged[(size_t)srcs[i].index] = 1;
+        if (!narrow(host_words + (size_t)srcs[i].index * per, st.host<int32_t>() + (size_t)srcs[i].index * per, per))
+            return fail(c, FHERAM_ERR_RANGE, "limb out of the normalised range [-2^16, 2^16]");
+    }
+    return FHERAM_OK;
+}
+// ... and copied to the device on the bank's stream, slot by slot
+int host_words_copy(fheram_bank* b, HostStage& st, const fheram_select_src* srcs, int n, int n_host) {
+    fheram_ctx* c = b->c;
+    if (!n_host) return FHERAM_OK;
+    const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
+    for (int sl = 0; sl < n_host; sl++) {
+        bool used = false;
+        for (int i = 0; i < n && !used; i++) used = srcs[i].kind == FHERAM_SRC_HOST && srcs[i].index == sl;
+        if (used) HIPCHK(c, hipMemcpyAsync(st.dev<int32_t>() + (size_t)sl * per, st.host<int32_t>() + (size_t)sl * per, per * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    return stage_record(c, st);
 }
 // n independent Ram::read of one-row RAMs as one operation, on the caller's buffers (S.packed holds the n * ws rows): the selectors' digits
 // prepared, the products, the trace.  A select's chain (its packed candidates) and a register file's read (the fanned-out row, regs.hpp).
@@ -262,7 +321,7 @@ int select_chain(fheram_bank* b, const fheram_selector* const* sels, int n, int6
     const int Y = n * b->mws;
     one_row_reads(b, OneRowBufs{S.packed, S.ep, S.tmp, S.res, S.prep}, sels, n);
     HIPCHK(c, hipGetLastError());
-    b->sel_n = n;
+    b->last[LAST_SELECT].n = n;   // (in S.res: select_reserve keeps the record's home)
     if (!out) return FHERAM_OK;
     const ResRun run{S.res, (size_t)Y * fheram_ctx::GLWE};
     return result_export(c, &run, 1, S.h_res, S.d_h_res, out);
@@ -272,19 +331,15 @@ int select_chain(fheram_bank* b, const fheram_selector* const* sels, int n, int6
 int lane_table_reserve(fheram_bank* b) {
     fheram_ctx* c = b->c;
     SelectLaneTable& L = b->lanes;
-    if (L.d_tab) return FHERAM_OK;
+    if (L.d) return FHERAM_OK;
     SelectLaneTable nw;
     const size_t bytes = (size_t)SELECT_LANES_CT_MAX * SELECT_CAND_MAX * sizeof(const int32_t*);
     hipError_t e;
     if (b->sel_fail_alloc > 0 && --b->sel_fail_alloc == 0) e = hipErrorOutOfMemory;
-    else e = hipMalloc((void**)&nw.d_tab, bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&nw.h_tab, bytes, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&nw.ev, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        lane_table_free(nw);
-        (void)hipGetLastError();
-        return fail(c, FHERAM_ERR_DEVICE, std::string("pointer table of a lanes select: ") + hipGetErrorString(e));
-    }
+    else e = hipMalloc((void**)&nw.d, bytes);
+    if (e == hipSuccess) e = nw.pin(bytes);
+    if (e == hipSuccess) e = nw.event();
+    if (e != hipSuccess) { lane_table_free(nw); return reserve_failed(c, e, "pointer table of a lanes select"); }
     L = nw;
     return FHERAM_OK;
 }
@@ -301,20 +356,11 @@ int fheram_bank_selector_alloc(fheram_bank* b, int bits, fheram_selector** out) 
 }
 int fheram_bank_selector_create(fheram_bank* b, const int64_t* const* ggsw, int n_ggsw, int bits, fheram_selector** out) {
     if (!b) return FHERAM_ERR_INVALID_ARG;
-    fheram_ctx* c = b->c;
-    if (!out) return fail(c, FHERAM_ERR_INVALID_ARG, "null output");
-    *out = nullptr;
-    if (!ggsw) return fail(c, FHERAM_ERR_INVALID_ARG, "null ggsw");
     fheram_selector* s = nullptr;
-    int rc = selector_new(b, bits, &s);
+    int rc = selector_create_args(b, ggsw, out);
+    if (rc == FHERAM_OK) rc = selector_new(b, bits, &s);
     if (rc != FHERAM_OK) return rc;
-    if (n_ggsw != s->n_digits) rc = fail(c, FHERAM_ERR_INVALID_ARG, "a selector of " + std::to_string(bits) + " bits has " + std::to_string(s->n_digits) + " digits, not " + std::to_string(n_ggsw));
-    for (int i = 0; i < n_ggsw && rc == FHERAM_OK; i++)
-        rc = ggsw[i] ? upload_i64(c, s->d_ggsw + (size_t)i * fheram_ctx::GGSW, ggsw[i], fheram_ctx::GGSW) : fail(c, FHERAM_ERR_INVALID_ARG, "null ggsw digit");
-    if (rc != FHERAM_OK) { fheram_selector_destroy(s); return rc; }
-    s->empty = false;
-    *out = s;
-    return FHERAM_OK;
+    return selector_fill(b, s, ggsw, n_ggsw, "a selector of " + std::to_string(bits) + " bits has " + std::to_string(s->n_digits) + " digits, not " + std::to_string(n_ggsw), out);
 }
 int fheram_bank_selector_alloc_fields(fheram_bank* b, const int* widths, int n_fields, fheram_selector** out) {
     if (!b) return FHERAM_ERR_INVALID_ARG;
@@ -324,20 +370,11 @@ int fheram_bank_selector_alloc_fields(fheram_bank* b, const int* widths, int n_f
 }
 int fheram_bank_selector_create_fields(fheram_bank* b, const int64_t* const* ggsw, int n_ggsw, const int* widths, int n_fields, fheram_selector** out) {
     if (!b) return FHERAM_ERR_INVALID_ARG;
-    fheram_ctx* c = b->c;
-    if (!out) return fail(c, FHERAM_ERR_INVALID_ARG, "null output");
-    *out = nullptr;
-    if (!ggsw) return fail(c, FHERAM_ERR_INVALID_ARG, "null ggsw");
     fheram_selector* s = nullptr;
-    int rc = selector_new_fields(b, widths, n_fields, &s);
+    int rc = selector_create_args(b, ggsw, out);
+    if (rc == FHERAM_OK) rc = selector_new_fields(b, widths, n_fields, &s);
     if (rc != FHERAM_OK) return rc;
-    if (n_ggsw != n_fields) rc = fail(c, FHERAM_ERR_INVALID_ARG, "a selector of " + std::to_string(n_fields) + " fields has as many digits, not " + std::to_string(n_ggsw));
-    for (int i = 0; i < n_ggsw && rc == FHERAM_OK; i++)
-        rc = ggsw[i] ? upload_i64(c, s->d_ggsw + (size_t)i * fheram_ctx::GGSW, ggsw[i], fheram_ctx::GGSW) : fail(c, FHERAM_ERR_INVALID_ARG, "null ggsw digit");
-    if (rc != FHERAM_OK) { fheram_selector_destroy(s); return rc; }
-    s->empty = false;
-    *out = s;
-    return FHERAM_OK;
+    return selector_fill(b, s, ggsw, n_ggsw, "a selector of " + std::to_string(n_fields) + " fields has as many digits, not " + std::to_string(n_ggsw), out);
 }
 // digit d of sel <- bits [first_bit[d], first_bit[d] + widths[d]) of fus[d], in place: the unchanged k_cmux_chain, ONE LAUNCH PER FIELD of grid
 // (6, 1, 1) with `out` advanced to the digit and the plan's entry 0 set to the field's (the argument struct holds one plan for all its integers, and
@@ -437,49 +474,23 @@ int fheram_bank_select(fheram_bank* b, const fheram_selector* const* sels, const
     if (!sels || !n_cand || !srcs) return fail(c, FHERAM_ERR_INVALID_ARG, "null selector list, candidate counts or sources");
     int total = 0, n_host = 0;
     int rc = select_check_sels(b, sels, n_cand, n, &total);
+    if (rc == FHERAM_OK) rc = sources_check(b, srcs, total, host_words, 0, "", true, &n_host);
     if (rc != FHERAM_OK) return rc;
     const int ws = b->mws, Y = n * ws;
-    SelectNeeds need;
-    for (int i = 0; i < total; i++) {
-        rc = select_check_source(b, srcs[i].kind, srcs[i].index, "source " + std::to_string(i), host_words, need);
-        if (rc != FHERAM_OK) return rc;
-        if (srcs[i].kind == FHERAM_SRC_HOST) n_host = std::max(n_host, srcs[i].index + 1);
-    }
-    rc = select_check_state(b, need);
-    if (rc != FHERAM_OK) return rc;
-    for (int i = 0; i < total; i++)
-        if (srcs[i].kind == FHERAM_SRC_MEMBER_RESULT && !b->has_res[srcs[i].index])
-            return fail(c, FHERAM_ERR_STATE, "source " + std::to_string(i) + " names the result of member " + std::to_string(srcs[i].index) + ", which has none yet");
     HIPCHK(c, hipSetDevice(c->device));
     const int d = sels[0]->n_digits;
     rc = select_reserve(b, Y, n * d, n_host * ws);
     if (rc != FHERAM_OK) return rc;
     SelectBufs& S = b->sel;
-    const size_t per = (size_t)ws * fheram_ctx::GLWE;
-    if (n_host) {   // the host candidates, range-checked as write words are: only the slots a source names
-        if (S.host_busy) { HIPCHK(c, hipEventSynchronize(S.ev_host)); S.host_busy = false; }
-        std::vector<char> staged((size_t)n_host, 0);
-        for (int i = 0; i < total; i++) {
-            if (srcs[i].kind != FHERAM_SRC_HOST || staged[(size_t)srcs[i].index]) continue;
-            staged[(size_t)srcs[i].index] = 1;
-            if (!narrow(host_words + (size_t)srcs[i].index * per, S.h_host + (size_t)srcs[i].index * per, per))
-                return fail(c, FHERAM_ERR_RANGE, "limb out of the normalised range [-2^16, 2^16]");
-        }
-    }
+    rc = host_words_stage(b, S.host, srcs, total, n_host, host_words);   // the host candidates: only the slots a source names
+    if (rc != FHERAM_OK) return rc;
     // ---- enqueue ----
     main_enqueued(c);
     c->cur = c->stream;
     c->wide = true;   // (as a write: whatever gate wave a read_prepare_write parked is released by that operation's own trace chain, which is ahead of this on the stream)
-    if (n_host) {
-        for (int sl = 0; sl < n_host; sl++) {
-            bool used = false;
-            for (int i = 0; i < total && !used; i++) used = srcs[i].kind == FHERAM_SRC_HOST && srcs[i].index == sl;
-            if (used) HIPCHK(c, hipMemcpyAsync(S.d_host + (size_t)sl * per, S.h_host + (size_t)sl * per, per * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        }
-        HIPCHK(c, hipEventRecord(S.ev_host, c->stream));
-        S.host_busy = true;
-    }
-    b->sel_n = 0;   // until this select is enqueued there is no last select
+    rc = host_words_copy(b, S.host, srcs, total, n_host);
+    if (rc != FHERAM_OK) return rc;
+    b->last[LAST_SELECT].n = 0;   // until this select is enqueued there is no last select
     {   // the pack: ONE launch, whatever n and m are
         SelectPackArgs sa{};
         sa.out = S.packed; sa.ws = ws;
@@ -505,7 +516,7 @@ int fheram_bank_select_lanes(fheram_bank* b, const fheram_selector* const* sels,
     int rc = select_check_sels(b, sels, n_cand, n, &total);
     if (rc != FHERAM_OK) return rc;
     const int ws = b->mws, Y = n * ws, n_lanes = total * ws;
-    SelectNeeds need;
+    unsigned need = 0;
     for (int i = 0; i < n_lanes; i++) {
         const fheram_select_lane& l = lanes[i];
         const std::string who = "lane " + std::to_string(i % ws) + " of candidate " + std::to_string(i / ws);
@@ -532,23 +543,25 @@ int fheram_bank_select_lanes(fheram_bank* b, const fheram_selector* const* sels,
     const size_t G = fheram_ctx::GLWE;
     std::vector<char> staged((size_t)n_host * ws, 0);   // host ciphertext (slot, lane): named by a lane
     if (n_host) {   // range-checked as write words are: only the ciphertexts a lane names
-        if (S.host_busy) { HIPCHK(c, hipEventSynchronize(S.ev_host)); S.host_busy = false; }
+        rc = stage_wait(c, S.host);
+        if (rc != FHERAM_OK) return rc;
         for (int i = 0; i < n_lanes; i++) {
             if (lanes[i].kind != FHERAM_SRC_HOST) continue;
             const size_t at = (size_t)lanes[i].index * ws + lanes[i].lane;
             if (staged[at]) continue;
             staged[at] = 1;
-            if (!narrow(host_words + at * G, S.h_host + at * G, G))
+            if (!narrow(host_words + at * G, S.host.host<int32_t>() + at * G, G))
                 return fail(c, FHERAM_ERR_RANGE, "limb out of the normalised range [-2^16, 2^16]");
         }
     }
-    if (L.busy) { HIPCHK(c, hipEventSynchronize(L.ev)); L.busy = false; }   // the last call's copy out of the pinned table; no other host wait
+    rc = stage_wait(c, L);   // the last call's copy out of the pinned table
+    if (rc != FHERAM_OK) return rc;
     SelectLanesArgs sa{};
-    sa.table = L.d_tab; sa.out = S.packed; sa.ws = ws;
+    sa.table = L.dev<const int32_t*>(); sa.out = S.packed; sa.ws = ws;
     for (int k = 0, i = 0; k < n; k++) {
         sa.m[k] = n_cand[k];
         for (int j = 0; j < n_cand[k]; j++, i++)
-            for (int w = 0; w < ws; w++) L.h_tab[(size_t)(k * ws + w) * SELECT_CAND_MAX + j] = select_source_lane(b, lanes[(size_t)i * ws + w]);
+            for (int w = 0; w < ws; w++) L.host<const int32_t*>()[(size_t)(k * ws + w) * SELECT_CAND_MAX + j] = select_source_lane(b, lanes[(size_t)i * ws + w]);
     }
     // ---- enqueue ----
     main_enqueued(c);
@@ -556,14 +569,14 @@ int fheram_bank_select_lanes(fheram_bank* b, const fheram_selector* const* sels,
     c->wide = true;   // (as fheram_bank_select)
     if (n_host) {
         for (size_t at = 0; at < staged.size(); at++)
-            if (staged[at]) HIPCHK(c, hipMemcpyAsync(S.d_host + at * G, S.h_host + at * G, G * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipEventRecord(S.ev_host, c->stream));
-        S.host_busy = true;
+            if (staged[at]) HIPCHK(c, hipMemcpyAsync(S.host.dev<int32_t>() + at * G, S.host.host<int32_t>() + at * G, G * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        rc = stage_record(c, S.host);
+        if (rc != FHERAM_OK) return rc;
     }
-    b->sel_n = 0;   // until this select is enqueued there is no last select
-    HIPCHK(c, hipMemcpyAsync(L.d_tab, L.h_tab, (size_t)Y * SELECT_CAND_MAX * sizeof(const int32_t*), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(L.ev, c->stream));
-    L.busy = true;
+    b->last[LAST_SELECT].n = 0;   // until this select is enqueued there is no last select
+    HIPCHK(c, hipMemcpyAsync(L.d, L.h, (size_t)Y * SELECT_CAND_MAX * sizeof(const int32_t*), hipMemcpyHostToDevice, c->stream));
+    rc = stage_record(c, L);
+    if (rc != FHERAM_OK) return rc;
     {   // the pack: ONE launch, whatever n, m and the lanes are
         ProfScope ps(c, "select_pack", (uint64_t)Y);
         select_lanes_launch(Y, c->cur, sa);
@@ -571,16 +584,7 @@ int fheram_bank_select_lanes(fheram_bank* b, const fheram_selector* const* sels,
     return select_chain(b, sels, n, out);
 }
 int fheram_bank_select_result(fheram_bank* b, int first, int n, int64_t* out) {
-    if (!b) return FHERAM_ERR_INVALID_ARG;
-    fheram_ctx* c = b->c;
-    if (!out) return fail(c, FHERAM_ERR_INVALID_ARG, "null output");
-    if (!b->sel_n) return fail(c, FHERAM_ERR_STATE, "no select has run on this bank");
-    if (first < 0 || n < 1 || first > b->sel_n - n)
-        return fail(c, FHERAM_ERR_INVALID_ARG, "outputs [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") are empty or outside the last select's " + std::to_string(b->sel_n) + " outputs");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
-    const ResRun run{b->sel.res + (size_t)first * per, (size_t)n * per};
-    return result_export(c, &run, 1, b->sel.h_res, b->sel.d_h_res, out);
+    return b ? last_result(b, LAST_SELECT, first, n, out) : FHERAM_ERR_INVALID_ARG;
 }
 // n independent Ram::write, entry k's words = output picks[k] of the last select: bank_write_set with a stage that copies on the device
 // (no host wait, no range check: a select's outputs are normalised by construction)
@@ -589,10 +593,11 @@ int fheram_bank_write_list_selected(fheram_bank* b, const int* members, const fh
     const int rc = write_list_check(b, members, addrs, n, !picks, 1, &s);
     if (rc != FHERAM_OK) return rc;
     fheram_ctx* c = b->c;
-    if (!b->sel_n) return fail(c, FHERAM_ERR_STATE, "no select has run on this bank");
+    const int sel_n = b->last[LAST_SELECT].n;
+    if (!sel_n) return fail(c, FHERAM_ERR_STATE, "no select has run on this bank");
     for (int k = 0; k < n; k++)
-        if (picks[k] < 0 || picks[k] >= b->sel_n)
-            return fail(c, FHERAM_ERR_INVALID_ARG, "entry " + std::to_string(k) + " picks output " + std::to_string(picks[k]) + ", outside the last select's " + std::to_string(b->sel_n) + " outputs");
+        if (picks[k] < 0 || picks[k] >= sel_n)
+            return fail(c, FHERAM_ERR_INVALID_ARG, "entry " + std::to_string(k) + " picks output " + std::to_string(picks[k]) + ", outside the last select's " + std::to_string(sel_n) + " outputs");
     const long G = (long)fheram_ctx::GLWE;
     return bank_write_set(b, s, addrs, [&](int32_t* d_w, int) {
         main_enqueued(c);

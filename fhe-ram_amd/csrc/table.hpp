@@ -12,7 +12,7 @@
 //   selectors   WIDE selectors: fheram_selector handles of up to FHERAM_TABLE_BITS_MAX bits and FHERAM_SELECTOR_WIDE_DIGITS_MAX digits,
 //               made here; every derivation takes them unchanged, the select and the register file refuse them
 // Everything runs on the bank's main stream.  A table owns its row, allocated by fheram_bank_table_create; what the tables of a bank
-// share (path.hpp TableBufs) is allocated by the bank's first create.  No operation allocates.  No member's rows, state flag, tree, result
+// share (path.hpp OneRowSet) is allocated by the bank's first create.  No operation allocates.  No member's rows, state flag, tree, result
 // or kept memo is touched, no register file's row or state, nor the last read list's, select's or register read's results.
 //
 // This file has two parts: what table.hip (the kernels' translation unit) and fheram.hip share — the argument structs and the launchers —
@@ -61,35 +61,32 @@ static_assert((1 << FHERAM_TABLE_BITS_MAX) == N, "a table's row holds one word p
 void table_bank_release(fheram_bank* b) {
     for (fheram_table* t : b->tables) { if (t->row) hipFree(t->row); t->row = nullptr; t->bank = nullptr; t->initialized = false; }
     b->tables.clear();
-    table_bufs_free(b->tabs);
+    one_row_free(b->tabs);
 }
-// what the tables of a bank share, whole (path.hpp TableBufs)
+// what the tables of a bank share, whole (path.hpp OneRowSet): the stage holds the bytes of a load_plain
 int table_bufs_reserve(fheram_bank* b) {
-    fheram_ctx* c = b->c;
-    if (b->tabs.cap) return FHERAM_OK;
-    TableBufs nw;
-    nw.cap = std::min(FHERAM_SELECT_MAX * b->mws, TABLE_CT_MAX);
-    const size_t ct = (size_t)nw.cap * fheram_ctx::GLWE * sizeof(int32_t);
-    const size_t data = (size_t)(1 << FHERAM_TABLE_BITS_MAX) * b->mws;
-    hipError_t e = hipSuccess;
-    for (int32_t** p : {&nw.fan, &nw.ep, &nw.tmp, &nw.res}) if (e == hipSuccess) e = hipMalloc((void**)p, ct);
-    if (e == hipSuccess) e = hipMalloc((void**)&nw.prep, (size_t)FHERAM_SELECT_MAX * FHERAM_SELECTOR_WIDE_DIGITS_MAX * fheram_ctx::GGSW * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&nw.d_data, data);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&nw.h_res, ct * 2 + sizeof(int64_t), hipHostMallocMapped);   // int64, + the monitor's maximum
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&nw.d_h_res, nw.h_res, 0);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&nw.h_data, data, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&nw.ev_data, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        table_bufs_free(nw);
-        (void)hipGetLastError();   // the next op's error check must not see this allocation's failure
-        return fail(c, FHERAM_ERR_DEVICE, std::string("buffers of the bank's tables: ") + hipGetErrorString(e));
-    }
-    b->tabs = nw;
-    return FHERAM_OK;
+    return one_row_reserve(b->c, b->tabs, b->mws, FHERAM_SELECTOR_WIDE_DIGITS_MAX, (size_t)(1 << FHERAM_TABLE_BITS_MAX) * b->mws, "buffers of the bank's tables");
 }
 // the handle: null, of another bank (or of a destroyed one)
 int table_check_handle(fheram_bank* b, const fheram_table* t, const std::string& who) {
     if (!t || t->bank != b) return fail(b->c, FHERAM_ERR_INVALID_ARG, who + " is null or belongs to another bank");
+    return FHERAM_OK;
+}
+// n reads of tables as one operation, behind the lists: every table and its selector, then every table initialised.  who: what a selector
+// is called ("selector ", the mix's "table selector "); digits_tail: why two selectors may not differ in digits, in the caller's words
+int table_check_reads(fheram_bank* b, const fheram_table* const* tables, const fheram_selector* const* sels, int n, const std::string& who, const char* digits_tail) {
+    fheram_ctx* c = b->c;
+    for (int k = 0; k < n; k++) {
+        int rc = table_check_handle(b, tables[k], "table " + std::to_string(k));
+        if (rc == FHERAM_OK) rc = selector_check(b, sels[k], who + std::to_string(k), "fheram_bank_table_selector_alloc");
+        if (rc != FHERAM_OK) return rc;
+        const fheram_selector* s = sels[k];
+        if (s->bits != tables[k]->bits) return fail(c, FHERAM_ERR_INVALID_ARG, who + std::to_string(k) + " has " + std::to_string(s->bits) + " bits, table " + std::to_string(k) + " " + std::to_string(tables[k]->bits));
+        if (s->n_digits != sels[0]->n_digits)   // (the tables of a call may differ in bits; the operand table has one stride)
+            return fail(c, FHERAM_ERR_INVALID_ARG, who + std::to_string(k) + " has " + std::to_string(s->n_digits) + " digits, " + who + "0 " + std::to_string(sels[0]->n_digits) + ": " + digits_tail);
+    }
+    for (int k = 0; k < n; k++)
+        if (!tables[k]->initialized) return fail(c, FHERAM_ERR_UNINITIALIZED, "unitialized memory: table " + std::to_string(k) + " has had no fheram_bank_table_upload or fheram_bank_table_load_plain");
     return FHERAM_OK;
 }
 
@@ -133,26 +130,16 @@ int fheram_table_bits(const fheram_table* t) { return t ? t->bits : 0; }
 
 int fheram_bank_table_upload(fheram_bank* b, fheram_table* t, const int64_t* row) {
     if (!b) return FHERAM_ERR_INVALID_ARG;
-    fheram_ctx* c = b->c;
     int rc = table_check_handle(b, t, "the table");
-    if (rc != FHERAM_OK) return rc;
-    if (!row) return fail(c, FHERAM_ERR_INVALID_ARG, "null row");
-    HIPCHK(c, hipSetDevice(c->device));
-    rc = upload_i64(c, t->row, row, (size_t)b->mws * fheram_ctx::GLWE);
+    if (rc == FHERAM_OK) rc = row_upload(b, t->row, row);
     if (rc != FHERAM_OK) return rc;
     t->initialized = true;
     return FHERAM_OK;
 }
 int fheram_bank_table_download(fheram_bank* b, const fheram_table* t, int64_t* row) {
     if (!b) return FHERAM_ERR_INVALID_ARG;
-    fheram_ctx* c = b->c;
-    int rc = table_check_handle(b, t, "the table");
-    if (rc != FHERAM_OK) return rc;
-    if (!row) return fail(c, FHERAM_ERR_INVALID_ARG, "null row");
-    if (!t->initialized) return fail(c, FHERAM_ERR_UNINITIALIZED, "unitialized memory: the table has had no fheram_bank_table_upload or fheram_bank_table_load_plain");
-    HIPCHK(c, hipSetDevice(c->device));
-    rc = download_i64(c, row, t->row, (size_t)b->mws * fheram_ctx::GLWE);
-    return rc == FHERAM_OK ? check_precision(c) : rc;
+    const int rc = table_check_handle(b, t, "the table");
+    return rc == FHERAM_OK ? row_download(b, t->row, t->initialized, "unitialized memory: the table has had no fheram_bank_table_upload or fheram_bank_table_load_plain", row) : rc;
 }
 // the row <- the trivial ciphertext of public bytes (header comment): one copy out of the pinned staging buffer, one launch
 int fheram_bank_table_load_plain(fheram_bank* b, fheram_table* t, const uint8_t* data, size_t data_len) {
@@ -168,17 +155,18 @@ int fheram_bank_table_load_plain(fheram_bank* b, fheram_table* t, const uint8_t*
     const int k_pt = (int)c->p.k_glwe_pt, size_pt = (k_pt + BASE2K - 1) / BASE2K;
     if (k_pt <= 0 || k_pt > 8 + BASE2K || size_pt > fheram_ctx::S_CT) return fail(c, FHERAM_ERR_UNSUPPORTED, "k_glwe_pt out of range");   // (as fheram_ram_encrypt_sk)
     HIPCHK(c, hipSetDevice(c->device));
-    TableBufs& B = b->tabs;
-    if (B.data_busy) { HIPCHK(c, hipEventSynchronize(B.ev_data)); B.data_busy = false; }   // the last call's copy out of the pinned buffer; no other host wait
-    std::memcpy(B.h_data, data, data_len);
+    HostStage& st = b->tabs.stage;
+    rc = stage_wait(c, st);
+    if (rc != FHERAM_OK) return rc;
+    std::memcpy(st.h, data, data_len);
     // ---- enqueue ----
     main_enqueued(c);
     c->cur = c->stream;
-    HIPCHK(c, hipMemcpyAsync(B.d_data, B.h_data, data_len, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(B.ev_data, c->stream));
-    B.data_busy = true;
+    HIPCHK(c, hipMemcpyAsync(st.d, st.h, data_len, hipMemcpyHostToDevice, c->stream));
+    rc = stage_record(c, st);
+    if (rc != FHERAM_OK) return rc;
     {
-        const TableEncodeArgs ea{B.d_data, t->row, b->mws, 1 << t->bits, k_pt, size_pt};
+        const TableEncodeArgs ea{st.d, t->row, b->mws, 1 << t->bits, k_pt, size_pt};
         ProfScope ps(c, "elementwise", (uint64_t)b->mws);
         table_encode_launch(b->mws, c->cur, ea);
     }
@@ -198,25 +186,14 @@ int fheram_bank_table_read(fheram_bank* b, const fheram_table* const* tables, co
     const int ws = b->mws, Y = n * ws;
     if (Y > TABLE_CT_MAX)
         return fail(c, FHERAM_ERR_INVALID_ARG, "n * word_size = " + std::to_string(Y) + " exceeds 64, the ciphertext limit of the single-launch chains (k_chain_mid)");
-    for (int k = 0; k < n; k++) {
-        const std::string who = "selector " + std::to_string(k);
-        const int rc = table_check_handle(b, tables[k], "table " + std::to_string(k));
-        if (rc != FHERAM_OK) return rc;
-        const fheram_selector* s = sels[k];
-        if (!s || s->bank != b) return fail(c, FHERAM_ERR_INVALID_ARG, who + " is null or belongs to another bank");
-        if (s->empty) return fail(c, FHERAM_ERR_INVALID_ARG, who + " is empty: fheram_bank_table_selector_alloc without fheram_bank_selector_derive");
-        if (s->bits != tables[k]->bits) return fail(c, FHERAM_ERR_INVALID_ARG, who + " has " + std::to_string(s->bits) + " bits, table " + std::to_string(k) + " " + std::to_string(tables[k]->bits));
-        if (s->n_digits != sels[0]->n_digits)   // (the tables of a call may differ in bits; the operand table has one stride)
-            return fail(c, FHERAM_ERR_INVALID_ARG, who + " has " + std::to_string(s->n_digits) + " digits, selector 0 " + std::to_string(sels[0]->n_digits) + ": the operand table of one call has one stride");
-    }
-    for (int k = 0; k < n; k++)
-        if (!tables[k]->initialized) return fail(c, FHERAM_ERR_UNINITIALIZED, "unitialized memory: table " + std::to_string(k) + " has had no fheram_bank_table_upload or fheram_bank_table_load_plain");
+    const int rc = table_check_reads(b, tables, sels, n, "selector ", "the operand table of one call has one stride");
+    if (rc != FHERAM_OK) return rc;
     if (!c->keys_loaded) return fail(c, FHERAM_ERR_KEYS, "evaluation keys not loaded");
     HIPCHK(c, hipSetDevice(c->device));
     // ---- enqueue ----
-    TableBufs& B = b->tabs;
+    OneRowSet& B = b->tabs;
     regs_begin(c);
-    b->table_n = 0;   // until this read is enqueued there is no last table read
+    b->last[LAST_TABLE].n = 0;   // until this read is enqueued there is no last table read
     {
         TableFanArgs fa{};
         fa.out = B.fan;
@@ -227,23 +204,13 @@ int fheram_bank_table_read(fheram_bank* b, const fheram_table* const* tables, co
     }
     one_row_reads(b, OneRowBufs{B.fan, B.ep, B.tmp, B.res, B.prep}, sels, n);
     HIPCHK(c, hipGetLastError());
-    b->table_n = n;
-    b->table_home = ResHome{B.res, B.h_res, B.d_h_res, -1};
+    b->last[LAST_TABLE] = LastOutputs{n, ResHome{B.res, B.h_res, B.d_h_res, -1}};
     if (!out) return FHERAM_OK;
     const ResRun run{B.res, (size_t)Y * fheram_ctx::GLWE};
     return result_export(c, &run, 1, B.h_res, B.d_h_res, out);
 }
 int fheram_bank_table_result(fheram_bank* b, int first, int n, int64_t* out) {
-    if (!b) return FHERAM_ERR_INVALID_ARG;
-    fheram_ctx* c = b->c;
-    if (!out) return fail(c, FHERAM_ERR_INVALID_ARG, "null output");
-    if (!b->table_n) return fail(c, FHERAM_ERR_STATE, "no fheram_bank_table_read has run on this bank");
-    if (first < 0 || n < 1 || first > b->table_n - n)
-        return fail(c, FHERAM_ERR_INVALID_ARG, "outputs [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(n) + ") are empty or outside the last table read's " + std::to_string(b->table_n) + " outputs");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
-    const ResRun run{b->table_home.res + (size_t)first * per, (size_t)n * per};
-    return result_export(c, &run, 1, b->table_home.h, b->table_home.d_h, out);
+    return b ? last_result(b, LAST_TABLE, first, n, out) : FHERAM_ERR_INVALID_ARG;
 }
 
 // WIDE selectors: the selectors of select.hpp with the table's bound on the bits (selector_new says what else is refused)
@@ -255,20 +222,11 @@ int fheram_bank_table_selector_alloc(fheram_bank* b, int bits, fheram_selector**
 }
 int fheram_bank_table_selector_create(fheram_bank* b, const int64_t* const* ggsw, int n_ggsw, int bits, fheram_selector** out) {
     if (!b) return FHERAM_ERR_INVALID_ARG;
-    fheram_ctx* c = b->c;
-    if (!out) return fail(c, FHERAM_ERR_INVALID_ARG, "null output");
-    *out = nullptr;
-    if (!ggsw) return fail(c, FHERAM_ERR_INVALID_ARG, "null ggsw");
     fheram_selector* s = nullptr;
-    int rc = selector_new(b, bits, &s, FHERAM_TABLE_BITS_MAX, "FHERAM_TABLE_BITS_MAX");
+    int rc = selector_create_args(b, ggsw, out);
+    if (rc == FHERAM_OK) rc = selector_new(b, bits, &s, FHERAM_TABLE_BITS_MAX, "FHERAM_TABLE_BITS_MAX");
     if (rc != FHERAM_OK) return rc;
-    if (n_ggsw != s->n_digits) rc = fail(c, FHERAM_ERR_INVALID_ARG, "a selector of " + std::to_string(bits) + " bits has " + std::to_string(s->n_digits) + " digits, not " + std::to_string(n_ggsw));
-    for (int i = 0; i < n_ggsw && rc == FHERAM_OK; i++)
-        rc = ggsw[i] ? upload_i64(c, s->d_ggsw + (size_t)i * fheram_ctx::GGSW, ggsw[i], fheram_ctx::GGSW) : fail(c, FHERAM_ERR_INVALID_ARG, "null ggsw digit");
-    if (rc != FHERAM_OK) { fheram_selector_destroy(s); return rc; }
-    s->empty = false;
-    *out = s;
-    return FHERAM_OK;
+    return selector_fill(b, s, ggsw, n_ggsw, "a selector of " + std::to_string(bits) + " bits has " + std::to_string(s->n_digits) + " digits, not " + std::to_string(n_ggsw), out);
 }
 int fheram_bank_table_selector_alloc_fields(fheram_bank* b, const int* widths, int n_fields, fheram_selector** out) {
     if (!b) return FHERAM_ERR_INVALID_ARG;

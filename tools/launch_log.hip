@@ -29,6 +29,12 @@
 // the context's buffer fields and word count: a range's pointer arithmetic, and anything an operation leaves behind in the context, is in
 // the log.  What differs between trees — how a bank range is presented to the sequences, where the per-RAM state lives — is in the shim.
 // bank.hpp names entry points of fheram.hip that this program never calls: link with -Wl,--unresolved-symbols=ignore-all.
+// Fourth mode, `./launch_log onerow`: the operations that keep last outputs, stage host words and read one-row RAMs —
+// select, select_lanes, the register file, the tables, both mixes, peek and poke — through their entry points, on a bank of two at word
+// sizes 2 and 13: every launch, copy and event, and after every operation each kind's last-outputs record and what select_source
+// gives for it (one digest line per configuration; `./launch_log onerow <id>` prints one in full); then those operations' refusals and the reserve log of their buffer sets, the three self-test failing allocations at every
+// nth included.  The launchers of the other translation units are recorders here; pinned allocations are real memory at fixed addresses
+// (profiles/one_row_kinds_log.txt).
 // Third mode, `./launch_log config`: the switches IN EFFECT (ctx.hpp config_in_effect) for a list of requested configurations, one line per
 // input, both sides as departures from the built-in defaults D (profiles/ctx_config_in_effect.txt: the tree's of DESIGN.md 10.6).
 #include <hip/hip_runtime.h>
@@ -149,6 +155,49 @@ hipError_t event(const char* what, const void* ev, hipStream_t s) {
     if (path_mode) line(std::string("  ") + what + " " + arena_of((uint64_t)(uintptr_t)ev) + (s == main_stream ? " main" : " side"));
     return hipSuccess;
 }
+// onerow mode: pinned allocations have real, zeroed memory behind them (narrow and result_export touch it), allocation k at a fixed
+// address, so that the argument digests are reproducible; it shows as p<k>+<byte offset>.  Events are fake addresses of their own
+// (a230 ..), created, waited for and destroyed in the reserve log; copies are lines of the sequence.
+bool onerow_mode = false;
+constexpr uintptr_t PINNED_BASE = 0x7d0000000000ull, PINNED_STEP = 0x10000000ull;
+unsigned n_pinned = 0, n_events = 0;
+hipError_t alloc_pinned(void** p, size_t bytes) {
+    if (!onerow_mode) return alloc(p, bytes, "alloc pinned");
+    if (fail_nth > 0 && --fail_nth == 0) { call_event("alloc pinned " + std::to_string(bytes) + " -> out of memory"); return hipErrorOutOfMemory; }
+    void* want = reinterpret_cast<void*>(PINNED_BASE + PINNED_STEP * n_pinned++);
+    if (bytes > PINNED_STEP || mmap(want, bytes, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_FIXED_NOREPLACE, -1, 0) != want) { std::perror("mmap (pinned)"); std::exit(1); }
+    *p = want;
+    call_event("alloc pinned " + std::to_string(bytes));
+    return hipSuccess;
+}
+std::string ptr_name(const void* p) {
+    const uintptr_t v = (uintptr_t)p;
+    if (!p) return "0";
+    if (v >= PINNED_BASE && v < PINNED_BASE + PINNED_STEP * n_pinned) {
+        char buf[48];
+        std::snprintf(buf, sizeof buf, "p%u+%#x", (unsigned)((v - PINNED_BASE) / PINNED_STEP), (unsigned)((v - PINNED_BASE) % PINNED_STEP));
+        return buf;
+    }
+    const std::string a = arena_of(v);
+    return a.empty() ? "host" : a;
+}
+hipError_t copy(const void* dst, const void* src, size_t bytes, hipMemcpyKind kind, const char* how, hipStream_t s) {
+    const char* k = kind == hipMemcpyHostToDevice ? "h2d" : kind == hipMemcpyDeviceToHost ? "d2h" : kind == hipMemcpyDeviceToDevice ? "d2d" : "copy";
+    const std::string l = std::string(how) + " " + k + " " + ptr_name(dst) + " <- " + ptr_name(src) + " " + std::to_string(bytes) + "B" + (s == main_stream ? " main" : " side");
+    if (path_mode) line("  " + l);
+    if (reserve_mode) call_event(l);
+    return hipSuccess;
+}
+hipError_t event_create(hipEvent_t* e) {
+    *e =reinterpret_cast<hipEvent_t>((uintptr_t)0x100000000ull * (uintptr_t)(231 + n_events++ % 24));
+    call_event("event");
+    return hipSuccess;
+}
+hipError_t event_sync(hipEvent_t e) {
+    if (path_mode) line("  sync " + arena_of((uint64_t)(uintptr_t)e));
+    if (reserve_mode) call_event("wait event");
+    return hipSuccess;
+}
 }  // namespace ll
 
 #undef hipLaunchKernelGGL
@@ -162,18 +211,40 @@ hipError_t event(const char* what, const void* ev, hipStream_t s) {
 #define hipSetDevice(d) ((void)(d), hipSuccess)
 // nothing is allocated: a fake address back, and a line in the reserve log
 #define hipMalloc(p, bytes) ll::alloc((void**)(p), bytes, "alloc")
-#define hipHostMalloc(p, bytes, flags) ll::alloc((void**)(p), bytes, "alloc pinned")
+#define hipHostMalloc(p, bytes, flags) ll::alloc_pinned((void**)(p), bytes)
 #define hipHostGetDevicePointer(d, h, flags) (*(d) = (h), hipSuccess)
 #define hipFree(p) ll::release("free")
 #define hipHostFree(p) ll::release("free pinned")
+// no copy is made; events with flags (the host stages') are fake addresses (onerow mode)
+#define hipMemcpyAsync(dst, src, bytes, kind, s) ll::copy(dst, src, bytes, kind, "copy", s)
+#define hipMemcpy(dst, src, bytes, kind) ll::copy(dst, src, bytes, kind, "copy (blocking)", ll::main_stream)
+#define hipEventCreateWithFlags(e, flags) ll::event_create(e)
+#define hipEventSynchronize(e) ll::event_sync(e)
+#define hipEventDestroy(e) ll::release("event destroy")
 
-#include "bank.hpp"
+#include "mix.hpp"         // (bank.hpp, select.hpp, regs.hpp and table.hpp with it)
+#include "public_io.hpp"
 #include <launch_log_shim.hpp>   // (angle brackets: from the include path, not from beside this file)
 
-// the write lists' row chains launch from a translation unit of their own (mapped_chains.hip): here they are recorders like every other launch
+// the launchers of the other translation units (mapped_chains.hip: the write lists' row chains; select_pack.hip, select_lanes.hip, regs.hip,
+// table.hip, mix.hip, public_io.hip, cmux_chain.hip): here they are recorders like every other launch
 namespace fk {
 void read_chain_m_launch(int sk, dim3 grid, hipStream_t stream, const RowChainTableArgs& ra) { ll::record(("k_read_chain_m<" + std::to_string(sk) + ">").c_str(), "", grid, dim3(256), 0, stream, ra); }
 void write_chain_m_launch(int sk, dim3 grid, hipStream_t stream, const RowChainTableArgs& ra) { ll::record(("k_write_chain_m<" + std::to_string(sk) + ">").c_str(), "", grid, dim3(256), 0, stream, ra); }
+void select_pack_launch(dim3 grid, hipStream_t stream, const SelectPackArgs& sa) { ll::record("k_select_pack", "", grid, dim3(256), 0, stream, sa); }
+void select_lanes_launch(int n_ct, hipStream_t stream, const SelectLanesArgs& sa) { ll::record("k_select_pack_lanes", "", dim3(1, n_ct, SELECT_LANES_SLICES), dim3(256), 0, stream, sa); }
+void regs_fan_launch(int n_ct, hipStream_t stream, const RegsFanArgs& fa) { ll::record("k_regs_fan", "", dim3(1, n_ct, REGS_SLICES), dim3(256), 0, stream, fa); }
+void regs_merge_launch(int ws, hipStream_t stream, const RegsMergeArgs& ma) { ll::record("k_regs_merge", "", dim3(1, ws, REGS_SLICES), dim3(256), 0, stream, ma); }
+void table_fan_launch(int n_ct, hipStream_t stream, const TableFanArgs& fa) { ll::record("k_table_fan", "", dim3(1, n_ct, TABLE_SLICES), dim3(256), 0, stream, fa); }
+void table_encode_launch(int ws, hipStream_t stream, const TableEncodeArgs& ea) { ll::record("k_table_encode", "", dim3(1, ws, TABLE_SLICES), dim3(256), 0, stream, ea); }
+hipError_t mix_register() { ll::call_event("mix_register"); return hipSuccess; }
+void trace_tail_x_launch(int sk, hipStream_t stream, const TailMixArgs& ta) { ll::record(("k_trace_tail_x<" + std::to_string(sk) + ">").c_str(), "", dim3(TAIL_GROUPS * 2 * sk * 3), dim3(256), 0, stream, ta); }
+void read_chain_x_launch(int sk, int n_ct, hipStream_t stream, const RowChainMixArgs& ra) { ll::record(("k_read_chain_x<" + std::to_string(sk) + ">").c_str(), "", dim3(1, n_ct), dim3(256), 0, stream, ra); }
+void mix_scatter_launch(int ws, hipStream_t stream, const MixScatterArgs& sa) { ll::record("k_mix_scatter", "", dim3(sa.n, ws, MIX_SCATTER_SLICES), dim3(256), 0, stream, sa); }
+void rows_plain_launch(int n_rows, hipStream_t stream, const RowsPlainArgs& ra) { ll::record("k_rows_plain", "", dim3(n_rows, ra.ws, PUB_SLICES), dim3(256), 0, stream, ra); }
+void peek_gather_launch(int n_ct, hipStream_t stream, const PeekGatherArgs& ga) { ll::record("k_peek_gather", "", dim3(1, n_ct, PUB_SLICES), dim3(256), 0, stream, ga); }
+void poke_merge_launch(int n_touched, int ws, hipStream_t stream, const PokeMergeArgs& ma) { ll::record("k_poke_merge", "", dim3(n_touched, ws, PUB_SLICES), dim3(256), 0, stream, ma); }
+void cmux_chain_launch(dim3 grid, hipStream_t stream, const CmuxChainArgs& ca) { ll::record("k_cmux_chain", "", grid, dim3(256), 0, stream, ca); }
 }  // namespace fk
 
 namespace {
@@ -520,7 +591,10 @@ template <typename F>
 void refuse(fheram_bank* b, const std::string& what, F&& check) {
     fheram_ctx* c = b->c;
     c->err.clear(); c->cfg.mid = 0; c->mid_saved = 2; c->mid_off_ops = 0;
+    const bool verbose = ll::verbose;
+    ll::verbose = false;   // (an accepted call enqueues: its launches are not part of the refusal log)
     const int rc = check();
+    ll::verbose = verbose;
     ll::line(what + " -> " + std::to_string(rc) + " \"" + c->err + "\" rearm=" + std::to_string(c->mid_off_ops));
 }
 void run_refusals(unsigned* host_words) {
@@ -687,6 +761,636 @@ int path_main(long only, unsigned* host_words) {
     return 0;
 }
 
+// ---- onerow mode: the operations that keep last outputs, stage host words and read one-row RAMs, on a bank of two ------------------------
+// select, select_lanes, the register file, the tables, the mixes, peek and poke through their ENTRY POINTS (the launchers of the other
+// translation units are recorders), each followed by the return code, what it allocated, the members, every kind's last-outputs record, the
+// pointer select_source gives for index 0 of every kind, the host stages' busy flags and a digest of what is staged.
+struct OneRow {
+    fheram_bank* b;
+    fheram_ctx* c;
+    const fheram_addr* a[3];
+    std::vector<int64_t> words, bad_words, out;
+    fheram_fheuint* fu;
+};
+OneRow make_onerow(unsigned* host_words, int lg, int ws, const Setting& st) {
+    OneRow w;
+    fheram_ctx* c = make_path_ctx(host_words, lg, 2 * ws, 4, st);
+    c->p.n_decomp = 4; c->p.max_addr = (uint64_t)1 << lg; c->p.k_glwe_pt = 3; c->p.word_size = (uint32_t)(2 * ws);
+    for (int i = 0; i < 4; i++) c->p.decomp_n[i] = 3;
+    c->cfg.pre_inv = 0;   // (fheram_bank_create)
+    c->h_w = new int32_t[64 * fheram_ctx::GLWE]();   // stage_words narrows into it (leaked with the configuration)
+    c->ev_w = fake<hipEvent_t>(29);
+    w.c = c;
+    w.b = new fheram_bank();
+    w.b->c = c; w.b->M = 2; w.b->mws = ws;
+    w.b->d_prep = fake<double*>(60); w.b->d_prep_inv = fake<double*>(61);
+    shim_loaded(w.b);
+    for (int k = 0; k < 3; k++) w.a[k] = make_addr(c, k);
+    const size_t per = (size_t)ws * fheram_ctx::GLWE;
+    w.words.resize(40 * per);
+    for (size_t i = 0; i < w.words.size(); i++) w.words[i] = (int64_t)(i % 2001) - 1000;
+    w.bad_words = w.words;
+    w.bad_words[per + 5] = 65537;   // slot 1, ciphertext 0
+    w.out.assign(120 * fheram_ctx::GLWE, 0);
+    w.fu = new fheram_fheuint{c, 0, 32, fake<int32_t*>(27), fake<double*>(28)};
+    return w;
+}
+void free_onerow(OneRow& w) {
+    shim_release(w.b);
+    for (int k = 0; k < 3; k++) delete w.a[k];
+    delete w.fu; delete w.b; delete w.c;
+    (void)ll::take_events();
+}
+const char* const KIND_NAMES[] = {"list", "select", "regs", "table", "peek"};
+void dump_last(const fheram_bank* b) {
+    std::string l = "  -> last";
+    for (int k = 0; k < 5; k++) {
+        const ShimLast r = shim_last(b, k);
+        l += std::string(" ") + KIND_NAMES[k] + "{n=" + std::to_string(r.n);
+        if (r.n) l += " res=" + ll::ptr_name(r.res) + " h=" + ll::ptr_name(r.h) + " slot=" + std::to_string(r.mix_slot);
+        l += "}";
+    }
+    l += " regs_old=" + ll::ptr_name(shim_regs_old(b));
+    ll::line(l);
+    const int kinds[] = {FHERAM_SRC_ZERO, FHERAM_SRC_HOST, FHERAM_SRC_MEMBER_RESULT, FHERAM_SRC_LIST_RESULT, FHERAM_SRC_SELECT_RESULT, FHERAM_SRC_REGS_RESULT, FHERAM_SRC_REGS_OLD, FHERAM_SRC_TABLE_RESULT, FHERAM_SRC_PEEK_RESULT};
+    const int has[] = {1, 0, 1, shim_last(b, 0).n, shim_last(b, 1).n, shim_last(b, 2).n, shim_regs_old(b) != nullptr, shim_last(b, 3).n, shim_last(b, 4).n};
+    l = "  -> source[0]";
+    for (int i = 0; i < 9; i++) l += " " + std::to_string(kinds[i]) + ":" + (has[i] ? ll::ptr_name(shim_source(b, kinds[i], 0)) : std::string("-"));
+    ll::line(l);
+    l = "  -> " + shim_busy(b) + " staged";
+    ShimPinned pin[6];
+    const int n = shim_pinned(b, pin);
+    for (int i = 0; i < n; i++) {
+        char buf[64];
+        std::snprintf(buf, sizeof buf, " %s=%016" PRIx64, pin[i].name, pin[i].p ? ll::fnv(0xcbf29ce484222325ull, pin[i].p, pin[i].bytes) : (uint64_t)0);
+        l += buf;
+        if (pin[i].p && !std::strcmp(pin[i].name, "lanes")) ll::arenas_in(l, pin[i].p, 16 * SELECT_CAND_MAX * sizeof(void*));   // (the first 16 output ciphertexts' pointers)
+    }
+    ll::line(l);
+}
+template <typename F>
+int step(OneRow& w, const std::string& what, F&& f) {
+    op(what);
+    w.c->err.clear();
+    const int rc = f();
+    ll::line("  -> rc=" + std::to_string(rc) + " \"" + w.c->err + "\" allocations: " + ll::take_events());
+    dump_bank(w.b);
+    dump_last(w.b);
+    return rc;
+}
+std::string regs_state(const fheram_regs* r) { return " (register file: initialized=" + std::to_string(r->initialized) + " state=" + std::to_string(r->state) + " memo=" + std::to_string(r->memo) + ")"; }
+using Src = fheram_select_src;
+// selectors of `bits` bits, derived from bits [first_bit, ..) of the integer by the recorded k_cmux_chain
+fheram_selector* new_selector(OneRow& w, int bits, int first_bit, bool wide = false) {
+    fheram_selector* s = nullptr;
+    if (wide) fheram_bank_table_selector_alloc(w.b, bits, &s); else fheram_bank_selector_alloc(w.b, bits, &s);
+    const fheram_fheuint* fus[] = {w.fu};
+    fheram_selector* sels[] = {s};
+    if (s) fheram_bank_selector_derive(w.b, fus, &first_bit, 1, sels);
+    return s;
+}
+void run_onerow(unsigned* host_words, int lg, int ws, const Setting& st) {
+    OneRow w = make_onerow(host_words, lg, ws, st);
+    fheram_bank* b = w.b;
+    const int64_t* hw = w.words.data();
+    int64_t* out = w.out.data();
+    const int nmax = std::min(4, 64 / ws);   // entries a call of this word size may have
+    op("selectors: bits 3 x2 (one digit), bits 5 x2 (two digits), a wide one of 7 bits (three digits)");
+    fheram_selector *s3a = new_selector(w, 3, 0), *s3b = new_selector(w, 3, 3), *s5a = new_selector(w, 5, 6), *s5b = new_selector(w, 5, 11), *w7 = new_selector(w, 7, 16, true);
+    ll::line("  -> allocations: " + ll::take_events());
+    const int m10[] = {1, 0}, m1[] = {1}, m0[] = {0};
+    const fheram_addr* a10[] = {w.a[1], w.a[0]};
+    step(w, "bank read [0, 2)", [&] { return fheram_bank_read(b, 0, 2, w.a, nullptr); });
+    step(w, "bank read_list [1, 0]", [&] { return fheram_bank_read_list(b, m10, a10, 2, out); });
+    // ---- the register file ----
+    fheram_regs *r3 = nullptr, *r5 = nullptr;
+    step(w, "regs_create bits=3, bits=5", [&] { const int rc = fheram_bank_regs_create(b, 3, &r3); return rc ? rc : fheram_bank_regs_create(b, 5, &r5); });
+    const Src pack8[] = {{FHERAM_SRC_HOST, 2}, {FHERAM_SRC_MEMBER_RESULT, 1}, {FHERAM_SRC_LIST_RESULT, 1}, {FHERAM_SRC_ZERO, 0}, {FHERAM_SRC_HOST, 0}, {FHERAM_SRC_HOST, 2}, {FHERAM_SRC_LIST_RESULT, 0}, {FHERAM_SRC_MEMBER_RESULT, 0}};
+    step(w, "regs_pack r3 <- [host2, member1, list1, zero, host0, host2, list0, member0]", [&] { return fheram_bank_regs_pack(b, r3, 8, pack8, hw); });
+    step(w, "regs_pack r5 <- [host2, member1, list1] (the host stage still busy)", [&] { return fheram_bank_regs_pack(b, r5, 3, pack8, hw); });
+    const fheram_selector* s3[] = {s3a, s3b, s3a, s3b}, *s5[] = {s5a, s5b, s5b, s5a};
+    step(w, "regs_read r3 x2 (one digit: no products in the tail)", [&] { return fheram_bank_regs_read(b, r3, s3, 2, out); });
+    step(w, "regs_read r5 x" + std::to_string(nmax) + " (two digits), no download", [&] { return fheram_bank_regs_read(b, r5, s5, nmax, nullptr); });
+    step(w, "regs_result [1, 2)", [&] { return fheram_bank_regs_result(b, 1, 1, out); });
+    step(w, "regs_read_prepare_write r3" + regs_state(r3), [&] { return fheram_bank_regs_read_prepare_write(b, r3, s3a, out); });
+    step(w, "regs_old_result", [&] { return fheram_bank_regs_old_result(b, out); });
+    step(w, "regs_write r3 <- host1" + regs_state(r3), [&] { return fheram_bank_regs_write(b, r3, s3a, Src{FHERAM_SRC_HOST, 1}, hw); });
+    step(w, "regs_read_prepare_write r5, no download" + regs_state(r5), [&] { return fheram_bank_regs_read_prepare_write(b, r5, s5a, nullptr); });
+    step(w, "regs_write r5 <- regs_old after new keys (memo void)" + regs_state(r5), [&] { regs_keys_changed(b); return fheram_bank_regs_write(b, r5, s5a, Src{FHERAM_SRC_REGS_OLD, 0}, nullptr); });
+    // ---- the tables ----
+    fheram_table *t5a = nullptr, *t5b = nullptr, *t7 = nullptr;
+    step(w, "table_create bits=5 x2, bits=7", [&] { int rc = fheram_bank_table_create(b, 5, &t5a); if (!rc) rc = fheram_bank_table_create(b, 5, &t5b); return rc ? rc : fheram_bank_table_create(b, 7, &t7); });
+    std::vector<uint8_t> bytes((size_t)128 * ws);
+    for (size_t i = 0; i < bytes.size(); i++) bytes[i] = (uint8_t)(i * 7 + 3);
+    step(w, "table_load_plain t5a", [&] { return fheram_bank_table_load_plain(b, t5a, bytes.data(), (size_t)32 * ws); });
+    step(w, "table_load_plain t5b (the stage still busy)", [&] { return fheram_bank_table_load_plain(b, t5b, bytes.data() + 5, (size_t)32 * ws); });
+    step(w, "table_load_plain t7", [&] { return fheram_bank_table_load_plain(b, t7, bytes.data(), (size_t)128 * ws); });
+    const fheram_table* t55[] = {t5a, t5b, t5b, t5a}, *t7s[] = {t7};
+    const fheram_selector* w7s[] = {w7};
+    step(w, "table_read [t5a, t5b]", [&] { return fheram_bank_table_read(b, t55, s5, 2, out); });
+    step(w, "table_read [t7] (three digits), no download", [&] { return fheram_bank_table_read(b, t7s, w7s, 1, nullptr); });
+    step(w, "table_result [0, 1)", [&] { return fheram_bank_table_result(b, 0, 1, out); });
+    // ---- the public side ----
+    const uint64_t pa[] = {5, (uint64_t)1 << (lg - 1), 5, 4097 % ((uint64_t)1 << lg)};
+    const int pm[] = {0, 1, 1, 0};
+    step(w, "peek [(0, 5), (1, 2^(lg-1))]", [&] { return fheram_bank_peek(b, pm, pa, 2, out); });
+    step(w, "peek_result [1, 2)", [&] { return fheram_bank_peek_result(b, 1, 1, out); });
+    // ---- the selects: every source kind ----
+    const Src cand8[] = {{FHERAM_SRC_HOST, 1}, {FHERAM_SRC_MEMBER_RESULT, 0}, {FHERAM_SRC_LIST_RESULT, 1}, {FHERAM_SRC_REGS_RESULT, 1}, {FHERAM_SRC_REGS_OLD, 0}, {FHERAM_SRC_TABLE_RESULT, 0}, {FHERAM_SRC_PEEK_RESULT, 1}, {FHERAM_SRC_ZERO, 0}};
+    const int n8[] = {8, 3, 2, 1};
+    const fheram_selector* sel1[] = {s3a};
+    step(w, "select x1 of [host1, member0, list1, regs1, regs_old, table0, peek1, zero]", [&] { return fheram_bank_select(b, sel1, n8, 1, cand8, hw, out); });
+    const Src cand_again[] = {{FHERAM_SRC_SELECT_RESULT, 0}, {FHERAM_SRC_HOST, 3}, {FHERAM_SRC_HOST, 0}, {FHERAM_SRC_SELECT_RESULT, 0}, {FHERAM_SRC_HOST, 3}, {FHERAM_SRC_PEEK_RESULT, 0}, {FHERAM_SRC_SELECT_RESULT, 0}, {FHERAM_SRC_TABLE_RESULT, 0},
+                              {FHERAM_SRC_REGS_RESULT, 0}, {FHERAM_SRC_SELECT_RESULT, 0}, {FHERAM_SRC_LIST_RESULT, 0}, {FHERAM_SRC_SELECT_RESULT, 0}, {FHERAM_SRC_REGS_OLD, 0}, {FHERAM_SRC_SELECT_RESULT, 0}};
+    const int n_again[] = {3, 3, 4, 4};
+    step(w, "select x2 (two digits) of [select0, host3, host0 | select0, host3, peek0]: the buffers grow, the last outputs move", [&] { return fheram_bank_select(b, s5, n_again, 2, cand_again, hw, nullptr); });
+    step(w, "select_result [0, 2)", [&] { return fheram_bank_select_result(b, 0, 2, out); });
+    if (nmax >= 4) step(w, "select x4 of 3, 3, 4, 4 candidates: the buffers grow again", [&] { return fheram_bank_select(b, s5, n_again, 4, cand_again, hw, out); });
+    std::vector<fheram_select_lane> lanes;
+    for (int j = 0; j < 8; j++)
+        for (int l = 0; l < ws; l++) lanes.push_back(fheram_select_lane{cand8[j].kind, cand8[j].index, cand8[j].kind == FHERAM_SRC_ZERO ? 0 : (l + j) % ws, 0});
+    lanes[1] = fheram_select_lane{FHERAM_SRC_SELECT_RESULT, 1, 0, 0};
+    step(w, "select_lanes x1 of the eight kinds, lane (l + j) mod ws; lane 1 of candidate 0 from select1", [&] { return fheram_bank_select_lanes(b, sel1, n8, 1, lanes.data(), hw, out); });
+    step(w, "select_lanes again (table and stage still busy), no download", [&] { return fheram_bank_select_lanes(b, sel1, n8 + 1, 1, lanes.data(), hw, nullptr); });
+    const int picks[] = {0, 0};
+    step(w, "read_prepare_write_list [1, 0]", [&] { return fheram_bank_read_prepare_write_list(b, m10, a10, 2, nullptr); });
+    step(w, "write_list_selected [1, 0] <- select0, select0", [&] { return fheram_bank_write_list_selected(b, m10, a10, 2, picks); });
+    // ---- the mixes: both top forms (the tail up to 8 ciphertexts with 0 or 2+ digits everywhere), empty groups after single calls ----
+    fheram_mix_reads mr{};
+    mr.members = m10; mr.addrs = a10; mr.tables = t55; mr.table_sels = s5; mr.regs = r5; mr.reg_sels = s5;
+    auto mix = [&](int nl, int nt, int nr, bool dl) {
+        mr.n_list = nl; mr.n_table = nt; mr.n_regs = nr;
+        step(w, "read_mix list=" + std::to_string(nl) + " table=" + std::to_string(nt) + " regs=" + std::to_string(nr) + (dl ? "" : ", no download"),
+             [&] { return fheram_bank_read_mix(b, &mr, dl ? out : nullptr, dl ? out + 26 * fheram_ctx::GLWE : nullptr, dl ? out + 52 * fheram_ctx::GLWE : nullptr); });
+    };
+    mix(0, 1, 1, true);       // the list keeps its own home
+    mix(1, 0, 0, true);       // table and regs in mix slot 0: this one takes slot 1
+    mix(0, 0, 1, false);      // list in 1, table in 0: slot 2
+    if (nmax >= 4) mix(2, 1, 1, true);
+    step(w, "table_read [t5a] (the kind goes home)", [&] { return fheram_bank_table_read(b, t55, s5, 1, nullptr); });
+    mix(0, 1, 0, true);
+    mr.regs = r3; mr.reg_sels = s3;
+    mix(1, 0, 1, true);       // a one-digit selector: never the tail form
+    mr.regs = r5; mr.reg_sels = s5;
+    fheram_mix_prepares mp{};
+    auto rpw_mix = [&](const char* what, int nl, int nt, int nr, const int* pmem, const fheram_addr* const* paddr, int np, fheram_regs* pr, const fheram_selector* ps) {
+        mr.n_list = nl; mr.n_table = nt; mr.n_regs = nr;
+        mp.members = pmem; mp.addrs = paddr; mp.n_list = np; mp.regs = pr; mp.reg_sel = ps;
+        step(w, std::string("read_prepare_write_mix ") + what, [&] {
+            const size_t G = fheram_ctx::GLWE;
+            return fheram_bank_read_prepare_write_mix(b, &mr, &mp, out, out + 26 * G, out + 52 * G, out + 78 * G, out + 104 * G);
+        });
+    };
+    rpw_mix("table=1 | prepare [1] in place, r5", 0, 1, 0, m1, w.a + 1, 1, r5, s5a);
+    step(w, "write_list [1]", [&] { return fheram_bank_write_list(b, m1, w.a + 1, 1, hw); });
+    step(w, "regs_write r5 <- select0" + regs_state(r5), [&] { return fheram_bank_regs_write(b, r5, s5a, Src{FHERAM_SRC_SELECT_RESULT, 0}, nullptr); });
+    rpw_mix("no reads | prepare [1, 0] dense (the fourth result buffer)", 0, 0, 0, m10, a10, 2, nullptr, nullptr);
+    step(w, "write_list [1, 0]", [&] { return fheram_bank_write_list(b, m10, a10, 2, hw); });
+    rpw_mix("list=1 (member 1) | prepare [1] (the packed row moves out of the way), r3", 1, 0, 0, m1, w.a + 1, 1, r3, s3b);
+    step(w, "write_list [1]", [&] { return fheram_bank_write_list(b, m1, w.a + 1, 1, hw); });
+    step(w, "regs_write r3 <- peek0" + regs_state(r3), [&] { return fheram_bank_regs_write(b, r3, s3b, Src{FHERAM_SRC_PEEK_RESULT, 0}, nullptr); });
+    // ---- peek and poke ----
+    const Src poke_srcs[] = {{FHERAM_SRC_HOST, 3}, {FHERAM_SRC_PEEK_RESULT, 0}, {FHERAM_SRC_HOST, 1}, {FHERAM_SRC_HOST, 3}};
+    step(w, "poke [(0, 5) <- host3, (1, 2^(lg-1)) <- peek0]: the peek's outputs flip", [&] { return fheram_bank_poke(b, pm, pa, 2, poke_srcs, hw); });
+    step(w, "poke x" + std::to_string(nmax) + " (the stage still busy)", [&] { return fheram_bank_poke(b, pm, pa, nmax, poke_srcs, hw); });
+    step(w, "peek x1, no download", [&] { return fheram_bank_peek(b, pm + 1, pa + 1, 1, nullptr); });
+    std::vector<uint8_t> image((size_t)N * ws, 9);
+    step(w, "ram_load_plain member 0, row 0", [&] { return fheram_bank_ram_load_plain(b, 0, 0, 1, image.data(), image.size()); });
+    step(w, "regs_load_plain r3", [&] { return fheram_bank_regs_load_plain(b, r3, bytes.data(), (size_t)8 * ws); });
+    (void)m0;
+    fheram_regs_destroy(r3);
+    ll::line("  regs_destroy r3 -> regs_old=" + ll::ptr_name(shim_regs_old(b)));
+    fheram_regs_destroy(r5);
+    ll::line("  regs_destroy r5 (the owner of the last read_prepare_write) -> regs_old=" + ll::ptr_name(shim_regs_old(b)));
+    for (fheram_table* t : {t5a, t5b, t7}) fheram_table_destroy(t);
+    for (fheram_selector* s : {s3a, s3b, s5a, s5b, w7}) fheram_selector_destroy(s);
+    free_onerow(w);
+}
+
+// the refusals of those operations' checks: one line per case as in path mode.  Bank of two, word size 2, 2^13; `fresh`: nothing has run on it
+void run_onerow_refusals(unsigned* host_words) {
+    std::puts("# refusals: bank of two, word_size 2, 2^13; <case> -> <code> \"<message>\" rearm=<mid re-arm count>");
+    OneRow w = make_onerow(host_words, 13, 2, PATH_SETTINGS[0]), o = make_onerow(host_words, 13, 2, PATH_SETTINGS[0]);
+    fheram_bank *b = w.b, *ob = o.b;
+    fheram_ctx* c = w.c;
+    const int64_t *hw = w.words.data(), *bad = w.bad_words.data();
+    int64_t* out = w.out.data();
+    ll::verbose = false;
+    fheram_selector *s3 = new_selector(w, 3, 0), *s3b = new_selector(w, 3, 3), *s5 = new_selector(w, 5, 6), *w7 = new_selector(w, 7, 16, true), *foreign = new_selector(o, 3, 0), *empty = nullptr, *f3 = nullptr, *fresh_sel = nullptr;
+    fheram_bank_selector_alloc(b, 3, &empty);
+    const int widths[] = {1, 1, 1}, first_bits[] = {0, 1, 2};
+    fheram_bank_selector_alloc_fields(b, widths, 3, &f3);
+    const fheram_fheuint* fus3[] = {w.fu, w.fu, w.fu};
+    fheram_bank_selector_derive_fields(b, f3, fus3, first_bits);
+    fheram_regs *r3 = nullptr, *r3_new = nullptr, *o_regs = nullptr;
+    fheram_table *t3 = nullptr, *t5 = nullptr, *t_new = nullptr, *o_tab = nullptr;
+    fheram_bank_regs_create(b, 3, &r3); fheram_bank_regs_create(b, 3, &r3_new); fheram_bank_regs_create(ob, 3, &o_regs);
+    fheram_bank_table_create(b, 3, &t3); fheram_bank_table_create(b, 5, &t5); fheram_bank_table_create(b, 3, &t_new); fheram_bank_table_create(ob, 3, &o_tab);
+    ll::verbose = true;
+    const int one[] = {1, 1, 1, 1, 1, 1, 1, 1, 1};
+    const std::vector<std::pair<const char*, const fheram_selector*>> bad_sels = {{"null", nullptr}, {"foreign", foreign}, {"empty", empty}, {"of 5 bits", s5}, {"of three fields", f3}};
+    const fheram_selector* sels[9] = {s3, s3b, s3, s3b, s3, s3b, s3, s3b, s3};
+    auto sel_with = [&](const fheram_selector* s) { static const fheram_selector* v[2]; v[0] = s3; v[1] = s; return v; };
+    auto refuse_src = [&](const std::string& what, fheram_bank* bk, Src s, const int64_t* host) {
+        refuse(b, "select " + what, [&] { return fheram_bank_select(bk, sels, one, 1, &s, host, nullptr); });
+    };
+    // 1. nothing has run: the five _result downloads and every kind a source may name
+    refuse(b, "read_list_result null bank", [&] { return fheram_bank_read_list_result(nullptr, 0, 1, out); });
+    refuse(b, "read_list_result null output", [&] { return fheram_bank_read_list_result(b, 0, 1, nullptr); });
+    refuse(b, "read_list_result none has run", [&] { return fheram_bank_read_list_result(b, 0, 1, out); });
+    refuse(b, "select_result null output", [&] { return fheram_bank_select_result(b, 0, 1, nullptr); });
+    refuse(b, "select_result none has run", [&] { return fheram_bank_select_result(b, 0, 1, out); });
+    refuse(b, "regs_result null output", [&] { return fheram_bank_regs_result(b, 0, 1, nullptr); });
+    refuse(b, "regs_result none has run", [&] { return fheram_bank_regs_result(b, 0, 1, out); });
+    refuse(b, "regs_old_result none has run", [&] { return fheram_bank_regs_old_result(b, out); });
+    refuse(b, "table_result null output", [&] { return fheram_bank_table_result(b, 0, 1, nullptr); });
+    refuse(b, "table_result none has run", [&] { return fheram_bank_table_result(b, 0, 1, out); });
+    refuse(b, "peek_result null output", [&] { return fheram_bank_peek_result(b, 0, 1, nullptr); });
+    refuse(b, "peek_result none has run", [&] { return fheram_bank_peek_result(b, 0, 1, out); });
+    for (int kind : std::initializer_list<int>{FHERAM_SRC_LIST_RESULT, FHERAM_SRC_SELECT_RESULT, FHERAM_SRC_REGS_RESULT, FHERAM_SRC_REGS_OLD, FHERAM_SRC_TABLE_RESULT, FHERAM_SRC_PEEK_RESULT})
+        refuse_src("source kind " + std::to_string(kind) + ", none has run", b, Src{kind, 0}, nullptr);
+    refuse_src("member 0 has no result", b, Src{FHERAM_SRC_MEMBER_RESULT, 0}, nullptr);
+    // 2. everything has run once (quietly): list of 2, select of 2, register read of 3, table read of 2, peek of 2, a register read_prepare_write
+    ll::verbose = false;
+    {
+        const int m10[] = {1, 1};   // member 0 stays without a result
+        const fheram_addr* a10[] = {w.a[1], w.a[0]};
+        const Src z[] = {{FHERAM_SRC_ZERO, 0}, {FHERAM_SRC_ZERO, 0}};
+        const fheram_table* tt[] = {t3, t3};
+        const uint64_t pa[] = {1, 2};
+        std::vector<uint8_t> bytes(64, 1);
+        fheram_bank_read(b, 1, 1, w.a, nullptr);
+        fheram_bank_read_list(b, m10, a10, 2, nullptr);
+        fheram_bank_select(b, sels, one, 2, z, nullptr, nullptr);
+        fheram_bank_regs_pack(b, r3, 1, z, nullptr);
+        fheram_bank_regs_read(b, r3, sels, 3, nullptr);
+        fheram_bank_regs_read_prepare_write(b, r3, s3, nullptr);
+        fheram_bank_table_load_plain(b, t3, bytes.data(), 16);
+        fheram_bank_table_load_plain(b, t5, bytes.data(), 64);
+        fheram_bank_table_read(b, tt, sels, 2, nullptr);
+        fheram_bank_peek(b, m10, pa, 2, nullptr);
+        (void)ll::take_events();
+    }
+    ll::verbose = true;
+    for (int kind = 0; kind < 5; kind++) {
+        auto result = [&](int first, int n) {
+            switch (kind) {
+            case 0: return fheram_bank_read_list_result(b, first, n, out);
+            case 1: return fheram_bank_select_result(b, first, n, out);
+            case 2: return fheram_bank_regs_result(b, first, n, out);
+            case 3: return fheram_bank_table_result(b, first, n, out);
+            default: return fheram_bank_peek_result(b, first, n, out);
+            }
+        };
+        const std::string k = std::string(KIND_NAMES[kind]) + " result ";
+        refuse(b, k + "first=-1", [&] { return result(-1, 1); });
+        refuse(b, k + "n=0", [&] { return result(0, 0); });
+        refuse(b, k + "[1, 4)", [&] { return result(1, 3); });
+        refuse(b, k + "[3, 4)", [&] { return result(3, 1); });
+    }
+    // the select's own arguments and selectors
+    refuse(b, "select null bank", [&] { return fheram_bank_select(nullptr, sels, one, 1, nullptr, nullptr, nullptr); });
+    refuse(b, "select null sources", [&] { return fheram_bank_select(b, sels, one, 1, nullptr, nullptr, nullptr); });
+    const Src zero9[9] = {};
+    refuse(b, "select n=0", [&] { return fheram_bank_select(b, sels, one, 0, zero9, nullptr, nullptr); });
+    refuse(b, "select n=9", [&] { return fheram_bank_select(b, sels, one, 9, zero9, nullptr, nullptr); });
+    b->mws = 13;
+    refuse(b, "select n * word_size = 65", [&] { return fheram_bank_select(b, sels, one, 5, zero9, nullptr, nullptr); });
+    b->mws = 2;
+    refuse(b, "select selector 1 null", [&] { return fheram_bank_select(b, sel_with(nullptr), one, 2, zero9, nullptr, nullptr); });
+    refuse(b, "select selector 1 foreign", [&] { return fheram_bank_select(b, sel_with(foreign), one, 2, zero9, nullptr, nullptr); });
+    refuse(b, "select selector 1 empty", [&] { return fheram_bank_select(b, sel_with(empty), one, 2, zero9, nullptr, nullptr); });
+    refuse(b, "select selector 1 wide", [&] { return fheram_bank_select(b, sel_with(w7), one, 2, zero9, nullptr, nullptr); });
+    refuse(b, "select selector 1 of 5 bits", [&] { return fheram_bank_select(b, sel_with(s5), one, 2, zero9, nullptr, nullptr); });
+    refuse(b, "select selector 1 of three fields", [&] { return fheram_bank_select(b, sel_with(f3), one, 2, zero9, nullptr, nullptr); });
+    const int none[] = {0}, nine[] = {9};
+    refuse(b, "select 0 candidates", [&] { return fheram_bank_select(b, sels, none, 1, zero9, nullptr, nullptr); });
+    refuse(b, "select 9 candidates of 8", [&] { return fheram_bank_select(b, sels, nine, 1, zero9, nullptr, nullptr); });
+    // every kind and index of a source
+    refuse_src("host, null host_words", b, Src{FHERAM_SRC_HOST, 0}, nullptr);
+    refuse_src("host slot -1", b, Src{FHERAM_SRC_HOST, -1}, hw);
+    refuse_src("host slot 256", b, Src{FHERAM_SRC_HOST, 256}, hw);
+    refuse_src("member -1", b, Src{FHERAM_SRC_MEMBER_RESULT, -1}, hw);
+    refuse_src("member 2", b, Src{FHERAM_SRC_MEMBER_RESULT, 2}, hw);
+    refuse_src("member 0 has no result", b, Src{FHERAM_SRC_MEMBER_RESULT, 0}, hw);
+    for (int kind : std::initializer_list<int>{FHERAM_SRC_LIST_RESULT, FHERAM_SRC_SELECT_RESULT, FHERAM_SRC_REGS_RESULT, FHERAM_SRC_TABLE_RESULT, FHERAM_SRC_PEEK_RESULT}) {
+        refuse_src("kind " + std::to_string(kind) + " index -1", b, Src{kind, -1}, hw);
+        refuse_src("kind " + std::to_string(kind) + " index 2", b, Src{kind, 2}, hw);
+        refuse_src("kind " + std::to_string(kind) + " index 3", b, Src{kind, 3}, hw);
+    }
+    refuse_src("regs_old index 1", b, Src{FHERAM_SRC_REGS_OLD, 1}, hw);
+    for (int kind : {7, 9, 11, -1}) refuse_src("unknown kind " + std::to_string(kind), b, Src{kind, 0}, hw);
+    c->keys_loaded = false;
+    refuse_src("no keys", b, Src{FHERAM_SRC_ZERO, 0}, hw);
+    c->keys_loaded = true;
+    refuse_src("host slot 1 out of range", b, Src{FHERAM_SRC_HOST, 1}, bad);
+    refuse_src("host slot 0 accepted", b, Src{FHERAM_SRC_HOST, 0}, bad);
+    // lanes
+    {
+        fheram_select_lane l2[2] = {{FHERAM_SRC_HOST, 0, 0, 0}, {FHERAM_SRC_HOST, 0, 1, 0}};
+        auto lanes = [&](const std::string& what, fheram_select_lane l1, const int64_t* host) {
+            l2[1] = l1;
+            refuse(b, "select_lanes " + what, [&] { return fheram_bank_select_lanes(b, sels, one, 1, l2, host, nullptr); });
+        };
+        refuse(b, "select_lanes null lanes", [&] { return fheram_bank_select_lanes(b, sels, one, 1, nullptr, hw, nullptr); });
+        refuse(b, "select_lanes n=9", [&] { return fheram_bank_select_lanes(b, sels, one, 9, l2, hw, nullptr); });
+        lanes("lane 1 host, null host_words", {FHERAM_SRC_HOST, 0, 1, 0}, nullptr);
+        lanes("lane 1 list index 2", {FHERAM_SRC_LIST_RESULT, 2, 0, 0}, hw);
+        lanes("lane 1 unknown kind", {7, 0, 0, 0}, hw);
+        lanes("lane 1 reserved = 1", {FHERAM_SRC_HOST, 0, 1, 1}, hw);
+        lanes("lane 1 names lane 2", {FHERAM_SRC_HOST, 0, 2, 0}, hw);
+        lanes("lane 1 names lane -1", {FHERAM_SRC_LIST_RESULT, 0, -1, 0}, hw);
+        lanes("lane 1 member 0 has no result", {FHERAM_SRC_MEMBER_RESULT, 0, 0, 0}, hw);
+        lanes("lane 1 host slot 1 lane 0 out of range", {FHERAM_SRC_HOST, 1, 0, 0}, bad);
+        lanes("lane 1 host slot 1 lane 1 accepted", {FHERAM_SRC_HOST, 1, 1, 0}, bad);
+        c->keys_loaded = false;
+        lanes("no keys", {FHERAM_SRC_ZERO, 0, 0, 0}, hw);
+        c->keys_loaded = true;
+    }
+    refuse(b, "write_list_selected pick 2 of 1", [&] { const int m[] = {0}, p[] = {2}; return fheram_bank_write_list_selected(b, m, w.a, 1, p); });
+    // the register file: handle, selectors, sources (a register file takes host slots [0, 32), and a pack needs no keys), state
+    const Src h0{FHERAM_SRC_HOST, 0};
+    refuse(b, "regs_pack null handle", [&] { return fheram_bank_regs_pack(b, nullptr, 1, &h0, hw); });
+    refuse(b, "regs_pack foreign handle", [&] { return fheram_bank_regs_pack(b, o_regs, 1, &h0, hw); });
+    refuse(b, "regs_pack null sources", [&] { return fheram_bank_regs_pack(b, r3_new, 1, nullptr, hw); });
+    refuse(b, "regs_pack 0 candidates", [&] { return fheram_bank_regs_pack(b, r3_new, 0, &h0, hw); });
+    refuse(b, "regs_pack 9 candidates of 8", [&] { return fheram_bank_regs_pack(b, r3_new, 9, &h0, hw); });
+    auto pack_src = [&](const std::string& what, Src s, const int64_t* host) { refuse(b, "regs_pack " + what, [&] { return fheram_bank_regs_pack(b, r3_new, 1, &s, host); }); };
+    pack_src("host, null host_words", h0, nullptr);
+    pack_src("host slot 32", Src{FHERAM_SRC_HOST, 32}, hw);
+    pack_src("host slot 256", Src{FHERAM_SRC_HOST, 256}, hw);
+    pack_src("list index 2", Src{FHERAM_SRC_LIST_RESULT, 2}, hw);
+    pack_src("member 0 has no result", Src{FHERAM_SRC_MEMBER_RESULT, 0}, hw);
+    pack_src("host slot 1 out of range", Src{FHERAM_SRC_HOST, 1}, bad);
+    refuse(b, "regs_pack on the pending register file", [&] { return fheram_bank_regs_pack(b, r3, 1, &h0, hw); });
+    refuse(ob, "regs_pack a fresh bank's select result", [&] { const Src s{FHERAM_SRC_SELECT_RESULT, 0}; return fheram_bank_regs_pack(ob, o_regs, 1, &s, hw); });
+    c->keys_loaded = false;
+    pack_src("host slot 0 without keys, accepted", h0, hw);
+    c->keys_loaded = true;
+    refuse(b, "regs_read null handle", [&] { return fheram_bank_regs_read(b, nullptr, sels, 1, nullptr); });
+    refuse(b, "regs_read null selectors", [&] { return fheram_bank_regs_read(b, r3_new, nullptr, 1, nullptr); });
+    refuse(b, "regs_read n=0", [&] { return fheram_bank_regs_read(b, r3_new, sels, 0, nullptr); });
+    refuse(b, "regs_read n=9", [&] { return fheram_bank_regs_read(b, r3_new, sels, 9, nullptr); });
+    b->mws = 13;
+    refuse(b, "regs_read n * word_size = 65", [&] { return fheram_bank_regs_read(b, r3_new, sels, 5, nullptr); });
+    b->mws = 2;
+    for (const auto& ns : bad_sels) {
+        const char* name = ns.first; const fheram_selector* s = ns.second;
+        refuse(b, std::string("regs_read selector 1 ") + name, [&] { return fheram_bank_regs_read(b, r3_new, sel_with(s), 2, nullptr); });
+        if (s != f3) refuse(b, std::string("regs_read_prepare_write selector ") + name, [&] { return fheram_bank_regs_read_prepare_write(b, r3_new, s, nullptr); });
+        if (s != f3) refuse(b, std::string("regs_write selector ") + name, [&] { return fheram_bank_regs_write(b, r3, s, h0, hw); });
+    }
+    refuse(b, "regs_read the pending register file", [&] { return fheram_bank_regs_read(b, r3, sels, 1, nullptr); });
+    refuse(b, "regs_read_prepare_write the pending register file", [&] { return fheram_bank_regs_read_prepare_write(b, r3, s3, nullptr); });
+    refuse(b, "regs_write a register file that is not pending", [&] { return fheram_bank_regs_write(b, r3_new, s3, h0, hw); });
+    refuse(b, "regs_write host slot 32", [&] { return fheram_bank_regs_write(b, r3, s3, Src{FHERAM_SRC_HOST, 32}, hw); });
+    refuse(b, "regs_write table index 2", [&] { return fheram_bank_regs_write(b, r3, s3, Src{FHERAM_SRC_TABLE_RESULT, 2}, hw); });
+    refuse(b, "regs_write host slot 1 out of range", [&] { return fheram_bank_regs_write(b, r3, s3, Src{FHERAM_SRC_HOST, 1}, bad); });
+    c->keys_loaded = false;
+    refuse(b, "regs_write no keys", [&] { return fheram_bank_regs_write(b, r3, s3, h0, hw); });
+    refuse(b, "regs_read no keys", [&] { return fheram_bank_regs_read(b, r3_new, sels, 1, nullptr); });
+    c->keys_loaded = true;
+    r3_new->initialized = false;
+    refuse(b, "regs_read uninitialised", [&] { return fheram_bank_regs_read(b, r3_new, sels, 1, nullptr); });
+    refuse(b, "regs_download uninitialised", [&] { return fheram_bank_regs_download(b, r3_new, out); });
+    refuse(b, "regs_download null handle", [&] { return fheram_bank_regs_download(b, nullptr, out); });
+    refuse(b, "regs_download null row", [&] { return fheram_bank_regs_download(b, r3_new, nullptr); });
+    refuse(b, "regs_upload foreign handle", [&] { return fheram_bank_regs_upload(b, o_regs, hw); });
+    refuse(b, "regs_upload null row", [&] { return fheram_bank_regs_upload(b, r3_new, nullptr); });
+    // the tables
+    const fheram_table* t33[] = {t3, t3};
+    auto tab_with = [&](const fheram_table* t) { static const fheram_table* v[2]; v[0] = t3; v[1] = t; return v; };
+    refuse(b, "table_read null tables", [&] { return fheram_bank_table_read(b, nullptr, sels, 1, nullptr); });
+    refuse(b, "table_read null selectors", [&] { return fheram_bank_table_read(b, t33, nullptr, 1, nullptr); });
+    refuse(b, "table_read n=0", [&] { return fheram_bank_table_read(b, t33, sels, 0, nullptr); });
+    refuse(b, "table_read n=9", [&] { return fheram_bank_table_read(b, t33, sels, 9, nullptr); });
+    refuse(b, "table_read table 1 null", [&] { return fheram_bank_table_read(b, tab_with(nullptr), sels, 2, nullptr); });
+    refuse(b, "table_read table 1 foreign", [&] { return fheram_bank_table_read(b, tab_with(o_tab), sels, 2, nullptr); });
+    refuse(b, "table_read table 1 uninitialised", [&] { return fheram_bank_table_read(b, tab_with(t_new), sels, 2, nullptr); });
+    for (const auto& ns : bad_sels)
+        refuse(b, std::string("table_read selector 1 ") + ns.first, [&] { return fheram_bank_table_read(b, t33, sel_with(ns.second), 2, nullptr); });
+    refuse(b, "table_read [t3, t5] with selectors of 1 and 2 digits", [&] { return fheram_bank_table_read(b, tab_with(t5), sel_with(s5), 2, nullptr); });
+    c->keys_loaded = false;
+    refuse(b, "table_read no keys", [&] { return fheram_bank_table_read(b, t33, sels, 1, nullptr); });
+    c->keys_loaded = true;
+    refuse(b, "table_download uninitialised", [&] { return fheram_bank_table_download(b, t_new, out); });
+    refuse(b, "table_download null handle", [&] { return fheram_bank_table_download(b, nullptr, out); });
+    refuse(b, "table_download null row", [&] { return fheram_bank_table_download(b, t3, nullptr); });
+    refuse(b, "table_upload foreign handle", [&] { return fheram_bank_table_upload(b, o_tab, hw); });
+    refuse(b, "table_upload null row", [&] { return fheram_bank_table_upload(b, t3, nullptr); });
+    // the mixes: each group with the rules of its single call
+    {
+        const int m10[] = {1, 0}, m12[] = {1, 2};
+        const fheram_addr* a10[] = {w.a[1], w.a[0]};
+        fheram_mix_reads mr{};
+        auto mix = [&](const std::string& what) { refuse(b, "read_mix " + what, [&] { return fheram_bank_read_mix(b, &mr, nullptr, nullptr, nullptr); }); };
+        auto reset = [&] { mr = fheram_mix_reads{}; mr.members = m10; mr.addrs = a10; mr.tables = t33; mr.table_sels = sels; mr.regs = r3_new; mr.reg_sels = sels; };
+        r3_new->initialized = true;
+        reset(); mix("all groups empty");
+        reset(); mr.n_table = 5; mr.n_regs = 4; mix("9 entries");
+        reset(); mr.n_list = 1; mr.members = nullptr; mix("null member list");
+        reset(); mr.n_list = 2; mr.members = m12; mix("list member 2");
+        reset(); mr.n_table = 1; mr.tables = nullptr; mix("null table list");
+        reset(); mr.n_table = 2; mr.tables = tab_with(nullptr); mix("table 1 null");
+        reset(); mr.n_table = 2; mr.tables = tab_with(t_new); mix("table 1 uninitialised");
+        for (const auto& ns : bad_sels) {
+        const char* name = ns.first; const fheram_selector* s = ns.second;
+            reset(); mr.n_table = 2; mr.table_sels = sel_with(s); mix(std::string("table selector 1 ") + name);
+            reset(); mr.n_regs = 2; mr.reg_sels = sel_with(s); mix(std::string("register selector 1 ") + name);
+        }
+        reset(); mr.n_regs = 1; mr.regs = nullptr; mix("null register file");
+        reset(); mr.n_regs = 1; mr.regs = o_regs; mix("foreign register file");
+        reset(); mr.n_regs = 1; mr.reg_sels = nullptr; mix("null register selectors");
+        reset(); mr.n_regs = 1; mr.regs = r3; mix("the pending register file");
+        r3_new->initialized = false;
+        reset(); mr.n_regs = 1; mix("uninitialised register file");
+        r3_new->initialized = true;
+        c->keys_loaded = false;
+        reset(); mr.n_table = 1; mix("no keys");
+        c->keys_loaded = true;
+        fheram_mix_prepares mp{};
+        auto rpw = [&](const std::string& what) { refuse(b, "read_prepare_write_mix " + what, [&] { return fheram_bank_read_prepare_write_mix(b, &mr, &mp, nullptr, nullptr, nullptr, nullptr, nullptr); }); };
+        reset(); rpw("no preparation");
+        reset(); mp.regs = r3; mp.reg_sel = s3; rpw("the pending register file");
+        mp.regs = r3_new; mp.reg_sel = empty; rpw("empty selector");
+        mp.reg_sel = s5; rpw("selector of 5 bits");
+        mp.regs = o_regs; mp.reg_sel = s3; rpw("foreign register file");
+        mp.regs = r3_new; mr.n_table = 2; mr.table_sels = sel_with(empty); rpw("table selector 1 empty");
+        r3_new->initialized = false;
+    }
+    // the poke's sources (host slots [0, 16))
+    {
+        const int m[] = {1, 1};
+        const uint64_t pa[] = {3, 4};
+        auto poke = [&](const std::string& what, Src s, const int64_t* host) {
+            const Src two[] = {{FHERAM_SRC_ZERO, 0}, s};
+            refuse(b, "poke " + what, [&] { return fheram_bank_poke(b, m, pa, 2, two, host); });
+        };
+        refuse(b, "poke null sources", [&] { return fheram_bank_poke(b, m, pa, 2, nullptr, hw); });
+        poke("source 1 host, null host_words", h0, nullptr);
+        poke("source 1 host slot 16", Src{FHERAM_SRC_HOST, 16}, hw);
+        poke("source 1 host slot 256", Src{FHERAM_SRC_HOST, 256}, hw);
+        poke("source 1 peek index 2", Src{FHERAM_SRC_PEEK_RESULT, 2}, hw);
+        poke("source 1 unknown kind", Src{7, 0}, hw);
+        poke("source 1 member 0 has no result", Src{FHERAM_SRC_MEMBER_RESULT, 0}, hw);
+        poke("source 1 host slot 1 out of range", Src{FHERAM_SRC_HOST, 1}, bad);
+        refuse(ob, "poke a fresh bank's table result", [&] { const Src s[] = {{FHERAM_SRC_TABLE_RESULT, 0}, {FHERAM_SRC_ZERO, 0}}; return fheram_bank_poke(ob, m, pa, 2, s, hw); });
+        c->keys_loaded = false;
+        poke("no keys", h0, hw);
+        c->keys_loaded = true;
+    }
+    // the selectors' three _create entry points and the two allocation forms
+    {
+        const int64_t* digits[3] = {hw, nullptr, hw};
+        refuse(b, "selector_create null output", [&] { return fheram_bank_selector_create(b, digits, 1, 3, nullptr); });
+        refuse(b, "selector_create null ggsw", [&] { return fheram_bank_selector_create(b, nullptr, 1, 3, &fresh_sel); });
+        refuse(b, "selector_create bits=0", [&] { return fheram_bank_selector_create(b, digits, 1, 0, &fresh_sel); });
+        refuse(b, "selector_create bits=6", [&] { return fheram_bank_selector_create(b, digits, 2, 6, &fresh_sel); });
+        refuse(b, "selector_create 2 digits for 3 bits", [&] { return fheram_bank_selector_create(b, digits, 2, 3, &fresh_sel); });
+        refuse(b, "selector_create null digit 0", [&] { return fheram_bank_selector_create(b, digits + 1, 1, 3, &fresh_sel); });
+        refuse(b, "table_selector_create null ggsw", [&] { return fheram_bank_table_selector_create(b, nullptr, 1, 7, &fresh_sel); });
+        refuse(b, "table_selector_create bits=13", [&] { return fheram_bank_table_selector_create(b, digits, 1, 13, &fresh_sel); });
+        refuse(b, "table_selector_create 2 digits for 7 bits", [&] { return fheram_bank_table_selector_create(b, digits, 2, 7, &fresh_sel); });
+        refuse(b, "table_selector_create null digit 0", [&] { return fheram_bank_table_selector_create(b, digits + 1, 3, 7, &fresh_sel); });
+        const int wide_w[] = {3, 0, 3, 3, 3, 3}, long_w[] = {3, 3};
+        refuse(b, "selector_create_fields null widths", [&] { return fheram_bank_selector_create_fields(b, digits, 1, nullptr, 1, &fresh_sel); });
+        refuse(b, "selector_create_fields 0 fields", [&] { return fheram_bank_selector_create_fields(b, digits, 0, widths, 0, &fresh_sel); });
+        refuse(b, "selector_create_fields 6 fields", [&] { return fheram_bank_selector_create_fields(b, digits, 6, wide_w, 6, &fresh_sel); });
+        refuse(b, "selector_create_fields width 0", [&] { return fheram_bank_selector_create_fields(b, digits, 2, wide_w, 2, &fresh_sel); });
+        refuse(b, "selector_create_fields 6 bits", [&] { return fheram_bank_selector_create_fields(b, digits, 2, long_w, 2, &fresh_sel); });
+        refuse(b, "selector_create_fields 2 digits for 3 fields", [&] { return fheram_bank_selector_create_fields(b, digits, 2, widths, 3, &fresh_sel); });
+        refuse(b, "selector_create_fields null digit 1", [&] { return fheram_bank_selector_create_fields(b, digits, 3, widths, 3, &fresh_sel); });
+        refuse(b, "table_selector_alloc_fields 13 bits", [&] { const int v[] = {5, 5, 3}; return fheram_bank_table_selector_alloc_fields(b, v, 3, &fresh_sel); });
+        refuse(b, "selector_download empty", [&] { return fheram_bank_selector_download(b, empty, out); });
+        (void)ll::take_events();
+    }
+    ll::verbose = false;
+    for (fheram_regs* r : {r3, r3_new, o_regs}) fheram_regs_destroy(r);
+    for (fheram_table* t : {t3, t5, t_new, o_tab}) fheram_table_destroy(t);
+    for (fheram_selector* s : {s3, s3b, s5, w7, foreign, empty, f3}) fheram_selector_destroy(s);
+    free_onerow(w); free_onerow(o);
+    ll::verbose = true;
+}
+
+// the reserve log of the one-row kinds: the first create or call of each kind, a select that grows twice, and the three self-test failing
+// allocations at every nth.  One line per call, as in path mode, then what every buffer set of the bank holds.
+void run_onerow_reserves(unsigned* host_words) {
+    std::puts("# reserves: bank of two, word_size 2, 2^13; one line per call: every allocation (bytes), event, copy, free and wait in order, then the code, the message and what the bank's buffer sets hold");
+    ll::reserve_mode = true;
+    const Src z8[8] = {};
+    const int one[] = {1, 1, 1, 1}, two[] = {2, 2, 2, 2};
+    auto call = [&](OneRow& w, const std::string& what, auto&& f) {
+        ll::verbose = false;
+        w.c->err.clear();
+        const int rc = f();
+        ll::verbose = true;
+        ll::line(what + ": " + ll::take_events() + " -> " + std::to_string(rc) + " \"" + w.c->err + "\" " + shim_sets(w.b));
+    };
+    const int m10[] = {1, 0}, m1[] = {1};
+    const uint64_t pa[] = {1, 2};
+    std::vector<uint8_t> bytes(64, 1);
+    {
+        OneRow w = make_onerow(host_words, 13, 2, PATH_SETTINGS[0]);
+        fheram_bank* b = w.b;
+        const fheram_addr* a10[] = {w.a[1], w.a[0]};
+        ll::verbose = false;
+        fheram_selector *s3 = new_selector(w, 3, 0), *s5 = new_selector(w, 5, 6);
+        (void)ll::take_events();
+        const fheram_selector *s3s[] = {s3, s3, s3, s3}, *s5s[] = {s5, s5, s5, s5};
+        const Src host3[] = {{FHERAM_SRC_HOST, 0}, {FHERAM_SRC_HOST, 3}, {FHERAM_SRC_SELECT_RESULT, 0}, {FHERAM_SRC_HOST, 5}};
+        fheram_regs* r = nullptr;
+        fheram_table* t = nullptr;
+        call(w, "select x1, no host candidate", [&] { return fheram_bank_select(b, s3s, one, 1, z8, nullptr, nullptr); });
+        call(w, "select x1 again", [&] { return fheram_bank_select(b, s3s, one, 1, z8, nullptr, nullptr); });
+        call(w, "select x2 with host slots 0 and 3: grows, the last output moves", [&] { return fheram_bank_select(b, s3s, two, 2, host3, w.words.data(), nullptr); });
+        call(w, "select x4 of two digits, host slot 5: grows again", [&] { return fheram_bank_select(b, s5s, one, 4, host3, w.words.data(), nullptr); });
+        call(w, "select x1: nothing to grow", [&] { return fheram_bank_select(b, s3s, one, 1, z8, nullptr, nullptr); });
+        const fheram_select_lane l2[] = {{FHERAM_SRC_ZERO, 0, 0, 0}, {FHERAM_SRC_ZERO, 0, 0, 0}};
+        call(w, "select_lanes x1: the pointer table", [&] { return fheram_bank_select_lanes(b, s3s, one, 1, l2, nullptr, nullptr); });
+        call(w, "select_lanes x1 again", [&] { return fheram_bank_select_lanes(b, s3s, one, 1, l2, nullptr, nullptr); });
+        call(w, "regs_create: the shared set and the register file's own", [&] { return fheram_bank_regs_create(b, 3, &r); });
+        fheram_regs* r2 = nullptr;
+        call(w, "regs_create again: the register file's own", [&] { return fheram_bank_regs_create(b, 5, &r2); });
+        call(w, "table_create: the shared set and the row", [&] { return fheram_bank_table_create(b, 3, &t); });
+        fheram_table* t2 = nullptr;
+        call(w, "table_create again: the row", [&] { return fheram_bank_table_create(b, 3, &t2); });
+        call(w, "table_load_plain", [&] { return fheram_bank_table_load_plain(b, t, bytes.data(), 16); });
+        call(w, "regs_pack", [&] { return fheram_bank_regs_pack(b, r, 1, z8, nullptr); });
+        call(w, "peek: the public side", [&] { return fheram_bank_peek(b, m10, pa, 2, nullptr); });
+        call(w, "poke", [&] { return fheram_bank_poke(b, m10, pa, 2, host3, w.words.data()); });
+        fheram_mix_reads mr{};
+        const fheram_table* ts[] = {t};
+        mr.members = m10; mr.addrs = a10; mr.n_list = 2; mr.tables = ts; mr.table_sels = s3s; mr.n_table = 1; mr.regs = r; mr.reg_sels = s3s; mr.n_regs = 1;
+        call(w, "read_mix list=2 table=1 regs=1: the mix's set and the read list's", [&] { return fheram_bank_read_mix(b, &mr, nullptr, nullptr, nullptr); });
+        fheram_mix_prepares mp{};
+        mp.members = m1; mp.addrs = w.a + 1; mp.n_list = 1; mp.regs = r; mp.reg_sel = s3;
+        call(w, "read_prepare_write_mix: what the prepares add", [&] { return fheram_bank_read_prepare_write_mix(b, &mr, &mp, nullptr, nullptr, nullptr, nullptr, nullptr); });
+        call(w, "read_mix again", [&] { mr.n_list = 0; return fheram_bank_read_mix(b, &mr, nullptr, nullptr, nullptr); });
+        ll::verbose = false;
+        fheram_regs_destroy(r); fheram_regs_destroy(r2); fheram_table_destroy(t); fheram_table_destroy(t2);
+        ll::verbose = true;
+        ll::line("destroy of both register files and both tables: " + ll::take_events());
+        shim_release(b);
+        ll::line("release of the bank's sets: " + ll::take_events() + " -> " + shim_sets(b));
+        ll::verbose = false;
+        fheram_selector_destroy(s3); fheram_selector_destroy(s5);
+        free_onerow(w);
+    }
+    // the self-test's failing allocations: a fresh bank for every nth, the call that reserves, then the same call again (nth 0)
+    for (int which = 0; which < 3; which++) {
+        const char* name = which == 0 ? "fail_select_alloc" : which == 1 ? "fail_public_alloc" : "fail_list_alloc";
+        const int last = which == 0 ? 9 : which == 1 ? 7 : 12;
+        for (int nth = 1; nth <= last; nth++) {
+            OneRow w = make_onerow(host_words, 13, 2, PATH_SETTINGS[0]);
+            fheram_bank* b = w.b;
+            const fheram_addr* a10[] = {w.a[1], w.a[0]};
+            ll::verbose = false;
+            fheram_selector* s3 = new_selector(w, 3, 0);
+            (void)ll::take_events();
+            const fheram_selector* s3s[] = {s3, s3};
+            const Src host1[] = {{FHERAM_SRC_HOST, 1}, {FHERAM_SRC_SELECT_RESULT, 0}};
+            const fheram_select_lane l2[] = {{FHERAM_SRC_HOST, 1, 0, 0}, {FHERAM_SRC_HOST, 1, 1, 0}};
+            const std::string tag = std::string(name) + " " + std::to_string(nth);
+            if (which == 0) {
+                call(w, tag + ": select_lanes x1 on a fresh bank", [&] { fheram_bank_selftest_fail_select_alloc(b, nth); return fheram_bank_select_lanes(b, s3s, one, 1, l2, w.words.data(), nullptr); });
+                call(w, tag + ": select x1, disarmed", [&] { fheram_bank_selftest_fail_select_alloc(b, 0); return fheram_bank_select(b, s3s, one, 1, host1, w.words.data(), nullptr); });
+                if (nth <= 7) call(w, tag + ": select x2 grows", [&] { fheram_bank_selftest_fail_select_alloc(b, nth); return fheram_bank_select(b, s3s, two, 2, host1, w.words.data(), nullptr); });
+                call(w, tag + ": select x1 of the last select's output, disarmed", [&] { fheram_bank_selftest_fail_select_alloc(b, 0); return fheram_bank_select(b, s3s, one, 1, host1 + 1, nullptr, nullptr); });
+            } else if (which == 1) {
+                call(w, tag + ": peek on a fresh bank", [&] { fheram_bank_selftest_fail_public_alloc(b, nth); return fheram_bank_peek(b, m10, pa, 2, nullptr); });
+                call(w, tag + ": peek, disarmed", [&] { fheram_bank_selftest_fail_public_alloc(b, 0); return fheram_bank_peek(b, m10, pa, 2, nullptr); });
+            } else {
+                call(w, tag + ": read_prepare_write_list [1, 0] on a fresh bank", [&] { fheram_bank_selftest_fail_list_alloc(b, nth); return fheram_bank_read_prepare_write_list(b, m10, a10, 2, nullptr); });
+                call(w, tag + ": read_prepare_write_list [1, 0], disarmed", [&] { fheram_bank_selftest_fail_list_alloc(b, 0); return fheram_bank_read_prepare_write_list(b, m10, a10, 2, nullptr); });
+            }
+            ll::verbose = false;
+            fheram_selector_destroy(s3);
+            free_onerow(w);
+            ll::verbose = true;
+        }
+    }
+    ll::reserve_mode = false;
+}
+
+int onerow_main(long only, unsigned* host_words) {
+    ll::path_mode = true; ll::onerow_mode = true;
+    std::puts("# arenas: a32=data a33=scrA a34=scrB a35=scrC a36=scrD a37=tree a38=res a39=tmp a40=tmp2 a41=w a42=part a43=trtop; a13=prep a14=prep_inv a27,a28=the encrypted integer a56..=address digits a60=bank prep a61=bank prep_inv;");
+    std::puts("# a129.. = device allocations in order (per configuration); p<k> = pinned allocation k (real memory); events: a231.. = created with flags, in order");
+    const struct { int lg, ws; const Setting& st; } CONFIGS[] = {{12, 2, PATH_SETTINGS[0]}, {13, 2, PATH_SETTINGS[0]}, {16, 2, PATH_SETTINGS[0]}, {13, 2, PATH_SETTINGS[1]}, {14, 13, PATH_SETTINGS[0]}};
+    long id = 0;
+    for (const auto& cf : CONFIGS) {
+        if (only >= 0 && id != only) { id++; continue; }
+        ll::verbose = only >= 0;
+        ll::digest = 0xcbf29ce484222325ull; ll::lines = 0; path_ops = 0; ll::n_alloc = 0; ll::n_events = 0;
+        std::printf("config %ld: max_addr=2^%d word_size=%d bank of 2 %s\n", id, cf.lg, cf.ws, cf.st.name);
+        run_onerow(host_words, cf.lg, cf.ws, cf.st);
+        std::printf("config %ld: %" PRIu64 " operations, %" PRIu64 " lines, digest %016" PRIx64 "\n", id, path_ops, ll::lines, ll::digest);
+        id++;
+    }
+    if (only < 0) { ll::verbose = true; run_onerow_refusals(host_words); run_onerow_reserves(host_words); }
+    return 0;
+}
+
 // ---- config mode: config_in_effect of each input ------------------------------------------------------------------------------------
 struct CfgField { const char* name; int32_t fheram_config::*p; };
 #define CFG_FIELD(f) {#f, &fheram_config::f}
@@ -719,10 +1423,12 @@ int config_main() {
 
 int main(int argc, char** argv) {
     if (argc > 1 && !std::strcmp(argv[1], "config")) return config_main();
+    const bool onerow = argc > 1 && !std::strcmp(argv[1], "onerow");
     const bool path = argc > 1 && !std::strcmp(argv[1], "path");
-    const long only = argc > 1 + path ? std::atol(argv[1 + path]) : -1;
+    const long only = argc > 1 + (path || onerow) ? std::atol(argv[1 + (path || onerow)]) : -1;
     unsigned* host_words = static_cast<unsigned*>(mmap(reinterpret_cast<void*>(0x7e0000000000ull), 4096, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_FIXED_NOREPLACE, -1, 0));
     if (host_words == MAP_FAILED) { std::perror("mmap"); return 1; }
+    if (onerow) return onerow_main(only, host_words);
     if (path) return path_main(only, host_words);
     long id = 0;
     for (int cus : CUS) for (int s_evk = 4; s_evk <= 5; s_evk++) for (const Setting& st : SETTINGS)

@@ -1,11 +1,6 @@
 // tools/launch_log.hip: what this tree's csrc/ has no name for, and what it names differently from another tree.
 namespace {
 
-// bank.hpp's hooks into regs.hpp and table.hpp, which this program does not include: its banks hold no register files and no tables
-void regs_keys_changed(fheram_bank*) {}
-void regs_bank_release(fheram_bank*) {}
-void table_bank_release(fheram_bank*) {}
-
 // read_top's fuse_ep and gated ask whether the final trace over Y ciphertexts takes the tail launch (path.hpp read_top, tail_top)
 bool shim_tail_top(const fheram_ctx* c, int Y) { return chain_form(c, ChainQuery{false, LOGN, 1, Y}).form == ChainForm::Tail; }
 // an operand set for the predicates alone; own_rows: a context's (n == 1) or a bank range's, else a batch's
@@ -115,5 +110,62 @@ std::string shim_reads_holds(const ShimReadSet& L) { return shim_held(L, false);
 int shim_wl_reserve(fheram_bank* b, int n) { return dense_reserve(b->c, b->wl, n, b->mws, true, &b->wl_fail_alloc); }
 void shim_wl_free(fheram_bank* b) { dense_free(b->wl); }
 std::string shim_wl_holds(const fheram_bank* b) { return shim_held(b->wl, true) + " fail_alloc=" + std::to_string(b->wl_fail_alloc); }
+
+// ---- onerow mode: where the last operation of a kind left its outputs, the host stages, the one-row buffer sets ----------------------------
+// kind: 0 list, 1 select, 2 regs, 3 table, 4 peek.  res / h mean something only while n > 0.
+struct ShimLast { int n; const int32_t* res; const int64_t* h; int mix_slot; };
+ShimLast shim_last(const fheram_bank* b, int kind) {
+    const LastOutputs& L = b->last[kind];   // (LastKind is in this order)
+    return ShimLast{L.n, L.home.res, L.home.h, L.home.mix_slot};
+}
+const int32_t* shim_regs_old(const fheram_bank* b) { return b->regs_old; }
+const int32_t* shim_source(const fheram_bank* b, int kind, int index) { return select_source(b, fheram_select_src{kind, index}); }
+// the host stages: busy flags, and the pinned side of each (what a refused or accepted call left staged)
+std::string shim_busy(const fheram_bank* b) {
+    char buf[160];
+    std::snprintf(buf, sizeof buf, "busy sel.host=%d lanes=%d regs.host=%d tabs.data=%d pub.host=%d pub.data=%d", b->sel.host.busy, b->lanes.busy, b->regs.stage.busy,
+                  b->tabs.stage.busy, b->pub.host.busy, b->pub.data.busy);
+    return buf;
+}
+struct ShimPinned { const char* name; const void* p; size_t bytes; };
+int shim_pinned(const fheram_bank* b, ShimPinned* out) {   // up to 6
+    const size_t G4 = fheram_ctx::GLWE * sizeof(int32_t);
+    int n = 0;
+    out[n++] = ShimPinned{"sel.host", b->sel.host.h, (size_t)b->sel.host_cap * G4};
+    out[n++] = ShimPinned{"lanes", b->lanes.h, b->lanes.h ? (size_t)SELECT_LANES_CT_MAX * SELECT_CAND_MAX * sizeof(const int32_t*) : 0};
+    out[n++] = ShimPinned{"regs.host", b->regs.stage.h, b->regs.cap ? (size_t)(1 << FHERAM_SELECT_BITS_MAX) * b->mws * G4 : 0};
+    out[n++] = ShimPinned{"tabs.data", b->tabs.stage.h, b->tabs.cap ? (size_t)(1 << FHERAM_TABLE_BITS_MAX) * b->mws : 0};
+    out[n++] = ShimPinned{"pub.host", b->pub.host.h, b->pub.cap ? (size_t)PUB_MAX * b->mws * G4 : 0};
+    out[n++] = ShimPinned{"pub.data", b->pub.data.h, b->pub.cap ? (size_t)b->c->rows * N * b->mws : 0};
+    return n;
+}
+// what each buffer set holds: the capacities and the buffers, in one order for every tree
+std::string shim_sets(const fheram_bank* b) {
+    using F = std::pair<const char*, const void*>;
+    std::string s;
+    auto add = [&](const char* set, std::initializer_list<int> caps, std::initializer_list<F> f) {
+        s += std::string(s.empty() ? "" : " | ") + set + " cap=";
+        bool first = true;
+        for (int cp : caps) { s += (first ? "" : "/") + std::to_string(cp); first = false; }
+        for (const F& x : f) if (x.second) s += std::string(" ") + x.first;
+    };
+    const SelectBufs& S = b->sel;
+    add("sel", {S.cap, S.prep_cap, S.host_cap}, {{"packed", S.packed}, {"ep", S.ep}, {"tmp", S.tmp}, {"tmp2", S.tmp2}, {"res", S.res}, {"prep", S.prep}, {"h_res", S.h_res}, {"d_h_res", S.d_h_res}, {"d_host", S.host.d}, {"h_host", S.host.h}, {"ev", S.host.ev}});
+    add("lanes", {}, {{"d_tab", b->lanes.d}, {"h_tab", b->lanes.h}, {"ev", b->lanes.ev}});
+    const OneRowSet& R = b->regs;
+    add("regs", {R.cap}, {{"fan", R.fan}, {"ep", R.ep}, {"tmp", R.tmp}, {"res", R.res}, {"prep", R.prep}, {"h_res", R.h_res}, {"d_h_res", R.d_h_res}, {"d_stage", R.stage.d}, {"h_stage", R.stage.h}, {"ev", R.stage.ev}});
+    const OneRowSet& T = b->tabs;
+    add("tabs", {T.cap}, {{"fan", T.fan}, {"ep", T.ep}, {"tmp", T.tmp}, {"res", T.res}, {"prep", T.prep}, {"h_res", T.h_res}, {"d_h_res", T.d_h_res}, {"d_stage", T.stage.d}, {"h_stage", T.stage.h}, {"ev", T.stage.ev}});
+    const PublicBufs& P = b->pub;
+    add("pub", {P.cap, P.cur}, {{"fan", P.fan}, {"tmp", P.tmp}, {"res0", P.res[0]}, {"res1", P.res[1]}, {"h_res", P.h_res}, {"d_h_res", P.d_h_res}, {"d_host", P.host.d}, {"h_host", P.host.h}, {"ev_host", P.host.ev}, {"d_data", P.data.d}, {"h_data", P.data.h}, {"ev_data", P.data.ev}});
+    const MixBufs& M = b->mix;
+    add("mix", {M.cap}, {{"ep", M.ep}, {"tmp", M.tmp}, {"res0", M.res[0]}, {"res1", M.res[1]}, {"res2", M.res[2]}, {"h_res", M.h_res}, {"d_h_res", M.d_h_res}, {"own", M.own}, {"keep", M.keep}, {"prep", M.prep}});
+    return s + " | fail sel=" + std::to_string(b->sel_fail_alloc) + " pub=" + std::to_string(b->pub_fail_alloc) + " wl=" + std::to_string(b->wl_fail_alloc);
+}
+// what fheram_bank_destroy frees of the bank's own (the context is this program's)
+void shim_release(fheram_bank* b) {
+    dense_free(b->list); dense_free(b->wl); select_free(b->sel); lane_table_free(b->lanes);
+    regs_bank_release(b); table_bank_release(b); mix_bufs_free(b->mix); public_bufs_free(b->pub);
+}
 
 }  // namespace
