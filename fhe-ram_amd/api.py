@@ -188,6 +188,7 @@ _SYMBOLS = [
     ("fheram_bank_write_list_selected", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int)]),
     ("fheram_bank_selftest_fail_select_alloc", C.c_int, [C.c_void_p, C.c_int]),
     ("fheram_bank_regs_create", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    ("fheram_bank_regs_create_wide", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     ("fheram_regs_destroy", None, [C.c_void_p]),
     ("fheram_regs_bits", C.c_int, [C.c_void_p]),
     ("fheram_bank_regs_state", C.c_int, [C.c_void_p, C.c_void_p]),
@@ -215,6 +216,8 @@ _SYMBOLS = [
     ("fheram_bank_peek", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.c_int, I64P]),
     ("fheram_bank_peek_result", C.c_int, [C.c_void_p, C.c_int, C.c_int, I64P]),
     ("fheram_bank_poke", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.c_int, C.POINTER(_CSelectSrc), I64P]),
+    ("fheram_bank_regs_peek", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_int, I64P]),
+    ("fheram_bank_regs_poke", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_int, C.POINTER(_CSelectSrc), I64P]),
     ("fheram_bank_selftest_fail_public_alloc", C.c_int, [C.c_void_p, C.c_int]),
     ("fheram_bank_read_mix", C.c_int, [C.c_void_p, C.POINTER(_CMixReads), I64P, I64P, I64P]),
     ("fheram_bank_read_prepare_write_mix", C.c_int, [C.c_void_p, C.POINTER(_CMixReads), C.POINTER(_CMixPrepares), I64P, I64P, I64P, I64P, I64P]),
@@ -947,8 +950,10 @@ class Selector:
 
 class RegFile:
     """A register file of a bank (fheram_regs): a one-row RAM of 2^bits words of the bank's word_size that lives beside the members and is
-    read and written by the bank's Selectors.  Made by RamBank.regfile(bits).  load / pack make it readable; read runs several reads as
-    one operation; read_prepare_write and write are the two halves of a register write, whose word comes from any Src."""
+    read and written by the bank's Selectors.  Made by RamBank.regfile(bits), bits <= SELECT_BITS_MAX, or WIDE by RamBank.scratch(bits),
+    bits <= TABLE_BITS_MAX (up to 4096 words, addressed by RamBank.table_selector / table_selector_fields).  load / pack / load_plain /
+    encrypt_sk make it readable; read runs several reads as one operation; read_prepare_write and write are the two halves of a register
+    write, whose word comes from any Src; peek and poke read and write single words at PUBLIC indices."""
 
     def __init__(self, bank: "RamBank", handle, bits: int):
         self.bank, self._h, self.bits = bank, handle, int(bits)
@@ -992,6 +997,59 @@ class RegFile:
             raise FheRamError(1, f"invalid data: a register file of {self.bits} bits takes 2^bits * word_size = {want} bytes, got {data.size}")
         self.bank._chk(library().fheram_bank_regs_load_plain(self.bank._h, self._h, data.ctypes.data_as(C.POINTER(C.c_uint8)), data.size))
 
+    def _public_entries(self, what, indices):
+        indices = [int(i) for i in indices]
+        n = len(indices)
+        if not 1 <= n <= PEEK_MAX:
+            raise FheRamError(1, f"RegFile.{what} takes 1 to PEEK_MAX = {PEEK_MAX} indices, got {n}")
+        if n * self.bank.params.word_size() > 64:
+            raise FheRamError(1, f"RegFile.{what}: n * word_size = {n * self.bank.params.word_size()} exceeds 64")
+        for i in indices:
+            if not 0 <= i < (1 << self.bits):
+                raise FheRamError(1, f"RegFile.{what}: index {i} is outside the register file's 2^bits = {1 << self.bits} words")
+        return n, indices
+
+    def peek(self, indices, download: bool = True, keys: Optional["EvaluationKeysPrepared"] = None):
+        """len(indices) reads at PUBLIC word indices as ONE operation (fheram_bank_regs_peek); indices may repeat.  int64
+        [n][word_size][GLWE], each an encryption of [v, 0, .., 0]; download=False: no host wait (RamBank.peek_result later).  Nothing
+        changes but the bank's last peek (Src.peek(k))."""
+        n, indices = self._public_entries("peek", indices)
+        if keys is not None:
+            self.bank._use_keys(keys)
+        p = self.bank.params
+        out = np.zeros((n, p.word_size(), p.glwe_len()), dtype=np.int64) if download else None
+        self.bank._chk(library().fheram_bank_regs_peek(self.bank._h, self._h, (C.c_uint32 * n)(*indices), n, _p(out) if download else None))
+        return out
+
+    def poke(self, indices, words=None, srcs=None, keys: Optional["EvaluationKeysPrepared"] = None):
+        """len(indices) writes at distinct PUBLIC word indices as ONE operation (fheram_bank_regs_poke).  Either words: int64
+        [n][word_size][GLWE] host ciphertexts, entry k's at k — or srcs: one Src per entry, with words the host_words its Src.host(i)
+        name.  Every entry sees the row as it was before the call; the OLD words are the bank's last peek afterwards
+        (RamBank.peek_result, Src.peek(k)).  Never waits for the device."""
+        n, indices = self._public_entries("poke", indices)
+        if len(set(indices)) != n:
+            raise FheRamError(1, "the targets of a poke are distinct indices")
+        p = self.bank.params
+        if srcs is None:
+            if words is None:
+                raise FheRamError(1, "poke takes words, or srcs")
+            srcs = [Src.host(k) for k in range(n)]
+            if _i64(words).size != n * p.word_size() * p.glwe_len():
+                raise FheRamError(1, f"poke: expected {n} x {p.word_size()} GLWEs of words")
+        srcs = list(srcs)
+        if len(srcs) != n or not all(isinstance(s, Src) for s in srcs):
+            raise FheRamError(1, f"poke takes one Src per entry, got {len(srcs)} for {n} entries")
+        slots = [s.index for s in srcs if s.kind == SRC_HOST]
+        if slots and words is None:
+            raise FheRamError(1, "a host source needs words")
+        if slots and max(slots) >= PEEK_MAX:
+            raise FheRamError(1, f"a poke takes host slots [0, PEEK_MAX = {PEEK_MAX})")
+        hw = self.bank._host_words(words, slots)
+        if keys is not None:
+            self.bank._use_keys(keys)
+        arr = (_CSelectSrc * n)(*[_CSelectSrc(s.kind, s.index) for s in srcs])
+        self.bank._chk(library().fheram_bank_regs_poke(self.bank._h, self._h, (C.c_uint32 * n)(*indices), n, arr, _p(hw) if hw is not None else None))
+
     def store(self) -> np.ndarray:
         """the row, [word_size][GLWE] (fheram_bank_regs_download)"""
         out = self._row()
@@ -999,7 +1057,7 @@ class RegFile:
         return out
 
     def pack(self, sources, host_words=None):
-        """row <- the pack of RamBank.select over `sources` (a list of 1..2^bits Src), word j at coefficient j (fheram_bank_regs_pack);
+        """row <- the pack of RamBank.select over `sources` (a list of 1..min(2^bits, 32) Src), word j at coefficient j (fheram_bank_regs_pack);
         [Src.zero()] * 2**bits is the all-zero register file"""
         sources = list(sources)
         if not sources or not all(isinstance(s, Src) for s in sources):
@@ -2142,6 +2200,16 @@ class RamBank:
         self._chk(library().fheram_bank_regs_create(self._h, int(bits), C.byref(out)))
         return RegFile(self, out.value, bits)
 
+    def scratch(self, bits: int) -> RegFile:
+        """a WIDE register file of 2^bits words, 1 <= bits <= TABLE_BITS_MAX (fheram_bank_regs_create_wide): a writable one-row memory of
+        up to 4096 words.  Above SELECT_BITS_MAX bits its addresses are wide Selectors (table_selector / table_selector_fields)."""
+        bits = int(bits)
+        if not 1 <= bits <= TABLE_BITS_MAX:
+            raise FheRamError(1, f"bits = {bits} is outside [1, TABLE_BITS_MAX = {TABLE_BITS_MAX}]")
+        out = C.c_void_p()
+        self._chk(library().fheram_bank_regs_create_wide(self._h, bits, C.byref(out)))
+        return RegFile(self, out.value, bits)
+
     # -- tables (include/fheram.h: read-only one-row RAMs of up to 4096 words, read by wide selectors)
     def table(self, bits: int) -> Table:
         """a table of 2^bits words, bits <= TABLE_BITS_MAX, with every device buffer it will need (fheram_bank_table_create); Table.load /
@@ -2152,8 +2220,8 @@ class RamBank:
 
     def table_selector(self, bits: int, ggsw_digits=None) -> Selector:
         """a WIDE selector of up to TABLE_BITS_MAX bits: without digits (fheram_bank_table_selector_alloc; derive_selectors / derive_list
-        fill it), or from host std-form GGSW digits (fheram_bank_table_selector_create).  select and RegFile refuse it above
-        SELECT_BITS_MAX bits."""
+        fill it), or from host std-form GGSW digits (fheram_bank_table_selector_create).  It addresses a Table or a wide RegFile
+        (scratch) of its bits; select refuses it above SELECT_BITS_MAX bits."""
         out = C.c_void_p()
         if ggsw_digits is None:
             self._chk(library().fheram_bank_table_selector_alloc(self._h, int(bits), C.byref(out)))

@@ -14,6 +14,9 @@
 //   poke        every touched row ciphertext R <- normalize(R - sum_j glwe_rotate(+q_j, t_j) + sum_j glwe_rotate(+q_j, w_j[y])) over the
 //               entries j of that row, t_j = the peek of entry j: write_first_step's normalize(a - b + c) (ram.rs:574-576) on that one
 //               row.  The peek's gather and trace, then ONE launch (k_poke_merge).  All entries see the rows as they were before the call.
+//   regs        fheram_bank_regs_peek / _poke: the same on a register file's one row (narrow or wide, regs.hpp): word i is coefficient i of
+//               row 0 of the one-row RAM.  An entry is a PLACE (PubPlace: the row, the stride between its word ciphertexts, the
+//               coefficient), and pub_peek / pub_poke run the members' and the register file's entries alike.
 // Everything runs on the bank's main stream.  The public side's buffers (path.hpp PublicBufs) are allocated whole by the first call that
 // needs them and freed with the bank; no later operation allocates.  The outputs of the last peek or poke are the source kind
 // FHERAM_SRC_PEEK_RESULT.  There are TWO result buffers: an operation writes the one that does not hold the last outputs, so a poke
@@ -151,13 +154,38 @@ int pub_check_entries(fheram_bank* b, const int* members, const uint64_t* addrs,
             return fail(c, FHERAM_ERR_STATE, std::string("invalid call to ") + who + ": the member is between read_prepare_write and write, its rows are rotated (member " + std::to_string(members[k]) + ")");
     return FHERAM_OK;
 }
-// row r_k of word ciphertext w of members[k]
+// row r of word ciphertext w of a member
 int32_t* pub_row(const fheram_bank* b, int member, size_t r, int w) {
     const fheram_ctx* c = b->c;
     return c->d_data + (((size_t)member * b->mws + (size_t)w) * c->rows + r) * fheram_ctx::GLWE;
 }
+// where an entry of a peek or a poke sits: word ciphertext 0 of its row (word ciphertext w is w * w_stride further) and its coefficient.
+// A member's entry at address a: row a / N, coefficient a % N; a register file's entry at word i: its one row, coefficient i.
+struct PubPlace { int32_t* row0; long w_stride; int q; };
+void pub_member_places(const fheram_bank* b, const int* members, const uint64_t* addrs, int n, PubPlace* at) {
+    for (int k = 0; k < n; k++) at[k] = PubPlace{pub_row(b, members[k], (size_t)(addrs[k] / N), 0), (long)(b->c->rows * fheram_ctx::GLWE), (int)(addrs[k] % N)};
+}
+void pub_regs_places(const fheram_regs* r, const uint32_t* idx, int n, PubPlace* at) {
+    for (int k = 0; k < n; k++) at[k] = PubPlace{r->row, (long)fheram_ctx::GLWE, (int)idx[k]};
+}
+// the entries of a register file's peek or poke, in the order of pub_check_entries: n, every index, then what the register file must be
+int pub_check_regs_entries(fheram_bank* b, const fheram_regs* r, const uint32_t* idx, int n, const char* who) {
+    fheram_ctx* c = b->c;
+    if (n < 1 || n > PUB_MAX)
+        return fail(c, FHERAM_ERR_INVALID_ARG, "n = " + std::to_string(n) + " is outside [1, FHERAM_PEEK_MAX = " + std::to_string(PUB_MAX) + "]");
+    if ((long)n * b->mws > PUB_CT_MAX)
+        return fail(c, FHERAM_ERR_INVALID_ARG, "n * word_size = " + std::to_string((long)n * b->mws) + " exceeds 64, the ciphertext limit of the single-launch chains (k_chain_mid)");
+    for (int k = 0; k < n; k++)
+        if (idx[k] >= ((uint32_t)1 << r->bits))
+            return fail(c, FHERAM_ERR_INVALID_ARG, "entry " + std::to_string(k) + " names word " + std::to_string(idx[k]) + ", outside the register file's 2^bits = " + std::to_string(1 << r->bits) + " words");
+    if (!r->initialized) return fail(c, FHERAM_ERR_UNINITIALIZED, "unitialized memory: the register file has had no fheram_bank_regs_upload or fheram_bank_regs_pack");
+    if (!c->keys_loaded) return fail(c, FHERAM_ERR_KEYS, "evaluation keys not loaded");
+    if (r->state)
+        return fail(c, FHERAM_ERR_STATE, std::string("invalid call to ") + who + ": the register file is between read_prepare_write and write, its row is rotated");
+    return FHERAM_OK;
+}
 // gather + trace of the n entries into the result buffer that does not hold the last outputs; returns it (the caller makes it the last)
-int32_t* pub_peek_enqueue(fheram_bank* b, const int* members, const uint64_t* addrs, int n) {
+int32_t* pub_peek_enqueue(fheram_bank* b, const PubPlace* at, int n) {
     fheram_ctx* c = b->c;
     PublicBufs& P = b->pub;
     const int ws = b->mws, Y = n * ws;
@@ -168,8 +196,8 @@ int32_t* pub_peek_enqueue(fheram_bank* b, const int* members, const uint64_t* ad
         ga.out = P.fan;
         for (int k = 0; k < n; k++)
             for (int w = 0; w < ws; w++) {
-                ga.src[k * ws + w] = pub_row(b, members[k], (size_t)(addrs[k] / N), w);
-                ga.q[k * ws + w] = (int)(addrs[k] % N);
+                ga.src[k * ws + w] = at[k].row0 + (long)w * at[k].w_stride;
+                ga.q[k * ws + w] = at[k].q;
             }
         ProfScope ps(c, "elementwise", (uint64_t)Y);
         peek_gather_launch(Y, c->cur, ga);
@@ -181,6 +209,60 @@ void pub_peek_done(fheram_bank* b, int n) {
     PublicBufs& P = b->pub;
     P.cur ^= 1;
     b->last[LAST_PEEK] = LastOutputs{n, ResHome{P.res[P.cur], P.h_res, P.d_h_res, -1}};
+}
+// behind the checks and pub_reserve: the peek of the n entries, enqueued and exported
+int pub_peek(fheram_bank* b, const PubPlace* at, int n, int64_t* out) {
+    fheram_ctx* c = b->c;
+    // ---- enqueue ----
+    regs_begin(c);
+    const int32_t* res = pub_peek_enqueue(b, at, n);
+    HIPCHK(c, hipGetLastError());
+    pub_peek_done(b, n);
+    if (!out) return FHERAM_OK;
+    const ResRun run{res, (size_t)n * b->mws * fheram_ctx::GLWE};
+    return result_export(c, &run, 1, b->pub.h_res, b->pub.d_h_res, out);
+}
+// behind the checks and pub_reserve: the poke of the n entries (distinct places; n_host: sources_check's).  The caller voids what was kept
+// of the touched rows.
+int pub_poke(fheram_bank* b, const PubPlace* at, int n, const fheram_select_src* srcs, int n_host, const int64_t* host_words) {
+    fheram_ctx* c = b->c;
+    PublicBufs& P = b->pub;
+    const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
+    int rc = host_words_stage(b, P.host, srcs, n, n_host, host_words);
+    if (rc != FHERAM_OK) return rc;
+    // ---- enqueue ----
+    regs_begin(c);
+    rc = host_words_copy(b, P.host, srcs, n, n_host);
+    if (rc != FHERAM_OK) return rc;
+    PokeMergeArgs ma{};
+    // the words, where they sit NOW: a PEEK_RESULT source names the outputs this call's own peek is about to succeed
+    const int32_t* words[PUB_MAX];
+    for (int k = 0; k < n; k++) words[k] = select_source(b, srcs[k], P.host.dev<int32_t>());
+    const int32_t* t = pub_peek_enqueue(b, at, n);
+    // the touched rows, each with its entries side by side
+    int n_touched = 0, n_ent = 0;
+    bool placed[PUB_MAX] = {};
+    for (int k = 0; k < n; k++) {
+        if (placed[k]) continue;
+        ma.row[n_touched] = at[k].row0;
+        ma.first[n_touched++] = n_ent;
+        for (int j = k; j < n; j++) {
+            if (placed[j] || at[j].row0 != at[k].row0) continue;
+            placed[j] = true;
+            ma.t[n_ent] = t + (size_t)j * per;
+            ma.w[n_ent] = words[j];
+            ma.q[n_ent++] = at[j].q;
+        }
+    }
+    ma.first[n_touched] = n_ent;
+    ma.w_stride = at[0].w_stride;   // (one call's entries are all members' or all one register file's)
+    {
+        ProfScope ps(c, "elementwise", (uint64_t)n_touched * b->mws);
+        poke_merge_launch(n_touched, b->mws, c->cur, ma);
+    }
+    HIPCHK(c, hipGetLastError());
+    pub_peek_done(b, n);   // the OLD words, as read_prepare_write returns them
+    return FHERAM_OK;
 }
 
 }  // namespace
@@ -247,14 +329,9 @@ int fheram_bank_peek(fheram_bank* b, const int* members, const uint64_t* addrs, 
     HIPCHK(c, hipSetDevice(c->device));
     rc = pub_reserve(b);
     if (rc != FHERAM_OK) return rc;
-    // ---- enqueue ----
-    regs_begin(c);
-    const int32_t* res = pub_peek_enqueue(b, members, addrs, n);
-    HIPCHK(c, hipGetLastError());
-    pub_peek_done(b, n);
-    if (!out) return FHERAM_OK;
-    const ResRun run{res, (size_t)n * b->mws * fheram_ctx::GLWE};
-    return result_export(c, &run, 1, b->pub.h_res, b->pub.d_h_res, out);
+    PubPlace at[PUB_MAX];
+    pub_member_places(b, members, addrs, n, at);
+    return pub_peek(b, at, n, out);
 }
 int fheram_bank_selftest_fail_public_alloc(fheram_bank* b, int nth) {
     if (!b || nth < 0) return FHERAM_ERR_INVALID_ARG;
@@ -282,44 +359,57 @@ int fheram_bank_poke(fheram_bank* b, const int* members, const uint64_t* addrs, 
     HIPCHK(c, hipSetDevice(c->device));
     rc = pub_reserve(b);
     if (rc != FHERAM_OK) return rc;
-    PublicBufs& P = b->pub;
-    const size_t per = (size_t)b->mws * fheram_ctx::GLWE;
-    rc = host_words_stage(b, P.host, srcs, n, n_host, host_words);
+    PubPlace at[PUB_MAX];
+    pub_member_places(b, members, addrs, n, at);
+    rc = pub_poke(b, at, n, srcs, n_host, host_words);
     if (rc != FHERAM_OK) return rc;
-    // ---- enqueue ----
-    regs_begin(c);
-    rc = host_words_copy(b, P.host, srcs, n, n_host);
-    if (rc != FHERAM_OK) return rc;
-    PokeMergeArgs ma{};
-    // the words, where they sit NOW: a PEEK_RESULT source names the outputs this call's own peek is about to succeed
-    const int32_t* words[PUB_MAX];
-    for (int k = 0; k < n; k++) words[k] = select_source(b, srcs[k], P.host.dev<int32_t>());
-    const int32_t* t = pub_peek_enqueue(b, members, addrs, n);
-    // the touched rows, each with its entries side by side
-    int n_touched = 0, n_ent = 0;
-    bool placed[PUB_MAX] = {};
-    for (int k = 0; k < n; k++) {
-        if (placed[k]) continue;
-        const size_t r = (size_t)(addrs[k] / N);
-        ma.row[n_touched] = pub_row(b, members[k], r, 0);
-        ma.first[n_touched++] = n_ent;
-        for (int j = k; j < n; j++) {
-            if (placed[j] || members[j] != members[k] || (size_t)(addrs[j] / N) != r) continue;
-            placed[j] = true;
-            ma.t[n_ent] = t + (size_t)j * per;
-            ma.w[n_ent] = words[j];
-            ma.q[n_ent++] = (int)(addrs[j] % N);
-        }
-    }
-    ma.first[n_touched] = n_ent;
-    ma.w_stride = (long)(c->rows * fheram_ctx::GLWE);
-    {
-        ProfScope ps(c, "elementwise", (uint64_t)n_touched * b->mws);
-        poke_merge_launch(n_touched, b->mws, c->cur, ma);
-    }
-    HIPCHK(c, hipGetLastError());
-    pub_peek_done(b, n);   // the OLD words, as read_prepare_write returns them
     for (int k = 0; k < n; k++) pub_rows_changed(b, members[k]);
+    return FHERAM_OK;
+}
+// The register file's twins: word idx[k] of the one row is coefficient idx[k] of row 0 of the one-row RAM, so the same gather, trace and
+// merge run with the row's pointer — ONE touched row for a poke, whatever n is.
+int fheram_bank_regs_peek(fheram_bank* b, const fheram_regs* r, const uint32_t* idx, int n, int64_t* out) {
+    if (!b) return FHERAM_ERR_INVALID_ARG;
+    fheram_ctx* c = b->c;
+    mid_rearm(c);
+    // ---- every check before anything is enqueued: a refused call changes nothing ----
+    int rc = regs_check_handle(b, r);
+    if (rc != FHERAM_OK) return rc;
+    if (!idx) return fail(c, FHERAM_ERR_INVALID_ARG, "null index list");
+    rc = pub_check_regs_entries(b, r, idx, n, "fheram_bank_regs_peek");
+    if (rc != FHERAM_OK) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = pub_reserve(b);
+    if (rc != FHERAM_OK) return rc;
+    PubPlace at[PUB_MAX];
+    pub_regs_places(r, idx, n, at);
+    return pub_peek(b, at, n, out);
+}
+int fheram_bank_regs_poke(fheram_bank* b, fheram_regs* r, const uint32_t* idx, int n, const fheram_select_src* srcs, const int64_t* host_words) {
+    if (!b) return FHERAM_ERR_INVALID_ARG;
+    fheram_ctx* c = b->c;
+    mid_rearm(c);
+    // ---- every check before anything is enqueued: a refused call changes nothing ----
+    int rc = regs_check_handle(b, r);
+    if (rc != FHERAM_OK) return rc;
+    if (!idx || !srcs) return fail(c, FHERAM_ERR_INVALID_ARG, "null index list or null sources");
+    rc = pub_check_regs_entries(b, r, idx, n, "fheram_bank_regs_poke");
+    if (rc != FHERAM_OK) return rc;
+    for (int k = 0; k < n; k++)
+        for (int j = 0; j < k; j++)
+            if (idx[j] == idx[k])
+                return fail(c, FHERAM_ERR_INVALID_ARG, "entry " + std::to_string(k) + " names word " + std::to_string(idx[k]) + " a second time: the targets of a poke are distinct");
+    int n_host = 0;
+    rc = sources_check(b, srcs, n, host_words, PUB_MAX, "a poke takes", true, &n_host);   // the public side stages PUB_MAX host slots
+    if (rc != FHERAM_OK) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = pub_reserve(b);
+    if (rc != FHERAM_OK) return rc;
+    PubPlace at[PUB_MAX];
+    pub_regs_places(r, idx, n, at);
+    rc = pub_poke(b, at, n, srcs, n_host, host_words);
+    if (rc != FHERAM_OK) return rc;
+    r->memo = false;   // the kept trace was of the row before the poke
     return FHERAM_OK;
 }
 

@@ -1,4 +1,5 @@
-// A bank's REGISTER FILE: a one-row RAM of 2^bits words (1 <= bits <= FHERAM_SELECT_BITS_MAX) that lives beside the bank's members, under
+// A bank's REGISTER FILE: a one-row RAM of 2^bits words (1 <= bits <= FHERAM_SELECT_BITS_MAX; a WIDE one, made by
+// fheram_bank_regs_create_wide and addressed by wide selectors: <= FHERAM_TABLE_BITS_MAX) that lives beside the bank's members, under
 // the bank's keys, stream, configuration and round-off monitor.  Its addresses are the bank's selectors, its results feed the selects,
 // and it takes a written word from any source a select candidate may come from.
 //
@@ -51,14 +52,18 @@ struct fheram_regs {
     bool initialized = false, state = false;
     bool memo = false;     // tr = trace(row), left by read_prepare_write on this very row (RamState::memo_top)
     int32_t *row = nullptr, *tr = nullptr, *tmp = nullptr, *tmp2 = nullptr;   // [ws] GLWE
-    double* prep = nullptr;       // [FHERAM_SELECT_BITS_MAX] prepared GGSW: read_prepare_write's digits
-    int32_t* inv_std = nullptr;   // [FHERAM_SELECT_BITS_MAX] std-form GGSW: the write's inverse digits
-    double* inv_prep = nullptr;   // [FHERAM_SELECT_BITS_MAX] prepared GGSW: the same, prepared
+    double* prep = nullptr;       // [REGS_DIGITS_MAX] prepared GGSW: read_prepare_write's digits
+    int32_t* inv_std = nullptr;   // [REGS_DIGITS_MAX] std-form GGSW: the write's inverse digits
+    double* inv_prep = nullptr;   // [REGS_DIGITS_MAX] prepared GGSW: the same, prepared
 };
 
 namespace {
 
 static_assert(REGS_SLICES == EW_SLICES && REGS_CT_MAX == 64, "the register kernels cover a ciphertext as the elementwise kernels do; a call has at most 64 ciphertexts");
+// the digits of one selector a register file's own buffers (prep, inv_std, inv_prep) and the shared set's prepared digits hold
+constexpr int REGS_DIGITS_MAX = FHERAM_SELECT_BITS_MAX;
+static_assert(REGS_DIGITS_MAX == FHERAM_SELECTOR_WIDE_DIGITS_MAX, "a wide register file's selector has up to FHERAM_SELECTOR_WIDE_DIGITS_MAX digits: the per-object and per-bank digit buffers hold them");
+static_assert((1 << FHERAM_TABLE_BITS_MAX) == N, "a wide register file's row holds one word per coefficient");
 
 void regs_free_device(fheram_regs* r) {
     void* bufs[] = {r->row, r->tr, r->tmp, r->tmp2, r->prep, r->inv_std, r->inv_prep};
@@ -78,7 +83,7 @@ void regs_bank_release(fheram_bank* b) {
 }
 // what the register files of a bank share, whole (path.hpp OneRowSet): the stage holds the 2^FHERAM_SELECT_BITS_MAX host words of a pack or a write
 int regs_bufs_reserve(fheram_bank* b) {
-    return one_row_reserve(b->c, b->regs, b->mws, FHERAM_SELECT_BITS_MAX, (size_t)(1 << FHERAM_SELECT_BITS_MAX) * b->mws * fheram_ctx::GLWE * sizeof(int32_t), "buffers of the bank's register files");
+    return one_row_reserve(b->c, b->regs, b->mws, REGS_DIGITS_MAX, (size_t)(1 << FHERAM_SELECT_BITS_MAX) * b->mws * fheram_ctx::GLWE * sizeof(int32_t), "buffers of the bank's register files");
 }
 // the handle: null, of another bank (or of a destroyed one)
 int regs_check_handle(fheram_bank* b, const fheram_regs* r) {
@@ -138,23 +143,18 @@ void regs_begin(fheram_ctx* c) {
     c->cur = c->stream;
     c->wide = true;   // (as a select: whatever gate wave a member's read_prepare_write parked is released by that operation's own trace chain, ahead of this on the stream)
 }
-
-}  // namespace
-
-extern "C" {
-
-int fheram_bank_regs_create(fheram_bank* b, int bits, fheram_regs** out) {
-    if (!b) return FHERAM_ERR_INVALID_ARG;
+// both creators: the bound on the bits is the caller's (bits_max, by its name), everything else is one register file's
+int regs_new(fheram_bank* b, int bits, int bits_max, const char* max_name, fheram_regs** out) {
     fheram_ctx* c = b->c;
     if (!out) return fail(c, FHERAM_ERR_INVALID_ARG, "null output");
     *out = nullptr;
-    if (bits < 1 || bits > FHERAM_SELECT_BITS_MAX)
-        return fail(c, FHERAM_ERR_INVALID_ARG, "bits = " + std::to_string(bits) + " is outside [1, FHERAM_SELECT_BITS_MAX = " + std::to_string(FHERAM_SELECT_BITS_MAX) + "]");
+    if (bits < 1 || bits > bits_max)
+        return fail(c, FHERAM_ERR_INVALID_ARG, "bits = " + std::to_string(bits) + " is outside [1, " + max_name + " = " + std::to_string(bits_max) + "]");
     HIPCHK(c, hipSetDevice(c->device));
     int rc = regs_bufs_reserve(b);
     if (rc != FHERAM_OK) return rc;
     fheram_regs* r = new fheram_regs{b, c->device, bits};
-    const size_t ct = (size_t)b->mws * fheram_ctx::GLWE * sizeof(int32_t), digits = (size_t)FHERAM_SELECT_BITS_MAX * fheram_ctx::GGSW;
+    const size_t ct = (size_t)b->mws * fheram_ctx::GLWE * sizeof(int32_t), digits = (size_t)REGS_DIGITS_MAX * fheram_ctx::GGSW;
     hipError_t e = hipSuccess;
     for (int32_t** p : {&r->row, &r->tr, &r->tmp, &r->tmp2}) if (e == hipSuccess) e = hipMalloc((void**)p, ct);
     if (e == hipSuccess) e = hipMalloc((void**)&r->prep, digits * sizeof(double));
@@ -169,6 +169,18 @@ int fheram_bank_regs_create(fheram_bank* b, int bits, fheram_regs** out) {
     b->regfiles.push_back(r);
     *out = r;
     return FHERAM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fheram_bank_regs_create(fheram_bank* b, int bits, fheram_regs** out) {
+    return b ? regs_new(b, bits, FHERAM_SELECT_BITS_MAX, "FHERAM_SELECT_BITS_MAX", out) : FHERAM_ERR_INVALID_ARG;
+}
+// a WIDE register file: up to one word per coefficient of the row, addressed by wide selectors (table.hpp)
+int fheram_bank_regs_create_wide(fheram_bank* b, int bits, fheram_regs** out) {
+    return b ? regs_new(b, bits, FHERAM_TABLE_BITS_MAX, "FHERAM_TABLE_BITS_MAX", out) : FHERAM_ERR_INVALID_ARG;
 }
 // Who frees: a register file frees its own device buffers here while its bank lives; fheram_bank_destroy frees those of every register file
 // still alive and detaches them, after which this only releases the handle.  Either order is safe.
@@ -209,6 +221,8 @@ int fheram_bank_regs_pack(fheram_bank* b, fheram_regs* r, int n_cand, const fher
     if (!srcs) return fail(c, FHERAM_ERR_INVALID_ARG, "null sources");
     if (n_cand < 1 || n_cand > (1 << r->bits))
         return fail(c, FHERAM_ERR_INVALID_ARG, "the pack has " + std::to_string(n_cand) + " candidates, outside [1, 2^bits = " + std::to_string(1 << r->bits) + "]");
+    if (n_cand > SELECT_CAND_MAX)   // (a wide register file)
+        return fail(c, FHERAM_ERR_INVALID_ARG, "the pack has " + std::to_string(n_cand) + " candidates, more than the " + std::to_string(SELECT_CAND_MAX) + " the argument struct of k_select_pack holds (words behind them: fheram_bank_regs_poke)");
     int n_host = 0;
     rc = regs_check_sources(b, srcs, n_cand, host_words, false, &n_host);
     if (rc != FHERAM_OK) return rc;

@@ -728,7 +728,9 @@ public:
     static fheram_select_src src_regs_old() { return {FHERAM_SRC_REGS_OLD, 0}; }                 // the bank's last RegFile::read_prepare_write result
     class RegFile {
     public:
+        struct Wide {};   // RegFile(bank, bits, Wide{}): up to FHERAM_TABLE_BITS_MAX bits, addressed by wide selectors (Bank::scratch)
         RegFile(Bank& bank, int bits) : bank_(bank) { bank.chk(fheram_bank_regs_create(bank.bank_, bits, &h_)); }
+        RegFile(Bank& bank, int bits, Wide) : bank_(bank) { bank.chk(fheram_bank_regs_create_wide(bank.bank_, bits, &h_)); }
         ~RegFile() { if (h_) fheram_regs_destroy(h_); }
         RegFile(const RegFile&) = delete;
         int bits() const { return fheram_regs_bits(h_); }
@@ -789,11 +791,29 @@ public:
             bank_.chk(fheram_bank_regs_decrypt(bank_.bank_, h_, sk.h_, values.data(), worst));
             return values;
         }
+        // indices.size() reads at PUBLIC word indices as ONE operation (fheram_bank_regs_peek); the outputs are the bank's last peek
+        // (Bank::peek_result, src_peek); download = false: no host wait, an empty result
+        std::vector<std::vector<Glwe>> peek(const std::vector<uint32_t>& indices, bool download = true) {
+            if (indices.empty()) throw Error(FHERAM_ERR_INVALID_ARG, "peek takes at least one index");
+            std::vector<int64_t> out(download ? indices.size() * bank_.params.word_size() * bank_.glwe_len() : 0);
+            bank_.chk(fheram_bank_regs_peek(bank_.bank_, h_, indices.data(), (int)indices.size(), download ? out.data() : nullptr));
+            return download ? bank_.split(out, indices.size()) : std::vector<std::vector<Glwe>>();
+        }
+        // indices.size() writes at distinct PUBLIC word indices as ONE operation (fheram_bank_regs_poke): entry k writes the word srcs[k]
+        // names; the old words are the bank's last peek afterwards.  Never waits for the device.
+        void poke(const std::vector<uint32_t>& indices, const std::vector<fheram_select_src>& srcs, const std::vector<std::vector<Glwe>>& host_words = {}) {
+            if (indices.empty() || srcs.size() != indices.size()) throw Error(FHERAM_ERR_INVALID_ARG, "poke takes at least one index and one source per index");
+            const std::vector<int64_t> flat = bank_.flat_words(srcs, host_words);
+            bank_.chk(fheram_bank_regs_poke(bank_.bank_, h_, indices.data(), (int)indices.size(), srcs.data(), flat.empty() ? nullptr : flat.data()));
+        }
     private:
         friend class Bank;
         Bank& bank_;
         fheram_regs* h_ = nullptr;
     };
+    // a WIDE register file of 2^bits words, bits <= FHERAM_TABLE_BITS_MAX (fheram_bank_regs_create_wide): a writable one-row memory of up to
+    // 4096 words; above FHERAM_SELECT_BITS_MAX bits its addresses are wide selectors (Selector::Wide)
+    RegFile scratch(int bits) { return RegFile(*this, bits, RegFile::Wide{}); }
     // ---- a table (include/fheram.h): a READ-ONLY one-row RAM of 2^bits words, bits <= FHERAM_TABLE_BITS_MAX, beside the members and the
     // register files — an instruction ROM or a lookup table — read at wide selectors (Selector::Wide)
     static fheram_select_src src_table(int output) { return {FHERAM_SRC_TABLE_RESULT, output}; }   // output of the bank's last table_read

@@ -349,6 +349,38 @@ int main() {
                     catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 28; }
                     std::printf("bank public side: load_plain, peek, peek_result, poke: ok\n");
                 }
+                {   // Bank::scratch: a WIDE register file of 4096 words holds a public image; a peek, a poke and a write cycle at a wide selector
+                    B::RegFile ls = lists.scratch(12), ts = twin.scratch(12);
+                    if (ls.bits() != 12) return 29;
+                    std::vector<uint8_t> image(4096 * 4);
+                    for (size_t i = 0; i < image.size(); i++) image[i] = (uint8_t)(i * 41 + 3);
+                    lists.load_plain(ls, image);
+                    twin.load_plain(ts, image);
+                    const auto row = ls.store();
+                    if (!ls.peek({7, 4095}, false).empty()) return 29;
+                    if (lists.peek_result(0, 2) != ts.peek({7, 4095})) { std::printf("RegFile::peek: the two banks differ\n"); return 29; }
+                    if (ls.store() != row) { std::printf("RegFile::peek changed the row\n"); return 29; }
+                    ls.poke({7, 2048}, {B::src_host(1), B::src_zero()}, words);
+                    ts.poke({7, 2048}, {B::src_host(1), B::src_zero()}, words);
+                    if (ls.store() != ts.store() || ls.store() == row) { std::printf("RegFile::poke: the two banks differ\n"); return 29; }
+                    const std::vector<int64_t> ipc = synth(14 * 4 * 2 * 5 * 2 * n);
+                    B::FheUintPrepared lpc(lists, ipc, 14), tpc(twin, ipc, 14);
+                    B::Selector lw(lists, B::Selector::Wide{}, 12), tw(twin, B::Selector::Wide{}, 12);
+                    lists.derive_list({B::derive_selector(lpc, lw, 2)});
+                    twin.derive_list({B::derive_selector(tpc, tw, 2)});
+                    if (ls.read({&lw}) != ts.read({&tw})) { std::printf("wide RegFile::read: the two banks differ\n"); return 29; }
+                    if (ls.read_prepare_write(lw) != ts.read_prepare_write(tw) || !ls.state()) { std::printf("wide RegFile::read_prepare_write: the two banks differ\n"); return 29; }
+                    ls.write(lw, B::src_host(0), words);
+                    ts.write(tw, B::src_host(0), words);
+                    if (ls.state() || ls.store() != ts.store()) { std::printf("wide RegFile::write: the two banks differ\n"); return 29; }
+                    try { B::RegFile six(lists, 6); return 30; }   // fheram_bank_regs_create keeps its bound
+                    catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 30; }
+                    try { ls.poke({7, 7}, {B::src_zero(), B::src_zero()}); return 30; }   // one target twice
+                    catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 30; }
+                    try { ls.peek({4096}); return 30; }   // an index outside the register file
+                    catch (const fheram::Error& e) { if (e.code != FHERAM_ERR_INVALID_ARG) return 30; }
+                    std::printf("bank scratch: wide RegFile peek, poke, read, read_prepare_write, write: ok\n");
+                }
             }
         }
     } catch (const fheram::Error& e) {

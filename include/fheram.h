@@ -664,6 +664,15 @@ typedef struct fheram_regs fheram_regs;
  * buffers of every register file still alive and detaches it; such a handle is then good for fheram_regs_destroy only, which releases
  * it.  Either order is safe.  Destroying the register file whose read_prepare_write was the bank's last voids FHERAM_SRC_REGS_OLD. */
 int fheram_bank_regs_create(fheram_bank* bank, int bits, fheram_regs** out);
+/* A WIDE register file: the same object with 1 <= bits <= FHERAM_TABLE_BITS_MAX, so up to 4096 words — a stack, a CSR
+ * block, a scratch buffer or the data memory of a small program beside members of any shape.  It is the one-row RAM of max_addr =
+ * 2^bits and every call below takes it unchanged; with bits > FHERAM_SELECT_BITS_MAX its addresses are WIDE selectors
+ * (fheram_bank_table_selector_alloc / _create / _alloc_fields, up to FHERAM_SELECTOR_WIDE_DIGITS_MAX digits) under the same rule:
+ * the selector's bits equal the register file's.  The buffers are those of fheram_bank_regs_create (the digit buffers hold
+ * FHERAM_SELECTOR_WIDE_DIGITS_MAX digits either way).  fheram_bank_regs_create keeps its own bound.  What stays narrow:
+ * fheram_bank_regs_pack holds at most min(2^bits, 32) candidates (fheram_bank_regs_load_plain / _encrypt_sk / _upload fill a whole
+ * row, fheram_bank_regs_poke places single words), and fheram_bank_select / _select_lanes refuse a wide selector. */
+int fheram_bank_regs_create_wide(fheram_bank* bank, int bits, fheram_regs** out);
 void fheram_regs_destroy(fheram_regs* regs);
 int fheram_regs_bits(const fheram_regs* regs);
 /* 1 between read_prepare_write and write */
@@ -672,7 +681,7 @@ int fheram_bank_regs_state(const fheram_bank* bank, const fheram_regs* regs);
  * readable, sets state 0 and voids anything kept — also between read_prepare_write and write, as fheram_bank_ram_upload. */
 int fheram_bank_regs_upload(fheram_bank* bank, fheram_regs* regs, const int64_t* row);
 int fheram_bank_regs_download(fheram_bank* bank, const fheram_regs* regs, int64_t* row);
-/* row_w <- glwe_normalize( sum_{j < n_cand} X^j * source(srcs[j])[w] ), 1 <= n_cand <= 2^bits: exactly the pack of fheram_bank_select
+/* row_w <- glwe_normalize( sum_{j < n_cand} X^j * source(srcs[j])[w] ), 1 <= n_cand <= min(2^bits, 32): exactly the pack of fheram_bank_select
  * (the same kernel, the same source checks) written into the register file; 2^bits ZERO sources give the all-zero register file with no
  * host encryption.  HOST slots are [0, 2^FHERAM_SELECT_BITS_MAX) of host_words, range-checked (FHERAM_ERR_RANGE).  Sets state 0; needs
  * no keys.  No host wait beyond the previous call's copy out of the pinned staging buffer. */
@@ -712,8 +721,8 @@ int fheram_bank_regs_write(fheram_bank* bank, fheram_regs* regs, const fheram_se
  * more than FHERAM_SELECTOR_WIDE_DIGITS_MAX digits.  fheram_bank_selector_derive, _derive_fields, fheram_bank_derive_list (SELECTOR and
  * FIELD items), _download, fheram_selector_n_digits and fheram_selector_destroy take a wide selector unchanged, so a fetch index is
  * bits [2, 2 + bits) of the pc in the derive list's one launch.  fheram_bank_select and fheram_bank_select_lanes refuse a selector of
- * more than FHERAM_SELECT_BITS_MAX bits (FHERAM_ERR_INVALID_ARG: their pack holds 32 candidates); a register file refuses it by its
- * bits rule.
+ * more than FHERAM_SELECT_BITS_MAX bits (FHERAM_ERR_INVALID_ARG: their pack holds 32 candidates); a register file takes it by its
+ * bits rule (a wide one: fheram_bank_regs_create_wide).
  * No member's rows, state flag, tree, result or kept memo changes, no register file's row or state; the last read list's, select's
  * and register read's results stay readable.  Every check runs before anything is enqueued and a refused call changes nothing.
  * FHERAM_ERR_INVALID_ARG: null arguments, a table or selector of another bank, an empty selector, a selector whose bits are not the
@@ -815,6 +824,15 @@ int fheram_bank_peek_result(fheram_bank* bank, int first, int n, int64_t* out);
  * HOST source with host_words == NULL; FHERAM_ERR_STATE: a source kind whose operation has not run, a MEMBER_RESULT member without a
  * result; FHERAM_ERR_RANGE: a host limb out of range. */
 int fheram_bank_poke(fheram_bank* bank, const int* members, const uint64_t* addrs, int n, const fheram_select_src* srcs, const int64_t* host_words);
+/* The register file's twins, narrow or wide: entry k is word idx[k] < 2^bits of the one row, which is address idx[k] of the one-row RAM
+ * (row 0, coefficient idx[k]).  The same launches as above — one k_peek_gather, one trace over the n * word_size ciphertexts, and for
+ * a poke one k_poke_merge on the one row — the same limits (FHERAM_PEEK_MAX entries, n * word_size <= 64, distinct targets of a poke),
+ * the same source rules and host slots, and the same outputs: the bank's "last peek" (fheram_bank_peek_result,
+ * FHERAM_SRC_PEEK_RESULT).  Both need keys, an initialised row (FHERAM_ERR_UNINITIALIZED) and state 0 (FHERAM_ERR_STATE: between
+ * read_prepare_write and write the row is rotated).  A peek changes nothing else; a poke voids what the register file kept for a write.
+ * FHERAM_ERR_INVALID_ARG: null pointers, a register file of another bank, n out of range, an index >= 2^bits, a target named twice. */
+int fheram_bank_regs_peek(fheram_bank* bank, const fheram_regs* regs, const uint32_t* idx, int n, int64_t* out /* [n][word_size][GLWE] or NULL */);
+int fheram_bank_regs_poke(fheram_bank* bank, fheram_regs* regs, const uint32_t* idx, int n, const fheram_select_src* srcs, const int64_t* host_words);
 /* Self-test of the public side's FHERAM_ERR_DEVICE path, as fheram_bank_selftest_fail_select_alloc: the nth device allocation its
  * buffers ask for from now on fails once (0 withdraws the request). */
 int fheram_bank_selftest_fail_public_alloc(fheram_bank* bank, int nth);

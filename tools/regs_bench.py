@@ -92,10 +92,11 @@ class Worker:
         return out
 
 
-def worker_main():
+def worker_main(w=None):
+    """w: the worker object whose methods the driver calls (tools/scratch_bench.py brings its own)"""
     out = os.fdopen(os.dup(1), "w")   # replies on the original stdout; anything a library prints goes to stderr
     os.dup2(2, 1)
-    w = Worker()
+    w = w or Worker()
     for line in sys.stdin:
         cmd = json.loads(line)
         try:
@@ -109,13 +110,14 @@ def worker_main():
 
 
 class Remote:
-    def __init__(self, lib):
+    def __init__(self, lib, script=None):
+        """script: the tool whose --worker the process runs (this one unless given)"""
         env = dict(os.environ)
         if lib:
             env["FHERAM_LIB"] = os.path.abspath(lib)
         else:
             env.pop("FHERAM_LIB", None)
-        self.p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker"], stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True, env=env, cwd=ROOT)
+        self.p = subprocess.Popen([sys.executable, os.path.abspath(script or __file__), "--worker"], stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True, env=env, cwd=ROOT)
 
     def call(self, op, **kw):
         self.p.stdin.write(json.dumps(dict(op=op, **kw)) + "\n")
